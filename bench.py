@@ -10,8 +10,17 @@ ranks (strong scaling: J is fixed); the step has no collective.
 
 Rank 0 prints ONE JSON line.  `value` is the like-for-like path: the same 4*N*M*J flop per step the reference
 performs (F = A^T U, d cost/d f, A G), i.e. the kernel that also serves the Poisson / Bernoulli / Student-t costs.
-The Gaussian/identity algebraic shortcut (B = A A^T precomputed, 2*M^2*J flop per step; README.md:9's O(M^3 + J M^2))
-is measured in the same run and reported under "gaussian_fast_path" -- never mixed into `value`.
+
+A plain run sets up, warms up, times the K steps and prints the headline (`value`, `ms_per_step`).  `--full` adds
+everything else in the same run: the roofline of the step's kernels (a library timeline around every launch of the
+timed steps), the k(Z,X) build on the HBM roofline, sustained windows, the Gaussian/identity algebraic shortcut
+(B = A A^T precomputed, 2*M^2*J flop per step; README.md:9's O(M^3 + J M^2)) under "gaussian_fast_path" -- never
+mixed into `value` --, train_pls to a converged energy, the inducing-point basis, the multi-rank shard check, the
+reference's profiler protocol and experiment sizes, and the CPU baseline.
+
+`--dump-outputs DIR` writes the particles the last timed step returned to DIR/particles.npy (float64; a fixed,
+seeded sample of the columns when the whole matrix would exceed 32 MiB).  Inputs, initial particles and the noise
+stream are seeded, so two runs with the same arguments compute on identical inputs.
 """
 from __future__ import annotations
 
@@ -358,6 +367,33 @@ def reference_scale_block(pkg, iterations: int):
                         "experiments/profiler/config.yaml; median of 3 runs"}
 
 
+DUMP_CAP_BYTES = 32 << 20  # --dump-outputs writes at most this many bytes of particles
+
+
+def dump_outputs(out_dir: str, particles: torch.Tensor, j_total: int):
+    """`--dump-outputs DIR`: the (M_k, J) particles the last timed step returned, as DIR/particles.npy in float64.  A matrix
+    larger than DUMP_CAP_BYTES keeps a fixed sample of its columns (torch.randperm with seed 0, in ascending order): the same
+    columns for every build and GPU count.  A J-sharded run gathers the shards first and rank 0 writes."""
+    import numpy as np
+    import torch.distributed as dist
+
+    from projected_langevin_sampling_amd import distributed as D
+
+    if dist.is_initialized() and dist.get_world_size() > 1:
+        on_host = "nccl" not in str(dist.get_backend()).lower()  # (gloo gathers host tensors)
+        particles = D.gather_particles(particles.cpu() if on_host else particles, j_total)
+        if dist.get_rank() != 0:
+            return
+    mk, j = particles.shape
+    keep = max(1, min(j, DUMP_CAP_BYTES // (8 * mk)))
+    if keep < j:
+        cols = torch.randperm(j, generator=torch.Generator().manual_seed(0))[:keep].sort().values
+        particles = particles[:, cols.to(particles.device)]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "particles.npy"), particles.to(torch.float64).cpu().numpy())
+    log(f"dumped particles {tuple(particles.shape)} of ({mk}, {j}) to {out_dir}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -366,6 +402,13 @@ def main():
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS) + ["profiler-grid"],
                     help="c2 = configs[1] of BASELINE.json (the headline); profiler-grid = the reference's own timing protocol "
                          "(experiments/profiler/config.yaml) through tools/profiler_grid.py, GPU beside the CPU oracle")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run every other measurement and check of the line (roofline, sustained, "
+                         "fast path, train_pls, inducing-point basis, shard check, profiler protocol, reference sizes, CPU "
+                         "baseline); the options below that tune those sections apply with --full only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the particles the last timed step returned to DIR/particles.npy (float64; a fixed, seeded "
+                         "sample of the columns when the whole matrix exceeds 32 MiB)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--workspace-gb", type=float, default=8.0, help="cap of the per-step G-chunk workspace")
     ap.add_argument("--converge-steps", type=int, default=4000,
@@ -386,6 +429,8 @@ def main():
                     help="development aid: run rank 0's particle shard of an N-GPU job on ONE GPU (no collectives); "
                          "the JSON line is marked emulated and is not a scaling result")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.config == "profiler-grid":
         return profiler_grid_line(args)
     cfg = CONFIGS[args.config]
@@ -485,7 +530,7 @@ def main():
     # ---- the kernel build k(Z, X) on the roofline (north_star: "achieved HBM GB/s on the kernel build"): the launch of the
     # setup again, five times, each bracketed by HIP events on the launch stream (the library timeline) ----
     gram_roofline = None
-    if rank == 0:
+    if args.full and rank == 0:
         gx, gz = x.cuda(), z.cuda()
         kernel.base_kernel(x1=gz, x2=gx)  # warm-up (allocation of the 8 N M bytes)
         torch.cuda.synchronize()
@@ -563,71 +608,76 @@ def main():
         return dt, (tl.summary() if tl else {})
 
     n, m = cfg["n"], mk
-    # ---- like-for-like path (headline) ----
-    dt, tl = run(force_generic=True, steps=args.steps, warmup=args.warmup, timeline=True)
+    # ---- like-for-like path (headline); --full brackets every launch of it with the library timeline (HIP event pairs) for
+    # the roofline below ----
+    dt, tl = run(force_generic=True, steps=args.steps, warmup=args.warmup, timeline=args.full)
     ms_per_step = dt / args.steps * 1e3
     value = args.steps / dt
     headline_rank_ms = [d / args.steps * 1e3 for d in rank_dt]
     log(f"like-for-like path: {ms_per_step:.2f} ms/step")
-    # dominant kernels of the step: the two GEMM launches, or (rank <= 128) the one fused small-rank launch
-    dom = ("small_rank_drift",) if "small_rank_drift" in tl else ("gemm_cost_deriv", "gemm_store")
-    gemm_ms = sum(tl[k]["total_ms"] for k in dom if k in tl)
-    gemm_launches = sum(tl[k]["launches"] for k in dom if k in tl)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, ping, j_total)
     flop_per_step_rank = 4.0 * n * m * j_loc
-    achieved = flop_per_step_rank * args.steps / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0
-    # HBM bytes per launch of the same two kernels on the same workload come from separate rocprofv3 --pmc passes
-    # (FETCH_SIZE doubled, WRITE_SIZE as is: MI355X_MICROARCH.md "HBM"; tools/profile_bench.sh + tools/summarize_prof.py).
-    # A counter pass cannot run inside this process, so the committed summary is used ONLY when it was collected from
-    # exactly the kernel sources of this tree (tools/source_hash.py stamp); otherwise traffic stays null.
-    traffic, traffic_src = None, None
-    if args.config == "c2" and world == 1 and shard_world == 1:
-        import glob
+    roofline = None
+    if args.full:
+        # dominant kernels of the step: the two GEMM launches, or (rank <= 128) the one fused small-rank launch
+        dom = ("small_rank_drift",) if "small_rank_drift" in tl else ("gemm_cost_deriv", "gemm_store")
+        gemm_ms = sum(tl[k]["total_ms"] for k in dom if k in tl)
+        gemm_launches = sum(tl[k]["launches"] for k in dom if k in tl)
+        achieved = flop_per_step_rank * args.steps / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0
+        # HBM bytes per launch of the same two kernels on the same workload come from separate rocprofv3 --pmc passes
+        # (FETCH_SIZE doubled, WRITE_SIZE as is, the MI355X's HBM byte accounting; tools/profile_bench.sh + tools/summarize_prof.py).
+        # A counter pass cannot run inside this process, so the committed summary is used ONLY when it was collected from
+        # exactly the kernel sources of this tree (tools/source_hash.py stamp); otherwise traffic stays null.
+        traffic, traffic_src = None, None
+        if args.config == "c2" and world == 1 and shard_world == 1:
+            import glob
 
-        from tools.source_hash import kernel_source_hash
+            from tools.source_hash import kernel_source_hash
 
-        here = kernel_source_hash()
-        traffic_src = "no PMC summary under profiles/ was collected from the current kernel sources"
-        # (rNN_pmc_summary.json only: that name is the configs[1] workload on one GPU; other configs and shard runs carry a tag)
-        import re
+            here = kernel_source_hash()
+            traffic_src = "no PMC summary under profiles/ was collected from the current kernel sources"
+            # (rNN_pmc_summary.json only: that name is the configs[1] workload on one GPU; other configs and shard runs carry a tag)
+            import re
 
-        for prof in sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_pmc_summary.json")), reverse=True):
-            if not re.fullmatch(r"r\d+_pmc_summary\.json", os.path.basename(prof)):
-                continue
-            pm = json.load(open(prof))
-            if pm.get("_kernel_source_hash") != here:
-                continue
-            ks = [pm.get("gemm_tn_f64<128x128>::EpiGaussDeriv", pm.get("gemm_tn_f64<128x128>::EpiCostDeriv", {})),
-                  pm.get("gemm_tn_f64<128x128>::EpiStore", {})]
-            if all("hbm_bytes_per_launch" in k for k in ks):
-                traffic = sum(k["hbm_bytes_per_launch"] for k in ks) / len(ks)
-                traffic_src = f"profiles/{os.path.basename(prof)} (kernel sources {here[:12]})"
-                break
-    step_tflops = flop_per_step_rank / (ms_per_step * 1e-3) / 1e12  # whole step: every launch and every gap of the timed region
-    roofline = {
-        "kernel": ("small_rank_kernel<KB,drift> (F, d cost/d f and back-projection fused; N x J intermediates never written)"
-                   if dom[0] == "small_rank_drift" else
-                   "gemm_tn_f64_kernel<128,128,64,64,16,*> (cost-derivative + back-projection launches of the step)"),
-        "bound": "mfma",
-        "achieved": achieved,
-        "peak": FP64_MFMA_PEAK_TFLOPS,
-        "unit": "TFLOP/s",
-        "frac": achieved / FP64_MFMA_PEAK_TFLOPS,
-        "frac_note": "algorithmic flop of the step's dominant launches / their summed durations (HIP events around every launch)",
-        "step_achieved": step_tflops,
-        "step_frac": step_tflops / FP64_MFMA_PEAK_TFLOPS,
-        "step_frac_note": "the same flop / ms_per_step: update kernel, launch gaps and host overhead of the timed region included",
-        "algorithmic_bytes_per_step": 8.0 * (n * m + 2 * m * j_loc),
-        "algorithmic_bytes_note": "SURVEY 8(d): A once, U in, U out; the two-GEMM path below also writes and re-reads G",
-        "traffic": traffic,
-        "traffic_unit": "bytes per launch (fabric-side L2 misses incl. Infinity-Cache hits)",
-        "traffic_source": traffic_src,
-        "algorithmic_bytes_per_launch": (8.0 * (n * m + 2 * m * j_loc) if dom[0] == "small_rank_drift"
-                                         else 8.0 * (n * m + m * j_loc + 2 * n * j_loc) / 2.0),
-        "flop_per_launch": flop_per_step_rank / max(gemm_launches / args.steps, 1),
-        "avg_launch_ms": gemm_ms / max(gemm_launches, 1),
-        "launches_per_step": gemm_launches / args.steps,
-        "per_kernel_ms": {k: round(v["avg_ms"], 4) for k, v in tl.items()},
-    }
+            for prof in sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_pmc_summary.json")), reverse=True):
+                if not re.fullmatch(r"r\d+_pmc_summary\.json", os.path.basename(prof)):
+                    continue
+                pm = json.load(open(prof))
+                if pm.get("_kernel_source_hash") != here:
+                    continue
+                ks = [pm.get("gemm_tn_f64<128x128>::EpiGaussDeriv", pm.get("gemm_tn_f64<128x128>::EpiCostDeriv", {})),
+                      pm.get("gemm_tn_f64<128x128>::EpiStore", {})]
+                if all("hbm_bytes_per_launch" in k for k in ks):
+                    traffic = sum(k["hbm_bytes_per_launch"] for k in ks) / len(ks)
+                    traffic_src = f"profiles/{os.path.basename(prof)} (kernel sources {here[:12]})"
+                    break
+        step_tflops = flop_per_step_rank / (ms_per_step * 1e-3) / 1e12  # whole step: every launch and every gap of the timed region
+        roofline = {
+            "kernel": ("small_rank_kernel<KB,drift> (F, d cost/d f and back-projection fused; N x J intermediates never written)"
+                       if dom[0] == "small_rank_drift" else
+                       "gemm_tn_f64_kernel<128,128,64,64,16,*> (cost-derivative + back-projection launches of the step)"),
+            "bound": "mfma",
+            "achieved": achieved,
+            "peak": FP64_MFMA_PEAK_TFLOPS,
+            "unit": "TFLOP/s",
+            "frac": achieved / FP64_MFMA_PEAK_TFLOPS,
+            "frac_note": "algorithmic flop of the step's dominant launches / their summed durations (HIP events around every launch)",
+            "step_achieved": step_tflops,
+            "step_frac": step_tflops / FP64_MFMA_PEAK_TFLOPS,
+            "step_frac_note": "the same flop / ms_per_step: update kernel, launch gaps and host overhead of the timed region included",
+            "algorithmic_bytes_per_step": 8.0 * (n * m + 2 * m * j_loc),
+            "algorithmic_bytes_note": "SURVEY 8(d): A once, U in, U out; the two-GEMM path below also writes and re-reads G",
+            "traffic": traffic,
+            "traffic_unit": "bytes per launch (fabric-side L2 misses incl. Infinity-Cache hits)",
+            "traffic_source": traffic_src,
+            "algorithmic_bytes_per_launch": (8.0 * (n * m + 2 * m * j_loc) if dom[0] == "small_rank_drift"
+                                             else 8.0 * (n * m + m * j_loc + 2 * n * j_loc) / 2.0),
+            "flop_per_launch": flop_per_step_rank / max(gemm_launches / args.steps, 1),
+            "avg_launch_ms": gemm_ms / max(gemm_launches, 1),
+            "launches_per_step": gemm_launches / args.steps,
+            "per_kernel_ms": {k: round(v["avg_ms"], 4) for k, v in tl.items()},
+        }
     out = {
         "metric": "Langevin steps/sec",
         "value": value,
@@ -646,8 +696,9 @@ def main():
                    "path": "like-for-like: F=A^T U -> d cost/d f -> A G, 4*N*M*J flop/step", "step_size": eta,
                    "parallelism": f"J-sharded x{world}, no per-step collective", "setup_s": round(t_setup, 2),
                    "setup_breakdown": setup},
-        "roofline": roofline,
     }
+    if roofline is not None:
+        out["roofline"] = roofline
     if dist.is_initialized():
         # who ran: the process group as the ranks see it, and every rank's own clock over the headline region (`ms_per_step` is
         # the slowest rank's)
@@ -663,7 +714,7 @@ def main():
     if gram_roofline is not None:
         out["roofline_gram"] = gram_roofline
     # ---- sustained: the same like-for-like step for >= 10 s, in windows of 50 steps (does the clock hold?) ----
-    if args.sustained_steps >= 50:
+    if args.full and args.sustained_steps >= 50:
         # 50-step windows at configs[1] (300 steps = 13.4 s); a configuration whose step takes seconds (configs[4]: 1.8 s) gets
         # the same six windows over ~20 s instead of 300 steps = 9 minutes
         nwin = max(args.sustained_steps // 50, 1)
@@ -685,7 +736,7 @@ def main():
         }
         log(f"sustained: {nwin * win} steps, {out['sustained']['ms_per_step']:.2f} ms/step, windows {windows[0]:.2f} .. {windows[-1]:.2f}")
     # ---- Gaussian algebraic fast path, same run ----
-    if cfg["cost"] == "gaussian":
+    if args.full and cfg["cost"] == "gaussian":
         fsteps = max(args.steps * 10, 50)
         # every section starts from a settled chip, like the headline run does after the setup: after the 45 ms-per-step
         # phase above (0.6 s of sustained full-rate MFMA) the power controller holds the clock lower for SECONDS -- these
@@ -761,7 +812,7 @@ def main():
         out["gaussian_fast_path"]["hipgraph_steps_per_s"] = reps * gsteps / dtg
         del run_g
     # ---- wall-clock to converged energy: the reference's train_pls loop (step, energy, early stop) ----
-    if cfg["cost"] == "gaussian" and args.converge_steps > 0:
+    if args.full and cfg["cost"] == "gaussian" and args.converge_steps > 0:
         from projected_langevin_sampling_amd.trainers import train_pls
 
         eta_c = 1.0 / rho_max
@@ -814,7 +865,7 @@ def main():
             log(f"train_pls_captured: {len(energies_c)} steps in {wall_c:.3f} s")
     # ---- train_pls iteration cost for the other costs: step + energy, pipelined (energy as a by-product of the step's
     # own F) against the plain loop (step, then a separate energy pass as the reference does) ----
-    if cfg["cost"] != "gaussian" and args.converge_steps > 0:
+    if args.full and cfg["cost"] != "gaussian" and args.converge_steps > 0:
         from projected_langevin_sampling_amd.trainers import train_pls
         iters = min(args.converge_steps, 20)
         res = {}
@@ -844,7 +895,7 @@ def main():
         }
         log(f"train_pls iteration: pipelined {res['pipelined'][0]:.3f} ms, plain {res['plain'][0]:.3f} ms")
     # ---- setup extra: greedy conditional-variance inducing-point selection at this N, M ----
-    if rank == 0 and args.select_inducing:
+    if args.full and rank == 0 and args.select_inducing:
         import numpy as np
         from projected_langevin_sampling_amd.inducing_point_selectors import ConditionalVarianceInducingPointSelector
 
@@ -864,7 +915,7 @@ def main():
         }
         log(f"inducing-point selection: {t_sel:.3f} s")
     # ---- inducing-point basis: same data, same cost, one rank's shard ----
-    if args.ipb_steps > 0:
+    if args.full and args.ipb_steps > 0:
         from projected_langevin_sampling_amd.basis import InducingPointBasis
 
         t_ipb = time.perf_counter()
@@ -963,7 +1014,7 @@ def main():
     # steps (library noise keyed by the GLOBAL column); the shards are gathered and rank 0 recomputes every shard on its own
     # GPU -- the same column block, the same column offset, hence the same kernels: bit for bit or the line says so -- and the
     # whole matrix unsharded (other tile shapes for a wider matrix: equal to rounding) ----
-    if dist.is_initialized() or shard_world > 1:
+    if args.full and (dist.is_initialized() or shard_world > 1):
         t_chk = time.perf_counter()
         seed_chk = 97531
         k_fast = 20 if cfg["cost"] == "gaussian" else 0
@@ -1033,7 +1084,7 @@ def main():
     # ---- the reference's profiler protocol (experiments/profiler/main.py:41-82, :141-169): construction of kernel, basis,
     # cost and PLS, particle initialisation and T steps `particles += pls.calculate_particle_update(particles, eta)` timed
     # as ONE block ----
-    if rank == 0 and world == 1 and args.profiler_steps > 0 and shard_world == 1:
+    if args.full and rank == 0 and world == 1 and args.profiler_steps > 0 and shard_world == 1:
         del ping, pong
         torch.cuda.empty_cache()
 
@@ -1074,12 +1125,12 @@ def main():
                         "drop-in API",
         }
         log(f"profiler protocol: construction {t_construct:.2f} s + {args.profiler_steps} steps = {t_block:.2f} s")
-    if rank == 0 and world == 1 and shard_world == 1 and args.reference_scale_iterations > 0:
+    if args.full and rank == 0 and world == 1 and shard_world == 1 and args.reference_scale_iterations > 0:
         out["reference_scale"] = reference_scale_block(pkg, args.reference_scale_iterations)
         log("reference scale: " + "; ".join(f"N={r['n']} M={r['m']} J={r['j']}: onb {r['orthonormal/gaussian_identity']} / {r['orthonormal/bernoulli_sigmoid']}, "
                                             f"ipb {r['inducing_point/gaussian_identity']} / {r['inducing_point/bernoulli_sigmoid']} us" for r in out["reference_scale"]["rows"]))
     # ---- CPU baseline (rank 0, N=1 only) ----
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         lam_all, vec_all = basis.eigenvalues.cpu(), basis.eigenvectors.cpu()
         out["cpu_baseline"] = cpu_baseline(cfg, x, z, y, ls, lam_all, vec_all)
         out["gpu_over_cpu"] = value / out["cpu_baseline"]["value"]

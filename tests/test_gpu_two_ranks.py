@@ -232,16 +232,18 @@ def test_bench_line_of_two_ranks_checks_its_own_shards(tmp_path):
     """`PLS_BENCH_BACKEND=gloo python bench.py --gpus 2` on the one card of this box (the control flow of the driver's
     multi-GPU run, RCCL replaced by gloo): the JSON line carries the process group as the ranks saw it, every rank's own
     clock, and a shard check -- the ranks' gathered particles are, bit for bit, what rank 0 computes for the same columns
-    (distributed.py:1-7), energies included."""
+    (distributed.py:1-7), energies included.  `--dump-outputs` gathers the shards: the same columns as a one-GPU run of the
+    same arguments, equal to rounding (wider tiles)."""
     import json
     import subprocess
     import sys
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, PLS_BENCH_BACKEND="gloo")
-    run = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
+    run = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full",
                           "--no-cpu-baseline", "--sustained-steps", "0", "--profiler-steps", "0", "--ipb-steps", "0",
-                          "--converge-steps", "0"], env=env, capture_output=True, text=True, timeout=600, cwd=root)
+                          "--converge-steps", "0", "--dump-outputs", str(tmp_path / "two")], env=env, capture_output=True, text=True,
+                         timeout=600, cwd=root)
     assert run.returncode == 0, run.stderr[-3000:]
     line = json.loads(run.stdout.strip().splitlines()[-1])
     assert line["n_gpus"] == 2 and line["backend"] == "gloo"
@@ -255,3 +257,11 @@ def test_bench_line_of_two_ranks_checks_its_own_shards(tmp_path):
     assert chk["steps"]["gaussian_fast_path"] == 20 and chk["steps"]["like_for_like"] >= 2
     assert chk["max_rel_diff_vs_one_unsharded_matrix"] < 1e-12
     assert abs(chk["mean_energy_all_reduce"] - chk["mean_energy_rank0_recomputed"]) <= 1e-12 * abs(chk["mean_energy_rank0_recomputed"])
+    one = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                          "--dump-outputs", str(tmp_path / "one")], capture_output=True, text=True, timeout=600, cwd=root)
+    assert one.returncode == 0, one.stderr[-3000:]
+    import numpy as np
+
+    u2, u1 = np.load(tmp_path / "two" / "particles.npy"), np.load(tmp_path / "one" / "particles.npy")
+    assert u2.shape == u1.shape and u2.shape[1] < 8192  # (the 64 MiB matrix is dumped as a column sample)
+    assert np.abs(u2 - u1).max() < 1e-12 * np.abs(u1).max()

@@ -244,6 +244,25 @@ def test_bench_self_launches_its_ranks(monkeypatch):
     assert seen["env"]["HSA_ENABLE_IPC_MODE_LEGACY"] == "0"
 
 
+def test_bench_dump_outputs_keeps_a_fixed_column_sample_under_the_cap(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs DIR` writes the particles of the last timed step as float64 .npy: whole when they fit under
+    bench.DUMP_CAP_BYTES, otherwise the same seeded sample of columns every time (so two builds compare output for output)."""
+    import bench
+
+    u = torch.arange(6 * 40, dtype=torch.float64).reshape(6, 40)
+    bench.dump_outputs(str(tmp_path / "whole"), u, 40)
+    got = np.load(tmp_path / "whole" / "particles.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, u.numpy())
+    monkeypatch.setattr(bench, "DUMP_CAP_BYTES", 8 * 6 * 10)  # room for 10 of the 40 columns
+    bench.dump_outputs(str(tmp_path / "a"), u, 40)
+    bench.dump_outputs(str(tmp_path / "b"), u.float(), 40)
+    a, b = np.load(tmp_path / "a" / "particles.npy"), np.load(tmp_path / "b" / "particles.npy")
+    assert a.shape == (6, 10) and a.dtype == np.float64 and a.nbytes <= bench.DUMP_CAP_BYTES
+    assert np.array_equal(a, b)
+    cols = a[0].astype(np.int64)  # row 0 of u holds the column indices
+    assert np.all(np.diff(cols) > 0) and np.array_equal(a, u.numpy()[:, cols])
+
+
 def test_whitened_route_and_inverse_factor_products_are_as_accurate_as_substitution():
     """Numerics behind round 3's inducing-point Gaussian step, in plain torch on the host.
     With ONE Cholesky factor of k(Z,Z) (cond 2e10 here) the whitened route  Lc (Q S - c~),  Q = Lc^-1 (B / sigma2 + M I) Lc^-T,
