@@ -70,7 +70,7 @@ class BlockSpec:
         #: LAGGED energies (pls_block_desc.energy_partials ...): this launch leaves its partial rows in ``energy_partials``
         #: and finishes the previous launch's (``energy_partials_prev``) into ``energy_prev`` (J device doubles) and, optionally,
         #: ``energy_sums_prev`` (raw address of cdiv(J, 256) doubles, device or pinned host memory); ``energy_flush``: no
-        #: step, only that finish (BasisWithFlush.flush_energies)
+        #: step, only that finish (OrthonormalBasis.flush_energies, BoundStep.flush)
         for t in (energy_partials, energy_partials_prev, energy_prev):
             if t is not None:
                 L.require_gpu_tensor(t, "energy buffer")
@@ -99,6 +99,149 @@ class BlockSpec:
         d.step_sync = None if self.step_sync is None else self.step_sync.data_ptr()
         d.energy_sums16 = self.energy_sums16
         return d
+
+
+class StepRoute:
+    """A basis' answer to "how does one step of this cost over ``j`` particle columns run" (PLSBasis._route): the C entry --
+    ``entry`` takes the step size as a double, ``blocks_entry`` a pls_block_desc (after ``blocks_head``) --, the arguments
+    in front of the particles (the descriptor, Gaussian constants prepared, the cost descriptor and the targets) and behind
+    the output mode, the workspace bytes it asks for, and whether it is the one-launch small-rank step, which meets through
+    zeroed arrival counters (pls_block_desc.step_sync).  ``holds``: what the descriptor points into.  ``sums`` / ``lagged``:
+    the step can leave the 256-column chunk sums of its energy by-product / finish them one launch later."""
+
+    __slots__ = ("entry", "blocks_entry", "fn", "fn_blocks", "head", "tail", "blocks_head", "ws_bytes", "ws_for_energy_only",
+                 "holds", "one_launch", "sums", "lagged")
+
+    def __init__(self, entry, blocks_entry, head, tail, ws_bytes, holds, one_launch=False, sums=False, lagged=False,
+                 ws_for_energy_only=False, blocks_head=()):
+        lib = L.load()
+        self.entry, self.blocks_entry = entry, blocks_entry
+        self.fn = None if entry is None else getattr(lib, entry)
+        self.fn_blocks = getattr(lib, blocks_entry)
+        self.head, self.tail, self.blocks_head = head, tail, blocks_head
+        self.ws_bytes, self.ws_for_energy_only, self.holds = int(ws_bytes), ws_for_energy_only, holds
+        self.one_launch, self.sums, self.lagged = one_launch, sums, lagged
+
+    def workspace_bytes(self, with_energy: bool) -> int:
+        return 0 if self.ws_for_energy_only and not with_energy else self.ws_bytes
+
+    def call(self, bd, u_ptr, ldu, j, step_size, nd, out_ptr, ldo, mode, energy_ptr, ws_ptr, ws_bytes, stream) -> int:
+        mid = (step_size,) if bd is None else (*self.blocks_head, bd)
+        fn = self.fn if bd is None else self.fn_blocks
+        return fn(*self.head, u_ptr, ldu, j, *mid, nd, out_ptr, ldo, mode, *self.tail, energy_ptr, ws_ptr, ws_bytes, stream)
+
+
+class BoundStep:
+    """One step call bound once for a loop that makes it thousands of times (PLSBasis._bind_step): at the reference's own
+    problem sizes a step is a 5-10 us kernel, and building the call afresh (descriptors, workspace, counters: ~10-20 us of
+    Python) is what an iteration would cost.  The object OWNS every tensor whose address sits in its descriptors -- the
+    workspace, the step-size word, the arrival counters, the lagged partial rows, and (``route.holds``) the basis constants --,
+    so nothing it launches with can be freed or replaced under it.
+
+    ``form`` -- what a launch does with the energies of its input particles:
+      "none"    no energies (the drop-in step);
+      "lagged"  leaves their partial rows; the NEXT launch finishes them into its ``energy`` / ``slot`` (reports_previous)
+                at its start, under the landing of its first operand rows -- the reduction's serial tail (4-5 us) leaves the
+                critical path; the last launch's rows take a small launch of their own (flush);
+      "sums"    the 256-column chunk sums into ``slot``, finished by the step launch itself (pls_block_desc.energy_sync:
+                ONE launch per iteration, no separate finishing or mean launch);
+      "sums16"  the 16-column sums into ``slot`` (the one-launch small-rank step);
+      "means"   the per-particle energies into ``energy``, then their mean into ``slot`` (pls_block_means).
+    A launch: bound.launch(u_ptr, ldu, out_ptr, ldo, noise, energy_ptr, slot_ptr), ``noise`` the Philox key, or the (M, J)
+    device noise matrix when bound with ``injected``; ``slot``: ``slot_doubles`` doubles, device or pinned host memory.
+    (``launch`` is a closure over what it needs: at these sizes an attribute lookup per argument is a measurable share.)"""
+
+    def __init__(self, basis, route: StepRoute, state: torch.Tensor, step_size: float, form: str, injected: bool = False,
+                 new_state: bool = True):
+        assert form in ("none", "lagged", "sums", "sums16", "means")
+        lib, dev = L.load(), state.device
+        j = self.j = state.shape[1]
+        self.route, self.form, self.injected, self.step_size = route, form, bool(injected), float(step_size)
+        self.reports_previous = form == "lagged"
+        self.slot_doubles = (0 if form == "none" else 1 if form == "means" else (j + 15) // 16 if form == "sums16"
+                             else (j + 255) // 256)
+        ws_bytes = route.workspace_bytes(form not in ("none", "lagged"))
+        self.workspace = torch.empty((ws_bytes + 7) // 8, dtype=torch.float64, device=dev) if ws_bytes else None
+        self.eta = step_sync = energy_sync = bd = None
+        self.partials = part = ()
+        if form != "means" and (form != "none" or route.one_launch):
+            self.eta = torch.full((1,), self.step_size, dtype=torch.float64, device=dev)
+            bd = L.BlockDesc()
+            bd.block_cols, bd.eta = j, self.eta.data_ptr()
+            if route.one_launch:
+                step_sync = torch.zeros(max(int(lib.pls_step_sync_words(j)), 1), dtype=torch.int32, device=dev)
+                bd.step_sync = step_sync.data_ptr()
+            if form == "sums":
+                energy_sync = torch.zeros(self.slot_doubles, dtype=torch.int32, device=dev)
+                bd.energy_sync = energy_sync.data_ptr()
+            if form == "lagged":
+                pbytes = basis.energy_partial_rows_bytes(j)
+                self.partials = tuple(torch.empty((pbytes + 7) // 8, dtype=torch.float64, device=dev) for _ in range(2))
+                part = tuple(p.data_ptr() for p in self.partials)
+        self.blocks, self.step_sync, self.energy_sync, self._part_ptr = bd, step_sync, energy_sync, part
+        nd = L.NoiseDesc()
+        if injected:
+            nd.kind = L.NOISE_INJECTED
+        else:
+            nd.kind, nd.step, nd.j_offset = L.NOISE_PHILOX, 0, int(basis.j_offset)
+        fn = route.fn if bd is None else route.fn_blocks
+        mid = (self.step_size,) if bd is None else (*route.blocks_head, bd)
+        mode = L.OUT_NEW_STATE if new_state else L.OUT_DELTA
+        ws_ptr, stream, means = L.ptr(self.workspace), L.stream_ptr(), lib.pls_block_means
+        # the C entry's argument list, built once: a launch stores its particle, output and energy addresses into it
+        args = [*route.head, None, None, j, *mid, nd, None, None, mode, *route.tail, None, ws_ptr, ws_bytes, stream]
+        iu = len(route.head)
+        io = iu + 4 + len(mid)
+        ie = io + 3 + len(route.tail)
+        launches = self._launches = [0]  # (lagged: which partial-row buffer a launch leaves its rows in)
+        entry = route.entry if bd is None else route.blocks_entry
+        self._stream, self.workspace_ptr = stream, ws_ptr
+
+        def failed(rc: int) -> None:
+            # stale arrival counters would make every later launch wrong: zero them before the error goes up
+            for t in (step_sync, energy_sync):
+                if t is not None:
+                    t.zero_()
+            L.check(rc, entry)
+
+        def launch(u_ptr, ldu, out_ptr, ldo, noise, energy_ptr=None, slot_ptr=None):
+            if injected:
+                xi = L.require_gpu_tensor(noise, "noise", promote=True)
+                nd.xi, nd.ldxi = xi.data_ptr(), L.ld(xi)
+            else:
+                nd.seed = noise
+            if form == "lagged":  # this launch leaves its partial rows, and finishes those of the previous launch (if any)
+                k = launches[0]
+                bd.energy_partials = part[k & 1]
+                bd.energy_partials_prev = None if energy_ptr is None else part[(k - 1) & 1]
+                bd.energy_prev, bd.energy_sums_prev = energy_ptr, slot_ptr
+                launches[0] = k + 1
+                energy_ptr = None
+            elif form == "sums16":
+                bd.energy_sums16 = slot_ptr
+            elif form == "sums":
+                bd.energy_sums = slot_ptr
+            args[iu], args[iu + 1], args[io], args[io + 1], args[ie] = u_ptr, ldu, out_ptr, ldo, energy_ptr
+            rc = fn(*args)
+            if rc == 0 and form == "means":
+                rc = means(energy_ptr, j, j, slot_ptr, stream)
+            if rc:
+                failed(rc)
+
+        self.launch, self._failed = launch, failed
+
+    def flush(self, u_ptr, ldu, energy_ptr, slot_ptr) -> None:
+        """"lagged": finish the partial rows the LAST launch left into ``energy`` / ``slot`` (a small launch of its own, no
+        step); ``u``: the particles that launch was given (shape and strides only)."""
+        bd = L.BlockDesc()
+        bd.block_cols, bd.eta = self.j, self.eta.data_ptr()
+        bd.energy_partials_prev = self._part_ptr[(self._launches[0] - 1) & 1]
+        bd.energy_prev, bd.energy_sums_prev, bd.energy_flush = energy_ptr, slot_ptr, 1
+        nd = L.NoiseDesc()
+        nd.kind = L.NOISE_NONE
+        rc = self.route.call(bd, u_ptr, ldu, self.j, 0.0, nd, None, 0, L.OUT_DELTA, None, None, 0, self._stream)
+        if rc:
+            self._failed(rc)
 
 
 class PLSBasis(ABC):
@@ -160,7 +303,6 @@ class PLSBasis(ABC):
     def zero_step_sync(self) -> None:
         """Forget every counter set (after a failed or aborted launch): the next step allocates zeroed ones."""
         self.__dict__.pop("_sync_pool", None)
-        self.__dict__.pop("_eager", None)  # (the eager step binds a counter set)
 
     def _eta_word(self, step_size: float, device) -> torch.Tensor:
         """``step_size`` as a device word (pls_block_desc.eta), remembered per value: an eager caller steps with the same size
@@ -230,6 +372,93 @@ class PLSBasis(ABC):
     # ---- fused native path (used by PLS when the cost is native) -------------------------------------------------
     def supports_fused_step(self) -> bool:
         return False
+
+    #: ranks up to which a cost without the Gaussian algebra takes the small-rank kernels (csrc/small_rank.h, small_rank_step.h)
+    SMALL_RANK_MAX = 128
+
+    @staticmethod
+    def _is_gaussian(cost, force_generic: bool = False, cd=None) -> bool:
+        """The Gaussian cost with the identity link: the step has the closed Gaussian algebra (unless ``force_generic``);
+        ``cd``: the cost's descriptor, if the caller holds it already."""
+        cd = cost.desc() if cd is None else cd
+        return cd.cost == L.COST_GAUSSIAN and cd.link == L.LINK_IDENTITY and not force_generic
+
+    def _one_launch_rank(self, cost) -> bool:
+        return (not self._is_gaussian(cost)) and 1 <= self.approximation_dimension <= self.SMALL_RANK_MAX
+
+    def _route(self, cost, j: int, force_generic: bool = False, whitened: bool = False) -> StepRoute:
+        """How one step of ``cost`` over ``j`` columns runs (StepRoute); ``whitened``: on whitened particles."""
+        raise NotImplementedError
+
+    def step_workspace_bytes(self, cost, j: int, with_energy: bool, force_generic: bool = False) -> int:
+        """Bytes fused_step asks of its workspace for ``j`` columns (graph captures allocate their own buffer)."""
+        return self._route(cost, j, force_generic).workspace_bytes(with_energy)
+
+    def _bind_step(self, cost, state: torch.Tensor, step_size: float, whitened: bool = False, energies: bool = True,
+                   lagged: bool = True, injected: bool = False, new_state: bool = True) -> BoundStep:
+        """The step of ``cost`` on particle buffers shaped like ``state`` as a BoundStep.  With ``energies`` it reports the
+        energies of its input particles in the cheapest form the route has: the 16-column sums of the one-launch step, the
+        lagged chunk sums of the Gaussian fast paths (``lagged``, else finished by the launch itself), or a mean launch."""
+        r = self._route(cost, state.shape[1], whitened=whitened)
+        if not energies:
+            form = "none"
+        elif r.one_launch:
+            form = "sums16"
+        elif r.lagged and lagged:
+            form = "lagged"
+        else:
+            form = "sums" if r.sums else "means"
+        return BoundStep(self, r, state, step_size, form, injected=injected, new_state=new_state)
+
+    def fused_step(self, cost, particles: torch.Tensor, step_size: float, out: torch.Tensor | None = None,
+                   new_state: bool = False, noise: NoiseSpec | None = None, force_generic: bool = False,
+                   input_energy: torch.Tensor | None = None, blocks: BlockSpec | None = None,
+                   workspace: torch.Tensor | None = None) -> torch.Tensor:
+        """One whole Langevin step in libplship (the basis' step entry, see _route): returns dU, or U + dU when new_state.
+        ``input_energy`` (J,) receives the per-particle energy of ``particles`` as a by-product.  ``blocks``: one step size
+        per column block (the _blocks entry; ``step_size`` is then ignored).  ``workspace``: a caller-owned buffer -- a
+        captured hipGraph freezes its address, so captures never use the basis' own growable scratch."""
+        u = _rows_contiguous(L.require_gpu_tensor(particles, "particles", promote=True))
+        return self._step(cost, u, step_size, out, new_state, noise, input_energy, blocks, workspace, force_generic)
+
+    def _step(self, cost, u, step_size, out, new_state, noise, input_energy, blocks, workspace, force_generic=False,
+              whitened=False) -> torch.Tensor:
+        j = u.shape[1]
+        if out is None:
+            out = torch.empty_like(u, memory_format=torch.contiguous_format)
+        else:  # (written as float64 through a raw pointer: a buffer of another dtype or shape must never get this far)
+            L.require_gpu_tensor(out, "out")
+            assert out.shape == u.shape, f"out has shape {tuple(out.shape)}, the particles {tuple(u.shape)}"
+        if j == 0:
+            return out
+        assert out.data_ptr() != u.data_ptr(), "the step's out must not alias its particles"
+        r = self._route(cost, j, force_generic, whitened)
+        ws_bytes = r.workspace_bytes(input_energy is not None)
+        ws = self._pick_workspace(workspace, ws_bytes, u.device) if ws_bytes else None
+        nd = (noise if noise is not None else self._draw_noise_spec(None)).desc()
+        bd = None if blocks is None else blocks.desc()
+        if r.one_launch:
+            # the one-launch small-rank step meets through zeroed counters: the basis' own (per stream) unless the caller's
+            # BlockSpec brings some -- without them the library puts a memset node in front of every launch
+            if bd is None:
+                bd = L.BlockDesc()
+                bd.block_cols, bd.eta = j, self._eta_word(step_size, u.device).data_ptr()
+            if not bd.step_sync:
+                bd.step_sync = self._step_sync(j, u.device).data_ptr()
+        try:
+            L.check(r.call(bd, u.data_ptr(), L.ld(u), j, float(step_size), nd, out.data_ptr(), L.ld(out),
+                           L.OUT_NEW_STATE if new_state else L.OUT_DELTA, L.ptr(input_energy), L.ptr(ws), ws_bytes,
+                           L.stream_ptr()),
+                    r.entry if bd is None else r.blocks_entry)
+        except L.PlsHipError:
+            self.zero_step_sync()
+            raise
+        return out
+
+
+def _rows_contiguous(t: torch.Tensor) -> torch.Tensor:
+    assert t.dim() == 2, "expected a 2-D tensor"
+    return t if t.stride(1) == 1 or t.shape[1] <= 1 and t.is_contiguous() else t.contiguous()
 
 
 def padded_ld(cols: int) -> int:

@@ -8,8 +8,7 @@ from .. import _lib as L
 from .. import _ops
 from ..kernel import PLSKernel, _dev
 from ..samplers import sample_multivariate_normal
-from .base import BlockSpec, NoiseSpec, PLSBasis, alloc_matrix
-from .orthonormal import _rows_contiguous
+from .base import BlockSpec, NoiseSpec, PLSBasis, StepRoute, _rows_contiguous, alloc_matrix
 
 
 class InducingPointBasis(PLSBasis):
@@ -175,47 +174,19 @@ class InducingPointBasis(PLSBasis):
     def whitened_step(self, cost, whitened: torch.Tensor, step_size: float, out: torch.Tensor | None = None,
                       new_state: bool = False, noise: NoiseSpec | None = None, input_energy: torch.Tensor | None = None,
                       blocks: BlockSpec | None = None, workspace: torch.Tensor | None = None) -> torch.Tensor:
-        """One Langevin step of whitened particles (pls_ipb_whitened_step): ONE M x M x J contraction with the update,
-        the noise and -- optionally -- the energy of the input particles in its epilogue.  ``noise`` injected = xi itself
-        (standard normal, not coloured); Philox noise draws the xi of fused_step's e = Lc xi."""
+        """One Langevin step of whitened particles: ONE M x M x J contraction with the update, the noise and -- optionally --
+        the energy of the input particles in its epilogue (pls_ipb_whitened_step); any other cost: the one-launch small-rank
+        step over Awa (pls_ipb_whitened_generic_step, at most 128 points).  ``noise`` injected = xi itself (standard normal,
+        not coloured); Philox noise draws the xi of fused_step's e = Lc xi."""
         s = _rows_contiguous(L.require_gpu_tensor(whitened, "whitened particles"))
-        j = s.shape[1]
-        if out is None:
-            out = torch.empty_like(s, memory_format=torch.contiguous_format)
-        else:  # (written as float64 through a raw pointer: a buffer of another dtype or shape must never get this far)
-            L.require_gpu_tensor(out, "out")
-            assert out.shape == s.shape, f"out has shape {tuple(out.shape)}, the particles {tuple(s.shape)}"
-        if j == 0:
-            return out
-        assert out.data_ptr() != s.data_ptr(), "whitened_step: out must not alias its input"
-        assert self.whitened, "whitened coordinates are switched off on this basis"
-        if not self._is_gaussian(cost, False):  # any other cost: the one-launch small-rank step over Awa (at most 128 points)
-            return self._whitened_generic_step(cost, s, step_size, out, new_state, noise, input_energy, blocks, workspace)
-        self._prepare_for(cost)
-        lib = L.load()
-        desc = self._desc(with_gaussian=True)
-        ws, ws_bytes = None, 0
-        if input_energy is not None:
-            ws_bytes = lib.pls_ipb_whitened_workspace_bytes(desc, j)
-            ws = self._pick_workspace(workspace, ws_bytes, s.device)
-        nd = (noise if noise is not None else self._draw_noise_spec(None)).desc()
-        mode = L.OUT_NEW_STATE if new_state else L.OUT_DELTA
-        if blocks is None:
-            L.check(lib.pls_ipb_whitened_step(desc, cost.desc(), s.data_ptr(), L.ld(s), j, float(step_size), nd, out.data_ptr(),
-                                              L.ld(out), mode, L.ptr(input_energy), L.ptr(ws), ws_bytes, L.stream_ptr()),
-                    "pls_ipb_whitened_step")
-        else:
-            L.check(lib.pls_ipb_whitened_step_blocks(desc, cost.desc(), s.data_ptr(), L.ld(s), j, blocks.desc(), nd,
-                                                     out.data_ptr(), L.ld(out), mode, L.ptr(input_energy), L.ptr(ws), ws_bytes,
-                                                     L.stream_ptr()), "pls_ipb_whitened_step_blocks")
-        return out
+        return self._step(cost, s, step_size, out, new_state, noise, input_energy, blocks, workspace, whitened=True)
 
     # ---- whitened coordinates for the costs WITHOUT the Gaussian algebra (at most 128 inducing points, launch-bound sizes) ----
     def whitened_generic_applies(self, cost, j: int) -> bool:
         """True if a loop over `j` particle columns may keep this cost's particles whitened: every step is then ONE launch
         (pls_ipb_whitened_generic_step: the one-launch small-rank step over k(X,Z) Lc^-T with the prior as rows) instead of the
         solve, the coloured noise and the step.  The operand is built on first use."""
-        if not (self.whitened and cost.is_native()) or self._is_gaussian(cost, False):
+        if not (self.whitened and cost.is_native()) or self._is_gaussian(cost):
             return False
         if not (1 <= self.approximation_dimension <= self.SMALL_RANK_MAX) or self._chol.Linv is None or j <= 0:
             return False
@@ -229,113 +200,23 @@ class InducingPointBasis(PLSBasis):
             self._Awa = awa
         return bool(L.load().pls_ipb_whitened_generic_applies(self._desc(), cost.y_device().data_ptr(), int(j)))
 
-    def _whitened_generic_call(self, cost, j: int, device):
-        lib = L.load()
-        desc = self._desc()
-        ws_bytes = int(lib.pls_ipb_whitened_generic_workspace_bytes(desc, j))
-        return lib, desc, ws_bytes
-
-    def whitened_generic_sums_step_launcher(self, cost, state: torch.Tensor, eta: torch.Tensor):
-        """(see OrthonormalBasis.sums_step_launcher) -- pls_ipb_whitened_generic_step on WHITENED particles, pre-bound"""
-        s = _rows_contiguous(L.require_gpu_tensor(state, "whitened particles"))
-        j = s.shape[1]
-        assert self.whitened_generic_applies(cost, j)
-        lib, desc, ws_bytes = self._whitened_generic_call(cost, j, s.device)
-        cd, y = cost.desc(), cost.y_device()
-        ws = torch.empty((ws_bytes + 7) // 8 + 1, dtype=torch.float64, device=s.device)
-        sync = torch.zeros(max(int(lib.pls_step_sync_words(j)), 1), dtype=torch.int32, device=s.device)
-        blocks, nd = L.BlockDesc(), L.NoiseDesc()
-        blocks.block_cols, blocks.eta = j, L.require_gpu_tensor(eta, "eta").data_ptr()
-        blocks.step_sync = sync.data_ptr()
-        nd.kind, nd.step, nd.j_offset = L.NOISE_PHILOX, 0, int(self.j_offset)
-        fn = lib.pls_ipb_whitened_generic_step
-        y_ptr, ws_ptr, stream, mode = y.data_ptr(), ws.data_ptr(), L.stream_ptr(), L.OUT_NEW_STATE
-
-        def launch(s_ptr, lds, out_ptr, ldo, seed, energy_ptr, sums_ptr):
-            nd.seed = seed
-            blocks.energy_sums16 = sums_ptr
-            rc = fn(desc, cd, y_ptr, s_ptr, lds, j, 0.0, blocks, nd, out_ptr, ldo, mode, energy_ptr, ws_ptr, ws_bytes, stream)
-            if rc:
-                L.check(rc, "pls_ipb_whitened_generic_step")
-
-        launch.keep_alive = (desc, cd, y, ws, sync, eta, self)
-        return launch
-
-    def _whitened_generic_step(self, cost, s, step_size, out, new_state, noise, input_energy, blocks, workspace):
-        j = s.shape[1]
-        assert self.whitened_generic_applies(cost, j), "this cost / size has no whitened step: stay in the original coordinates"
-        lib, desc, ws_bytes = self._whitened_generic_call(cost, j, s.device)
-        ws = self._pick_workspace(workspace, ws_bytes, s.device)
-        nd = (noise if noise is not None else self._draw_noise_spec(None)).desc()
-        bd = None if blocks is None else blocks.desc()
-        if bd is None:
-            bd = L.BlockDesc()
-            bd.block_cols, bd.eta = j, self._eta_word(step_size, s.device).data_ptr()
-        if not bd.step_sync:
-            bd.step_sync = self._step_sync(j, s.device).data_ptr()
-        try:
-            L.check(lib.pls_ipb_whitened_generic_step(desc, cost.desc(), cost.y_device().data_ptr(), s.data_ptr(), L.ld(s), j, 0.0, bd,
-                                                      nd, out.data_ptr(), L.ld(out), L.OUT_NEW_STATE if new_state else L.OUT_DELTA,
-                                                      L.ptr(input_energy), ws.data_ptr(), ws_bytes, L.stream_ptr()),
-                    "pls_ipb_whitened_generic_step")
-        except L.PlsHipError:
-            self.zero_step_sync()
-            raise
-        return out
-
     def supports_lagged_energies(self, cost) -> bool:
         """(see OrthonormalBasis.supports_lagged_energies) -- for loops that stay in whitened coordinates: the Gaussian/identity
         route only (the one-launch small-rank step finishes its energies itself)"""
-        return bool(cost.is_native()) and self.whitened and self._is_gaussian(cost, False)
+        return bool(cost.is_native()) and self.whitened and self._is_gaussian(cost)
 
     def energy_partial_rows_bytes(self, j: int) -> int:
         return int(L.load().pls_energy_partials_bytes(self.approximation_dimension, j))
-
-    def lagged_step_launcher(self, cost, state: torch.Tensor, eta: torch.Tensor):
-        """(see OrthonormalBasis.lagged_step_launcher) -- the whitened step, pls_ipb_whitened_step_blocks, pre-bound"""
-        s = _rows_contiguous(L.require_gpu_tensor(state, "whitened particles"))
-        assert self.whitened and self._is_gaussian(cost, False)
-        self._prepare_for(cost)
-        fn = L.load().pls_ipb_whitened_step_blocks
-        desc, cd = self._desc(with_gaussian=True), cost.desc()
-        blocks, nd = L.BlockDesc(), L.NoiseDesc()
-        j = s.shape[1]
-        blocks.block_cols, blocks.eta = j, L.require_gpu_tensor(eta, "eta").data_ptr()
-        nd.kind, nd.step, nd.j_offset = L.NOISE_PHILOX, 0, int(self.j_offset)
-        stream, mode = L.stream_ptr(), L.OUT_NEW_STATE
-
-        def launch(s_ptr, lds, out_ptr, ldo, seed, partials_out, partials_prev, energy_prev, sums_prev):
-            nd.seed = seed
-            blocks.energy_partials, blocks.energy_partials_prev = partials_out, partials_prev
-            blocks.energy_prev, blocks.energy_sums_prev = energy_prev, sums_prev
-            rc = fn(desc, cd, s_ptr, lds, j, blocks, nd, out_ptr, ldo, mode, None, None, 0, stream)
-            if rc:
-                L.check(rc, "pls_ipb_whitened_step_blocks")
-
-        launch.keep_alive = (desc, cd, eta, self)
-        return launch
-
-    def flush_energies(self, cost, state: torch.Tensor, blocks: BlockSpec) -> None:
-        """(see OrthonormalBasis.flush_energies); ``state`` = the WHITENED particle matrix of the whitened_step calls"""
-        s = _rows_contiguous(L.require_gpu_tensor(state, "whitened particles"))
-        self._prepare_for(cost)
-        nd = NoiseSpec(none=True).desc()
-        L.check(
-            L.load().pls_ipb_whitened_step_blocks(self._desc(with_gaussian=True), cost.desc(), s.data_ptr(), L.ld(s), s.shape[1],
-                                                  blocks.desc(), nd, None, 0, L.OUT_DELTA, None, None, 0, L.stream_ptr()),
-            "pls_ipb_whitened_step_blocks",
-        )
 
     def whitened_particle_energy(self, cost, whitened: torch.Tensor) -> torch.Tensor:
         """e_j of whitened particles: S^T Q S / 2 - c~^T S + y^T y / (2 sigma2) (pls_ipb_whitened_energy)."""
         s = _rows_contiguous(L.require_gpu_tensor(whitened, "whitened particles"))
         j = s.shape[1]
-        if not self._is_gaussian(cost, False):
+        if not self._is_gaussian(cost):
             # (plain loops and final values only: a step with step size zero and no noise, for its energy by-product)
             e = torch.empty(j, dtype=torch.float64, device=s.device)
             if j:
-                scratch = torch.empty_like(s, memory_format=torch.contiguous_format)
-                self._whitened_generic_step(cost, s, 0.0, scratch, False, NoiseSpec(none=True), e, None, None)
+                self.whitened_step(cost, s, 0.0, noise=NoiseSpec(none=True), input_energy=e)
             return e
         self._prepare_for(cost)
         lib = L.load()
@@ -347,11 +228,6 @@ class InducingPointBasis(PLSBasis):
             L.check(lib.pls_ipb_whitened_energy(desc, cost.desc(), s.data_ptr(), L.ld(s), j, e.data_ptr(), ws.data_ptr(), ws_bytes,
                                                 L.stream_ptr()), "pls_ipb_whitened_energy")
         return e
-
-    @staticmethod
-    def _is_gaussian(cost, force_generic: bool) -> bool:
-        cd = cost.desc()
-        return cd.cost == L.COST_GAUSSIAN and cd.link == L.LINK_IDENTITY and not force_generic
 
     def _initialise_particles(self, number_of_particles: int, noise_only: bool = True, seed: int | None = None) -> torch.Tensor:
         particle_noise = self._initialise_particles_noise(number_of_particles=number_of_particles, seed=seed)
@@ -410,148 +286,52 @@ class InducingPointBasis(PLSBasis):
     def supports_fused_step(self) -> bool:
         return True
 
-    def fused_step(self, cost, particles: torch.Tensor, step_size: float, out: torch.Tensor | None = None,
-                   new_state: bool = False, noise: NoiseSpec | None = None, force_generic: bool = False,
-                   input_energy: torch.Tensor | None = None, blocks: BlockSpec | None = None,
-                   workspace: torch.Tensor | None = None) -> torch.Tensor:
-        """One whole Langevin step (pls_ipb_step).  ``input_energy`` (J,) receives the per-particle energy of
-        ``particles`` as a by-product (cost of the same F + (M/2)||K^-1 U||^2).  ``blocks``: one step size per column
-        block (pls_ipb_step_blocks; ``step_size`` is then ignored).  ``workspace``: a caller-owned buffer (graph captures)."""
-        u = _rows_contiguous(L.require_gpu_tensor(particles, "particles", promote=True))
-        j = u.shape[1]
-        if out is None:
-            out = torch.empty_like(u, memory_format=torch.contiguous_format)
-        else:  # (written as float64 through a raw pointer: a buffer of another dtype or shape must never get this far)
-            L.require_gpu_tensor(out, "out")
-            assert out.shape == u.shape, f"out has shape {tuple(out.shape)}, the particles {tuple(u.shape)}"
-        if j == 0:
-            return out
-        assert out.data_ptr() != u.data_ptr(), "fused_step: out must not alias particles"
-        lib = L.load()
-        gaussian = self._is_gaussian(cost, force_generic)
+    def _route(self, cost, j: int, force_generic: bool = False, whitened: bool = False) -> StepRoute:
+        """pls_ipb_step[_blocks] on the original coordinates (the Gaussian/identity fast path with B, c and the whitened
+        operator prepared; at most 128 points and any other cost, the one-launch small-rank step).  ``whitened``: the
+        Gaussian/identity step of whitened particles, pls_ipb_whitened_step[_blocks] (workspace for its energy by-product
+        only), or for any other cost the one-launch step over Awa, pls_ipb_whitened_generic_step."""
+        lib, cd, y = L.load(), cost.desc(), cost.y_device()
+        gaussian = self._is_gaussian(cost, force_generic, cd)
         if gaussian:
             self._prepare_for(cost)
+        if whitened:
+            assert self.whitened, "whitened coordinates are switched off on this basis"
+            if not gaussian:
+                assert self.whitened_generic_applies(cost, j), "this cost / size has no whitened step: stay in the original coordinates"
+                desc = self._desc()
+                return StepRoute(None, "pls_ipb_whitened_generic_step", (desc, cd, y.data_ptr()), (),
+                                 lib.pls_ipb_whitened_generic_workspace_bytes(desc, j), self._holds(y), one_launch=True,
+                                 blocks_head=(0.0,))
+            desc = self._desc(with_gaussian=True)
+            return StepRoute("pls_ipb_whitened_step", "pls_ipb_whitened_step_blocks", (desc, cd), (),
+                             lib.pls_ipb_whitened_workspace_bytes(desc, j), self._holds(y), sums=True, lagged=True,
+                             ws_for_energy_only=True)
         desc = self._desc(with_gaussian=gaussian)
-        need_min = lib.pls_ipb_step_workspace_bytes(desc, j, 128)
-        need_full = lib.pls_ipb_step_workspace_bytes(desc, j, self._n)
-        ws_bytes = max(need_min, min(need_full, self.workspace_bytes))
-        ws = self._pick_workspace(workspace, ws_bytes, u.device)
-        nd = (noise if noise is not None else self._draw_noise_spec(None)).desc()
-        mode = L.OUT_NEW_STATE if new_state else L.OUT_DELTA
-        bd = None if blocks is None else blocks.desc()
-        if not gaussian and 1 <= self.approximation_dimension <= self.SMALL_RANK_MAX:
-            # (the one-launch small-rank step meets through zeroed counters: see OrthonormalBasis.fused_step)
-            if bd is None:
-                bd = L.BlockDesc()
-                bd.block_cols, bd.eta = j, self._eta_word(step_size, u.device).data_ptr()
-            if not bd.step_sync:
-                bd.step_sync = self._step_sync(j, u.device).data_ptr()
-        try:
-            if bd is None:
-                L.check(
-                    lib.pls_ipb_step(desc, cost.desc(), cost.y_device().data_ptr(), u.data_ptr(), L.ld(u), j, float(step_size), nd,
-                                     out.data_ptr(), L.ld(out), mode, 1 if force_generic else 0, L.ptr(input_energy), ws.data_ptr(),
-                                     ws_bytes, L.stream_ptr()),
-                    "pls_ipb_step",
-                )
-            else:
-                L.check(
-                    lib.pls_ipb_step_blocks(desc, cost.desc(), cost.y_device().data_ptr(), u.data_ptr(), L.ld(u), j, bd, nd,
-                                            out.data_ptr(), L.ld(out), mode, 1 if force_generic else 0, L.ptr(input_energy),
-                                            ws.data_ptr(), ws_bytes, L.stream_ptr()),
-                    "pls_ipb_step_blocks",
-                )
-        except L.PlsHipError:
-            self.zero_step_sync()
-            raise
-        return out
+        ws_bytes = max(lib.pls_ipb_step_workspace_bytes(desc, j, 128),
+                       min(lib.pls_ipb_step_workspace_bytes(desc, j, self._n), self.workspace_bytes))
+        return StepRoute("pls_ipb_step", "pls_ipb_step_blocks", (desc, cd, y.data_ptr()), (int(force_generic),), ws_bytes,
+                         self._holds(y), one_launch=not gaussian and 1 <= self.approximation_dimension <= self.SMALL_RANK_MAX,
+                         sums=gaussian and self.whitened)
 
-    def step_launcher(self, cost, state: torch.Tensor, step_size: float):
-        """(see OrthonormalBasis.step_launcher) -- pls_ipb_step with the energy by-product + pls_block_means, pre-bound for a
-        training loop that stays in the original coordinates (any cost but the Gaussian fast path's whitened loop)"""
-        u = _rows_contiguous(L.require_gpu_tensor(state, "particles"))
-        j = u.shape[1]
-        lib = L.load()
-        gaussian = self._is_gaussian(cost, False)
-        if gaussian:
-            self._prepare_for(cost)
-        desc, cd, y = self._desc(with_gaussian=gaussian), cost.desc(), cost.y_device()
-        ws_bytes = max(lib.pls_ipb_step_workspace_bytes(desc, j, 128), min(lib.pls_ipb_step_workspace_bytes(desc, j, self._n), self.workspace_bytes))
-        ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.float64, device=u.device)
-        nd = L.NoiseDesc()
-        nd.kind, nd.step, nd.j_offset = L.NOISE_PHILOX, 0, int(self.j_offset)
-        step, means = lib.pls_ipb_step, lib.pls_block_means
-        y_ptr, ws_ptr, stream, mode, eta = y.data_ptr(), ws.data_ptr(), L.stream_ptr(), L.OUT_NEW_STATE, float(step_size)
-
-        def launch(u_ptr, ldu, out_ptr, ldo, seed, energy_ptr, mean_ptr):
-            nd.seed = seed
-            rc = step(desc, cd, y_ptr, u_ptr, ldu, j, eta, nd, out_ptr, ldo, mode, 0, energy_ptr, ws_ptr, ws_bytes, stream)
-            if rc:
-                L.check(rc, "pls_ipb_step")
-            rc = means(energy_ptr, j, j, mean_ptr, stream)
-            if rc:
-                L.check(rc, "pls_block_means")
-
-        launch.keep_alive = (desc, cd, y, ws, self)
-        return launch
-
-    def step_workspace_bytes(self, cost, j: int, with_energy: bool, force_generic: bool = False) -> int:
-        """Bytes fused_step asks of its workspace for ``j`` columns (graph captures allocate their own buffer)."""
-        lib = L.load()
-        desc = self._desc(with_gaussian=self._is_gaussian(cost, force_generic) and self._B is not None)
-        need_min = lib.pls_ipb_step_workspace_bytes(desc, j, 128)
-        need_full = lib.pls_ipb_step_workspace_bytes(desc, j, self._n)
-        return max(need_min, min(need_full, self.workspace_bytes))
+    def _holds(self, y: torch.Tensor) -> tuple:
+        """what a descriptor of this basis points into (StepRoute.holds)"""
+        return (y, self.base_gram_induce_train, self._Kxz, self._W, self._chol, self._chol.tri_scratch(), self._Awa, self._B,
+                self._c, self._Q, self._ct, self._Pt)
 
     def supports_input_energy(self, cost) -> bool:
         return bool(cost.is_native())
-
-    #: inducing-point counts up to which a cost without the Gaussian algebra takes the small-rank kernels
-    SMALL_RANK_MAX = 128
 
     def supports_energy_sums(self, cost) -> bool:
         """the whitened Gaussian/identity route, and every other native cost on at most 128 inducing points (the one-launch
         small-rank step writes the sums itself; see OrthonormalBasis.supports_energy_sums)"""
         if not cost.is_native():
             return False
-        return (self.whitened and self._is_gaussian(cost, False)) or self._one_launch_rank(cost)
-
-    def _one_launch_rank(self, cost) -> bool:
-        return (not self._is_gaussian(cost, False)) and 1 <= self.approximation_dimension <= self.SMALL_RANK_MAX
+        return (self.whitened and self._is_gaussian(cost)) or self._one_launch_rank(cost)
 
     def uses_sums16(self, cost) -> bool:
         """(see OrthonormalBasis.uses_sums16)"""
         return bool(cost.is_native()) and self._one_launch_rank(cost)
-
-    def sums_step_launcher(self, cost, state: torch.Tensor, eta: torch.Tensor):
-        """(see OrthonormalBasis.sums_step_launcher) -- pls_ipb_step_blocks with the energies of the input particles and their
-        16-column sums, pre-bound: V = k(Z,Z)^-1 U and the coloured noise by their own launches, everything else of the step
-        in ONE (csrc/small_rank_step.h) while the problem is launch-bound.  None for the Gaussian fast path."""
-        if not (cost.is_native() and self._one_launch_rank(cost)):
-            return None
-        u = _rows_contiguous(L.require_gpu_tensor(state, "particles"))
-        j = u.shape[1]
-        lib = L.load()
-        desc, cd, y = self._desc(with_gaussian=False), cost.desc(), cost.y_device()
-        ws_bytes = max(lib.pls_ipb_step_workspace_bytes(desc, j, 128), min(lib.pls_ipb_step_workspace_bytes(desc, j, self._n), self.workspace_bytes))
-        ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.float64, device=u.device)
-        sync = torch.zeros(max(int(lib.pls_step_sync_words(j)), 1), dtype=torch.int32, device=u.device)
-        blocks, nd = L.BlockDesc(), L.NoiseDesc()
-        blocks.block_cols, blocks.eta = j, L.require_gpu_tensor(eta, "eta").data_ptr()
-        blocks.step_sync = sync.data_ptr()
-        nd.kind, nd.step, nd.j_offset = L.NOISE_PHILOX, 0, int(self.j_offset)
-        fn = lib.pls_ipb_step_blocks
-        y_ptr, ws_ptr, stream, mode = y.data_ptr(), ws.data_ptr(), L.stream_ptr(), L.OUT_NEW_STATE
-
-        def launch(u_ptr, ldu, out_ptr, ldo, seed, energy_ptr, sums_ptr):
-            nd.seed = seed
-            blocks.energy_sums16 = sums_ptr
-            rc = fn(desc, cd, y_ptr, u_ptr, ldu, j, blocks, nd, out_ptr, ldo, mode, 0, energy_ptr, ws_ptr, ws_bytes, stream)
-            if rc:
-                L.check(rc, "pls_ipb_step_blocks")
-
-        launch.keep_alive = (desc, cd, y, ws, sync, eta, self)
-        return launch
 
     def fused_particle_energy(self, cost, particles: torch.Tensor, force_generic: bool = False) -> torch.Tensor:
         u = _rows_contiguous(L.require_gpu_tensor(particles, "particles", promote=True))

@@ -1,14 +1,13 @@
 """Orthonormal basis (drop-in for src/projected_langevin_sampling/basis/orthonormal.py:10-244)."""
 from __future__ import annotations
 
-
 import torch
 
 from .. import _lib as L
 from .. import _ops
 from ..kernel import PLSKernel, _dev
 from ..samplers import sample_multivariate_normal
-from .base import BlockSpec, NoiseSpec, PLSBasis, alloc_matrix
+from .base import BlockSpec, NoiseSpec, PLSBasis, StepRoute, _rows_contiguous, alloc_matrix
 
 
 class OrthonormalBasis(PLSBasis):
@@ -264,107 +263,43 @@ class OrthonormalBasis(PLSBasis):
         derivative is taken of (the reference recomputes F for the energy: projected_langevin_sampling.py:125-138)."""
         return bool(cost.is_native())
 
-    #: ranks up to which a cost without the Gaussian algebra takes the small-rank kernels (csrc/small_rank.h, small_rank_step.h)
-    SMALL_RANK_MAX = 128
-
     def supports_energy_sums(self, cost) -> bool:
         """True if the launch that finishes the step's energy by-product can also leave the 256-column chunk sums of the
         energies (BlockSpec.energy_sums): the Gaussian/identity fast path, and every native cost on a basis of at most 128
         functions -- the one-launch small-rank step (pls_block_desc.step_sync) writes them itself, its fall-back for large
         problems appends pls_chunk_sums."""
-        cd = cost.desc() if cost.is_native() else None
-        if cd is None:
-            return False
-        return (cd.cost == L.COST_GAUSSIAN and cd.link == L.LINK_IDENTITY) or self._one_launch_rank(cd)
+        return bool(cost.is_native()) and (self._is_gaussian(cost) or self._one_launch_rank(cost))
 
     def uses_sums16(self, cost) -> bool:
         """True if a training loop should ask for the 16-column sums of the energies (BlockSpec.energy_sums16) instead of the
         256-column chunk sums: the costs whose step is the one-launch small-rank kernel."""
-        return bool(cost.is_native()) and self._one_launch_rank(cost.desc())
+        return bool(cost.is_native()) and self._one_launch_rank(cost)
 
-    def _one_launch_rank(self, cd) -> bool:
-        gaussian = cd.cost == L.COST_GAUSSIAN and cd.link == L.LINK_IDENTITY
-        return (not gaussian) and 1 <= self.approximation_dimension <= self.SMALL_RANK_MAX
-
-    def step_workspace_bytes(self, cost, j: int, with_energy: bool, force_generic: bool = False) -> int:
-        """Bytes fused_step asks of its workspace for ``j`` columns (graph captures allocate their own buffer)."""
-        cd = cost.desc()
-        if cd.cost == L.COST_GAUSSIAN and cd.link == L.LINK_IDENTITY and not force_generic:
-            return 2 * ((self.approximation_dimension + 127) // 128) * j * 8 if with_energy else 0
-        lib = L.load()
-        desc = self._desc()
-        need_min = lib.pls_onb_step_workspace_bytes(desc, j, 128)
-        need_full = lib.pls_onb_step_workspace_bytes(desc, j, self._n)
-        return max(need_min, min(need_full, self.workspace_bytes))
-
-    def fused_step(self, cost, particles: torch.Tensor, step_size: float, out: torch.Tensor | None = None,
-                   new_state: bool = False, noise: NoiseSpec | None = None, force_generic: bool = False,
-                   input_energy: torch.Tensor | None = None, blocks: BlockSpec | None = None,
-                   workspace: torch.Tensor | None = None) -> torch.Tensor:
-        """One whole Langevin step in libplship (pls_onb_step): returns dU, or U + dU when new_state.
-        ``input_energy`` (J,) receives the per-particle energy of ``particles`` as a by-product.  ``blocks``: one step size
-        per column block (pls_onb_step_blocks; ``step_size`` is then ignored).  ``workspace``: a caller-owned buffer --
-        a captured hipGraph freezes its address, so captures never use the basis' own growable scratch."""
-        u = _rows_contiguous(L.require_gpu_tensor(particles, "particles", promote=True))
-        j = u.shape[1]
-        if out is None:
-            out = torch.empty_like(u, memory_format=torch.contiguous_format)
-        else:  # (written as float64 through a raw pointer: a buffer of another dtype or shape must never get this far)
-            L.require_gpu_tensor(out, "out")
-            assert out.shape == u.shape, f"out has shape {tuple(out.shape)}, the particles {tuple(u.shape)}"
-        if j == 0:
-            return out
-        assert out.data_ptr() != u.data_ptr(), "fused_step: out must not alias particles"
-        y = cost.y_device()
-        cd = cost.desc()
-        gaussian = cd.cost == L.COST_GAUSSIAN and cd.link == L.LINK_IDENTITY and not force_generic
+    def _route(self, cost, j: int, force_generic: bool = False, whitened: bool = False) -> StepRoute:
+        """pls_onb_step[_blocks].  The Gaussian/identity fast path takes B = A A^T, c = A y and asks for workspace only for
+        the partial rows of its energy by-product (one per 64 data rows); any other cost takes the slab kernels' G chunks
+        (or, on a basis of at most 128 functions, the one-launch small-rank step)."""
+        assert not whitened, "the orthonormal basis has no whitened coordinates"
+        y, cd = cost.y_device(), cost.desc()
+        gaussian = self._is_gaussian(cost, force_generic, cd)
         if gaussian:
             self.prepare_gaussian(y)
-        lib = L.load()
         desc = self._desc(with_gaussian=gaussian)
+        mk = self.approximation_dimension
         if gaussian:
-            ws, ws_bytes = None, 0
-            if input_energy is not None:
-                ws_bytes = 2 * ((self.approximation_dimension + 127) // 128) * j * 8  # one partial row per 64 data rows
-                ws = self._pick_workspace(workspace, ws_bytes, u.device)
+            ws_bytes = 2 * ((mk + 127) // 128) * j * 8
         else:
             wkey = (j, self.workspace_bytes)
             ws_bytes = self.__dict__.setdefault("_ws_bytes_cache", {}).get(wkey)
             if ws_bytes is None:
+                lib = L.load()
                 need_min = lib.pls_onb_step_workspace_bytes(desc, j, 128)
                 need_full = lib.pls_onb_step_workspace_bytes(desc, j, self._n)
-                ws_bytes = max(need_min, min(need_full, self.workspace_bytes))
-                self._ws_bytes_cache[wkey] = ws_bytes
-            ws = self._pick_workspace(workspace, ws_bytes, u.device)
-        nd = (noise if noise is not None else self._draw_noise_spec(None)).desc()
-        mode = L.OUT_NEW_STATE if new_state else L.OUT_DELTA
-        bd = None if blocks is None else blocks.desc()
-        if not gaussian and 1 <= self.approximation_dimension <= self.SMALL_RANK_MAX:
-            # the one-launch small-rank step meets through zeroed counters: the basis' own (per stream) unless the caller's
-            # BlockSpec brings some -- without them the library puts a memset node in front of every launch
-            if bd is None:
-                bd = L.BlockDesc()
-                bd.block_cols, bd.eta = j, self._eta_word(step_size, u.device).data_ptr()
-            if not bd.step_sync:
-                bd.step_sync = self._step_sync(j, u.device).data_ptr()
-        try:
-            if bd is None:
-                L.check(
-                    lib.pls_onb_step(desc, cd, y.data_ptr(), u.data_ptr(), L.ld(u), j, float(step_size), nd, out.data_ptr(), L.ld(out),
-                                     mode, 1 if force_generic else 0, L.ptr(input_energy), L.ptr(ws), ws_bytes, L.stream_ptr()),
-                    "pls_onb_step",
-                )
-            else:
-                L.check(
-                    lib.pls_onb_step_blocks(desc, cd, y.data_ptr(), u.data_ptr(), L.ld(u), j, bd, nd, out.data_ptr(),
-                                            L.ld(out), mode, 1 if force_generic else 0, L.ptr(input_energy), L.ptr(ws), ws_bytes,
-                                            L.stream_ptr()),
-                    "pls_onb_step_blocks",
-                )
-        except L.PlsHipError:
-            self.zero_step_sync()
-            raise
-        return out
+                ws_bytes = self._ws_bytes_cache[wkey] = max(need_min, min(need_full, self.workspace_bytes))
+        return StepRoute("pls_onb_step", "pls_onb_step_blocks", (desc, cd, y.data_ptr()), (int(force_generic),),
+                         ws_bytes, (y, self._A, self._At, self.eigenvalues, self._B, self._c),
+                         one_launch=not gaussian and 1 <= mk <= self.SMALL_RANK_MAX, sums=gaussian, lagged=gaussian,
+                         ws_for_energy_only=gaussian)
 
     #: fused_step itself takes BlockSpec.energy_partials (the inducing-point basis only in whitened_step)
     fused_step_takes_lagged_energies = True
@@ -372,48 +307,18 @@ class OrthonormalBasis(PLSBasis):
     def supports_lagged_energies(self, cost) -> bool:
         """True if a training loop may let launch k + 1 finish the energies of launch k (BlockSpec.energy_partials ...): the
         Gaussian/identity fast path."""
-        cd = cost.desc() if cost.is_native() else None
-        return cd is not None and cd.cost == L.COST_GAUSSIAN and cd.link == L.LINK_IDENTITY
+        return bool(cost.is_native()) and self._is_gaussian(cost)
 
     def energy_partial_rows_bytes(self, j: int) -> int:
         return int(L.load().pls_energy_partials_bytes(self.approximation_dimension, j))
 
-    def lagged_step_launcher(self, cost, state: torch.Tensor, eta: torch.Tensor):
-        """The lagged Gaussian step of a training loop (pls_onb_step_blocks with energy_partials ...) as a PRE-BOUND call:
-        the descriptors, the step-size word, the Philox column offset and the stream are fixed for the whole loop, so they are
-        built once; the returned function takes what changes from launch to launch as raw addresses.  (Building the same call
-        through fused_step costs ~10 us of Python per iteration -- half of an iteration at the reference's own problem sizes.)
-        launch(u_ptr, ldu, out_ptr, ldo, seed, partials_out, partials_prev, energy_prev, sums_prev); ``state``: any of the
-        loop's particle buffers (shape only)."""
-        u = _rows_contiguous(L.require_gpu_tensor(state, "particles"))
-        y = cost.y_device()
-        self.prepare_gaussian(y)
-        fn = L.load().pls_onb_step_blocks
-        desc, cd = self._desc(with_gaussian=True), cost.desc()
-        blocks, nd = L.BlockDesc(), L.NoiseDesc()
-        j = u.shape[1]
-        blocks.block_cols, blocks.eta = j, L.require_gpu_tensor(eta, "eta").data_ptr()
-        nd.kind, nd.step, nd.j_offset = L.NOISE_PHILOX, 0, int(self.j_offset)
-        y_ptr, stream, mode = y.data_ptr(), L.stream_ptr(), L.OUT_NEW_STATE
-
-        def launch(u_ptr, ldu, out_ptr, ldo, seed, partials_out, partials_prev, energy_prev, sums_prev):
-            nd.seed = seed
-            blocks.energy_partials, blocks.energy_partials_prev = partials_out, partials_prev
-            blocks.energy_prev, blocks.energy_sums_prev = energy_prev, sums_prev
-            rc = fn(desc, cd, y_ptr, u_ptr, ldu, j, blocks, nd, out_ptr, ldo, mode, 0, None, None, 0, stream)
-            if rc:
-                L.check(rc, "pls_onb_step_blocks")
-
-        launch.keep_alive = (desc, cd, y, eta, self)
-        return launch
-
     def eager_step(self, cost, particles: torch.Tensor, step_size: float) -> torch.Tensor | None:
         """dU of one step with the library's own noise for the drop-in loop `particles += pls.calculate_particle_update(...)`
-        (README.md:257-262, experiments/profiler/main.py:77-82): fused_step(cost, particles, step_size) with everything that
-        does not change from call to call bound once per (cost, J, step size, stream) -- descriptors, workspace, counters.
-        At the reference's own benchmark sizes a step is a 5 us kernel, and building the call afresh (~20 us of Python) is
-        what an iteration costs.  One draw from torch's global generator per call, like fused_step.  None: not applicable
-        (the caller takes fused_step)."""
+        (README.md:257-262, experiments/profiler/main.py:77-82): fused_step(cost, particles, step_size) through a BoundStep
+        cached per (cost, J, step size, stream, targets, ...) -- it owns its workspace, step-size word and counters.  At the
+        reference's own benchmark sizes a step is a 5 us kernel, and building the call afresh (~20 us of Python) is what an
+        iteration costs.  One draw from torch's global generator per call, like fused_step.  None: not applicable (the
+        caller takes fused_step)."""
         if not (particles.is_cuda and particles.dtype == torch.float64 and particles.dim() == 2 and particles.stride(1) == 1):
             return None
         j = particles.shape[1]
@@ -422,131 +327,27 @@ class OrthonormalBasis(PLSBasis):
         y = cost.y_device()
         key = (id(cost), j, float(step_size), L.stream_ptr(), y.data_ptr(), y._version, getattr(cost, "observation_noise", None),
                self.j_offset, self.workspace_bytes, type(cost), type(cost.link_function), getattr(cost.link_function, "jitter", None))
-        bound = self.__dict__.get("_eager")
-        if bound is None or bound[0] != key:
-            cd = cost.desc()
-            gaussian = cd.cost == L.COST_GAUSSIAN and cd.link == L.LINK_IDENTITY
-            if gaussian:
-                self.prepare_gaussian(y)
-            lib = L.load()
-            desc = self._desc(with_gaussian=gaussian)
-            nd = L.NoiseDesc()
-            nd.kind, nd.step, nd.j_offset = L.NOISE_PHILOX, 0, int(self.j_offset)
-            if gaussian:
-                ws, ws_bytes, bd = None, 0, None
-            else:
-                need_min = lib.pls_onb_step_workspace_bytes(desc, j, 128)
-                need_full = lib.pls_onb_step_workspace_bytes(desc, j, self._n)
-                ws_bytes = max(need_min, min(need_full, self.workspace_bytes))
-                ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.float64, device=particles.device)
-                bd = None
-                if self._one_launch_rank(cd):
-                    bd = L.BlockDesc()
-                    bd.block_cols, bd.eta = j, self._eta_word(step_size, particles.device).data_ptr()
-                    bd.step_sync = self._step_sync(j, particles.device).data_ptr()
-            bound = (key, (lib, desc, cd, y, nd, ws, ws_bytes, bd, self._B, self._c))
-            self._eager = bound
-        lib, desc, cd, y, nd, ws, ws_bytes, bd, _, _ = bound[1]
-        nd.seed = int(torch.randint(0, 2**62, (1,), dtype=torch.int64).item())
+        cached = self.__dict__.get("_eager")  # (key, BoundStep)
+        if cached is None or cached[0] != key:
+            cached = self._eager = (key, self._bind_step(cost, particles, step_size, energies=False, new_state=False))
+        bound = cached[1]
+        seed = int(torch.randint(0, 2**62, (1,), dtype=torch.int64).item())
         out = torch.empty_like(particles, memory_format=torch.contiguous_format)
-        ldu = particles.stride(0) if particles.shape[0] > 1 else max(j, particles.stride(0))
-        ws_ptr = None if ws is None else ws.data_ptr()
-        if bd is None:
-            rc = lib.pls_onb_step(desc, cd, y.data_ptr(), particles.data_ptr(), ldu, j, float(step_size), nd, out.data_ptr(), j,
-                                  L.OUT_DELTA, 0, None, ws_ptr, ws_bytes, key[3])
-        else:
-            rc = lib.pls_onb_step_blocks(desc, cd, y.data_ptr(), particles.data_ptr(), ldu, j, bd, nd, out.data_ptr(), j, L.OUT_DELTA, 0,
-                                         None, ws_ptr, ws_bytes, key[3])
-        if rc:
-            self.zero_step_sync()
+        ldu = particles.stride(0) if particles.shape[0] > 1 else max(j, particles.stride(0))  # (L.ld, inline: host-bound)
+        try:
+            bound.launch(particles.data_ptr(), ldu, out.data_ptr(), j, seed)
+        except L.PlsHipError:
             self.__dict__.pop("_eager", None)
-            L.check(rc, "pls_onb_step")
+            raise
         return out
-
-    def sums_step_launcher(self, cost, state: torch.Tensor, eta: torch.Tensor):
-        """The step of a training loop for a cost WITHOUT the Gaussian algebra on a basis of at most 128 functions, as a
-        PRE-BOUND call (see lagged_step_launcher for why): pls_onb_step_blocks with the energies of the input particles and their
-        16-column sums (BlockSpec.energy_sums16, straight into the caller's pinned slot) -- ONE launch per iteration in the
-        launch-bound regime (csrc/small_rank_step.h; the loop owns the counters and the workspace this binds), the slab
-        kernels + pls_sums16 beyond.  None for other bases / costs.
-        launch(u_ptr, ldu, out_ptr, ldo, seed, energy_ptr, sums_ptr)"""
-        cd = cost.desc()
-        if not self._one_launch_rank(cd):
-            return None
-        u = _rows_contiguous(L.require_gpu_tensor(state, "particles"))
-        j = u.shape[1]
-        y = cost.y_device()
-        lib = L.load()
-        desc = self._desc()
-        need_min = lib.pls_onb_step_workspace_bytes(desc, j, 128)
-        need_full = lib.pls_onb_step_workspace_bytes(desc, j, self._n)
-        ws_bytes = max(need_min, min(need_full, self.workspace_bytes))
-        ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.float64, device=u.device)
-        sync = torch.zeros(max(int(lib.pls_step_sync_words(j)), 1), dtype=torch.int32, device=u.device)
-        blocks, nd = L.BlockDesc(), L.NoiseDesc()
-        blocks.block_cols, blocks.eta = j, L.require_gpu_tensor(eta, "eta").data_ptr()
-        blocks.step_sync = sync.data_ptr()
-        nd.kind, nd.step, nd.j_offset = L.NOISE_PHILOX, 0, int(self.j_offset)
-        fn = lib.pls_onb_step_blocks
-        y_ptr, ws_ptr, stream, mode = y.data_ptr(), ws.data_ptr(), L.stream_ptr(), L.OUT_NEW_STATE
-
-        def launch(u_ptr, ldu, out_ptr, ldo, seed, energy_ptr, sums_ptr):
-            nd.seed = seed
-            blocks.energy_sums16 = sums_ptr
-            rc = fn(desc, cd, y_ptr, u_ptr, ldu, j, blocks, nd, out_ptr, ldo, mode, 0, energy_ptr, ws_ptr, ws_bytes, stream)
-            if rc:
-                L.check(rc, "pls_onb_step_blocks")
-
-        launch.keep_alive = (desc, cd, y, ws, sync, eta, self)
-        return launch
-
-    def step_launcher(self, cost, state: torch.Tensor, step_size: float):
-        """pls_onb_step with the energy by-product, followed by the mean of the energies into a caller's slot (pls_block_means),
-        as a PRE-BOUND call for a training loop -- any cost (see lagged_step_launcher for why).  The loop owns the workspace
-        this binds.  launch(u_ptr, ldu, out_ptr, ldo, seed, energy_ptr, mean_ptr)"""
-        u = _rows_contiguous(L.require_gpu_tensor(state, "particles"))
-        j = u.shape[1]
-        y, cd = cost.y_device(), cost.desc()
-        gaussian = cd.cost == L.COST_GAUSSIAN and cd.link == L.LINK_IDENTITY
-        if gaussian:
-            self.prepare_gaussian(y)
-        lib = L.load()
-        desc = self._desc(with_gaussian=gaussian)
-        if gaussian:
-            ws_bytes = 2 * ((self.approximation_dimension + 127) // 128) * j * 8
-        else:
-            need_min = lib.pls_onb_step_workspace_bytes(desc, j, 128)
-            need_full = lib.pls_onb_step_workspace_bytes(desc, j, self._n)
-            ws_bytes = max(need_min, min(need_full, self.workspace_bytes))
-        ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.float64, device=u.device)
-        nd = L.NoiseDesc()
-        nd.kind, nd.step, nd.j_offset = L.NOISE_PHILOX, 0, int(self.j_offset)
-        step, means = lib.pls_onb_step, lib.pls_block_means
-        y_ptr, ws_ptr, stream, mode, eta = y.data_ptr(), ws.data_ptr(), L.stream_ptr(), L.OUT_NEW_STATE, float(step_size)
-
-        def launch(u_ptr, ldu, out_ptr, ldo, seed, energy_ptr, mean_ptr):
-            nd.seed = seed
-            rc = step(desc, cd, y_ptr, u_ptr, ldu, j, eta, nd, out_ptr, ldo, mode, 0, energy_ptr, ws_ptr, ws_bytes, stream)
-            if rc:
-                L.check(rc, "pls_onb_step")
-            rc = means(energy_ptr, j, j, mean_ptr, stream)
-            if rc:
-                L.check(rc, "pls_block_means")
-
-        launch.keep_alive = (desc, cd, y, ws, self)
-        return launch
 
     def flush_energies(self, cost, state: torch.Tensor, blocks: BlockSpec) -> None:
         """Finish the partial rows the LAST step launch of a loop left (``blocks``: energy_flush=True, energy_partials_prev,
         energy_prev[, energy_sums_prev]); ``state``: the particle matrix the step calls were given (same shape / strides)."""
         u = _rows_contiguous(L.require_gpu_tensor(state, "particles"))
-        self.prepare_gaussian(cost.y_device())
-        nd = NoiseSpec(none=True).desc()
-        L.check(
-            L.load().pls_onb_step_blocks(self._desc(with_gaussian=True), cost.desc(), cost.y_device().data_ptr(), u.data_ptr(), L.ld(u),
-                                         u.shape[1], blocks.desc(), nd, None, 0, L.OUT_DELTA, 0, None, None, 0, L.stream_ptr()),
-            "pls_onb_step_blocks",
-        )
+        r = self._route(cost, u.shape[1])
+        L.check(r.call(blocks.desc(), u.data_ptr(), L.ld(u), u.shape[1], 0.0, NoiseSpec(none=True).desc(), None, 0, L.OUT_DELTA,
+                       None, None, 0, L.stream_ptr()), r.blocks_entry)
 
     def fused_particle_energy(self, cost, particles: torch.Tensor, force_generic: bool = False) -> torch.Tensor:
         """Per-particle energy (pls_onb_energy): the cost is reduced inside a GEMM epilogue -- the N x Mk x J forward
@@ -555,7 +356,7 @@ class OrthonormalBasis(PLSBasis):
         j = u.shape[1]
         lib = L.load()
         cd = cost.desc()
-        gaussian = cd.cost == L.COST_GAUSSIAN and cd.link == L.LINK_IDENTITY and not force_generic
+        gaussian = self._is_gaussian(cost, force_generic, cd)
         if gaussian:
             self.prepare_gaussian(cost.y_device())
         desc = self._desc(with_gaussian=gaussian)
@@ -634,8 +435,3 @@ def _cached_factor(basis, x: torch.Tensor, covariance) -> torch.Tensor:
     cache.append((x, key, lt))
     del cache[:-PREDICTIVE_FACTOR_CACHE_ENTRIES]
     return lt
-
-
-def _rows_contiguous(t: torch.Tensor) -> torch.Tensor:
-    assert t.dim() == 2, "expected a 2-D tensor"
-    return t if t.stride(1) == 1 or t.shape[1] <= 1 and t.is_contiguous() else t.contiguous()

@@ -44,10 +44,6 @@ def mean_from_chunk_sums(sums, count: int) -> float:
     return total / count
 
 
-def _supports_energy_sums(pls: PLS) -> bool:
-    return bool(getattr(pls.basis, "supports_energy_sums", lambda c: False)(pls.cost))
-
-
 class _LoopSpace:
     """The coordinates a training loop keeps its particles in between steps.  Identity for every basis but one: the
     inducing-point basis under the Gaussian cost with the identity link, whose step is ONE contraction per iteration in
@@ -72,31 +68,15 @@ class _LoopSpace:
     def enter(self, particles: torch.Tensor) -> torch.Tensor:
         return self.pls.basis.whiten(particles) if self.whitened else particles
 
-    def step(self, state, step_size, out, noise, input_energy, blocks=None):
+    def step(self, state, step_size, out, noise, input_energy):
         basis, cost = self.pls.basis, self.pls.cost
         fn = basis.whitened_step if self.whitened else basis.fused_step
-        return fn(cost, state, float(step_size), out=out, new_state=True, noise=noise, input_energy=input_energy, blocks=blocks)
+        return fn(cost, state, float(step_size), out=out, new_state=True, noise=noise, input_energy=input_energy)
 
-    def general_launcher(self, state, step_size):
-        """step + energy by-product + mean as a pre-bound call (basis.step_launcher), or None"""
-        make = None if self.whitened else getattr(self.pls.basis, "step_launcher", None)
-        return None if make is None else make(self.pls.cost, state, step_size)
-
-    def sums_launcher(self, state, eta_dev):
-        """step + energies + their chunk sums as a pre-bound call (basis.sums_step_launcher: the one-launch small-rank step), or None"""
-        if self.whitened_generic:
-            return self.pls.basis.whitened_generic_sums_step_launcher(self.pls.cost, state, eta_dev)
-        make = None if self.whitened else getattr(self.pls.basis, "sums_step_launcher", None)
-        return None if make is None else make(self.pls.cost, state, eta_dev)
-
-    def lagged_launcher(self, state, eta_dev):
-        """the lagged Gaussian step as a pre-bound call (basis.lagged_step_launcher), or None"""
-        make = getattr(self.pls.basis, "lagged_step_launcher", None)
-        return None if make is None else make(self.pls.cost, state, eta_dev)
-
-    def flush(self, state, blocks) -> None:
-        """finish the partial rows of the last step launch (lagged energies: BlockSpec.energy_flush)"""
-        self.pls.basis.flush_energies(self.pls.cost, state, blocks)
+    def bind(self, state, step_size, injected: bool):
+        """the loop's step call with its energies, bound once (basis._bind_step: a BoundStep)"""
+        return self.pls.basis._bind_step(self.pls.cost, state, step_size, whitened=self.whitened, lagged=LAGGED_ENERGIES,
+                                         injected=injected)
 
     def energy(self, state) -> torch.Tensor:
         if self.whitened:
@@ -205,15 +185,17 @@ IN_FLIGHT_BUFFER_BYTES = 4 << 30
 def _train_pls_in_flight(pls: PLS, particles: torch.Tensor, number_of_epochs: int, step_size: float,
                          early_stopper: EarlyStopper, noises, depth: int | None = None, mean=None) -> Tuple[torch.Tensor, List[float]]:
     """The pipelined loop with `depth` step launches queued: launch k computes U_{k+1} from U_k and, as a by-product, the
-    energy of U_k.  The mean energy travels to pinned host memory by the launch that finishes the by-product (the host
-    polls that slot; costs without fused chunk sums: a mean launch followed by an event), and launches k+1 .. k+depth-1
-    are already queued behind it while the host waits -- so the GPU never idles over the host's round trip (early-stop
-    logic + next launch, ~30 us against a 270 us step at configs[1]) nor over a descheduled host thread.  depth + 1 particle buffers rotate, so the launches made speculatively
-    past the stop never touch the returned state, and the torch RNG state is rewound to what the plain loop would have
-    consumed.  Same particles, energies and stop index as the plain loop (tests/test_gpu_parity.py)."""
-    from .basis.base import NoiseSpec
-
-    from .basis.base import BlockSpec
+    energy of U_k (or, lagged, finishes that of U_{k-1}), which travels to a slot of pinned host memory: the sums of its
+    column chunks, or its mean (basis._bind_step decides the form).  The host polls that slot while launches k+1 .. k+depth-1
+    are already queued behind it -- so the GPU never idles over the host's round trip (early-stop logic + next launch, ~30 us
+    against a 270 us step at configs[1]) nor over a descheduled host thread.  At the reference's own problem sizes the host's
+    share of an iteration bounds the loop (a 10 us kernel against 20 us of Python): the step call is bound once, the buffers'
+    addresses are looked up once, the slots are polled through numpy views, and the per-step keys are drawn from torch's
+    global generator in batches -- the same stream of draws as one per step.  depth + 1 particle buffers rotate, so the
+    launches made speculatively past the stop never touch the returned state, and the generator is left where the plain
+    loop leaves it: one draw per executed step.  Same particles, energies and stop index as the plain loop
+    (tests/test_gpu_parity.py)."""
+    from .basis.base import UNWRITTEN_ENERGY_BITS as UNWRITTEN
 
     T = number_of_epochs
     j = particles.shape[1]
@@ -222,140 +204,58 @@ def _train_pls_in_flight(pls: PLS, particles: torch.Tensor, number_of_epochs: in
         while depth > 2 and (depth + 1) * particles.numel() * 8 > IN_FLIGHT_BUFFER_BYTES:
             depth -= 1
     depth = max(2, min(int(depth), max(T, 2)))
-    NB = depth + 1  # rotating slots: particle buffers, energy vectors, host sums, events
+    NB = depth + 1  # rotating slots: particle buffers, energy vectors, host slots
     space = _LoopSpace(pls, noises, j)
-    bufs = [space.enter(particles)] + [torch.empty_like(particles, memory_format=torch.contiguous_format) for _ in range(NB - 1)]
+    first = space.enter(particles)
+    if first.stride(1) != 1:  # (the launches take row-contiguous buffers; leave() copies the final state back)
+        first = first.contiguous()
+    bufs = [first] + [torch.empty_like(particles, memory_format=torch.contiguous_format) for _ in range(NB - 1)]
     e_dev = [torch.empty(j, dtype=torch.float64, device=particles.device) for _ in range(NB)]
-    # Gaussian/identity fast paths: the launch that finishes the energy by-product also leaves the 256-column chunk sums of
-    # the energies -- straight in pinned host memory -- so an iteration is the step kernel and ONE small launch (round 2: a
-    # finishing launch plus a mean launch, 15 us of a 280 us iteration); other costs keep the separate mean launch
-    fused_sums = _supports_energy_sums(pls)
-    # (costs without the Gaussian algebra on a small basis: the one-launch step leaves the sums of 16 columns each -- for free,
-    # where the 256-column chunk sums cost it a second hand-over between workgroups, csrc/small_rank_step.h)
-    sums16 = bool(fused_sums and getattr(pls.basis, "uses_sums16", lambda c: False)(pls.cost))
-    nchunk = ((j + 15) // 16 if sums16 else (j + 255) // 256) if fused_sums else 1
+    step = space.bind(first, step_size, injected=noises is not None)
+    launch_step = step.launch
+    lag = 1 if step.reports_previous else 0  # launch k reports the energies of U_{k - lag}
+    means = step.form == "means"  # (a slot holds the mean; otherwise the sums of column chunks)
+    nchunk = step.slot_doubles
     host = torch.empty(NB * nchunk, dtype=torch.float64).pin_memory()
     host_ptr = host.data_ptr()  # (hipHostMalloc'ed by torch: host and device addresses coincide)
-    # Fused chunk sums: no event per launch.  An event record puts a barrier packet between the finishing launch and the
-    # next step (5.8 us of idle GPU per iteration in rocprofv3's trace, 2 % of a 0.27 ms iteration); instead the host
-    # fills a slot with a NaN of a payload no computation produces before it queues the launch, and reads the slot once
-    # every entry has been overwritten (each chunk sum is ONE 8-byte store by the finishing launch into coherent pinned
-    # memory; a diverged run's NaN / inf energies are ordinary values here)
-    host_bits = host.view(torch.int64)
-    from .basis.base import UNWRITTEN_ENERGY_BITS as UNWRITTEN
-    eta_dev = torch.full((1,), float(step_size), dtype=torch.float64, device=particles.device) if fused_sums else None
-    # ... and, with one zeroed counter per chunk (pls_block_desc.energy_sync), the step launch finishes the energies itself:
-    # an iteration is ONE launch (the finishing launch was 5-6 us of a 47 us iteration on the shard of an 8-GPU run)
-    sync = torch.zeros(nchunk, dtype=torch.int32, device=particles.device) if fused_sums else None
-    # ... or, better, launch k + 1 finishes the energies of launch k at its START, under the landing of its first operand rows
-    # (pls_block_desc.energy_partials / _prev): the reduction over the tile rows -- 4.4-5 us of serial tail behind the last MFMA
-    # when a launch finishes its own -- leaves the critical path altogether; E(U_k) then arrives with launch k + 1, and the
-    # last launch's partial rows are finished by a small launch of their own (flush)
-    lagged = bool(fused_sums and LAGGED_ENERGIES and getattr(pls.basis, "supports_lagged_energies", lambda c: False)(pls.cost)
-                  and (space.whitened or getattr(pls.basis, "fused_step_takes_lagged_energies", False)))
-    fast = None
-    if lagged:
-        pbytes = pls.basis.energy_partial_rows_bytes(j)
-        parts = [torch.empty((pbytes + 7) // 8, dtype=torch.float64, device=particles.device) for _ in range(2)]
-        if noises is None and all(b.dim() == 2 and b.stride(1) == 1 for b in bufs):
-            # The host's share of an iteration is what bounds the loop at the reference's own problem sizes (a 10 us kernel
-            # against 20 us of Python): the step call is bound once (descriptors, stream), the buffers' addresses are looked up
-            # once, the pinned slots are polled through numpy views, and the per-step keys are drawn from torch's global
-            # generator in batches -- the same stream of draws as one per step, and the generator is left exactly where the
-            # plain loop leaves it (below)
-            fast = space.lagged_launcher(bufs[0], eta_dev)
-    sums = None
-    if fused_sums and fast is None and not lagged and noises is None and pls.cost.is_native() \
-            and all(b.dim() == 2 and b.stride(1) == 1 for b in bufs):
-        # costs without the Gaussian algebra on a small basis: ONE launch per iteration leaves the new state, the energies of its
-        # input and their chunk sums in the pinned slot (csrc/small_rank_step.h), bound once like the lagged Gaussian step
-        sums = space.sums_launcher(bufs[0], eta_dev)
-    general = None
-    if not fused_sums and noises is None and pls.cost.is_native() and all(b.dim() == 2 and b.stride(1) == 1 for b in bufs):
-        # (other costs: the same host-side trim around pls_onb_step + pls_block_means; the mean's pinned slot is polled like
-        # the chunk sums instead of waited for through an event)
-        general = space.general_launcher(bufs[0], step_size)
-    if fast is not None or general is not None or sums is not None:
-        buf_ptr, buf_ld = [b.data_ptr() for b in bufs], [L.ld(b) for b in bufs]
-        e_ptr = [e.data_ptr() for e in e_dev]
-        part_ptr = [p_.data_ptr() for p_ in parts] if fast is not None else None
-        keys: List[int] = []
-        rng_start = torch.get_rng_state()
+    # No event per launch.  An event record puts a barrier packet between the finishing launch and the next step (5.8 us of
+    # idle GPU per iteration in rocprofv3's trace, 2 % of a 0.27 ms iteration); instead the host fills a slot with a NaN of a
+    # payload no computation produces before it queues the launch, and reads the slot once every entry has been overwritten
+    # (each entry is ONE 8-byte store into coherent pinned memory; a diverged run's NaN / inf energies are ordinary values here)
     host_np = host.numpy()  # (shares the pinned pages)
-    host_np_bits = host_np.view(np.int64)
-    flushed = [False]
-    events = [torch.cuda.Event() for _ in range(NB)]
-    rng_states = {}
+    host_bits = host_np.view(np.int64)
+    buf_ptr, buf_ld = [b.data_ptr() for b in bufs], [L.ld(b) for b in bufs]
+    e_ptr = [e.data_ptr() for e in e_dev]
+    keys: List[int] = []
+    rng_start = torch.get_rng_state() if noises is None else None
     launched = 0
+    flushed = False
 
     def launch():
         nonlocal launched
         k = launched
-        if fast is not None:  # launch k leaves the partial rows of E(U_k) and finishes those of E(U_{k-1}) into slot k - 1
+        if noises is None:
             if k >= len(keys):
                 keys.extend(torch.randint(0, 2**62, (256,), dtype=torch.int64).tolist())
-            a, b, prev = k % NB, (k + 1) % NB, (k - 1) % NB
-            if k > 0:
-                host_np_bits[prev * nchunk:(prev + 1) * nchunk] = UNWRITTEN
-                fast(buf_ptr[a], buf_ld[a], buf_ptr[b], buf_ld[b], keys[k], part_ptr[k % 2], part_ptr[(k - 1) % 2], e_ptr[prev],
-                     host_ptr + 8 * nchunk * prev)
-            else:
-                fast(buf_ptr[a], buf_ld[a], buf_ptr[b], buf_ld[b], keys[k], part_ptr[0], None, None, None)
-            launched += 1
-            return
-        if sums is not None:  # launch k: U_{k+1} from U_k, E(U_k) and its chunk sums (slot k) from the same launch
-            if k >= len(keys):
-                keys.extend(torch.randint(0, 2**62, (256,), dtype=torch.int64).tolist())
-            a, b = k % NB, (k + 1) % NB
-            host_np_bits[a * nchunk:(a + 1) * nchunk] = UNWRITTEN
-            sums(buf_ptr[a], buf_ld[a], buf_ptr[b], buf_ld[b], keys[k], e_ptr[a], host_ptr + 8 * nchunk * a)
-            launched += 1
-            return
-        if general is not None:  # launch k: U_{k+1} from U_k, E(U_k) as a by-product, its mean into slot k
-            if k >= len(keys):
-                keys.extend(torch.randint(0, 2**62, (256,), dtype=torch.int64).tolist())
-            a, b = k % NB, (k + 1) % NB
-            host_np_bits[a] = UNWRITTEN
-            general(buf_ptr[a], buf_ld[a], buf_ptr[b], buf_ld[b], keys[k], e_ptr[a], host_ptr + 8 * a)
-            launched += 1
-            return
-        rng_states[k] = torch.get_rng_state()  # (a speculative launch may have to be un-drawn)
-        spec = NoiseSpec(injected=noises[k]) if noises is not None else None
-        if lagged:  # launch k leaves the partial rows of E(U_k) and finishes those of E(U_{k-1}) into slot k - 1
-            prev = (k - 1) % NB
-            if k > 0:
-                host_bits[prev * nchunk:(prev + 1) * nchunk] = UNWRITTEN
-            blocks = BlockSpec(j, eta_dev, energy_partials=parts[k % 2], energy_partials_prev=parts[(k - 1) % 2] if k > 0 else None,
-                               energy_prev=e_dev[prev] if k > 0 else None,
-                               energy_sums_prev=host_ptr + 8 * nchunk * prev if k > 0 else None)
-            space.step(bufs[k % NB], step_size, bufs[(k + 1) % NB], spec, None, blocks=blocks)
-        elif fused_sums:  # one column block = all particles, its step size from a device word, chunk sums to the host slot
-            host_bits[(k % NB) * nchunk:(k % NB + 1) * nchunk] = UNWRITTEN
-            slot = host_ptr + 8 * nchunk * (k % NB)
-            blocks = BlockSpec(j, eta_dev, energy_sums16=slot) if sums16 else BlockSpec(j, eta_dev, energy_sums=slot, energy_sync=sync)
-            space.step(bufs[k % NB], step_size, bufs[(k + 1) % NB], spec, e_dev[k % NB], blocks=blocks)
+            noise = keys[k]
         else:
-            space.step(bufs[k % NB], step_size, bufs[(k + 1) % NB], spec, e_dev[k % NB])
-            # E(U_k): the reduction kernel stores the mean straight into pinned host memory (mapped into the device's
-            # address space); the host reads it after the event -- no torch reduce kernel, no copy kernel per iteration
-            _ops.block_means(e_dev[k % NB], out_ptr=host_ptr + 8 * (k % NB))
-            events[k % NB].record()
-        rng_states.pop(k - NB - 1, None)
+            noise = noises[k]
+        a, b, s = k % NB, (k + 1) % NB, (k - lag) % NB
+        if k >= lag:
+            host_bits[s * nchunk:(s + 1) * nchunk] = UNWRITTEN
+            launch_step(buf_ptr[a], buf_ld[a], buf_ptr[b], buf_ld[b], noise, e_ptr[s], host_ptr + 8 * nchunk * s)
+        else:
+            launch_step(buf_ptr[a], buf_ld[a], buf_ptr[b], buf_ld[b], noise)
         launched += 1
 
     def read_energy(slot: int) -> float:
+        vals = host_np[slot * nchunk:(slot + 1) * nchunk]
         if mean is not None:  # J-sharded run (distributed.EnergyMean): the local SUM goes to the ranks' host-side exchange
-            local = mean_from_chunk_sums(host_np[slot * nchunk:(slot + 1) * nchunk], 1) if fused_sums else float(host_np[slot]) * j
-            return mean.reduce_local_sum(local)
-        if fused_sums:
-            return mean_from_chunk_sums(host_np[slot * nchunk:(slot + 1) * nchunk], j)
-        return float(host_np[slot])
+            return mean.reduce_local_sum(float(vals[0]) * j if means else mean_from_chunk_sums(vals, 1))
+        return float(vals[0]) if means else mean_from_chunk_sums(vals, j)
 
     def wait_for(slot: int) -> None:
-        if not fused_sums and general is None:
-            events[slot].synchronize()
-            return
-        bits = host_np_bits[slot * nchunk:(slot + 1) * nchunk]
+        bits = host_bits[slot * nchunk:(slot + 1) * nchunk]
         spins = 0
         while bool((bits == UNWRITTEN).any()):
             spins += 1
@@ -374,13 +274,12 @@ def _train_pls_in_flight(pls: PLS, particles: torch.Tensor, number_of_epochs: in
             # the stop below may return slot (t+1) % NB: k + 1 - (t + 1) <= depth < NB, so that slot is never overwritten
             while launched < T and launched <= t + depth:
                 launch()
-            if lagged and launched == T and not flushed[0]:
+            if lag and launched == T and not flushed:
                 # every step is queued: E(U_{T-1}) has no following launch to ride on -- a small finishing launch of its own
-                k = T - 1
-                host_bits[(k % NB) * nchunk:(k % NB + 1) * nchunk] = UNWRITTEN
-                space.flush(bufs[k % NB], BlockSpec(j, eta_dev, energy_partials_prev=parts[k % 2], energy_prev=e_dev[k % NB],
-                                                    energy_sums_prev=host_ptr + 8 * nchunk * (k % NB), energy_flush=True))
-                flushed[0] = True
+                s = (T - 1) % NB
+                host_bits[s * nchunk:(s + 1) * nchunk] = UNWRITTEN
+                step.flush(buf_ptr[s], buf_ld[s], e_ptr[s], host_ptr + 8 * nchunk * s)
+                flushed = True
             if t + 1 < T:
                 wait_for((t + 1) % NB)
                 energy_potential = read_energy((t + 1) % NB)
@@ -388,10 +287,7 @@ def _train_pls_in_flight(pls: PLS, particles: torch.Tensor, number_of_epochs: in
                 last = space.energy(bufs[T % NB])
                 energy_potential = _mean_energy(last) if mean is None else mean.reduce_local_sum(last.sum().item())
             if early_stopper.should_stop(loss=energy_potential, step_size=step_size):
-                if fast is not None or general is not None or sums is not None:
-                    keys_used = t + 1
-                elif launched > t + 1:
-                    torch.set_rng_state(rng_states[t + 1])
+                keys_used = t + 1
                 final = bufs[(t + 1) % NB]
                 break
             energy_potentials.append(energy_potential)
@@ -404,7 +300,7 @@ def _train_pls_in_flight(pls: PLS, particles: torch.Tensor, number_of_epochs: in
         # up to `depth` launches are still queued: they write the pinned slots and the rotating buffers, which must not go
         # back to torch's allocators (on ANY exit: a raising early stopper, a failed launch) before they have drained
         torch.cuda.current_stream().synchronize()
-    if fast is not None or general is not None or sums is not None:  # leave torch's generator where one draw per executed step leaves it
+    if rng_start is not None:  # leave torch's generator where one draw per executed step leaves it
         torch.set_rng_state(rng_start)
         if keys_used > 0:
             torch.randint(0, 2**62, (keys_used,), dtype=torch.int64)

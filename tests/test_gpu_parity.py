@@ -722,35 +722,91 @@ def test_train_pls_is_pipelined_for_every_native_cost(P, rank_path):
     assert np.allclose(runs["pipelined"][1], want, rtol=1e-8)
 
 
-@pytest.mark.parametrize("basis_kind", ["onb", "ipb"])
-def test_pre_bound_step_calls_change_nothing(P, basis_kind):
-    """The pipelined loop binds its step call once (basis.step_launcher: descriptors, workspace, stream), draws the per-step
-    keys from torch's generator in batches and polls the mean's pinned slot instead of an event.  Against the same loop
-    building every call through fused_step: the same particles, energies, stop index and generator state, bit for bit --
-    library noise (Philox), a cost without the Gaussian algebra, both bases, with and without an early stop."""
-    pr = make_problem(700, 24, 80, 2, seed=11 + FUZZ_SEED)
-    if basis_kind == "onb":
+# (case, basis, cost index, m, form, C entry of the bound step, whitened loop, LAGGED_ENERGIES, injected noise)
+PRE_BOUND_CASES = [
+    ("onb-lagged", "onb", 0, 24, "lagged", "pls_onb_step_blocks", False, True, False),
+    ("ipb-lagged", "ipb", 0, 24, "lagged", "pls_ipb_whitened_step_blocks", True, True, False),
+    ("onb-sums16", "onb", 2, 24, "sums16", "pls_onb_step_blocks", False, True, False),
+    ("ipb-sums16", "ipb-unwhitened", 2, 24, "sums16", "pls_ipb_step_blocks", False, True, False),
+    ("ipb-whitened-generic", "ipb", 2, 24, "sums16", "pls_ipb_whitened_generic_step", True, True, False),
+    ("onb-chunk-sums", "onb", 0, 24, "sums", "pls_onb_step_blocks", False, False, False),
+    ("onb-means", "onb", 2, 150, "means", "pls_onb_step", False, True, False),
+    ("ipb-means", "ipb", 2, 150, "means", "pls_ipb_step", False, True, False),
+    ("onb-lagged-injected", "onb", 0, 24, "lagged", "pls_onb_step_blocks", False, True, True),
+]
+
+
+@pytest.mark.parametrize("case", PRE_BOUND_CASES, ids=[c[0] for c in PRE_BOUND_CASES])
+def test_pre_bound_step_calls_change_nothing(P, case):
+    """The pipelined loop binds its step call once (basis._bind_step: a BoundStep that owns its descriptors' buffers), draws
+    the per-step keys from torch's generator in batches and polls the pinned slot its energies go to.  Against the plain loop
+    (a fused step and an energy evaluation per iteration): the same stop index, energies and generator state, and the same
+    particles -- bit for bit in the original coordinates, to rounding where the loop keeps them whitened -- for every form
+    the bound step takes, with and without an early stop; each run asserts the form and the C entry it was bound to."""
+    from projected_langevin_sampling_amd import trainers
+
+    _, kind, cost_idx, m, form, entry, whitened, lagged, injected = case
+    pr = make_problem(700, m, 80, 2, seed=11 + FUZZ_SEED)
+    if kind == "onb" and m > 128:  # (a projection of full rank 150: a kernel basis keeps fewer eigenvalues)
+        a = torch.randn(m, 700, generator=pr["gen"]) / math.sqrt(700)
+        gb = P.basis.OrthonormalBasis.from_projection(cu(a), cu(torch.rand(m, generator=pr["gen"]) + 0.5))
+        eta = 0.25 * float(gb.eigenvalues.min())
+    elif kind == "onb":
         _, gb = build_onb(P, pr)
+        eta = 0.25 * float(gb.eigenvalues.min())
     else:
+        pr["ls"] = pr["ls"] * 0.35
         _, gb = build_ipb(P, pr)
+        if kind == "ipb-unwhitened":
+            gb.whitened = False  # (an instance attribute: the loop stays in the original coordinates)
+        eta = 0.25 * float(torch.linalg.eigvalsh(gb.base_gram_induce.cpu()).min()) / m  # (eta M / lambda_min < 2)
     mk = gb.approximation_dimension
-    _, _, gc = make_costs(P, pr["y"], pr["fstar"], pr["gen"])[2]  # bernoulli/sigmoid
+    assert (mk > 128) == (form == "means"), mk
+    _, _, gc = make_costs(P, pr["y"], pr["fstar"], pr["gen"])[cost_idx]
     pls = P.pkg.PLS(gb, gc)
     u0 = cu(pr["u"][:mk].contiguous())
-    for patience in (1e9, 5e-6):
-        runs = []
-        for bound in (True, False):
-            if not bound:
-                gb.step_launcher = None  # (an instance attribute shadows the method: the loop falls back to fused_step)
-            try:
-                torch.manual_seed(44)
-                u, e = P.pkg.train_pls(pls, u0.clone(), 25, 2e-6, patience)
-                runs.append((u, e, torch.get_rng_state()))
-            finally:
-                if not bound:
-                    del gb.step_launcher
-        assert runs[0][1] == runs[1][1] and len(runs[0][1]) >= 1
-        assert torch.equal(runs[0][0], runs[1][0]) and torch.equal(runs[0][2], runs[1][2])
+    steps = 25
+    noises = [cu(torch.randn(mk, 80, generator=pr["gen"])) for _ in range(steps)] if injected else None
+    bound, real_bind = [], gb._bind_step
+
+    def bind(*a, **k):
+        bound.append(real_bind(*a, **k))
+        return bound[-1]
+
+    keep = trainers.LAGGED_ENERGIES
+    trainers.LAGGED_ENERGIES = lagged
+    try:
+        for patience in (1e9, 0.0):  # (patience 0: the run stops at the first energy that does not improve)
+            runs = {}
+            for mode in ("bound", "plain"):
+                gb._bind_step, bound[:] = bind, []
+                if mode == "plain":
+                    gb.supports_input_energy = lambda c: False
+                try:
+                    torch.manual_seed(44)
+                    u, e = P.pkg.train_pls(pls, u0.clone(), steps, eta, patience, noises=noises)
+                    runs[mode] = (u, e, torch.get_rng_state())
+                finally:
+                    del gb._bind_step
+                    if mode == "plain":
+                        del gb.supports_input_energy
+                if mode == "bound":
+                    b0 = bound[0] if len(bound) == 1 else None
+                    assert b0 is not None and b0.form == form and b0.injected == injected
+                    assert (b0.route.entry if b0.blocks is None else b0.route.blocks_entry) == entry
+                else:
+                    assert not bound
+            (ua, ea, ra), (ub, eb, rb) = runs["bound"], runs["plain"]
+            assert len(ea) == len(eb) >= 1 and np.allclose(ea, eb, rtol=1e-11, atol=0), (len(ea), len(eb))
+            if patience == 1e9:
+                assert len(ea) == steps
+            assert torch.equal(ra, rb)
+            if whitened:
+                assert relerr(ua, ub) < 1e-12
+            else:
+                assert torch.equal(ua, ub)
+    finally:
+        trainers.LAGGED_ENERGIES = keep
 
 
 @pytest.mark.parametrize("cost_idx,epochs,k,patience", [(0, 37, 8, 1e9), (0, 40, 16, 3e-3), (0, 40, 5, 3e-3), (0, 40, 1, 3e-3),

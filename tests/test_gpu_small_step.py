@@ -306,6 +306,74 @@ def test_the_drop_in_loop_takes_a_pre_bound_step_and_nothing_changes(P, route):
     assert pls.calculate_particle_update(u0.float(), 1e-4).dtype == torch.float64
 
 
+def _assert_owns_its_addresses(bound):
+    """every nonzero pointer of the bound step's pls_block_desc, and its workspace pointer, lies in a tensor the object holds"""
+    held = [t for t in (bound.workspace, bound.eta, bound.step_sync, bound.energy_sync, *bound.partials) if t is not None]
+    spans = [(t.data_ptr(), t.data_ptr() + t.numel() * t.element_size()) for t in held]
+    ptrs = [bound.workspace_ptr]
+    if bound.blocks is not None:
+        ptrs += [getattr(bound.blocks, f) for f, _ in bound.blocks._fields_ if f not in ("block_cols", "energy_flush", "reserved")]
+    for p in ptrs:
+        assert not p or any(a <= p < b for a, b in spans), (bound.form, hex(p))
+
+
+def test_the_drop_in_step_owns_its_counters_and_step_size_word(P, route):
+    """The drop-in step's BoundStep owns its arrival counters and its step-size word: the basis growing its own counter pool
+    (a fused_step over more columns on the same stream) and forgetting its step-size words (more than 64 step sizes) between
+    two drop-in calls changes nothing -- the second call gives the bits of fused_step with the same draws.  And every form a
+    step can be bound in points only into tensors the bound object holds."""
+    route(1)
+    pr = make_problem(1000, 16, 100, 2, seed=29 + FUZZ_SEED)
+    _, gb = build_onb(P, pr)
+    mk = gb.approximation_dimension
+    costs = make_costs(P, pr["y"], pr["fstar"], pr["gen"])
+    gauss, bern = costs[0][2], costs[2][2]
+    pls = P.pkg.PLS(gb, bern)
+    u = cu(pr["u"][:mk].contiguous())
+    eta = 1e-4
+    torch.manual_seed(5)
+    first = pls.calculate_particle_update(u, eta)
+    bound = gb._eager[1]
+    assert bound.form == "none" and bound.route.one_launch and bound.step_sync is not None
+    _assert_owns_its_addresses(bound)
+    torch.manual_seed(5)
+    assert torch.equal(first, gb.fused_step(bern, u, eta))
+    pool = gb._sync_pool
+    small = next(iter(pool.values()))
+    wide = cu(torch.randn(mk, 1200, generator=pr["gen"]))
+    gb.fused_step(bern, wide, eta)  # (J = 1200: more counter words than the pool's set held -- it is replaced)
+    assert next(iter(gb._sync_pool.values())) is not small
+    for i in range(65):  # (65 step sizes: the basis' step-size words are cleared once)
+        gb.fused_step(bern, u, eta * (1 + (i + 1) / 128))
+    assert len(gb._eta_words) < 65
+    del small, pool
+    torch.cuda.synchronize()
+    torch.manual_seed(6)
+    second = pls.calculate_particle_update(u, eta)
+    assert gb._eager[1] is bound, "the same key must reuse the bound step"
+    torch.manual_seed(6)
+    assert torch.equal(second, gb.fused_step(bern, u, eta))
+    assert int(bound.step_sync.abs().sum()) == 0
+    # every form a step can be bound in
+    forms = {}
+    for cost, kw in ((gauss, {}), (gauss, {"lagged": False}), (gauss, {"energies": False}), (bern, {})):
+        b = gb._bind_step(cost, u, eta, **kw)
+        forms[b.form] = b
+    ranked = P.basis.OrthonormalBasis.from_projection(cu(torch.randn(140, 300, generator=pr["gen"]) / 20),
+                                                      cu(torch.rand(140, generator=pr["gen"]) + 0.5))
+    y300 = pr["y"][:300]
+    b = ranked._bind_step(P.costs.BernoulliCost((y300 > 0).double(), P.links.SigmoidLinkFunction()),
+                          cu(torch.randn(140, 50, generator=pr["gen"])), eta)
+    forms[b.form] = b
+    assert set(forms) == {"lagged", "sums", "none", "sums16", "means"}, set(forms)
+    _, ib = build_ipb(P, pr)
+    s = cu(torch.randn(16, 100, generator=pr["gen"]))
+    forms_ipb = [ib._bind_step(gauss, s, eta, whitened=True), ib._bind_step(bern, s, eta, whitened=True), ib._bind_step(bern, s, eta)]
+    assert [b.form for b in forms_ipb] == ["lagged", "sums16", "sums16"]
+    for b in (*forms.values(), *forms_ipb):
+        _assert_owns_its_addresses(b)
+
+
 @pytest.mark.parametrize("n,mk,j", [(1, 1, 1), (17, 1, 16), (64, 128, 3), (65, 127, 33), (700, 5, 600), (2600, 64, 530)])
 def test_edges_of_the_one_launch_step(P, route, n, mk, j):
     """One data row, one function, one particle; a rank of exactly 128 and an odd one below it; more columns than one
