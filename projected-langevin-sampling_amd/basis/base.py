@@ -390,6 +390,11 @@ class PLSBasis(ABC):
         """How one step of ``cost`` over ``j`` columns runs (StepRoute); ``whitened``: on whitened particles."""
         raise NotImplementedError
 
+    def _general_ws_bytes(self, query, desc, j: int) -> int:
+        """Workspace of a step entry's general route, whose size query (pls_*_step_workspace_bytes) is ``query``: the basis'
+        budget (workspace_bytes), but at least what chunks of 128 rows need and at most what one chunk of all rows needs."""
+        return max(query(desc, j, 128), min(query(desc, j, self._n), self.workspace_bytes))
+
     def step_workspace_bytes(self, cost, j: int, with_energy: bool, force_generic: bool = False) -> int:
         """Bytes fused_step asks of its workspace for ``j`` columns (graph captures allocate their own buffer)."""
         return self._route(cost, j, force_generic).workspace_bytes(with_energy)

@@ -308,8 +308,7 @@ class InducingPointBasis(PLSBasis):
                              lib.pls_ipb_whitened_workspace_bytes(desc, j), self._holds(y), sums=True, lagged=True,
                              ws_for_energy_only=True)
         desc = self._desc(with_gaussian=gaussian)
-        ws_bytes = max(lib.pls_ipb_step_workspace_bytes(desc, j, 128),
-                       min(lib.pls_ipb_step_workspace_bytes(desc, j, self._n), self.workspace_bytes))
+        ws_bytes = self._general_ws_bytes(lib.pls_ipb_step_workspace_bytes, desc, j)
         return StepRoute("pls_ipb_step", "pls_ipb_step_blocks", (desc, cd, y.data_ptr()), (int(force_generic),), ws_bytes,
                          self._holds(y), one_launch=not gaussian and 1 <= self.approximation_dimension <= self.SMALL_RANK_MAX,
                          sums=gaussian and self.whitened)

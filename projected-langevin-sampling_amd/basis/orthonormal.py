@@ -286,16 +286,11 @@ class OrthonormalBasis(PLSBasis):
             self.prepare_gaussian(y)
         desc = self._desc(with_gaussian=gaussian)
         mk = self.approximation_dimension
-        if gaussian:
-            ws_bytes = 2 * ((mk + 127) // 128) * j * 8
-        else:
-            wkey = (j, self.workspace_bytes)
-            ws_bytes = self.__dict__.setdefault("_ws_bytes_cache", {}).get(wkey)
-            if ws_bytes is None:
-                lib = L.load()
-                need_min = lib.pls_onb_step_workspace_bytes(desc, j, 128)
-                need_full = lib.pls_onb_step_workspace_bytes(desc, j, self._n)
-                ws_bytes = self._ws_bytes_cache[wkey] = max(need_min, min(need_full, self.workspace_bytes))
+        wkey = (gaussian, j, self.workspace_bytes)
+        ws_bytes = self.__dict__.setdefault("_ws_bytes_cache", {}).get(wkey)
+        if ws_bytes is None:
+            ws_bytes = self._ws_bytes_cache[wkey] = (self.energy_partial_rows_bytes(j) if gaussian else
+                                                     self._general_ws_bytes(L.load().pls_onb_step_workspace_bytes, desc, j))
         return StepRoute("pls_onb_step", "pls_onb_step_blocks", (desc, cd, y.data_ptr()), (int(force_generic),),
                          ws_bytes, (y, self._A, self._At, self.eigenvalues, self._B, self._c),
                          one_launch=not gaussian and 1 <= mk <= self.SMALL_RANK_MAX, sums=gaussian, lagged=gaussian,

@@ -28,6 +28,7 @@
 #include "ipb_prep.h"
 #include "small_rank_step_launch.h"
 #include "step_params.h"
+#include "step_plan.h"
 
 namespace plship {
 
@@ -548,43 +549,6 @@ struct EpiIpbFinish {
         add_u ? U : nullptr, ldu);
   }
 };
-
-// Split-K plan for the back-projection D (I x J) = L^T R with a long contraction (K = rows of the N chunk).  Two reasons
-// to cut the contraction into slabs (summed in a fixed order by the update kernel: deterministic, no atomics):
-//   occupancy -- too few 128x128 output tiles to put two workgroups on each of the 256 CUs (narrow particle shards);
-//   locality  -- over a very long k-loop the co-resident workgroups drift apart and stop sharing operand panels in
-//                their XCD's L2: at K = 1e5 one slab reads 66 GB through the fabric, 8 slabs 20 GB, at equal speed
-//                (DESIGN.md "tuning log"); slabs of <= 16384 rows keep the drift inside the L2 window.
-// Returns the number of slabs (<= 16).
-static int64_t plan_split_k(int64_t I, int64_t J, int64_t K, int64_t *kchunk) {
-  const int64_t tiles = cdiv(I, 128) * cdiv(J, 128);
-  int64_t s = 1;
-  if (tiles < 512) s = cdiv(512, tiles);
-  const int64_t s_local = cdiv(K, 16384);
-  if (s_local > s) s = s_local;
-  if (s > 16) s = 16;
-  // wave quantisation: tiles * s workgroups run in rounds of 512 (2 per CU); a few more slabs can fill the last round
-  // (J = 2048: 128 tiles x 7 slabs = 1.75 rounds -> 87 % of the MFMA rate; x 8 = 2 rounds)
-  if (s > 1) {
-    auto waste = [&](int64_t sl) {
-      const double rounds = (double)(tiles * sl) / 512.0;
-      return std::ceil(rounds) / rounds;
-    };
-    int64_t best = s;
-    for (int64_t sl = s + 1; sl <= 16 && sl <= s + 4; ++sl)
-      if (waste(sl) < waste(best) - 0.03) best = sl;
-    s = best;
-  }
-  // keep every slab's k-loop long enough to amortise its prologue / epilogue; a handful of tiles (small ranks AND few
-  // particles) is latency-bound on its serial k-loop instead, so shorter slabs pay (M_k = 129, J = 256, N = 2000:
-  // 12 workgroups walked 125 k-steps each)
-  const int64_t min_chunk = tiles < 64 ? 256 : 1024;
-  while (s > 1 && K / s < min_chunk) --s;
-  int64_t kc = cdiv(cdiv(K, s), 16) * 16;
-  s = cdiv(K, kc);
-  *kchunk = (s > 1) ? kc : 0;
-  return s;
-}
 
 // ---- few output tiles: 64 x 64 tiles with the k range split over wave groups inside the workgroup (gemm_tn_f64_kg.h) ----
 static thread_local RouteOption g_ksplit_mode{1};          // pls_set_option(PLS_OPT_KSPLIT_MODE): 0 off, 1 auto, 2 / 3 force 2 / 1 k-groups
@@ -1480,7 +1444,7 @@ static int validate_cost(const pls_cost_desc *c) {
   return PLS_OK;
 }
 
-static int validate_noise(const pls_noise_desc *n, int64_t rows, int64_t j) {
+static int validate_noise(const pls_noise_desc *n, int64_t j) {
   if (!n) return PLS_OK;
   PLS_REQUIRE(n->kind >= PLS_NOISE_NONE && n->kind <= PLS_NOISE_PHILOX, "unknown noise kind %d", n->kind);
   if (n->kind == PLS_NOISE_INJECTED) {
@@ -1488,7 +1452,6 @@ static int validate_noise(const pls_noise_desc *n, int64_t rows, int64_t j) {
     // (the kernels read xi[row * ldxi + column] for every particle column: a narrower matrix would be read out of bounds)
     PLS_REQUIRE(n->ldxi >= j, "injected noise: leading dimension %lld < %lld particle columns", (long long)n->ldxi, (long long)j);
   }
-  (void)rows;
   return PLS_OK;
 }
 
@@ -1753,12 +1716,12 @@ static int fast_step_launch(const FastOp &op, const double *U, int64_t ldu, int6
                             size_t workspace_bytes, hipStream_t st, const char *who, double *esums = nullptr,
                             uint32_t *esync = nullptr, const EnergyLag &lag = EnergyLag{}) {
   const bool big = pick_gemm_cfg(op.B, op.ldb, U, ldu, op.mk, j, op.mk) == CFG_BIG;
-  const int64_t parts = big ? 2 * cdiv(op.mk, 128) : cdiv(op.mk, 64);  // partial rows THIS launch's tiling leaves
+  const int64_t parts = gaussian_partial_rows(op.mk, big, true);  // partial rows THIS launch's tiling leaves
   // A LAGGED buffer is finished by another launch, whose tiling may differ (the choice follows the alignment and leading
   // dimension of its own particle tensor and the k-split options): such a buffer always holds 2 cdiv(mk, 128) rows -- what
   // pls_energy_partials_bytes sizes it for -- and a launch that writes fewer zeroes the rest, so that whoever finishes it adds
   // the same rows whatever either launch chose.
-  const int64_t lag_rows = 2 * cdiv(op.mk, 128);
+  const int64_t lag_rows = gaussian_partial_rows(op.mk, true, true);
   if (lag.flush) {  // no step: the partial rows of the LAST launch of a loop are finished by the finishing kernel
     hipLaunchKernelGGL(gaussian_energy_finish_kernel, dim3((unsigned)cdiv(j, 256)), dim3(256), 0, st, lag.partials_prev, j, lag_rows, j,
                        lag.e_prev, op.yscale, op.yty, lag.sums_prev);
@@ -1766,9 +1729,8 @@ static int fast_step_launch(const FastOp &op, const double *U, int64_t ldu, int6
   }
   double *epart = lag.partials_out;
   if (energy_in && !epart) {
-    if (!workspace || workspace_bytes < (size_t)parts * j * sizeof(double))
-      return fail(PLS_ERR_WORKSPACE_TOO_SMALL, "%s: energy by-product needs %zu workspace bytes", who,
-                  (size_t)parts * j * sizeof(double));
+    if (!workspace || workspace_bytes < gaussian_partial_bytes(parts, j))
+      return fail(PLS_ERR_WORKSPACE_TOO_SMALL, "%s: energy by-product needs %zu workspace bytes", who, gaussian_partial_bytes(parts, j));
     epart = static_cast<double *>(workspace);
   }
   EpiLangevinGaussian e{out, ldo, U, ldu, op.c, op.lam, etap, op.inv_noise, out_mode, nz, epart, j, 2, big ? 128 : 64, {}, {}};
@@ -1791,8 +1753,8 @@ static int fast_step_launch(const FastOp &op, const double *U, int64_t ldu, int6
 static int fast_energy_launch(const FastOp &op, const double *U, int64_t ldu, int64_t j, double *e, void *workspace,
                               size_t workspace_bytes, hipStream_t st, const char *who) {
   const GemmCfg cfg = pick_gemm_cfg(op.B, op.ldb, U, ldu, op.mk, j, op.mk);
-  const int64_t parts = cfg == CFG_BIG ? cdiv(op.mk, 128) : cdiv(op.mk, 64);
-  if (!workspace || workspace_bytes < (size_t)parts * j * sizeof(double))
+  const int64_t parts = gaussian_partial_rows(op.mk, cfg == CFG_BIG, false);
+  if (!workspace || workspace_bytes < gaussian_partial_bytes(parts, j))
     return fail(PLS_ERR_WORKSPACE_TOO_SMALL, "%s: workspace %zu bytes too small", who, workspace_bytes);
   double *partial = static_cast<double *>(workspace);
   GemmShape g{op.B, op.ldb, U, ldu, op.mk, j, op.mk, 0, 0, 0};
@@ -1831,7 +1793,7 @@ size_t pls_tri_scratch_bytes(int64_t m, int64_t j) { return (m > 0 && j > 0) ? k
 size_t pls_step_sync_words(int64_t j) { return j > 0 ? small_rank_step_sync_words(j) : 0; }
 
 size_t pls_energy_partials_bytes(int64_t rows, int64_t j) {
-  return (rows > 0 && j > 0) ? (size_t)(2 * cdiv(rows, 128)) * j * sizeof(double) : 0;
+  return (rows > 0 && j > 0) ? gaussian_step_partial_bytes(rows, j) : 0;
 }
 
 int pls_set_option(int32_t option, int64_t value) {
@@ -2162,7 +2124,7 @@ int pls_onb_particle_update(const pls_onb_desc *basis, const double *U, int64_t 
                             int64_t j, double eta, const pls_noise_desc *noise, double *dU, int64_t lddu, void *stream) {
   int rc = validate_onb(basis);
   if (rc) return rc;
-  rc = validate_noise(noise, basis->mk, j);
+  rc = validate_noise(noise, j);
   if (rc) return rc;
   PLS_REQUIRE(U && G && dU && j >= 0 && ldu >= j && ldg >= j && lddu >= j, "onb_particle_update: bad arguments");
   PLS_REQUIRE(eta >= 0.0, "onb_particle_update: step size must be >= 0");
@@ -2176,71 +2138,85 @@ int pls_onb_particle_update(const pls_onb_desc *basis, const double *U, int64_t 
   return check_launch("langevin_update");
 }
 
-static bool onb_fast_path(const pls_onb_desc *b, const pls_cost_desc *c, int force_generic) {
-  return !force_generic && b->B && b->c && c->cost == PLS_COST_GAUSSIAN && c->link == PLS_LINK_IDENTITY;
+// ---- one step call: its arguments, its validation and its route -------------------------------------------------------
+
+// The arguments of one step call as the step entries take them (U: the particles, or the whitened particles S)
+struct StepCall {
+  const pls_cost_desc *cost;
+  const double *y;
+  const double *U;
+  int64_t ldu, j;
+  double eta;
+  const pls_block_desc *blocks;
+  const pls_noise_desc *noise;
+  double *out;
+  int64_t ldo;
+  int32_t out_mode;
+  double *energy_in;
+  void *workspace;
+  size_t workspace_bytes;
+  hipStream_t st;
+  EtaP etap() const { return make_etap(eta, blocks); }
+  NoiseP noisep() const { return make_noisep(noise, blocks); }
+  double *energy_sums() const { return blocks ? blocks->energy_sums : nullptr; }
+  uint32_t *energy_sync() const { return blocks ? blocks->energy_sync : nullptr; }
+};
+
+static int validate_blocks(const pls_block_desc *b) {
+  if (!b) return PLS_OK;
+  PLS_REQUIRE(b->block_cols > 0 && b->eta != nullptr, "step_blocks: block_cols must be > 0 and eta set");
+  return PLS_OK;
 }
 
-static int64_t onb_max_slabs(int64_t mk, int64_t j, int64_t n) {
-  int64_t kc;
-  int64_t s = plan_split_k(mk, j, n, &kc);
-  if (mk <= 256) {  // the fused small-rank kernels cut the rows into their own slabs (sized independently of the options)
-    int64_t rows;
-    const int64_t sr = small_rank_splits(j, n, &rows);
-    if (sr > s) s = sr;
-  }
-  return s;
+// The prologue of the four step entries after the basis descriptor: cost, noise, block descriptor, and the lagged energies
+// (pls_block_desc.energy_partials ...), which only the entries with a Gaussian/identity fast path take (`lagged`).
+static int validate_step(const char *who, const StepCall &c, bool lagged) {
+  if (int rc = validate_cost(c.cost)) return rc;
+  if (int rc = validate_noise(c.noise, c.j)) return rc;
+  if (int rc = validate_blocks(c.blocks)) return rc;
+  if (lagged) return validate_lag(c.blocks);
+  PLS_REQUIRE(!c.blocks || (!c.blocks->energy_partials && !c.blocks->energy_partials_prev && !c.blocks->energy_flush),
+              "%s: lagged energies (energy_partials) exist on the Gaussian/identity routes only", who);
+  return PLS_OK;
 }
 
-// partial rows of the step's energy by-product: one per 32 data rows of a chunk (the 64x64-tile worst case), or one per
-// small-rank row slab (<= 32); sized for the chunk, not for N
-static int64_t energy_partial_rows(int64_t n_chunk) { return cdiv(n_chunk, 32) < 32 ? 32 : cdiv(n_chunk, 32); }
-static size_t onb_energy_partial_bytes(int64_t n_chunk, int64_t j) {
-  return align_up((size_t)energy_partial_rows(n_chunk) * j * sizeof(double), 256);
+// ... and of a call that steps (not an energy flush): particles, output, targets (`needs_y`), sizes, step size, output mode
+static int validate_step_call(const char *who, const StepCall &c, bool needs_y) {
+  PLS_REQUIRE(c.U && c.out && (c.y || !needs_y), "%s: NULL pointer", who);
+  PLS_REQUIRE(c.out != c.U, "%s: out must not alias the particles (ping-pong the particle buffers)", who);
+  PLS_REQUIRE(c.j >= 0 && c.ldu >= c.j && c.ldo >= c.j, "%s: bad sizes", who);
+  PLS_REQUIRE(c.eta >= 0.0, "%s: step size must be >= 0", who);
+  PLS_REQUIRE(c.out_mode == 0 || c.out_mode == 1, "%s: out_mode must be 0 (delta) or 1 (new state)", who);
+  return PLS_OK;
 }
 
-// largest chunk (all rows, else a multiple of 128) whose G block and partial rows fit into `left` bytes
-static int64_t onb_pick_chunk(int64_t n, size_t left, int64_t j, int64_t min_rows) {
-  auto fits = [&](int64_t c) { return onb_energy_partial_bytes(c, j) + (size_t)c * j * sizeof(double) <= left; };
-  if (fits(n)) return n;
-  const double per_row = (double)j * sizeof(double) * (1.0 + 1.0 / 32.0);
-  int64_t c = (int64_t)(((double)left - 32.0 * j * sizeof(double) - 512.0) / per_row);
-  if (c > n) c = n;
-  c = c / 128 * 128;
-  while (c > min_rows && !fits(c)) c -= 128;
-  while (c + 128 <= n && fits(c + 128)) c += 128;
-  return c < min_rows ? min_rows : c;
+// The routes of a step call in original coordinates, decided once per call (onb_step_impl, ipb_step_impl)
+enum class StepRoute { Whitened, Fast, OneLaunch, General };
+
+// the Gaussian/identity fast path of either basis: the descriptor carries B and c (pls_*_build_gaussian)
+static bool gaussian_fast_path(const double *B, const double *c, const pls_cost_desc *cost, int force_generic) {
+  return !force_generic && B && c && cost->cost == PLS_COST_GAUSSIAN && cost->link == PLS_LINK_IDENTITY;
 }
 
-// workspace of the one-launch small-rank step: the slabs' partial drifts and cost sums, then (callers that hand in no
-// pls_block_desc.step_sync) the arrival counters
-static size_t sr_step_workspace_bytes(int64_t mk, int64_t j, int64_t n) {
-  if (mk < 1 || mk > 128) return 0;
-  return align_up(small_rank_step_slab_bytes(j, n, (int)mk), 256) + align_up(small_rank_step_sync_words(j) * sizeof(uint32_t), 256);
+// a workspace holds a layout of `total` bytes (one that needs none: any workspace, NULL included)
+static bool ws_holds(size_t total, const void *workspace, size_t workspace_bytes) {
+  return total == 0 || (workspace && total <= workspace_bytes);
 }
 
-size_t pls_onb_step_workspace_bytes(const pls_onb_desc *basis, int64_t j, int64_t n_chunk) {
-  if (!basis || j <= 0) return 0;
-  if (n_chunk <= 0 || n_chunk > basis->n) n_chunk = basis->n;
-  // D slabs (split-K of the back-projection, each mk x j) + cost partial rows of the energy by-product + G chunk
-  const size_t general = (size_t)onb_max_slabs(basis->mk, j, basis->n) * align_up((size_t)basis->mk * j * sizeof(double), 256) +
-                         onb_energy_partial_bytes(n_chunk, j) + (size_t)n_chunk * j * sizeof(double);
-  const size_t one_launch = sr_step_workspace_bytes(basis->mk, j, basis->n);
-  return general > one_launch ? general : one_launch;
-}
+// The launch-bound window of the one-launch step (csrc/small_rank_step.h): few enough particle columns for one workgroup per
+// 16 of them, and a step of at most 8 GFLOP (0.1 ms of matrix pipe) over the operand's n rows.  Beyond, the slab kernels of
+// small_rank.h share every tile of the operand between four column groups, which is what counts there.
+static bool launch_bound(int64_t n, int64_t mk, int64_t j) { return j <= 4096 && 4.0 * (double)n * (double)mk * (double)j <= 8e9; }
 
-// The one-launch step (csrc/small_rank_step.h) applies to the orthonormal basis with <= 128 functions whose back-projection
-// operand the LDS-DMA can stream (16-byte aligned rows); option 1 takes it while the problem is launch-bound -- few enough
-// particle columns for one workgroup per 16 of them, and a step of at most 8 GFLOP (0.1 ms of matrix pipe): beyond, the
-// slab kernels of small_rank.h share every tile of the operand between four column groups, which is what counts there.
+// The one-launch step applies to a basis of <= 128 functions whose back-projection operand the LDS-DMA can stream (16-byte
+// aligned rows) and 16-byte aligned targets (they travel by LDS-DMA like the rows).  Option 1 takes it inside the
+// launch-bound window; option 2 wherever it applies -- here only: the whitened generic step (ipb_whitened_generic_ok) keeps
+// the window under every option.
 static bool sr_step_route_for(const double *Lb, int64_t ldlb, int64_t mk, int64_t n, const double *y, int64_t j) {
   const int64_t mode = g_small_rank_step.load();
   if (mode == 0 || !small_rank_ok(Lb, ldlb, mk)) return false;
-  if (reinterpret_cast<uintptr_t>(y) & 15) return false;  // (the targets travel by 16-byte LDS-DMA like the rows)
-  if (mode >= 2) return true;
-  return j <= 4096 && 4.0 * (double)n * (double)mk * (double)j <= 8e9;
-}
-static bool sr_step_route(const pls_onb_desc *b, const double *y, int64_t j) {
-  return sr_step_route_for(b->At, b->ldat, b->mk, b->n, y, j);
+  if (reinterpret_cast<uintptr_t>(y) & 15) return false;
+  return mode >= 2 || launch_bound(n, mk, j);
 }
 
 // operands of the one-launch step for either basis: Lb (n x mk), the coordinates Vf the forward map contracts (and the prior
@@ -2257,88 +2233,55 @@ struct SrStepOperands {
   int64_t n_data = -1;  // rows of Lb that are data rows (the rest: prior rows, small_rank_step.h); -1: all n
 };
 
-// bytes the one-launch step takes from the workspace for j columns: its slabs, and its counters when the caller brings none
-static size_t sr_step_need_bytes(int64_t mk, int64_t n, int64_t j, const pls_block_desc *blocks, const double *energy_in) {
-  int64_t rows = 0;
-  int64_t ns = small_rank_step_splits(j, n, (int)mk, &rows);
-#ifdef PLS_SRS_PROBE
-  if (const char *f = getenv("PLS_SRS_FORCE_NS")) {
-    ns = atoi(f);
-    rows = (cdiv(n, ns) + 63) / 64 * 64;
-    ns = cdiv(n, rows);
-  }
-#endif
-  const size_t slab_bytes = ns > 1 ? align_up((size_t)cdiv(j, 16) * ns * ((size_t)mk + 1) * 16 * sizeof(double), 256) : 0;
-  const bool need_sync = ns > 1 || (blocks && energy_in && blocks->energy_sums);
-  const bool own_sync = blocks && blocks->step_sync;
-  return slab_bytes + ((need_sync && !own_sync) ? align_up(small_rank_step_sync_words(j) * sizeof(uint32_t), 256) : 0);
-}
-static bool sr_step_fits(int64_t mk, int64_t n, int64_t j, const pls_block_desc *blocks, const double *energy_in, size_t avail) {
-  return sr_step_need_bytes(mk, n, j, blocks, energy_in) <= avail;
+// the one-launch step's workspace for this call: counters for the slabs and the energy sums unless the caller brings them
+static SrStepLayout sr_step_plan(int lead, int64_t mk, int64_t n, const StepCall &c) {
+  return sr_step_layout(lead, mk, n, c.j, c.blocks && c.energy_in && c.blocks->energy_sums, c.blocks && c.blocks->step_sync);
 }
 
-static int sr_step_launch(const SrStepOperands &basis_ops, const CostP &cp, const double *y, int64_t j,
-                          const EtaP &etap, const NoiseP &nz, double *out, int64_t ldo, int out_mode, double *energy_in,
-                          const pls_block_desc *blocks, void *workspace, size_t workspace_bytes, hipStream_t st, bool *taken) {
-  const SrStepOperands *basis = &basis_ops;
-  *taken = false;
-  int64_t rows = 0;
-  int64_t ns = small_rank_step_splits(j, basis->n, (int)basis->mk, &rows);
-#ifdef PLS_SRS_PROBE
-  if (const char *f = getenv("PLS_SRS_FORCE_NS")) {
-    ns = atoi(f);
-    rows = (cdiv(basis->n, ns) + 63) / 64 * 64;
-    ns = cdiv(basis->n, rows);
-  }
-#endif
-  double *esums = (blocks && energy_in) ? blocks->energy_sums : nullptr;
-  const size_t slab_bytes = ns > 1 ? align_up((size_t)cdiv(j, 16) * ns * ((size_t)basis->mk + 1) * 16 * sizeof(double), 256) : 0;
-  const bool need_sync = ns > 1 || esums != nullptr;
-  uint32_t *sync = blocks ? blocks->step_sync : nullptr;
-  const size_t sync_bytes = small_rank_step_sync_words(j) * sizeof(uint32_t);
-  const size_t need = slab_bytes + ((need_sync && !sync) ? align_up(sync_bytes, 256) : 0);
-  if (need > 0 && (!workspace || workspace_bytes < need)) return PLS_OK;  // (the general route states its own needs)
-  if (need_sync && !sync) {  // counters from the workspace: zeroed by a memset node in front of the launch
-    sync = reinterpret_cast<uint32_t *>(static_cast<char *>(workspace) + slab_bytes);
-    hipError_t e = hipMemsetAsync(sync, 0, sync_bytes, st);
+// the one-launch step over a workspace laid out by `L`, which the caller checked it holds (ws_holds)
+static int sr_step_launch(const SrStepOperands &basis, const SrStepLayout &L, const StepCall &c, const NoiseP &nz) {
+  char *w = static_cast<char *>(c.workspace);
+  uint32_t *sync = c.blocks ? c.blocks->step_sync : nullptr;
+  if (L.counters) {  // counters from the workspace: zeroed by a memset node in front of the launch
+    sync = reinterpret_cast<uint32_t *>(w + L.sync_off);
+    hipError_t e = hipMemsetAsync(sync, 0, L.sync_bytes, c.st);
     if (e != hipSuccess) return fail(PLS_ERR_HIP, "onb_step: hipMemsetAsync: %s", hipGetErrorString(e));
   }
-  const int64_t ncb = cdiv(j, 16);
+  const int64_t ncb = cdiv(c.j, 16);
   SrStepP p{};
-  p.Lb = basis->Lb;
-  p.ldlb = basis->ldlb;
-  p.U = basis->Vf;
-  p.ldu = basis->ldvf;
-  p.Uadd = basis->Uadd;
-  p.lduadd = basis->lduadd;
-  p.y = y;
-  p.lam = basis->lam;
-  p.pconst = basis->pconst;
-  p.N = basis->n;
-  p.Ndata = basis->n_data >= 0 ? basis->n_data : basis->n;
-  p.J = j;
-  p.K = (int)basis->mk;
-  p.rows_per_split = rows;
-  p.nsplit = (int)ns;
-  p.cp = cp;
-  p.out = out;
-  p.ldo = ldo;
-  p.add_u = out_mode;
-  p.etap = etap;
+  p.Lb = basis.Lb;
+  p.ldlb = basis.ldlb;
+  p.U = basis.Vf;
+  p.ldu = basis.ldvf;
+  p.Uadd = basis.Uadd;
+  p.lduadd = basis.lduadd;
+  p.y = c.y;
+  p.lam = basis.lam;
+  p.pconst = basis.pconst;
+  p.N = basis.n;
+  p.Ndata = basis.n_data >= 0 ? basis.n_data : basis.n;
+  p.J = c.j;
+  p.K = (int)basis.mk;
+  p.rows_per_split = L.rows;
+  p.nsplit = (int)L.ns;
+  p.cp = make_costp(c.cost);
+  p.out = c.out;
+  p.ldo = c.ldo;
+  p.add_u = c.out_mode;
+  p.etap = c.etap();
   p.nz = nz;
   p.cb_sync = sync;
   p.chunk_sync = sync ? sync + ncb : nullptr;
-  p.slab = static_cast<double *>(workspace);
-  p.vslab = p.slab ? p.slab + ncb * ns * basis->mk * 16 : nullptr;
-  p.e = energy_in;
-  p.esums = esums;
-  p.sums16 = (blocks && energy_in) ? blocks->energy_sums16 : nullptr;
+  p.slab = reinterpret_cast<double *>(w + L.slab_off);
+  p.vslab = p.slab ? p.slab + ncb * L.ns * basis.mk * 16 : nullptr;
+  p.e = c.energy_in;
+  p.esums = (c.blocks && c.energy_in) ? c.blocks->energy_sums : nullptr;
+  p.sums16 = (c.blocks && c.energy_in) ? c.blocks->energy_sums16 : nullptr;
 #ifdef PLS_SRS_PROBE
   p.debug_stop = getenv("PLS_SRS_STOP") ? atoi(getenv("PLS_SRS_STOP")) : 0;
 #endif
-  *taken = true;
-  if (p.Ndata < p.N) return energy_in ? launch_small_rank_step_prior_value(p, st) : launch_small_rank_step_prior(p, st);
-  return energy_in ? launch_small_rank_step_value(p, st) : launch_small_rank_step(p, st);
+  if (p.Ndata < p.N) return c.energy_in ? launch_small_rank_step_prior_value(p, c.st) : launch_small_rank_step_prior(p, c.st);
+  return c.energy_in ? launch_small_rank_step_value(p, c.st) : launch_small_rank_step(p, c.st);
 }
 
 // pls_block_desc.energy_sums on the routes whose kernels do not leave them as a by-product (the generic N x M x J step, the
@@ -2365,103 +2308,102 @@ static int finish_sums16(const pls_block_desc *blocks, const double *energy_in, 
   return check_launch("sums16");
 }
 
-static int validate_blocks(const pls_block_desc *b, int64_t j) {
-  if (!b) return PLS_OK;
-  PLS_REQUIRE(b->block_cols > 0 && b->eta != nullptr, "step_blocks: block_cols must be > 0 and eta set");
-  (void)j;
-  return PLS_OK;
+// the Gaussian/identity fast path's step of either basis (operator `op`), then the 16-column sums its caller asked for
+static int fast_step(const FastOp &op, const StepCall &c, const char *who) {
+  const int rc = fast_step_launch(op, c.U, c.ldu, c.j, c.etap(), c.noisep(), c.out, c.ldo, c.out_mode, c.energy_in, c.workspace,
+                                  c.workspace_bytes, c.st, who, c.energy_sums(), c.energy_sync(), make_lag(c.blocks));
+  return rc ? rc : finish_sums16(c.blocks, c.energy_in, c.j, c.st);
 }
 
-static int onb_step_impl(const pls_onb_desc *basis, const pls_cost_desc *cost, const double *y, double *U, int64_t ldu,
-                         int64_t j, double eta, const pls_block_desc *blocks, const pls_noise_desc *noise, double *out,
-                         int64_t ldo, int32_t out_mode, int32_t force_generic, double *energy_in, void *workspace,
-                         size_t workspace_bytes, void *stream) {
-  int rc = validate_onb(basis);
-  if (rc) return rc;
-  rc = validate_cost(cost);
-  if (rc) return rc;
-  rc = validate_noise(noise, basis->mk, j);
-  if (rc) return rc;
-  rc = validate_blocks(blocks, j);
-  if (rc) return rc;
-  rc = validate_lag(blocks);
-  if (rc) return rc;
-  if (blocks && blocks->energy_flush) {  // finish the last launch's partial rows; no step (U / ldu as in the step calls)
-    PLS_REQUIRE(onb_fast_path(basis, cost, force_generic), "onb_step: energy_flush is for the Gaussian/identity fast path");
-    PLS_REQUIRE(U && j > 0 && ldu >= j, "onb_step: energy_flush needs the particle matrix of the step calls");
-    const FastOp op{basis->B, basis->ldb, basis->c, basis->lam, basis->mk, 1.0 / cost->p[0], 0.5 / cost->p[0], basis->c + basis->mk};
-    return fast_step_launch(op, U, ldu, j, make_etap(eta, blocks), make_noisep(noise, blocks), nullptr, 0, 0, nullptr, nullptr, 0,
-                            S(stream), "onb_step", nullptr, nullptr, make_lag(blocks));
-  }
-  PLS_REQUIRE(U && out && y, "onb_step: NULL pointer");
-  PLS_REQUIRE(out != U, "onb_step: out must not alias U (ping-pong the particle buffers)");
-  PLS_REQUIRE(j >= 0 && ldu >= j && ldo >= j, "onb_step: bad sizes");
-  PLS_REQUIRE(eta >= 0.0, "onb_step: step size must be >= 0");
-  PLS_REQUIRE(out_mode == 0 || out_mode == 1, "onb_step: out_mode must be 0 (delta) or 1 (new state)");
-  if (j == 0) return PLS_OK;
-  const CostP cp = make_costp(cost);
-  const NoiseP nz = make_noisep(noise, blocks);
-  const EtaP etap = make_etap(eta, blocks);
-  hipStream_t st = S(stream);
-  if (onb_fast_path(basis, cost, force_generic)) {
-    const FastOp op{basis->B, basis->ldb, basis->c, basis->lam, basis->mk, 1.0 / cost->p[0], 0.5 / cost->p[0], basis->c + basis->mk};
-    rc = fast_step_launch(op, U, ldu, j, etap, nz, out, ldo, out_mode, energy_in, workspace, workspace_bytes, st, "onb_step",
-                          blocks ? blocks->energy_sums : nullptr, blocks ? blocks->energy_sync : nullptr, make_lag(blocks));
-    return rc ? rc : finish_sums16(blocks, energy_in, j, st);
-  }
-  PLS_REQUIRE(!blocks || (!blocks->energy_partials && !blocks->energy_partials_prev),
-              "onb_step: lagged energies (energy_partials) exist on the Gaussian/identity fast path only");
-  if (sr_step_route(basis, y, j)) {  // launch-bound problems: the whole step, its energies and their chunk sums in ONE launch
-    bool taken = false;
-    const SrStepOperands ops{basis->At, basis->ldat, basis->mk, basis->n, U, ldu, nullptr, 0, basis->lam, 0.0};
-    rc = sr_step_launch(ops, cp, y, j, etap, nz, out, ldo, out_mode, energy_in, blocks, workspace, workspace_bytes, st, &taken);
-    if (rc || taken) return rc;
-  }
-  // workspace: [D slabs][cost partial rows (energy by-product)][G chunk]; the chunk length follows from what is left
-  const size_t d_bytes = align_up((size_t)basis->mk * j * sizeof(double), 256);
-  const int64_t max_slabs = onb_max_slabs(basis->mk, j, basis->n);
-  const int64_t min_rows = basis->n < 128 ? basis->n : 128;
-  const size_t need_min = max_slabs * d_bytes + onb_energy_partial_bytes(min_rows, j) + (size_t)min_rows * j * sizeof(double);
-  if (!workspace || workspace_bytes < need_min)
-    return fail(PLS_ERR_WORKSPACE_TOO_SMALL, "onb_step: workspace %zu bytes, need at least %zu", workspace_bytes,
-                pls_onb_step_workspace_bytes(basis, j, 128));
-  double *D = static_cast<double *>(workspace);
-  const size_t left = workspace_bytes - max_slabs * d_bytes;
-  const int64_t n_chunk = onb_pick_chunk(basis->n, left, j, min_rows);
-  double *vpart = reinterpret_cast<double *>(static_cast<char *>(workspace) + max_slabs * d_bytes);
-  double *Gbuf = reinterpret_cast<double *>(static_cast<char *>(workspace) + max_slabs * d_bytes +
-                                            onb_energy_partial_bytes(n_chunk, j));
+// ---- orthonormal basis: the step --------------------------------------------------------------------------------------
+
+static FastOp onb_fast_op(const pls_onb_desc *b, const pls_cost_desc *c) {
+  return FastOp{b->B, b->ldb, b->c, b->lam, b->mk, 1.0 / c->p[0], 0.5 / c->p[0], b->c + b->mk};
+}
+
+size_t pls_onb_step_workspace_bytes(const pls_onb_desc *basis, int64_t j, int64_t n_chunk) {
+  if (!basis || j <= 0) return 0;
+  if (n_chunk <= 0 || n_chunk > basis->n) n_chunk = basis->n;
+  const size_t general = drift_layout(0, basis->mk, basis->n, j, n_chunk).total;
+  const size_t one_launch = sr_step_query_bytes(0, basis->mk, basis->n, j);
+  return general > one_launch ? general : one_launch;
+}
+
+// the general route: the drift streamed over the N chunks the workspace holds (drift_plan), then the update
+static int onb_general_step(const pls_onb_desc *basis, const StepCall &c) {
+  const DriftLayout L = drift_plan(0, basis->mk, basis->n, c.j, c.workspace_bytes);
+  if (!c.workspace || L.total > c.workspace_bytes)
+    return fail(PLS_ERR_WORKSPACE_TOO_SMALL, "onb_step: workspace %zu bytes, need at least %zu", c.workspace_bytes,
+                pls_onb_step_workspace_bytes(basis, c.j, 128));
+  char *w = static_cast<char *>(c.workspace);
+  double *D = reinterpret_cast<double *>(w + L.d_off);
+  const int64_t slab_stride = (int64_t)(L.mj / sizeof(double));
   EnergySink sink;
-  if (energy_in) {  // e_j = cost_j(F(U)) + 1/2 sum_m U_mj^2 / lam_m of the INPUT particles (orthonormal.py:120-125)
-    sink.partial = vpart;
-    sink.rows_cap = energy_partial_rows(n_chunk);
-    sink.e = energy_in;
+  if (c.energy_in) {  // e_j = cost_j(F(U)) + 1/2 sum_m U_mj^2 / lam_m of the INPUT particles (orthonormal.py:120-125)
+    sink.partial = reinterpret_cast<double *>(w + L.part_off);
+    sink.rows_cap = L.part_rows;
+    sink.e = c.energy_in;
     sink.prior_kind = 1;
-    sink.P = U;
-    sink.ldp = ldu;
+    sink.P = c.U;
+    sink.ldp = c.ldu;
     sink.m = basis->mk;
     sink.lam = basis->lam;
   }
   int64_t nslab = 1;
-  rc = stream_drift(basis->A, basis->lda, basis->At, basis->ldat, basis->mk, basis->n, U, ldu, j, cp, y, D, j, max_slabs,
-                    (int64_t)(d_bytes / sizeof(double)), &nslab, Gbuf, n_chunk, st, energy_in ? &sink : nullptr);
+  int rc = stream_drift(basis->A, basis->lda, basis->At, basis->ldat, basis->mk, basis->n, c.U, c.ldu, c.j, make_costp(c.cost),
+                        c.y, D, c.j, L.slabs, slab_stride, &nslab, reinterpret_cast<double *>(w + L.g_off), L.n_chunk, c.st,
+                        c.energy_in ? &sink : nullptr);
   if (rc) return rc;
   {
-    LaunchScope scope(PLS_TAG_LANGEVIN_UPDATE, st);
-    hipLaunchKernelGGL(langevin_update_kernel, dim3((unsigned)cdiv(j, 256), rows_grid(cdiv(basis->mk, 8) * 4)), dim3(256), 0,
-                       st, out, ldo, U, ldu, D, j, (int)nslab, (int64_t)(d_bytes / sizeof(double)), U, ldu, basis->lam, 0.0,
-                       basis->mk, j, etap, out_mode, nz);
+    LaunchScope scope(PLS_TAG_LANGEVIN_UPDATE, c.st);
+    hipLaunchKernelGGL(langevin_update_kernel, dim3((unsigned)cdiv(c.j, 256), rows_grid(cdiv(basis->mk, 8) * 4)), dim3(256), 0,
+                       c.st, c.out, c.ldo, c.U, c.ldu, D, c.j, (int)nslab, slab_stride, c.U, c.ldu, basis->lam, 0.0, basis->mk,
+                       c.j, c.etap(), c.out_mode, c.noisep());
   }
   rc = check_launch("langevin_update");
   if (rc) return rc;
-  return finish_energy_sums(blocks, energy_in, j, st);
+  return finish_energy_sums(c.blocks, c.energy_in, c.j, c.st);
+}
+
+static int onb_step_impl(const pls_onb_desc *basis, const StepCall &c, int32_t force_generic) {
+  int rc = validate_onb(basis);
+  if (!rc) rc = validate_step("onb_step", c, true);
+  if (rc) return rc;
+  const bool fast = gaussian_fast_path(basis->B, basis->c, c.cost, force_generic);
+  if (c.blocks && c.blocks->energy_flush) {  // finish the last launch's partial rows; no step (U / ldu as in the step calls)
+    PLS_REQUIRE(fast, "onb_step: energy_flush is for the Gaussian/identity fast path");
+    PLS_REQUIRE(c.U && c.j > 0 && c.ldu >= c.j, "onb_step: energy_flush needs the particle matrix of the step calls");
+    return fast_step_launch(onb_fast_op(basis, c.cost), c.U, c.ldu, c.j, c.etap(), c.noisep(), nullptr, 0, 0, nullptr, nullptr, 0,
+                            c.st, "onb_step", nullptr, nullptr, make_lag(c.blocks));
+  }
+  if ((rc = validate_step_call("onb_step", c, true))) return rc;
+  if (c.j == 0) return PLS_OK;
+  StepRoute route = StepRoute::General;
+  SrStepLayout sl{};
+  if (fast) {
+    route = StepRoute::Fast;
+  } else if (sr_step_route_for(basis->At, basis->ldat, basis->mk, basis->n, c.y, c.j)) {
+    sl = sr_step_plan(0, basis->mk, basis->n, c);  // (launch-bound problems: the whole step, its energies and sums in ONE launch)
+    if (ws_holds(sl.total, c.workspace, c.workspace_bytes)) route = StepRoute::OneLaunch;
+  }
+  PLS_REQUIRE(fast || !c.blocks || (!c.blocks->energy_partials && !c.blocks->energy_partials_prev),
+              "onb_step: lagged energies (energy_partials) exist on the Gaussian/identity fast path only");
+  switch (route) {
+    case StepRoute::Fast:
+      return fast_step(onb_fast_op(basis, c.cost), c, "onb_step");
+    case StepRoute::OneLaunch:
+      return sr_step_launch(SrStepOperands{basis->At, basis->ldat, basis->mk, basis->n, c.U, c.ldu, nullptr, 0, basis->lam, 0.0},
+                            sl, c, c.noisep());
+    default:
+      return onb_general_step(basis, c);
+  }
 }
 
 int pls_onb_step(const pls_onb_desc *basis, const pls_cost_desc *cost, const double *y, double *U, int64_t ldu,
                  int64_t j, double eta, const pls_noise_desc *noise, double *out, int64_t ldo, int32_t out_mode,
                  int32_t force_generic, double *energy_in, void *workspace, size_t workspace_bytes, void *stream) {
-  return onb_step_impl(basis, cost, y, U, ldu, j, eta, nullptr, noise, out, ldo, out_mode, force_generic, energy_in, workspace,
-                       workspace_bytes, stream);
+  return onb_step_impl(basis, StepCall{cost, y, U, ldu, j, eta, nullptr, noise, out, ldo, out_mode, energy_in, workspace,
+                                       workspace_bytes, S(stream)}, force_generic);
 }
 
 int pls_onb_step_blocks(const pls_onb_desc *basis, const pls_cost_desc *cost, const double *y, double *U, int64_t ldu,
@@ -2469,16 +2411,16 @@ int pls_onb_step_blocks(const pls_onb_desc *basis, const pls_cost_desc *cost, co
                         int32_t out_mode, int32_t force_generic, double *energy_in, void *workspace,
                         size_t workspace_bytes, void *stream) {
   PLS_REQUIRE(blocks != nullptr, "onb_step_blocks: block descriptor is NULL");
-  return onb_step_impl(basis, cost, y, U, ldu, j, 0.0, blocks, noise, out, ldo, out_mode, force_generic, energy_in, workspace,
-                       workspace_bytes, stream);
+  return onb_step_impl(basis, StepCall{cost, y, U, ldu, j, 0.0, blocks, noise, out, ldo, out_mode, energy_in, workspace,
+                                       workspace_bytes, S(stream)}, force_generic);
 }
+
+// ---- orthonormal basis: the energy ------------------------------------------------------------------------------------
 
 size_t pls_onb_energy_workspace_bytes(const pls_onb_desc *basis, int64_t j, int64_t n_chunk) {
   if (!basis || j <= 0) return 0;
   if (n_chunk <= 0 || n_chunk > basis->n) n_chunk = basis->n;
-  int64_t parts = cdiv(n_chunk, 64) < 2 ? 2 : cdiv(n_chunk, 64);  // (the chunk planner needs two partial rows)
-  if (cdiv(basis->mk, 64) > parts) parts = cdiv(basis->mk, 64);  // the Gaussian quadratic form reduces over M_k instead
-  return (size_t)parts * j * sizeof(double);
+  return energy_layout(0, basis->mk, j, n_chunk).total;
 }
 
 int pls_onb_energy(const pls_onb_desc *basis, const pls_cost_desc *cost, const double *y, const double *U, int64_t ldu,
@@ -2489,21 +2431,14 @@ int pls_onb_energy(const pls_onb_desc *basis, const pls_cost_desc *cost, const d
   if (rc) return rc;
   PLS_REQUIRE(U && e && y && j >= 0 && ldu >= j, "onb_energy: bad arguments");
   if (j == 0) return PLS_OK;
-  if (onb_fast_path(basis, cost, force_generic)) {
-    // cost_j = (u^T B u - 2 c^T u + y^T y) / (2 sigma2): one Mk x Mk x J contraction, reduced per tile then per column
-    const FastOp op{basis->B, basis->ldb, basis->c, basis->lam, basis->mk, 1.0 / cost->p[0], 0.5 / cost->p[0], basis->c + basis->mk};
-    return fast_energy_launch(op, U, ldu, j, e, workspace, workspace_bytes, S(stream), "onb_energy");
-  }
-  // rows per chunk such that the partial buffer ((chunk/64) x j doubles) fits
-  const int64_t max_parts = (int64_t)(workspace_bytes / ((size_t)j * sizeof(double)));
-  if (!workspace || max_parts < 2)
+  if (gaussian_fast_path(basis->B, basis->c, cost, force_generic))  // cost_j = (u^T B u - 2 c^T u + y^T y) / (2 sigma2)
+    return fast_energy_launch(onb_fast_op(basis, cost), U, ldu, j, e, workspace, workspace_bytes, S(stream), "onb_energy");
+  const EnergyLayout L = energy_plan(0, basis->mk, basis->n, j, workspace_bytes);
+  if (!workspace || L.part_rows < 2)
     return fail(PLS_ERR_WORKSPACE_TOO_SMALL, "onb_energy: workspace %zu bytes too small", workspace_bytes);
-  int64_t n_chunk = max_parts * 64;
-  if (n_chunk > basis->n) n_chunk = basis->n;
-  else n_chunk = n_chunk / 128 * 128;
   return stream_cost(basis->A, basis->lda, basis->At, basis->ldat, basis->mk, basis->n, U, ldu, j, make_costp(cost), y,
-                     static_cast<double *>(workspace), max_parts, n_chunk, e, 1, U, ldu, basis->mk, basis->lam, 0.0,
-                     S(stream));
+                     reinterpret_cast<double *>(static_cast<char *>(workspace) + L.part_off), L.part_rows, L.n_chunk, e, 1, U,
+                     ldu, basis->mk, basis->lam, 0.0, S(stream));
 }
 
 int pls_onb_prior_energy(const pls_onb_desc *basis, const double *U, int64_t ldu, int64_t j, const double *cost,
@@ -2618,10 +2553,6 @@ static int ipb_finish(const pls_ipb_desc *basis, const double *U, int64_t ldu, c
   return check_launch("langevin_update");
 }
 
-static bool ipb_fast_path(const pls_ipb_desc *b, const pls_cost_desc *c, int force_generic) {
-  return !force_generic && b->B && b->c && c->cost == PLS_COST_GAUSSIAN && c->link == PLS_LINK_IDENTITY;
-}
-
 // Gaussian/identity constants of the inducing-point basis: B = Kzx Kxz (M x M), c[0..M) = Kzx y, c[M] = y^T y.
 // With V = K^-1 U the data drift is Kzx (Kxz V - y) / sigma2 = (B V - c) / sigma2: two M x M x J products per step
 // instead of two N x M x J ones (the same algebra as pls_onb_build_gaussian).
@@ -2644,7 +2575,7 @@ int pls_ipb_particle_update(const pls_ipb_desc *basis, const double *U, int64_t 
                             void *workspace, size_t workspace_bytes, void *stream) {
   int rc = validate_ipb(basis);
   if (rc) return rc;
-  rc = validate_noise(noise, basis->m, j);
+  rc = validate_noise(noise, j);
   if (rc) return rc;
   PLS_REQUIRE(U && G && dU && j >= 0 && ldu >= j && ldg >= j && lddu >= j, "ipb_particle_update: bad arguments");
   PLS_REQUIRE(eta >= 0.0, "ipb_particle_update: step size must be >= 0");
@@ -2662,159 +2593,173 @@ int pls_ipb_particle_update(const pls_ipb_desc *basis, const double *U, int64_t 
   return ipb_finish(basis, U, ldu, D, 1, (int64_t)0, V, j, eta, noise, dU, lddu, 0, xi, e, S(stream));
 }
 
+// ---- inducing-point basis: the step -----------------------------------------------------------------------------------
+// Every route takes V, xi and e (m x j each) from the front of the workspace: the lead buffers of its layout.
+constexpr int IPB_LEAD = 3;
+
 size_t pls_ipb_step_workspace_bytes(const pls_ipb_desc *basis, int64_t j, int64_t n_chunk) {
   if (!basis || j <= 0) return 0;
   if (n_chunk <= 0 || n_chunk > basis->n) n_chunk = basis->n;
-  // V, xi, e (m x j each) + D slabs + cost partial rows of the energy by-product + G chunk
-  const size_t mj = align_up((size_t)basis->m * j * sizeof(double), 256);
-  const size_t general = (size_t)(3 + onb_max_slabs(basis->m, j, basis->n)) * mj + onb_energy_partial_bytes(n_chunk, j) +
-                         (size_t)n_chunk * j * sizeof(double);
-  const size_t one_launch = 3 * mj + sr_step_workspace_bytes(basis->m, j, basis->n);  // (V, xi, e, then the step's slabs)
+  const size_t general = drift_layout(IPB_LEAD, basis->m, basis->n, j, n_chunk).total;
+  const size_t one_launch = sr_step_query_bytes(IPB_LEAD, basis->m, basis->n, j);
   return general > one_launch ? general : one_launch;
 }
 
-static int ipb_step_impl(const pls_ipb_desc *basis, const pls_cost_desc *cost, const double *y, double *U, int64_t ldu, int64_t j,
-                         double eta, const pls_block_desc *blocks, const pls_noise_desc *noise, double *out, int64_t ldo,
-                         int32_t out_mode, int32_t force_generic, double *energy_in, void *workspace, size_t workspace_bytes,
-                         void *stream) {
-  int rc = validate_ipb(basis);
-  if (rc) return rc;
-  rc = validate_cost(cost);
-  if (rc) return rc;
-  rc = validate_noise(noise, basis->m, j);
-  if (rc) return rc;
-  rc = validate_blocks(blocks, j);
-  if (rc) return rc;
-  PLS_REQUIRE(!blocks || (!blocks->energy_partials && !blocks->energy_partials_prev && !blocks->energy_flush),
-              "ipb_step: lagged energies (energy_partials) exist on pls_onb_step_blocks and pls_ipb_whitened_step_blocks only");
-  PLS_REQUIRE(U && out && y, "ipb_step: NULL pointer");
-  PLS_REQUIRE(out != U, "ipb_step: out must not alias U");
-  PLS_REQUIRE(j >= 0 && ldu >= j && ldo >= j && eta >= 0.0, "ipb_step: bad sizes");
-  PLS_REQUIRE(out_mode == 0 || out_mode == 1, "ipb_step: out_mode must be 0 or 1");
-  if (j == 0) return PLS_OK;
-  const size_t mj = align_up((size_t)basis->m * j * sizeof(double), 256);
-  const int64_t max_slabs = onb_max_slabs(basis->m, j, basis->n);
-  const size_t fixed = (size_t)(3 + max_slabs) * mj;
-  const int64_t min_rows = basis->n < 128 ? basis->n : 128;
-  if (!workspace ||
-      workspace_bytes < fixed + onb_energy_partial_bytes(min_rows, j) + (size_t)min_rows * j * sizeof(double))
-    return fail(PLS_ERR_WORKSPACE_TOO_SMALL, "ipb_step: workspace %zu bytes, need at least %zu", workspace_bytes,
-                pls_ipb_step_workspace_bytes(basis, j, 128));
-  char *w = static_cast<char *>(workspace);
-  double *V = reinterpret_cast<double *>(w), *xi = reinterpret_cast<double *>(w + mj);
-  double *e = reinterpret_cast<double *>(w + 2 * mj), *D = reinterpret_cast<double *>(w + 3 * mj);
-  const int64_t n_chunk = onb_pick_chunk(basis->n, workspace_bytes - fixed, j, min_rows);
-  double *vpart = reinterpret_cast<double *>(w + fixed);
-  double *Gbuf = reinterpret_cast<double *>(w + fixed + onb_energy_partial_bytes(n_chunk, j));
-  hipStream_t st = S(stream);
-  if (ipb_fast_path(basis, cost, force_generic) && ipb_whitened_ok(basis, cost)) {
-    // whitened route: S = Lc^-1 U -> dS (fused kernel, energy by-product) -> out = [U +] Lc dS
-    double *Sw = V, *Wd = xi, *epart = e;  // (m x j each; the partial rows of the energy fit: 2 cdiv(m, 128) <= m + 1)
-    NoiseP nz = make_noisep(noise, blocks);
-    const bool injected = nz.kind == PLS_NOISE_INJECTED;
-    const double *e_inj = injected ? nz.xi : nullptr;
-    const int64_t ld_inj = nz.ldxi;
-    if (injected) nz.kind = PLS_NOISE_NONE;  // (the injected noise is already coloured: it enters after the product with Lc)
-    if (basis->Pt && !energy_in && g_ipb_step_operator.load() != 0) {
-      // dS straight from U: Q S = Q Lc^-1 U = P U with P^T = Lc^-T Q in the descriptor (pls_ipb_build_step_operator), so
-      // the forward solve is folded into the operator -- two launches and 3 M^2 J flop per call instead of three and 4 M^2 J.
-      // (The energy by-product is a quadratic form in S, so a call that wants it keeps the route below.)
-      FastOp op = ipb_whitened_op(basis);
-      op.B = basis->Pt;
-      op.ldb = basis->ldpt;
-      rc = fast_step_launch(op, U, ldu, j, make_etap(eta, blocks), nz, Wd, j, 0, nullptr, nullptr, 0, st, "ipb_step");
-    } else {
-      const pls_chol_desc f = ipb_factor(basis);
-      rc = chol_forward_solve(&f, U, ldu, j, Sw, j, st);
-      if (rc) return rc;
-      rc = fast_step_launch(ipb_whitened_op(basis), Sw, j, j, make_etap(eta, blocks), nz, Wd, j, 0, energy_in, epart,
-                            2 * mj, st, "ipb_step", blocks ? blocks->energy_sums : nullptr, blocks ? blocks->energy_sync : nullptr);
-    }
-    if (rc) return rc;
-    rc = finish_sums16(blocks, energy_in, j, st);
-    if (rc) return rc;
-    EpiIpbFinish fin{out, ldo, U, ldu, out_mode, make_etap(eta, blocks), e_inj, ld_inj};
-    return launch_gemm_any(basis->LcT, basis->ldlct, Wd, j, basis->m, j, basis->m, fin, st, 0, 1,
-                           TriScratch{basis->tri_scratch, basis->tri_scratch_bytes});
-  }
-  // launch-bound problems (the reference's curve experiments build this basis with 10-100 inducing points and 50-100
-  // particles): the one-launch small-rank step after the solve and the coloured noise -- and those two in one launch of
-  // their own when the descriptor carries the inverse factor (csrc/ipb_prep.h): 2 launches per step instead of 8
-  const bool fast = ipb_fast_path(basis, cost, force_generic);
-  const bool one_launch = !fast && sr_step_route_for(basis->Kxz, basis->ldkxz, basis->m, basis->n, y, j) &&
-                          sr_step_fits(basis->m, basis->n, j, blocks, energy_in, workspace_bytes - 3 * mj);
-  bool coloured = false;  // the noise of this step already sits in e
-  if (one_launch && g_ipb_prep.load() != 0 && basis->m <= IPB_PREP_MAX_M && basis->Linv && basis->LinvT && solve_mode() != 0 &&
-      !(g_ipb_explicit_inverse.load() != 0 && basis->W)) {
-    const NoiseP nz0 = make_noisep(noise, blocks);
-    const int draw = nz0.kind == PLS_NOISE_PHILOX ? 1 : 0;
-    if (draw && !basis->LcT) return fail(PLS_ERR_INVALID_ARGUMENT, "ipb: Philox noise needs the Cholesky factor LcT");
-    const IpbPrepP pp{basis->LinvT, basis->ldlinvt, basis->Linv, basis->ldlinv, basis->LcT, basis->ldlct, U, ldu, V, j, e, j,
-                      (int)basis->m, j, draw, nz0};
-    rc = launch_ipb_prep(pp, st);
-    coloured = draw != 0;
+// whitened route: S = Lc^-1 U -> dS (fused kernel, energy by-product) -> out = [U +] Lc dS.  S, dS and the energy's partial
+// rows in V, xi and e (the partial rows take e and what follows: 2 cdiv(m, 128) <= m + 1 rows)
+static int ipb_whitened_route(const pls_ipb_desc *basis, const StepCall &c, const DriftLayout &L) {
+  char *w = static_cast<char *>(c.workspace);
+  double *Sw = reinterpret_cast<double *>(w), *Wd = reinterpret_cast<double *>(w + L.mj);
+  double *epart = reinterpret_cast<double *>(w + 2 * L.mj);
+  NoiseP nz = c.noisep();
+  const bool injected = nz.kind == PLS_NOISE_INJECTED;
+  const double *e_inj = injected ? nz.xi : nullptr;
+  const int64_t ld_inj = nz.ldxi;
+  if (injected) nz.kind = PLS_NOISE_NONE;  // (the injected noise is already coloured: it enters after the product with Lc)
+  int rc;
+  if (basis->Pt && !c.energy_in && g_ipb_step_operator.load() != 0) {
+    // dS straight from U: Q S = Q Lc^-1 U = P U with P^T = Lc^-T Q in the descriptor (pls_ipb_build_step_operator), so
+    // the forward solve is folded into the operator -- two launches and 3 M^2 J flop per call instead of three and 4 M^2 J.
+    // (The energy by-product is a quadratic form in S, so a call that wants it keeps the route below.)
+    FastOp op = ipb_whitened_op(basis);
+    op.B = basis->Pt;
+    op.ldb = basis->ldpt;
+    rc = fast_step_launch(op, c.U, c.ldu, c.j, c.etap(), nz, Wd, c.j, 0, nullptr, nullptr, 0, c.st, "ipb_step");
   } else {
-    rc = ipb_apply_kinv(basis, U, ldu, j, V, stream, xi);  // (xi is free until the noise is drawn)
+    const pls_chol_desc f = ipb_factor(basis);
+    rc = chol_forward_solve(&f, c.U, c.ldu, c.j, Sw, c.j, c.st);
+    if (rc) return rc;
+    rc = fast_step_launch(ipb_whitened_op(basis), Sw, c.j, c.j, c.etap(), nz, Wd, c.j, 0, c.energy_in, epart, 2 * L.mj, c.st,
+                          "ipb_step", c.energy_sums(), c.energy_sync());
   }
   if (rc) return rc;
-  if (ipb_fast_path(basis, cost, force_generic)) {
-    const double inv_noise = 1.0 / cost->p[0];
-    rc = pls_gemm_tn(basis->B, basis->ldb, V, j, D, j, basis->m, j, basis->m, inv_noise, 0.0, stream);  // B symmetric
+  rc = finish_sums16(c.blocks, c.energy_in, c.j, c.st);
+  if (rc) return rc;
+  EpiIpbFinish fin{c.out, c.ldo, c.U, c.ldu, c.out_mode, c.etap(), e_inj, ld_inj};
+  return launch_gemm_any(basis->LcT, basis->ldlct, Wd, c.j, basis->m, c.j, basis->m, fin, c.st, 0, 1,
+                         TriScratch{basis->tri_scratch, basis->tri_scratch_bytes});
+}
+
+// Gaussian/identity route: V = K^-1 U, D = B V / sigma2, the energies from both, then the update
+static int ipb_fast_route(const pls_ipb_desc *basis, const StepCall &c, const DriftLayout &L) {
+  char *w = static_cast<char *>(c.workspace);
+  double *V = reinterpret_cast<double *>(w), *xi = reinterpret_cast<double *>(w + L.mj);
+  double *e = reinterpret_cast<double *>(w + 2 * L.mj), *D = reinterpret_cast<double *>(w + L.d_off);
+  int rc = ipb_apply_kinv(basis, c.U, c.ldu, c.j, V, c.st, xi);  // (xi is free until the noise is drawn)
+  if (rc) return rc;
+  const double inv_noise = 1.0 / c.cost->p[0];
+  rc = pls_gemm_tn(basis->B, basis->ldb, V, c.j, D, c.j, basis->m, c.j, basis->m, inv_noise, 0.0, c.st);  // B symmetric
+  if (rc) return rc;
+  if (c.energy_in) {
+    hipLaunchKernelGGL(ipb_gaussian_energy_kernel, dim3((unsigned)cdiv(c.j, 64)), dim3(256), 0, c.st, V, c.j, D, c.j, basis->c,
+                       basis->m, c.j, inv_noise, 0.5 * (double)basis->m, c.energy_in);
+    rc = check_launch("ipb_gaussian_energy");
     if (rc) return rc;
-    if (energy_in) {
-      hipLaunchKernelGGL(ipb_gaussian_energy_kernel, dim3((unsigned)cdiv(j, 64)), dim3(256), 0, st, V, j, D, j, basis->c,
-                         basis->m, j, inv_noise, 0.5 * (double)basis->m, energy_in);
-      rc = check_launch("ipb_gaussian_energy");
-      if (rc) return rc;
-    }
-    rc = ipb_finish(basis, U, ldu, D, 1, (int64_t)0, V, j, eta, noise, out, ldo, out_mode, xi, e, st, basis->c, inv_noise,
-                    blocks);
-    if (rc) return rc;
-    return finish_energy_sums(blocks, energy_in, j, st);
   }
-  if (one_launch) {
-    NoiseP nz = make_noisep(noise, blocks);
-    if (coloured) {
+  rc = ipb_finish(basis, c.U, c.ldu, D, 1, (int64_t)0, V, c.j, c.eta, c.noise, c.out, c.ldo, c.out_mode, xi, e, c.st, basis->c,
+                  inv_noise, c.blocks);
+  if (rc) return rc;
+  return finish_energy_sums(c.blocks, c.energy_in, c.j, c.st);
+}
+
+// launch-bound problems (the reference's curve experiments build this basis with 10-100 inducing points and 50-100
+// particles): the one-launch small-rank step after the solve and the coloured noise -- and those two in one launch of
+// their own when the descriptor carries the inverse factor (csrc/ipb_prep.h): 2 launches per step instead of 8
+static int ipb_one_launch_route(const pls_ipb_desc *basis, const StepCall &c, const DriftLayout &L, const SrStepLayout &sl) {
+  char *w = static_cast<char *>(c.workspace);
+  double *V = reinterpret_cast<double *>(w), *xi = reinterpret_cast<double *>(w + L.mj);
+  double *e = reinterpret_cast<double *>(w + 2 * L.mj);
+  NoiseP nz = c.noisep();
+  int rc;
+  if (g_ipb_prep.load() != 0 && basis->m <= IPB_PREP_MAX_M && basis->Linv && basis->LinvT && solve_mode() != 0 &&
+      !(g_ipb_explicit_inverse.load() != 0 && basis->W)) {
+    const int draw = nz.kind == PLS_NOISE_PHILOX ? 1 : 0;
+    if (draw && !basis->LcT) return fail(PLS_ERR_INVALID_ARGUMENT, "ipb: Philox noise needs the Cholesky factor LcT");
+    const IpbPrepP pp{basis->LinvT, basis->ldlinvt, basis->Linv, basis->ldlinv, basis->LcT, basis->ldlct, c.U, c.ldu, V, c.j, e,
+                      c.j, (int)basis->m, c.j, draw, nz};
+    rc = launch_ipb_prep(pp, c.st);
+    if (rc) return rc;
+    if (draw) {  // the noise of this step already sits in e
       nz.kind = PLS_NOISE_INJECTED;
       nz.xi = e;
-      nz.ldxi = j;
-    } else {
-      rc = ipb_colour_noise(basis, nz, j, xi, e, st);
-      if (rc) return rc;
+      nz.ldxi = c.j;
     }
-    bool taken = false;
-    const SrStepOperands ops{basis->Kxz, basis->ldkxz, basis->m, basis->n, V, j, U, ldu, nullptr, (double)basis->m};
-    rc = sr_step_launch(ops, make_costp(cost), y, j, make_etap(eta, blocks), nz, out, ldo, out_mode, energy_in, blocks, D,
-                        workspace_bytes - 3 * mj, st, &taken);
+  } else {
+    rc = ipb_apply_kinv(basis, c.U, c.ldu, c.j, V, c.st, xi);  // (xi is free until the noise is drawn)
     if (rc) return rc;
-    return taken ? PLS_OK : fail(PLS_ERR_WORKSPACE_TOO_SMALL, "ipb_step: the one-launch step refused a workspace it was sized for");
+    rc = ipb_colour_noise(basis, nz, c.j, xi, e, c.st);
+    if (rc) return rc;
   }
+  return sr_step_launch(SrStepOperands{basis->Kxz, basis->ldkxz, basis->m, basis->n, V, c.j, c.U, c.ldu, nullptr, (double)basis->m},
+                        sl, c, nz);
+}
+
+// the general route: V = K^-1 U, the drift streamed over the N chunks the workspace holds (drift_plan), then the update
+static int ipb_general_route(const pls_ipb_desc *basis, const StepCall &c, const DriftLayout &L) {
+  char *w = static_cast<char *>(c.workspace);
+  double *V = reinterpret_cast<double *>(w), *xi = reinterpret_cast<double *>(w + L.mj);
+  double *e = reinterpret_cast<double *>(w + 2 * L.mj), *D = reinterpret_cast<double *>(w + L.d_off);
+  const int64_t slab_stride = (int64_t)(L.mj / sizeof(double));
+  int rc = ipb_apply_kinv(basis, c.U, c.ldu, c.j, V, c.st, xi);  // (xi is free until the noise is drawn)
+  if (rc) return rc;
   EnergySink sink;
-  if (energy_in) {  // e_j = cost_j(F(U)) + (M/2) ||K^-1 U_j||^2 of the INPUT particles (inducing_point.py:95-115)
-    sink.partial = vpart;
-    sink.rows_cap = energy_partial_rows(n_chunk);
-    sink.e = energy_in;
+  if (c.energy_in) {  // e_j = cost_j(F(U)) + (M/2) ||K^-1 U_j||^2 of the INPUT particles (inducing_point.py:95-115)
+    sink.partial = reinterpret_cast<double *>(w + L.part_off);
+    sink.rows_cap = L.part_rows;
+    sink.e = c.energy_in;
     sink.prior_kind = 2;
     sink.P = V;
-    sink.ldp = j;
+    sink.ldp = c.j;
     sink.m = basis->m;
     sink.scale = 0.5 * (double)basis->m;
   }
   int64_t nslab = 1;
-  rc = stream_drift(basis->Kzx, basis->ldkzx, basis->Kxz, basis->ldkxz, basis->m, basis->n, V, j, j, make_costp(cost), y,
-                    D, j, max_slabs, (int64_t)(mj / sizeof(double)), &nslab, Gbuf, n_chunk, st, energy_in ? &sink : nullptr);
+  rc = stream_drift(basis->Kzx, basis->ldkzx, basis->Kxz, basis->ldkxz, basis->m, basis->n, V, c.j, c.j, make_costp(c.cost), c.y,
+                    D, c.j, L.slabs, slab_stride, &nslab, reinterpret_cast<double *>(w + L.g_off), L.n_chunk, c.st,
+                    c.energy_in ? &sink : nullptr);
   if (rc) return rc;
-  rc = ipb_finish(basis, U, ldu, D, (int)nslab, (int64_t)(mj / sizeof(double)), V, j, eta, noise, out, ldo, out_mode, xi, e,
-                  st, nullptr, 0.0, blocks);
+  rc = ipb_finish(basis, c.U, c.ldu, D, (int)nslab, slab_stride, V, c.j, c.eta, c.noise, c.out, c.ldo, c.out_mode, xi, e, c.st,
+                  nullptr, 0.0, c.blocks);
   if (rc) return rc;
-  return finish_energy_sums(blocks, energy_in, j, st);
+  return finish_energy_sums(c.blocks, c.energy_in, c.j, c.st);
+}
+
+static int ipb_step_impl(const pls_ipb_desc *basis, const StepCall &c, int32_t force_generic) {
+  int rc = validate_ipb(basis);
+  if (!rc) rc = validate_step("ipb_step", c, false);
+  if (!rc) rc = validate_step_call("ipb_step", c, true);
+  if (rc) return rc;
+  if (c.j == 0) return PLS_OK;
+  // every route's buffers lie where the general route's layout puts them, which the workspace must hold (128-row chunks at least)
+  const DriftLayout L = drift_plan(IPB_LEAD, basis->m, basis->n, c.j, c.workspace_bytes);
+  if (!c.workspace || L.total > c.workspace_bytes)
+    return fail(PLS_ERR_WORKSPACE_TOO_SMALL, "ipb_step: workspace %zu bytes, need at least %zu", c.workspace_bytes,
+                pls_ipb_step_workspace_bytes(basis, c.j, 128));
+  StepRoute route = StepRoute::General;
+  SrStepLayout sl{};
+  if (gaussian_fast_path(basis->B, basis->c, c.cost, force_generic)) {
+    route = ipb_whitened_ok(basis, c.cost) ? StepRoute::Whitened : StepRoute::Fast;
+  } else if (sr_step_route_for(basis->Kxz, basis->ldkxz, basis->m, basis->n, c.y, c.j)) {
+    sl = sr_step_plan(IPB_LEAD, basis->m, basis->n, c);
+    if (ws_holds(sl.total, c.workspace, c.workspace_bytes)) route = StepRoute::OneLaunch;
+  }
+  switch (route) {
+    case StepRoute::Whitened:
+      return ipb_whitened_route(basis, c, L);
+    case StepRoute::Fast:
+      return ipb_fast_route(basis, c, L);
+    case StepRoute::OneLaunch:
+      return ipb_one_launch_route(basis, c, L, sl);
+    default:
+      return ipb_general_route(basis, c, L);
+  }
 }
 
 int pls_ipb_step(const pls_ipb_desc *basis, const pls_cost_desc *cost, const double *y, double *U, int64_t ldu, int64_t j,
                  double eta, const pls_noise_desc *noise, double *out, int64_t ldo, int32_t out_mode, int32_t force_generic,
                  double *energy_in, void *workspace, size_t workspace_bytes, void *stream) {
-  return ipb_step_impl(basis, cost, y, U, ldu, j, eta, nullptr, noise, out, ldo, out_mode, force_generic, energy_in, workspace,
-                       workspace_bytes, stream);
+  return ipb_step_impl(basis, StepCall{cost, y, U, ldu, j, eta, nullptr, noise, out, ldo, out_mode, energy_in, workspace,
+                                       workspace_bytes, S(stream)}, force_generic);
 }
 
 int pls_ipb_step_blocks(const pls_ipb_desc *basis, const pls_cost_desc *cost, const double *y, double *U, int64_t ldu,
@@ -2822,17 +2767,16 @@ int pls_ipb_step_blocks(const pls_ipb_desc *basis, const pls_cost_desc *cost, co
                         int32_t out_mode, int32_t force_generic, double *energy_in, void *workspace,
                         size_t workspace_bytes, void *stream) {
   PLS_REQUIRE(blocks != nullptr, "ipb_step_blocks: block descriptor is NULL");
-  return ipb_step_impl(basis, cost, y, U, ldu, j, 0.0, blocks, noise, out, ldo, out_mode, force_generic, energy_in, workspace,
-                       workspace_bytes, stream);
+  return ipb_step_impl(basis, StepCall{cost, y, U, ldu, j, 0.0, blocks, noise, out, ldo, out_mode, energy_in, workspace,
+                                       workspace_bytes, S(stream)}, force_generic);
 }
+
+// ---- inducing-point basis: the energy ---------------------------------------------------------------------------------
 
 size_t pls_ipb_energy_workspace_bytes(const pls_ipb_desc *basis, int64_t j, int64_t n_chunk) {
   if (!basis || j <= 0) return 0;
   if (n_chunk <= 0 || n_chunk > basis->n) n_chunk = basis->n;
-  const int64_t parts = cdiv(n_chunk, 64) < 2 ? 2 : cdiv(n_chunk, 64);
-  const size_t mj = align_up((size_t)basis->m * j * sizeof(double), 256);
-  const size_t generic = mj + (size_t)parts * j * sizeof(double);
-  return generic > 2 * mj ? generic : 2 * mj;  // (the Gaussian fast path keeps V and B V)
+  return energy_layout(1, basis->m, j, n_chunk).total;
 }
 
 int pls_ipb_energy(const pls_ipb_desc *basis, const pls_cost_desc *cost, const double *y, const double *U, int64_t ldu,
@@ -2843,37 +2787,33 @@ int pls_ipb_energy(const pls_ipb_desc *basis, const pls_cost_desc *cost, const d
   if (rc) return rc;
   PLS_REQUIRE(U && e && y && j >= 0 && ldu >= j, "ipb_energy: bad arguments");
   if (j == 0) return PLS_OK;
-  const size_t mj = align_up((size_t)basis->m * j * sizeof(double), 256);
-  if (!workspace || workspace_bytes < mj + 2 * (size_t)j * sizeof(double))
+  const EnergyLayout L = energy_plan(1, basis->m, basis->n, j, workspace_bytes);
+  if (!workspace || L.part_rows < 2)
     return fail(PLS_ERR_WORKSPACE_TOO_SMALL, "ipb_energy: workspace %zu bytes too small", workspace_bytes);
   double *V = static_cast<double *>(workspace);
-  if (ipb_fast_path(basis, cost, force_generic)) {
-    if (workspace_bytes < 2 * mj) return fail(PLS_ERR_WORKSPACE_TOO_SMALL, "ipb_energy: workspace %zu < %zu bytes", workspace_bytes, 2 * mj);
-    double *D = reinterpret_cast<double *>(static_cast<char *>(workspace) + mj);
+  double *partial = reinterpret_cast<double *>(static_cast<char *>(workspace) + L.part_off);  // (B V on the fast path)
+  if (gaussian_fast_path(basis->B, basis->c, cost, force_generic)) {
+    if (workspace_bytes < L.gauss_bytes)
+      return fail(PLS_ERR_WORKSPACE_TOO_SMALL, "ipb_energy: workspace %zu < %zu bytes", workspace_bytes, L.gauss_bytes);
     const double inv_noise = 1.0 / cost->p[0];
     if (ipb_whitened_ok(basis, cost)) {  // S = Lc^-1 U, then the quadratic form in whitened coordinates
       const pls_chol_desc f = ipb_factor(basis);
       rc = chol_forward_solve(&f, U, ldu, j, V, j, S(stream));
       if (rc) return rc;
-      return fast_energy_launch(ipb_whitened_op(basis), V, j, j, e, D, workspace_bytes - mj, S(stream), "ipb_energy");
+      return fast_energy_launch(ipb_whitened_op(basis), V, j, j, e, partial, workspace_bytes - L.part_off, S(stream), "ipb_energy");
     }
-    rc = ipb_apply_kinv(basis, U, ldu, j, V, stream, D);
+    rc = ipb_apply_kinv(basis, U, ldu, j, V, stream, partial);
     if (rc) return rc;
-    rc = pls_gemm_tn(basis->B, basis->ldb, V, j, D, j, basis->m, j, basis->m, inv_noise, 0.0, stream);
+    rc = pls_gemm_tn(basis->B, basis->ldb, V, j, partial, j, basis->m, j, basis->m, inv_noise, 0.0, stream);
     if (rc) return rc;
-    hipLaunchKernelGGL(ipb_gaussian_energy_kernel, dim3((unsigned)cdiv(j, 64)), dim3(256), 0, S(stream), V, j, D, j, basis->c,
+    hipLaunchKernelGGL(ipb_gaussian_energy_kernel, dim3((unsigned)cdiv(j, 64)), dim3(256), 0, S(stream), V, j, partial, j, basis->c,
                        basis->m, j, inv_noise, 0.5 * (double)basis->m, e);
     return check_launch("ipb_gaussian_energy");
   }
-  double *partial = reinterpret_cast<double *>(static_cast<char *>(workspace) + mj);
-  const int64_t max_parts = (int64_t)((workspace_bytes - mj) / ((size_t)j * sizeof(double)));
-  int64_t n_chunk = max_parts * 64;
-  if (n_chunk > basis->n) n_chunk = basis->n;
-  else n_chunk = n_chunk / 128 * 128;
   rc = ipb_apply_kinv(basis, U, ldu, j, V, stream);
   if (rc) return rc;
   return stream_cost(basis->Kzx, basis->ldkzx, basis->Kxz, basis->ldkxz, basis->m, basis->n, V, j, j, make_costp(cost), y,
-                     partial, max_parts, n_chunk, e, 2, V, j, basis->m, nullptr, 0.5 * (double)basis->m, S(stream));
+                     partial, L.part_rows, L.n_chunk, e, 2, V, j, basis->m, nullptr, 0.5 * (double)basis->m, S(stream));
 }
 
 int pls_ipb_prior_energy(const pls_ipb_desc *basis, const double *U, int64_t ldu, int64_t j, const double *cost,
@@ -2967,52 +2907,39 @@ int pls_ipb_unwhiten(const pls_ipb_desc *basis, const double *Sw, int64_t lds, i
 
 size_t pls_ipb_whitened_workspace_bytes(const pls_ipb_desc *basis, int64_t j) {
   if (!basis || j <= 0) return 0;
-  return (size_t)(2 * cdiv(basis->m, 128)) * j * sizeof(double);
+  return gaussian_step_partial_bytes(basis->m, j);
 }
 
-static int ipb_whitened_step_impl(const pls_ipb_desc *basis, const pls_cost_desc *cost, const double *Sw, int64_t lds, int64_t j,
-                                  double eta, const pls_block_desc *blocks, const pls_noise_desc *noise, double *out, int64_t ldo,
-                                  int32_t out_mode, double *energy_in, void *workspace, size_t workspace_bytes, void *stream) {
+static int ipb_whitened_step_impl(const pls_ipb_desc *basis, const StepCall &c) {
   int rc = validate_ipb(basis);
+  if (!rc) rc = validate_step("ipb_whitened_step", c, true);
   if (rc) return rc;
-  rc = validate_cost(cost);
-  if (rc) return rc;
-  rc = validate_noise(noise, basis->m, j);
-  if (rc) return rc;
-  rc = validate_blocks(blocks, j);
-  if (rc) return rc;
-  PLS_REQUIRE(cost->cost == PLS_COST_GAUSSIAN && cost->link == PLS_LINK_IDENTITY, "ipb_whitened_step: Gaussian cost with the identity link only");
-  PLS_REQUIRE(basis->Q && basis->ct && basis->q_inv_noise == 1.0 / cost->p[0],
+  PLS_REQUIRE(c.cost->cost == PLS_COST_GAUSSIAN && c.cost->link == PLS_LINK_IDENTITY, "ipb_whitened_step: Gaussian cost with the identity link only");
+  PLS_REQUIRE(basis->Q && basis->ct && basis->q_inv_noise == 1.0 / c.cost->p[0],
               "ipb_whitened_step: the descriptor's Q / ct were not built for this observation noise (pls_ipb_build_whitened)");
-  rc = validate_lag(blocks);
-  if (rc) return rc;
-  if (blocks && blocks->energy_flush) {
-    PLS_REQUIRE(Sw && j > 0 && lds >= j, "ipb_whitened_step: energy_flush needs the particle matrix of the step calls");
-    return fast_step_launch(ipb_whitened_op(basis), Sw, lds, j, make_etap(eta, blocks), make_noisep(noise, blocks), nullptr, 0, 0,
-                            nullptr, nullptr, 0, S(stream), "ipb_whitened_step", nullptr, nullptr, make_lag(blocks));
+  if (c.blocks && c.blocks->energy_flush) {
+    PLS_REQUIRE(c.U && c.j > 0 && c.ldu >= c.j, "ipb_whitened_step: energy_flush needs the particle matrix of the step calls");
+    return fast_step_launch(ipb_whitened_op(basis), c.U, c.ldu, c.j, c.etap(), c.noisep(), nullptr, 0, 0, nullptr, nullptr, 0, c.st,
+                            "ipb_whitened_step", nullptr, nullptr, make_lag(c.blocks));
   }
-  PLS_REQUIRE(Sw && out && out != Sw && j >= 0 && lds >= j && ldo >= j && eta >= 0.0, "ipb_whitened_step: bad arguments");
-  PLS_REQUIRE(out_mode == 0 || out_mode == 1, "ipb_whitened_step: out_mode must be 0 or 1");
-  if (j == 0) return PLS_OK;
-  rc = fast_step_launch(ipb_whitened_op(basis), Sw, lds, j, make_etap(eta, blocks), make_noisep(noise, blocks), out, ldo,
-                        out_mode, energy_in, workspace, workspace_bytes, S(stream), "ipb_whitened_step",
-                        blocks ? blocks->energy_sums : nullptr, blocks ? blocks->energy_sync : nullptr, make_lag(blocks));
-  return rc ? rc : finish_sums16(blocks, energy_in, j, S(stream));
+  if ((rc = validate_step_call("ipb_whitened_step", c, false))) return rc;
+  if (c.j == 0) return PLS_OK;
+  return fast_step(ipb_whitened_op(basis), c, "ipb_whitened_step");
 }
 
 int pls_ipb_whitened_step(const pls_ipb_desc *basis, const pls_cost_desc *cost, const double *Sw, int64_t lds, int64_t j,
                           double eta, const pls_noise_desc *noise, double *out, int64_t ldo, int32_t out_mode, double *energy_in,
                           void *workspace, size_t workspace_bytes, void *stream) {
-  return ipb_whitened_step_impl(basis, cost, Sw, lds, j, eta, nullptr, noise, out, ldo, out_mode, energy_in, workspace,
-                                workspace_bytes, stream);
+  return ipb_whitened_step_impl(basis, StepCall{cost, nullptr, Sw, lds, j, eta, nullptr, noise, out, ldo, out_mode, energy_in,
+                                                workspace, workspace_bytes, S(stream)});
 }
 
 int pls_ipb_whitened_step_blocks(const pls_ipb_desc *basis, const pls_cost_desc *cost, const double *Sw, int64_t lds, int64_t j,
                                  const pls_block_desc *blocks, const pls_noise_desc *noise, double *out, int64_t ldo,
                                  int32_t out_mode, double *energy_in, void *workspace, size_t workspace_bytes, void *stream) {
   PLS_REQUIRE(blocks != nullptr, "ipb_whitened_step_blocks: block descriptor is NULL");
-  return ipb_whitened_step_impl(basis, cost, Sw, lds, j, 0.0, blocks, noise, out, ldo, out_mode, energy_in, workspace,
-                                workspace_bytes, stream);
+  return ipb_whitened_step_impl(basis, StepCall{cost, nullptr, Sw, lds, j, 0.0, blocks, noise, out, ldo, out_mode, energy_in,
+                                                workspace, workspace_bytes, S(stream)});
 }
 
 // ---- whitened coordinates for every cost: the prior as rows of the forward operand (pls_ipb_desc.Awa) ------------------------
@@ -3034,7 +2961,7 @@ int pls_ipb_build_whitened_operand(const pls_ipb_desc *basis, double *Awa, int64
 static bool ipb_whitened_generic_ok(const pls_ipb_desc *b, const double *y, int64_t j) {
   if (!b->Awa || b->ldawa < b->m || g_small_rank_step.load() == 0) return false;
   if (!small_rank_ok(b->Awa, b->ldawa, b->m) || (reinterpret_cast<uintptr_t>(y) & 15)) return false;
-  return j <= 4096 && 4.0 * (double)(b->n + b->m) * (double)b->m * (double)j <= 8e9;  // (sr_step_route_for's launch-bound window)
+  return launch_bound(b->n + b->m, b->m, j);  // (under every option: see sr_step_route_for)
 }
 
 int pls_ipb_whitened_generic_applies(const pls_ipb_desc *basis, const double *y, int64_t j) {
@@ -3044,39 +2971,29 @@ int pls_ipb_whitened_generic_applies(const pls_ipb_desc *basis, const double *y,
 
 size_t pls_ipb_whitened_generic_workspace_bytes(const pls_ipb_desc *basis, int64_t j) {
   if (!basis || j <= 0) return 0;
-  return sr_step_workspace_bytes(basis->m, j, basis->n + basis->m);
+  return sr_step_query_bytes(0, basis->m, basis->n + basis->m, j);
 }
 
 int pls_ipb_whitened_generic_step(const pls_ipb_desc *basis, const pls_cost_desc *cost, const double *y, const double *Sw,
                                   int64_t lds, int64_t j, double eta, const pls_block_desc *blocks, const pls_noise_desc *noise,
                                   double *out, int64_t ldo, int32_t out_mode, double *energy_in, void *workspace,
                                   size_t workspace_bytes, void *stream) {
+  const StepCall c{cost, y, Sw, lds, j, eta, blocks, noise, out, ldo, out_mode, energy_in, workspace, workspace_bytes, S(stream)};
   int rc = validate_ipb(basis);
+  if (!rc) rc = validate_step("ipb_whitened_generic_step", c, false);
+  if (!rc) rc = validate_step_call("ipb_whitened_generic_step", c, true);
   if (rc) return rc;
-  rc = validate_cost(cost);
-  if (rc) return rc;
-  rc = validate_noise(noise, basis->m, j);
-  if (rc) return rc;
-  rc = validate_blocks(blocks, j);
-  if (rc) return rc;
-  PLS_REQUIRE(!blocks || (!blocks->energy_partials && !blocks->energy_partials_prev && !blocks->energy_flush),
-              "ipb_whitened_generic_step: lagged energies exist on the Gaussian/identity routes only");
-  PLS_REQUIRE(y && Sw && out && out != Sw && j >= 0 && lds >= j && ldo >= j && eta >= 0.0, "ipb_whitened_generic_step: bad arguments");
-  PLS_REQUIRE(out_mode == 0 || out_mode == 1, "ipb_whitened_generic_step: out_mode must be 0 or 1");
   if (j == 0) return PLS_OK;
   if (!ipb_whitened_generic_ok(basis, y, j))
     return fail(PLS_ERR_INVALID_ARGUMENT, "ipb_whitened_generic_step: needs pls_ipb_desc.Awa (pls_ipb_build_whitened_operand), at most 128 "
                 "inducing points, 16-byte aligned targets and a launch-bound problem (pls_ipb_whitened_generic_applies)");
-  if (!sr_step_fits(basis->m, basis->n + basis->m, j, blocks, energy_in, workspace ? workspace_bytes : 0))
+  const SrStepLayout sl = sr_step_plan(0, basis->m, basis->n + basis->m, c);
+  if (!ws_holds(sl.total, workspace, workspace_bytes))
     return fail(PLS_ERR_WORKSPACE_TOO_SMALL, "ipb_whitened_generic_step: workspace %zu bytes, need %zu", workspace_bytes,
                 pls_ipb_whitened_generic_workspace_bytes(basis, j));
   SrStepOperands ops{basis->Awa, basis->ldawa, basis->m, basis->n + basis->m, Sw, lds, nullptr, 0, nullptr, 0.0};
   ops.n_data = basis->n;
-  bool taken = false;
-  rc = sr_step_launch(ops, make_costp(cost), y, j, make_etap(eta, blocks), make_noisep(noise, blocks), out, ldo, out_mode, energy_in,
-                      blocks, workspace, workspace ? workspace_bytes : 0, S(stream), &taken);
-  if (rc) return rc;
-  return taken ? PLS_OK : fail(PLS_ERR_WORKSPACE_TOO_SMALL, "ipb_whitened_generic_step: the one-launch step refused a workspace it was sized for");
+  return sr_step_launch(ops, sl, c, c.noisep());
 }
 
 int pls_ipb_whitened_energy(const pls_ipb_desc *basis, const pls_cost_desc *cost, const double *Sw, int64_t lds, int64_t j,

@@ -138,12 +138,6 @@ static inline int64_t small_rank_step_splits(int64_t J, int64_t N, int K, int64_
 }
 
 static inline size_t small_rank_step_sync_words(int64_t J) { return (size_t)((J + 15) / 16 + (J + 255) / 256); }
-static inline size_t small_rank_step_slab_bytes(int64_t J, int64_t N, int K) {
-  int64_t rows;
-  const int64_t ns = small_rank_step_splits(J, N, K, &rows);
-  if (ns <= 1) return 0;
-  return (size_t)((J + 15) / 16) * ns * ((size_t)K + 1) * 16 * sizeof(double);
-}
 
 // dU of one element (langevin_update_kernel's formula), evaluated without contraction: the same bits with and without the
 // energy by-product, whatever else the instantiation computes next to it

@@ -572,3 +572,99 @@ int main() {
     assert plans[(100, 1032, 32)] == (9, 128)  # 1000 data rows + 32 prior rows: one short slab more, not a third round for all
     assert plans[(512, 4096, 128)] == (8, 512)
     assert plans[(512, 4224, 128)] == (8, 576)  # (nine slabs would be 288 workgroups)
+
+
+def test_workspace_layouts_of_the_step_plan(tmp_path):
+    """csrc/step_plan.h: the workspace layouts the size queries and the step / energy entries share, compiled from the header
+    and checked over a grid of sizes -- every region 256-byte aligned, the regions disjoint and inside the total; the one-launch
+    step's query is its layout (slabs, then counters); every workspace at least the query at 128-row chunks gets a chunk of at
+    least min(n, 128) rows whose layout fits it, the largest such; the query at n rows gets all n rows in one chunk."""
+    import os
+    import shutil
+    import subprocess
+
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    if not os.path.exists(hipcc):
+        pytest.skip("hipcc not found")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    src = tmp_path / "layouts.cpp"
+    src.write_text('''#include <cstdio>
+#include <cstdint>
+#include <hip/hip_runtime.h>
+#include "step_plan.h"
+using namespace plship;
+int main() {
+  const int64_t ranks[] = {1, 10, 32, 89, 128, 129, 200, 1024};
+  const int64_t ns[] = {1, 64, 100, 1000, 4096, 20000, 100000};
+  const int64_t js[] = {1, 16, 64, 100, 512, 1024, 8192};
+  for (int64_t mk : ranks) for (int64_t n : ns) for (int64_t j : js) {
+    for (int lead : {0, 3}) {
+      if (mk <= 128) {
+        const SrStepLayout s = sr_step_layout(lead, mk, n, j, true, false);
+        printf("sr %d %ld %ld %ld %ld %ld %zu %zu %zu %zu %zu %zu\\n", lead, (long)mk, (long)n, (long)j, (long)s.ns, (long)s.rows,
+               mj_bytes(mk, j), s.slab_off, s.slab_bytes, s.sync_off, s.sync_bytes, sr_step_query_bytes(lead, mk, n, j));
+      }
+      const int64_t c128 = n < 128 ? n : 128;
+      for (int64_t c : {c128, n}) {
+        const DriftLayout d = drift_layout(lead, mk, n, j, c);
+        printf("dl %d %ld %ld %ld %ld %zu %zu %zu %zu %zu\\n", lead, (long)mk, (long)n, (long)j, (long)c, d.mj, d.d_off, d.part_off,
+               d.g_off, d.total);
+      }
+      const size_t q128 = drift_layout(lead, mk, n, j, c128).total, qn = drift_layout(lead, mk, n, j, n).total;
+      for (size_t w : {q128, q128 + 1, q128 + 4096, (q128 + qn) / 2, qn > q128 ? qn - 1 : qn, qn, 3 * qn}) {
+        const DriftLayout d = drift_plan(lead, mk, n, j, w);
+        const size_t next = d.n_chunk < n ? drift_layout(lead, mk, n, j, d.n_chunk + 128 < n ? d.n_chunk + 128 : n).total : 0;
+        printf("dp %d %ld %ld %ld %zu %zu %zu %ld %zu %zu\\n", lead, (long)mk, (long)n, (long)j, w, q128, qn, (long)d.n_chunk,
+               d.total, next);
+      }
+    }
+    for (int lead : {0, 1}) for (int64_t c : {n < 128 ? n : (int64_t)128, n}) {
+      const EnergyLayout q = energy_layout(lead, mk, j, c);
+      const EnergyLayout p = energy_plan(lead, mk, n, j, q.total);
+      printf("en %d %ld %ld %ld %ld %zu %zu %zu %ld %ld %zu\\n", lead, (long)mk, (long)n, (long)j, (long)c, mj_bytes(mk, j),
+             q.part_off, q.total, (long)p.part_rows, (long)p.n_chunk, p.gauss_bytes);
+    }
+  }
+  return 0;
+}
+''')
+    exe = tmp_path / "layouts"
+    subprocess.run([hipcc, "-std=c++17", "--offload-arch=gfx950", "-I", os.path.join(root, "projected-langevin-sampling_amd", "csrc"),
+                    "-o", str(exe), str(src)], check=True, capture_output=True, timeout=300)
+    out = subprocess.run([str(exe)], check=True, capture_output=True, text=True, timeout=60).stdout
+
+    def al(*offsets):
+        return all(o % 256 == 0 for o in offsets)
+
+    seen = {"sr": 0, "dl": 0, "dp": 0, "en": 0}
+    for line in out.splitlines():
+        tag, *v = line.split()
+        v = [int(x) for x in v]
+        seen[tag] += 1
+        if tag == "sr":
+            lead, mk, n, j, ns, rows, mj, slab_off, slab_bytes, sync_off, sync_bytes, query = v
+            assert ns >= 1 and ns * rows >= n, line
+            want = 0 if ns == 1 else -(-((j + 15) // 16) * ns * (mk + 1) * 16 * 8 // 256) * 256
+            assert slab_bytes == want and al(slab_off, slab_bytes, sync_off), line
+            assert slab_off == lead * mj and sync_off == slab_off + slab_bytes, f"overlapping regions: {line}"
+            assert query == sync_off + -(-sync_bytes // 256) * 256, f"the query is not the layout: {line}"
+            assert query - slab_off - -(-sync_bytes // 256) * 256 == slab_bytes, line
+        elif tag == "dl":
+            lead, mk, n, j, c, mj, d_off, part_off, g_off, total = v
+            assert al(mj, d_off, part_off, g_off), line
+            assert d_off == lead * mj and part_off >= d_off + mj and g_off > part_off and total == g_off + c * j * 8, line
+        elif tag == "dp":
+            lead, mk, n, j, w, q128, qn, chunk, total, nxt = v
+            assert chunk >= min(n, 128) and total <= w, f"the picked chunk does not fit: {line}"
+            assert chunk == n or chunk % 128 == 0, line
+            assert chunk == n or nxt > w, f"a larger chunk would fit: {line}"
+            if w >= qn:
+                assert chunk == n, f"the query at n rows does not give one chunk: {line}"
+        else:
+            lead, mk, n, j, c, mj, part_off, total, part_rows, chunk, gauss = v
+            assert al(part_off) and part_off == lead * mj, line
+            assert part_rows >= max(2, -(-c // 64)) and part_off + part_rows * j * 8 <= total and gauss <= total, line
+            assert chunk >= min(n, 128) and (chunk == n or chunk % 128 == 0), line
+            if c == n:
+                assert chunk == n, line
+    assert seen["sr"] > 0 and seen["dl"] > 0 and seen["dp"] > 0 and seen["en"] > 0
