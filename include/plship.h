@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define PLSHIP_ABI_VERSION 5
+#define PLSHIP_ABI_VERSION 6
 
 typedef enum {
   PLS_OK = 0,
@@ -325,7 +325,13 @@ typedef enum pls_option {
    * coloured Philox noise Lc xi in ONE launch (csrc/ipb_prep.h; needs the inverse factor Linv / LinvT in the descriptor and
    * PLS_OPT_SOLVE_MODE 1), 0 = the two triangular products, the fill and the third product as launches of their own (A/B
    * runs, tests).  Same draws either way; results agree to rounding. */
-  PLS_OPT_IPB_PREP = 14
+  PLS_OPT_IPB_PREP = 14,
+  /* The general step of the orthonormal basis through pls_onb_step_wg / pls_onb_step_blocks_wg with the basis' left-hand
+   * planes (pls_onb_winograd_prepare): 1 (default) = one level of Strassen-Winograd for the back-projection D = A G where J is
+   * a multiple of 128 and >= 2048 and the workspace holds the route's layout in chunks of >= 8192 paired rows: seven half-size
+   * products instead of eight, 7/8 of the matrix work of the back-projection (csrc/winograd.h); 0 = the
+   * plain contraction (A/B runs, tests).  Deterministic either way; results agree to rounding, not bit for bit. */
+  PLS_OPT_WINOGRAD = 15
 } pls_option;
 /* Diagnostic: out[i] = op(x[i]) with the device exp (op 0) / log (op 1) the per-element kernels use (csrc/fmath.h), or
  * out[i] = x[i] / x[n + i] with their division (op 2: fast_div, IEEE special cases restored; op 3: fast_div_normal), so
@@ -521,6 +527,26 @@ size_t pls_step_sync_words(int64_t j);
 /* Bytes of pls_block_desc.energy_partials for a basis with `rows` functions (Mk, or M of the inducing-point basis) and j
  * particle columns. */
 size_t pls_energy_partials_bytes(int64_t rows, int64_t j);
+
+/* The Winograd route of the general step (ABI 6; csrc/winograd.h, PLS_OPT_WINOGRAD).  pls_onb_winograd_bytes: bytes of the
+ * basis' left-hand planes S1..S4 (N/2 x M_k/2 doubles each, 256-byte aligned), 0 where the route does not apply: M_k a
+ * multiple of 16 and >= 512, N a multiple of 4 and >= 16384, A / At 16-byte aligned with even leading dimensions.
+ * pls_onb_winograd_prepare builds them from At (once per basis; again only if At changes) into `planes` (16-byte aligned).
+ * pls_onb_step_wg / pls_onb_step_blocks_wg are pls_onb_step / pls_onb_step_blocks with the planes (wg_planes, wg_bytes)
+ * handed in; wg_planes NULL: exactly pls_onb_step / pls_onb_step_blocks.  The route pairs data row n with n + N/2 and particle
+ * column j with j + J/2, so a J-shard and the whole particle matrix agree to rounding, not bit for bit.  Its workspace is
+ * no larger than the plain route's: it is taken where the workspace handed in (pls_onb_step_workspace_bytes) holds its
+ * chunks, else the plain route runs. */
+size_t pls_onb_winograd_bytes(const pls_onb_desc *basis);
+int pls_onb_winograd_prepare(const pls_onb_desc *basis, double *planes, size_t planes_bytes, void *stream);
+int pls_onb_step_wg(const pls_onb_desc *basis, const pls_cost_desc *cost, const double *y, double *U, int64_t ldu, int64_t j,
+                    double eta, const pls_noise_desc *noise, double *out, int64_t ldo, int32_t out_mode, int32_t force_generic,
+                    const double *wg_planes, size_t wg_bytes, double *energy_in, void *workspace, size_t workspace_bytes,
+                    void *stream);
+int pls_onb_step_blocks_wg(const pls_onb_desc *basis, const pls_cost_desc *cost, const double *y, double *U, int64_t ldu,
+                           int64_t j, const pls_block_desc *blocks, const pls_noise_desc *noise, double *out, int64_t ldo,
+                           int32_t out_mode, int32_t force_generic, const double *wg_planes, size_t wg_bytes, double *energy_in,
+                           void *workspace, size_t workspace_bytes, void *stream);
 
 /* pls_onb_step with one step size PER COLUMN BLOCK (pls_block_desc): the batched step-size search. */
 int pls_onb_step_blocks(const pls_onb_desc *basis, const pls_cost_desc *cost, const double *y, double *U, int64_t ldu,

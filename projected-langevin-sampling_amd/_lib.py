@@ -196,10 +196,14 @@ SIGNATURES = {
     "pls_ipb_whitened_generic_workspace_bytes": (_SZ, [_ID, _I64]),
     "pls_ipb_whitened_generic_step": (C.c_int, [_ID, _CD, _P, _P, _I64, _I64, _D, _BD, _ND, _P, _I64, _I32, _P, _P, _SZ, _P]),
     "pls_onb_step_blocks": (C.c_int, [_OD, _CD, _P, _P, _I64, _I64, _BD, _ND, _P, _I64, _I32, _I32, _P, _P, _SZ, _P]),
+    "pls_onb_winograd_bytes": (_SZ, [_OD]),
+    "pls_onb_winograd_prepare": (C.c_int, [_OD, _P, _SZ, _P]),
+    "pls_onb_step_wg": (C.c_int, [_OD, _CD, _P, _P, _I64, _I64, _D, _ND, _P, _I64, _I32, _I32, _P, _SZ, _P, _P, _SZ, _P]),
+    "pls_onb_step_blocks_wg": (C.c_int, [_OD, _CD, _P, _P, _I64, _I64, _BD, _ND, _P, _I64, _I32, _I32, _P, _SZ, _P, _P, _SZ, _P]),
     "pls_ipb_step_blocks": (C.c_int, [_ID, _CD, _P, _P, _I64, _I64, _BD, _ND, _P, _I64, _I32, _I32, _P, _P, _SZ, _P]),
 }
 
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 _lib = None
 
@@ -237,6 +241,7 @@ OPT_ENERGY_FUSED_FINISH = 11
 OPT_KG_NOISE_PREGEN = 12
 OPT_SMALL_RANK_STEP = 13
 OPT_IPB_PREP = 14
+OPT_WINOGRAD = 15
 TAG_NAMES = {1: "gemm_store", 2: "gemm_cost_deriv", 3: "gemm_cost_value", 4: "gemm_langevin_gaussian",
              5: "langevin_update", 6: "kernel_gram", 7: "other", 8: "small_rank_drift", 9: "small_rank_value",
              10: "tri_solve", 11: "small_rank_step", 12: "ipb_prep"}

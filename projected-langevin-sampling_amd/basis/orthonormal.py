@@ -291,10 +291,34 @@ class OrthonormalBasis(PLSBasis):
         if ws_bytes is None:
             ws_bytes = self._ws_bytes_cache[wkey] = (self.energy_partial_rows_bytes(j) if gaussian else
                                                      self._general_ws_bytes(L.load().pls_onb_step_workspace_bytes, desc, j))
-        return StepRoute("pls_onb_step", "pls_onb_step_blocks", (desc, cd, y.data_ptr()), (int(force_generic),),
-                         ws_bytes, (y, self._A, self._At, self.eigenvalues, self._B, self._c),
+        planes = None if gaussian else self._winograd_planes(desc)
+        entries, tail = ("pls_onb_step", "pls_onb_step_blocks"), (int(force_generic),)
+        if planes is not None:  # (the same entries, with the left-hand planes of the Winograd back-projection handed in)
+            entries, tail = ("pls_onb_step_wg", "pls_onb_step_blocks_wg"), (*tail, planes.data_ptr(), planes.numel() * 8)
+        return StepRoute(*entries, (desc, cd, y.data_ptr()), tail, ws_bytes,
+                         (y, self._A, self._At, self.eigenvalues, self._B, self._c, planes),
                          one_launch=not gaussian and 1 <= mk <= self.SMALL_RANK_MAX, sums=gaussian, lagged=gaussian,
                          ws_for_energy_only=gaussian)
+
+    def _winograd_planes(self, desc) -> torch.Tensor | None:
+        """The left-hand planes of the general step's Strassen-Winograd back-projection (pls_onb_winograd_prepare), built once
+        per projection: None where the route does not apply, and while a graph is being captured (no allocation or setup
+        launch inside a capture; that step takes the plain route)."""
+        key = self._At.data_ptr()
+        cached = self.__dict__.get("_wg_cache")
+        if cached is not None and cached[0] == key:
+            return cached[1]
+        lib = L.load()
+        nbytes = int(lib.pls_onb_winograd_bytes(desc))
+        planes = None
+        if nbytes:
+            if torch.cuda.is_current_stream_capturing():
+                return None
+            planes = torch.empty(nbytes // 8, dtype=torch.float64, device=self._At.device)
+            L.check(lib.pls_onb_winograd_prepare(desc, planes.data_ptr(), nbytes, L.stream_ptr()), "pls_onb_winograd_prepare")
+            torch.cuda.current_stream(self._At.device).synchronize()  # (steps on any stream read them from here on)
+        self._wg_cache = (key, planes)
+        return planes
 
     #: fused_step itself takes BlockSpec.energy_partials (the inducing-point basis only in whitened_step)
     fused_step_takes_lagged_energies = True

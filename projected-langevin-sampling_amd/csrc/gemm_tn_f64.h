@@ -40,6 +40,7 @@ struct GemmShape {
                    // 2: L[k][i] == 0 for k < i (lower-triangular), a tile contracts k >= i0 only
   double *tri_part;     // balanced triangular products (gemm_tn_f64_kg_tri_kernel): partial-sum slots and flag words of
   unsigned *tri_flags;  // the caller's scratch; NULL elsewhere
+  int64_t pair_i, pair_j;  // paired tiles (winograd.h): first column of the second half of L / R; unused elsewhere
 #ifdef PLS_STAMP
   unsigned long long *stamps;  // diagnostic build only: 4 s_memtime stamps per workgroup (never read by the kernel)
 #endif
@@ -89,6 +90,12 @@ struct AccFrag {
   double4_t v[TI][TJ];
 };
 
+// Paired tiles (winograd.h): a 128 x 128 tile covers 64 paired columns of each operand, column c and column c + pair of
+// both halves.  LDS column t holds the column at offset pair_offset(t) of half pair_half(t): each 64-column wave block then
+// holds 32 columns of the first half (its 16-column blocks 0, 1) and the same 32 of the second half (blocks 2, 3).
+__device__ __forceinline__ int pair_offset(int t) { return (t >> 6) * 32 + (t & 31); }
+__device__ __forceinline__ int pair_half(int t) { return (t >> 5) & 1; }
+
 // The k-loop, specialised at compile time on
 //   VEC : operands are 16-B aligned with even leading dimensions -> one global_load_dwordx4 per pair
 //   EDGE: the tile overhangs I or J -> overhanging lanes read column 0 of their row (always inside the matrix)
@@ -102,7 +109,9 @@ struct AccFrag {
 //   TIU / AST / a_off: the wave contracts its first TIU (<= TI) row blocks, AST columns of the L tile apart, starting at
 //         column a_off of the tile (the usual wave block: TIU = TI, AST = 16, a_off = the wave's row offset; the
 //         row-interleaved tiles of gemm_tn_f64_rows.h: AST = 32, a_off = 16 * wave row, TIU = the blocks that hold rows)
-template <int BI, int BJ, int WI, int WJ, int BK, bool VEC, bool EDGE, bool DMA, int TIU, int AST, int TI, int TJ>
+//   PAIRED: the paired tiles above (i0, j0 and I, J count paired columns; only the global column of a lane changes)
+template <int BI, int BJ, int WI, int WJ, int BK, bool VEC, bool EDGE, bool DMA, int TIU, int AST, int TI, int TJ,
+          bool PAIRED = false>
 __device__ __forceinline__ void gemm_tn_mainloop(const GemmShape &g, int64_t i0, int64_t j0, double *lds,
                                                  AccFrag<TI, TJ> &acc, int a_off) {
   static_assert(TIU >= 1 && TIU <= TI && (AST == 16 || AST == 32), "row blocks of the wave");
@@ -126,11 +135,16 @@ __device__ __forceinline__ void gemm_tn_mainloop(const GemmShape &g, int64_t i0,
 
   const int lcol = (tid % (BI / 2)) * 2, lrow = tid / (BI / 2);
   const int rcol = (tid % (BJ / 2)) * 2, rrow = tid / (BJ / 2);
-  const int64_t lrem = EDGE ? g.I - i0 - lcol : 2;  // valid columns from this thread's first column
-  const int64_t rrem = EDGE ? g.J - j0 - rcol : 2;
+  static_assert(!PAIRED || (BI == 128 && BJ == 128), "paired tiles are 128 x 128");
+  // global column of this thread's first L / R column (a pair never straddles a 32-column group of a paired tile)
+  const int lpos = PAIRED ? pair_offset(lcol) : lcol, rpos = PAIRED ? pair_offset(rcol) : rcol;
+  const int64_t lcg = (PAIRED && pair_half(lcol) ? g.pair_i : 0) + i0 + lpos;
+  const int64_t rcg = (PAIRED && pair_half(rcol) ? g.pair_j : 0) + j0 + rpos;
+  const int64_t lrem = EDGE ? g.I - i0 - lpos : 2;  // valid columns from this thread's first column
+  const int64_t rrem = EDGE ? g.J - j0 - rpos : 2;
   const bool l0 = lrem >= 1, l1 = lrem >= 2, r0 = rrem >= 1, r1 = rrem >= 2;
-  const double *Lq = g.L + (l0 ? i0 + lcol : 0);
-  const double *Rq = g.R + (r0 ? j0 + rcol : 0);
+  const double *Lq = g.L + (l0 ? lcg : 0);
+  const double *Rq = g.R + (r0 ? rcg : 0);
 
   double2_t lreg[LPASS], rreg[RPASS];
   bool lkin[LPASS], rkin[RPASS];  // only meaningful for the K-tail step
@@ -141,7 +155,7 @@ __device__ __forceinline__ void gemm_tn_mainloop(const GemmShape &g, int64_t i0,
   // inside the step as an SGPR offset, and ONE loop-invariant 32-bit lane offset in a VGPR: no VALU in the k-loop.
   static_assert(!DMA || (BI == 128 && BJ == 128), "one wave-instruction must cover exactly one k-row");
   const int wrow = __builtin_amdgcn_readfirstlane(lrow);  // = wave index: uniform
-  const int loff = (int)((l0 ? i0 + lcol : 0) * 8), roff = (int)((r0 ? j0 + rcol : 0) * 8);
+  const int loff = (int)((l0 ? lcg : 0) * 8), roff = (int)((r0 ? rcg : 0) * 8);
   int lsoff[LPASS], rsoff[RPASS];
 #pragma unroll
   for (int p = 0; p < LPASS; ++p) lsoff[p] = (int)((int64_t)(wrow + p * LROWS) * g.ldl * 8);

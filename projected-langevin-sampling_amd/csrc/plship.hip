@@ -28,6 +28,7 @@
 #include "ipb_prep.h"
 #include "small_rank_step_launch.h"
 #include "step_params.h"
+#include "winograd.h"
 #include "step_plan.h"
 
 namespace plship {
@@ -944,6 +945,125 @@ __global__ __launch_bounds__(256) void langevin_update_kernel(double *out, int64
   }
 }
 
+// ---- the Winograd route of the orthonormal basis (winograd.h) ------------------------------------------------------------
+// The left-hand planes S1..S4 (N/2 x M_k/2 each, leading dimension mh, `plane` doubles apart) of At (N x M_k).
+__global__ __launch_bounds__(256) void winograd_left_kernel(const double *__restrict__ At, int64_t ldat, int64_t nh, int64_t mh,
+                                                            double *__restrict__ S, int64_t plane) {
+  const int64_t m = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (m >= mh) return;
+  for (int64_t p = blockIdx.y; p < nh; p += gridDim.y) {
+    const double *top = At + p * ldat, *bot = At + (nh + p) * ldat;
+    const double a11 = top[m], a21 = top[mh + m], a12 = bot[m], a22 = bot[mh + m];
+    const double s1 = a21 + a22, s2 = s1 - a11, s3 = a11 - a21, s4 = a12 - s2;
+    double *o = S + p * mh + m;
+    o[0] = s1;
+    o[plane] = s2;
+    o[2 * plane] = s3;
+    o[3 * plane] = s4;
+  }
+}
+
+// The seven products of one chunk in ONE launch: blockIdx.z picks the product's operands from the table; product p's split-K
+// slabs (blockIdx.y, as in gemm_tn_f64_kernel) start prod_stride doubles after product p - 1's.
+struct WinoProducts {
+  const double *L[7];
+  int64_t ldl[7];
+  const double *R[7];
+  int64_t prod_stride;
+};
+
+__global__ __launch_bounds__(256, 2) void wino_products_kernel(GemmShape g, EpiStore epi, WinoProducts t) {
+  extern __shared__ __attribute__((aligned(16))) double lds[];
+  const int p = blockIdx.z;
+  g.L = t.L[p];
+  g.ldl = t.ldl[p];
+  g.R = t.R[p];
+  epi.C0 += p * t.prod_stride;
+  int tile_i, tile_j;
+  gemm_tile_coords(blockIdx.x, g.nti, g.ntj, tile_i, tile_j);
+  gemm_tile<128, 128, 64, 64, 16>(g, epi, tile_i, tile_j, lds);
+}
+
+// P_p (mh x jh, ld jh) = L_p^T R_p over K paired rows, beta = 0: write, 1: accumulate (the chunks after the first)
+static int launch_wino_products(const WinoProducts &t, int64_t mh, int64_t jh, int64_t K, int64_t kchunk, double *P, int64_t slab,
+                                double beta, hipStream_t st) {
+  constexpr size_t lds_bytes = (size_t)2 * 16 * ((128 + 16) + (128 + 16)) * sizeof(double);
+  static std::atomic<uint64_t> lds_ready{0};
+  if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(wino_products_kernel), lds_bytes, lds_ready)) return rc;
+  GemmShape g{nullptr, 0, nullptr, jh, mh, jh, K, 0, 0, kchunk, 0};
+  g.nti = (int)cdiv(mh, 128);
+  g.ntj = (int)cdiv(jh, 128);
+  const unsigned nsplit = (kchunk > 0 && kchunk < K) ? (unsigned)cdiv(K, kchunk) : 1u;
+  EpiStore e{P, jh, 1.0, beta, slab};
+  {
+    LaunchScope scope(PLS_TAG_GEMM_STORE, st);
+    hipLaunchKernelGGL(wino_products_kernel, dim3((unsigned)(g.nti * g.ntj), nsplit, 7), dim3(256), lds_bytes, st, g, e, t);
+  }
+  return check_launch("wino_products");
+}
+
+// The Winograd route's update: D from the seven products (each summed over its split-K slabs in a fixed order) by the formulas
+// of winograd.h, then langevin_update_kernel's update at the quadrant partners of a (row pair, column) of the top-left
+// quadrant: rows {ib, ib + 4} and {mh + ib, mh + ib + 4}, columns c and c + jh -- the same Philox pairs as that kernel.
+// P: product p, slab s at P + (p * nslab + s) * slab_stride, each mh x jh (ld jh).  mh must be a multiple of 8.
+__global__ __launch_bounds__(256) void langevin_update_wino_kernel(double *out, int64_t ldo, const double *__restrict__ U,
+                                                                    int64_t ldu, const double *__restrict__ P, int nslab,
+                                                                    int64_t slab_stride, const double *__restrict__ lam,
+                                                                    int64_t mh, int64_t jh, EtaP etap, int add_u, NoiseP nz) {
+  const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (c >= jh) return;
+  const int64_t cols[2] = {c, c + jh};
+  double eta[2], sq2eta[2];
+  int64_t jg[2];
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    eta[h] = etap.at(cols[h]);
+    sq2eta[h] = sqrt(2.0 * eta[h]);
+    jg[h] = nz.global_column(cols[h]);
+  }
+  const int64_t npairs = cdiv(mh, 8) * 4;
+  for (int64_t pr = blockIdx.y; pr < npairs; pr += gridDim.y) {
+    const int64_t ib = (pr >> 2) * 8 + (pr & 3);
+    double z[2][2][2];  // [row half][column half][row of the pair]
+#pragma unroll
+    for (int rh = 0; rh < 2; ++rh)
+#pragma unroll
+      for (int ch = 0; ch < 2; ++ch) {
+        const int64_t i = rh * mh + ib;
+        z[rh][ch][0] = z[rh][ch][1] = 0.0;
+        if (nz.kind == PLS_NOISE_PHILOX) {
+          normal_pair(nz.seed, nz.live_step(), i, jg[ch], z[rh][ch][0], z[rh][ch][1]);
+        } else if (nz.kind == PLS_NOISE_INJECTED) {
+          z[rh][ch][0] = nz.xi[i * nz.ldxi + cols[ch]];
+          z[rh][ch][1] = nz.xi[(i + 4) * nz.ldxi + cols[ch]];
+        }
+      }
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int64_t i = ib + 4 * h;
+      double p[7];
+#pragma unroll
+      for (int k = 0; k < 7; ++k) {
+        const double *src = P + (int64_t)k * nslab * slab_stride + i * jh + c;
+        double s = src[0];
+        for (int sl = 1; sl < nslab; ++sl) s += src[(int64_t)sl * slab_stride];
+        p[k] = s;
+      }
+      const double w = p[0] + p[5], w7 = w + p[6];
+      const double d[2][2] = {{p[0] + p[1], (w + p[4]) + p[2]}, {w7 - p[3], w7 + p[4]}};  // [row half][column half]
+#pragma unroll
+      for (int rh = 0; rh < 2; ++rh)
+#pragma unroll
+        for (int ch = 0; ch < 2; ++ch) {
+          const int64_t row = rh * mh + i, col = cols[ch];
+          const double u = U[row * ldu + col];
+          const double dd = -eta[ch] * d[rh][ch] - eta[ch] * (1.0 / lam[row]) * u + sq2eta[ch] * z[rh][ch][h];
+          out[row * ldo + col] = add_u ? u + dd : dd;
+        }
+    }
+  }
+}
+
 // IPB Gaussian fast path: e[col] = sum_i v (0.5 d - c_i / sigma2) + (M/2) v^2  + y^T y / (2 sigma2),
 //   v = V[i][col] = (K^-1 U)_i,  d = D[i][col] = (Kzx Kxz V)_i / sigma2  (the quadratic form of the Gaussian cost in V).
 // 64 columns x 4 row slices per block, slices summed through LDS in a fixed order.
@@ -1463,6 +1583,7 @@ static thread_local RouteOption g_energy_fused_finish{1};   // pls_set_option(PL
 static thread_local RouteOption g_ipb_step_operator{1};     // pls_set_option(PLS_OPT_IPB_STEP_OPERATOR): 1 = Pt route when the descriptor has it
 static thread_local RouteOption g_small_rank_step{1};  // pls_set_option(PLS_OPT_SMALL_RANK_STEP): 0 never, 1 launch-bound problems, 2 wherever it applies
 static thread_local RouteOption g_ipb_prep{1};         // pls_set_option(PLS_OPT_IPB_PREP): solve + coloured noise of a small inducing-point step in one launch
+static thread_local RouteOption g_winograd{1};    // pls_set_option(PLS_OPT_WINOGRAD): 0 plain back-projection, 1 Strassen-Winograd where eligible
 static thread_local RouteOption g_solve_mode{1};  // pls_set_option(PLS_OPT_SOLVE_MODE): 0 block substitution, 1 inverse-factor products where available
 int64_t solve_mode() { return g_solve_mode.load(); }
 
@@ -1846,6 +1967,10 @@ int pls_set_option(int32_t option, int64_t value) {
       PLS_REQUIRE(value == 0 || value == 1, "set_option: ipb prep mode must be 0 or 1");
       g_ipb_prep.store(value);
       return PLS_OK;
+    case PLS_OPT_WINOGRAD:
+      PLS_REQUIRE(value == 0 || value == 1, "set_option: winograd mode must be 0 or 1");
+      g_winograd.store(value);
+      return PLS_OK;
     default: return fail(PLS_ERR_INVALID_ARGUMENT, "set_option: unknown option %d", (int)option);
   }
 }
@@ -1872,6 +1997,7 @@ int64_t pls_get_option(int32_t option) {
     case PLS_OPT_KG_NOISE_PREGEN: return g_kg_noise_pregen.load();
     case PLS_OPT_SMALL_RANK_STEP: return g_small_rank_step.load();
     case PLS_OPT_IPB_PREP: return g_ipb_prep.load();
+    case PLS_OPT_WINOGRAD: return g_winograd.load();
     default: return -1;
   }
 }
@@ -2191,7 +2317,7 @@ static int validate_step_call(const char *who, const StepCall &c, bool needs_y) 
 }
 
 // The routes of a step call in original coordinates, decided once per call (onb_step_impl, ipb_step_impl)
-enum class StepRoute { Whitened, Fast, OneLaunch, General };
+enum class StepRoute { Whitened, Fast, OneLaunch, General, Winograd };
 
 // the Gaussian/identity fast path of either basis: the descriptor carries B and c (pls_*_build_gaussian)
 static bool gaussian_fast_path(const double *B, const double *c, const pls_cost_desc *cost, int force_generic) {
@@ -2321,6 +2447,44 @@ static FastOp onb_fast_op(const pls_onb_desc *b, const pls_cost_desc *c) {
   return FastOp{b->B, b->ldb, b->c, b->lam, b->mk, 1.0 / c->p[0], 0.5 / c->p[0], b->c + b->mk};
 }
 
+// The bases the Winograd route applies to: halves of whole row pairs (M_k % 16), an even N / 2 (16-byte aligned second halves),
+// operands the paired tiles and the products stream with 16-byte loads, and a back-projection big enough to fill the chip with
+// the seven products (7 x 128 tiles at M_k = 1024, J = 8192)
+static bool wino_basis_ok(const pls_onb_desc *b) {
+  auto al = [](const void *p, int64_t ld) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0 && (ld & 1) == 0; };
+  return b->mk % 16 == 0 && b->mk >= 512 && b->n % 4 == 0 && b->n >= 16384 && al(b->A, b->lda) && al(b->At, b->ldat);
+}
+
+constexpr int64_t kWinoMinChunk = 8192;  // paired rows: shorter chunks leave the products' split-K rounds part empty
+
+// ... and the step calls: the option on, the basis' left-hand planes handed in, whole 64-column paired tiles (J % 128)
+static bool wino_route_for(const pls_onb_desc *b, const double *planes, size_t planes_bytes, const double *U, int64_t ldu,
+                           int64_t j) {
+  return g_winograd.load() != 0 && planes && (reinterpret_cast<uintptr_t>(planes) & 15) == 0 && wino_basis_ok(b) &&
+         planes_bytes >= 4 * wino_left_plane_bytes(b->mk, b->n) && j % 128 == 0 && j >= 2048 &&
+         (reinterpret_cast<uintptr_t>(U) & 15) == 0 && (ldu & 1) == 0;
+}
+
+size_t pls_onb_winograd_bytes(const pls_onb_desc *basis) {
+  return (basis && validate_onb(basis) == PLS_OK && wino_basis_ok(basis)) ? 4 * wino_left_plane_bytes(basis->mk, basis->n) : 0;
+}
+
+int pls_onb_winograd_prepare(const pls_onb_desc *basis, double *planes, size_t planes_bytes, void *stream) {
+  int rc = validate_onb(basis);
+  if (rc) return rc;
+  PLS_REQUIRE(wino_basis_ok(basis), "onb_winograd_prepare: the basis' shape or operands do not take the Winograd route");
+  const size_t plane = wino_left_plane_bytes(basis->mk, basis->n);
+  PLS_REQUIRE(planes && (reinterpret_cast<uintptr_t>(planes) & 15) == 0 && planes_bytes >= 4 * plane,
+              "onb_winograd_prepare: planes must be 16-byte aligned and hold %zu bytes", 4 * plane);
+  const int64_t mh = basis->mk / 2, nh = basis->n / 2;
+  {
+    LaunchScope scope(PLS_TAG_OTHER, S(stream));
+    hipLaunchKernelGGL(winograd_left_kernel, dim3((unsigned)cdiv(mh, 256), (unsigned)(nh < 8192 ? nh : 8192)), dim3(256), 0,
+                       S(stream), basis->At, basis->ldat, nh, mh, planes, (int64_t)(plane / sizeof(double)));
+  }
+  return check_launch("winograd_left");
+}
+
 size_t pls_onb_step_workspace_bytes(const pls_onb_desc *basis, int64_t j, int64_t n_chunk) {
   if (!basis || j <= 0) return 0;
   if (n_chunk <= 0 || n_chunk > basis->n) n_chunk = basis->n;
@@ -2365,7 +2529,57 @@ static int onb_general_step(const pls_onb_desc *basis, const StepCall &c) {
   return finish_energy_sums(c.blocks, c.energy_in, c.j, c.st);
 }
 
-static int onb_step_impl(const pls_onb_desc *basis, const StepCall &c, int32_t force_generic) {
+// the Winograd route (winograd.h): per chunk of paired rows the paired forward (its epilogue leaves the seven right-hand planes)
+// and the seven products in one launch, then the update that combines them.  S: the basis' left-hand planes S1..S4.
+static int onb_wino_step(const pls_onb_desc *basis, const StepCall &c, const WinoLayout &L, const double *S) {
+  char *w = static_cast<char *>(c.workspace);
+  double *P = reinterpret_cast<double *>(w + L.p_off);
+  double *Q = reinterpret_cast<double *>(w + L.q_off);
+  double *part = reinterpret_cast<double *>(w + L.part_off);
+  const int64_t mh = L.mh, nh = L.nh, jh = L.jh, mk = basis->mk;
+  const int64_t splane = (int64_t)(L.s_plane / sizeof(double)), pslab = (int64_t)(L.p_slab / sizeof(double));
+  const int64_t qplane = (int64_t)(L.q_plane / sizeof(double));
+  int rc = PLS_OK;
+  int64_t kchunk = 0;
+  const int64_t nslab = wino_split_k(mh, jh, L.n_chunk, &kchunk);  // (== L.slabs)
+  const CostP cp = make_costp(c.cost);
+  const double *At = basis->At;
+  const int64_t ldat = basis->ldat;
+  for (int64_t p0 = 0, ci = 0; p0 < nh; p0 += L.n_chunk, ++ci) {
+    const int64_t rows = (nh - p0 < L.n_chunk) ? (nh - p0) : L.n_chunk;
+    rc = launch_cost_deriv_paired(basis->A + p0, basis->lda, nh, c.U, c.ldu, jh, rows, mk, Q, qplane, c.y + p0, cp,
+                                  c.energy_in ? part : nullptr, c.j, c.st);
+    if (rc) return rc;
+    if (c.energy_in) {  // e_j = cost_j(F(U)) + 1/2 sum_m U_mj^2 / lam_m of the INPUT particles, as on the general route
+      LaunchScope scope(PLS_TAG_OTHER, c.st);
+      hipLaunchKernelGGL(column_reduce_kernel, dim3((unsigned)cdiv(c.j, 256)), dim3(256), 0, c.st, part, c.j, cdiv(rows, 32), c.j,
+                         c.energy_in, ci == 0 ? 0 : 1, p0 + L.n_chunk >= nh ? 1 : 0, c.U, c.ldu, mk, basis->lam, 0.0, 1.0,
+                         (const double *)nullptr);
+      if ((rc = check_launch("column_reduce"))) return rc;
+    }
+    const double *S1 = S + p0 * mh, *S2 = S1 + splane, *S3 = S2 + splane, *S4 = S3 + splane;
+    const double *A11 = At + p0 * ldat, *A12 = At + (nh + p0) * ldat, *A22 = A12 + mh;
+    WinoProducts t{{A11, A12, S4, A22, S1, S2, S3},
+                   {ldat, ldat, mh, ldat, mh, mh, mh},
+                   {Q + WQ_G11 * qplane, Q + WQ_G21 * qplane, Q + WQ_G22 * qplane, Q + WQ_T4 * qplane, Q + WQ_T1 * qplane,
+                    Q + WQ_T2 * qplane, Q + WQ_T3 * qplane},
+                   nslab * pslab};
+    rc = launch_wino_products(t, mh, jh, rows, nslab > 1 ? kchunk : 0, P, pslab, ci == 0 ? 0.0 : 1.0, c.st);
+    if (rc) return rc;
+  }
+  {
+    LaunchScope scope(PLS_TAG_LANGEVIN_UPDATE, c.st);
+    hipLaunchKernelGGL(langevin_update_wino_kernel, dim3((unsigned)cdiv(jh, 256), rows_grid(cdiv(mh, 8) * 4)), dim3(256), 0, c.st,
+                       c.out, c.ldo, c.U, c.ldu, P, (int)nslab, pslab, basis->lam, mh, jh, c.etap(), c.out_mode, c.noisep());
+  }
+  rc = check_launch("langevin_update_wino");
+  if (rc) return rc;
+  return finish_energy_sums(c.blocks, c.energy_in, c.j, c.st);
+}
+
+// wg_planes / wg_bytes: the basis' left-hand planes (pls_onb_winograd_prepare), NULL: no Winograd route
+static int onb_step_impl(const pls_onb_desc *basis, const StepCall &c, int32_t force_generic, const double *wg_planes = nullptr,
+                         size_t wg_bytes = 0) {
   int rc = validate_onb(basis);
   if (!rc) rc = validate_step("onb_step", c, true);
   if (rc) return rc;
@@ -2386,6 +2600,12 @@ static int onb_step_impl(const pls_onb_desc *basis, const StepCall &c, int32_t f
     sl = sr_step_plan(0, basis->mk, basis->n, c);  // (launch-bound problems: the whole step, its energies and sums in ONE launch)
     if (ws_holds(sl.total, c.workspace, c.workspace_bytes)) route = StepRoute::OneLaunch;
   }
+  WinoLayout wl{};
+  if (route == StepRoute::General && wino_route_for(basis, wg_planes, wg_bytes, c.U, c.ldu, c.j)) {
+    wl = wino_plan(basis->mk, basis->n, c.j, c.workspace_bytes);
+    const int64_t min_chunk = wl.nh < kWinoMinChunk ? wl.nh : kWinoMinChunk;
+    if (c.workspace && wl.total <= c.workspace_bytes && wl.n_chunk >= min_chunk) route = StepRoute::Winograd;
+  }
   PLS_REQUIRE(fast || !c.blocks || (!c.blocks->energy_partials && !c.blocks->energy_partials_prev),
               "onb_step: lagged energies (energy_partials) exist on the Gaussian/identity fast path only");
   switch (route) {
@@ -2394,6 +2614,8 @@ static int onb_step_impl(const pls_onb_desc *basis, const StepCall &c, int32_t f
     case StepRoute::OneLaunch:
       return sr_step_launch(SrStepOperands{basis->At, basis->ldat, basis->mk, basis->n, c.U, c.ldu, nullptr, 0, basis->lam, 0.0},
                             sl, c, c.noisep());
+    case StepRoute::Winograd:
+      return onb_wino_step(basis, c, wl, wg_planes);
     default:
       return onb_general_step(basis, c);
   }
@@ -2404,6 +2626,23 @@ int pls_onb_step(const pls_onb_desc *basis, const pls_cost_desc *cost, const dou
                  int32_t force_generic, double *energy_in, void *workspace, size_t workspace_bytes, void *stream) {
   return onb_step_impl(basis, StepCall{cost, y, U, ldu, j, eta, nullptr, noise, out, ldo, out_mode, energy_in, workspace,
                                        workspace_bytes, S(stream)}, force_generic);
+}
+
+int pls_onb_step_wg(const pls_onb_desc *basis, const pls_cost_desc *cost, const double *y, double *U, int64_t ldu, int64_t j,
+                    double eta, const pls_noise_desc *noise, double *out, int64_t ldo, int32_t out_mode, int32_t force_generic,
+                    const double *wg_planes, size_t wg_bytes, double *energy_in, void *workspace, size_t workspace_bytes,
+                    void *stream) {
+  return onb_step_impl(basis, StepCall{cost, y, U, ldu, j, eta, nullptr, noise, out, ldo, out_mode, energy_in, workspace,
+                                       workspace_bytes, S(stream)}, force_generic, wg_planes, wg_bytes);
+}
+
+int pls_onb_step_blocks_wg(const pls_onb_desc *basis, const pls_cost_desc *cost, const double *y, double *U, int64_t ldu,
+                           int64_t j, const pls_block_desc *blocks, const pls_noise_desc *noise, double *out, int64_t ldo,
+                           int32_t out_mode, int32_t force_generic, const double *wg_planes, size_t wg_bytes, double *energy_in,
+                           void *workspace, size_t workspace_bytes, void *stream) {
+  PLS_REQUIRE(blocks != nullptr, "onb_step_blocks: block descriptor is NULL");
+  return onb_step_impl(basis, StepCall{cost, y, U, ldu, j, 0.0, blocks, noise, out, ldo, out_mode, energy_in, workspace,
+                                       workspace_bytes, S(stream)}, force_generic, wg_planes, wg_bytes);
 }
 
 int pls_onb_step_blocks(const pls_onb_desc *basis, const pls_cost_desc *cost, const double *y, double *U, int64_t ldu,

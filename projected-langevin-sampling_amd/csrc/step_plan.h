@@ -167,6 +167,80 @@ static inline DriftLayout drift_plan(int lead, int64_t mk, int64_t n, int64_t j,
   return drift_chunk(all, j, c < min_rows ? min_rows : c);
 }
 
+// ---- the Winograd route of the orthonormal basis (winograd.h) --------------------------------------------------------------
+// [the seven products' D slabs, M_k/2 x J/2 each, product-major][partial rows of the energy by-product][the seven right-hand
+// planes of a chunk, n_chunk x J/2 each].  Chunks are ranges of PAIRED rows (row p stands for data rows p and p + N/2).  The
+// left-hand planes S1..S4 (N/2 x M_k/2 each, s_plane bytes apart) are the basis' own (pls_onb_winograd_prepare), not workspace.
+struct WinoLayout {
+  int64_t mh, nh, jh;          // M_k / 2, N / 2, J / 2
+  int64_t slabs;               // split-K slabs of each product
+  int64_t n_chunk, part_rows;  // paired rows per chunk, partial rows of the energy by-product
+  size_t s_plane, p_slab, q_plane;  // bytes of one left-hand plane, one product slab, one right-hand plane
+  size_t p_off, part_off, q_off, total;
+};
+
+// Split-K plan of the seven products (M_k/2 x J/2 each) over K paired rows: the slabs that put the 7 x tiles x slabs
+// workgroups in whole rounds of 512 (2 per CU), with slabs of <= 16384 rows (the L2 locality of plan_split_k).  <= 16.
+static inline int64_t wino_split_k(int64_t mh, int64_t jh, int64_t K, int64_t *kchunk) {
+  const int64_t tiles = 7 * cdiv(mh, 128) * cdiv(jh, 128);
+  int64_t s = tiles < 512 ? cdiv(512, tiles) : 1;
+  const int64_t s_local = cdiv(K, 16384);
+  if (s_local > s) s = s_local;
+  if (s > 16) s = 16;
+  auto waste = [&](int64_t sl) {
+    const double rounds = (double)(tiles * sl) / 512.0;
+    return std::ceil(rounds) / rounds;
+  };
+  int64_t best = s;
+  for (int64_t sl = s + 1; sl <= 16 && sl <= s + 4; ++sl)
+    if (waste(sl) < waste(best) - 0.03) best = sl;
+  s = best;
+  while (s > 1 && K / s < 1024) --s;
+  int64_t kc = cdiv(cdiv(K, s), 16) * 16;
+  s = cdiv(K, kc);
+  *kchunk = (s > 1) ? kc : 0;
+  return s;
+}
+
+// one left-hand plane (N/2 x M_k/2); the four take 4 x this
+static inline size_t wino_left_plane_bytes(int64_t mk, int64_t n) { return align_up((size_t)(n / 2) * (mk / 2) * sizeof(double), 256); }
+
+static inline WinoLayout wino_chunk(WinoLayout L, int64_t n_chunk) {
+  L.n_chunk = n_chunk;
+  L.part_rows = energy_partial_rows(n_chunk);
+  L.q_plane = align_up((size_t)n_chunk * L.jh * sizeof(double), 256);
+  L.q_off = L.part_off + align_up((size_t)L.part_rows * 2 * L.jh * sizeof(double), 256);
+  L.total = L.q_off + 7 * L.q_plane;
+  return L;
+}
+
+// the layout for chunks of n_chunk paired rows; the slab count is planned for the largest chunk
+static inline WinoLayout wino_layout(int64_t mk, int64_t n, int64_t j, int64_t n_chunk) {
+  WinoLayout L{};
+  L.mh = mk / 2;
+  L.nh = n / 2;
+  L.jh = j / 2;
+  int64_t kc;
+  L.slabs = wino_split_k(L.mh, L.jh, n_chunk < L.nh ? n_chunk : L.nh, &kc);
+  L.s_plane = wino_left_plane_bytes(mk, n);
+  L.p_slab = align_up((size_t)L.mh * L.jh * sizeof(double), 256);
+  L.p_off = 0;
+  L.part_off = L.p_off + 7 * (size_t)L.slabs * L.p_slab;
+  return wino_chunk(L, n_chunk);
+}
+
+// The layout of the largest chunk that fits `avail` bytes: all N/2 paired rows, else a multiple of 128, never below
+// min(N/2, 128); when not even that fits, that layout all the same (its total exceeds `avail`: the caller takes another route)
+static inline WinoLayout wino_plan(int64_t mk, int64_t n, int64_t j, size_t avail) {
+  const int64_t nh = n / 2;
+  const WinoLayout all = wino_layout(mk, n, j, nh);
+  if (all.total <= avail) return all;
+  const int64_t min_rows = nh < 128 ? nh : 128;
+  int64_t c = nh / 128 * 128;
+  while (c > min_rows && wino_layout(mk, n, j, c).total > avail) c -= 128;
+  return wino_layout(mk, n, j, c < min_rows ? min_rows : c);
+}
+
 // ---- the energy entries (pls_onb_energy, pls_ipb_energy) ---------------------------------------------------------------
 // [lead m x j buffers: none on the orthonormal basis, V on the inducing-point basis][partial rows].  The cost value streams N
 // in chunks and leaves one partial row per 64 data rows of a chunk, at least two.  The Gaussian/identity fast path reduces

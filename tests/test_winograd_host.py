@@ -1,0 +1,111 @@
+"""CPU: the arithmetic and the workspace layout of the Strassen-Winograd back-projection (csrc/winograd.h, csrc/step_plan.h)."""
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+
+def _winograd(a, g):
+    """D = A G by the seven products and the combination csrc/winograd.h documents (A: M x N, G: N x J, all even)."""
+    m, n = a.shape
+    j = g.shape[1]
+    mh, nh, jh = m // 2, n // 2, j // 2
+    a11, a12, a21, a22 = a[:mh, :nh], a[:mh, nh:], a[mh:, :nh], a[mh:, nh:]
+    g11, g12, g21, g22 = g[:nh, :jh], g[:nh, jh:], g[nh:, :jh], g[nh:, jh:]
+    s1 = a21 + a22
+    s2 = s1 - a11
+    s3 = a11 - a21
+    s4 = a12 - s2
+    t1 = g12 - g11
+    t2 = g22 - t1
+    t3 = g22 - g12
+    t4 = t2 - g21
+    p1, p2, p3, p4, p5, p6, p7 = a11 @ g11, a12 @ g21, s4 @ g22, a22 @ t4, s1 @ t1, s2 @ t2, s3 @ t3
+    w = p1 + p6
+    d = np.empty((m, j), dtype=a.dtype)
+    d[:mh, :jh] = p1 + p2
+    d[mh:, :jh] = (w + p7) - p4
+    d[mh:, jh:] = (w + p7) + p5
+    d[:mh, jh:] = (w + p5) + p3
+    return d
+
+
+@pytest.mark.parametrize("shape", [(2, 2, 2), (16, 12, 8), (32, 100, 64), (48, 4, 128)])
+def test_winograd_products_reproduce_the_product_exactly(shape):
+    m, n, j = shape
+    rng = np.random.default_rng(sum(shape))
+    a = rng.integers(-1000, 1000, size=(m, n), dtype=np.int64)
+    g = rng.integers(-1000, 1000, size=(n, j), dtype=np.int64)
+    assert np.array_equal(_winograd(a, g), a @ g)
+
+
+def test_winograd_in_floating_point_agrees_to_rounding():
+    rng = np.random.default_rng(0)
+    a = rng.standard_normal((64, 400))
+    g = rng.standard_normal((400, 96))
+    want = a @ g
+    assert np.abs(_winograd(a, g) - want).max() <= 1e-12 * np.abs(want).max()
+
+
+def test_winograd_layout_of_the_step_plan(tmp_path):
+    """csrc/step_plan.h: the Winograd route's workspace layout over a grid of sizes -- regions 256-byte aligned, disjoint,
+    inside the total and of the documented sizes; the plan's chunk fits the workspace it was planned for and is the largest multiple of
+    128 that does (or all rows); the split-K slabs fill whole rounds at the headline shape."""
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    if not os.path.exists(hipcc):
+        pytest.skip("hipcc not found")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    src = tmp_path / "wino.cpp"
+    src.write_text('''#include <cstdio>
+#include <cstdint>
+#include <hip/hip_runtime.h>
+#include "step_plan.h"
+using namespace plship;
+int main() {
+  const int64_t mks[] = {512, 1024, 2048};
+  const int64_t ns[] = {16384, 40000, 100000, 200000};
+  const int64_t js[] = {2048, 4096, 8192};
+  for (int64_t mk : mks) for (int64_t n : ns) for (int64_t j : js) {
+    const WinoLayout all = wino_layout(mk, n, j, n / 2);
+    for (double f : {0.3, 0.5, 0.8, 1.0, 2.0}) {
+      const size_t w = (size_t)(f * (double)all.total);
+      const WinoLayout L = wino_plan(mk, n, j, w);
+      const size_t next = L.n_chunk < L.nh ? wino_layout(mk, n, j, L.n_chunk + 128 < L.nh ? L.n_chunk + 128 : L.nh).total : 0;
+      printf("%ld %ld %ld %zu %ld %ld %ld %ld %ld %ld %zu %zu %zu %zu %zu %zu %zu %zu %zu\\n", (long)mk, (long)n, (long)j, w,
+             (long)L.mh, (long)L.nh, (long)L.jh, (long)L.slabs, (long)L.n_chunk, (long)L.part_rows, L.s_plane, L.p_slab, L.q_plane,
+             wino_left_plane_bytes(mk, n), L.p_off, L.part_off, L.q_off, L.total, next);
+    }
+  }
+  return 0;
+}
+''')
+    exe = tmp_path / "wino"
+    subprocess.run([hipcc, "-std=c++17", "--offload-arch=gfx950", "-I", os.path.join(root, "projected-langevin-sampling_amd", "csrc"),
+                    "-o", str(exe), str(src)], check=True, capture_output=True, timeout=300)
+    out = subprocess.run([str(exe)], check=True, capture_output=True, text=True, timeout=60).stdout
+    rows = [[int(x) for x in line.split()] for line in out.splitlines()]
+    assert len(rows) == 3 * 4 * 3 * 5
+
+    def up(x):
+        return -(-x // 256) * 256
+
+    for v in rows:
+        mk, n, j, w, mh, nh, jh, slabs, chunk, part_rows, s_plane, p_slab, q_plane, left, p_off, part_off, q_off, total, nxt = v
+        line = " ".join(map(str, v))
+        assert (mh, nh, jh) == (mk // 2, n // 2, j // 2), line
+        assert all(x % 256 == 0 for x in (s_plane, p_slab, q_plane, p_off, part_off, q_off)), line
+        assert s_plane == left == up(nh * mh * 8) and p_slab == up(mh * jh * 8) and q_plane == up(chunk * jh * 8), line
+        assert 1 <= slabs <= 16 and part_rows >= -(-chunk // 32), line
+        # [7 products x slabs][partial rows][7 planes], back to back (S1..S4 are the basis' own)
+        assert p_off == 0 and part_off == 7 * slabs * p_slab, line
+        assert q_off >= part_off + part_rows * j * 8 and total == q_off + 7 * q_plane, line
+        assert 1 <= chunk <= nh, line
+        if total <= w:
+            assert chunk == nh or chunk % 128 == 0, line
+            assert chunk == nh or nxt > w, f"a larger chunk fits: {line}"
+    head = [v for v in rows if v[:3] == [1024, 100000, 8192]]
+    assert any(v[8] == 50000 for v in head)  # all paired rows in one chunk when the workspace holds them
+    # two chunks and four slabs in the bench's 8 GiB: 7 products x 128 tiles x 4 slabs = 7 rounds of 512 workgroups
+    assert all(v[7] == 4 for v in head if v[8] > 16384)
