@@ -68,6 +68,18 @@ def relerr(got, want):
     return ((got - want).abs().max() / want.abs().max().clamp_min(1e-300)).item()
 
 
+def row_relerr(got, want):
+    """The largest over rows of max|got_r - want_r| / max|want_r|: rows are the eigen-directions of a step (or rows of D =
+    A G), whose scales differ by orders of magnitude -- relerr measures every row against the largest."""
+    got = got.detach().cpu().double() if isinstance(got, torch.Tensor) else torch.as_tensor(got).double()
+    want = want.detach().cpu().double() if isinstance(want, torch.Tensor) else torch.as_tensor(want).double()
+    assert got.shape == want.shape and want.dim() == 2, (got.shape, want.shape)
+    if want.numel() == 0:
+        return 0.0
+    err = (got - want).abs().amax(dim=1)
+    return (err / want.abs().amax(dim=1).clamp_min(1e-300)).max().item()
+
+
 def cu(t):
     return t.to(device="cuda", dtype=torch.float64)
 

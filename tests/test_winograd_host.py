@@ -109,3 +109,119 @@ int main() {
     assert any(v[8] == 50000 for v in head)  # all paired rows in one chunk when the workspace holds them
     # two chunks and four slabs in the bench's 8 GiB: 7 products x 128 tiles x 4 slabs = 7 rounds of 512 workgroups
     assert all(v[7] == 4 for v in head if v[8] > 16384)
+
+
+def _plans(tmp_path, queries):
+    """wino_plan(mk, n, j, ws) of csrc/step_plan.h for each (mk, n, j, ws, plain_fraction): ws < 0 means plain_fraction of the
+    plain route's all-rows workspace (pls_onb_step_workspace_bytes(basis, j, 0)).  Rows: mk n j ws slabs n_chunk nh total."""
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    if not os.path.exists(hipcc):
+        pytest.skip("hipcc not found")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    rows = "\n".join(f"  {{{mk}, {n}, {j}, {ws}, {num}, {den}}}," for mk, n, j, ws, num, den in queries)
+    src = tmp_path / "plans.cpp"
+    src.write_text('''#include <cstdio>
+#include <cstdint>
+#include <hip/hip_runtime.h>
+#include "step_plan.h"
+using namespace plship;
+struct Q { int64_t mk, n, j, ws, num, den; };
+int main() {
+  const Q qs[] = {
+''' + rows + '''
+  };
+  for (const Q &q : qs) {
+    size_t ws = (size_t)q.ws;
+    if (q.ws < 0) {
+      const size_t g = drift_layout(0, q.mk, q.n, q.j, q.n).total, o = sr_step_query_bytes(0, q.mk, q.n, q.j);
+      ws = (g > o ? g : o) * q.num / q.den;
+    }
+    const WinoLayout L = wino_plan(q.mk, q.n, q.j, ws);
+    printf("%ld %ld %ld %zu %ld %ld %ld %zu\\n", (long)q.mk, (long)q.n, (long)q.j, ws, (long)L.slabs, (long)L.n_chunk, (long)L.nh,
+           L.total);
+  }
+  return 0;
+}
+''')
+    exe = tmp_path / "plans"
+    subprocess.run([hipcc, "-std=c++17", "--offload-arch=gfx950", "-I", os.path.join(root, "projected-langevin-sampling_amd", "csrc"),
+                    "-o", str(exe), str(src)], check=True, capture_output=True, timeout=300)
+    out = subprocess.run([str(exe)], check=True, capture_output=True, text=True, timeout=60).stdout
+    return [[int(x) for x in line.split()] for line in out.splitlines()]
+
+
+def test_plans_of_the_gpu_envelope_shapes(tmp_path):
+    """The shapes and workspaces tests/test_gpu_winograd.py runs get the plans they are there for: each edge shape ONE chunk in
+    wino_one_chunk_bytes (one slab for WINO_ONE_SLAB, several for the rest), three chunks with a short last one and several
+    slabs in 9/10 of the plain workspace, and at the headline shape two chunks / four slabs in 8 GiB, one chunk in
+    wino_one_chunk_bytes."""
+    from step_fixtures import WINO_EDGES, WINO_ONE_SLAB, WINO_THREE_CHUNKS, wino_one_chunk_bytes
+
+    head = (1024, 100_000, 8192)
+    qs = [(*s, wino_one_chunk_bytes(*s), 1, 1) for s in WINO_EDGES] + [(*WINO_THREE_CHUNKS, -1, 9, 10), (*head, 8 << 30, 1, 1),
+                                                                        (*head, wino_one_chunk_bytes(*head), 1, 1)]
+    rows = _plans(tmp_path, qs)
+    assert len(rows) == len(qs)
+    for (mk, n, j, ws, slabs, chunk, nh, total), s in zip(rows[:len(WINO_EDGES)], WINO_EDGES):
+        assert total <= ws and chunk == nh == n // 2, s
+        assert (slabs == 1) == (tuple(s) == WINO_ONE_SLAB), (s, slabs)
+    mk, n, j, ws, slabs, chunk, nh, total = rows[len(WINO_EDGES)]
+    assert total <= ws and chunk >= 8192 and -(-nh // chunk) == 3 and nh % chunk < chunk // 2 and slabs > 1
+    mk, n, j, ws, slabs, chunk, nh, total = rows[-2]
+    assert total <= ws and -(-nh // chunk) == 2 and slabs == 4
+    mk, n, j, ws, slabs, chunk, nh, total = rows[-1]
+    assert total <= ws and chunk == nh and slabs == 4
+
+
+# ---- per-direction accuracy on a graded spectrum ------------------------------------------------------------------------
+def _rbf_projection(n, m, d, ls_scale, seed=0):
+    """A = V~^T k(Z, X) of an RBF/ARD basis on configs[1]'s kind of data (x uniform in [-1, 1]^d, Z a subset of X, length
+    scales 0.5 + U(0, 1) as benched, times ls_scale), every positive eigenvalue of k(Z, Z) / M kept, M_k trimmed to a multiple
+    of 16 (the smallest go); rows in eigh's ascending order, like the library's."""
+    rng = np.random.default_rng(seed)
+    x = rng.uniform(-1.0, 1.0, size=(n, d))
+    z = x[rng.permutation(n)[:m]]
+    ls = (0.5 + np.random.default_rng(1).uniform(size=d)) * ls_scale
+
+    def k(p, q):
+        s = ((p[:, None, :] - q[None, :, :]) / ls) ** 2
+        return np.exp(-0.5 * s.sum(-1))
+
+    kzx = np.concatenate([k(z, x[i:i + 4096]) for i in range(0, n, 4096)], axis=1)
+    lam, vec = np.linalg.eigh(k(z, z) / m)
+    keep = np.where(lam > 0)[0]
+    keep = keep[keep.size % 16:]
+    lam, vec = lam[keep], vec[:, keep]
+    a = (vec / np.sqrt(lam.size * lam)[None, :]).T @ kzx
+    y = np.sin(2.0 * x @ rng.standard_normal(d)) + 0.1 * rng.standard_normal(n)
+    return a, lam, y
+
+
+def _row_err(got, want):
+    return (np.abs(got - want).max(axis=1) / np.abs(want).max(axis=1)).astype(np.float64)
+
+
+# (length-scale factor, the per-row error of D = A G recorded for Winograd's combination on the host, its bound):
+# N = 16384, M = 1024, d = 8, 8 columns (4 Winograd pairs), longdouble reference.  Plain fp64: <= 1e-14 on both spectra.
+GRADED = [(1.0, 1.6e-13, 2e-12), (3.0, 5e-11, 5e-10)]
+
+
+@pytest.mark.parametrize("ls_scale,recorded,bound", GRADED)
+def test_winograd_per_direction_on_a_graded_spectrum(ls_scale, recorded, bound):
+    """The rows of A scale like sqrt(lambda) and eigh sorts lambda ascending: Winograd pairs each small top-half row i with the
+    large bottom-half row M/2 + i, and D12 / D21 come out of large terms that cancel.  The error is norm-wise, so small rows
+    lose digits that relerr over the whole matrix never sees: per row, Winograd stays within the documented bound (DESIGN.md
+    section 3) while the plain product is at rounding level, and the worst Winograd rows are top-half rows."""
+    a, lam, y = _rbf_projection(16384, 1024, 8, ls_scale)
+    m, n = a.shape
+    rng = np.random.default_rng(2)
+    u = rng.standard_normal((m, 8)) * np.sqrt(lam)[:, None]
+    g = (a.T @ u - y[:, None]) / 0.01  # Gaussian cost derivative, configs[1]'s variance
+    ref = (a.astype(np.longdouble) @ g.astype(np.longdouble)).astype(np.float64)
+    plain = _row_err(a @ g, ref)
+    wino = _row_err(_winograd(a, g), ref)
+    print(f"ls x{ls_scale:g}: M_k {m}, lambda {lam.min():.1e} .. {lam.max():.1e}; per-row error of D: plain {plain.max():.2e}, "
+          f"Winograd {wino.max():.2e} (row {wino.argmax()})")
+    assert plain.max() <= 1e-14
+    assert wino.max() <= bound
+    assert wino.argmax() < m // 2
