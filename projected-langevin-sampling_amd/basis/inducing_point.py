@@ -42,6 +42,37 @@ class InducingPointBasis(PLSBasis):
         self.gram_induce = self.kernel.forward(x1=x_induce, x2=x_induce)  # r(Z,Z)  :38-40
         self.base_gram_induce = self.kernel.base_kernel(x1=x_induce, x2=x_induce)  # k(Z,Z)  :41-43
         self.base_gram_induce_train = self.kernel.base_kernel(x1=x_induce, x2=x_train)  # k(Z,X) (M,N) :44-46
+        self._setup(cholesky_factor, explicit_inverse)
+
+    @classmethod
+    def from_gram(cls, kzz: torch.Tensor, kzx: torch.Tensor, y_induce: torch.Tensor | None = None,
+                  cholesky_factor: torch.Tensor | None = None, explicit_inverse: bool = False,
+                  poison_padding: bool = False) -> "InducingPointBasis":
+        """A basis given directly by its Gram matrices k(Z,Z) (M, M) and k(Z,X) (M, N) (the analogue of
+        OrthonormalBasis.from_projection): everything on the per-step path works (forward, update, fused step, whitened
+        coordinates, energy); prediction needs the kernel and is unavailable.  ``cholesky_factor``, ``explicit_inverse``: as
+        in the constructor.  ``poison_padding`` fills the alignment padding of the device copies of k(Z,X) and k(X,Z) with
+        NaN (tests: padding must never be read as data)."""
+        kzz = L.require_gpu_tensor(kzz, "kzz")
+        kzx = L.require_gpu_tensor(kzx, "kzx")
+        m, n = kzx.shape
+        assert kzz.shape == (m, m), "k(Z,Z) must be square with one row per row of k(Z,X)"
+        self = cls.__new__(cls)
+        PLSBasis.__init__(self, additional_predictive_noise_distribution=None)
+        self.kernel = None
+        self.x_induce = None
+        self.y_induce = y_induce
+        self.gram_induce = None
+        self.base_gram_induce = kzz.contiguous()
+        self.base_gram_induce_train = alloc_matrix(m, n, kzx.device)
+        if poison_padding:
+            self.base_gram_induce_train._base.fill_(float("nan"))
+        self.base_gram_induce_train.copy_(kzx)
+        self._setup(cholesky_factor, explicit_inverse, poison_padding)
+        return self
+
+    def _setup(self, cholesky_factor: torch.Tensor | None, explicit_inverse: bool, poison_padding: bool = False) -> None:
+        """the device state behind the Gram matrices: the factor of k(Z,Z), its inverse factor, k(X,Z)"""
         dev = self.base_gram_induce.device
         m, n = self.base_gram_induce_train.shape
         self._n = n
@@ -57,6 +88,8 @@ class InducingPointBasis(PLSBasis):
             self._W = _dev(torch.cholesky_inverse(self._chol.Lc.cpu()))
         # k(X,Z) as its own k-major operand for the back-projection k(Z,X) G
         self._Kxz = alloc_matrix(n, m, dev)
+        if poison_padding:
+            self._Kxz._base.fill_(float("nan"))
         self._Kxz.copy_(self.base_gram_induce_train.T)
         self._B = None  # Gaussian fast path constants, keyed by the y they were built from
         self._c = None
@@ -70,7 +103,7 @@ class InducingPointBasis(PLSBasis):
 
     @property
     def approximation_dimension(self) -> int:
-        return self.x_induce.shape[0]  # :52-58
+        return self.base_gram_induce.shape[0]  # :52-58 (the number of inducing points)
 
     def _desc(self, with_gaussian: bool = False) -> L.IpbDesc:
         d = L.IpbDesc()
@@ -173,20 +206,22 @@ class InducingPointBasis(PLSBasis):
 
     def whitened_step(self, cost, whitened: torch.Tensor, step_size: float, out: torch.Tensor | None = None,
                       new_state: bool = False, noise: NoiseSpec | None = None, input_energy: torch.Tensor | None = None,
-                      blocks: BlockSpec | None = None, workspace: torch.Tensor | None = None) -> torch.Tensor:
+                      blocks: BlockSpec | None = None, workspace: torch.Tensor | None = None,
+                      force_generic: bool = False) -> torch.Tensor:
         """One Langevin step of whitened particles: ONE M x M x J contraction with the update, the noise and -- optionally --
         the energy of the input particles in its epilogue (pls_ipb_whitened_step); any other cost: the one-launch small-rank
         step over Awa (pls_ipb_whitened_generic_step, at most 128 points).  ``noise`` injected = xi itself (standard normal,
-        not coloured); Philox noise draws the xi of fused_step's e = Lc xi."""
+        not coloured); Philox noise draws the xi of fused_step's e = Lc xi.  ``force_generic`` (tests, A/B runs): the Gaussian
+        cost through the one-launch step over Awa as well."""
         s = _rows_contiguous(L.require_gpu_tensor(whitened, "whitened particles"))
-        return self._step(cost, s, step_size, out, new_state, noise, input_energy, blocks, workspace, whitened=True)
+        return self._step(cost, s, step_size, out, new_state, noise, input_energy, blocks, workspace, force_generic, whitened=True)
 
     # ---- whitened coordinates for the costs WITHOUT the Gaussian algebra (at most 128 inducing points, launch-bound sizes) ----
-    def whitened_generic_applies(self, cost, j: int) -> bool:
+    def whitened_generic_applies(self, cost, j: int, force_generic: bool = False) -> bool:
         """True if a loop over `j` particle columns may keep this cost's particles whitened: every step is then ONE launch
         (pls_ipb_whitened_generic_step: the one-launch small-rank step over k(X,Z) Lc^-T with the prior as rows) instead of the
         solve, the coloured noise and the step.  The operand is built on first use."""
-        if not (self.whitened and cost.is_native()) or self._is_gaussian(cost):
+        if not (self.whitened and cost.is_native()) or self._is_gaussian(cost, force_generic):
             return False
         if not (1 <= self.approximation_dimension <= self.SMALL_RANK_MAX) or self._chol.Linv is None or j <= 0:
             return False
@@ -298,7 +333,7 @@ class InducingPointBasis(PLSBasis):
         if whitened:
             assert self.whitened, "whitened coordinates are switched off on this basis"
             if not gaussian:
-                assert self.whitened_generic_applies(cost, j), "this cost / size has no whitened step: stay in the original coordinates"
+                assert self.whitened_generic_applies(cost, j, force_generic), "this cost / size has no whitened step: stay in the original coordinates"
                 desc = self._desc()
                 return StepRoute(None, "pls_ipb_whitened_generic_step", (desc, cd, y.data_ptr()), (),
                                  lib.pls_ipb_whitened_generic_workspace_bytes(desc, j), self._holds(y), one_launch=True,

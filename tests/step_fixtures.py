@@ -1,8 +1,10 @@
 """Loader for tests/golden/oracle_step_vectors.npz (written by tests/golden/make_oracle_step_vectors.py): the frozen
 Langevin step.  Builds the oracle's objects -- and, for the GPU tests, the library's -- from the stored inputs."""
+import math
 import os
 
 import numpy as np
+import pytest
 import torch
 
 from oracle import pls_oracle as O
@@ -92,7 +94,7 @@ class ExactProblem:
         self.a = ints((mk, n), amax)
         self.u = ints((mk, j), umax)
         self.y = ints((n,), ymax)
-        self.xi = ints((mk, j), xmax)
+        self.xi = self.injected = ints((mk, j), xmax)  # (the orthonormal basis' noise is white: injected as it is)
         self.lam = 2.0 ** torch.randint(lam_exp[0], lam_exp[1] + 1, (mk,), generator=g, dtype=torch.int64).double()
         self.bound = self._bound(amax, umax, ymax, xmax, lam_exp)
 
@@ -138,6 +140,288 @@ class ExactProblem:
             out = uc + out
         e = ((f - self.y[:, None]) ** 2).sum(0) / (2 * EXACT_S2) + 0.5 * (uc * uc / self.lam[:, None]).sum(0)
         return out, e
+
+
+# ---- exact problems of the inducing-point basis -------------------------------------------------------------------------------
+# k(Z,Z) = Lc Lc^T with Lc = diag(d) (I + Nl): d powers of two, Nl strictly lower triangular with small integers at (odd row,
+# even column) only, so that Nl Nl = 0 and Lc^-1 = (I - Nl) diag(1 / d) exactly.  Every pivot of the factorisation is a power
+# of four (sqrt and reciprocal exact), every Schur complement, substitution partial sum, solve, projection, back-projection,
+# whitened operator and update a dyadic number of a few dozen bits: exact in any summation order (checked by _bound from the
+# data, not assumed), so every route of the basis must reproduce plain fp64 torch on the host bit for bit, and the
+# conditioning of k(Z,Z) does not enter.
+def _unit(x):
+    """the finest bit of a tensor of dyadic numbers: the largest power of two that divides every entry (1 for all zeros)"""
+    nz = x[x != 0]
+    if nz.numel() == 0:
+        return 1.0
+    _, e = torch.frexp(nz)  # x = m 2^e, m in [0.5, 1) with 53 bits: the lowest set bit of m 2^53 gives the unit
+    mant = (torch.ldexp(nz, 53 - e)).abs().to(torch.int64)
+    low = mant & -mant
+    return float(torch.ldexp(low.double(), e - 53).min())
+
+
+class ExactIpbProblem:
+    """M inducing points, N data rows, J particles.  ``nmax``: range of Nl's entries, ``emax``: d = 2^e with e in 0..emax,
+    ``kmax`` / ``umax`` / ``ximax`` / ``ymax``: ranges of k(Z,X), U, xi, y.  ``eta``: the step size the bound is proved for
+    (and for eta / 4 .. 4 eta); ``chain``: number of consecutive whitened steps the bound must also hold for."""
+
+    def __init__(self, m, n, j, seed=0, nmax=2, emax=2, kmax=3, umax=3, ximax=3, ymax=8, eta=EXACT_ETA, chain=0):
+        g = torch.Generator().manual_seed(seed)
+
+        def ints(shape, r):
+            return torch.randint(-r, r + 1, shape, generator=g, dtype=torch.int64).double()
+
+        self.m, self.mk, self.n, self.j, self.eta, self.seed = m, m, n, j, eta, seed
+        idx = torch.arange(m)
+        mask = (idx[:, None] % 2 == 1) & (idx[None, :] % 2 == 0) & (idx[:, None] > idx[None, :])
+        self.nl = ints((m, m), nmax) * mask
+        self.d = 2.0 ** torch.randint(0, emax + 1, (m,), generator=g, dtype=torch.int64).double()
+        eye = torch.eye(m, dtype=torch.float64)
+        self.lc = self.d[:, None] * (eye + self.nl)
+        self.linv = (eye - self.nl) / self.d[None, :]
+        self.kzz = self.lc @ self.lc.T
+        self.kzx = ints((m, n), kmax)
+        self.u = ints((m, j), umax)
+        self.xi = ints((m, j), ximax)
+        self.y = ints((n,), ymax)
+        self.e = self.injected = self.lc @ self.xi  # the coloured noise pls_ipb_step takes as injected noise: integers
+        self.s = self.linv @ self.u  # the whitened particles
+        self.bits = {}
+        self._bound(chain)
+        self.energy_exact = max(v for k, v in self.bits.items() if k.startswith("energy")) < 52
+
+    # -- the bit budget -------------------------------------------------------------------------------------------------------
+    def _fits(self, name, a, b, limit=52):
+        """The product a @ b in any summation order: (sum of absolute values) / (finest bit of a term) must stay below
+        2^limit; returns the product, computed in fp64 (then exact)."""
+        unit = _unit(a) * _unit(b)
+        bits = math.log2(max((a.abs() @ b.abs()).max().item() / unit, 1.0))
+        self.bits[name] = max(self.bits.get(name, 0.0), bits)
+        assert bits < limit, f"exact inducing-point problem {self.m}x{self.n}x{self.j}: {name} needs {bits:.1f} bits"
+        return a @ b
+
+    def _fits_sum(self, name, *terms, limit=52):
+        unit = min(_unit(t) for t in terms)
+        bits = math.log2(max(sum(t.abs() for t in terms).max().item() / unit, 1.0))
+        self.bits[name] = max(self.bits.get(name, 0.0), bits)
+        assert bits < limit, f"exact inducing-point problem {self.m}x{self.n}x{self.j}: {name} needs {bits:.1f} bits"
+
+    def _bound(self, chain):
+        """Proves from the data that every product a route forms is exact: the factorisation's Schur complements, both
+        substitution sweeps, the inverse-factor products, the explicit inverse, the projection, the back-projection, the
+        Gaussian constants, the whitened operators and steps, the prior-row operand (M a power of four), the final update
+        for step sizes eta / 4 .. 4 eta, and ``chain`` consecutive whitened steps.  The energies' budget is recorded
+        (bits["energy ..."]) and decides ``energy_exact``; everything else is asserted."""
+        m, f = self.m, self._fits
+        lc, li, u, kzx, y = self.lc, self.linv, self.u, self.kzx, self.y[:, None]
+        f("Lc Lc^T", lc, lc.T)  # the trailing updates of the factorisation, in any blocking
+        f("Lc^-1 Lc", li, lc)  # the panels' triangular solves and the inverse factor's substitution
+        s = f("Lc^-1 U", li, u)
+        f("forward substitution", li, u.abs() + lc.abs() @ s.abs())  # u_b - sum_k L_bk s_k, then the diagonal block's inverse
+        v = f("Lc^-T S", li.T, s)
+        f("backward substitution", li.T, s.abs() + lc.T.abs() @ v.abs())
+        w = f("W = Lc^-T Lc^-1", li.T, li)
+        f("W U", w, u)
+        f("Lc xi", lc, self.xi)
+        fx = f("F = k(X,Z) V", kzx.T, v)
+        gr = (fx - y) / EXACT_S2
+        self._fits_sum("G = (F - y) / sigma2", fx / EXACT_S2, y / EXACT_S2)
+        dd = f("k(Z,X) G", kzx, gr)
+        b = f("B = k(Z,X) k(X,Z)", kzx, kzx.T)
+        c = f("c = k(Z,X) y", kzx, y)
+        bv = f("B V", b, v)
+        self._fits_sum("(B V - c) / sigma2", bv / EXACT_S2, c / EXACT_S2)
+        bp = b / EXACT_S2 + m * torch.eye(m, dtype=torch.float64)
+        t2 = f("Lc^-1 B'", li, bp)
+        q = f("Q = Lc^-1 B' Lc^-T", li, t2.T)
+        f("Q (other order)", t2, li.T)
+        ct = f("c~", li, c / EXACT_S2)
+        pt = f("Pt = Lc^-T Q", li.T, q)
+        self.q, self.ct = q, ct
+        qs = f("Q S", q, s)
+        f("P U", pt.T, u)
+        self._fits_sum("Q S - c~", qs, ct)
+        f("Lc dS", lc, (qs - ct).abs() + 8 * self.xi.abs())
+        root = math.isqrt(m)
+        if root * root == m and root & (root - 1) == 0:  # sqrt(M) exact: the prior-row operand k(X,Z) Lc^-T over sqrt(M) Lc^-T
+            awa = torch.cat([f("k(X,Z) Lc^-T", kzx.T, li.T), root * li.T])
+            fa = f("Awa S", awa, s)
+            ga = torch.cat([(fa[: self.n] - y) / EXACT_S2, fa[self.n:]])
+            f("Awa^T G", awa.T, ga)
+        # the update [U +] -eta D - eta M V + sqrt(2 eta) e over eta / 4 .. 4 eta, in units of its finest bit
+        for lo, hi in ((self.eta / 4, 4 * self.eta),):
+            self._fits_sum("update", u, hi * dd, hi * m * v, math.sqrt(2 * hi) * self.e, lo * dd, lo * m * v, math.sqrt(2 * lo) * self.e)
+            self._fits_sum("whitened update", s, hi * qs, hi * ct, math.sqrt(2 * hi) * self.xi, lo * qs, lo * ct,
+                           math.sqrt(2 * lo) * self.xi)
+        # energies: the three forms the routes use (data term + prior; fast path from V, B V, c; whitened quadratic form)
+        yty = (y * y).sum()
+        self._energy_bits("energy general", ((fx - y) ** 2).sum(0) / (2 * EXACT_S2) + 0.5 * m * (v * v).sum(0), _unit(fx) ** 2)
+        self._energy_bits("energy fast", ((v * bv).abs().sum(0) + 2 * (v * c).abs().sum(0) + yty) / (2 * EXACT_S2)
+                          + 0.5 * m * (v * v).sum(0), _unit(v) * _unit(bv))
+        self._energy_bits("energy whitened", 0.5 * (s * qs).abs().sum(0) + (s * ct).abs().sum(0) + yty / (2 * EXACT_S2),
+                          0.5 * _unit(s) * _unit(qs))
+        state = s
+        for k in range(chain):  # consecutive whitened steps with fresh noise: the state's bits grow every step
+            xi = self.chain_noise(k)
+            qs = f(f"chain step {k}: Q S", q, state)
+            new = state - self.eta * (qs - ct) + math.sqrt(2 * self.eta) * xi
+            self._fits_sum(f"chain step {k}: update", state, self.eta * qs, self.eta * ct, math.sqrt(2 * self.eta) * xi)
+            state = new
+
+    def _energy_bits(self, name, magnitude, unit):
+        self.bits[name] = math.log2(max(magnitude.max().item() / unit, 1.0))
+
+    def chain_noise(self, k):
+        g = torch.Generator().manual_seed(1000 + k)
+        return torch.randint(-3, 4, (self.m, self.j), generator=g, dtype=torch.int64).double()
+
+    # -- the library's objects ------------------------------------------------------------------------------------------------
+    def cost(self, P):
+        return P.costs.GaussianCost(EXACT_S2, self.y, P.links.IdentityLinkFunction())
+
+    def basis(self, P, host_factor=False, explicit_inverse=False):
+        """the device factorisation of k(Z,Z), or (``host_factor``) the constructed factor uploaded (factor_from_host)"""
+        return P.basis.InducingPointBasis.from_gram(self.kzz.cuda(), self.kzx.cuda(), cholesky_factor=self.lc if host_factor else None,
+                                                    explicit_inverse=explicit_inverse, poison_padding=True)
+
+    # -- the steps, written out in fp64 on the host (exact here) ----------------------------------------------------------------
+    def _drift(self, v, reverse=False):
+        """(k(Z,X) G + M V, energies) of V = k(Z,Z)^-1 U; ``reverse``: every contraction summed in the opposite order"""
+        mm = (lambda a, b: a.flip(1) @ b.flip(0)) if reverse else (lambda a, b: a @ b)
+        f = mm(self.kzx.T, v)
+        r = f - self.y[:, None]
+        d = mm(self.kzx, r / EXACT_S2) + self.m * v
+        e = (r * r).sum(0) / (2 * EXACT_S2) + 0.5 * self.m * (v * v).sum(0)
+        return d, e
+
+    def solve(self, u, reverse=False):
+        mm = (lambda a, b: a.flip(1) @ b.flip(0)) if reverse else (lambda a, b: a @ b)
+        return mm(self.linv.T, mm(self.linv, u))
+
+    def step(self, cols=None, eta=None, noise=True, new_state=False, reverse=False):
+        """The step of pls_ipb_step on columns ``cols`` (default: all): -eta k(Z,X) G - eta M V + sqrt(2 eta) e, e = Lc xi the
+        injected noise (already coloured, as the entry's contract says), and the energies cost + M/2 |V|^2 of the input
+        particles.  ``eta``: a number or one step size per column of ``cols``."""
+        cols = torch.arange(self.j) if cols is None else torch.as_tensor(cols)
+        eta = torch.as_tensor(self.eta if eta is None else eta, dtype=torch.float64).expand(len(cols))[None, :]
+        uc = self.u[:, cols]
+        d, e = self._drift(self.solve(uc, reverse), reverse)
+        out = -eta * d
+        if noise:
+            out = out + (2 * eta).sqrt() * self.e[:, cols]
+        return (uc + out if new_state else out), e
+
+    def whitened_step(self, cols=None, eta=None, noise=True, new_state=False, state=None, xi=None, reverse=False):
+        """The same step in whitened coordinates S = Lc^-1 U (default state: the whitened particles): dS = Lc^-1 (-eta k(Z,X) G
+        - eta M V) + sqrt(2 eta) xi with V = Lc^-T S; the injected noise xi is white (pls_ipb_whitened_step's contract)."""
+        mm = (lambda a, b: a.flip(1) @ b.flip(0)) if reverse else (lambda a, b: a @ b)
+        cols = torch.arange(self.j) if cols is None else torch.as_tensor(cols)
+        eta = torch.as_tensor(self.eta if eta is None else eta, dtype=torch.float64).expand(len(cols))[None, :]
+        sc = (self.s if state is None else state)[:, cols]
+        d, e = self._drift(mm(self.linv.T, sc), reverse)
+        out = -eta * mm(self.linv, d)
+        if noise:
+            out = out + (2 * eta).sqrt() * (self.xi if xi is None else xi)[:, cols]
+        return (sc + out if new_state else out), e
+
+
+# the shapes tests/test_gpu_exact_ipb.py runs; tests/test_host_logic.py proves on the CPU that the reference alone is exact on each
+IPB_FACTOR_M = [1, 2, 17, 63, 64, 65, 127, 128, 129, 200, 257, 520, 1024, 1153]  # chol.hip: panel 64, block 128, strip depth 32
+# (M, J): J in {1, 5, 64, 65, 700, 1024, 4100} across M; 960 and 1088 have an odd number of 64-row tile rows (ragged pairs)
+IPB_SOLVE_CASES = [(1, 1), (2, 5), (17, 64), (63, 65), (64, 5), (65, 700), (127, 64), (128, 65), (129, 1024), (200, 5), (257, 700),
+                   (520, 65), (960, 1024), (1088, 700), (1024, 1024), (1024, 700), (1024, 4100), (1153, 64)]
+# (M, N, J): N off the 128 grid, ragged last column tiles, the narrow shard M = 1024 with J = 700 / 1024, the mid-size config
+IPB_STEP_SHAPES = [(64, 300, 40), (200, 1500, 333), (129, 5000, 200), (1024, 3000, 700), (1024, 3000, 1024), (1024, 8000, 512)]
+# (M, N, J, rows per chunk): N = 300 runs in one split-K slab, N = 20000 in several; the last: three chunks
+IPB_GENERAL_CASES = [(200, 300, 333, None), (200, 20000, 333, None), (200, 20000, 333, 20000 // 3), (1024, 8000, 512, None)]
+IPB_ONE_LAUNCH_SHAPES = [(100, 10, 64), (333, 17, 37), (1000, 32, 100), (1100, 128, 90), (520, 65, 16)]  # (N, M, J)
+IPB_PREP_M = [1, 2, 3, 5, 15, 16, 17, 18, 31, 32, 33, 48, 49, 63, 64, 65, 80, 81, 97, 112, 113, 127]
+IPB_WHITENED_GENERIC_SHAPES = [(50, 1, 8), (100, 4, 64), (333, 16, 37), (1000, 64, 100)]  # (N, M, J), M a power of four
+# three consecutive whitened steps: every step multiplies the state's bits by those of eta Q, so the ranges shrink (Nl, k(Z,X) in
+# [-1, 1], d = 1) and eta grows until the third step's Q S fits one mantissa (ExactIpbProblem._bound, chain=3)
+IPB_CHAIN_CASES = [(200, 100, 70, dict(eta=2.0 ** -13, nmax=1, emax=0, kmax=1)),
+                   (320, 100, 130, dict(eta=2.0 ** -15, nmax=1, emax=0, kmax=1, umax=1, ymax=2)),
+                   (64, 60, 40, dict(eta=2.0 ** -11, nmax=1, emax=0, kmax=1))]
+_exact_ipb = {}
+
+
+def exact_ipb(m, n, j, **kw):
+    """the exact problem of a shape, built (and its bit budget proved) once per process"""
+    key = (m, n, j, tuple(sorted(kw.items())))
+    if key not in _exact_ipb:
+        if len(_exact_ipb) >= 6:
+            _exact_ipb.clear()
+        _exact_ipb[key] = ExactIpbProblem(m, n, j, seed=m + n + j, **kw)
+    return _exact_ipb[key]
+
+
+def exact_ipb_cases():
+    """every (M, N, J, options) tests/test_gpu_exact_ipb.py builds"""
+    cases = [(m, 16, 8, {}) for m in IPB_FACTOR_M] + [(m, 16, j, {}) for m, j in IPB_SOLVE_CASES] + [(200, 16, 65, {})]
+    cases += [(m, n, j, {}) for m, n, j in IPB_STEP_SHAPES] + [(m, n, j, {}) for m, n, j, _ in IPB_GENERAL_CASES]
+    cases += [(m, n, j, {}) for n, m, j in IPB_ONE_LAUNCH_SHAPES + IPB_WHITENED_GENERIC_SHAPES]
+    cases += [(m, 200 + m, j, {}) for m in IPB_PREP_M for j in (1, 17, 50)]
+    cases += [(m, n, j, dict(chain=3, **kw)) for m, n, j, kw in IPB_CHAIN_CASES]
+    return list({(m, n, j, tuple(sorted(kw.items()))): (m, n, j, kw) for m, n, j, kw in cases}.values())
+
+
+# ---- the checks both exact files share (tests/test_gpu_exact_step.py, tests/test_gpu_exact_ipb.py) ----------------------------
+BLOCK_ETAS = [EXACT_ETA, 0.0, 4 * EXACT_ETA, EXACT_ETA / 4]  # sqrt(2 eta) = 2^-10, 0, 2^-9, 2^-11: all exact
+
+
+class option:
+    def __init__(self, P, opt, mode):
+        self.L, self.lib, self.opt, self.mode = P.pkg._lib, P.pkg._lib.load(), opt, mode
+
+    def __enter__(self):
+        self.prev = self.lib.pls_get_option(self.opt)
+        self.L.check(self.lib.pls_set_option(self.opt, self.mode), "pls_set_option")
+
+    def __exit__(self, *exc):
+        self.L.check(self.lib.pls_set_option(self.opt, self.prev), "pls_set_option")
+        return False
+
+
+def assert_exact(ex, got, cols=None, energy=None, eta=EXACT_ETA, noise=True, new_state=False, what=""):
+    want, e_want = ex.step(cols, eta, noise, new_state)
+    got = got.cpu() if cols is None else got.cpu()[:, cols]
+    assert torch.isfinite(got).all(), what
+    bad = (got != want).any(dim=1).nonzero().flatten()
+    assert bad.numel() == 0, f"{what}: {bad.numel()} rows differ from the exact step, first {bad[:8].tolist()}, " \
+                             f"max |diff| {(got - want).abs().max().item():.3e}"
+    if energy is not None:
+        e = energy.cpu() if cols is None else energy.cpu()[cols]
+        rel = ((e - e_want).abs() / e_want.abs()).max().item()
+        assert rel <= 1e-13, f"{what}: energy by-product, relative error {rel:.2e}"
+        if getattr(ex, "energy_exact", False):  # (the quadratic forms fit one mantissa too: ExactIpbProblem._bound)
+            assert torch.equal(e, e_want), f"{what}: energy by-product differs from the exact one, relative error {rel:.2e}"
+
+
+def run_forms(P, ex, gb, cost, cols, what, force_generic=True):
+    """The step out of place (fresh output, with energies), into a strided output buffer (guard columns untouched), as the
+    new state, and with per-block step sizes (one block frozen) -- each against the exact step."""
+    j = ex.j
+    u = ex.u.cuda()
+    xi = P.basis.NoiseSpec(injected=ex.injected.cuda())
+    e = torch.full((j,), float("nan"), device="cuda")
+    got = gb.fused_step(cost, u, EXACT_ETA, noise=xi, force_generic=force_generic, input_energy=e)
+    assert_exact(ex, got, cols, energy=e, what=f"{what}: out of place")
+    wide = torch.full((ex.mk, j + 64), float("nan"), device="cuda")
+    out = wide[:, :j]
+    gb.fused_step(cost, u, EXACT_ETA, noise=xi, force_generic=force_generic, out=out)
+    assert_exact(ex, out, cols, what=f"{what}: strided output")
+    assert wide[:, j:].isnan().all(), f"{what}: the step wrote past J"
+    new = gb.fused_step(cost, u, EXACT_ETA, noise=xi, force_generic=force_generic, new_state=True)
+    assert_exact(ex, new, cols, new_state=True, what=f"{what}: new state")
+    bc = -(-j // len(BLOCK_ETAS))
+    blocks = P.basis.BlockSpec(bc, torch.tensor(BLOCK_ETAS, device="cuda"))
+    got = gb.fused_step(cost, u, 0.0, noise=xi, force_generic=force_generic, blocks=blocks, new_state=True)
+    etas = torch.tensor(BLOCK_ETAS)[torch.arange(j) // bc]
+    assert_exact(ex, got, cols, eta=etas if cols is None else etas[cols], new_state=True, what=f"{what}: blocks")
+    assert torch.equal(got[:, bc:2 * bc].cpu(), ex.u[:, bc:2 * bc]), f"{what}: a frozen block moved"
+    with pytest.raises(P.pkg._lib.PlsHipError):  # in place: the entries refuse an output that aliases the particles
+        P.pkg._lib.check(gb._route(cost, j, force_generic).call(None, u.data_ptr(), j, j, EXACT_ETA, xi.desc(), u.data_ptr(), j,
+                                                                 0, None, None, 0, P.pkg._lib.stream_ptr()), "in place")
 
 
 def spread_columns(j, per_tile=2, seed=0):

@@ -9,28 +9,13 @@ energy by-product is compared per particle at 1e-13."""
 import pytest
 import torch
 
-from step_fixtures import (EXACT_ETA, ExactProblem, probe_winograd, spread_columns, step_wg, winograd_option,
-                           wino_one_chunk_bytes)
+from step_fixtures import (EXACT_ETA, ExactProblem, assert_exact, option, probe_winograd, run_forms, spread_columns, step_wg,
+                           winograd_option, wino_one_chunk_bytes)
 from test_gpu_ksplit import ksplit
 from test_gpu_parity import P, _f64_default  # noqa: F401  (fixtures)
 from test_gpu_rows import row_blocks
 
 pytestmark = pytest.mark.gpu
-
-BLOCK_ETAS = [EXACT_ETA, 0.0, 4 * EXACT_ETA, EXACT_ETA / 4]  # sqrt(2 eta) = 2^-10, 0, 2^-9, 2^-11: all exact
-
-
-class option:
-    def __init__(self, P, opt, mode):
-        self.L, self.lib, self.opt, self.mode = P.pkg._lib, P.pkg._lib.load(), opt, mode
-
-    def __enter__(self):
-        self.prev = self.lib.pls_get_option(self.opt)
-        self.L.check(self.lib.pls_set_option(self.opt, self.mode), "pls_set_option")
-
-    def __exit__(self, *exc):
-        self.L.check(self.lib.pls_set_option(self.opt, self.prev), "pls_set_option")
-        return False
 
 
 def sample(j):
@@ -38,46 +23,6 @@ def sample(j):
     if j <= 512:
         return None
     return torch.unique(torch.cat([spread_columns(j), torch.tensor([j - 1])]))
-
-
-def assert_exact(ex, got, cols=None, energy=None, eta=EXACT_ETA, noise=True, new_state=False, what=""):
-    want, e_want = ex.step(cols, eta, noise, new_state)
-    got = got.cpu() if cols is None else got.cpu()[:, cols]
-    assert torch.isfinite(got).all(), what
-    bad = (got != want).any(dim=1).nonzero().flatten()
-    assert bad.numel() == 0, f"{what}: {bad.numel()} rows differ from the exact step, first {bad[:8].tolist()}, " \
-                             f"max |diff| {(got - want).abs().max().item():.3e}"
-    if energy is not None:
-        e = energy.cpu() if cols is None else energy.cpu()[cols]
-        rel = ((e - e_want).abs() / e_want.abs()).max().item()
-        assert rel <= 1e-13, f"{what}: energy by-product, relative error {rel:.2e}"
-
-
-def run_forms(P, ex, gb, cost, cols, what, force_generic=True):
-    """The step out of place (fresh output, with energies), into a strided output buffer (guard columns untouched), as the
-    new state, and with per-block step sizes (one block frozen) -- each against the exact step."""
-    j = ex.j
-    u = ex.u.cuda()
-    xi = P.basis.NoiseSpec(injected=ex.xi.cuda())
-    e = torch.full((j,), float("nan"), device="cuda")
-    got = gb.fused_step(cost, u, EXACT_ETA, noise=xi, force_generic=force_generic, input_energy=e)
-    assert_exact(ex, got, cols, energy=e, what=f"{what}: out of place")
-    wide = torch.full((ex.mk, j + 64), float("nan"), device="cuda")
-    out = wide[:, :j]
-    gb.fused_step(cost, u, EXACT_ETA, noise=xi, force_generic=force_generic, out=out)
-    assert_exact(ex, out, cols, what=f"{what}: strided output")
-    assert wide[:, j:].isnan().all(), f"{what}: the step wrote past J"
-    new = gb.fused_step(cost, u, EXACT_ETA, noise=xi, force_generic=force_generic, new_state=True)
-    assert_exact(ex, new, cols, new_state=True, what=f"{what}: new state")
-    bc = -(-j // len(BLOCK_ETAS))
-    blocks = P.basis.BlockSpec(bc, torch.tensor(BLOCK_ETAS, device="cuda"))
-    got = gb.fused_step(cost, u, 0.0, noise=xi, force_generic=force_generic, blocks=blocks, new_state=True)
-    etas = torch.tensor(BLOCK_ETAS)[torch.arange(j) // bc]
-    assert_exact(ex, got, cols, eta=etas if cols is None else etas[cols], new_state=True, what=f"{what}: blocks")
-    assert torch.equal(got[:, bc:2 * bc].cpu(), ex.u[:, bc:2 * bc]), f"{what}: a frozen block moved"
-    with pytest.raises(P.pkg._lib.PlsHipError):  # in place: the entries refuse an output that aliases the particles
-        P.pkg._lib.check(gb._route(cost, j, force_generic).call(None, u.data_ptr(), j, j, EXACT_ETA, xi.desc(), u.data_ptr(), j,
-                                                                 0, None, None, 0, P.pkg._lib.stream_ptr()), "in place")
 
 
 # -------------------------------------------------------------------------------------------------------------------------

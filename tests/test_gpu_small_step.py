@@ -15,7 +15,8 @@ pytestmark = pytest.mark.gpu
 
 from oracle import pls_oracle as O
 
-from test_gpu_parity import FUZZ_SEED, TOL, build_ipb, build_onb, cu, make_costs, make_problem, relerr, step_tolerance  # noqa: E402
+from test_gpu_parity import (FUZZ_SEED, TOL, build_ipb, build_onb, cu, make_costs, make_problem, relerr, row_relerr,  # noqa: E402
+                             step_tolerance)
 from test_gpu_parity import P, _f64_default  # noqa: F401,E402  (fixtures)
 
 
@@ -612,7 +613,11 @@ def test_whitened_step_of_every_cost_against_the_oracle(P, route, n, m, j, d):
     """pls_ipb_whitened_generic_step (inducing_point.py:117-150 in the coordinates S = Lc^-1 U: ONE launch, the prior as M rows of
     the forward operand, white noise) against the oracle's update in the ORIGINAL coordinates with the coloured noise e = Lc xi
     injected: U + dU = Lc (S + dS), the energies of the input particles, delta and new-state forms, column blocks with their own
-    step sizes; and against the library's own step in the original coordinates over the same Philox draws."""
+    step sizes; and against the library's own step in the original coordinates over the same Philox draws.  Beside relerr (every
+    row against the largest entry of the matrix) the step is held row by row (row_relerr): rows of small magnitude are
+    legitimately less accurate relative to themselves, and two host computations of the same step show by how much -- the oracle
+    with LAPACK's solve and the oracle with the product solve Linv^T (Linv u); the bound is 8 x their per-row difference, with
+    the tolerance of the relerr check as floor."""
     pr = make_problem(n, m, j, d, seed=17 * n + m + FUZZ_SEED)
     pr["ls"] = pr["ls"] * 0.35
     ob, gb = build_ipb(P, pr)
@@ -624,6 +629,7 @@ def test_whitened_step_of_every_cost_against_the_oracle(P, route, n, m, j, d):
     eta = 1e-3
     s_dev = gb.whiten(cu(u))
     assert relerr(s_dev, torch.linalg.solve_triangular(lc, u, upper=False)) < 1e-11 * max(1.0, cond / 1e5)
+    linv = torch.linalg.solve_triangular(lc, torch.eye(m), upper=False)
     checked = 0
     route(1)
     for name, oc, gc in make_costs(P, pr["y"], pr["fstar"], pr["gen"]):
@@ -644,6 +650,15 @@ def test_whitened_step_of_every_cost_against_the_oracle(P, route, n, m, j, d):
         s_new = gb.whitened_step(gc, s_dev, eta, noise=spec, new_state=True, input_energy=e_in)
         assert relerr(s_new, s_dev + ds) < 1e-14
         assert relerr(gb.unwhiten(ds), want) < tol, name
+        lapack_solve = O._chol_solve
+        try:  # the same step on the host with the product solve in place of LAPACK's
+            O._chol_solve = lambda k, b: linv.T @ (linv @ b)
+            want_products = O.PLS(ob, oc).calculate_particle_update(u.clone(), eta, noise=e_noise)
+        finally:
+            O._chol_solve = lapack_solve
+        host_pair, per_row = row_relerr(want_products, want), row_relerr(gb.unwhiten(ds), want)
+        print(f"per row, {name} (m {m}, cond {cond:.1e}): device {per_row:.2e}, host pair {host_pair:.2e}, floor {tol:.1e}")
+        assert per_row <= max(tol, 8 * host_pair), f"{name}: per row {per_row:.2e}, host pair {host_pair:.2e}, floor {tol:.1e}"
         assert relerr(gb.unwhiten(s_new), u + want) < max(tol, 1e-12), name
         v = torch.cholesky_solve(u, lc)
         e_want = oc.calculate_cost(ob.calculate_untransformed_train_prediction_samples(u)) + 0.5 * m * (v * v).sum(dim=0)
