@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define PLSHIP_ABI_VERSION 6
+#define PLSHIP_ABI_VERSION 7
 
 typedef enum {
   PLS_OK = 0,
@@ -41,8 +41,16 @@ typedef enum {
 } pls_status;
 
 /* base kernel k (third party gpytorch ScaleKernel(RBFKernel(ard)) in the reference,
- * constructed at experiments/uci/regression/main.py:171-173; MockKernel = mockers/kernel.py:13-23) */
-typedef enum { PLS_KERNEL_RBF_ARD = 0, PLS_KERNEL_LINEAR = 1 } pls_kernel_kind;
+ * constructed at experiments/uci/regression/main.py:171-173; MockKernel = mockers/kernel.py:13-23).
+ * MATERN12 / 32 / 52: gpytorch ScaleKernel(MaternKernel(nu = 1/2, 3/2, 5/2)) with ARD lengthscales (since ABI 7):
+ * with r = |(a - b) / lengthscale| and t = sqrt(2 nu) r,  k = outputscale * p(t) * exp(-t),  p = 1, 1 + t, 1 + t + t^2/3. */
+typedef enum {
+  PLS_KERNEL_RBF_ARD = 0,
+  PLS_KERNEL_LINEAR = 1,
+  PLS_KERNEL_MATERN12 = 2,
+  PLS_KERNEL_MATERN32 = 3,
+  PLS_KERNEL_MATERN52 = 4
+} pls_kernel_kind;
 
 /* src/projected_langevin_sampling/costs/{gaussian,poisson,bernoulli,student_t,multimodal}.py */
 typedef enum {
@@ -367,7 +375,7 @@ int pls_timeline_end(float *ms, int32_t *tags, int32_t capacity, int32_t *count)
 
 /* out(n1 x n2) = k(x1, x2); x1 (n1 x d), x2 (n2 x d) row-major contiguous.
  * Replaces kernel.base_kernel(x1=.., x2=..) at orthonormal.py:36-41, inducing_point.py:41-46.
- * lengthscale: d values (RBF_ARD; ignored for LINEAR). */
+ * lengthscale: d values (every kind except LINEAR needs it; ignored for LINEAR). */
 int pls_kernel_gram(int32_t kernel_kind, const double *x1, int64_t n1, const double *x2, int64_t n2,
                     int64_t d, const double *lengthscale, double outputscale, double *out, int64_t ldout,
                     void *stream);
@@ -672,6 +680,7 @@ int pls_ipb_prior_energy(const pls_ipb_desc *basis, const double *U, int64_t ldu
  * (:108-113).  No N x N Gram matrix is formed (the reference builds one just to read its diagonal, :64-69).
  * indices: m int64 (device), count: 1 int64 (device) = number of points selected (m unless the threshold stopped it).
  * Nothing synchronises: the pivot of every iteration stays on the device.  Ties are broken towards the smaller index.
+ * kernel_kind: any pls_kernel_kind; lengthscale: d values (every kind except LINEAR needs it; ignored for LINEAR).
  * workspace: pls_select_inducing_workspace_bytes(n, m) bytes. */
 size_t pls_select_inducing_workspace_bytes(int64_t n, int64_t m);
 int pls_select_inducing_conditional_variance(int32_t kernel_kind, const double *x, int64_t n, int64_t d,

@@ -4,8 +4,8 @@ jswu18/projected-langevin-sampling behind the reference's PLS / basis / cost / l
 All numerics run in libplship.so (hand-written HIP for gfx950, see csrc/); this package is the thin host
 side: it owns device memory through torch tensors and calls the C ABI (include/plship.h) with raw pointers."""
 from . import _lib
-from .kernel import ARDKernel, LinearKernel, PLSKernel
+from .kernel import ARDKernel, LinearKernel, MaternKernel, PLSKernel
 from .projected_langevin_sampling import PLS
 from .trainers import EarlyStopper, train_pls, train_pls_captured
 
-__all__ = ["PLS", "PLSKernel", "ARDKernel", "LinearKernel", "EarlyStopper", "train_pls", "train_pls_captured", "_lib"]
+__all__ = ["PLS", "PLSKernel", "ARDKernel", "MaternKernel", "LinearKernel", "EarlyStopper", "train_pls", "train_pls_captured", "_lib"]

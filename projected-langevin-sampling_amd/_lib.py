@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get("PLSHIP_LIBRARY") or os.path.join(_HERE, "libplship.so
 
 # enums (include/plship.h)
 KERNEL_RBF_ARD, KERNEL_LINEAR = 0, 1
+KERNEL_MATERN12, KERNEL_MATERN32, KERNEL_MATERN52 = 2, 3, 4
 COST_GAUSSIAN, COST_POISSON, COST_BERNOULLI, COST_STUDENT_T, COST_MULTIMODAL = range(5)
 LINK_IDENTITY, LINK_SQUARE, LINK_SIGMOID, LINK_PROBIT = range(4)
 DERIV_REFERENCE, DERIV_AUTOGRAD = 0, 1
@@ -203,7 +204,7 @@ SIGNATURES = {
     "pls_ipb_step_blocks": (C.c_int, [_ID, _CD, _P, _P, _I64, _I64, _BD, _ND, _P, _I64, _I32, _I32, _P, _P, _SZ, _P]),
 }
 
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 _lib = None
 

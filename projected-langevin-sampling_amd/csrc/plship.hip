@@ -694,8 +694,9 @@ static int64_t cost_value_partial_rows(int64_t I, int64_t J) { return use_big_ti
 // exp(x) for x <= 0 (the RBF exponent): n = rint(x log2 e), r = x - n ln 2 (two-piece ln 2), degree-13 Taylor polynomial
 // in Horner form (|r| <= 0.347: truncation 4e-18 relative), scaled by 2^n with v_ldexp (gradual underflow as libm).
 // Within 1 ulp of the correctly rounded value; about half the instructions of the library exp (no special-case
-// ladder, constants in scalar registers).
-__device__ __forceinline__ double exp_nonpos(double x) {
+// ladder, constants in scalar registers).  exp_nonpos_unguarded is the same without the underflow select: meaningless
+// below x = -745.2, where the caller selects 0 itself.
+__device__ __forceinline__ double exp_nonpos_unguarded(double x) {
   const double n = rint(x * 1.4426950408889634074);
   double r = fma(n, -6.93147180369123816490e-01, x);
   r = fma(n, -1.90821492927058770002e-10, r);
@@ -713,8 +714,29 @@ __device__ __forceinline__ double exp_nonpos(double x) {
   p = fma(p, r, 0.5);
   p = fma(p, r, 1.0);
   p = fma(p, r, 1.0);
-  const double v = ldexp(p, (int)n);
+  return ldexp(p, (int)n);
+}
+__device__ __forceinline__ double exp_nonpos(double x) {
+  const double v = exp_nonpos_unguarded(x);
   return (x < -745.2) ? 0.0 : v;
+}
+
+// Matern-nu (gpytorch's MaternKernel times the outputscale): with r = |(a - b) / lengthscale| and t = sqrt(2 nu) r,
+// k = outputscale * p(t) exp(-t), p = 1 (nu = 1/2), 1 + t (3/2), 1 + t (1 + t/3) (5/2) in Horner form.  Where exp(-t)
+// underflows (t > 745.2, r = inf included) the entry is selected to 0 -- p(inf) * 0 would be NaN; a NaN t stays NaN.
+// The Gram kernel folds sqrt(2 nu) into its inverse lengthscales, so that its distance sum is t^2 itself.
+constexpr double SQRT3 = 1.7320508075688772935, SQRT5 = 2.2360679774997896964;
+__host__ __device__ constexpr double matern_t_scale(int kind) {
+  return kind == PLS_KERNEL_MATERN32 ? SQRT3 : kind == PLS_KERNEL_MATERN52 ? SQRT5 : 1.0;
+}
+__device__ __forceinline__ double matern_poly(int kind, double t) {
+  return (kind == PLS_KERNEL_MATERN12) ? 1.0 : (kind == PLS_KERNEL_MATERN32) ? 1.0 + t : fma(t, fma(t, 1.0 / 3.0, 1.0), 1.0);
+}
+template <int KIND>
+__device__ __forceinline__ double matern_from_t2(double t2, double outputscale) {
+  const double t = sqrt(t2);
+  const double k = outputscale * (matern_poly(KIND, t) * exp_nonpos_unguarded(-t));
+  return (t > 745.2) ? 0.0 : k;
 }
 
 // k(x1, x2): a block covers GRAM_ROWS rows x 512 columns; a thread owns one PAIR of columns (its two x2 points stay in
@@ -734,7 +756,7 @@ __global__ __launch_bounds__(256) void kernel_gram_kernel(const double *__restri
   const int t = threadIdx.x;
   const int64_t row0 = (int64_t)blockIdx.y * GRAM_ROWS;
   const int nrows = (int)((n1 - row0 < GRAM_ROWS) ? (n1 - row0) : GRAM_ROWS);
-  if (t < D_MAX) inv_ls[t] = (t < d) ? ((KIND == PLS_KERNEL_RBF_ARD) ? 1.0 / lengthscale[t] : 1.0) : 0.0;
+  if (t < D_MAX) inv_ls[t] = (t < d) ? ((KIND != PLS_KERNEL_LINEAR) ? matern_t_scale(KIND) / lengthscale[t] : 1.0) : 0.0;
   __syncthreads();
   for (int e = t; e < nrows * D_MAX; e += 256) {
     const int r = e / D_MAX, k = e % D_MAX;
@@ -765,6 +787,16 @@ __global__ __launch_bounds__(256) void kernel_gram_kernel(const double *__restri
       }
       s0 = outputscale * exp_nonpos(-0.5 * s0);
       s1 = outputscale * exp_nonpos(-0.5 * s1);
+    } else if (KIND != PLS_KERNEL_LINEAR) {  // Matern: the same distance sum as RBF, of t^2 (inv_ls holds sqrt(2 nu))
+#pragma unroll
+      for (int k = 0; k < D_MAX; ++k) {
+        const double a = a_s[r][k];
+        const double e0 = a - b0[k], e1 = a - b1[k];
+        s0 = fma(e0, e0, s0);
+        s1 = fma(e1, e1, s1);
+      }
+      s0 = matern_from_t2<KIND>(s0, outputscale);
+      s1 = matern_from_t2<KIND>(s1, outputscale);
     } else {
 #pragma unroll
       for (int k = 0; k < D_MAX; ++k) {
@@ -1387,6 +1419,15 @@ __device__ inline double cv_kernel_eval(int kind, const double *__restrict__ x, 
     }
     return outputscale * exp(-0.5 * s);
   }
+  if (kind != PLS_KERNEL_LINEAR) {  // Matern (see matern_from_t2)
+    for (int k = 0; k < d; ++k) {
+      const double e = (x[a * d + k] - x[b * d + k]) * inv_ls[k];
+      s = fma(e, e, s);
+    }
+    const double t = matern_t_scale(kind) * sqrt(s);
+    const double v = outputscale * (matern_poly(kind, t) * exp(-t));
+    return (t > 745.2) ? 0.0 : v;
+  }
   for (int k = 0; k < d; ++k) s = fma(x[a * d + k], x[b * d + k], s);
   return s;
 }
@@ -1399,7 +1440,7 @@ __global__ __launch_bounds__(CV_BLOCK) void cv_init_kernel(int kind, const doubl
                                                             double jitter, double *__restrict__ di,
                                                             unsigned char *__restrict__ chosen, CvState *st) {
   __shared__ double inv_ls[64];
-  if ((int)threadIdx.x < d) inv_ls[threadIdx.x] = (kind == PLS_KERNEL_RBF_ARD) ? 1.0 / lengthscale[threadIdx.x] : 1.0;
+  if ((int)threadIdx.x < d) inv_ls[threadIdx.x] = (kind != PLS_KERNEL_LINEAR) ? 1.0 / lengthscale[threadIdx.x] : 1.0;
   __syncthreads();
   const int64_t i = (int64_t)blockIdx.x * CV_BLOCK + threadIdx.x;
   if (i == 0) {
@@ -1514,7 +1555,7 @@ __global__ __launch_bounds__(CV_BLOCK) void cv_update_kernel(int kind, const dou
   constexpr int NSL = CV_BLOCK / CV_COLS;
   __shared__ double inv_ls[64];
   __shared__ double part[NSL][CV_COLS];
-  if ((int)threadIdx.x < d) inv_ls[threadIdx.x] = (kind == PLS_KERNEL_RBF_ARD) ? 1.0 / lengthscale[threadIdx.x] : 1.0;
+  if ((int)threadIdx.x < d) inv_ls[threadIdx.x] = (kind != PLS_KERNEL_LINEAR) ? 1.0 / lengthscale[threadIdx.x] : 1.0;
   __syncthreads();
   if (st->stopped || st->count != iter + 1) return;  // (stopped early, or ran out of candidates; uniform)
   const int64_t j = st->pivot;
@@ -2044,12 +2085,12 @@ int pls_timeline_end(float *ms, int32_t *tags, int32_t capacity, int32_t *count)
 
 int pls_kernel_gram(int32_t kernel_kind, const double *x1, int64_t n1, const double *x2, int64_t n2, int64_t d,
                     const double *lengthscale, double outputscale, double *out, int64_t ldout, void *stream) {
-  PLS_REQUIRE(kernel_kind == PLS_KERNEL_RBF_ARD || kernel_kind == PLS_KERNEL_LINEAR, "unknown kernel kind %d", kernel_kind);
+  PLS_REQUIRE(kernel_kind >= PLS_KERNEL_RBF_ARD && kernel_kind <= PLS_KERNEL_MATERN52, "unknown kernel kind %d", kernel_kind);
   PLS_REQUIRE(x1 && x2 && out, "kernel_gram: NULL pointer");
   PLS_REQUIRE(n1 >= 0 && n2 >= 0 && d >= 1, "kernel_gram: bad sizes n1=%lld n2=%lld d=%lld", (long long)n1, (long long)n2, (long long)d);
   PLS_REQUIRE(d <= 64, "kernel_gram: input dimension %lld > 64 is not supported", (long long)d);
   PLS_REQUIRE(ldout >= n2, "kernel_gram: ldout < n2");
-  PLS_REQUIRE(kernel_kind != PLS_KERNEL_RBF_ARD || lengthscale, "kernel_gram: RBF needs lengthscale");
+  PLS_REQUIRE(kernel_kind == PLS_KERNEL_LINEAR || lengthscale, "kernel_gram: kernel kind %d needs lengthscale", kernel_kind);
   if (n1 == 0 || n2 == 0) return PLS_OK;
   PLS_REQUIRE(cdiv(n2, 512) <= 0x7fffffff, "kernel_gram: n2 too large");
   const int64_t max_rows = 65535LL * GRAM_ROWS;  // gridDim.y <= 65535: taller Gram matrices go in row slabs
@@ -2057,10 +2098,15 @@ int pls_kernel_gram(int32_t kernel_kind, const double *x1, int64_t n1, const dou
     const int64_t rows = (n1 - r0 < max_rows) ? n1 - r0 : max_rows;
     dim3 g2((unsigned)cdiv(n2, 512), (unsigned)cdiv(rows, GRAM_ROWS));
     LaunchScope scope(PLS_TAG_KERNEL_GRAM, S(stream));
-    if (kernel_kind == PLS_KERNEL_RBF_ARD)
-      launch_gram<PLS_KERNEL_RBF_ARD>(g2, S(stream), x1 + r0 * d, rows, x2, n2, (int)d, lengthscale, outputscale, out + r0 * ldout, ldout);
-    else
-      launch_gram<PLS_KERNEL_LINEAR>(g2, S(stream), x1 + r0 * d, rows, x2, n2, (int)d, lengthscale, outputscale, out + r0 * ldout, ldout);
+    const double *a = x1 + r0 * d;
+    double *o = out + r0 * ldout;
+    switch (kernel_kind) {
+      case PLS_KERNEL_RBF_ARD: launch_gram<PLS_KERNEL_RBF_ARD>(g2, S(stream), a, rows, x2, n2, (int)d, lengthscale, outputscale, o, ldout); break;
+      case PLS_KERNEL_LINEAR: launch_gram<PLS_KERNEL_LINEAR>(g2, S(stream), a, rows, x2, n2, (int)d, lengthscale, outputscale, o, ldout); break;
+      case PLS_KERNEL_MATERN12: launch_gram<PLS_KERNEL_MATERN12>(g2, S(stream), a, rows, x2, n2, (int)d, lengthscale, outputscale, o, ldout); break;
+      case PLS_KERNEL_MATERN32: launch_gram<PLS_KERNEL_MATERN32>(g2, S(stream), a, rows, x2, n2, (int)d, lengthscale, outputscale, o, ldout); break;
+      default: launch_gram<PLS_KERNEL_MATERN52>(g2, S(stream), a, rows, x2, n2, (int)d, lengthscale, outputscale, o, ldout); break;
+    }
     int rc = check_launch("kernel_gram");
     if (rc) return rc;
   }
@@ -3260,11 +3306,11 @@ int pls_select_inducing_conditional_variance(int32_t kernel_kind, const double *
                                              const double *lengthscale, double outputscale, int64_t m, double jitter,
                                              double threshold, int64_t *indices, int64_t *count, void *workspace,
                                              size_t workspace_bytes, void *stream) {
-  PLS_REQUIRE(kernel_kind == PLS_KERNEL_RBF_ARD || kernel_kind == PLS_KERNEL_LINEAR, "unknown kernel kind %d", kernel_kind);
+  PLS_REQUIRE(kernel_kind >= PLS_KERNEL_RBF_ARD && kernel_kind <= PLS_KERNEL_MATERN52, "unknown kernel kind %d", kernel_kind);
   PLS_REQUIRE(x && indices && count, "select_inducing: NULL pointer");
   PLS_REQUIRE(m > 1, "select_inducing: Must have at least 2 inducing points");  // conditional_variance.py:57
   PLS_REQUIRE(n >= m && d >= 1 && d <= 64, "select_inducing: need n >= m and 1 <= d <= 64");
-  PLS_REQUIRE(kernel_kind != PLS_KERNEL_RBF_ARD || lengthscale, "select_inducing: RBF needs lengthscale");
+  PLS_REQUIRE(kernel_kind == PLS_KERNEL_LINEAR || lengthscale, "select_inducing: kernel kind %d needs lengthscale", kernel_kind);
   const size_t need = pls_select_inducing_workspace_bytes(n, m);
   if (!workspace || workspace_bytes < need)
     return fail(PLS_ERR_WORKSPACE_TOO_SMALL, "select_inducing: workspace %zu < %zu bytes", workspace_bytes, need);

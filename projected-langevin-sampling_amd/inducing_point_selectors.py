@@ -41,9 +41,11 @@ class ConditionalVarianceInducingPointSelector(InducingPointSelector):
         if isinstance(kernel, PLSKernel):
             # the reference would select on r = k(., S) k(S, .)^T / |S| (an N x N Gram of the PLS kernel); its experiments
             # always pass the base ScaleKernel(RBFKernel) (experiments/uci/regression/main.py:203), and so must callers here
-            raise TypeError("ConditionalVarianceInducingPointSelector selects on a base kernel (ARDKernel / LinearKernel / a "
-                            "gpytorch ScaleKernel(RBFKernel)); pass pls_kernel.base_kernel, not the PLSKernel")
-        base = as_base_kernel(kernel)  # ARDKernel / LinearKernel as is; ScaleKernel(RBFKernel): lengthscale AND outputscale
+            raise TypeError("ConditionalVarianceInducingPointSelector selects on a base kernel (ARDKernel / MaternKernel / "
+                            "LinearKernel / a gpytorch ScaleKernel(RBFKernel) or ScaleKernel(MaternKernel)); pass "
+                            "pls_kernel.base_kernel, not the PLSKernel")
+        # ARDKernel / MaternKernel / LinearKernel as is; ScaleKernel(RBFKernel | MaternKernel): lengthscale AND outputscale (and nu)
+        base = as_base_kernel(kernel)
         n = x.shape[0]
         perm = np.random.permutation(n)  # permute entries so tie-breaking is random (:58-61)
         xp = x[torch.as_tensor(perm)] if isinstance(x, torch.Tensor) else torch.as_tensor(x)[perm]

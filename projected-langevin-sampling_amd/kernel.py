@@ -2,8 +2,8 @@
 
 The reference takes a gpytorch kernel object; gpytorch is a host-side hyper-parameter container there.
 Here kernels are plain parameter holders whose Gram matrices are built by libplship on the MI355X.
-A gpytorch ScaleKernel(RBFKernel) instance is accepted wherever a base kernel is expected: its
-lengthscale / outputscale are read once (``as_base_kernel``)."""
+A gpytorch ScaleKernel(RBFKernel) or ScaleKernel(MaternKernel) instance is accepted wherever a base kernel is
+expected: its lengthscale / outputscale (and nu) are read once (``as_base_kernel``)."""
 from __future__ import annotations
 
 import torch
@@ -50,11 +50,9 @@ class BaseKernel:
     forward = __call__
 
 
-class ARDKernel(BaseKernel):
-    """ScaleKernel(RBFKernel(ard_num_dims=D)): k(a,b) = outputscale * exp(-0.5 sum_d ((a_d-b_d)/lengthscale_d)^2)
-    (constructed in the reference at experiments/uci/regression/main.py:171-173, README.md:144-146)."""
-
-    kind = L.KERNEL_RBF_ARD
+class _StationaryKernel(BaseKernel):
+    """Holds per-dimension (or one shared) lengthscales and the outputscale; the lengthscales are cached per D on the
+    device."""
 
     def __init__(self, lengthscale, outputscale: float = 1.0):
         self.lengthscale = torch.as_tensor(lengthscale, dtype=torch.float64).reshape(-1).cpu()
@@ -71,6 +69,31 @@ class ARDKernel(BaseKernel):
         return self._ls_dev[d]
 
 
+class ARDKernel(_StationaryKernel):
+    """ScaleKernel(RBFKernel(ard_num_dims=D)): k(a,b) = outputscale * exp(-0.5 sum_d ((a_d-b_d)/lengthscale_d)^2)
+    (constructed in the reference at experiments/uci/regression/main.py:171-173, README.md:144-146)."""
+
+    kind = L.KERNEL_RBF_ARD
+
+
+class MaternKernel(_StationaryKernel):
+    """ScaleKernel(MaternKernel(nu, ard_num_dims=D)): with r = |(a - b) / lengthscale| (per-dimension lengthscales),
+    k(a,b) = outputscale * exp(-r)                              (nu = 1/2)
+           = outputscale * (1 + sqrt3 r) exp(-sqrt3 r)           (nu = 3/2)
+           = outputscale * (1 + sqrt5 r + 5 r^2 / 3) exp(-sqrt5 r) (nu = 5/2),
+    gpytorch's MaternKernel; nu is one of the three it offers.  Lengthscale handling as ARDKernel."""
+
+    KINDS = {0.5: L.KERNEL_MATERN12, 1.5: L.KERNEL_MATERN32, 2.5: L.KERNEL_MATERN52}
+
+    def __init__(self, lengthscale, outputscale: float = 1.0, nu: float = 2.5):
+        nu = float(nu)
+        if nu not in self.KINDS:
+            raise ValueError(f"MaternKernel: nu must be 0.5, 1.5 or 2.5 (gpytorch's MaternKernel), got {nu}")
+        super().__init__(lengthscale, outputscale)
+        self.nu = nu
+        self.kind = self.KINDS[nu]
+
+
 class LinearKernel(BaseKernel):
     """k(x1, x2) = x1 x2^T: the reference's test double (mockers/kernel.py:8-23)."""
 
@@ -78,16 +101,18 @@ class LinearKernel(BaseKernel):
 
 
 def as_base_kernel(kernel) -> BaseKernel:
-    """Accept our kernels, or read the hyper-parameters of a gpytorch ScaleKernel(RBFKernel)."""
+    """Accept our kernels, or read the hyper-parameters of a gpytorch ScaleKernel(RBFKernel) or
+    ScaleKernel(MaternKernel) (an inner kernel with a ``nu`` attribute; nu outside {0.5, 1.5, 2.5} raises ValueError)."""
     if isinstance(kernel, BaseKernel):
         return kernel
     inner = getattr(kernel, "base_kernel", None)
     if inner is not None and hasattr(inner, "lengthscale") and hasattr(kernel, "outputscale"):
-        return ARDKernel(
-            lengthscale=torch.as_tensor(inner.lengthscale).detach().reshape(-1),
-            outputscale=float(torch.as_tensor(kernel.outputscale).detach()),
-        )
-    raise TypeError(f"unsupported base kernel {type(kernel).__name__}: use ARDKernel / LinearKernel")
+        lengthscale = torch.as_tensor(inner.lengthscale).detach().reshape(-1)
+        outputscale = float(torch.as_tensor(kernel.outputscale).detach())
+        if hasattr(inner, "nu"):
+            return MaternKernel(lengthscale=lengthscale, outputscale=outputscale, nu=inner.nu)
+        return ARDKernel(lengthscale=lengthscale, outputscale=outputscale)
+    raise TypeError(f"unsupported base kernel {type(kernel).__name__}: use ARDKernel / MaternKernel / LinearKernel")
 
 
 class PLSKernel:

@@ -1,0 +1,233 @@
+"""GPU: the Matern base kernels (nu = 1/2, 3/2, 5/2) end to end -- the Gram build against the closed form (every D_MAX
+instantiation, both store paths), its exact properties, the conditional-variance selector, one ONB and one IPB step
+against the CPU oracle on the closed form, prediction, and gpytorch-shaped kernels through PLSKernel."""
+import numpy as np
+import pytest
+import torch
+
+from matern_closed_form import NUS, matern_numpy, matern_torch
+from oracle import pls_oracle as O
+from test_gpu_parity import P, TOL, _f64_default, cu, make_costs, make_problem, relerr, step_tolerance  # noqa: F401
+
+pytestmark = pytest.mark.gpu
+
+GRAM_DIMS = [1, 2, 3, 5, 8, 13, 33, 64]  # every D_MAX of the Gram kernel: 1, 2, 4, 8, 16, 32, 64, padded and exact
+
+
+def _gram_into(P, kernel, x1, x2, out_view, ldout):
+    """pls_kernel_gram through the C ABI into a strided (possibly unaligned) view."""
+    L = P.pkg._lib
+    a, b = cu(x1).contiguous(), cu(x2).contiguous()
+    ls = kernel._lengthscale_dev(a.shape[1])
+    L.check(L.load().pls_kernel_gram(kernel.kind, a.data_ptr(), a.shape[0], b.data_ptr(), b.shape[0], a.shape[1], ls.data_ptr(),
+                                     float(kernel.outputscale), out_view.data_ptr(), ldout, L.stream_ptr()), "pls_kernel_gram")
+
+
+@pytest.mark.parametrize("nu", NUS)
+@pytest.mark.parametrize("d", GRAM_DIMS)
+@pytest.mark.parametrize("ard", [True, False], ids=["ard", "scalar"])
+def test_matern_gram_against_the_closed_form(P, nu, d, ard):
+    g = torch.Generator().manual_seed(1000 * d + int(10 * nu) + ard)
+    n1, n2 = 100, 515  # n1 not a multiple of 64 (a short row block), n2 odd (a lone last column)
+    x1, x2 = torch.randn(n1, d, generator=g), torch.randn(n2, d, generator=g)
+    ls = ((0.5 + torch.rand(d if ard else 1, generator=g)) * d**0.5)  # r = O(1) at every D
+    s = 2.5
+    k = P.pkg.MaternKernel(ls, s, nu=nu)
+    want = matern_torch(ls, s, nu)(x1, x2)
+    got = k(x1, x2)
+    err = relerr(got, want)
+    print(f"nu={nu} d={d} {'ard' if ard else 'scalar'}: rel err {err:.2e}")
+    assert err < 1e-13
+    assert (want > 1e-3 * s).double().mean().item() >= 0.5, "test construction: most entries must not underflow"
+    # strided output, odd ldout, 8 bytes past a 16-byte boundary: the scalar store path; the padding stays untouched
+    ldout = n2 + 2
+    buf = torch.full((1 + n1 * ldout,), float("nan"), dtype=torch.float64, device="cuda")
+    view = buf[1:].view(n1, ldout)
+    assert view.data_ptr() % 16 == 8
+    _gram_into(P, k, x1, x2, view, ldout)
+    assert relerr(view[:, :n2], want) < 1e-13
+    assert torch.equal(view[:, :n2], got), "scalar store path != 16-byte store path"
+    assert torch.isnan(view[:, n2:]).all() and torch.isnan(buf[:1]).all()
+
+
+@pytest.mark.parametrize("nu", NUS)
+def test_matern_gram_exact_properties(P, nu):
+    g = torch.Generator().manual_seed(5)
+    d = 5
+    z = torch.randn(131, d, generator=g)
+    ls = 0.5 + torch.rand(d, generator=g)
+    s = 1.7
+    k = P.pkg.MaternKernel(ls, s, nu=nu)
+    kzz = k(z, z)
+    assert torch.equal(kzz, kzz.T), "k(Z, Z) is not exactly symmetric"
+    assert torch.all(kzz.diagonal() == s)
+    # every entry whose two rows are equal is exactly the outputscale (x2 repeats rows of x1 at other positions)
+    pick = torch.randperm(131, generator=g)[:77]
+    x2 = torch.cat([torch.randn(40, d, generator=g), z[pick]])
+    kx = k(z, x2).cpu()
+    assert torch.all(kx[pick, 40 + torch.arange(77)] == s)
+    # pairs ~1e200 apart (r = inf): exactly 0, no NaN
+    far = torch.cat([torch.full((3, d), 1e200), torch.full((2, d), -1e200)])
+    kf = k(far, -far).cpu()
+    assert not torch.isnan(kf).any()
+    assert torch.all(kf[:3, :3] == 0) and torch.all(kf[3:, 3:] == 0)
+    assert torch.all(k(far, torch.zeros(4, d)).cpu() == 0)
+
+
+@pytest.mark.parametrize("nu", NUS)
+@pytest.mark.parametrize("n,m,d", [(200, 12, 2), (1000, 40, 3), (2000, 64, 3)])
+def test_conditional_variance_selector_matern(P, nu, n, m, d):
+    """The HIP selector with a Matern kernel picks exactly the oracle's indices (on these inputs the best and the runner-up
+    residual variance differ by 4.3e-7 or more, relative, at every pick)."""
+    from oracle import selectors_oracle as SO
+    from projected_langevin_sampling_amd.inducing_point_selectors import ConditionalVarianceInducingPointSelector
+
+    g = torch.Generator().manual_seed(n + m)
+    x = torch.rand(n, d, generator=g) * 2 - 1
+    ls = 0.4 + torch.rand(d, generator=g)
+    kern = matern_numpy(ls.numpy(), 1.7, nu)
+    np.random.seed(7)
+    x_sel, idx = ConditionalVarianceInducingPointSelector()(x, m, P.pkg.MaternKernel(ls, 1.7, nu=nu))
+    np.random.seed(7)
+    x_want, idx_want, _, _ = SO.conditional_variance_select(x.numpy(), m, kern)
+    assert idx.shape == (m,) and len(set(idx.tolist())) == m
+    assert np.array_equal(x_sel.numpy(), x.numpy()[idx.numpy()])
+    got = idx.numpy()
+    assert np.array_equal(got, idx_want), f"picks differ from pick {int(np.argmax(got != idx_want))} on"
+    xp = x.numpy()
+    for t in range(1, m, max(1, m // 8)):
+        di = SO.residual_variances(xp, list(got[:t]), kern)
+        rest = np.ones(n, dtype=bool)
+        rest[got[:t]] = False
+        assert di[got[t]] >= di[rest].max() * (1 - 1e-9), f"pick {t} is not the largest residual variance"
+
+
+STEP_PROBLEMS = [dict(n=3000, m=200, j=128, d=3, seed=11), dict(n=1000, m=40, j=64, d=5, seed=12)]
+
+
+def _problem(spec):
+    return make_problem(spec["n"], spec["m"], spec["j"], spec["d"], seed=spec["seed"])
+
+
+def _onb_pair(P, pr, nu, threshold=1e-6):
+    """Oracle basis on the closed form and GPU basis on MaternKernel, sharing ONE spectrum (as build_onb does)."""
+    ob = O.OrthonormalBasis(matern_torch(pr["ls"], 1.3, nu), pr["z"], pr["x"], threshold)
+    lam_all, vec_all = torch.linalg.eigh((1 / pr["z"].shape[0]) * ob.base_gram_induce)
+    gb = P.basis.OrthonormalBasis(P.pkg.PLSKernel(P.pkg.MaternKernel(pr["ls"], 1.3, nu=nu), pr["z"]), pr["z"], pr["x"], threshold,
+                                  spectrum=(lam_all, vec_all), verbose=False)
+    assert gb.approximation_dimension == ob.approximation_dimension
+    return ob, gb
+
+
+def _onb_inputs(pr, ob, spec):
+    """Prior-scaled particles, injected noise, and the Poisson particles shifted off the pole of -2 y log|f| (f = A^T u
+    stays near 3), as test_gpu_configs' mid-size test builds them."""
+    mk = ob.approximation_dimension
+    u = (pr["u"][:mk] * torch.sqrt(ob.eigenvalues)[:, None]).contiguous()
+    xi = torch.randn(mk, spec["j"], generator=pr["gen"])
+    a_or = ob.scaled_eigenvectors.T @ ob.base_gram_induce_train
+    e1 = a_or @ torch.ones(spec["n"])
+    u_pos = (e1 * (3.0 / (a_or.T @ e1).mean()))[:, None] + 0.02 * u
+    return u, u_pos, xi
+
+
+@pytest.mark.parametrize("nu", NUS)
+@pytest.mark.parametrize("spec", STEP_PROBLEMS, ids=["mk200", "mk40"])
+def test_matern_onb_step_against_the_oracle_every_native_cost(P, nu, spec):
+    """M_k = 200 runs the GEMM routes, M_k = 40 the small-rank and one-launch routes; every native (cost, link) pair is held
+    to step_tolerance, none skipped."""
+    pr = _problem(spec)
+    ob, gb = _onb_pair(P, pr, nu)
+    u_prior, u_pos, xi = _onb_inputs(pr, ob, spec)
+    eta = 1e-4
+    checked = 0
+    for name, oc, gc in make_costs(P, pr["y"], pr["fstar"], pr["gen"])[:6]:
+        u = u_pos if name.startswith("poisson") else u_prior
+        want = O.PLS(ob, oc).calculate_particle_update(u.clone(), eta, noise=xi)
+        tol = step_tolerance(ob, oc, u, eta, xi, want)
+        assert tol < 1e-8, f"{name}: the problem cannot be held to 1e-8 (tol {tol:.1e})"
+        got = gb.fused_step(gc, cu(u), eta, noise=P.basis.NoiseSpec(injected=cu(xi)), force_generic=True)
+        err = relerr(got, want)
+        print(f"nu={nu} mk={ob.approximation_dimension} {name}: rel err {err:.2e} (tol {tol:.1e})")
+        assert err < tol, f"{name}: {err:.2e} (tol {tol:.1e})"
+        e_want = O.PLS(ob, oc).calculate_energy_potential(u.clone())
+        e_got = gb.fused_particle_energy(gc, cu(u), force_generic=True).mean().item()
+        assert abs(e_got - e_want) <= max(1e-9, tol) * abs(e_want), name
+        if name == "gaussian/identity":
+            fast = gb.fused_step(gc, cu(u), eta, noise=P.basis.NoiseSpec(injected=cu(xi)))
+            assert relerr(fast, want) < 1e-8, f"fast path: {relerr(fast, want):.2e}"
+        checked += 1
+    assert checked == 6
+
+
+@pytest.mark.parametrize("nu", NUS)
+@pytest.mark.parametrize("spec", STEP_PROBLEMS, ids=["m200", "m40"])
+def test_matern_ipb_step_against_the_oracle(P, nu, spec):
+    pr = _problem(spec)
+    m = spec["m"]
+    yz = pr["y"][:m]
+    ob = O.InducingPointBasis(matern_torch(pr["ls"], 1.3, nu), pr["z"], yz, pr["x"])
+    cond = torch.linalg.cond(ob.base_gram_induce).item()
+    gb = P.basis.InducingPointBasis(P.pkg.PLSKernel(P.pkg.MaternKernel(pr["ls"], 1.3, nu=nu), pr["z"]), pr["z"], yz, pr["x"])
+    u = pr["u"]
+    e_noise = torch.randn(m, spec["j"], generator=pr["gen"])
+    eta = 1e-4
+    costs = make_costs(P, pr["y"], pr["fstar"], pr["gen"])
+    for name, oc, gc in (costs[0], costs[2]):
+        want = O.PLS(ob, oc).calculate_particle_update(u.clone(), eta, noise=e_noise)
+        tol = step_tolerance(ob, oc, u, eta, e_noise, want, solve_cond=cond)
+        got = gb.fused_step(gc, cu(u), eta, noise=P.basis.NoiseSpec(injected=cu(e_noise)), force_generic=True)
+        err = relerr(got, want)
+        print(f"nu={nu} m={m} {name}: rel err {err:.2e} (tol {tol:.1e}, cond {cond:.1e})")
+        assert err < tol, f"{name} (cond {cond:.1e}): {err:.2e} (tol {tol:.1e})"
+        e_want = O.PLS(ob, oc).calculate_energy_potential(u.clone())
+        assert abs(P.pkg.PLS(gb, gc).calculate_energy_potential(cu(u)) - e_want) <= max(1e-9, tol) * abs(e_want), name
+        if name == "gaussian/identity":
+            fast = gb.fused_step(gc, cu(u), eta, noise=P.basis.NoiseSpec(injected=cu(e_noise)))
+            assert relerr(fast, want) < 1e-8, f"M x M x J path: {relerr(fast, want):.2e}"
+
+
+def test_matern_prediction_vs_oracle(P):
+    """test_gpu_parity.test_prediction_vs_oracle with Matern-3/2."""
+    nu = 1.5
+    pr = make_problem(300, 12, 40, 2, seed=31)
+    ob, gb = _onb_pair(P, pr, nu)
+    ls_i = pr["ls"] * 0.35
+    yz = pr["y"][:12]
+    oi = O.InducingPointBasis(matern_torch(ls_i, 1.3, nu), pr["z"], yz, pr["x"])
+    gi = P.basis.InducingPointBasis(P.pkg.PLSKernel(P.pkg.MaternKernel(ls_i, 1.3, nu=nu), pr["z"]), pr["z"], yz, pr["x"])
+    g = pr["gen"]
+    xs = torch.rand(9, 2, generator=g) * 2 - 1
+    mk = ob.approximation_dimension
+    u = pr["u"][:mk].contiguous()
+    noise = torch.randn(mk + 9, 40, generator=g)
+    err = relerr(gb.predict_untransformed_samples(cu(u), xs, noise=cu(noise)), ob.predict_untransformed_samples(u, xs, noise=noise))
+    print(f"ONB prediction: rel err {err:.2e}")
+    assert err < TOL
+    noise_i = torch.randn(12 + 9, 40, generator=g)
+    tol_i = max(TOL, torch.linalg.cond(oi.r_kernel(pr["z"], pr["z"], xs)).item() * 1e-14)
+    err = relerr(gi.predict_untransformed_samples(cu(pr["u"]), xs, noise=cu(noise_i)),
+                 oi.predict_untransformed_samples(pr["u"], xs, noise=noise_i))
+    print(f"IPB prediction: rel err {err:.2e} (tol {tol_i:.1e})")
+    assert err < tol_i
+
+
+@pytest.mark.parametrize("nu", NUS)
+def test_gpytorch_shaped_scale_matern_kernel_drops_in(P, nu):
+    """A ScaleKernel(MaternKernel)-shaped object through PLSKernel, a basis and one step equals, bit for bit, the same step
+    built from MaternKernel directly."""
+    pr = make_problem(1000, 40, 64, 5, seed=12)
+    inner = type("MaternStub", (), {"lengthscale": pr["ls"][None, :].clone(), "nu": nu})()
+    stub = type("ScaleStub", (), {"base_kernel": inner, "outputscale": torch.tensor(1.3)})()
+    steps = []
+    for base in (stub, P.pkg.MaternKernel(pr["ls"], 1.3, nu=nu)):
+        kern = P.pkg.PLSKernel(base, pr["z"])
+        assert type(kern.base_kernel) is P.pkg.MaternKernel and kern.base_kernel.nu == nu
+        gb = P.basis.OrthonormalBasis(kern, pr["z"], pr["x"], 1e-6, verbose=False)
+        mk = gb.approximation_dimension
+        u = cu(pr["u"][:mk])
+        xi = cu(torch.randn(mk, 64, generator=torch.Generator().manual_seed(3)))
+        gc = P.costs.BernoulliCost((pr["y"] > 0).double(), P.links.SigmoidLinkFunction())
+        steps.append(P.pkg.PLS(gb, gc).calculate_particle_update(u, 1e-3, noise=xi))
+    assert torch.isfinite(steps[0]).all()
+    assert torch.equal(steps[0], steps[1])
