@@ -120,8 +120,12 @@ __device__ inline double cost_deriv(const CostP &c, double y, double f) {
   switch (c.cost) {
     case PLS_COST_GAUSSIAN:  // gaussian.py:86-88 closed form == chain rule for the identity link
       return (p - y) * c.ip0 * slope;  // (* 1/sigma2 instead of / sigma2: <= 1 ulp, and no fp64 division per element)
-    case PLS_COST_POISSON:  // poisson.py:76-82 (square link closed form == chain rule); else autograd value
-      return fast_div(-2.0 * y, f) + slope;
+    case PLS_COST_POISSON: {  // poisson.py:76-82 (square link closed form == chain rule); else autograd value
+      const double d = fast_div(-2.0 * y, f) + slope;
+      // at the pole f = +-0 the closed form divides by f (-+inf, NaN for y = 0); autograd differentiates |f| with
+      // sgn(0) = 0 and returns inf * 0
+      return (f != 0.0 || (ref && c.link == PLS_LINK_SQUARE)) ? d : __builtin_nan("");
+    }
     case PLS_COST_BERNOULLI:
       if (ref && c.link == PLS_LINK_SIGMOID)  // bernoulli.py:64-77, uses the CLIPPED p
         return -y * (1.0 - p) + (1.0 - y) * p;

@@ -525,3 +525,294 @@ WINO_ONE_SLAB = (512, 16384, 18688)
 WINO_THREE_CHUNKS = (512, 40000, 2048)
 # just outside the route: M_k, N, J below a limit or off its grid
 WINO_OUTSIDE = [(496, 16384, 2048), (512, 16380, 2048), (512, 16384, 1920), (512, 16384, 2112)]
+
+
+# ---- selector problems: G observable bit for bit through a step, for any cost ---------------------------------------------------
+# One carrier direction k0 has A[k0, n] = c_n (signed powers of two, 2^-3 .. 2^3) and U[k0, j] = V_j (any nonzero double); every
+# other row of U is zero.  So F[n, j] = c_n V_j exactly in any summation order (one product by a power of two plus zeros): F
+# is arbitrary, finite and nonzero, and runs through the regimes of tests/cost_truth.py.  Every other direction k carries one
+# probe entry A[k, n_k] = 2^p_k and zeros, so D[k, j] = 2^p_k G[n_k, j] exactly, the prior term U[k, j] / lambda_k is zero,
+# and without noise (or with injected zeros) out[k, j] = -eta 2^p_k G[n_k, j] with eta a power of two: not one rounding after
+# cost_deriv.  A probe row of a step therefore shows G[n_k, :] bit for bit, on any route, in any tile position.
+SELECTOR_PLACEMENTS = ["head", "half", "tail", "spread"]
+
+
+def selector_values(pair, pset="a", lo=1e-30, hi=1e30):
+    """the finite nonzero f of the pair's cost_truth grid (|f| in [lo, hi]): the regimes the carrier values run through"""
+    import cost_truth
+
+    y, f, _ = cost_truth.grid(pair, pset)
+    keep = np.isfinite(f) & (np.abs(f) >= lo) & (np.abs(f) <= hi)
+    return np.unique(f[keep]), y
+
+
+class SelectorProblem:
+    """M_k directions, N data rows, J particles for the (cost, link) pair ``pair``.  ``placement``: where the probe rows n_k
+    sit -- "head": rows 0, 1, ... (every row slot of the first tiles), "half": from N / 2 (the second operand of paired
+    tiles), "tail": the last rows (the ragged last tile), "spread": a seeded sample that holds row 0 and row N - 1."""
+
+    def __init__(self, pair, mk, n, j, placement="head", seed=0, pset="a", k0=None):
+        g = torch.Generator().manual_seed(seed)
+        self.pair, self.pset, self.mk, self.n, self.j, self.placement = pair, pset, mk, n, j, placement
+        self.k0 = k0 = (mk // 3 if k0 is None else k0)
+        vals, ys = selector_values(pair, pset)
+        # V_j: the grid's values (every regime), each also scaled by a full-mantissa factor near one, and plain normals
+        pick = torch.as_tensor(vals)[torch.randint(0, len(vals), (j,), generator=g)]
+        jiggle = 1 + (torch.rand(j, generator=g, dtype=torch.float64) - 0.5) * 2.0 ** -3
+        third = torch.arange(j) % 3
+        self.v = torch.where(third == 0, pick, torch.where(third == 1, pick * jiggle, 1.5 * torch.randn(j, generator=g, dtype=torch.float64)))
+        self.v[self.v == 0] = 0.75
+        self.c = (2.0 ** torch.randint(-3, 4, (n,), generator=g).double()) * (1 - 2 * torch.randint(0, 2, (n,), generator=g).double())
+        self.c[torch.arange(n) % 3 == 0] = 1.0  # a third of the rows see the carrier values themselves
+        self.y = torch.as_tensor(ys)[torch.randint(0, len(ys), (n,), generator=g)]
+        self.lam = 2.0 ** torch.randint(-2, 4, (mk,), generator=g, dtype=torch.int64).double()
+        others = [k for k in range(mk) if k != k0]
+        nprobe = min(len(others), n)
+        if placement == "head":
+            rows = torch.arange(nprobe)
+        elif placement == "half":
+            rows = (n // 2 + torch.arange(nprobe)) % n
+        elif placement == "tail":
+            rows = n - 1 - torch.arange(nprobe)
+        else:
+            perm = torch.randperm(n, generator=g)[:nprobe]
+            perm = perm[(perm != 0) & (perm != n - 1)]
+            rows = torch.cat([torch.tensor([0, n - 1]), perm])[:nprobe] if n > 1 else perm
+            rows = torch.unique(rows)
+        nprobe = len(rows)
+        order = torch.randperm(len(others), generator=g)[:nprobe]
+        self.probe_k = torch.as_tensor(others)[order]  # direction k of probe i
+        self.probe_n = rows[torch.randperm(nprobe, generator=g)]  # its data row n_k
+        self.probe_p = torch.randint(-2, 3, (nprobe,), generator=g)  # A[k, n_k] = 2^p
+        self.a = torch.zeros(mk, n, dtype=torch.float64)
+        self.a[k0] = self.c
+        self.a[self.probe_k, self.probe_n] = 2.0 ** self.probe_p.double()
+        self.u = torch.zeros(mk, j, dtype=torch.float64)
+        self.u[k0] = self.v
+        self.injected = torch.zeros(mk, j, dtype=torch.float64)
+        self._check()
+
+    def _check(self):
+        """From the data: F = A^T U equals c_n V_j in either summation order, is finite and nonzero, no product left the
+        normal range (so it is exact), and every probe direction holds exactly one entry, a power of two."""
+        cols = torch.unique(torch.linspace(0, self.j - 1, min(self.j, 192)).long())  # (a column sample keeps wide J cheap)
+        f, u = self.f(cols), self.u[:, cols]
+        assert torch.equal(self.a.T @ u, f) and torch.equal(self.a.T.flip(1) @ u.flip(0), f)
+        f = self.f()
+        assert torch.isfinite(f).all() and (f.abs() >= 2.0 ** -1000).all() and (f.abs() <= 2.0 ** 1000).all()
+        m, _ = torch.frexp(self.c)
+        assert (m.abs() == 0.5).all() and (self.c.abs() >= 2.0 ** -3).all() and (self.c.abs() <= 8).all()
+        rest = self.a.clone()
+        rest[self.k0] = 0
+        assert ((rest != 0).sum(1)[self.probe_k] == 1).all() and (rest != 0).sum() == len(self.probe_k)
+        assert len(torch.unique(self.probe_n)) == len(self.probe_n) == len(torch.unique(self.probe_k))
+        assert (self.u[torch.arange(self.mk) != self.k0] == 0).all() and (self.v != 0).all()
+        ml, _ = torch.frexp(self.lam)
+        assert (ml == 0.5).all()
+        self.state = self.u  # what a new-state step adds its update to
+        self.row_scale = torch.ones(self.mk, dtype=torch.float64)
+
+    def prior_row(self, cols):
+        """the prior term of the carrier row, per unit eta"""
+        return self.v[cols] / self.lam[self.k0]
+
+    def prior_energy(self, col):
+        return float(self.v[col]) ** 2 / (2 * float(self.lam[self.k0]))
+
+    def f(self, cols=None):
+        v = self.v if cols is None else self.v[torch.as_tensor(cols)]
+        return self.c[:, None] * v[None, :]
+
+    def cost(self, P, force_autograd=False):
+        import cost_truth
+
+        cost = cost_truth.gpu_cost(P, self.pair, self.pset, self.y)
+        if force_autograd:  # the step takes the derivative mode from the cost's descriptor
+            plain = cost.desc
+            cost.desc = lambda force_autograd=False: plain(force_autograd=True)
+        return cost
+
+    def basis(self, P):
+        return P.basis.OrthonormalBasis.from_projection(self.a.cuda(), self.lam.cuda(), poison_padding=True)
+
+    def g_direct(self, P, cost, cols=None, force_autograd=False):
+        """G on the host-built F through the element-wise entry (tests/test_gpu_cost_elements.py holds it to the truth)"""
+        return cost.calculate_cost_derivative(self.f(cols).cuda(), force_autograd=force_autograd).cpu()
+
+    def g_gauss_fma(self, g, cols=None, rows=None):
+        """Gaussian/identity on the routes whose forward GEMM carries the cost in its epilogue: G = fma(F, 1 / sigma2,
+        -(1 / sigma2) y) (csrc/cost_epilogues.h EpiGaussDeriv: one fma per element in every tile shape), not the element-wise
+        entry's (F - y) (1 / sigma2).  That operation order, emulated exactly (rational arithmetic, one rounding), replaces
+        ``g`` on ``rows`` (default: the probe rows); returns (G, carrier slack): the other rows keep the element-wise G, and
+        the carrier row may differ by the two formulas' roundings, sum_n |c_n| 2^-52 (|F| + |y|) / sigma2 per unit eta."""
+        from fractions import Fraction
+
+        import cost_truth
+
+        assert self.pair == "gaussian/identity"
+        ip0 = 1.0 / cost_truth.PARAMS[self.pset]["gaussian"][0]
+        f = self.f(cols)
+        rows = self.probe_n if rows is None else rows
+        g = g.clone()
+        fi = Fraction(ip0)
+        for a in torch.as_tensor(rows).tolist():
+            c = Fraction(-ip0 * float(self.y[a]))
+            g[a] = torch.tensor([float(Fraction(v) * fi + c) for v in f[a].tolist()], dtype=torch.float64)
+        slack = (self.c.abs()[:, None] * 2.0 ** -52 * (f.abs() + self.y.abs()[:, None]) * ip0).sum(0)
+        return g, slack
+
+    def values_direct(self, P, cols=None):
+        """cost(y_n, F[n, j]) per element through the element-wise entry pls_cost_value (which sums over rows: the rows of one
+        label go in as a single row, every element a column of its own; tests/test_gpu_cost_elements.py holds the entry to
+        the truth)"""
+        import cost_truth
+
+        f = self.f(cols)
+        out = torch.empty_like(f)
+        for yy in torch.unique(self.y).tolist():
+            rows = (self.y == yy).nonzero().flatten()
+            cost = cost_truth.gpu_cost(P, self.pair, self.pset, torch.tensor([yy], dtype=torch.float64))
+            out[rows] = cost.calculate_cost(f[rows].reshape(1, -1).cuda()).cpu().reshape(len(rows), -1)
+        return out
+
+    def energy_direct(self, P, cols=None, gauss_fma=False):
+        """(want, tolerance) of the energies on ``cols``: fsum of values_direct plus the prior, within the N roundings of any
+        summation order (cost_value is evaluated without contraction, so every route forms the same element values).
+        ``gauss_fma``: the Gaussian/identity GEMM epilogues form the value as G^2 sigma2 / 2 from G = fma(F, 1 / sigma2,
+        -(1 / sigma2) y), which differs from (F - y)^2 / (2 sigma2) by 2^-52 |F - y| (|F| + |y|) / sigma2 per element."""
+        import cost_truth
+
+        cols = torch.arange(self.j) if cols is None else torch.as_tensor(cols)
+        v = self.values_direct(P, cols)
+        assert torch.isfinite(v).all()
+        prior = torch.tensor([self.prior_energy(c) for c in cols.tolist()], dtype=torch.float64)
+        want = torch.tensor([math.fsum(v[:, b].tolist()) for b in range(len(cols))], dtype=torch.float64) + prior
+        tol = (self.n + 2) * 2.0 ** -53 * (v.abs().sum(0) + prior) + 2.0 ** -52 * want.abs()
+        if gauss_fma:
+            f = self.f(cols)
+            s2 = cost_truth.PARAMS[self.pset]["gaussian"][0]
+            tol = tol + 2.0 ** -51 * ((f - self.y[:, None]).abs() * (f.abs() + self.y.abs()[:, None])).sum(0) / s2
+        return want, tol
+
+    def expected(self, g, cols=None, eta=EXACT_ETA, new_state=False):
+        """(want, probe mask, carrier tolerance) of the step on columns ``cols`` given G = g_direct there.  ``want``: exact on
+        every row but k0 (probe rows -eta 2^p G[n_k], the others 0); row k0 holds fsum_n c_n G[n, j] and the prior, and may
+        differ by N 2^-53 sum_n |c_n G[n, j]| + 2 ulp.  Checks that no probe value over- or underflows after scaling."""
+        cols = torch.arange(self.j) if cols is None else torch.as_tensor(cols)
+        eta = torch.as_tensor(eta, dtype=torch.float64).expand(len(cols))[None, :]
+        m, _ = torch.frexp(eta[eta != 0])
+        assert (m == 0.5).all(), "the step sizes must be powers of two"
+        assert torch.isfinite(g).all(), "the selector problem's G must be finite (choose the carrier values accordingly)"
+        gp = g[self.probe_n] * (2.0 ** self.probe_p.double() * self.row_scale[self.probe_k])[:, None]
+        scaled = -eta * gp
+        live = (gp != 0) & (eta != 0)
+        assert (scaled[live].abs() >= 2.0 ** -1000).all() and (scaled.abs() <= 2.0 ** 1000).all(), "a probe value leaves the range"
+        want = torch.zeros(self.mk, len(cols), dtype=torch.float64)
+        want[self.probe_k] = scaled
+        terms = self.c[:, None] * g  # exact: powers of two
+        carrier = torch.tensor([math.fsum(terms[:, b].tolist()) for b in range(len(cols))], dtype=torch.float64)
+        prior = self.prior_row(cols)
+        rs = self.row_scale[self.k0]  # (a power of two)
+        want[self.k0] = (-eta[0] * carrier - eta[0] * prior) * rs
+        mag = terms.abs().sum(0)
+        tol = rs * eta[0].abs() * (self.n * 2.0 ** -53 * mag + 2.0 ** -51 * (carrier.abs() + prior.abs()) + getattr(self, "carrier_slack", 0.0))
+        if new_state:
+            want[self.k0] = want[self.k0] + self.state[self.k0, cols]
+            tol = tol + 2.0 ** -52 * want[self.k0].abs()
+        probe = torch.ones(self.mk, dtype=torch.bool)
+        probe[self.k0] = False
+        return want, probe, tol
+
+    def energy_truth(self, cols):
+        """per column: the sum of the mpmath cost values plus the exact prior V_j^2 / (2 lambda_k0), sum_n |cost_n|, and
+        the sum of the elements' error units (the larger of an ulp of the value and cost_truth's cancel unit)"""
+        import cost_truth
+        import mpmath as mp
+
+        f = self.f(cols)
+        want, mag, units = [], [], []
+        for b, col in enumerate(torch.as_tensor(cols).tolist()):
+            tot, ab, un = mp.mpf(0), mp.mpf(0), mp.mpf(0)
+            for a in range(self.n):
+                t, cu = cost_truth.point_truth(self.pair, self.pset, "value", float(self.y[a]), float(f[a, b]))
+                tot, ab, un = tot + t, ab + abs(t), un + max(cu, abs(t) * mp.mpf(2) ** -52)
+            want.append(float(tot + mp.mpf(self.prior_energy(col))))
+            mag.append(float(ab))
+            units.append(float(un))
+        return tuple(torch.tensor(x, dtype=torch.float64) for x in (want, mag, units))
+
+
+def assert_selector(ex, got, g, cols=None, eta=EXACT_ETA, new_state=False, what=""):
+    """probe rows (all rows but the carrier's) bit for bit, the carrier row within its summation bound"""
+    want, probe, tol = ex.expected(g, cols, eta, new_state)
+    got = got.cpu() if cols is None else got.cpu()[:, torch.as_tensor(cols)]
+    bad = (got[probe] != want[probe]).any(dim=1).nonzero().flatten()
+    assert bad.numel() == 0, f"{what}: {bad.numel()} probe rows differ from -eta 2^p G[n_k], first (row index among the " \
+                             f"non-carrier rows) {bad[:8].tolist()}, max |diff| {(got[probe] - want[probe]).abs().max().item():.3e}"
+    err = (got[ex.k0] - want[ex.k0]).abs()
+    over = (err > tol).nonzero().flatten()
+    assert over.numel() == 0, f"{what}: carrier row over its bound at columns {over[:8].tolist()}: {(err / tol).max().item():.2f} x"
+
+
+def run_selector_forms(P, ex, gb, cost, g, cols, what, force_generic=True, whitened=False):
+    """The step out of place (with and without the energy request: bit-identical), into a strided buffer (guard columns
+    untouched), as the new state, and with per-block step sizes -- the probe rows of each against G.  ``whitened``: through
+    whitened_step on the whitened particles (SelectorIpbProblem.whitened()).  Returns the energies."""
+    j = ex.j
+    u = ex.state.cuda()
+    xi = P.basis.NoiseSpec(injected=ex.injected.cuda())
+    entry = gb.whitened_step if whitened else gb.fused_step
+    e = torch.full((j,), float("nan"), device="cuda")
+    got = entry(cost, u, EXACT_ETA, noise=xi, force_generic=force_generic, input_energy=e)
+    assert_selector(ex, got, g, cols, what=f"{what}: out of place")
+    bare = entry(cost, u, EXACT_ETA, noise=xi, force_generic=force_generic)
+    assert torch.equal(got, bare), f"{what}: asking for the energies moved the step"
+    wide = torch.full((ex.mk, j + 64), float("nan"), device="cuda")
+    out = wide[:, :j]
+    entry(cost, u, EXACT_ETA, noise=xi, force_generic=force_generic, out=out)
+    assert torch.equal(out, got), f"{what}: strided output"
+    assert wide[:, j:].isnan().all(), f"{what}: the step wrote past J"
+    new = entry(cost, u, EXACT_ETA, noise=xi, force_generic=force_generic, new_state=True)
+    assert_selector(ex, new, g, cols, new_state=True, what=f"{what}: new state")
+    bc = -(-j // len(BLOCK_ETAS))
+    blocks = P.basis.BlockSpec(bc, torch.tensor(BLOCK_ETAS, device="cuda"))
+    got = entry(cost, u, 0.0, noise=xi, force_generic=force_generic, blocks=blocks, new_state=True)
+    etas = torch.tensor(BLOCK_ETAS)[torch.arange(j) // bc]
+    assert_selector(ex, got, g, cols, eta=etas if cols is None else etas[torch.as_tensor(cols)], new_state=True, what=f"{what}: blocks")
+    assert torch.equal(got[:, bc:2 * bc].cpu(), ex.state[:, bc:2 * bc]), f"{what}: a frozen block moved"
+    if hasattr(gb, "zero_step_sync"):
+        gb.zero_step_sync()
+    return e
+
+
+class SelectorIpbProblem(SelectorProblem):
+    """The inducing-point form: k(Z,Z) = diag(4^e_k), so the factor Lc = diag(2^e_k), its inverse and both solves are exact,
+    and k(Z,X) built like A above.  The carrier's particles are U[k0] = 4^e V_j, so V = k(Z,Z)^-1 U holds V_j on row k0 and
+    zeros elsewhere: F = k(X,Z) V = c_n V_j, and the prior M V vanishes on the probe rows.  ``whitened()`` switches the
+    expectations to whitened coordinates S = Lc^-1 U, where a probe row shows -eta 2^p G[n_k] / 2^e_k."""
+
+    def __init__(self, pair, m, n, j, placement="head", seed=0, pset="a"):
+        super().__init__(pair, m, n, j, placement, seed, pset)
+        g = torch.Generator().manual_seed(seed + 77)
+        self.m = m
+        self.d = 2.0 ** torch.randint(0, 3, (m,), generator=g, dtype=torch.int64).double()
+        self.kzz = torch.diag(self.d * self.d)
+        self.kzx = self.a
+        self.u = self.u * (self.d * self.d)[:, None]  # exact: powers of four
+        self.s = self.u / self.d[:, None]
+        assert torch.equal(self.u / (self.d * self.d)[:, None], torch.where(torch.arange(m)[:, None] == self.k0, self.v[None, :], 0.0))
+        self.state = self.u
+
+    def whitened(self, on=True):
+        self.state = self.s if on else self.u
+        self.row_scale = 1.0 / self.d if on else torch.ones(self.m, dtype=torch.float64)
+        return self
+
+    def prior_row(self, cols):
+        return self.m * self.v[cols]
+
+    def prior_energy(self, col):
+        return 0.5 * self.m * float(self.v[col]) ** 2
+
+    def basis(self, P, explicit_inverse=False):
+        return P.basis.InducingPointBasis.from_gram(self.kzz.cuda(), self.kzx.cuda(), explicit_inverse=explicit_inverse, poison_padding=True)
