@@ -486,6 +486,54 @@ int pls_tri_multiply(const double *LcT, int64_t ldlct, int64_t m, const double *
                      int64_t ldo, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Exact-GP hyper-parameters: the marginal log-likelihood and its gradient
+ * ------------------------------------------------------------------------------------------- */
+
+/* The d + 1 sums over all ordered pairs (i, j) of n points that the gradient of the exact-GP marginal log-likelihood
+ * with respect to the base kernel's parameters is made of (the kernel-dependent part of loss.backward() at
+ * experiments/trainers.py:49, gpytorch's autograd through ScaleKernel(RBFKernel | MaternKernel)).  With
+ * e_k = (x_ik - x_jk) / lengthscale_k, r^2 = sum_k e_k^2, W_ij = alpha_i alpha_j - P_ij and kappa the kernel WITHOUT
+ * its outputscale s:
+ *   out[0]     = sum_ij W_ij kappa_ij                                   (the d / d log s sum, divided by s)
+ *   out[1 + k] = sum_ij W_ij dK_ij / d log lengthscale_k
+ *       RBF:    dK_ij / d log l_k = s exp(-r^2 / 2) e_k^2
+ *       Matern: dK_ij / d log l_k = s q(t) exp(-t) 2 nu e_k^2,  t = sqrt(2 nu) r,  q = 1/t, 1, (1 + t)/3 (nu = 1/2, 3/2, 5/2)
+ * A pair with r = 0 (the diagonal, duplicated points) contributes exactly 0 to every out[1 + k]; a pair whose
+ * exponential underflows contributes exactly 0 to every sum.  PLS_KERNEL_LINEAR is rejected.
+ * x (n x d) row-major contiguous, alpha (n), P (n x n, SYMMETRIC, leading dimension ldp; read once -- 16 bytes per lane
+ * where ldp is even and P is 16-byte aligned), out (d + 1, device).  kappa is recomputed from x; no Gram matrix is read.
+ * Deterministic summation order (no atomics): two calls give the same bits.
+ * workspace: pls_kernel_grad_sums_workspace_bytes(n, d) = 8 (d + 1) ceil(n / 512) ceil(n / 64) bytes. */
+size_t pls_kernel_grad_sums_workspace_bytes(int64_t n, int64_t d);
+int pls_kernel_grad_sums(int32_t kernel_kind, const double *x, int64_t n, int64_t d, const double *lengthscale,
+                         double outputscale, const double *alpha, const double *P, int64_t ldp,
+                         double *out /* d + 1, device */, void *workspace, size_t workspace_bytes, void *stream);
+
+/* One evaluation of the exact-GP marginal log-likelihood and its gradient: replaces mll(model(x), y) and
+ * loss.backward() at experiments/trainers.py:45-49 (gpytorch ExactMarginalLogLikelihood, GaussianLikelihood,
+ * ConstantMean, one output).  With K_y = s kappa(x, x) + (noise + jitter) I = Lc Lc^T, r = y - mean, alpha = K_y^-1 r
+ * and W = alpha alpha^T - K_y^-1:
+ *   out[0]     = mll = -1/2 r^T alpha - sum_i log Lc_ii - n/2 log 2 pi
+ *   out[1]     = d mll / d mean  = sum_i alpha_i
+ *   out[2]     = d mll / d noise = 1/2 tr W
+ *   out[3]     = d mll / d log s
+ *   out[4 + k] = d mll / d log lengthscale_k                            (d mll / d theta = 1/2 sum_ij W_ij dK_ij / d theta)
+ * Steps: pls_kernel_gram, the diagonal, pls_chol_factor, pls_chol_solve, pls_chol_build_inverse, K_y^-1 = Linv^T Linv on
+ * the MFMA contraction, pls_kernel_grad_sums with P = K_y^-1, a one-workgroup finishing kernel (fixed-order sums).
+ * out: 4 + d doubles, device memory or pinned host memory mapped into the device.  info (DEVICE int32): as
+ * pls_chol_factor -- 0, or the 1-based index of the first pivot that was not positive; the outputs are then unspecified
+ * and the caller retries with a larger jitter.  Nothing synchronises or allocates.
+ * workspace (16-byte aligned): with ld = n rounded up to even and v(k) = k rounded up to even,
+ *   pls_gp_mll_workspace_bytes(n, d) = 8 (7 n ld + 2 v(n) + v((d + 1) ceil(n / 512) ceil(n / 64)) + v(d + 1)) bytes:
+ * seven n x ld planes (K_y, reused for K_y^-1; Lc; Lc^T; Sf; Sb; Linv, which first holds the Gram matrix; Linv^T), r,
+ * alpha, the partial rows of the reduction and its d + 1 sums. */
+size_t pls_gp_mll_workspace_bytes(int64_t n, int64_t d);
+int pls_gp_mll_grad(int32_t kernel_kind, const double *x, int64_t n, int64_t d, const double *lengthscale,
+                    double outputscale, double noise, double mean, double jitter, const double *y,
+                    double *out /* 4 + d, device or mapped pinned host */, int32_t *info /* device */,
+                    void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Orthonormal basis: setup + step
  * ------------------------------------------------------------------------------------------- */
 

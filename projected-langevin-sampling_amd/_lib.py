@@ -202,6 +202,10 @@ SIGNATURES = {
     "pls_onb_step_wg": (C.c_int, [_OD, _CD, _P, _P, _I64, _I64, _D, _ND, _P, _I64, _I32, _I32, _P, _SZ, _P, _P, _SZ, _P]),
     "pls_onb_step_blocks_wg": (C.c_int, [_OD, _CD, _P, _P, _I64, _I64, _BD, _ND, _P, _I64, _I32, _I32, _P, _SZ, _P, _P, _SZ, _P]),
     "pls_ipb_step_blocks": (C.c_int, [_ID, _CD, _P, _P, _I64, _I64, _BD, _ND, _P, _I64, _I32, _I32, _P, _P, _SZ, _P]),
+    "pls_kernel_grad_sums_workspace_bytes": (_SZ, [_I64, _I64]),
+    "pls_kernel_grad_sums": (C.c_int, [_I32, _P, _I64, _I64, _P, _D, _P, _P, _I64, _P, _P, _SZ, _P]),
+    "pls_gp_mll_workspace_bytes": (_SZ, [_I64, _I64]),
+    "pls_gp_mll_grad": (C.c_int, [_I32, _P, _I64, _I64, _P, _D, _D, _D, _D, _P, _P, _P, _P, _SZ, _P]),
 }
 
 ABI_VERSION = 7

@@ -1,0 +1,342 @@
+// Exact-GP marginal log-likelihood and its gradient with respect to the base-kernel hyper-parameters.
+//
+// Reference: mll(model(x), y) and loss.backward() of train_exact_gp (experiments/trainers.py:45-49), i.e. gpytorch's
+// ExactMarginalLogLikelihood of ScaleKernel(RBFKernel | MaternKernel) + GaussianLikelihood with a constant mean.
+//
+//   K_y = s kappa(x, x) + (noise + jitter) I = Lc Lc^T,   r = y - mean,   alpha = K_y^-1 r,   W = alpha alpha^T - K_y^-1
+//   mll = -1/2 r^T alpha - sum_i log Lc_ii - n/2 log 2 pi,                d mll / d theta = 1/2 sum_ij W_ij dK_ij / d theta
+//
+// The Gram build, the factorisation, the solve, the inverse factor and K_y^-1 = Linv^T Linv are the library's existing
+// kernels.  New here is the reduction over all n^2 pairs, kernel_grad_sums_kernel: one pass over P (= K_y^-1) that
+// recomputes kappa and its lengthscale derivatives from x and leaves d + 1 sums,
+//   out[0]     = sum_ij W_ij kappa_ij                  (kappa: the kernel without its outputscale)
+//   out[1 + k] = sum_ij W_ij dK_ij / d log l_k         (RBF: s exp(-r^2/2) e_k^2;  Matern: s q(t) exp(-t) 2 nu e_k^2 with
+//                                                       q = 1/t, 1, (1 + t)/3 for nu = 1/2, 3/2, 5/2;  e_k = (x_ik - x_jk)/l_k)
+// in a fixed summation order: per thread down the rows of its column pair, xor butterfly inside each wave, (w0 + w1) +
+// (w2 + w3) per workgroup, the workgroups' partial rows in ascending order (a second one-workgroup launch).  No atomics.
+#include <hip/hip_runtime.h>
+
+#define PLS_SCALAR_POLY_CONSTANTS 1  // (fmath.h: the exp polynomial's constants as scalar operands, as in the Gram build)
+#include "../../include/plship.h"
+#include "chol.h"
+#include "common.h"
+#include "gemm_api.h"
+#include "gp_mll.h"
+#include "kernel_math.h"
+
+namespace plship {
+
+typedef double double2m __attribute__((ext_vector_type(2)));
+
+// One pair from its distance sum s2 (RBF: r^2; Matern: t^2 = 2 nu r^2, the inverse lengthscales carry sqrt(2 nu)):
+//   kap = kappa_ij;  g: dK_ij / d log l_k = outputscale * g * e'_k^2 with e'_k the pre-scaled difference;
+//   returns false for a pair whose exponential underflows -- the caller skips it, so that it contributes exactly 0 (its
+//   e'_k^2 may be inf: 0 * inf would be NaN).
+template <int KIND>
+__device__ __forceinline__ bool pair_factors(double s2, double &kap, double &g) {
+  if (KIND == PLS_KERNEL_RBF_ARD) {
+    kap = g = exp_nonpos_unguarded(-0.5 * s2);
+    return !(s2 > 1490.4);
+  }
+  const double t = sqrt(s2);
+  const double ex = exp_nonpos_unguarded(-t);
+  kap = matern_poly(KIND, t) * ex;
+  if (KIND == PLS_KERNEL_MATERN12) g = (t > 0.0) ? ex / t : 0.0;  // r = 0: every e_k is 0 and the pair contributes 0
+  else if (KIND == PLS_KERNEL_MATERN32) g = ex;
+  else g = ex * ((1.0 + t) * (1.0 / 3.0));
+  return !(t > 745.2);
+}
+
+// A workgroup covers GRAD_ROWS rows x GRAD_COLS columns of the n x n pair matrix, laid out as kernel_gram_kernel: a
+// thread owns a PAIR of columns (its two points stay in registers, pre-scaled by 1/lengthscale) and walks down the rows,
+// whose pre-scaled points sit in LDS (broadcast reads).  P is read once, 16 B per lane where ldp is even and P is
+// 16-byte aligned.  D_MAX + 1 accumulators per thread; the padding coordinates are zero on both sides.
+template <int KIND, int D_MAX>
+__global__ __launch_bounds__(256) void kernel_grad_sums_kernel(const double *__restrict__ x, int64_t n, int d,
+                                                                const double *__restrict__ lengthscale, double outputscale,
+                                                                const double *__restrict__ alpha, const double *__restrict__ P,
+                                                                int64_t ldp, double *__restrict__ partials) {
+  __shared__ double inv_ls[D_MAX];
+  __shared__ __attribute__((aligned(16))) double a_s[GRAD_ROWS][D_MAX];
+  __shared__ double al_s[GRAD_ROWS];
+  __shared__ double red[4][D_MAX + 1];
+  const int t = threadIdx.x;
+  const int64_t row0 = (int64_t)blockIdx.y * GRAD_ROWS;
+  const int nrows = (int)((n - row0 < GRAD_ROWS) ? (n - row0) : GRAD_ROWS);
+  if (t < D_MAX) inv_ls[t] = (t < d) ? matern_t_scale(KIND) / lengthscale[t] : 0.0;
+  if (t < GRAD_ROWS) al_s[t] = (t < nrows) ? alpha[row0 + t] : 0.0;
+  __syncthreads();
+  for (int e = t; e < nrows * D_MAX; e += 256) {
+    const int r = e / D_MAX, k = e % D_MAX;
+    a_s[r][k] = (k < d) ? x[(row0 + r) * d + k] * inv_ls[k] : 0.0;
+  }
+  __syncthreads();
+  const int64_t col = ((int64_t)blockIdx.x * 256 + t) * 2;
+  const bool one = col < n, two = col + 1 < n;
+  double acc[D_MAX + 1];
+#pragma unroll
+  for (int k = 0; k <= D_MAX; ++k) acc[k] = 0.0;
+  if (one) {
+    double b0[D_MAX], b1[D_MAX];
+#pragma unroll
+    for (int k = 0; k < D_MAX; ++k) {
+      b0[k] = (k < d) ? x[col * d + k] * inv_ls[k] : 0.0;
+      b1[k] = (k < d && two) ? x[(col + 1) * d + k] * inv_ls[k] : 0.0;
+    }
+    const double aj0 = alpha[col], aj1 = two ? alpha[col + 1] : 0.0;
+    const bool vec = two && ((ldp & 1) == 0) && ((reinterpret_cast<uintptr_t>(P) & 15) == 0);
+    const double *src = P + row0 * ldp + col;
+    for (int r = 0; r < nrows; ++r, src += ldp) {
+      double p0, p1 = 0.0;
+      if (vec) {
+        const double2m v = *reinterpret_cast<const double2m *>(src);
+        p0 = v.x;
+        p1 = v.y;
+      } else {
+        p0 = src[0];
+        if (two) p1 = src[1];
+      }
+      const double ai = al_s[r];
+      const double w0 = __dsub_rn(__dmul_rn(ai, aj0), p0), w1 = __dsub_rn(__dmul_rn(ai, aj1), p1);  // W_ij, two roundings
+      double s0 = 0.0, s1 = 0.0;
+#pragma unroll
+      for (int k = 0; k < D_MAX; ++k) {
+        const double a = a_s[r][k];
+        const double e0 = a - b0[k], e1 = a - b1[k];
+        s0 = fma(e0, e0, s0);
+        s1 = fma(e1, e1, s1);
+      }
+      double kap0, g0, kap1, g1;
+      const bool live0 = pair_factors<KIND>(s0, kap0, g0);
+      const bool live1 = pair_factors<KIND>(s1, kap1, g1) && two;
+      if (live0) {
+        const double gw = w0 * (outputscale * g0);
+        acc[0] = fma(w0, kap0, acc[0]);
+#pragma unroll
+        for (int k = 0; k < D_MAX; ++k) {
+          const double e = a_s[r][k] - b0[k];
+          acc[1 + k] = fma(gw, e * e, acc[1 + k]);
+        }
+      }
+      if (live1) {
+        const double gw = w1 * (outputscale * g1);
+        acc[0] = fma(w1, kap1, acc[0]);
+#pragma unroll
+        for (int k = 0; k < D_MAX; ++k) {
+          const double e = a_s[r][k] - b1[k];
+          acc[1 + k] = fma(gw, e * e, acc[1 + k]);
+        }
+      }
+    }
+  }
+  // workgroup sum in a fixed order: xor butterfly inside each wave, then (w0 + w1) + (w2 + w3)
+#pragma unroll
+  for (int k = 0; k <= D_MAX; ++k) {
+    double v = acc[k];
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+    if ((t & 63) == 0) red[t >> 6][k] = v;
+  }
+  __syncthreads();
+  if (t <= d) {
+    const int64_t blk = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
+    partials[blk * (d + 1) + t] = (red[0][t] + red[1][t]) + (red[2][t] + red[3][t]);
+  }
+}
+
+// out[k] = the partial rows of the workgroups added in ascending order
+__global__ __launch_bounds__(128) void grad_sums_finish_kernel(const double *__restrict__ partials, int64_t nblocks, int d,
+                                                                double *__restrict__ out) {
+  const int k = threadIdx.x;
+  if (k > d) return;
+  double s = 0.0;
+  for (int64_t b = 0; b < nblocks; ++b) s += partials[b * (d + 1) + k];
+  out[k] = s;
+}
+
+template <int KIND>
+static void launch_grad_sums(dim3 grid, hipStream_t st, const double *x, int64_t n, int d, const double *lengthscale,
+                             double outputscale, const double *alpha, const double *P, int64_t ldp, double *partials) {
+#define PLS_GRAD_CASE(DM)                                                                                          \
+  hipLaunchKernelGGL((kernel_grad_sums_kernel<KIND, DM>), grid, dim3(256), 0, st, x, n, d, lengthscale, outputscale, \
+                     alpha, P, ldp, partials)
+  if (d <= 1) PLS_GRAD_CASE(1);
+  else if (d <= 2) PLS_GRAD_CASE(2);
+  else if (d <= 4) PLS_GRAD_CASE(4);
+  else if (d <= 8) PLS_GRAD_CASE(8);
+  else if (d <= 16) PLS_GRAD_CASE(16);
+  else if (d <= 32) PLS_GRAD_CASE(32);
+  else PLS_GRAD_CASE(64);
+#undef PLS_GRAD_CASE
+}
+
+static size_t grad_sums_workspace_bytes(int64_t n, int64_t d) { return (size_t)grad_sums_blocks(n) * (size_t)(d + 1) * sizeof(double); }
+
+// the reduction and its finishing launch (arguments already validated)
+static int grad_sums_launch(int kind, const double *x, int64_t n, int d, const double *lengthscale, double outputscale,
+                            const double *alpha, const double *P, int64_t ldp, double *out, double *partials, hipStream_t st) {
+  const dim3 grid((unsigned)cdiv(n, GRAD_COLS), (unsigned)cdiv(n, GRAD_ROWS));
+  {
+    LaunchScope scope(PLS_TAG_OTHER, st);
+    switch (kind) {
+      case PLS_KERNEL_RBF_ARD: launch_grad_sums<PLS_KERNEL_RBF_ARD>(grid, st, x, n, d, lengthscale, outputscale, alpha, P, ldp, partials); break;
+      case PLS_KERNEL_MATERN12: launch_grad_sums<PLS_KERNEL_MATERN12>(grid, st, x, n, d, lengthscale, outputscale, alpha, P, ldp, partials); break;
+      case PLS_KERNEL_MATERN32: launch_grad_sums<PLS_KERNEL_MATERN32>(grid, st, x, n, d, lengthscale, outputscale, alpha, P, ldp, partials); break;
+      default: launch_grad_sums<PLS_KERNEL_MATERN52>(grid, st, x, n, d, lengthscale, outputscale, alpha, P, ldp, partials); break;
+    }
+  }
+  if (int rc = check_launch("kernel_grad_sums")) return rc;
+  {
+    LaunchScope scope(PLS_TAG_OTHER, st);
+    hipLaunchKernelGGL(grad_sums_finish_kernel, dim3(1), dim3(128), 0, st, partials, grad_sums_blocks(n), d, out);
+  }
+  return check_launch("grad_sums_finish");
+}
+
+// r = y - mean
+__global__ __launch_bounds__(256) void gp_center_kernel(const double *__restrict__ y, double mean, int64_t n, double *__restrict__ r) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) r[i] = y[i] - mean;
+}
+
+// workgroup sum of one value per thread in the library's fixed order; every thread returns the total
+__device__ __forceinline__ double block256_sum(double v, double (*ws)[4], int slot) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+  if ((threadIdx.x & 63) == 0) ws[slot][threadIdx.x >> 6] = v;
+  __syncthreads();
+  return (ws[slot][0] + ws[slot][1]) + (ws[slot][2] + ws[slot][3]);
+}
+
+// The value and the 3 + d derivatives from the pieces (one workgroup): thread t adds entries t, t + 256, ... in ascending
+// order, then block256_sum.  sums: the d + 1 outputs of the reduction with P = K_y^-1.
+__global__ __launch_bounds__(256) void gp_mll_finish_kernel(int64_t n, int d, double outputscale, const double *__restrict__ r,
+                                                             const double *__restrict__ alpha, const double *__restrict__ Lc,
+                                                             int64_t ldlc, const double *__restrict__ P, int64_t ldp,
+                                                             const double *__restrict__ sums, double *__restrict__ out) {
+  __shared__ double ws[4][4];
+  double ra = 0.0, ld = 0.0, sa = 0.0, tw = 0.0;
+  for (int64_t i = threadIdx.x; i < n; i += 256) {
+    const double a = alpha[i];
+    ra = fma(r[i], a, ra);
+    ld += log(Lc[i * ldlc + i]);
+    sa += a;
+    tw += __dsub_rn(__dmul_rn(a, a), P[i * ldp + i]);  // W_ii
+  }
+  ra = block256_sum(ra, ws, 0);
+  ld = block256_sum(ld, ws, 1);
+  sa = block256_sum(sa, ws, 2);
+  tw = block256_sum(tw, ws, 3);
+  if (threadIdx.x == 0) {
+    out[0] = -0.5 * ra - ld - 0.5 * (double)n * 1.8378770664093454836;  // log 2 pi
+    out[1] = sa;
+    out[2] = 0.5 * tw;
+    out[3] = 0.5 * outputscale * sums[0];
+  }
+  if ((int)threadIdx.x < d) out[4 + threadIdx.x] = 0.5 * sums[1 + threadIdx.x];
+}
+
+struct GpMllPlan {  // offsets in doubles into the workspace of pls_gp_mll_grad
+  int64_t ld, plane, r, alpha, partials, sums, total;
+};
+static GpMllPlan gp_mll_plan(int64_t n, int64_t d) {
+  GpMllPlan p;
+  p.ld = gp_mll_ld(n);
+  p.plane = n * p.ld;
+  p.r = 7 * p.plane;
+  p.alpha = p.r + gp_mll_vec(n);
+  p.partials = p.alpha + gp_mll_vec(n);
+  p.sums = p.partials + gp_mll_vec(grad_sums_blocks(n) * (d + 1));
+  p.total = p.sums + gp_mll_vec(d + 1);
+  return p;
+}
+
+static bool stationary_kind(int32_t kind) {
+  return kind == PLS_KERNEL_RBF_ARD || kind == PLS_KERNEL_MATERN12 || kind == PLS_KERNEL_MATERN32 || kind == PLS_KERNEL_MATERN52;
+}
+
+}  // namespace plship
+
+using namespace plship;
+
+extern "C" {
+
+size_t pls_kernel_grad_sums_workspace_bytes(int64_t n, int64_t d) {
+  return (n > 0 && d > 0 && d <= GRAD_D_MAX) ? grad_sums_workspace_bytes(n, d) : 0;
+}
+
+int pls_kernel_grad_sums(int32_t kernel_kind, const double *x, int64_t n, int64_t d, const double *lengthscale,
+                         double outputscale, const double *alpha, const double *P, int64_t ldp, double *out, void *workspace,
+                         size_t workspace_bytes, void *stream) {
+  PLS_REQUIRE(kernel_kind != PLS_KERNEL_LINEAR, "kernel_grad_sums: the linear kernel has no lengthscale or outputscale to learn");
+  PLS_REQUIRE(stationary_kind(kernel_kind), "kernel_grad_sums: unknown kernel kind %d", kernel_kind);
+  PLS_REQUIRE(n > 0 && d > 0, "kernel_grad_sums: bad sizes n=%lld d=%lld", (long long)n, (long long)d);
+  PLS_REQUIRE(d <= GRAD_D_MAX, "kernel_grad_sums: input dimension %lld > 64 is not supported", (long long)d);
+  PLS_REQUIRE(cdiv(n, GRAD_ROWS) <= 65535, "kernel_grad_sums: n=%lld too large", (long long)n);
+  PLS_REQUIRE(x && lengthscale && alpha && P && out, "kernel_grad_sums: NULL pointer");
+  PLS_REQUIRE(ldp >= n, "kernel_grad_sums: ldp < n");
+  PLS_REQUIRE(workspace, "kernel_grad_sums: NULL workspace");
+  if (workspace_bytes < pls_kernel_grad_sums_workspace_bytes(n, d))
+    return fail(PLS_ERR_WORKSPACE_TOO_SMALL, "kernel_grad_sums: workspace of %zu bytes, %zu needed", workspace_bytes,
+                pls_kernel_grad_sums_workspace_bytes(n, d));
+  PLS_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, "kernel_grad_sums: workspace must be 8-byte aligned");
+  return grad_sums_launch(kernel_kind, x, n, (int)d, lengthscale, outputscale, alpha, P, ldp, out,
+                          static_cast<double *>(workspace), S(stream));
+}
+
+size_t pls_gp_mll_workspace_bytes(int64_t n, int64_t d) {
+  return (n > 0 && d > 0 && d <= GRAD_D_MAX) ? (size_t)gp_mll_plan(n, d).total * sizeof(double) : 0;
+}
+
+int pls_gp_mll_grad(int32_t kernel_kind, const double *x, int64_t n, int64_t d, const double *lengthscale, double outputscale,
+                    double noise, double mean, double jitter, const double *y, double *out, int32_t *info, void *workspace,
+                    size_t workspace_bytes, void *stream) {
+  PLS_REQUIRE(kernel_kind != PLS_KERNEL_LINEAR, "gp_mll_grad: the linear kernel has no lengthscale or outputscale to learn");
+  PLS_REQUIRE(stationary_kind(kernel_kind), "gp_mll_grad: unknown kernel kind %d", kernel_kind);
+  PLS_REQUIRE(n > 0 && d > 0, "gp_mll_grad: bad sizes n=%lld d=%lld", (long long)n, (long long)d);
+  PLS_REQUIRE(d <= GRAD_D_MAX, "gp_mll_grad: input dimension %lld > 64 is not supported", (long long)d);
+  PLS_REQUIRE(cdiv(n, GRAD_ROWS) <= 65535, "gp_mll_grad: n=%lld too large", (long long)n);
+  PLS_REQUIRE(x && lengthscale && y && out && info, "gp_mll_grad: NULL pointer");
+  PLS_REQUIRE(noise >= 0.0, "gp_mll_grad: noise must be >= 0");
+  PLS_REQUIRE(jitter >= 0.0, "gp_mll_grad: jitter must be >= 0");
+  PLS_REQUIRE(workspace, "gp_mll_grad: NULL workspace");
+  if (workspace_bytes < pls_gp_mll_workspace_bytes(n, d))
+    return fail(PLS_ERR_WORKSPACE_TOO_SMALL, "gp_mll_grad: workspace of %zu bytes, %zu needed", workspace_bytes,
+                pls_gp_mll_workspace_bytes(n, d));
+  PLS_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "gp_mll_grad: workspace must be 16-byte aligned");
+  hipStream_t st = S(stream);
+  const GpMllPlan p = gp_mll_plan(n, d);
+  double *w = static_cast<double *>(workspace);
+  double *Ky = w, *Lc = w + p.plane, *LcT = w + 2 * p.plane, *Sf = w + 3 * p.plane, *Sb = w + 4 * p.plane;
+  double *Linv = w + 5 * p.plane, *LinvT = w + 6 * p.plane;
+  double *r = w + p.r, *al = w + p.alpha, *partials = w + p.partials, *sums = w + p.sums;
+  // 1. K_y = s kappa(x, x) + (noise + jitter) I   (the Gram matrix passes through the plane of Linv, still free)
+  int rc = pls_kernel_gram(kernel_kind, x, n, x, n, d, lengthscale, outputscale, Linv, p.ld, stream);
+  if (rc) return rc;
+  rc = launch_scale_add_diag(Linv, p.ld, 1.0, noise + jitter, Ky, p.ld, n, st);
+  if (rc) return rc;
+  // 2. K_y = Lc Lc^T and the substitution operators
+  rc = pls_chol_factor(Ky, p.ld, n, 0.0, Lc, p.ld, LcT, p.ld, Sf, p.ld, Sb, p.ld, info, stream);
+  if (rc) return rc;
+  pls_chol_desc f{};
+  f.m = n;
+  f.Lc = Lc, f.ldlc = p.ld, f.LcT = LcT, f.ldlct = p.ld, f.Sf = Sf, f.ldsf = p.ld, f.Sb = Sb, f.ldsb = p.ld;
+  // 3. alpha = K_y^-1 (y - mean)
+  hipLaunchKernelGGL(gp_center_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, y, mean, n, r);
+  if ((rc = check_launch("gp_center"))) return rc;
+  rc = pls_chol_solve(&f, r, 1, 1, al, 1, stream);
+  if (rc) return rc;
+  // 4. Linv = Lc^-1, then P = K_y^-1 = Linv^T Linv over the plane of K_y (Linv lower triangular: only k >= row contracted)
+  rc = pls_chol_build_inverse(&f, Linv, p.ld, LinvT, p.ld, stream);
+  if (rc) return rc;
+  rc = gemm_tn_ex(Linv, p.ld, Linv, p.ld, Ky, p.ld, n, n, n, 1.0, 0.0, 2, st);
+  if (rc) return rc;
+  // 5. the d + 1 sums with P = K_y^-1
+  rc = grad_sums_launch(kernel_kind, x, n, (int)d, lengthscale, outputscale, al, Ky, p.ld, sums, partials, st);
+  if (rc) return rc;
+  // 6. value and derivatives
+  hipLaunchKernelGGL(gp_mll_finish_kernel, dim3(1), dim3(256), 0, st, n, (int)d, outputscale, r, al, Lc, p.ld, Ky, p.ld, sums, out);
+  return check_launch("gp_mll_finish");
+}
+
+}  // extern "C"
