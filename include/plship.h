@@ -533,6 +533,39 @@ int pls_gp_mll_grad(int32_t kernel_kind, const double *x, int64_t n, int64_t d, 
                     double *out /* 4 + d, device or mapped pinned host */, int32_t *info /* device */,
                     void *workspace, size_t workspace_bytes, void *stream);
 
+/* The same evaluation for `classes` independent GPs on the shared x, in ONE call: the per-epoch work of exact-GP
+ * classification with gpytorch's DirichletClassificationLikelihood(learn_additional_noise=True) and a batch of
+ * num_classes GPs (experiments/curves/classification/main.py:162-192; Milios et al. 2018).  Class c has its own
+ * lengthscales, outputscale s_c, constant mean, learned noise sigma_c and a FIXED noise per point:
+ *   K_y,c = s_c kappa(x, x; l_c) + diag(fixed_noise[c][.] + noise[c] + jitter)
+ * fixed_noise == NULL: no fixed part (row c is then exactly pls_gp_mll_grad with class c's parameters).
+ *   lengthscale (classes x d, contiguous) DEVICE;  outputscale, noise, mean (classes each) HOST arrays, read before the
+ *   call returns;  fixed_noise (classes x n, leading dimension ldf) and y (classes x n, leading dimension ldy) DEVICE.
+ *   out (classes x (4 + d), contiguous; device or mapped pinned host): row c laid out as the out of pls_gp_mll_grad,
+ *   out[c][2] the derivative with respect to noise[c];  info (classes, DEVICE int32): per class as pls_gp_mll_grad.
+ * A non-positive pivot in class c is reported in info[c] alone: the call returns PLS_OK and the rows of the other classes
+ * are valid.  The classes run one after another on `stream` and share the workspace of ONE evaluation:
+ *   pls_gp_mll_classes_workspace_bytes(n, d, classes) = pls_gp_mll_workspace_bytes(n, d)   (16-byte aligned). */
+size_t pls_gp_mll_classes_workspace_bytes(int64_t n, int64_t d, int64_t classes);
+int pls_gp_mll_grad_classes(int32_t kernel_kind, const double *x, int64_t n, int64_t d, int64_t classes,
+                            const double *lengthscale /* device */, const double *outputscale /* host */,
+                            const double *noise /* host */, const double *mean /* host */,
+                            const double *fixed_noise /* device, may be NULL */, int64_t ldf, const double *y, int64_t ldy,
+                            double jitter, double *out /* classes x (4 + d) */, int32_t *info /* classes, device */,
+                            void *workspace, size_t workspace_bytes, void *stream);
+
+/* Class probabilities of the Dirichlet GP at t test points from the latent means mu and variances var (classes x t,
+ * leading dimensions ldmu, ldvar; device): the Monte-Carlo mean of the softmax under independent normals,
+ *   out[i][c] = (1 / samples) sum_s softmax_c(mu[.][i] + sqrt(max(var[.][i], 0)) z[s][.])      out: t x classes (ldo), device
+ * with z[s][c] element (row s, column c) of the library's normal matrix (PLS_NOISE_PHILOX) for step = first_point + i
+ * under `seed`: the draws of a test point depend on its global index alone, so a batch of points can be split.
+ * The softmax subtracts the maximum first.  Summation order: one wave per point; lane l adds the sample pairs
+ * (s, s + 4), s = 8 (p / 4) + p % 4, of p = l, l + 64, ... in ascending order, then an xor butterfly over the 64 lanes
+ * (offsets 32 ... 1), then the division by `samples`.  No atomics: two calls give the same bits.
+ * classes <= 64; any samples >= 1 and t >= 1.  Nothing synchronises or allocates. */
+int pls_softmax_normal_mean(const double *mu, int64_t ldmu, const double *var, int64_t ldvar, int64_t classes, int64_t t,
+                            int64_t samples, uint64_t seed, uint64_t first_point, double *out, int64_t ldo, void *stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Orthonormal basis: setup + step
  * ------------------------------------------------------------------------------------------- */

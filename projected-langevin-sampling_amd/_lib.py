@@ -206,6 +206,9 @@ SIGNATURES = {
     "pls_kernel_grad_sums": (C.c_int, [_I32, _P, _I64, _I64, _P, _D, _P, _P, _I64, _P, _P, _SZ, _P]),
     "pls_gp_mll_workspace_bytes": (_SZ, [_I64, _I64]),
     "pls_gp_mll_grad": (C.c_int, [_I32, _P, _I64, _I64, _P, _D, _D, _D, _D, _P, _P, _P, _P, _SZ, _P]),
+    "pls_gp_mll_classes_workspace_bytes": (_SZ, [_I64, _I64, _I64]),
+    "pls_gp_mll_grad_classes": (C.c_int, [_I32, _P, _I64, _I64, _I64, _P, _P, _P, _P, _P, _I64, _P, _I64, _D, _P, _P, _P, _SZ, _P]),
+    "pls_softmax_normal_mean": (C.c_int, [_P, _I64, _P, _I64, _I64, _I64, _I64, _U64, _U64, _P, _I64, _P]),
 }
 
 ABI_VERSION = 7

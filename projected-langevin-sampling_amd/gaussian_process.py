@@ -6,9 +6,12 @@ Replaces ``src/gaussian_process/exact_gp.py`` as it is used by ``train_exact_gp`
 (experiments/constructors.py:9-53).  The reference builds these on gpytorch (ConstantMean, ScaleKernel(RBFKernel |
 MaternKernel), GaussianLikelihood, ExactMarginalLogLikelihood); here the model is a plain parameter holder and one
 evaluation of the marginal log-likelihood with its gradient is ONE library call, ``pls_gp_mll_grad`` (csrc/gp_mll.hip).
-One output, Gaussian likelihood; no gpytorch objects anywhere."""
+One output with a Gaussian likelihood (``ExactGP``), or classification with the Dirichlet likelihood of Milios et al. 2018 as
+the reference's two classification drivers use it (``DirichletExactGP``: one GP per class, ``pls_gp_mll_grad_classes``);
+no gpytorch objects anywhere."""
 from __future__ import annotations
 
+import ctypes
 import math
 import warnings
 from typing import Callable, List, Sequence, Tuple
@@ -36,6 +39,26 @@ def _inverse_softplus(v: torch.Tensor) -> torch.Tensor:
     return v + torch.log(-torch.expm1(-v))
 
 
+def _kernel_choice(who: str, kernel, nu: float, ard: bool, d: int):
+    """(name, nu, ard, start) of the ``kernel`` argument of ExactGP / DirichletExactGP; start: the kernel object whose values
+    the raw parameters start from, or None"""
+    start = None
+    if isinstance(kernel, BaseKernel):
+        if not isinstance(kernel, (ARDKernel, MaternKernel)):
+            raise TypeError(f"{who}: the kernel must be an ARDKernel or a MaternKernel (a lengthscale and an outputscale to learn)")
+        start = kernel
+        name, nu = ("matern", kernel.nu) if isinstance(kernel, MaternKernel) else ("rbf", nu)
+        ard = kernel.lengthscale.numel() > 1 or d == 1 and ard
+    else:
+        if kernel not in _KERNEL_NAMES:
+            raise ValueError(f"{who}: kernel must be one of {sorted(_KERNEL_NAMES)} or a kernel object, got {kernel!r}")
+        name, named_nu = _KERNEL_NAMES[kernel]
+        nu = named_nu if named_nu is not None else nu
+    if name == "matern" and float(nu) not in MaternKernel.KINDS:
+        raise ValueError(f"{who}: nu must be 0.5, 1.5 or 2.5, got {nu}")
+    return name, (float(nu) if name == "matern" else None), bool(ard), start
+
+
 class ExactGP:
     """Exact GP regression with a constant mean, a scaled stationary kernel and Gaussian noise, parametrised as gpytorch
     does: ``lengthscale = softplus(raw)``, ``outputscale = softplus(raw)``, ``noise = 1e-4 + softplus(raw)``, the mean
@@ -58,22 +81,8 @@ class ExactGP:
         self.y = y.detach().reshape(-1).to(torch.float64)
         assert self.x.shape[0] == self.y.shape[0] and self.x.shape[0] > 0, "x (n, d) and y (n) must share n > 0"
         self.n, self.d = self.x.shape
-        start = None
-        if isinstance(kernel, BaseKernel):
-            if not isinstance(kernel, (ARDKernel, MaternKernel)):
-                raise TypeError("ExactGP: the kernel must be an ARDKernel or a MaternKernel (a lengthscale and an outputscale to learn)")
-            start = kernel
-            name, nu = ("matern", kernel.nu) if isinstance(kernel, MaternKernel) else ("rbf", nu)
-            ard = kernel.lengthscale.numel() > 1 or self.d == 1 and ard
-        else:
-            if kernel not in _KERNEL_NAMES:
-                raise ValueError(f"ExactGP: kernel must be one of {sorted(_KERNEL_NAMES)} or a kernel object, got {kernel!r}")
-            name, named_nu = _KERNEL_NAMES[kernel]
-            nu = named_nu if named_nu is not None else nu
-        self.kernel_name, self.ard = name, bool(ard)
-        self.nu = float(nu) if name == "matern" else None
-        if name == "matern" and self.nu not in MaternKernel.KINDS:
-            raise ValueError(f"ExactGP: nu must be 0.5, 1.5 or 2.5, got {nu}")
+        name, nu, ard, start = _kernel_choice("ExactGP", kernel, nu, ard, self.d)
+        self.kernel_name, self.ard, self.nu = name, ard, nu
         self.kind = MaternKernel.KINDS[self.nu] if name == "matern" else L.KERNEL_RBF_ARD
         nls = self.d if self.ard else 1
         raw = torch.zeros(3 + nls, dtype=torch.float64)
@@ -199,15 +208,244 @@ class ExactGP:
         return mean[:, 0] + self.mean_constant, var, var + self.noise
 
 
+#: gpytorch's DirichletClassificationLikelihood: the Dirichlet concentration of a class that was not observed
+ALPHA_EPSILON = 0.01
+
+
+def dirichlet_targets(labels: torch.Tensor, number_of_classes: int | None = None, alpha_epsilon: float = ALPHA_EPSILON,
+                      target_dtype: torch.dtype = torch.float32) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(transformed targets, fixed noise), both (C, n) float64, of integer labels in 0 .. C - 1 (Milios et al. 2018 as
+    gpytorch's DirichletClassificationLikelihood._prepare_targets states it): with a_ci = alpha_epsilon + [y_i == c],
+    v_ci = log(1 / a_ci + 1) and y~_ci = log a_ci - v_ci / 2.  Both are rounded to ``target_dtype`` (gpytorch's ``dtype``
+    argument, float32 by default) and then promoted to float64.  C defaults to ``labels.max() + 1``."""
+    labels = torch.as_tensor(labels).detach().reshape(-1).cpu()
+    if labels.numel() == 0:
+        raise ValueError("dirichlet_targets: no labels")
+    if labels.is_floating_point():
+        if not torch.equal(labels, labels.round()):
+            raise ValueError("dirichlet_targets: the labels must be integers")
+    labels = labels.to(torch.int64)
+    classes = int(labels.max()) + 1 if number_of_classes is None else int(number_of_classes)
+    if classes < 1 or int(labels.min()) < 0 or int(labels.max()) >= classes:
+        raise ValueError(f"dirichlet_targets: labels must lie in 0 .. {classes - 1}, got {int(labels.min())} .. {int(labels.max())}")
+    if target_dtype not in (torch.float32, torch.float64):
+        raise ValueError("dirichlet_targets: target_dtype must be torch.float32 or torch.float64")
+    a = torch.full((classes, labels.numel()), float(alpha_epsilon), dtype=torch.float64)
+    a[labels, torch.arange(labels.numel())] += 1.0
+    v = torch.log(1.0 / a + 1.0)
+    targets = torch.log(a) - 0.5 * v
+    return targets.to(target_dtype).to(torch.float64), v.to(target_dtype).to(torch.float64)
+
+
+class DirichletExactGP:
+    """Exact-GP classification with the Dirichlet likelihood: ``number_of_classes`` independent GPs on the shared x, class c
+    with a constant mean m_c, K_c = s_c kappa(x, x; l_c) and K_y,c = K_c + diag(v_c) + sigma_c I, where v_c is the fixed
+    per-point noise of ``dirichlet_targets`` and sigma_c = 1e-4 + softplus(raw) the learned "second noise"
+    (``learn_additional_noise=True``); regression targets are the transformed labels.  Replaces the batch-of-classes
+    gpytorch model of experiments/curves/classification/main.py:162-192 and experiments/uci/classification/main.py:133-163.
+
+    ``raw`` is ONE (C, 3 + nls) float64 CPU parameter, row c in ExactGP's column order (mean, raw noise, raw outputscale,
+    raw lengthscales); every raw value starts at 0.  ``transformed_targets`` and ``fixed_noise`` are (C, n);
+    ``fixed_noise=False`` leaves the fixed part out (``self.fixed_noise`` is then None): what the reference trains on
+    when its subsample is smaller than its data.
+    One evaluation of all classes is ONE library call with one read-back, ``pls_gp_mll_grad_classes``."""
+
+    def __init__(self, x: torch.Tensor, labels: torch.Tensor, kernel="rbf", nu: float = 2.5, ard: bool = True,
+                 number_of_classes: int | None = None, alpha_epsilon: float = ALPHA_EPSILON,
+                 target_dtype: torch.dtype = torch.float32, fixed_noise: bool = True):
+        x = x.detach()
+        self.x = (x if x.dim() == 2 else x[:, None]).to(torch.float64)
+        self.labels = torch.as_tensor(labels).detach().reshape(-1).cpu().to(torch.int64)
+        assert self.x.shape[0] == self.labels.shape[0] and self.x.shape[0] > 0, "x (n, d) and labels (n) must share n > 0"
+        self.n, self.d = self.x.shape
+        self.transformed_targets, v = dirichlet_targets(labels, number_of_classes, alpha_epsilon, target_dtype)
+        self.fixed_noise = v if fixed_noise else None
+        self.number_of_classes = self.transformed_targets.shape[0]
+        name, nu, ard, start = _kernel_choice("DirichletExactGP", kernel, nu, ard, self.d)
+        self.kernel_name, self.ard, self.nu = name, ard, nu
+        self.kind = MaternKernel.KINDS[self.nu] if name == "matern" else L.KERNEL_RBF_ARD
+        nls = self.d if self.ard else 1
+        raw = torch.zeros(self.number_of_classes, 3 + nls, dtype=torch.float64)
+        if start is not None:
+            assert start.lengthscale.numel() in (1, nls), "the kernel's lengthscales do not fit the data"
+            raw[:, 2] = _inverse_softplus(torch.tensor(start.outputscale, dtype=torch.float64))
+            raw[:, 3:] = _inverse_softplus(start.lengthscale.expand(nls) if start.lengthscale.numel() == 1 else start.lengthscale)
+        self.raw = torch.nn.Parameter(raw)
+        self._dev: dict = {}
+
+    # ---- parameters -------------------------------------------------------------------------------------------------
+    def raw_parameters(self) -> torch.Tensor:
+        """A copy of ``raw`` (C, 3 + nls; float64, CPU)."""
+        return self.raw.detach().clone()
+
+    def set_raw_parameters(self, raw: torch.Tensor) -> "DirichletExactGP":
+        raw = torch.as_tensor(raw, dtype=torch.float64)
+        assert raw.shape == self.raw.shape, f"raw parameters of shape {tuple(self.raw.shape)} expected, got {tuple(raw.shape)}"
+        with torch.no_grad():
+            self.raw.copy_(raw)
+        return self
+
+    @property
+    def mean_constant(self) -> torch.Tensor:
+        return self.raw.detach()[:, 0].clone()
+
+    @property
+    def noise(self) -> torch.Tensor:
+        """(C) the learned second noise sigma_c"""
+        return NOISE_LOWER_BOUND + _softplus(self.raw.detach()[:, 1])
+
+    @property
+    def outputscale(self) -> torch.Tensor:
+        return _softplus(self.raw.detach()[:, 2])
+
+    @property
+    def lengthscale(self) -> torch.Tensor:
+        """(C, d) lengthscales (a shared one repeated)."""
+        ls = _softplus(self.raw.detach()[:, 3:])
+        return ls.expand(self.number_of_classes, self.d).clone() if ls.shape[1] == 1 and self.d > 1 else ls
+
+    def _make_kernel(self, lengthscale: torch.Tensor, outputscale: float) -> BaseKernel:
+        if self.kernel_name == "matern":
+            return MaternKernel(lengthscale, outputscale, nu=self.nu)
+        return ARDKernel(lengthscale, outputscale)
+
+    @property
+    def kernels(self) -> List[BaseKernel]:
+        """The fitted kernel of every class."""
+        ls, s = self.lengthscale, self.outputscale
+        return [self._make_kernel(ls[c], float(s[c])) for c in range(self.number_of_classes)]
+
+    @property
+    def kernel(self) -> BaseKernel:
+        """ONE kernel for PLSKernel and the inducing-point selectors: the raw kernel parameters averaged over the classes,
+        softplus applied afterwards (constructors.py:28-53 with one model)."""
+        return construct_average_ard_kernel([self])
+
+    # ---- the loss ---------------------------------------------------------------------------------------------------
+    def chain_rule(self, out: torch.Tensor) -> Tuple[float, torch.Tensor]:
+        """(-sum_c mll_c / n, its gradient with respect to ``raw`` (C, 3 + nls)) from the (C, 4 + d) outputs of
+        pls_gp_mll_grad_classes at the current parameters: host arithmetic only."""
+        out = torch.as_tensor(out, dtype=torch.float64).reshape(self.number_of_classes, 4 + self.d)
+        raw = self.raw.detach()
+        slope = torch.sigmoid(raw)  # d softplus(raw) / d raw
+        g = torch.empty_like(raw)
+        g[:, 0] = out[:, 1]
+        g[:, 1] = out[:, 2] * slope[:, 1]
+        g[:, 2] = out[:, 3] / _softplus(raw[:, 2]) * slope[:, 2]
+        per_dim = out[:, 4:] / self.lengthscale
+        g[:, 3:] = (per_dim if self.ard else per_dim.sum(dim=1, keepdim=True)) * slope[:, 3:]
+        return -float(out[:, 0].sum()) / self.n, -g / self.n
+
+    def _device_state(self) -> dict:
+        if not self._dev:
+            from .kernel import _dev
+
+            lib = L.load()
+            x = _dev(self.x)
+            c, width = self.number_of_classes, 4 + self.d
+            nbytes = int(lib.pls_gp_mll_classes_workspace_bytes(self.n, self.d, c))
+            self._dev = {
+                "x": x, "y": _dev(self.transformed_targets.contiguous()),
+                "fixed": _dev(self.fixed_noise.contiguous()) if self.fixed_noise is not None else None,
+                "ws": torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=x.device),
+                # the C (4 + d) outputs and behind them the C int32 info words: one read-back per evaluation
+                "out": torch.zeros(c * width + (c + 1) // 2, dtype=torch.float64, device=x.device),
+            }
+        return self._dev
+
+    def evaluate_on_device(self, jitter: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor]:
+        """One pls_gp_mll_grad_classes call at the current parameters: (the (C, 4 + d) outputs on the CPU, info (C))."""
+        st = self._device_state()
+        c, width = self.number_of_classes, 4 + self.d
+        ls = st["x"].new_tensor(self.lengthscale.tolist()).contiguous()
+        host = (ctypes.c_double * c)
+        s, noise, mean = host(*self.outputscale.tolist()), host(*self.noise.tolist()), host(*self.mean_constant.tolist())
+        out, ws, fixed = st["out"], st["ws"], st["fixed"]
+        L.check(
+            L.load().pls_gp_mll_grad_classes(self.kind, st["x"].data_ptr(), self.n, self.d, c, ls.data_ptr(),
+                                             ctypes.cast(s, ctypes.c_void_p), ctypes.cast(noise, ctypes.c_void_p),
+                                             ctypes.cast(mean, ctypes.c_void_p), fixed.data_ptr() if fixed is not None else None,
+                                             self.n, st["y"].data_ptr(), self.n, float(jitter), out.data_ptr(),
+                                             out.data_ptr() + 8 * c * width, ws.data_ptr(), ws.numel() * 8, L.stream_ptr()),
+            "pls_gp_mll_grad_classes",
+        )
+        got = out.cpu()
+        return got[: c * width].reshape(c, width), got[c * width:].view(torch.int32)[:c].clone()
+
+    def loss_and_grad(self) -> Tuple[float, torch.Tensor]:
+        """(-sum_c mll_c / n, its gradient with respect to ``raw``).  When ANY class meets a non-positive pivot the whole
+        call is retried with psd_safe_cholesky's jitters (1e-8, 1e-7, 1e-6), a warning per attempt, NotPSDError after
+        the last."""
+        attempts = [0.0] + [CHOLESKY_JITTER * 10**i for i in range(CHOLESKY_MAX_TRIES)]
+        for jit in attempts:
+            if jit > 0.0:
+                warnings.warn(f"A not p.d., added jitter of {jit:.1e} to the diagonal", RuntimeWarning, stacklevel=2)
+            out, info = self.evaluate_on_device(jit)
+            if not info.any():
+                return self.chain_rule(out)
+        raise NotPSDError(f"Matrix not positive definite after repeatedly adding jitter up to {attempts[-1]:.1e}.")
+
+    # ---- prediction -------------------------------------------------------------------------------------------------
+    def predict(self, x_test: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(latent mean, latent variance), both (C, t) float64 on the device: per class m_c + k*^T alpha_c and
+        k** - |Lc^-1 k*|^2 with K_y,c = Lc Lc^T and alpha_c = K_y,c^-1 (y~_c - m_c)."""
+        st = self._device_state()
+        xt = x_test if x_test.dim() == 2 else x_test[:, None]
+        means, variances = [], []
+        noise, mean_c, s = self.noise.tolist(), self.mean_constant.tolist(), self.outputscale.tolist()
+        for c, kern in enumerate(self.kernels):
+            ky = kern(st["x"], st["x"])
+            ky.diagonal().add_(st["fixed"][c] + noise[c] if st["fixed"] is not None else noise[c])
+            factor = cholesky_factor(ky)
+            alpha = factor.solve((st["y"][c] - mean_c[c])[:, None].contiguous())
+            ks = kern(st["x"], xt)  # (n, t): k-major
+            t = ks.shape[1]
+            mean = torch.empty((t, 1), dtype=torch.float64, device=ks.device)
+            L.check(L.load().pls_gemm_tn(ks.data_ptr(), L.ld(ks), alpha.data_ptr(), 1, mean.data_ptr(), 1, t, 1, self.n, 1.0, 0.0,
+                                         L.stream_ptr()), "pls_gemm_tn")
+            v = factor.forward_solve(ks)
+            means.append(mean[:, 0] + mean_c[c])
+            variances.append(s[c] - v.square().sum(dim=0))
+        return torch.stack(means), torch.stack(variances)
+
+    def predict_proba(self, x_test: torch.Tensor, number_of_samples: int = 256, seed: int = 0) -> torch.Tensor:
+        """(t, C) class probabilities: the mean over ``number_of_samples`` draws of softmax(f), f_c ~ N(mean_c, var_c)
+        independently (gpytorch's ``pred.sample(...).exp()`` normalised and averaged), on the library's Philox stream
+        (pls_softmax_normal_mean): test point i draws under ``seed`` with step i."""
+        mean, var = self.predict(x_test)
+        return softmax_normal_mean(mean, var, number_of_samples, seed)
+
+
+def softmax_normal_mean(mean: torch.Tensor, variance: torch.Tensor, number_of_samples: int = 256, seed: int = 0,
+                        first_point: int = 0) -> torch.Tensor:
+    """pls_softmax_normal_mean on (C, t) device tensors of latent means and variances -> (t, C) probabilities; column i
+    draws under ``seed`` with step ``first_point + i``, so a long list of test points can be split into calls."""
+    assert mean.dim() == 2 and mean.shape == variance.shape and mean.is_cuda and variance.is_cuda
+    mean, variance = mean.to(torch.float64).contiguous(), variance.to(torch.float64).contiguous()
+    c, t = mean.shape
+    out = torch.empty((t, c), dtype=torch.float64, device=mean.device)
+    L.check(L.load().pls_softmax_normal_mean(mean.data_ptr(), t, variance.data_ptr(), t, c, t, int(number_of_samples), int(seed),
+                                             int(first_point), out.data_ptr(), c, L.stream_ptr()), "pls_softmax_normal_mean")
+    return out
+
+
 def train_exact_gp(x: torch.Tensor, y: torch.Tensor, kernel, seed: int, number_of_epochs: int, learning_rate: float,
                    early_stopper_patience: float, evaluate: Callable[[ExactGP], Tuple[float, torch.Tensor]] | None = None,
+                   likelihood: str = "gaussian", number_of_classes: int | None = None, fixed_noise: bool = True,
                    ) -> Tuple[ExactGP, List[float]]:
     """experiments/trainers.py:15-52, statement for statement: seed, Adam over the raw parameters, and per epoch the
     loss, the early-stopper check BEFORE the loss is recorded and before the step, then the step.  ``evaluate(model) ->
-    (loss, gradient)`` replaces ``model.loss_and_grad`` (a host evaluation drives the same loop without a device)."""
+    (loss, gradient)`` replaces ``model.loss_and_grad`` (a host evaluation drives the same loop without a device).
+    ``likelihood="dirichlet"``: y holds integer labels and the model is a DirichletExactGP (``number_of_classes`` and
+    ``fixed_noise`` go to it); the loss is then summed over the classes, as the reference's ``.sum()`` over the batch."""
     set_seed(seed)
-    model = ExactGP(x, y, kernel)
-    evaluate = evaluate if evaluate is not None else ExactGP.loss_and_grad
+    if likelihood == "gaussian":
+        model = ExactGP(x, y, kernel)
+    elif likelihood == "dirichlet":
+        model = DirichletExactGP(x, y, kernel, number_of_classes=number_of_classes, fixed_noise=fixed_noise)
+    else:
+        raise ValueError(f"train_exact_gp: likelihood must be 'gaussian' or 'dirichlet', got {likelihood!r}")
+    evaluate = evaluate if evaluate is not None else type(model).loss_and_grad
     optimizer = torch.optim.Adam([model.raw], lr=learning_rate)
     losses: List[float] = []
     early_stopper = EarlyStopper(patience=early_stopper_patience)
@@ -225,9 +463,11 @@ def train_exact_gp(x: torch.Tensor, y: torch.Tensor, kernel, seed: int, number_o
 
 def construct_average_ard_kernel(models: Sequence[ExactGP]) -> BaseKernel:
     """The kernel of the AVERAGED RAW parameters, softplus applied afterwards (constructors.py:28-53 averages the
-    entries of ``state_dict()``, which are the raw values)."""
+    entries of ``state_dict()``, which are the raw values).  A DirichletExactGP holds one row of raw values per class: its
+    rows are averaged first (the reference's ``mean(dim=0)`` over the batch), then the models."""
     first = models[0]
-    raw = torch.stack([m.raw_parameters()[2:] for m in models]).mean(dim=0)
+    per_model = [m.raw_parameters() for m in models]
+    raw = torch.stack([(r.mean(dim=0) if r.dim() == 2 else r)[2:] for r in per_model]).mean(dim=0)
     outputscale, ls = float(_softplus(raw[0])), _softplus(raw[1:])
     ls = ls.expand(first.d).clone() if ls.numel() == 1 and first.d > 1 else ls
     if first.kernel_name == "matern":
@@ -252,9 +492,22 @@ def nearest_subsample(x: torch.Tensor, y: torch.Tensor, size: int, centre: torch
 
 
 def exact_gp_runner(x: torch.Tensor, y: torch.Tensor, kernel, subsample_size: int, seed: int, number_of_epochs: int,
-                    learning_rate: float, number_of_iterations: int, early_stopper_patience: float) -> List[ExactGP]:
+                    learning_rate: float, number_of_iterations: int, early_stopper_patience: float,
+                    likelihood: str = "gaussian", number_of_classes: int | None = None,
+                    subsample_fixed_noise: bool = True) -> List[ExactGP]:
     """runners.py:88-187 without its files and plots: ``number_of_iterations`` exact GPs, each on the ``subsample_size``
-    neighbours of a point drawn under ``seed + i``; ONE on all of the data when the subsample covers it."""
+    neighbours of a point drawn under ``seed + i``; ONE on all of the data when the subsample covers it.
+    ``likelihood="dirichlet"``: y holds integer labels; ``number_of_classes`` (default: ``y.max() + 1``) is taken from ALL
+    of the data, because a subsample may lack a class.  ``subsample_fixed_noise=False`` trains a subsample that is smaller
+    than the data without the fixed per-point noise, as the reference does (its likelihood is built on all N labels and
+    gpytorch replaces a fixed noise of another length by zero)."""
+    options = {}
+    if likelihood == "dirichlet":
+        classes = int(y.max()) + 1 if number_of_classes is None else int(number_of_classes)
+        options = dict(likelihood=likelihood, number_of_classes=classes,
+                       fixed_noise=bool(subsample_fixed_noise) or subsample_size >= x.shape[0])
+    elif likelihood != "gaussian":
+        raise ValueError(f"exact_gp_runner: likelihood must be 'gaussian' or 'dirichlet', got {likelihood!r}")
     if subsample_size >= x.shape[0]:
         number_of_iterations = 1
     models = []
@@ -262,10 +515,10 @@ def exact_gp_runner(x: torch.Tensor, y: torch.Tensor, kernel, subsample_size: in
         set_seed(seed + i)
         centre = x[torch.randperm(x.shape[0])[0]]  # sample_point (src/samplers.py:47-62)
         xs, ys = nearest_subsample(x, y, subsample_size, centre)
-        model, _ = train_exact_gp(xs, ys, kernel, seed, number_of_epochs, learning_rate, early_stopper_patience)
+        model, _ = train_exact_gp(xs, ys, kernel, seed, number_of_epochs, learning_rate, early_stopper_patience, **options)
         models.append(model)
     return models
 
 
-__all__ = ["ExactGP", "train_exact_gp", "construct_average_ard_kernel", "construct_average_gaussian_noise", "nearest_subsample",
+__all__ = ["ExactGP", "DirichletExactGP", "dirichlet_targets", "softmax_normal_mean", "train_exact_gp", "construct_average_ard_kernel", "construct_average_gaussian_noise", "nearest_subsample",
            "exact_gp_runner", "NotPSDError"]
