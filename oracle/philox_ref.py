@@ -44,8 +44,11 @@ def normal_matrix(rows: int, cols: int, seed: int, step: int, j_offset: int = 0)
     a = (x0 << np.uint64(32)) | x1
     b = (x2 << np.uint64(32)) | x3
     two_m53 = 2.0**-53
-    u1 = ((a >> np.uint64(11)).astype(np.float64) + 0.5) * two_m53
+    n1 = a >> np.uint64(11)
+    u1 = (n1.astype(np.float64) + 0.5) * two_m53
     u2 = ((b >> np.uint64(11)).astype(np.float64) + 0.5) * two_m53
-    rad = np.sqrt(-2.0 * np.log(u1))
+    # from n1 = 2^52 on u1 does not fit a double; its complement 1 - u1 = (2^53 - 1 - n1 + 1/2) 2^-53 does
+    comp = ((np.uint64(2**53 - 1) - n1).astype(np.float64) + 0.5) * two_m53
+    rad = np.sqrt(-2.0 * np.where(n1 >= np.uint64(2**52), np.log1p(-comp), np.log(u1)))
     hi = np.broadcast_to((i & np.uint64(4)) != 0, shape)
     return np.where(hi, rad * np.sin(2.0 * np.pi * u2), rad * np.cos(2.0 * np.pi * u2))

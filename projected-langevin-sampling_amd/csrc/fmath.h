@@ -101,10 +101,14 @@ __device__ __forceinline__ double fast_div(double a, double b) {
 
 // log(x) after fdlibm's e_log.c: x = 2^k (1 + f) with 1 + f in [sqrt(1/2), sqrt(2)), s = f / (2 + f),
 // log(1 + f) = f - (f^2/2 - s (f^2/2 + R(s^2))), R the degree-7 minimax polynomial (error < 2^-58.45).
-// fast_log_unit: any positive finite argument (subnormals included) -- in particular the uniform deviates of the noise
-// generator, (n + 1/2) 2^-53 with 0 <= n < 2^53, strictly inside (0, 1).  fast_log adds the three special cases (zero,
+// fast_log_unit: any positive finite argument (subnormals included).  fast_log adds the three special cases (zero,
 // infinity, negative: a compare and two 32-bit selects each, 9 vector instructions such an argument can never take).
-__device__ __forceinline__ double fast_log_unit(double x) {
+// fast_log_unit_tail(x, e): log(x + e) for an argument held in two pieces, |e| <= ulp(x) / 2 and x + e = 2^k (1 + f) with f
+// a double (TAIL) -- the uniform deviates of the noise generator, (n + 1/2) 2^-53 with 0 <= n < 2^53: from n = 2^52 on they
+// have 54 significant bits, and rounded to one double their logarithm is off by 2^-54 / (1 - u) relative, without bound as
+// u -> 1 (and log 1 = 0 for n = 2^53 - 1).  The tail enters f = m - 1, which stays exact; everything after f is shared.
+template <bool TAIL>
+__device__ __forceinline__ double fast_log_unit_pieces(double x, double e) {
   // (contraction written out: the noise generator is inlined into several kernels, and left to the compiler `t2 + t1` or
   // `dk * ln2 - ...` became an fma in one and a multiply-add pair in another -- 1 ulp apart in one normal deviate per ~6000,
   // so a particle's noise depended on the tiling its shard happened to take)
@@ -114,7 +118,8 @@ __device__ __forceinline__ double fast_log_unit(double x) {
   const bool low = m < 0.70710678118654752440;
   m = low ? m + m : m;
   k = low ? k - 1 : k;
-  const double f = m - 1.0;
+  double f = m - 1.0;
+  if constexpr (TAIL) f = f + ldexp(e, -k);  // (m - 1 is exact, and so is the sum: the pieces' f has at most 53 bits)
   const double dk = (double)k;
   const double s = fast_div_normal(f, 2.0 + f);
   const double z = s * s, w = z * z;
@@ -126,6 +131,9 @@ __device__ __forceinline__ double fast_log_unit(double x) {
   const double hfsq = 0.5 * f * f;
   return fma(dk, 6.93147180369123816490e-01, -((hfsq - fma(s, hfsq + R, dk * 1.90821492927058770002e-10)) - f));
 }
+
+__device__ __forceinline__ double fast_log_unit(double x) { return fast_log_unit_pieces<false>(x, 0.0); }
+__device__ __forceinline__ double fast_log_unit_tail(double x, double e) { return fast_log_unit_pieces<true>(x, e); }
 
 __device__ __forceinline__ double fast_log(double x) {
   double v = fast_log_unit(x);

@@ -50,7 +50,8 @@ __host__ __device__ inline void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t
 // Every vector instruction of the noise is paid in matrix-pipe issue slots (the f64 MFMA and the VALU do not overlap,
 // DESIGN.md section 3), so the pair costs what its instruction count says.  Same stream as above, to rounding:
 //   * Philox: one v_mad_u64_u32 per 32 x 32 -> 64 product and ONE v_bitop3_b32 per three-way xor (4 VALU per round);
-//   * u1 from the 53 high bits by two exact conversions and two fma (no 64-bit integer -> double sequence);
+//   * u1 from the 53 high bits by two exact conversions and two fma (no 64-bit integer -> double sequence), in two pieces
+//     where it does not fit one double (u1 >= 1/2);
 //   * sqrt by v_rsq_f64 + Newton (the argument -2 ln u1 lies in [1e-16, 75]: no scaling ladder);
 //   * sin / cos of 2 pi u2 without any argument reduction: the top 3 random bits ARE the octant, the next 50 the position
 //     inside it (reflected in odd octants by complementing the bits), then fdlibm's k_sin / k_cos kernels on [0, pi/4].
@@ -109,8 +110,13 @@ __device__ __forceinline__ void normal_pair(uint64_t seed, uint64_t step, int64_
                        (uint32_t)(seed >> 32), x);
   // u1 = ((x0:x1 >> 11) + 0.5) * 2^-53: the 53-bit integer is x0 * 2^21 + (x1 >> 11), both parts exact in a double
   const double n1 = fma((double)x[0], 2097152.0, (double)(x[1] >> 11));
+  // From n = 2^52 on u1 has 54 significant bits: the fma rounds it, and e1 = u1 - (its double) = 0 or +-2^-54 (both fma exact)
+  // goes into the logarithm as a second piece.  Without it -2 ln u1 is off by 2^-54 / (1 - u1) relative: one deviate in 30
+  // more than 9 units of 2^-53 |z| from the stream's definition, and the largest deviate of u1 (n = 2^53 - 1) rounds to 1:
+  // a radius of sqrt(-0).
   const double u1 = fma(n1, 1.1102230246251565e-16, 5.5511151231257827e-17);
-  const double rad = sqrt_normal(-2.0 * fast_log_unit(u1));  // (u1 in [2^-54, 1 - 2^-54]: no special cases)
+  const double e1 = fma(n1, 1.1102230246251565e-16, -u1) + 5.5511151231257827e-17;
+  const double rad = sqrt_normal(-2.0 * fast_log_unit_tail(u1, e1));  // (u1 in [2^-54, 1 - 2^-54]: no special cases)
   // 2 pi u2 = (pi / 4) (o + t), o = top 3 bits of x2, t = ((next 50 bits) + 0.5) * 2^-50 in (0, 1)
 #if defined(__HIP_DEVICE_COMPILE__)
   const uint32_t m = (uint32_t)__builtin_amdgcn_sbfe((int)x[2], 29, 1);  // all ones in odd octants: t -> 1 - t
