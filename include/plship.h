@@ -567,6 +567,83 @@ int pls_softmax_normal_mean(const double *mu, int64_t ldmu, const double *var, i
                             int64_t samples, uint64_t seed, uint64_t first_point, double *out, int64_t ldo, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Sparse variational GP (SVGP) baseline: fixed kernel, fixed inducing points, Gaussian likelihood
+ * ------------------------------------------------------------------------------------------- */
+
+/* Replaces SVGP (src/gaussian_process/svgp.py:6-49), the minibatch loop of train_svgp with is_fixed=True
+ * (experiments/trainers.py:55-136) and train_svgp_for_profiler (experiments/profiler/main.py:85-123).
+ * RECALLED, not read: the arithmetic is gpytorch 1.15's whitened VariationalStrategy + CholeskyVariationalDistribution +
+ * VariationalELBO + GaussianLikelihood as remembered (gpytorch is not available to this project); the formulas below are
+ * the contract.
+ *
+ * Setup (the caller, from existing entries): K_zz = k(Z,Z) + jitter I = L L^T, A = L^-1 k(Z,X) (M x n), held transposed
+ * as At (n x M, leading dimension ldat: one point's M values per row), q_i = k(x_i,x_i) + jitter - sum_p A_pi^2.
+ * State (device): m (M), L_s (M x M, leading dimension ldls; ONLY the lower triangle and the diagonal are ever read or
+ * written), scalars = {c, rho}: the constant mean and the raw noise, sigma^2 = softplus(rho) + 1e-4.
+ * One minibatch idx[0 .. B), a_i row idx[i] of At:
+ *   mu_i = c + a_i . m     w_i = L_s^T a_i     v_i = q_i + |w_i|^2
+ *   l_i  = -1/2 log 2 pi - 1/2 log sigma^2 - ((y_i - mu_i)^2 + v_i) / (2 sigma^2)
+ *   KL   = 1/2 (|tril L_s|_F^2 + |m|^2 - M - 2 sum_p log |L_s,pp|)          ELBO = (1/B) sum_i l_i - KL / n
+ *   d/dm   = (1/B) sum_i g_mu,i a_i - m / n                                  g_mu,i = (y_i - mu_i) / sigma^2
+ *   d/dL_s = tril[(2/B) sum_i g_v,i a_i w_i^T] - (tril L_s - diag(1 / L_s,pp)) / n      g_v,i = -1 / (2 sigma^2)
+ *   d/dc   = (1/B) sum_i g_mu,i
+ *   d/drho = sigmoid(rho) (1/B) sum_i [-1 / (2 sigma^2) + ((y_i - mu_i)^2 + v_i) / (2 sigma^4)]
+ * Both contractions run on v_mfma_f64_16x16x4_f64; every sum has a fixed order (no atomics): two calls give the same
+ * bits, and the outputs depend on the CONTENT of idx only (NULL = rows 0 .. B-1 in order = an explicit identity list).
+ * An index outside 0 .. n-1 is not read: its point becomes NaN.  Nothing synchronises or allocates. */
+typedef enum {
+  PLS_SVGP_GAUSSIAN = 0   /* the only likelihood accepted; the per-point epilogue is a template parameter of the kernels */
+} pls_svgp_likelihood;
+
+typedef enum {
+  PLS_SVGP_TRAIN_MEAN = 1,   /* pls_svgp_sgd_epoch updates c */
+  PLS_SVGP_TRAIN_NOISE = 2   /* pls_svgp_sgd_epoch updates rho */
+} pls_svgp_flags;
+
+typedef struct {
+  const double *At;   /* n x m, leading dimension ldat (columns m .. ldat-1 are never read) */
+  int64_t ldat;
+  const double *q;    /* n */
+  const double *y;    /* n */
+  int64_t n;
+  int64_t m;          /* 1 .. 256 inducing points */
+  int32_t likelihood; /* pls_svgp_likelihood */
+  int32_t reserved;
+} pls_svgp_desc;
+
+/* Workspace of the calls below (8-byte aligned), with MP = m rounded up to 16 and T(k) = ceil(k / 32) tiles of 32 points:
+ *   pls_svgp_workspace_bytes(n, m, batch) = 8 max(4 + 4 max(T(n), T(batch)),  4 + 4 T(batch) + T(batch) MP (MP + 1))
+ * (3 KL sums; 3 scalar partials per tile; per tile of a gradient call MP partials of d/dm and an MP x MP partial of
+ * d/dL_s).  pls_svgp_elbo_grad over b points needs the formula with n = batch = b at most. */
+size_t pls_svgp_workspace_bytes(int64_t n, int64_t m, int64_t batch);
+
+/* One evaluation.  idx: device int64, B entries, or NULL.  out (5, device or mapped pinned host): out[0] = ELBO,
+ * out[1] = d/dc, out[2] = d/drho, out[3] = (1/B) sum l_i, out[4] = KL.  grad_m (M), grad_L (M x M, ldgl; only the lower
+ * triangle is written): gradients of the ELBO.  grad_m == NULL && grad_L == NULL selects the value-only kernel, which
+ * skips the second contraction; its out equals the full call's bit for bit.  Two launches. */
+int pls_svgp_elbo_grad(const pls_svgp_desc *desc, const double *m, const double *L_s, int64_t ldls,
+                       const double *scalars /* {c, rho}, device */, const int64_t *idx, int64_t b, double *out,
+                       double *grad_m, double *grad_L, int64_t ldgl, void *workspace, size_t workspace_bytes, void *stream);
+
+/* One epoch of plain SGD on loss = -ELBO (the inner loop of experiments/trainers.py:120-127): the ceil(n / batch_size)
+ * minibatches perm[0 .. batch_size), perm[batch_size .. ), ... in order (perm: n device int64; the last batch is ragged and
+ * divides by its own length), each followed by p <- p - lr * dloss/dp for m, tril L_s, and c / rho where `flags` has
+ * PLS_SVGP_TRAIN_MEAN / PLS_SVGP_TRAIN_NOISE.  The update is a multiply followed by a subtract (no contraction), so a
+ * replay through pls_svgp_elbo_grad gives the same bits.  Then loss_out[0] (device or mapped pinned host) = -ELBO of the
+ * updated state over all n rows in order (the value-only evaluation).  Two launches per minibatch and two for the loss;
+ * the host does not touch the state in between. */
+int pls_svgp_sgd_epoch(const pls_svgp_desc *desc, double *m, double *L_s, int64_t ldls, double *scalars, const int64_t *perm,
+                       int64_t batch_size, double lr, int32_t flags, double *loss_out, void *workspace,
+                       size_t workspace_bytes, void *stream);
+
+/* Prediction at t points from their rows At_test (t x m, ldat) and q_test (t):  mean_out[i] = c + a_i . m,
+ * var_out[i] = q_i + |L_s^T a_i|^2 (the latent variance; the observation variance adds sigma^2).  scalars as above
+ * (device; only c is read).  One launch. */
+int pls_svgp_predict(const double *m, const double *L_s, int64_t ldls, const double *scalars, const double *At_test,
+                     int64_t ldat, const double *q_test, int64_t t, int64_t mdim, double *mean_out, double *var_out,
+                     void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Orthonormal basis: setup + step
  * ------------------------------------------------------------------------------------------- */
 

@@ -4,13 +4,15 @@ jswu18/projected-langevin-sampling behind the reference's PLS / basis / cost / l
 All numerics run in libplship.so (hand-written HIP for gfx950, see csrc/); this package is the thin host
 side: it owns device memory through torch tensors and calls the C ABI (include/plship.h) with raw pointers."""
 from . import _lib
-from .gaussian_process import (DirichletExactGP, ExactGP, construct_average_ard_kernel, construct_average_gaussian_noise,
+from .gaussian_process import (SVGP, DirichletExactGP, ExactGP, construct_average_ard_kernel, construct_average_gaussian_noise,
                                dirichlet_targets, exact_gp_runner, nearest_subsample, softmax_normal_mean, train_exact_gp)
 from .kernel import ARDKernel, LinearKernel, MaternKernel, PLSKernel
 from .projected_langevin_sampling import PLS
-from .trainers import EarlyStopper, train_pls, train_pls_captured
+from .runners import train_svgp_runner
+from .temper import TemperGP
+from .trainers import EarlyStopper, epoch_batches, train_pls, train_pls_captured, train_svgp
 
 __all__ = ["PLS", "PLSKernel", "ARDKernel", "MaternKernel", "LinearKernel", "EarlyStopper", "train_pls", "train_pls_captured", "ExactGP",
            "DirichletExactGP", "dirichlet_targets", "softmax_normal_mean",
            "train_exact_gp", "exact_gp_runner", "construct_average_ard_kernel", "construct_average_gaussian_noise",
-           "nearest_subsample", "_lib"]
+           "nearest_subsample", "SVGP", "train_svgp", "train_svgp_runner", "epoch_batches", "TemperGP", "_lib"]

@@ -19,6 +19,8 @@ LINK_IDENTITY, LINK_SQUARE, LINK_SIGMOID, LINK_PROBIT = range(4)
 DERIV_REFERENCE, DERIV_AUTOGRAD = 0, 1
 NOISE_NONE, NOISE_INJECTED, NOISE_PHILOX = 0, 1, 2
 OUT_DELTA, OUT_NEW_STATE = 0, 1
+SVGP_GAUSSIAN = 0
+SVGP_TRAIN_MEAN, SVGP_TRAIN_NOISE = 1, 2
 
 
 class PlsHipError(RuntimeError):
@@ -120,6 +122,11 @@ class CholDesc(C.Structure):
     ]
 
 
+class SvgpDesc(C.Structure):
+    _fields_ = [("At", C.c_void_p), ("ldat", C.c_int64), ("q", C.c_void_p), ("y", C.c_void_p), ("n", C.c_int64),
+                ("m", C.c_int64), ("likelihood", C.c_int32), ("reserved", C.c_int32)]
+
+
 class BlockDesc(C.Structure):
     _fields_ = [("block_cols", C.c_int64), ("eta", C.c_void_p), ("energy_sums", C.c_void_p), ("energy_sync", C.c_void_p),
                 ("energy_partials", C.c_void_p), ("energy_partials_prev", C.c_void_p), ("energy_prev", C.c_void_p),
@@ -129,7 +136,7 @@ class BlockDesc(C.Structure):
 
 _P, _I64, _I32, _U64, _D, _SZ = C.c_void_p, C.c_int64, C.c_int32, C.c_uint64, C.c_double, C.c_size_t
 _CD, _ND, _OD, _ID = C.POINTER(CostDesc), C.POINTER(NoiseDesc), C.POINTER(OnbDesc), C.POINTER(IpbDesc)
-_CHD, _BD = C.POINTER(CholDesc), C.POINTER(BlockDesc)
+_CHD, _BD, _SD = C.POINTER(CholDesc), C.POINTER(BlockDesc), C.POINTER(SvgpDesc)
 
 # name -> (restype, argtypes); every symbol include/plship.h declares
 SIGNATURES = {
@@ -209,6 +216,10 @@ SIGNATURES = {
     "pls_gp_mll_classes_workspace_bytes": (_SZ, [_I64, _I64, _I64]),
     "pls_gp_mll_grad_classes": (C.c_int, [_I32, _P, _I64, _I64, _I64, _P, _P, _P, _P, _P, _I64, _P, _I64, _D, _P, _P, _P, _SZ, _P]),
     "pls_softmax_normal_mean": (C.c_int, [_P, _I64, _P, _I64, _I64, _I64, _I64, _U64, _U64, _P, _I64, _P]),
+    "pls_svgp_workspace_bytes": (_SZ, [_I64, _I64, _I64]),
+    "pls_svgp_elbo_grad": (C.c_int, [_SD, _P, _P, _I64, _P, _P, _I64, _P, _P, _P, _I64, _P, _SZ, _P]),
+    "pls_svgp_sgd_epoch": (C.c_int, [_SD, _P, _P, _I64, _P, _P, _I64, _D, _I32, _P, _P, _SZ, _P]),
+    "pls_svgp_predict": (C.c_int, [_P, _P, _I64, _P, _P, _I64, _P, _I64, _I64, _P, _P, _P]),
 }
 
 ABI_VERSION = 7

@@ -208,6 +208,214 @@ class ExactGP:
         return mean[:, 0] + self.mean_constant, var, var + self.noise
 
 
+# ---- sparse variational GP (fixed kernel, fixed inducing points, Gaussian likelihood) ------------------------------------
+#: gpytorch's jitter on k(Z, Z) for float64 data (settings.variational_cholesky_jitter; 1e-4 for float32 data)
+SVGP_JITTER = 1e-6
+SVGP_M_MAX = 256
+
+
+def _kernel_diagonal(kernel, x: torch.Tensor) -> torch.Tensor:
+    """k(x_i, x_i) for every row of the device matrix x, without the n x n Gram matrix."""
+    from .kernel import LinearKernel, PLSKernel, _StationaryKernel
+
+    if isinstance(kernel, _StationaryKernel):
+        return torch.full((x.shape[0],), float(kernel.outputscale), dtype=torch.float64, device=x.device)
+    if isinstance(kernel, LinearKernel):
+        return x.square().sum(dim=1)
+    if isinstance(kernel, PLSKernel):
+        s = kernel.approximation_samples.detach().cpu().to(torch.float64)
+        s = (s if s.dim() == 2 else s[:, None]).unique(dim=0)
+        return kernel.base_kernel(s, x).square().sum(dim=0) / s.shape[0]
+    return torch.cat([kernel(c, c).diagonal() for c in x.split(1024)])
+
+
+class SVGP:
+    """The reference's SVGP baseline (src/gaussian_process/svgp.py:6-49) as every driver trains it (``is_fixed=True``): the
+    kernel and the inducing points are frozen; the variational mean ``m``, the variational Cholesky factor ``L_s``, the
+    constant mean ``c`` and the raw likelihood noise ``rho`` (noise = softplus(rho) + 1e-4) live on the device and are
+    learned by plain SGD on the minibatch ELBO.  The arithmetic is gpytorch 1.15's whitened VariationalStrategy +
+    CholeskyVariationalDistribution + VariationalELBO + GaussianLikelihood AS RECALLED (include/plship.h states the
+    formulas; they are the contract).  Everything that depends on the kernel is computed once, in ``fit_data``; one
+    evaluation is ``pls_svgp_elbo_grad``, one epoch ``pls_svgp_sgd_epoch``, a prediction ``pls_svgp_predict``.
+
+    ``kernel``: any kernel callable of the package (PLSKernel, ARDKernel, MaternKernel, LinearKernel).  ``noise``: the
+    starting likelihood noise (raw value 0 when None).  ``m`` starts at ``mean_init_std`` times standard normals from
+    torch's global generator (drawn here, on the host), ``L_s`` at the identity."""
+
+    def __init__(self, kernel, x_induce: torch.Tensor, likelihood: str = "gaussian", noise: float | None = None,
+                 mean_constant: float = 0.0, learn_inducing_locations: bool = False, jitter: float = SVGP_JITTER,
+                 mean_init_std: float = 1e-3):
+        if learn_inducing_locations:
+            raise NotImplementedError("SVGP: learn_inducing_locations=True is not supported: the inducing points and the "
+                                      "kernel are fixed (the reference's is_fixed=True); only the variational mean, the "
+                                      "variational Cholesky factor, the constant mean and the noise are learned")
+        if likelihood != "gaussian":
+            raise NotImplementedError(f"SVGP: likelihood {likelihood!r} is not supported: only 'gaussian' is "
+                                      "(Bernoulli and Student-t need a quadrature epilogue)")
+        z = x_induce.detach()
+        self.x_induce = (z if z.dim() == 2 else z[:, None]).to(torch.float64)
+        self.m = self.x_induce.shape[0]
+        if not 1 <= self.m <= SVGP_M_MAX:
+            raise ValueError(f"SVGP: {self.m} inducing points are not supported: 1 to {SVGP_M_MAX} are")
+        self.kernel, self.jitter, self.likelihood = kernel, float(jitter), likelihood
+        rho = 0.0
+        if noise is not None:
+            if not float(noise) > NOISE_LOWER_BOUND:
+                raise ValueError(f"SVGP: the noise must exceed {NOISE_LOWER_BOUND}")
+            rho = float(_inverse_softplus(torch.tensor(float(noise) - NOISE_LOWER_BOUND, dtype=torch.float64)))
+        mean = torch.zeros(self.m, dtype=torch.float64)
+        if mean_init_std:
+            mean = float(mean_init_std) * torch.randn(self.m, dtype=torch.float64)
+        self._start = (mean, float(mean_constant), rho)
+        self._dev: dict = {}
+        self.n = 0
+
+    # ---- setup ------------------------------------------------------------------------------------------------------
+    def _state(self) -> dict:
+        if not self._dev:
+            from .basis.base import alloc_matrix
+            from .kernel import _dev
+
+            mean, c, rho = self._start
+            z = _dev(self.x_induce)
+            kzz = self.kernel(z, z)
+            kzz.diagonal().add_(self.jitter)
+            ls = alloc_matrix(self.m, self.m, z.device)
+            ls.copy_(torch.eye(self.m, dtype=torch.float64))
+            self._dev = {"z": z, "factor": cholesky_factor(kzz), "mean": _dev(mean), "Ls": ls,
+                         "scalars": torch.tensor([c, rho], dtype=torch.float64, device=z.device),
+                         "out": torch.zeros(5, dtype=torch.float64, device=z.device), "ws": None}
+        return self._dev
+
+    def _whitened_rows(self, x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(At, q) of the points x: the rows of (L^-1 k(Z, x))^T with an even leading dimension, and
+        k(x_i, x_i) + jitter - |row i|^2"""
+        st = self._state()
+        a = st["factor"].forward_solve(self.kernel(st["z"], x))  # (M, t)
+        t = a.shape[1]
+        at = torch.zeros((t, (self.m + 1) & ~1), dtype=torch.float64, device=a.device)[:, : self.m]
+        at.copy_(a.T)
+        q = _kernel_diagonal(self.kernel, x) + self.jitter - a.square().sum(dim=0)
+        return at, q.contiguous()
+
+    def fit_data(self, x: torch.Tensor, y: torch.Tensor) -> "SVGP":
+        """The once-per-model setup: K_zz + jitter I = L L^T (retried with growing jitter as psd_safe_cholesky does;
+        NotPSDError after the last attempt), At = (L^-1 k(Z, X))^T and q on the device."""
+        from .kernel import _dev
+
+        st = self._state()
+        xd = _dev(x if x.dim() == 2 else x[:, None])
+        yd = _dev(y.reshape(-1))
+        assert xd.shape[0] == yd.shape[0] and xd.shape[0] > 0, "x (n, d) and y (n) must share n > 0"
+        self.n = xd.shape[0]
+        at, q = self._whitened_rows(xd)
+        desc = L.SvgpDesc()
+        desc.At, desc.ldat, desc.q, desc.y = at.data_ptr(), at.stride(0), q.data_ptr(), yd.data_ptr()
+        desc.n, desc.m, desc.likelihood = self.n, self.m, L.SVGP_GAUSSIAN
+        st.update(At=at, q=q, y=yd, desc=desc, ws=None)
+        return self
+
+    def _workspace(self, batch: int) -> torch.Tensor:
+        st = self._state()
+        nbytes = int(L.load().pls_svgp_workspace_bytes(self.n, self.m, batch))
+        if st["ws"] is None or st["ws"].numel() * 8 < nbytes:
+            st["ws"] = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=st["z"].device)
+        return st["ws"]
+
+    def _fitted(self) -> dict:
+        st = self._state()
+        if "desc" not in st:
+            raise RuntimeError("SVGP: call fit_data(x, y) first")
+        return st
+
+    # ---- parameters -------------------------------------------------------------------------------------------------
+    @property
+    def variational_mean(self) -> torch.Tensor:
+        """m (M), the device tensor itself"""
+        return self._state()["mean"]
+
+    @property
+    def chol_variational_covar(self) -> torch.Tensor:
+        """L_s (M, M) on the device; only its lower triangle and diagonal mean anything"""
+        return self._state()["Ls"]
+
+    @property
+    def scalars(self) -> torch.Tensor:
+        """the device pair (c, rho)"""
+        return self._state()["scalars"]
+
+    @property
+    def mean_constant(self) -> float:
+        return float(self._state()["scalars"][0])
+
+    @property
+    def noise(self) -> float:
+        rho = self._state()["scalars"][1].cpu()
+        return NOISE_LOWER_BOUND + float(torch.clamp(rho, min=0.0) + torch.log1p(torch.exp(-rho.abs())))
+
+    # ---- the ELBO ---------------------------------------------------------------------------------------------------
+    def evaluate_on_device(self, idx: torch.Tensor | None = None, gradients: bool = True
+                           ) -> Tuple[torch.Tensor, torch.Tensor | None, torch.Tensor | None]:
+        """One pls_svgp_elbo_grad call: (out (5, device): ELBO, d/dc, d/drho, (1/B) sum l_i, KL; d/dm (M); d/dL_s (M, M),
+        lower triangle, zeros above).  ``idx``: int64 indices of the minibatch, all rows in order when None."""
+        st = self._fitted()
+        if idx is not None:
+            idx = idx.to(device=st["z"].device, dtype=torch.int64).contiguous()
+            if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= self.n):
+                raise IndexError(f"SVGP: minibatch indices must lie in 0 .. {self.n - 1}")
+        b = self.n if idx is None else idx.numel()
+        ws = self._workspace(b)
+        gm = gl = None
+        if gradients:
+            gm = torch.empty(self.m, dtype=torch.float64, device=ws.device)
+            gl = torch.zeros((self.m, self.m), dtype=torch.float64, device=ws.device)
+        L.check(L.load().pls_svgp_elbo_grad(ctypes.byref(st["desc"]), st["mean"].data_ptr(), st["Ls"].data_ptr(), L.ld(st["Ls"]),
+                                            st["scalars"].data_ptr(), L.ptr(idx), b, st["out"].data_ptr(), L.ptr(gm), L.ptr(gl),
+                                            self.m, ws.data_ptr(), ws.numel() * 8, L.stream_ptr()), "pls_svgp_elbo_grad")
+        return st["out"], gm, gl
+
+    def elbo_and_grad(self, idx: torch.Tensor | None = None) -> Tuple[float, dict]:
+        """(ELBO of the minibatch, its gradients): ``variational_mean`` (M) and ``chol_variational_covar`` (M, M, lower
+        triangle) on the device, ``mean_constant`` and ``raw_noise`` as floats."""
+        out, gm, gl = self.evaluate_on_device(idx)
+        host = out.cpu()
+        return float(host[0]), {"variational_mean": gm, "chol_variational_covar": gl, "mean_constant": float(host[1]),
+                                "raw_noise": float(host[2])}
+
+    def sgd_epoch(self, perm: torch.Tensor, batch_size: int, learning_rate: float, train_mean: bool = True,
+                  train_noise: bool = True) -> torch.Tensor:
+        """One pls_svgp_sgd_epoch call over the device index list ``perm`` (n int64): every minibatch step on the device,
+        then the full-data loss of the updated state, returned as a 1-element device tensor."""
+        st = self._fitted()
+        perm = perm.to(device=st["z"].device, dtype=torch.int64).contiguous()
+        assert perm.numel() == self.n, "perm must list all n rows"
+        ws = self._workspace(min(int(batch_size), self.n))
+        loss = torch.empty(1, dtype=torch.float64, device=ws.device)
+        flags = (L.SVGP_TRAIN_MEAN if train_mean else 0) | (L.SVGP_TRAIN_NOISE if train_noise else 0)
+        L.check(L.load().pls_svgp_sgd_epoch(ctypes.byref(st["desc"]), st["mean"].data_ptr(), st["Ls"].data_ptr(), L.ld(st["Ls"]),
+                                            st["scalars"].data_ptr(), perm.data_ptr(), int(batch_size), float(learning_rate),
+                                            flags, loss.data_ptr(), ws.data_ptr(), ws.numel() * 8, L.stream_ptr()),
+                "pls_svgp_sgd_epoch")
+        return loss
+
+    # ---- prediction -------------------------------------------------------------------------------------------------
+    def predict(self, x_test: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """(mean, latent variance, observation variance) at x_test (t, d), float64 on the device: c + a* . m,
+        q* + |L_s^T a*|^2 and that plus the noise."""
+        from .kernel import _dev
+
+        st = self._state()
+        xt = _dev(x_test if x_test.dim() == 2 else x_test[:, None])
+        at, q = self._whitened_rows(xt)
+        t = xt.shape[0]
+        mean = torch.empty(t, dtype=torch.float64, device=xt.device)
+        var = torch.empty(t, dtype=torch.float64, device=xt.device)
+        L.check(L.load().pls_svgp_predict(st["mean"].data_ptr(), st["Ls"].data_ptr(), L.ld(st["Ls"]), st["scalars"].data_ptr(),
+                                          at.data_ptr(), at.stride(0), q.data_ptr(), t, self.m, mean.data_ptr(), var.data_ptr(),
+                                          L.stream_ptr()), "pls_svgp_predict")
+        return mean, var, var + self.noise
+
+
 #: gpytorch's DirichletClassificationLikelihood: the Dirichlet concentration of a class that was not observed
 ALPHA_EPSILON = 0.01
 
@@ -520,5 +728,5 @@ def exact_gp_runner(x: torch.Tensor, y: torch.Tensor, kernel, subsample_size: in
     return models
 
 
-__all__ = ["ExactGP", "DirichletExactGP", "dirichlet_targets", "softmax_normal_mean", "train_exact_gp", "construct_average_ard_kernel", "construct_average_gaussian_noise", "nearest_subsample",
+__all__ = ["ExactGP", "SVGP", "DirichletExactGP", "dirichlet_targets", "softmax_normal_mean", "train_exact_gp", "construct_average_ard_kernel", "construct_average_gaussian_noise", "nearest_subsample",
            "exact_gp_runner", "NotPSDError"]

@@ -255,3 +255,29 @@ def train_pls_runner(
     else:
         _run_one_by_one(pls, particles, runs, early_stopper_patience, seed, ledger, train_fn or train_pls)
     return ledger.result()
+
+
+def train_svgp_runner(x: torch.Tensor, y: torch.Tensor, x_induce: torch.Tensor, kernel, seed: int, number_of_epochs: int,
+                      batch_size: int, learning_rate_upper: float, learning_rate_lower: float,
+                      number_of_learning_rate_searches: int, early_stopper_patience: float,
+                      observation_noise: float | None = None, train_noise: bool = True):
+    """The learning-rate search of experiments/runners.py:449-542 with ``is_fixed=True``, without its files and plots:
+    ``number_of_learning_rate_searches`` log-spaced rates from the lower to the upper bound, ``set_seed(seed)`` before each
+    candidate, candidates that returned None skipped, the best by its LAST loss kept.  Returns (model, losses,
+    best_learning_rate); (None, None, None) when no candidate survived."""
+    import math
+
+    from .trainers import train_svgp
+
+    best_loss = float("inf")
+    model_out = losses_out = best_learning_rate = None
+    for learning_rate in np.logspace(math.log10(learning_rate_lower), math.log10(learning_rate_upper),
+                                     number_of_learning_rate_searches):
+        set_seed(seed)
+        model, losses = train_svgp(x, y, x_induce, kernel, seed, number_of_epochs, batch_size, float(learning_rate),
+                                   early_stopper_patience, likelihood_noise=observation_noise, train_noise=train_noise)
+        if model is None or not losses:
+            continue
+        if losses[-1] < best_loss:
+            best_loss, best_learning_rate, model_out, losses_out = losses[-1], float(learning_rate), model, losses
+    return model_out, losses_out, best_learning_rate

@@ -1,4 +1,4 @@
-"""Variance tempering (drop-in for src/temper/base.py:8-59 and src/temper/pls.py:8-52)."""
+"""Variance tempering (drop-in for src/temper/base.py:8-59, src/temper/pls.py:8-52 and src/temper/gp.py:11-40)."""
 from __future__ import annotations
 
 import torch
@@ -41,3 +41,26 @@ class TemperPLS:
 
     def __call__(self, x: torch.Tensor) -> torch.distributions.MultivariateNormal:
         return self.predict(x=x)
+
+
+class TemperGP:
+    """TemperPLS's scale for a GP baseline (temper/gp.py:11-40): scale = (2/N) sum_i (y_i - m(x_i))^2 / sigma_i^2 with
+    sigma_i^2 the OBSERVATION variance of ``gp.predict`` on the calibration set.  ``gp``: an ExactGP or an SVGP.
+    ``predict`` returns (mean, latent variance * scale, observation variance * scale), as ``gp.predict`` does."""
+
+    def __init__(self, gp, x_calibration: torch.Tensor, y_calibration: torch.Tensor):
+        from .gaussian_process import SVGP, ExactGP
+
+        if not isinstance(gp, (ExactGP, SVGP)):
+            raise TypeError(f"TemperGP: an ExactGP or an SVGP is expected, got {type(gp).__name__}")
+        self.gp = gp
+        mean, _, variance = gp.predict(x_calibration)
+        y = _dev(y_calibration.reshape(-1))
+        self.scale = 2 * torch.mean(torch.div(torch.square(y - mean), variance)).item()
+
+    def predict(self, x: torch.Tensor):
+        mean, latent, observation = self.gp.predict(x)
+        return mean, latent * self.scale, observation * self.scale
+
+    def __call__(self, x: torch.Tensor):
+        return self.predict(x)

@@ -366,3 +366,52 @@ def train_pls_captured(pls: PLS, particles: torch.Tensor, number_of_epochs: int,
                 energies.append(e)
             return particles, energies
     return particles, energies
+
+
+def epoch_batches(n: int, batch_size: int) -> List[torch.Tensor]:
+    """The index batches of one epoch of the reference's SVGP loader (experiments/trainers.py:112-113): a real
+    ``DataLoader(TensorDataset(arange(n)), batch_size, shuffle=True)`` is iterated, so torch's global generator is consumed
+    exactly as the reference's loader over (x, y) consumes it, and batch k lists the rows that loader would yield as its
+    batch k (the last one ragged)."""
+    from torch.utils.data import DataLoader, TensorDataset
+
+    loader = DataLoader(TensorDataset(torch.arange(n)), batch_size=batch_size, shuffle=True)
+    return [batch[0] for batch in loader]
+
+
+def train_svgp(x: torch.Tensor, y: torch.Tensor, x_induce: torch.Tensor, kernel, seed: int, number_of_epochs: int,
+               batch_size: int, learning_rate: float, early_stopper_patience: float, likelihood_noise: float | None = None,
+               learn_inducing_locations: bool = False, learn_kernel_parameters: bool = False, train_noise: bool = True,
+               mean_init_std: float = 1e-3):
+    """experiments/trainers.py:55-136 with ``is_fixed=True`` (what every driver of the reference runs): seed, the model, and per
+    epoch every minibatch SGD step on loss = -ELBO followed by the full-data loss -- ONE library call (pls_svgp_sgd_epoch)
+    and one host read --, the early-stopper check before the loss is recorded.  Returns (model, losses); (None, None) when
+    a loss is not finite or k(Z, Z) stays non-PSD (the reference's ``except ValueError``).  ``train_noise=False`` freezes
+    the likelihood noise (train_svgp_for_profiler, experiments/profiler/main.py:106-107)."""
+    from ._chol import NotPSDError
+    from .gaussian_process import SVGP
+    from .utils import set_seed
+
+    if learn_kernel_parameters:
+        raise NotImplementedError("train_svgp: learn_kernel_parameters=True is not supported: the kernel and the inducing "
+                                  "points are fixed (the reference's is_fixed=True)")
+    set_seed(seed)
+    model = SVGP(kernel, x_induce, noise=likelihood_noise, learn_inducing_locations=learn_inducing_locations,
+                 mean_init_std=mean_init_std)
+    try:
+        model.fit_data(x, y)
+    except NotPSDError as e:
+        print(e)
+        return None, None
+    early_stopper = EarlyStopper(patience=early_stopper_patience)
+    losses: List[float] = []
+    for _ in range(number_of_epochs):
+        perm = torch.cat(epoch_batches(model.n, batch_size))
+        loss = model.sgd_epoch(perm, batch_size, learning_rate, train_mean=True, train_noise=train_noise).item()
+        if not np.isfinite(loss):
+            print(f"train_svgp: the loss is {loss}")
+            return None, None
+        if early_stopper.should_stop(loss=loss, step_size=learning_rate):
+            break
+        losses.append(loss)
+    return model, losses
