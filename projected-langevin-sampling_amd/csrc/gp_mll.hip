@@ -261,6 +261,27 @@ static bool stationary_kind(int32_t kind) {
   return kind == PLS_KERNEL_RBF_ARD || kind == PLS_KERNEL_MATERN12 || kind == PLS_KERNEL_MATERN32 || kind == PLS_KERNEL_MATERN52;
 }
 
+// What pls_kernel_grad_sums, pls_gp_mll_grad and pls_gp_mll_grad_classes check alike, each under its own name `who`: the
+// kernel kind, the sizes (classes == NULL: the entry has no class axis), the grid limit of the reduction and the
+// workspace of `need` bytes on an `align`-byte boundary.  The entry's own checks follow it.
+static int gp_check_shared(const char *who, int32_t kernel_kind, int64_t n, int64_t d, const int64_t *classes,
+                           const void *workspace, size_t workspace_bytes, size_t need, int align) {
+  PLS_REQUIRE(kernel_kind != PLS_KERNEL_LINEAR, "%s: the linear kernel has no lengthscale or outputscale to learn", who);
+  PLS_REQUIRE(stationary_kind(kernel_kind), "%s: unknown kernel kind %d", who, kernel_kind);
+  if (classes)
+    PLS_REQUIRE(n > 0 && d > 0 && *classes > 0, "%s: bad sizes n=%lld d=%lld classes=%lld", who, (long long)n, (long long)d,
+                (long long)*classes);
+  PLS_REQUIRE(n > 0 && d > 0, "%s: bad sizes n=%lld d=%lld", who, (long long)n, (long long)d);
+  PLS_REQUIRE(d <= GRAD_D_MAX, "%s: input dimension %lld > 64 is not supported", who, (long long)d);
+  PLS_REQUIRE(cdiv(n, GRAD_ROWS) <= 65535, "%s: n=%lld too large", who, (long long)n);
+  PLS_REQUIRE(workspace, "%s: NULL workspace", who);
+  if (workspace_bytes < need)
+    return fail(PLS_ERR_WORKSPACE_TOO_SMALL, "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, need);
+  PLS_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & (uintptr_t)(align - 1)) == 0, "%s: workspace must be %d-byte aligned", who,
+              align);
+  return PLS_OK;
+}
+
 // out = in + diag(fixed + shift)  (m x m): the vector form of scale_add_diag_kernel (chol.hip), for a noise that differs
 // from point to point
 __global__ __launch_bounds__(256) void add_diag_vector_kernel(const double *__restrict__ in, int64_t ldi,
@@ -318,6 +339,20 @@ static int gp_mll_evaluate(int32_t kernel_kind, const double *x, int64_t n, int6
   // 6. value and derivatives
   hipLaunchKernelGGL(gp_mll_finish_kernel, dim3(1), dim3(256), 0, st, n, (int)d, outputscale, r, al, Lc, p.ld, Ky, p.ld, sums, out);
   return check_launch("gp_mll_finish");
+}
+
+// The C >= 1 evaluations of both pls_gp_mll_grad entries, one after another in the shared workspace w (arguments already
+// validated); fixed == NULL: no fixed noise
+static int gp_mll_evaluate_classes(int32_t kernel_kind, const double *x, int64_t n, int64_t d, int64_t classes,
+                                   const double *lengthscale, const double *outputscale, const double *noise, const double *mean,
+                                   const double *fixed, int64_t ldf, const double *y, int64_t ldy, double jitter, double *out,
+                                   int32_t *info, double *w, void *stream) {
+  for (int64_t c = 0; c < classes; ++c) {
+    const int rc = gp_mll_evaluate(kernel_kind, x, n, d, lengthscale + c * d, outputscale[c], noise[c], mean[c], jitter,
+                                   fixed ? fixed + c * ldf : nullptr, y + c * ldy, out + c * (4 + d), info + c, w, stream);
+    if (rc) return rc;
+  }
+  return PLS_OK;
 }
 
 // Class probabilities of a Dirichlet GP: out[i][c] = (1/S) sum_s softmax_c(mu[.][i] + sqrt(max(var[.][i], 0)) z[s][.]) with
@@ -423,18 +458,11 @@ size_t pls_kernel_grad_sums_workspace_bytes(int64_t n, int64_t d) {
 int pls_kernel_grad_sums(int32_t kernel_kind, const double *x, int64_t n, int64_t d, const double *lengthscale,
                          double outputscale, const double *alpha, const double *P, int64_t ldp, double *out, void *workspace,
                          size_t workspace_bytes, void *stream) {
-  PLS_REQUIRE(kernel_kind != PLS_KERNEL_LINEAR, "kernel_grad_sums: the linear kernel has no lengthscale or outputscale to learn");
-  PLS_REQUIRE(stationary_kind(kernel_kind), "kernel_grad_sums: unknown kernel kind %d", kernel_kind);
-  PLS_REQUIRE(n > 0 && d > 0, "kernel_grad_sums: bad sizes n=%lld d=%lld", (long long)n, (long long)d);
-  PLS_REQUIRE(d <= GRAD_D_MAX, "kernel_grad_sums: input dimension %lld > 64 is not supported", (long long)d);
-  PLS_REQUIRE(cdiv(n, GRAD_ROWS) <= 65535, "kernel_grad_sums: n=%lld too large", (long long)n);
+  if (int rc = gp_check_shared("kernel_grad_sums", kernel_kind, n, d, nullptr, workspace, workspace_bytes,
+                               pls_kernel_grad_sums_workspace_bytes(n, d), 8))
+    return rc;
   PLS_REQUIRE(x && lengthscale && alpha && P && out, "kernel_grad_sums: NULL pointer");
   PLS_REQUIRE(ldp >= n, "kernel_grad_sums: ldp < n");
-  PLS_REQUIRE(workspace, "kernel_grad_sums: NULL workspace");
-  if (workspace_bytes < pls_kernel_grad_sums_workspace_bytes(n, d))
-    return fail(PLS_ERR_WORKSPACE_TOO_SMALL, "kernel_grad_sums: workspace of %zu bytes, %zu needed", workspace_bytes,
-                pls_kernel_grad_sums_workspace_bytes(n, d));
-  PLS_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, "kernel_grad_sums: workspace must be 8-byte aligned");
   return grad_sums_launch(kernel_kind, x, n, (int)d, lengthscale, outputscale, alpha, P, ldp, out,
                           static_cast<double *>(workspace), S(stream));
 }
@@ -443,24 +471,18 @@ size_t pls_gp_mll_workspace_bytes(int64_t n, int64_t d) {
   return (n > 0 && d > 0 && d <= GRAD_D_MAX) ? (size_t)gp_mll_plan(n, d).total * sizeof(double) : 0;
 }
 
+// pls_gp_mll_grad_classes with one class and no fixed noise: the scalars go in as arrays of one
 int pls_gp_mll_grad(int32_t kernel_kind, const double *x, int64_t n, int64_t d, const double *lengthscale, double outputscale,
                     double noise, double mean, double jitter, const double *y, double *out, int32_t *info, void *workspace,
                     size_t workspace_bytes, void *stream) {
-  PLS_REQUIRE(kernel_kind != PLS_KERNEL_LINEAR, "gp_mll_grad: the linear kernel has no lengthscale or outputscale to learn");
-  PLS_REQUIRE(stationary_kind(kernel_kind), "gp_mll_grad: unknown kernel kind %d", kernel_kind);
-  PLS_REQUIRE(n > 0 && d > 0, "gp_mll_grad: bad sizes n=%lld d=%lld", (long long)n, (long long)d);
-  PLS_REQUIRE(d <= GRAD_D_MAX, "gp_mll_grad: input dimension %lld > 64 is not supported", (long long)d);
-  PLS_REQUIRE(cdiv(n, GRAD_ROWS) <= 65535, "gp_mll_grad: n=%lld too large", (long long)n);
+  if (int rc = gp_check_shared("gp_mll_grad", kernel_kind, n, d, nullptr, workspace, workspace_bytes,
+                               pls_gp_mll_workspace_bytes(n, d), 16))
+    return rc;
   PLS_REQUIRE(x && lengthscale && y && out && info, "gp_mll_grad: NULL pointer");
-  PLS_REQUIRE(noise >= 0.0, "gp_mll_grad: noise must be >= 0");
   PLS_REQUIRE(jitter >= 0.0, "gp_mll_grad: jitter must be >= 0");
-  PLS_REQUIRE(workspace, "gp_mll_grad: NULL workspace");
-  if (workspace_bytes < pls_gp_mll_workspace_bytes(n, d))
-    return fail(PLS_ERR_WORKSPACE_TOO_SMALL, "gp_mll_grad: workspace of %zu bytes, %zu needed", workspace_bytes,
-                pls_gp_mll_workspace_bytes(n, d));
-  PLS_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "gp_mll_grad: workspace must be 16-byte aligned");
-  return gp_mll_evaluate(kernel_kind, x, n, d, lengthscale, outputscale, noise, mean, jitter, nullptr, y, out, info,
-                         static_cast<double *>(workspace), stream);
+  PLS_REQUIRE(noise >= 0.0, "gp_mll_grad: noise must be >= 0");
+  return gp_mll_evaluate_classes(kernel_kind, x, n, d, 1, lengthscale, &outputscale, &noise, &mean, nullptr, n, y, n, jitter, out,
+                                 info, static_cast<double *>(workspace), stream);
 }
 
 size_t pls_gp_mll_classes_workspace_bytes(int64_t n, int64_t d, int64_t classes) {
@@ -471,30 +493,17 @@ int pls_gp_mll_grad_classes(int32_t kernel_kind, const double *x, int64_t n, int
                             const double *lengthscale, const double *outputscale, const double *noise, const double *mean,
                             const double *fixed_noise, int64_t ldf, const double *y, int64_t ldy, double jitter, double *out,
                             int32_t *info, void *workspace, size_t workspace_bytes, void *stream) {
-  PLS_REQUIRE(kernel_kind != PLS_KERNEL_LINEAR, "gp_mll_grad_classes: the linear kernel has no lengthscale or outputscale to learn");
-  PLS_REQUIRE(stationary_kind(kernel_kind), "gp_mll_grad_classes: unknown kernel kind %d", kernel_kind);
-  PLS_REQUIRE(n > 0 && d > 0 && classes > 0, "gp_mll_grad_classes: bad sizes n=%lld d=%lld classes=%lld", (long long)n,
-              (long long)d, (long long)classes);
-  PLS_REQUIRE(d <= GRAD_D_MAX, "gp_mll_grad_classes: input dimension %lld > 64 is not supported", (long long)d);
-  PLS_REQUIRE(cdiv(n, GRAD_ROWS) <= 65535, "gp_mll_grad_classes: n=%lld too large", (long long)n);
+  if (int rc = gp_check_shared("gp_mll_grad_classes", kernel_kind, n, d, &classes, workspace, workspace_bytes,
+                               pls_gp_mll_classes_workspace_bytes(n, d, classes), 16))
+    return rc;
   PLS_REQUIRE(x && lengthscale && outputscale && noise && mean && y && out && info, "gp_mll_grad_classes: NULL pointer");
   PLS_REQUIRE(ldy >= n, "gp_mll_grad_classes: ldy < n");
   PLS_REQUIRE(!fixed_noise || ldf >= n, "gp_mll_grad_classes: ldf < n");
   PLS_REQUIRE(jitter >= 0.0, "gp_mll_grad_classes: jitter must be >= 0");
-  PLS_REQUIRE(workspace, "gp_mll_grad_classes: NULL workspace");
-  if (workspace_bytes < pls_gp_mll_classes_workspace_bytes(n, d, classes))
-    return fail(PLS_ERR_WORKSPACE_TOO_SMALL, "gp_mll_grad_classes: workspace of %zu bytes, %zu needed", workspace_bytes,
-                pls_gp_mll_classes_workspace_bytes(n, d, classes));
-  PLS_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "gp_mll_grad_classes: workspace must be 16-byte aligned");
   for (int64_t c = 0; c < classes; ++c)  // (host arrays: read only after the pointer checks)
     PLS_REQUIRE(noise[c] >= 0.0, "gp_mll_grad_classes: noise must be >= 0 (class %lld)", (long long)c);
-  for (int64_t c = 0; c < classes; ++c) {
-    const int rc = gp_mll_evaluate(kernel_kind, x, n, d, lengthscale + c * d, outputscale[c], noise[c], mean[c], jitter,
-                                   fixed_noise ? fixed_noise + c * ldf : nullptr, y + c * ldy, out + c * (4 + d), info + c,
-                                   static_cast<double *>(workspace), stream);
-    if (rc) return rc;
-  }
-  return PLS_OK;
+  return gp_mll_evaluate_classes(kernel_kind, x, n, d, classes, lengthscale, outputscale, noise, mean, fixed_noise, ldf, y, ldy,
+                                 jitter, out, info, static_cast<double *>(workspace), stream);
 }
 
 int pls_softmax_normal_mean(const double *mu, int64_t ldmu, const double *var, int64_t ldvar, int64_t classes, int64_t t,

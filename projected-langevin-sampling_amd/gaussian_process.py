@@ -5,10 +5,10 @@ Replaces ``src/gaussian_process/exact_gp.py`` as it is used by ``train_exact_gp`
 ``exact_gp_runner`` / ``load_subsample_data`` (experiments/runners.py:66-187) and the two averaging constructors
 (experiments/constructors.py:9-53).  The reference builds these on gpytorch (ConstantMean, ScaleKernel(RBFKernel |
 MaternKernel), GaussianLikelihood, ExactMarginalLogLikelihood); here the model is a plain parameter holder and one
-evaluation of the marginal log-likelihood with its gradient is ONE library call, ``pls_gp_mll_grad`` (csrc/gp_mll.hip).
-One output with a Gaussian likelihood (``ExactGP``), or classification with the Dirichlet likelihood of Milios et al. 2018 as
-the reference's two classification drivers use it (``DirichletExactGP``: one GP per class, ``pls_gp_mll_grad_classes``);
-no gpytorch objects anywhere."""
+evaluation of the marginal log-likelihood with its gradient is ONE library call, ``pls_gp_mll_grad_classes``
+(csrc/gp_mll.hip).  One output with a Gaussian likelihood (``ExactGP``: one class, no fixed noise), or classification with the
+Dirichlet likelihood of Milios et al. 2018 as the reference's two classification drivers use it (``DirichletExactGP``: one
+GP per class); both are one private base class; no gpytorch objects anywhere."""
 from __future__ import annotations
 
 import ctypes
@@ -20,7 +20,7 @@ import torch
 
 from . import _lib as L
 from ._chol import CHOLESKY_JITTER, CHOLESKY_MAX_TRIES, NotPSDError, cholesky_factor
-from .kernel import ARDKernel, BaseKernel, MaternKernel
+from .kernel import ARDKernel, BaseKernel, MaternKernel, _dev
 from .trainers import EarlyStopper
 from .utils import set_seed
 
@@ -59,10 +59,164 @@ def _kernel_choice(who: str, kernel, nu: float, ard: bool, d: int):
     return name, (float(nu) if name == "matern" else None), bool(ard), start
 
 
-class ExactGP:
-    """Exact GP regression with a constant mean, a scaled stationary kernel and Gaussian noise, parametrised as gpytorch
-    does: ``lengthscale = softplus(raw)``, ``outputscale = softplus(raw)``, ``noise = 1e-4 + softplus(raw)``, the mean
-    constant itself; every raw value starts at 0.
+class _ExactGPClasses:
+    """What ExactGP and DirichletExactGP share: C independent exact GPs on the shared x, class c with a constant mean m_c,
+    K_c = s_c kappa(x, x; l_c) and K_y,c = K_c + diag(v_c) + sigma_c I, parametrised as gpytorch does: ``lengthscale =
+    softplus(raw)``, ``outputscale = softplus(raw)``, ``noise = 1e-4 + softplus(raw)``, the mean constant itself; every raw
+    value starts at 0.  ``raw`` is seen as (C, 3 + nls) rows: mean, raw noise, raw outputscale, raw lengthscales (d of
+    them, or one shared by all dimensions).  x (n, d), the targets (C, n) and the fixed noise v (C, n), or None, are kept
+    as given and uploaded once, on the first evaluation on the device.  One evaluation of all classes is ONE library call
+    with one read-back, ``pls_gp_mll_grad_classes``."""
+
+    def __init__(self, who: str, x: torch.Tensor, targets: torch.Tensor, fixed_noise: torch.Tensor | None, kernel, nu: float,
+                 ard: bool):
+        x = x.detach()
+        self.x = (x if x.dim() == 2 else x[:, None]).to(torch.float64)
+        self.n, self.d = self.x.shape
+        self._targets, self.fixed_noise = targets, fixed_noise
+        name, nu, ard, start = _kernel_choice(who, kernel, nu, ard, self.d)
+        self.kernel_name, self.ard, self.nu = name, ard, nu
+        self.kind = MaternKernel.KINDS[self.nu] if name == "matern" else L.KERNEL_RBF_ARD
+        nls = self.d if self.ard else 1
+        raw = torch.zeros(targets.shape[0], 3 + nls, dtype=torch.float64)
+        if start is not None:
+            assert start.lengthscale.numel() in (1, nls), "the kernel's lengthscales do not fit the data"
+            raw[:, 2] = _inverse_softplus(torch.tensor(start.outputscale, dtype=torch.float64))
+            raw[:, 3:] = _inverse_softplus(start.lengthscale.expand(nls) if start.lengthscale.numel() == 1 else start.lengthscale)
+        self.raw = torch.nn.Parameter(raw)
+        self._dev: dict = {}
+
+    # ---- parameters -------------------------------------------------------------------------------------------------
+    def raw_parameters(self) -> torch.Tensor:
+        """A copy of ``raw`` (float64, CPU; the order is in the class docstring)."""
+        return self.raw.detach().clone()
+
+    def set_raw_parameters(self, raw: torch.Tensor):
+        raw = torch.as_tensor(raw, dtype=torch.float64)
+        assert raw.shape == self.raw.shape, f"raw parameters of shape {tuple(self.raw.shape)} expected, got {tuple(raw.shape)}"
+        with torch.no_grad():
+            self.raw.copy_(raw)
+        return self
+
+    def _natural(self) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+        """(mean constant (C), noise (C), outputscale (C), lengthscale (C, d): a shared one repeated)"""
+        raw = self.raw.detach().reshape(self._targets.shape[0], -1)
+        ls = _softplus(raw[:, 3:])
+        ls = ls.expand(-1, self.d).clone() if ls.shape[1] == 1 and self.d > 1 else ls
+        return raw[:, 0].clone(), NOISE_LOWER_BOUND + _softplus(raw[:, 1]), _softplus(raw[:, 2]), ls
+
+    @property
+    def mean_constant(self) -> torch.Tensor:
+        return self._natural()[0]
+
+    @property
+    def noise(self) -> torch.Tensor:
+        """(C) the learned noise sigma_c"""
+        return self._natural()[1]
+
+    @property
+    def outputscale(self) -> torch.Tensor:
+        return self._natural()[2]
+
+    @property
+    def lengthscale(self) -> torch.Tensor:
+        """(C, d) lengthscales (a shared one repeated)."""
+        return self._natural()[3]
+
+    def _make_kernel(self, lengthscale: torch.Tensor, outputscale: float) -> BaseKernel:
+        if self.kernel_name == "matern":
+            return MaternKernel(lengthscale, outputscale, nu=self.nu)
+        return ARDKernel(lengthscale, outputscale)
+
+    # ---- the loss ---------------------------------------------------------------------------------------------------
+    def chain_rule(self, out: torch.Tensor) -> Tuple[float, torch.Tensor]:
+        """(-sum_c mll_c / n, its gradient with respect to ``raw``, in the shape of ``raw``) from the (C, 4 + d) outputs of
+        pls_gp_mll_grad_classes (per class: value, d/d mean, d/d noise, d/d log outputscale, d/d log lengthscale_k) at the
+        current parameters: host arithmetic only."""
+        raw = self.raw.detach().reshape(self._targets.shape[0], -1)
+        out = torch.as_tensor(out, dtype=torch.float64)
+        assert out.numel() == raw.shape[0] * (4 + self.d)
+        out = out.reshape(raw.shape[0], 4 + self.d)
+        slope = torch.sigmoid(raw)  # d softplus(raw) / d raw
+        g = torch.empty_like(raw)
+        g[:, 0] = out[:, 1]
+        g[:, 1] = out[:, 2] * slope[:, 1]
+        g[:, 2] = out[:, 3] / _softplus(raw[:, 2]) * slope[:, 2]
+        per_dim = out[:, 4:] / self._natural()[3]
+        g[:, 3:] = (per_dim if self.ard else per_dim.sum(dim=1, keepdim=True)) * slope[:, 3:]
+        return -float(out[:, 0].sum()) / self.n, (-g / self.n).reshape(self.raw.shape)
+
+    def _device_state(self) -> dict:
+        if not self._dev:
+            x = _dev(self.x)
+            c, width = self._targets.shape[0], 4 + self.d
+            nbytes = int(L.load().pls_gp_mll_classes_workspace_bytes(self.n, self.d, c))
+            self._dev = {
+                "x": x, "y": _dev(self._targets.contiguous()),
+                "fixed": _dev(self.fixed_noise.contiguous()) if self.fixed_noise is not None else None,
+                "ws": torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=x.device),
+                # the C (4 + d) outputs and behind them the C int32 info words: one read-back per evaluation
+                "out": torch.zeros(c * width + (c + 1) // 2, dtype=torch.float64, device=x.device),
+            }
+        return self._dev
+
+    def _evaluate(self, jitter: float) -> Tuple[torch.Tensor, torch.Tensor]:
+        """One pls_gp_mll_grad_classes call at the current parameters: (the (C, 4 + d) outputs on the CPU, info (C))."""
+        st = self._device_state()
+        c, width = self._targets.shape[0], 4 + self.d
+        mean, noise, s, ls = self._natural()
+        ls = st["x"].new_tensor(ls.tolist()).contiguous()
+        host = (ctypes.c_double * c)
+        s, noise, mean = host(*s.tolist()), host(*noise.tolist()), host(*mean.tolist())
+        out, ws, fixed = st["out"], st["ws"], st["fixed"]
+        L.check(
+            L.load().pls_gp_mll_grad_classes(self.kind, st["x"].data_ptr(), self.n, self.d, c, ls.data_ptr(),
+                                             ctypes.cast(s, ctypes.c_void_p), ctypes.cast(noise, ctypes.c_void_p),
+                                             ctypes.cast(mean, ctypes.c_void_p), fixed.data_ptr() if fixed is not None else None,
+                                             self.n, st["y"].data_ptr(), self.n, float(jitter), out.data_ptr(),
+                                             out.data_ptr() + 8 * c * width, ws.data_ptr(), ws.numel() * 8, L.stream_ptr()),
+            "pls_gp_mll_grad_classes",
+        )
+        got = out.cpu()
+        return got[: c * width].reshape(c, width), got[c * width:].view(torch.int32)[:c].clone()
+
+    def loss_and_grad(self) -> Tuple[float, torch.Tensor]:
+        """(-sum_c mll_c / n, its gradient with respect to ``raw``): gpytorch's ``-mll(model(x), y)``, summed over the
+        classes, and ``backward()``.  When ANY class meets a non-positive pivot the whole call is retried with
+        psd_safe_cholesky's jitters (1e-8, 1e-7, 1e-6), a warning per attempt, NotPSDError after the last."""
+        attempts = [0.0] + [CHOLESKY_JITTER * 10**i for i in range(CHOLESKY_MAX_TRIES)]
+        for jit in attempts:
+            if jit > 0.0:
+                warnings.warn(f"A not p.d., added jitter of {jit:.1e} to the diagonal", RuntimeWarning, stacklevel=2)
+            out, info = self._evaluate(jit)
+            if not info.any():
+                return self.chain_rule(out)
+        raise NotPSDError(f"Matrix not positive definite after repeatedly adding jitter up to {attempts[-1]:.1e}.")
+
+    # ---- prediction -------------------------------------------------------------------------------------------------
+    def _predict_class(self, c: int, x_test: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(latent mean, latent variance) of class c at x_test (t, d), float64 on the device: m_c + k*^T alpha_c and
+        k** - |Lc^-1 k*|^2 with K_y,c = Lc Lc^T and alpha_c = K_y,c^-1 (y_c - m_c)."""
+        st = self._device_state()
+        mean_c, noise, s, ls = (v[c] for v in self._natural())
+        mean_c, noise, s = float(mean_c), float(noise), float(s)
+        kern = self._make_kernel(ls, s)
+        ky = kern(st["x"], st["x"])
+        ky.diagonal().add_(st["fixed"][c] + noise if st["fixed"] is not None else noise)
+        factor = cholesky_factor(ky)
+        alpha = factor.solve((st["y"][c] - mean_c)[:, None].contiguous())
+        ks = kern(st["x"], x_test if x_test.dim() == 2 else x_test[:, None])  # (n, t): k-major
+        t = ks.shape[1]
+        mean = torch.empty((t, 1), dtype=torch.float64, device=ks.device)
+        L.check(L.load().pls_gemm_tn(ks.data_ptr(), L.ld(ks), alpha.data_ptr(), 1, mean.data_ptr(), 1, t, 1, self.n, 1.0, 0.0,
+                                     L.stream_ptr()), "pls_gemm_tn")
+        v = factor.forward_solve(ks)
+        return mean[:, 0] + mean_c, s - v.square().sum(dim=0)
+
+
+class ExactGP(_ExactGPClasses):
+    """Exact GP regression with a constant mean, a scaled stationary kernel and Gaussian noise: the one-class case of
+    _ExactGPClasses, without fixed noise.
 
     ``raw`` is ONE float64 CPU tensor, in this order::
 
@@ -73,139 +227,51 @@ class ExactGP:
 
     ``kernel``: "rbf" or "matern" (with ``nu``); "matern12" / "matern32" / "matern52" name nu as well; an ARDKernel /
     MaternKernel instance gives the kind and the starting values (as the reference's ``deepcopy(kernel)``).
-    x (n, d) and y (n) are kept as given and uploaded once, on the first evaluation on the device."""
+    x (n, d) and y (n) are kept as given."""
 
     def __init__(self, x: torch.Tensor, y: torch.Tensor, kernel="rbf", nu: float = 2.5, ard: bool = True):
-        x = x.detach()
-        self.x = (x if x.dim() == 2 else x[:, None]).to(torch.float64)
         self.y = y.detach().reshape(-1).to(torch.float64)
-        assert self.x.shape[0] == self.y.shape[0] and self.x.shape[0] > 0, "x (n, d) and y (n) must share n > 0"
-        self.n, self.d = self.x.shape
-        name, nu, ard, start = _kernel_choice("ExactGP", kernel, nu, ard, self.d)
-        self.kernel_name, self.ard, self.nu = name, ard, nu
-        self.kind = MaternKernel.KINDS[self.nu] if name == "matern" else L.KERNEL_RBF_ARD
-        nls = self.d if self.ard else 1
-        raw = torch.zeros(3 + nls, dtype=torch.float64)
-        if start is not None:
-            assert start.lengthscale.numel() in (1, nls), "the kernel's lengthscales do not fit the data"
-            raw[2] = _inverse_softplus(torch.tensor(start.outputscale, dtype=torch.float64))
-            raw[3:] = _inverse_softplus(start.lengthscale.expand(nls) if start.lengthscale.numel() == 1 else start.lengthscale)
-        self.raw = torch.nn.Parameter(raw)
-        self._dev: dict = {}
-
-    # ---- parameters -------------------------------------------------------------------------------------------------
-    def raw_parameters(self) -> torch.Tensor:
-        """A copy of ``raw`` (float64, CPU; the order is in the class docstring)."""
-        return self.raw.detach().clone()
+        assert x.shape[0] == self.y.shape[0] and x.shape[0] > 0, "x (n, d) and y (n) must share n > 0"
+        super().__init__("ExactGP", x, self.y[None, :], None, kernel, nu, ard)
+        self.raw = torch.nn.Parameter(self.raw.detach()[0].clone())
 
     def set_raw_parameters(self, raw: torch.Tensor) -> "ExactGP":
         raw = torch.as_tensor(raw, dtype=torch.float64).reshape(-1)
         assert raw.numel() == self.raw.numel(), f"{self.raw.numel()} raw parameters expected, got {raw.numel()}"
-        with torch.no_grad():
-            self.raw.copy_(raw)
-        return self
+        return super().set_raw_parameters(raw)
 
     @property
     def mean_constant(self) -> float:
-        return float(self.raw.detach()[0])
+        return float(self._natural()[0][0])
 
     @property
     def noise(self) -> float:
-        return NOISE_LOWER_BOUND + float(_softplus(self.raw.detach()[1]))
+        return float(self._natural()[1][0])
 
     @property
     def outputscale(self) -> float:
-        return float(_softplus(self.raw.detach()[2]))
+        return float(self._natural()[2][0])
 
     @property
     def lengthscale(self) -> torch.Tensor:
         """d lengthscales (a shared one repeated)."""
-        ls = _softplus(self.raw.detach()[3:])
-        return ls.expand(self.d).clone() if ls.numel() == 1 and self.d > 1 else ls
+        return self._natural()[3][0]
 
     @property
     def kernel(self) -> BaseKernel:
         """The fitted base kernel: goes straight into PLSKernel and the inducing-point selectors."""
-        if self.kernel_name == "matern":
-            return MaternKernel(self.lengthscale, self.outputscale, nu=self.nu)
-        return ARDKernel(self.lengthscale, self.outputscale)
-
-    # ---- the loss ---------------------------------------------------------------------------------------------------
-    def chain_rule(self, out: torch.Tensor) -> Tuple[float, torch.Tensor]:
-        """(-mll / n, d(-mll / n) / d raw) from the 4 + d outputs of pls_gp_mll_grad (value, d/d mean, d/d noise,
-        d/d log outputscale, d/d log lengthscale_k) at the current parameters: host arithmetic only."""
-        out = torch.as_tensor(out, dtype=torch.float64).reshape(-1)
-        assert out.numel() == 4 + self.d
-        raw = self.raw.detach()
-        slope = torch.sigmoid(raw)  # d softplus(raw) / d raw
-        g = torch.empty_like(raw)
-        g[0] = out[1]
-        g[1] = out[2] * slope[1]
-        g[2] = out[3] / _softplus(raw[2]) * slope[2]
-        per_dim = out[4:] / self.lengthscale
-        g[3:] = (per_dim if self.ard else per_dim.sum().reshape(1)) * slope[3:]
-        return -float(out[0]) / self.n, -g / self.n
-
-    def _device_state(self) -> dict:
-        if not self._dev:
-            from .kernel import _dev
-
-            lib = L.load()
-            x, y = _dev(self.x), _dev(self.y)
-            nbytes = int(lib.pls_gp_mll_workspace_bytes(self.n, self.d))
-            self._dev = {
-                "x": x, "y": y,
-                "ws": torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=x.device),
-                # the 4 + d outputs and, in the last slot, the int32 info word: one read-back per evaluation
-                "out": torch.zeros(4 + self.d + 1, dtype=torch.float64, device=x.device),
-            }
-        return self._dev
+        return self._make_kernel(self.lengthscale, self.outputscale)
 
     def evaluate_on_device(self, jitter: float = 0.0) -> Tuple[torch.Tensor, int]:
-        """One pls_gp_mll_grad call at the current parameters: (the 4 + d outputs on the CPU, info)."""
-        st = self._device_state()
-        ls = st["x"].new_tensor(self.lengthscale.tolist())
-        out, ws = st["out"], st["ws"]
-        L.check(
-            L.load().pls_gp_mll_grad(self.kind, st["x"].data_ptr(), self.n, self.d, ls.data_ptr(), self.outputscale, self.noise,
-                                     self.mean_constant, float(jitter), st["y"].data_ptr(), out.data_ptr(),
-                                     out.data_ptr() + 8 * (4 + self.d), ws.data_ptr(), ws.numel() * 8, L.stream_ptr()),
-            "pls_gp_mll_grad",
-        )
-        host = out.cpu()
-        return host[: 4 + self.d], int(host[4 + self.d:].view(torch.int32)[0])
+        """One pls_gp_mll_grad_classes call (one class) at the current parameters: (the 4 + d outputs on the CPU, info)."""
+        out, info = self._evaluate(jitter)
+        return out[0], int(info[0])
 
-    def loss_and_grad(self) -> Tuple[float, torch.Tensor]:
-        """(-mll / n, its gradient with respect to ``raw``): gpytorch's ``-mll(model(x), y)`` and ``backward()``.  A
-        factorisation that meets a non-positive pivot is retried with psd_safe_cholesky's jitters (1e-8, 1e-7, 1e-6), a
-        warning per attempt, NotPSDError after the last."""
-        attempts = [0.0] + [CHOLESKY_JITTER * 10**i for i in range(CHOLESKY_MAX_TRIES)]
-        for jit in attempts:
-            if jit > 0.0:
-                warnings.warn(f"A not p.d., added jitter of {jit:.1e} to the diagonal", RuntimeWarning, stacklevel=2)
-            out, info = self.evaluate_on_device(jit)
-            if info == 0:
-                return self.chain_rule(out)
-        raise NotPSDError(f"Matrix not positive definite after repeatedly adding jitter up to {attempts[-1]:.1e}.")
-
-    # ---- prediction -------------------------------------------------------------------------------------------------
     def predict(self, x_test: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """(mean, latent variance, observation variance) at x_test (t, d), float64 on the device:
         c + k*^T alpha,  k** - |Lc^-1 k*|^2  and that plus the noise, with K_y = Lc Lc^T and alpha = K_y^-1 (y - c)."""
-        st = self._device_state()
-        kern = self.kernel
-        ky = kern(st["x"], st["x"])
-        ky.diagonal().add_(self.noise)
-        factor = cholesky_factor(ky)
-        alpha = factor.solve((st["y"] - self.mean_constant)[:, None])
-        ks = kern(st["x"], x_test if x_test.dim() == 2 else x_test[:, None])  # (n, t): k-major
-        t = ks.shape[1]
-        mean = torch.empty((t, 1), dtype=torch.float64, device=ks.device)
-        L.check(L.load().pls_gemm_tn(ks.data_ptr(), L.ld(ks), alpha.data_ptr(), 1, mean.data_ptr(), 1, t, 1, self.n, 1.0, 0.0,
-                                     L.stream_ptr()), "pls_gemm_tn")
-        v = factor.forward_solve(ks)
-        var = self.outputscale - v.square().sum(dim=0)
-        return mean[:, 0] + self.mean_constant, var, var + self.noise
+        mean, var = self._predict_class(0, x_test)
+        return mean, var, var + self.noise
 
 
 # ---- sparse variational GP (fixed kernel, fixed inducing points, Gaussian likelihood) ------------------------------------
@@ -274,8 +340,6 @@ class SVGP:
     def _state(self) -> dict:
         if not self._dev:
             from .basis.base import alloc_matrix
-            from .kernel import _dev
-
             mean, c, rho = self._start
             z = _dev(self.x_induce)
             kzz = self.kernel(z, z)
@@ -301,8 +365,6 @@ class SVGP:
     def fit_data(self, x: torch.Tensor, y: torch.Tensor) -> "SVGP":
         """The once-per-model setup: K_zz + jitter I = L L^T (retried with growing jitter as psd_safe_cholesky does;
         NotPSDError after the last attempt), At = (L^-1 k(Z, X))^T and q on the device."""
-        from .kernel import _dev
-
         st = self._state()
         xd = _dev(x if x.dim() == 2 else x[:, None])
         yd = _dev(y.reshape(-1))
@@ -402,8 +464,6 @@ class SVGP:
     def predict(self, x_test: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """(mean, latent variance, observation variance) at x_test (t, d), float64 on the device: c + a* . m,
         q* + |L_s^T a*|^2 and that plus the noise."""
-        from .kernel import _dev
-
         st = self._state()
         xt = _dev(x_test if x_test.dim() == 2 else x_test[:, None])
         at, q = self._whitened_rows(xt)
@@ -445,7 +505,7 @@ def dirichlet_targets(labels: torch.Tensor, number_of_classes: int | None = None
     return targets.to(target_dtype).to(torch.float64), v.to(target_dtype).to(torch.float64)
 
 
-class DirichletExactGP:
+class DirichletExactGP(_ExactGPClasses):
     """Exact-GP classification with the Dirichlet likelihood: ``number_of_classes`` independent GPs on the shared x, class c
     with a constant mean m_c, K_c = s_c kappa(x, x; l_c) and K_y,c = K_c + diag(v_c) + sigma_c I, where v_c is the fixed
     per-point noise of ``dirichlet_targets`` and sigma_c = 1e-4 + softplus(raw) the learned "second noise"
@@ -461,61 +521,11 @@ class DirichletExactGP:
     def __init__(self, x: torch.Tensor, labels: torch.Tensor, kernel="rbf", nu: float = 2.5, ard: bool = True,
                  number_of_classes: int | None = None, alpha_epsilon: float = ALPHA_EPSILON,
                  target_dtype: torch.dtype = torch.float32, fixed_noise: bool = True):
-        x = x.detach()
-        self.x = (x if x.dim() == 2 else x[:, None]).to(torch.float64)
         self.labels = torch.as_tensor(labels).detach().reshape(-1).cpu().to(torch.int64)
-        assert self.x.shape[0] == self.labels.shape[0] and self.x.shape[0] > 0, "x (n, d) and labels (n) must share n > 0"
-        self.n, self.d = self.x.shape
+        assert x.shape[0] == self.labels.shape[0] and x.shape[0] > 0, "x (n, d) and labels (n) must share n > 0"
         self.transformed_targets, v = dirichlet_targets(labels, number_of_classes, alpha_epsilon, target_dtype)
-        self.fixed_noise = v if fixed_noise else None
         self.number_of_classes = self.transformed_targets.shape[0]
-        name, nu, ard, start = _kernel_choice("DirichletExactGP", kernel, nu, ard, self.d)
-        self.kernel_name, self.ard, self.nu = name, ard, nu
-        self.kind = MaternKernel.KINDS[self.nu] if name == "matern" else L.KERNEL_RBF_ARD
-        nls = self.d if self.ard else 1
-        raw = torch.zeros(self.number_of_classes, 3 + nls, dtype=torch.float64)
-        if start is not None:
-            assert start.lengthscale.numel() in (1, nls), "the kernel's lengthscales do not fit the data"
-            raw[:, 2] = _inverse_softplus(torch.tensor(start.outputscale, dtype=torch.float64))
-            raw[:, 3:] = _inverse_softplus(start.lengthscale.expand(nls) if start.lengthscale.numel() == 1 else start.lengthscale)
-        self.raw = torch.nn.Parameter(raw)
-        self._dev: dict = {}
-
-    # ---- parameters -------------------------------------------------------------------------------------------------
-    def raw_parameters(self) -> torch.Tensor:
-        """A copy of ``raw`` (C, 3 + nls; float64, CPU)."""
-        return self.raw.detach().clone()
-
-    def set_raw_parameters(self, raw: torch.Tensor) -> "DirichletExactGP":
-        raw = torch.as_tensor(raw, dtype=torch.float64)
-        assert raw.shape == self.raw.shape, f"raw parameters of shape {tuple(self.raw.shape)} expected, got {tuple(raw.shape)}"
-        with torch.no_grad():
-            self.raw.copy_(raw)
-        return self
-
-    @property
-    def mean_constant(self) -> torch.Tensor:
-        return self.raw.detach()[:, 0].clone()
-
-    @property
-    def noise(self) -> torch.Tensor:
-        """(C) the learned second noise sigma_c"""
-        return NOISE_LOWER_BOUND + _softplus(self.raw.detach()[:, 1])
-
-    @property
-    def outputscale(self) -> torch.Tensor:
-        return _softplus(self.raw.detach()[:, 2])
-
-    @property
-    def lengthscale(self) -> torch.Tensor:
-        """(C, d) lengthscales (a shared one repeated)."""
-        ls = _softplus(self.raw.detach()[:, 3:])
-        return ls.expand(self.number_of_classes, self.d).clone() if ls.shape[1] == 1 and self.d > 1 else ls
-
-    def _make_kernel(self, lengthscale: torch.Tensor, outputscale: float) -> BaseKernel:
-        if self.kernel_name == "matern":
-            return MaternKernel(lengthscale, outputscale, nu=self.nu)
-        return ARDKernel(lengthscale, outputscale)
+        super().__init__("DirichletExactGP", x, self.transformed_targets, v if fixed_noise else None, kernel, nu, ard)
 
     @property
     def kernels(self) -> List[BaseKernel]:
@@ -529,92 +539,15 @@ class DirichletExactGP:
         softplus applied afterwards (constructors.py:28-53 with one model)."""
         return construct_average_ard_kernel([self])
 
-    # ---- the loss ---------------------------------------------------------------------------------------------------
-    def chain_rule(self, out: torch.Tensor) -> Tuple[float, torch.Tensor]:
-        """(-sum_c mll_c / n, its gradient with respect to ``raw`` (C, 3 + nls)) from the (C, 4 + d) outputs of
-        pls_gp_mll_grad_classes at the current parameters: host arithmetic only."""
-        out = torch.as_tensor(out, dtype=torch.float64).reshape(self.number_of_classes, 4 + self.d)
-        raw = self.raw.detach()
-        slope = torch.sigmoid(raw)  # d softplus(raw) / d raw
-        g = torch.empty_like(raw)
-        g[:, 0] = out[:, 1]
-        g[:, 1] = out[:, 2] * slope[:, 1]
-        g[:, 2] = out[:, 3] / _softplus(raw[:, 2]) * slope[:, 2]
-        per_dim = out[:, 4:] / self.lengthscale
-        g[:, 3:] = (per_dim if self.ard else per_dim.sum(dim=1, keepdim=True)) * slope[:, 3:]
-        return -float(out[:, 0].sum()) / self.n, -g / self.n
-
-    def _device_state(self) -> dict:
-        if not self._dev:
-            from .kernel import _dev
-
-            lib = L.load()
-            x = _dev(self.x)
-            c, width = self.number_of_classes, 4 + self.d
-            nbytes = int(lib.pls_gp_mll_classes_workspace_bytes(self.n, self.d, c))
-            self._dev = {
-                "x": x, "y": _dev(self.transformed_targets.contiguous()),
-                "fixed": _dev(self.fixed_noise.contiguous()) if self.fixed_noise is not None else None,
-                "ws": torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=x.device),
-                # the C (4 + d) outputs and behind them the C int32 info words: one read-back per evaluation
-                "out": torch.zeros(c * width + (c + 1) // 2, dtype=torch.float64, device=x.device),
-            }
-        return self._dev
-
     def evaluate_on_device(self, jitter: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor]:
         """One pls_gp_mll_grad_classes call at the current parameters: (the (C, 4 + d) outputs on the CPU, info (C))."""
-        st = self._device_state()
-        c, width = self.number_of_classes, 4 + self.d
-        ls = st["x"].new_tensor(self.lengthscale.tolist()).contiguous()
-        host = (ctypes.c_double * c)
-        s, noise, mean = host(*self.outputscale.tolist()), host(*self.noise.tolist()), host(*self.mean_constant.tolist())
-        out, ws, fixed = st["out"], st["ws"], st["fixed"]
-        L.check(
-            L.load().pls_gp_mll_grad_classes(self.kind, st["x"].data_ptr(), self.n, self.d, c, ls.data_ptr(),
-                                             ctypes.cast(s, ctypes.c_void_p), ctypes.cast(noise, ctypes.c_void_p),
-                                             ctypes.cast(mean, ctypes.c_void_p), fixed.data_ptr() if fixed is not None else None,
-                                             self.n, st["y"].data_ptr(), self.n, float(jitter), out.data_ptr(),
-                                             out.data_ptr() + 8 * c * width, ws.data_ptr(), ws.numel() * 8, L.stream_ptr()),
-            "pls_gp_mll_grad_classes",
-        )
-        got = out.cpu()
-        return got[: c * width].reshape(c, width), got[c * width:].view(torch.int32)[:c].clone()
+        return self._evaluate(jitter)
 
-    def loss_and_grad(self) -> Tuple[float, torch.Tensor]:
-        """(-sum_c mll_c / n, its gradient with respect to ``raw``).  When ANY class meets a non-positive pivot the whole
-        call is retried with psd_safe_cholesky's jitters (1e-8, 1e-7, 1e-6), a warning per attempt, NotPSDError after
-        the last."""
-        attempts = [0.0] + [CHOLESKY_JITTER * 10**i for i in range(CHOLESKY_MAX_TRIES)]
-        for jit in attempts:
-            if jit > 0.0:
-                warnings.warn(f"A not p.d., added jitter of {jit:.1e} to the diagonal", RuntimeWarning, stacklevel=2)
-            out, info = self.evaluate_on_device(jit)
-            if not info.any():
-                return self.chain_rule(out)
-        raise NotPSDError(f"Matrix not positive definite after repeatedly adding jitter up to {attempts[-1]:.1e}.")
-
-    # ---- prediction -------------------------------------------------------------------------------------------------
     def predict(self, x_test: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
         """(latent mean, latent variance), both (C, t) float64 on the device: per class m_c + k*^T alpha_c and
         k** - |Lc^-1 k*|^2 with K_y,c = Lc Lc^T and alpha_c = K_y,c^-1 (y~_c - m_c)."""
-        st = self._device_state()
-        xt = x_test if x_test.dim() == 2 else x_test[:, None]
-        means, variances = [], []
-        noise, mean_c, s = self.noise.tolist(), self.mean_constant.tolist(), self.outputscale.tolist()
-        for c, kern in enumerate(self.kernels):
-            ky = kern(st["x"], st["x"])
-            ky.diagonal().add_(st["fixed"][c] + noise[c] if st["fixed"] is not None else noise[c])
-            factor = cholesky_factor(ky)
-            alpha = factor.solve((st["y"][c] - mean_c[c])[:, None].contiguous())
-            ks = kern(st["x"], xt)  # (n, t): k-major
-            t = ks.shape[1]
-            mean = torch.empty((t, 1), dtype=torch.float64, device=ks.device)
-            L.check(L.load().pls_gemm_tn(ks.data_ptr(), L.ld(ks), alpha.data_ptr(), 1, mean.data_ptr(), 1, t, 1, self.n, 1.0, 0.0,
-                                         L.stream_ptr()), "pls_gemm_tn")
-            v = factor.forward_solve(ks)
-            means.append(mean[:, 0] + mean_c[c])
-            variances.append(s[c] - v.square().sum(dim=0))
-        return torch.stack(means), torch.stack(variances)
+        rows = [self._predict_class(c, x_test) for c in range(self.number_of_classes)]
+        return torch.stack([mean for mean, _ in rows]), torch.stack([var for _, var in rows])
 
     def predict_proba(self, x_test: torch.Tensor, number_of_samples: int = 256, seed: int = 0) -> torch.Tensor:
         """(t, C) class probabilities: the mean over ``number_of_samples`` draws of softmax(f), f_c ~ N(mean_c, var_c)

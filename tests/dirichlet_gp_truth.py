@@ -3,7 +3,6 @@ per-class marginal log-likelihood with its gradient through LAPACK with the diag
 forms of tests/exact_gp_truth.py), the host restatement of the class probabilities (oracle/philox_ref + numpy +
 math.fsum), and the case table of tests/golden/dirichlet_gp_truth.npz (50-digit values, written by
 tests/golden/make_dirichlet_gp_truth.py)."""
-import hashlib
 import math
 import os
 
@@ -12,6 +11,7 @@ import torch
 
 import exact_gp_truth as E
 from oracle import philox_ref
+from truth_common import _normal, _uniform, checksum, fixture_truth  # noqa: F401
 
 EPS = E.EPS
 TRUTH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "dirichlet_gp_truth.npz")
@@ -33,39 +33,10 @@ def transform(labels, classes, alpha_epsilon=ALPHA_EPSILON):
     return y, v
 
 
-def mll_and_grad_class(kind, x, y, ls, s, sigma, mean, fixed=None):
-    """One class: the 4 + d outputs of a row of pls_gp_mll_grad_classes through LAPACK and, per output, its
-    sum-of-magnitudes scale (exact_gp_truth.mll_and_grad with the diagonal fixed + sigma)."""
-    x = x if x.dim() == 2 else x[:, None]
-    n = x.shape[0]
-    diag = torch.full((n,), float(sigma), dtype=torch.float64)
-    if fixed is not None:
-        diag = fixed.double() + float(sigma)
-    ky = s * E.kappa(kind, x, ls) + torch.diag(diag)
-    low = torch.linalg.cholesky(ky)
-    r = y.double() - mean
-    alpha = torch.cholesky_solve(r[:, None], low)[:, 0]
-    p = torch.cholesky_inverse(low)
-    p = 0.5 * (p + p.T)
-    logs = torch.log(low.diagonal())
-    quad = math.fsum((r * alpha).tolist())
-    sums, scale = E.grad_sums(kind, x, ls, s, alpha, p)
-    wdiag = alpha * alpha - p.diagonal()
-    out = np.empty(4 + x.shape[1])
-    mag = np.empty_like(out)
-    out[0] = -0.5 * quad - math.fsum(logs.tolist()) - 0.5 * n * math.log(2.0 * math.pi)
-    mag[0] = 0.5 * abs(quad) + math.fsum(logs.abs().tolist())
-    out[1], mag[1] = math.fsum(alpha.tolist()), math.fsum(alpha.abs().tolist())
-    out[2], mag[2] = 0.5 * math.fsum(wdiag.tolist()), 0.5 * math.fsum(wdiag.abs().tolist())
-    out[3], mag[3] = 0.5 * s * sums[0], 0.5 * s * scale[0]
-    out[4:], mag[4:] = 0.5 * sums[1:], 0.5 * scale[1:]
-    return out, mag
-
-
 def mll_and_grad(kind, x, targets, fixed, ls, s, sigma, mean):
     """all classes: (out, scale), both (C, 4 + d); ls (C, d), s / sigma / mean (C); fixed (C, n) or None"""
-    rows = [mll_and_grad_class(kind, x, targets[c], ls[c], float(s[c]), float(sigma[c]), float(mean[c]),
-                               None if fixed is None else fixed[c]) for c in range(targets.shape[0])]
+    rows = [E.mll_and_grad(kind, x, targets[c], ls[c], float(s[c]), float(sigma[c]), float(mean[c]),
+                           None if fixed is None else fixed[c]) for c in range(targets.shape[0])]
     return np.stack([r[0] for r in rows]), np.stack([r[1] for r in rows])
 
 
@@ -149,35 +120,20 @@ def case_inputs(name):
     sigma 0.05 + 0.2 U, mean U - 0.5 -- all distinct"""
     kind, n, d, classes, seed = CASES[name]
     g = torch.Generator().manual_seed(seed)
-    x = E._normal(g, (n, d))
+    x = _normal(g, (n, d))
     labels = torch.randint(0, classes, (n,), generator=g, dtype=torch.int64)
     y, v = transform(labels.tolist(), classes)
     y, v = y.float().double(), v.float().double()
-    ls = (0.5 + E._uniform(g, (classes, d))) * d**0.5
-    s = 0.8 + E._uniform(g, (classes,))
-    sigma = 0.05 + 0.2 * E._uniform(g, (classes,))
-    mean = E._uniform(g, (classes,)) - 0.5
+    ls = (0.5 + _uniform(g, (classes, d))) * d**0.5
+    s = 0.8 + _uniform(g, (classes,))
+    sigma = 0.05 + 0.2 * _uniform(g, (classes,))
+    mean = _uniform(g, (classes,)) - 0.5
     return kind, x, labels, y, v, ls, s, sigma, mean
-
-
-def checksum(*tensors):
-    h = hashlib.sha256()
-    for t in tensors:
-        h.update(t.contiguous().numpy().tobytes())
-    return h.hexdigest()
-
-
-_truth_cache = {}
 
 
 def truth(name):
     """the 50-digit outputs (C, 4 + d) of a case as (hi, lo) float64 pairs, after checking the regenerated inputs"""
-    if not _truth_cache:
-        with np.load(TRUTH) as f:
-            _truth_cache.update({k: f[k] for k in f.files})
-    inputs = case_inputs(name)
-    assert str(_truth_cache[f"{name}/sha256"]) == checksum(*inputs[1:]), f"{name}: the regenerated inputs are not the fixture's"
-    return _truth_cache[f"{name}/hi"], _truth_cache[f"{name}/lo"]
+    return fixture_truth(TRUTH, name, case_inputs(name)[1:])
 
 
 _cpu_cache = {}

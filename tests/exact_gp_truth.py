@@ -8,7 +8,6 @@ With e_k = (x_ik - x_jk) / l_k, r^2 = sum_k e_k^2, kappa the kernel without its 
     Matern:  kappa = p(t) exp(-t), t = sqrt(2 nu) r,  dK / d log l_k = s q(t) exp(-t) 2 nu e_k^2,
              q = 1/t, 1, (1 + t)/3 for nu = 1/2, 3/2, 5/2
 A pair with r = 0 has derivative 0 (also where q = 1/t), a pair whose exponential is 0 contributes 0 everywhere."""
-import hashlib
 import math
 import os
 
@@ -16,6 +15,7 @@ import numpy as np
 import torch
 
 from matern_closed_form import matern_torch
+from truth_common import _normal, _uniform, checksum, fixture_truth, relative_error  # noqa: F401
 
 RBF, MATERN12, MATERN32, MATERN52 = 0, 2, 3, 4  # pls_kernel_kind
 KINDS = (RBF, MATERN12, MATERN32, MATERN52)
@@ -80,13 +80,15 @@ def grad_sums(kind, x, ls, s, alpha, p):
     return fsum_rows(pair_terms(kind, x, ls, s, alpha, p))
 
 
-def mll_and_grad(kind, x, y, ls, s, noise, mean):
-    """The 4 + d outputs of pls_gp_mll_grad through LAPACK (Cholesky, cholesky_solve, cholesky_inverse) and, per output,
-    its sum-of-magnitudes scale: 1/2 |r^T alpha| + sum |log L_ii| for the value, sum |alpha_i| for d/d mean, and
-    S_theta = 1/2 sum_ij |W_ij dK_ij / d theta| for the rest."""
+def mll_and_grad(kind, x, y, ls, s, noise, mean, fixed=None):
+    """The 4 + d outputs of pls_gp_mll_grad (of a row of pls_gp_mll_grad_classes when ``fixed`` (n) joins the noise on the
+    diagonal) through LAPACK (Cholesky, cholesky_solve, cholesky_inverse) and, per output, its sum-of-magnitudes scale:
+    1/2 |r^T alpha| + sum |log L_ii| for the value, sum |alpha_i| for d/d mean, and S_theta = 1/2 sum_ij |W_ij dK_ij / d theta|
+    for the rest."""
     x = x if x.dim() == 2 else x[:, None]
     n = x.shape[0]
-    ky = s * kappa(kind, x, ls) + noise * torch.eye(n, dtype=torch.float64)
+    diag = torch.full((n,), float(noise), dtype=torch.float64) if fixed is None else fixed.double() + float(noise)
+    ky = s * kappa(kind, x, ls) + torch.diag(diag)
     low = torch.linalg.cholesky(ky)
     r = y.double() - mean
     alpha = torch.cholesky_solve(r[:, None], low)[:, 0]
@@ -122,21 +124,6 @@ for _n in (1, 2, 65, 130, 260):
             CASES[f"{KIND_NAMES[_kind]}-n{_n}-d{_d}"] = (_kind, _n, _d, 500000 + 1000 * _n + 10 * _d + _kind)
 
 
-def _uniform(g, shape):
-    """uniform on [0, 1) from 30-bit integer draws: the same doubles on every machine"""
-    return torch.randint(0, 2**30, shape, generator=g, dtype=torch.int64).double() / 2.0**30
-
-
-def _normal(g, shape):
-    """N(0, 1) as the sum of twelve uniforms minus 6 (mean 0, variance 1, exact additions).  torch.randn, torch.sin and BLAS
-    take different code paths on different CPUs; the fixture holds results, not inputs, so every machine must regenerate
-    the inputs to the bit: integer draws and correctly rounded elementwise operations only, sums in a fixed order."""
-    total = torch.zeros(shape, dtype=torch.float64)
-    for _ in range(12):
-        total = total + _uniform(g, shape)
-    return total - 6.0
-
-
 def case_inputs(name):
     """x ~ N(0, I) (n, d), y = 2 t / (1 + t^2) + 0.3 N(0, 1) with t = sum_k x_k, lengthscale = (0.5 + U) sqrt(d)"""
     kind, n, d, seed = CASES[name]
@@ -150,24 +137,9 @@ def case_inputs(name):
     return kind, x, y, ls
 
 
-def checksum(x, y, ls):
-    h = hashlib.sha256()
-    for t in (x, y, ls):
-        h.update(t.contiguous().numpy().tobytes())
-    return h.hexdigest()
-
-
-_truth_cache = {}
-
-
 def truth(name):
     """the 50-digit outputs (4 + d) of a case as (hi, lo) float64 pairs, after checking that the inputs are the recorded ones"""
-    if not _truth_cache:
-        with np.load(TRUTH) as f:
-            _truth_cache.update({k: f[k] for k in f.files})
-    _, x, y, ls = case_inputs(name)
-    assert str(_truth_cache[f"{name}/sha256"]) == checksum(x, y, ls), f"{name}: the regenerated inputs are not the fixture's"
-    return _truth_cache[f"{name}/hi"], _truth_cache[f"{name}/lo"]
+    return fixture_truth(TRUTH, name, case_inputs(name)[1:])
 
 
 _cpu_cache = {}
@@ -182,10 +154,3 @@ def cpu_case(name):
         hi, lo = truth(name)
         _cpu_cache[name] = (out, mag, relative_error(out, hi, lo, mag))
     return _cpu_cache[name]
-
-
-def relative_error(got, hi, lo, mag):
-    """|got - truth| / scale per output; where the scale is 0 (every term is 0: n = 1) only the exact value passes"""
-    err = np.abs((np.asarray(got, dtype=np.float64) - hi) - lo)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        return np.where(mag > 0, err / mag, np.where(err == 0, 0.0, np.inf))

@@ -13,12 +13,13 @@ An output vector is laid out as  [ELBO, d/dc, d/drho, (1/B) sum l_i, KL,  d/dm (
 The majorant: the same formulas with every input replaced by its magnitude, every subtraction by an addition and
 (y - mu)^2 by (|y| + mu_maj)^2: per output the sum of the magnitudes of everything that enters it, S.  Any summation
 order over at most M + B float64 products errs by at most about (M + B) eps S; the tests allow (M + B + 16) eps S."""
-import hashlib
 import math
 import os
 
 import numpy as np
 import torch
+
+from truth_common import _normal, _uniform, checksum, fixture_truth, relative_error  # noqa: F401
 
 EPS = 2.0**-52
 MIN_NOISE = 1e-4
@@ -181,17 +182,6 @@ def closed_form_optimum(At, y, c, rho):
 
 
 # ---- seeded inputs: integer draws and exactly rounded elementwise operations only (the same doubles on every machine) ----
-def _uniform(g, shape):
-    return torch.randint(0, 2**30, shape, generator=g, dtype=torch.int64).double() / 2.0**30
-
-
-def _normal(g, shape):
-    total = torch.zeros(shape, dtype=torch.float64)
-    for _ in range(12):
-        total = total + _uniform(g, shape)
-    return total - 6.0
-
-
 def make_inputs(seed, n, m, b=None):
     """At ~ 0.3 N(0, 1), q = 0.05 + U, y ~ N(0, 1), m ~ 0.5 N(0, 1), L_s = 0.2 N(0, 1) below a diagonal 0.5 + U with
     alternating sign, c = 0.3, rho = -0.7; idx: b distinct rows, 37 apart (mod n), None when b is None"""
@@ -218,11 +208,9 @@ def case_inputs(name):
     return make_inputs(seed, N_FIXTURE, m, b)
 
 
-def checksum(inp):
-    h = hashlib.sha256()
-    for k in ("At", "q", "y", "mean", "Ls", "idx"):
-        h.update(inp[k].contiguous().numpy().tobytes())
-    return h.hexdigest()
+def hashed(inp):
+    """the tensors of a case that the fixture's SHA-256 covers, in its order"""
+    return [inp[k] for k in ("At", "q", "y", "mean", "Ls", "idx")]
 
 
 def evaluate_inputs(inp, majorant=False):
@@ -230,16 +218,9 @@ def evaluate_inputs(inp, majorant=False):
                     inp["rho"], None if inp["idx"] is None else inp["idx"].numpy(), inp["n"], majorant)
 
 
-_truth_cache = {}
-
-
 def truth(name):
     """the 50-digit output vector of a fixture case as (hi, lo), after checking that the inputs are the recorded ones"""
-    if not _truth_cache:
-        with np.load(TRUTH) as f:
-            _truth_cache.update({k: f[k] for k in f.files})
-    assert str(_truth_cache[f"{name}/sha256"]) == checksum(case_inputs(name)), f"{name}: the regenerated inputs are not the fixture's"
-    return _truth_cache[f"{name}/hi"], _truth_cache[f"{name}/lo"]
+    return fixture_truth(TRUTH, name, hashed(case_inputs(name)))
 
 
 _cpu_cache = {}
@@ -251,10 +232,3 @@ def cpu_case(name):
         inp = case_inputs(name)
         _cpu_cache[name] = (inp, evaluate_inputs(inp), evaluate_inputs(inp, majorant=True))
     return _cpu_cache[name]
-
-
-def relative_error(got, hi, lo, scale):
-    """|got - truth| / S per output; where S is 0 only the exact value passes"""
-    err = np.abs((np.asarray(got, dtype=np.float64) - hi) - lo)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        return np.where(scale > 0, err / scale, np.where(err == 0, 0.0, np.inf))

@@ -151,7 +151,7 @@ def test_pivot_is_reported_for_its_class_alone(lib):
         assert rc == 0 and info == [0, 2, 0], (kind, rc, info)
         for c in (0, 2):
             hi, lo = M.evaluate(kind, x.numpy(), y[c].numpy(), (v[c] + sigma[c]).numpy(), ls[c].numpy(), s[c].item(), mean[c].item())
-            cpu, mag = T.mll_and_grad_class(kind, x, y[c], ls[c], s[c].item(), sigma[c].item(), mean[c].item(), v[c])
+            cpu, mag = E.mll_and_grad(kind, x, y[c], ls[c], s[c].item(), sigma[c].item(), mean[c].item(), v[c])
             bar = np.maximum(16.0 * E.relative_error(cpu, hi, lo, mag), 64.0 * E.EPS)
             err = E.relative_error(got[c].numpy(), hi, lo, mag)
             print(f"kind {kind} class {c} beside a failed class: max err/bar {np.max(err / bar):.3f}")

@@ -168,6 +168,25 @@ def test_not_positive_definite_is_reported_not_thrown(lib):
     assert np.isfinite(loss) and torch.isfinite(grad).all()
 
 
+@pytest.mark.parametrize("ard", [True, False], ids=["ard", "shared"])
+@pytest.mark.parametrize("name", ["rbf-n130-d3", "matern32-n65-d8", "matern52-n2-d1"])
+def test_model_evaluation_is_gp_mll_grad(lib, name, ard):
+    """ExactGP reaches the device through pls_gp_mll_grad_classes with one class: what it returns is, bit for bit, a
+    direct pls_gp_mll_grad call at the model's own parameters, without and with jitter."""
+    import projected_langevin_sampling_amd as pkg
+
+    kind, x, y, _ = T.case_inputs(name)
+    model = pkg.ExactGP(x, y, T.KIND_NAMES[kind], ard=ard)
+    assert model.kind == kind and model.raw.shape == (3 + (x.shape[1] if ard else 1),)
+    g = torch.Generator().manual_seed(900 + kind + ard)
+    model.set_raw_parameters(0.5 * torch.randn(model.raw.numel(), generator=g, dtype=F64))
+    for jitter in (0.0, 1e-6):
+        out, info = model.evaluate_on_device(jitter)
+        want, flag, rc = gp_mll(lib, kind, x, y, model.lengthscale, model.outputscale, model.noise, model.mean_constant, jitter)
+        assert rc == 0 and flag == 0 and info == 0
+        assert out.shape == (4 + x.shape[1],) and torch.equal(out, want), (name, ard, jitter)
+
+
 # ---- training ------------------------------------------------------------------------------------------------------------
 def _training_data(n, d, seed):
     g = torch.Generator().manual_seed(seed)
