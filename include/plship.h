@@ -592,7 +592,9 @@ int pls_softmax_normal_mean(const double *mu, int64_t ldmu, const double *var, i
  * bits, and the outputs depend on the CONTENT of idx only (NULL = rows 0 .. B-1 in order = an explicit identity list).
  * An index outside 0 .. n-1 is not read: its point becomes NaN.  Nothing synchronises or allocates. */
 typedef enum {
-  PLS_SVGP_GAUSSIAN = 0   /* the only likelihood accepted; the per-point epilogue is a template parameter of the kernels */
+  PLS_SVGP_GAUSSIAN = 0,   /* the only one pls_svgp_elbo_grad / pls_svgp_sgd_epoch accept (closed-form epilogue) */
+  PLS_SVGP_BERNOULLI = 1,  /* probit; through the pls_svgp_lik_* entries below */
+  PLS_SVGP_STUDENT_T = 2   /* fixed degrees of freedom; through the pls_svgp_lik_* entries below */
 } pls_svgp_likelihood;
 
 typedef enum {
@@ -642,6 +644,71 @@ int pls_svgp_sgd_epoch(const pls_svgp_desc *desc, double *m, double *L_s, int64_
 int pls_svgp_predict(const double *m, const double *L_s, int64_t ldls, const double *scalars, const double *At_test,
                      int64_t ldat, const double *q_test, int64_t t, int64_t mdim, double *mean_out, double *var_out,
                      void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * SVGP with a quadrature likelihood (Bernoulli, Student-t)
+ * ------------------------------------------------------------------------------------------- */
+
+/* Replaces SVGP(..., likelihood=BernoulliLikelihood()) of the two classification drivers
+ * (experiments/curves/classification/main.py:324-361, experiments/uci/classification/main.py:267-277) and the
+ * `svgp-student` model of experiments/uci/regression/main.py:353-401 (StudentTLikelihood, degrees of freedom pinned).
+ * RECALLED, not read: gpytorch 1.15's BernoulliLikelihood, StudentTLikelihood and the Gauss-Hermite quadrature of
+ * _OneDimensionalLikelihood.expected_log_prob (20 nodes by default) as remembered; gpytorch is not available to this
+ * project and the formulas below are the contract.
+ *
+ * mu_i, w_i, v_i, KL, the ELBO and the assembly d/dm, d/dL_s, d/dc are those of the SVGP section above; only the per-point
+ * terms l_i, g_mu,i, g_v,i differ.  With Q = 20, x_k and omega_k the nodes and weights of
+ * numpy.polynomial.hermite.hermgauss(20) as doubles (17 significant digits in csrc/svgp.hip) and w^_k = omega_k / sqrt(pi)
+ * rounded once:
+ *   f_k = mu_i + sqrt(2 v_i) x_k        l_i = sum_k w^_k g(f_k)
+ *   g_mu,i = sum_k w^_k g'(f_k)         g_v,i = (sum_k w^_k g'(f_k) x_k) / sqrt(2 v_i)
+ * the derivatives of the quadrature SUM (what autograd on gpytorch yields), not quadratures of derivatives.  They need
+ * v_i > 0: a point with v_i <= 0 becomes non-finite and shows in every output, as an out-of-range index does.
+ *
+ * PLS_SVGP_BERNOULLI (probit): y in {0, 1}, s = 2 y - 1, g(f) = log Phi(s f), g'(f) = s phi(s f) / Phi(s f), accurate in
+ * the tails: for z < 0  log Phi(z) = log(erfcx(-z / sqrt 2) / 2) - z^2 / 2 and phi / Phi = sqrt(2 / pi) / erfcx(-z / sqrt 2);
+ * for z >= 0  log Phi(z) = log1p(-erfc(z / sqrt 2) / 2).  No likelihood parameter: out[2] = 0 exactly and rho is never
+ * written, PLS_SVGP_TRAIN_NOISE or not.  Prediction: obs_out = p (1 - p) at p = Phi(mu / sqrt(1 + v)).
+ *
+ * PLS_SVGP_STUDENT_T: scale^2 = s^2 = noise = softplus(rho) (gpytorch's Positive constraint: NO 1e-4 floor, unlike the
+ * Gaussian likelihood's softplus(rho) + 1e-4).  nu = deg_free is a constant: the reference pins it inside an interval of
+ * width 2e-10, so its raw value's gradient is of order 1e-10 and is taken as 0.  With r = y - f:
+ *   g      = lgamma((nu + 1) / 2) - lgamma(nu / 2) - 1/2 log(nu pi s^2) - (nu + 1) / 2 log1p(r^2 / (nu s^2))
+ *   g'     = (nu + 1) r / (nu s^2 + r^2)
+ *   dg/ds2 = -1 / (2 s^2) + (nu + 1) r^2 / (2 s^2 (nu s^2 + r^2))
+ *   d/drho = sigmoid(rho) (1/B) sum_i sum_k w^_k dg/ds2(f_k)
+ * Prediction: obs_out = v + s^2 nu / (nu - 2).
+ *
+ * PLS_SVGP_GAUSSIAN through these entries: the bits of pls_svgp_elbo_grad / pls_svgp_sgd_epoch / pls_svgp_predict, and
+ * obs_out = v + sigma^2.
+ *
+ * The workspace is pls_svgp_workspace_bytes; the launches, the order of every sum and the promises of the SVGP section
+ * (two calls the same bits, the value-only call equals the full call, the outputs depend on the content of idx only) are
+ * the same.  Per point the nodes are added in a fixed order: 8 lanes, lane s adds nodes s, s + 8, s + 16, then an xor
+ * butterfly.  Validation comes before any HIP call: an unknown likelihood, a Student-t deg_free that is not finite or
+ * not > 2, and everything the SVGP entries check. */
+typedef struct {
+  pls_svgp_desc base; /* base.likelihood: any pls_svgp_likelihood */
+  double deg_free;    /* Student-t: nu > 2, fixed; ignored otherwise */
+} pls_svgp_lik_desc;
+
+/* pls_svgp_elbo_grad with the descriptor's likelihood (out[2] = d/drho: 0 for Bernoulli). */
+int pls_svgp_lik_elbo_grad(const pls_svgp_lik_desc *desc, const double *m, const double *L_s, int64_t ldls,
+                           const double *scalars /* {c, rho}, device */, const int64_t *idx, int64_t b, double *out,
+                           double *grad_m, double *grad_L, int64_t ldgl, void *workspace, size_t workspace_bytes,
+                           void *stream);
+
+/* pls_svgp_sgd_epoch with the descriptor's likelihood; a replay through pls_svgp_lik_elbo_grad gives the same bits. */
+int pls_svgp_lik_sgd_epoch(const pls_svgp_lik_desc *desc, double *m, double *L_s, int64_t ldls, double *scalars,
+                           const int64_t *perm, int64_t batch_size, double lr, int32_t flags, double *loss_out,
+                           void *workspace, size_t workspace_bytes, void *stream);
+
+/* pls_svgp_predict (the same bits in mean_out and var_out) and, where obs_out != NULL, the variance of an observation
+ * under the likelihood as stated above (t doubles).  Of desc only base.likelihood and deg_free are read; scalars: c and,
+ * for the Gaussian and Student-t likelihoods, rho.  One launch. */
+int pls_svgp_lik_predict(const pls_svgp_lik_desc *desc, const double *m, const double *L_s, int64_t ldls,
+                         const double *scalars, const double *At_test, int64_t ldat, const double *q_test, int64_t t,
+                         int64_t mdim, double *mean_out, double *var_out, double *obs_out, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Orthonormal basis: setup + step

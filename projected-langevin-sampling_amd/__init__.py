@@ -7,6 +7,7 @@ from . import _lib
 from .gaussian_process import (SVGP, DirichletExactGP, ExactGP, construct_average_ard_kernel, construct_average_gaussian_noise,
                                dirichlet_targets, exact_gp_runner, nearest_subsample, softmax_normal_mean, train_exact_gp)
 from .kernel import ARDKernel, LinearKernel, MaternKernel, PLSKernel
+from .likelihoods import BernoulliLikelihood, GaussianLikelihood, StudentTLikelihood
 from .projected_langevin_sampling import PLS
 from .runners import train_svgp_runner
 from .temper import TemperGP
@@ -15,4 +16,5 @@ from .trainers import EarlyStopper, epoch_batches, train_pls, train_pls_captured
 __all__ = ["PLS", "PLSKernel", "ARDKernel", "MaternKernel", "LinearKernel", "EarlyStopper", "train_pls", "train_pls_captured", "ExactGP",
            "DirichletExactGP", "dirichlet_targets", "softmax_normal_mean",
            "train_exact_gp", "exact_gp_runner", "construct_average_ard_kernel", "construct_average_gaussian_noise",
-           "nearest_subsample", "SVGP", "train_svgp", "train_svgp_runner", "epoch_batches", "TemperGP", "_lib"]
+           "nearest_subsample", "SVGP", "train_svgp", "train_svgp_runner", "epoch_batches", "TemperGP", "GaussianLikelihood",
+           "BernoulliLikelihood", "StudentTLikelihood", "_lib"]

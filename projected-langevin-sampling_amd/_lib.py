@@ -19,7 +19,7 @@ LINK_IDENTITY, LINK_SQUARE, LINK_SIGMOID, LINK_PROBIT = range(4)
 DERIV_REFERENCE, DERIV_AUTOGRAD = 0, 1
 NOISE_NONE, NOISE_INJECTED, NOISE_PHILOX = 0, 1, 2
 OUT_DELTA, OUT_NEW_STATE = 0, 1
-SVGP_GAUSSIAN = 0
+SVGP_GAUSSIAN, SVGP_BERNOULLI, SVGP_STUDENT_T = 0, 1, 2
 SVGP_TRAIN_MEAN, SVGP_TRAIN_NOISE = 1, 2
 
 
@@ -127,6 +127,10 @@ class SvgpDesc(C.Structure):
                 ("m", C.c_int64), ("likelihood", C.c_int32), ("reserved", C.c_int32)]
 
 
+class SvgpLikDesc(C.Structure):
+    _fields_ = [("base", SvgpDesc), ("deg_free", C.c_double)]
+
+
 class BlockDesc(C.Structure):
     _fields_ = [("block_cols", C.c_int64), ("eta", C.c_void_p), ("energy_sums", C.c_void_p), ("energy_sync", C.c_void_p),
                 ("energy_partials", C.c_void_p), ("energy_partials_prev", C.c_void_p), ("energy_prev", C.c_void_p),
@@ -136,7 +140,7 @@ class BlockDesc(C.Structure):
 
 _P, _I64, _I32, _U64, _D, _SZ = C.c_void_p, C.c_int64, C.c_int32, C.c_uint64, C.c_double, C.c_size_t
 _CD, _ND, _OD, _ID = C.POINTER(CostDesc), C.POINTER(NoiseDesc), C.POINTER(OnbDesc), C.POINTER(IpbDesc)
-_CHD, _BD, _SD = C.POINTER(CholDesc), C.POINTER(BlockDesc), C.POINTER(SvgpDesc)
+_CHD, _BD, _SD, _SLD = C.POINTER(CholDesc), C.POINTER(BlockDesc), C.POINTER(SvgpDesc), C.POINTER(SvgpLikDesc)
 
 # name -> (restype, argtypes); every symbol include/plship.h declares
 SIGNATURES = {
@@ -220,6 +224,9 @@ SIGNATURES = {
     "pls_svgp_elbo_grad": (C.c_int, [_SD, _P, _P, _I64, _P, _P, _I64, _P, _P, _P, _I64, _P, _SZ, _P]),
     "pls_svgp_sgd_epoch": (C.c_int, [_SD, _P, _P, _I64, _P, _P, _I64, _D, _I32, _P, _P, _SZ, _P]),
     "pls_svgp_predict": (C.c_int, [_P, _P, _I64, _P, _P, _I64, _P, _I64, _I64, _P, _P, _P]),
+    "pls_svgp_lik_elbo_grad": (C.c_int, [_SLD, _P, _P, _I64, _P, _P, _I64, _P, _P, _P, _I64, _P, _SZ, _P]),
+    "pls_svgp_lik_sgd_epoch": (C.c_int, [_SLD, _P, _P, _I64, _P, _P, _I64, _D, _I32, _P, _P, _SZ, _P]),
+    "pls_svgp_lik_predict": (C.c_int, [_SLD, _P, _P, _I64, _P, _P, _I64, _P, _I64, _I64, _P, _P, _P, _P]),
 }
 
 ABI_VERSION = 7

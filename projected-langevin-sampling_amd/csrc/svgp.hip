@@ -1,5 +1,5 @@
-// Sparse variational GP with a FIXED kernel and FIXED inducing points, Gaussian likelihood: the minibatch ELBO, its
-// gradient, the SGD epoch and the prediction.
+// Sparse variational GP with a FIXED kernel and FIXED inducing points: the minibatch ELBO, its gradient, the SGD epoch and
+// the prediction, with a Gaussian likelihood (closed form) or a Bernoulli / Student-t likelihood (20-node Gauss-Hermite).
 //
 // Reference: SVGP (src/gaussian_process/svgp.py:6-49), train_svgp with is_fixed=True (experiments/trainers.py:55-136) and
 // train_svgp_for_profiler (experiments/profiler/main.py:85-123).  The arithmetic is gpytorch 1.15's whitened
@@ -16,7 +16,9 @@
 //                       in 4-row k-panels straight from memory into the B fragment (an element of L_s is used by one wave
 //                       of a workgroup only, so an LDS copy would be written and read once), rows above the column's
 //                       diagonal are skipped and the upper triangle is never read.  Then mu and |w|^2 (a wave per point:
-//                       lane l adds k = l, l + 64, ...; xor butterfly 32 ... 1), the per-point likelihood epilogue, the
+//                       lane l adds k = l, l + 64, ...; xor butterfly 32 ... 1), the per-point likelihood epilogue (the
+//                       Gaussian one on lane 0; the quadrature ones after the wave's 8 points are known: 8 lanes per
+//                       point, lane s of a group adds nodes s, s + 8, s + 16 in that order, xor butterfly 4, 2, 1), the
 //                       tile's three scalar sums (xor butterfly over its 32 points), sum_i g_mu,i a_i (thread k adds the
 //                       points in ascending order) and the tile's partial of sum_i g_v,i a_i w_i^T: the lower 16 x 16
 //                       tiles dealt to the waves round-robin, 8 MFMAs each with the accumulator in place.  Workgroup 0
@@ -27,6 +29,8 @@
 //                       p <- p - lr * (-g) as a multiply and a subtract (no contraction), so a replay of
 //                       pls_svgp_elbo_grad + the same two operations elsewhere gives the same bits.
 #include <hip/hip_runtime.h>
+
+#include <cmath>
 
 #include "../../include/plship.h"
 #include "common.h"
@@ -88,6 +92,106 @@ struct SvgpEpilogue<PLS_SVGP_GAUSSIAN> {
   }
 };
 
+// The quadrature likelihoods (include/plship.h, "SVGP with a quadrature likelihood"): l = sum_k w^_k g(f_k) over the
+// SVGP_Q Gauss-Hermite nodes f_k = mu + sqrt(2 v) x_k, with g_mu and g_v the derivatives of that SUM.  x_k, omega_k are
+// numpy.polynomial.hermite.hermgauss(20) as doubles; w^_k = omega_k / sqrt(pi) rounded once.
+constexpr int SVGP_Q = 20;
+__constant__ double svgp_gh_x[SVGP_Q] = {
+    -5.3874808900112328,  -4.6036824495507442,  -3.9447640401156252,  -3.3478545673832163, -2.7888060584281305,
+    -2.2549740020892757,  -1.7385377121165861,  -1.2340762153953231,  -0.73747372854539439, -0.24534070830090124,
+    0.24534070830090124,  0.73747372854539439,  1.2340762153953231,   1.7385377121165861,  2.2549740020892757,
+    2.7888060584281305,   3.3478545673832163,   3.9447640401156252,   4.6036824495507442,  5.3874808900112328};
+__constant__ double svgp_gh_w[SVGP_Q] = {
+    1.2578006724379234e-13, 2.4820623623151755e-10, 6.127490259982928e-08, 4.402121090230851e-06, 0.00012882627996192928,
+    0.0018301031310804898,  0.013997837447101022,   0.06150637206397689,   0.16173933398399998,   0.26079306344955483,
+    0.26079306344955483,    0.16173933398399998,    0.06150637206397689,   0.013997837447101022,  0.0018301031310804898,
+    0.00012882627996192928, 4.402121090230851e-06,  6.127490259982928e-08, 2.4820623623151755e-10, 1.2578006724379234e-13};
+
+constexpr double SVGP_INV_SQRT2 = 0.70710678118654752440;
+constexpr double SVGP_SQRT_2_OVER_PI = 0.79788456080286535588;
+constexpr double SVGP_INV_SQRT_2PI = 0.39894228040143267794;
+
+// what the likelihood adds to the arguments: Student-t's fixed degrees of freedom and the part of its log-normaliser that
+// does not depend on the scale, lgamma((nu + 1) / 2) - lgamma(nu / 2) - 1/2 log(nu pi), evaluated once on the host
+struct SvgpLikArgs {
+  double nu, lgc;
+};
+
+// the likelihood's noise from the raw value: Gaussian softplus + 1e-4 (GreaterThan(1e-4)), Student-t softplus alone
+// (Positive), Bernoulli none
+template <int LIK>
+__device__ __forceinline__ double svgp_noise(double rho) {
+  if (LIK == PLS_SVGP_GAUSSIAN) return svgp_softplus(rho) + SVGP_MIN_NOISE;
+  if (LIK == PLS_SVGP_STUDENT_T) return svgp_softplus(rho);
+  return 0.0;
+}
+
+// One node: g(f), g'(f) and dg / d sigma^2.
+template <int LIK>
+struct SvgpNode;
+// probit: g = log Phi(s f), s = 2 y - 1.  Below 0 through erfcx (Phi itself underflows from s f = -38 on), above through
+// log1p of the upper tail.
+template <>
+struct SvgpNode<PLS_SVGP_BERNOULLI> {
+  __device__ __forceinline__ static void eval(double y, double f, double, const SvgpLikArgs &, double &g, double &gp, double &gs) {
+    const double s = 2.0 * y - 1.0, z = s * f;
+    double ratio;
+    if (z < 0.0) {
+      const double t = erfcx(-z * SVGP_INV_SQRT2);
+      g = log(0.5 * t) - 0.5 * (z * z);
+      ratio = SVGP_SQRT_2_OVER_PI / t;
+    } else {
+      const double up = 0.5 * erfc(z * SVGP_INV_SQRT2);
+      g = log1p(-up);
+      ratio = SVGP_INV_SQRT_2PI * exp(-0.5 * (z * z)) / (1.0 - up);
+    }
+    gp = s * ratio;
+    gs = 0.0;
+  }
+};
+// Student-t with scale^2 = sig2 and fixed nu
+template <>
+struct SvgpNode<PLS_SVGP_STUDENT_T> {
+  __device__ __forceinline__ static void eval(double y, double f, double sig2, const SvgpLikArgs &k, double &g, double &gp,
+                                              double &gs) {
+    const double r = y - f, r2 = r * r, a = k.nu * sig2, d = a + r2, np1 = k.nu + 1.0;
+    g = (k.lgc - 0.5 * log(sig2)) - 0.5 * np1 * log1p(r2 / a);
+    gp = np1 * r / d;
+    gs = -0.5 / sig2 + np1 * r2 / (2.0 * sig2 * d);
+  }
+};
+
+// The quadrature of the wave's 8 points: lane = 8 * (point of the wave) + s; lane s of a group adds its nodes s, s + 8,
+// s + 16 (< SVGP_Q) in ascending order, then the group's xor butterfly 4, 2, 1 (a dead point's lanes carry zeros).  Every
+// lane of a group returns the point's sums.
+template <int LIK>
+__device__ __forceinline__ void svgp_quadrature(bool live, double y, double mu, double v, double sig2, const SvgpLikArgs &k,
+                                                double &ell, double &gmu, double &gv, double &ds) {
+  const int sub = threadIdx.x & 7;
+  const double sq = sqrt(2.0 * v);
+  double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+  if (live) {
+#pragma unroll
+    for (int node = sub; node < SVGP_Q; node += 8) {
+      const double x = svgp_gh_x[node], w = svgp_gh_w[node];
+      double g, gp, gs;
+      SvgpNode<LIK>::eval(y, fma(sq, x, mu), sig2, k, g, gp, gs);
+      s0 = fma(w, g, s0);
+      s1 = fma(w, gp, s1);
+      s2 = fma(w * x, gp, s2);
+      s3 = fma(w, gs, s3);
+    }
+  }
+#pragma unroll
+  for (int o = 4; o >= 1; o >>= 1) {
+    s0 += __shfl_xor(s0, o);
+    s1 += __shfl_xor(s1, o);
+    s2 += __shfl_xor(s2, o);
+    s3 += __shfl_xor(s3, o);
+  }
+  ell = s0, gmu = s1, gv = live ? s2 / sq : 0.0, ds = s3;
+}
+
 // rows i0 ... i0 + np - 1 of the batch into a_s (SVGP_TILE x lda, zero beyond np and beyond column m).  A live row whose
 // index lies outside 0 ... n - 1 is not read: it becomes NaN and shows in every output.
 __device__ __forceinline__ void svgp_gather(const double *__restrict__ At, int64_t ldat, const int64_t *__restrict__ idx, int64_t n,
@@ -141,6 +245,7 @@ struct SvgpBatchArgs {
   const int64_t *idx;
   int64_t b;
   double *kl, *scal, *pm, *pG;  // workspace pieces
+  SvgpLikArgs lik;              // (read by the quadrature likelihoods only)
 };
 
 template <int LIK, bool GRAD>
@@ -154,7 +259,7 @@ __global__ __launch_bounds__(256) void svgp_batch_kernel(SvgpBatchArgs a) {
   const int64_t tile = blockIdx.x, i0 = tile * SVGP_TILE;
   const int np = (int)((a.b - i0 < SVGP_TILE) ? (a.b - i0) : SVGP_TILE);
   const double c = a.scalars[0], rho = a.scalars[1];
-  const double sig2 = svgp_softplus(rho) + SVGP_MIN_NOISE;
+  const double sig2 = svgp_noise<LIK>(rho);
 
   svgp_gather(a.At, a.ldat, a.idx, a.n, i0, np, m, mp, lda, a_s);
   for (int k = t; k < mp; k += 256) m_s[k] = (k < m) ? a.mean[k] : 0.0;
@@ -170,15 +275,33 @@ __global__ __launch_bounds__(256) void svgp_batch_kernel(SvgpBatchArgs a) {
   svgp_tile_w(a.Ls, a.ldls, m, mp, lda, a_s, w_s);
   __syncthreads();
   // per point: mu, |w|^2 and the likelihood epilogue (a wave per point, 8 points per wave)
-  for (int j = 0; j < SVGP_TILE / 4; ++j) {
-    const int r = wave * (SVGP_TILE / 4) + j;
-    const double mu = c + svgp_wave_dot(a_s + r * lda, m_s, mp);
-    const double wn = svgp_wave_dot(w_s + r * lda, w_s + r * lda, mp);
-    if (lane == 0) {
-      double ell = 0.0, gmu = 0.0, gv = 0.0, ds = 0.0;
-      if (r < np) SvgpEpilogue<LIK>::eval(y_s[r], mu, q_s[r] + wn, sig2, ell, gmu, gv, ds);
-      ell_s[r] = ell, gmu_s[r] = gmu, gv_s[r] = gv, ds_s[r] = ds;
+  if constexpr (LIK == PLS_SVGP_GAUSSIAN) {
+    for (int j = 0; j < SVGP_TILE / 4; ++j) {
+      const int r = wave * (SVGP_TILE / 4) + j;
+      const double mu = c + svgp_wave_dot(a_s + r * lda, m_s, mp);
+      const double wn = svgp_wave_dot(w_s + r * lda, w_s + r * lda, mp);
+      if (lane == 0) {
+        double ell = 0.0, gmu = 0.0, gv = 0.0, ds = 0.0;
+        if (r < np) SvgpEpilogue<LIK>::eval(y_s[r], mu, q_s[r] + wn, sig2, ell, gmu, gv, ds);
+        ell_s[r] = ell, gmu_s[r] = gmu, gv_s[r] = gv, ds_s[r] = ds;
+      }
     }
+  } else {
+    // mu and v of the wave's 8 points are deposited first (in ell_s / gmu_s), then the 8 x SVGP_Q (point, node) pairs are
+    // dealt over the 64 lanes
+    for (int j = 0; j < SVGP_TILE / 4; ++j) {
+      const int r = wave * (SVGP_TILE / 4) + j;
+      const double mu = c + svgp_wave_dot(a_s + r * lda, m_s, mp);
+      const double wn = svgp_wave_dot(w_s + r * lda, w_s + r * lda, mp);
+      if (lane == 0) ell_s[r] = mu, gmu_s[r] = q_s[r] + wn;
+    }
+    __syncthreads();
+    const int r = wave * (SVGP_TILE / 4) + (lane >> 3);
+    const double mu = ell_s[r], v = gmu_s[r];
+    double ell, gmu, gv, ds;
+    svgp_quadrature<LIK>(r < np, y_s[r], mu, v, sig2, a.lik, ell, gmu, gv, ds);
+    __syncthreads();  // (every lane holds its point's mu and v before they are overwritten)
+    if ((lane & 7) == 0) ell_s[r] = ell, gmu_s[r] = gmu, gv_s[r] = gv, ds_s[r] = ds;
   }
   __syncthreads();
   if (wave == 0) {  // the tile's scalar sums: lanes 32 ... 63 carry zeros
@@ -244,7 +367,7 @@ struct SvgpFinishArgs {
   double *scalars;
   double *out, *grad_m, *grad_L;
   int64_t ldgl;
-  int update, flags;
+  int update, flags, lik;  // lik: Bernoulli has no likelihood parameter -- d/drho = 0 exactly and rho is never written
   double lr;
   double *loss_out;
 };
@@ -290,22 +413,27 @@ __global__ __launch_bounds__(256) void svgp_finish_kernel(SvgpFinishArgs a) {
     const double kl = 0.5 * (((a.kl[0] + a.kl[1]) - (double)a.m) - 2.0 * a.kl[2]);
     const double elbo = ell - kl / nd;
     const double gc = s1 / bd;
-    const double grho = svgp_sigmoid(rho) * (s2 / bd);
+    const bool has_noise = a.lik != PLS_SVGP_BERNOULLI;
+    const double grho = has_noise ? svgp_sigmoid(rho) * (s2 / bd) : 0.0;
     if (a.out) a.out[0] = elbo, a.out[1] = gc, a.out[2] = grho, a.out[3] = ell, a.out[4] = kl;
     if (a.loss_out) a.loss_out[0] = -elbo;
     if (a.update) {
       if (a.flags & PLS_SVGP_TRAIN_MEAN) a.scalars[0] = c - a.lr * (-gc);
-      if (a.flags & PLS_SVGP_TRAIN_NOISE) a.scalars[1] = rho - a.lr * (-grho);
+      if ((a.flags & PLS_SVGP_TRAIN_NOISE) && has_noise) a.scalars[1] = rho - a.lr * (-grho);
     }
   }
 }
 
-// mean and latent variance at t points (no likelihood, no sums across points)
+// mean and latent variance at t points (no sums across points) and, where obs_out is given, the likelihood's variance of
+// an observation there: Gaussian v + sigma^2, Student-t v + sigma^2 nu / (nu - 2), Bernoulli p (1 - p) at
+// p = Phi(mu / sqrt(1 + v)) with 1 - p taken as Phi(-...)
+template <int LIK>
 __global__ __launch_bounds__(256) void svgp_predict_kernel(const double *__restrict__ At, int64_t ldat, const double *__restrict__ q,
                                                             int64_t tn, int m, int mp, const double *__restrict__ mean,
                                                             const double *__restrict__ Ls, int64_t ldls,
                                                             const double *__restrict__ scalars, double *__restrict__ mean_out,
-                                                            double *__restrict__ var_out) {
+                                                            double *__restrict__ var_out, double *__restrict__ obs_out,
+                                                            double nu) {
   extern __shared__ __attribute__((aligned(16))) double svgp_lds[];
   const int lda = mp + SVGP_LDS_PAD;
   double *a_s = svgp_lds, *w_s = a_s + SVGP_TILE * lda, *m_s = w_s + SVGP_TILE * lda;
@@ -323,42 +451,93 @@ __global__ __launch_bounds__(256) void svgp_predict_kernel(const double *__restr
     const double mu = c + svgp_wave_dot(a_s + r * lda, m_s, mp);
     const double wn = svgp_wave_dot(w_s + r * lda, w_s + r * lda, mp);
     if (lane == 0 && r < np) {
+      const double v = q[i0 + r] + wn;
       mean_out[i0 + r] = mu;
-      var_out[i0 + r] = q[i0 + r] + wn;
+      var_out[i0 + r] = v;
+      if (obs_out) {
+        double obs;
+        if (LIK == PLS_SVGP_BERNOULLI) {
+          const double z = mu / sqrt(1.0 + v) * SVGP_INV_SQRT2;
+          obs = (0.5 * erfc(-z)) * (0.5 * erfc(z));
+        } else if (LIK == PLS_SVGP_STUDENT_T) {
+          obs = v + svgp_noise<LIK>(scalars[1]) * (nu / (nu - 2.0));
+        } else {
+          obs = v + svgp_noise<LIK>(scalars[1]);
+        }
+        obs_out[i0 + r] = obs;
+      }
     }
   }
 }
 
-static std::atomic<uint64_t> g_lds_batch_grad{0}, g_lds_batch_value{0}, g_lds_predict{0};
+static std::atomic<uint64_t> g_lds_batch[3][2] = {}, g_lds_predict[3] = {};
+
+template <int LIK, bool GRAD>
+static int svgp_launch_batch(const SvgpBatchArgs &ba, int64_t tiles, size_t lds, hipStream_t st) {
+  auto kern = svgp_batch_kernel<LIK, GRAD>;
+  if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(kern), svgp_lds_bytes(SVGP_M_MAX), g_lds_batch[LIK][GRAD ? 1 : 0]))
+    return rc;
+  hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(256), lds, st, ba);
+  return PLS_OK;
+}
+
+template <int LIK>
+static int svgp_launch_predict(const double *m, const double *Ls, int64_t ldls, const double *scalars, const double *At, int64_t ldat,
+                               const double *q, int64_t t, int64_t mdim, double *mean_out, double *var_out, double *obs_out, double nu,
+                               hipStream_t st) {
+  const int64_t mp = svgp_mp(mdim);
+  auto kern = svgp_predict_kernel<LIK>;
+  if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(kern), svgp_lds_bytes(SVGP_M_MAX), g_lds_predict[LIK])) return rc;
+  hipLaunchKernelGGL(kern, dim3((unsigned)svgp_tiles(t)), dim3(256), svgp_lds_bytes(mp), st, At, ldat, q, t, (int)mdim, (int)mp, m, Ls,
+                     ldls, scalars, mean_out, var_out, obs_out, nu);
+  return PLS_OK;
+}
+
+// the likelihood of a validated descriptor as the kernels take it
+static SvgpLikArgs svgp_lik_args(int likelihood, double deg_free) {
+  SvgpLikArgs k{0.0, 0.0};
+  if (likelihood == PLS_SVGP_STUDENT_T) {
+    k.nu = deg_free;
+    k.lgc = (std::lgamma(0.5 * (deg_free + 1.0)) - std::lgamma(0.5 * deg_free)) - 0.5 * std::log(deg_free * 3.14159265358979323846);
+  }
+  return k;
+}
 
 // the two launches of one evaluation over idx[0 .. b) (arguments already validated); ws laid out for THIS call's tiles
-static int svgp_evaluate(const pls_svgp_desc *d, double *mean, double *Ls, int64_t ldls, double *scalars, const int64_t *idx,
-                         int64_t b, bool grad, double *out, double *grad_m, double *grad_L, int64_t ldgl, int update, int flags,
-                         double lr, double *loss_out, double *ws, hipStream_t st) {
+static int svgp_evaluate(const pls_svgp_desc *d, const SvgpLikArgs &lik, double *mean, double *Ls, int64_t ldls, double *scalars,
+                         const int64_t *idx, int64_t b, bool grad, double *out, double *grad_m, double *grad_L, int64_t ldgl,
+                         int update, int flags, double lr, double *loss_out, double *ws, hipStream_t st) {
   const int64_t mp = svgp_mp(d->m), tiles = svgp_tiles(b);
   SvgpBatchArgs ba{};
   ba.At = d->At, ba.ldat = d->ldat, ba.q = d->q, ba.y = d->y, ba.n = d->n, ba.m = (int)d->m, ba.mp = (int)mp;
   ba.mean = mean, ba.Ls = Ls, ba.ldls = ldls, ba.scalars = scalars, ba.idx = idx, ba.b = b;
   ba.kl = ws, ba.scal = ws + 4, ba.pm = ba.scal + 4 * tiles, ba.pG = ba.pm + tiles * mp;
-  const size_t lds = svgp_lds_bytes(mp), lds_max = svgp_lds_bytes(SVGP_M_MAX);
+  ba.lik = lik;
+  const size_t lds = svgp_lds_bytes(mp);
   {
     LaunchScope scope(PLS_TAG_OTHER, st);
-    if (grad) {
-      auto kern = svgp_batch_kernel<PLS_SVGP_GAUSSIAN, true>;
-      if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(kern), lds_max, g_lds_batch_grad)) return rc;
-      hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(256), lds, st, ba);
-    } else {
-      auto kern = svgp_batch_kernel<PLS_SVGP_GAUSSIAN, false>;
-      if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(kern), lds_max, g_lds_batch_value)) return rc;
-      hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(256), lds, st, ba);
+    int rc = PLS_OK;
+    switch (d->likelihood) {
+      case PLS_SVGP_BERNOULLI:
+        rc = grad ? svgp_launch_batch<PLS_SVGP_BERNOULLI, true>(ba, tiles, lds, st)
+                  : svgp_launch_batch<PLS_SVGP_BERNOULLI, false>(ba, tiles, lds, st);
+        break;
+      case PLS_SVGP_STUDENT_T:
+        rc = grad ? svgp_launch_batch<PLS_SVGP_STUDENT_T, true>(ba, tiles, lds, st)
+                  : svgp_launch_batch<PLS_SVGP_STUDENT_T, false>(ba, tiles, lds, st);
+        break;
+      default:
+        rc = grad ? svgp_launch_batch<PLS_SVGP_GAUSSIAN, true>(ba, tiles, lds, st)
+                  : svgp_launch_batch<PLS_SVGP_GAUSSIAN, false>(ba, tiles, lds, st);
     }
+    if (rc) return rc;
   }
   if (int rc = check_launch("svgp_batch")) return rc;
   SvgpFinishArgs fa{};
   fa.m = (int)d->m, fa.mp = (int)mp, fa.rows = grad ? (int)d->m : 0, fa.n = d->n, fa.b = b, fa.tiles = tiles;
   fa.kl = ba.kl, fa.scal = ba.scal, fa.pm = ba.pm, fa.pG = ba.pG, fa.mean = mean, fa.Ls = Ls, fa.ldls = ldls;
   fa.scalars = scalars, fa.out = out, fa.grad_m = grad_m, fa.grad_L = grad_L, fa.ldgl = ldgl;
-  fa.update = update, fa.flags = flags, fa.lr = lr, fa.loss_out = loss_out;
+  fa.update = update, fa.flags = flags, fa.lik = d->likelihood, fa.lr = lr, fa.loss_out = loss_out;
   {
     LaunchScope scope(PLS_TAG_OTHER, st);
     hipLaunchKernelGGL(svgp_finish_kernel, dim3((unsigned)(fa.rows + 1)), dim3(256), 0, st, fa);
@@ -366,15 +545,107 @@ static int svgp_evaluate(const pls_svgp_desc *d, double *mean, double *Ls, int64
   return check_launch("svgp_finish");
 }
 
-static int svgp_check_desc(const pls_svgp_desc *d, const char *who) {
-  PLS_REQUIRE(d, "%s: NULL descriptor", who);
-  PLS_REQUIRE(d->likelihood == PLS_SVGP_GAUSSIAN, "%s: likelihood %d is not supported (PLS_SVGP_GAUSSIAN only)", who, d->likelihood);
+// everything about a descriptor but its likelihood
+static int svgp_check_sizes(const pls_svgp_desc *d, const char *who) {
   PLS_REQUIRE(d->n > 0 && d->m > 0, "%s: bad sizes n=%lld m=%lld", who, (long long)d->n, (long long)d->m);
   PLS_REQUIRE(d->m <= SVGP_M_MAX, "%s: %lld inducing points > %d are not supported", who, (long long)d->m, SVGP_M_MAX);
   PLS_REQUIRE(svgp_tiles(d->n) <= 2147483647, "%s: n=%lld too large", who, (long long)d->n);
   PLS_REQUIRE(d->At && d->q && d->y, "%s: NULL pointer in the descriptor", who);
   PLS_REQUIRE(d->ldat >= d->m, "%s: ldat < m", who);
   return PLS_OK;
+}
+
+static int svgp_check_desc(const pls_svgp_desc *d, const char *who) {
+  PLS_REQUIRE(d, "%s: NULL descriptor", who);
+  PLS_REQUIRE(d->likelihood == PLS_SVGP_GAUSSIAN, "%s: likelihood %d is not supported (PLS_SVGP_GAUSSIAN only)", who, d->likelihood);
+  return svgp_check_sizes(d, who);
+}
+
+static int svgp_check_likelihood(int likelihood, double deg_free, const char *who) {
+  PLS_REQUIRE(likelihood == PLS_SVGP_GAUSSIAN || likelihood == PLS_SVGP_BERNOULLI || likelihood == PLS_SVGP_STUDENT_T,
+              "%s: unknown likelihood %d", who, likelihood);
+  PLS_REQUIRE(likelihood != PLS_SVGP_STUDENT_T || (std::isfinite(deg_free) && deg_free > 2.0),
+              "%s: the Student-t likelihood needs finite deg_free > 2, got %g", who, deg_free);
+  return PLS_OK;
+}
+
+static int svgp_check_lik_desc(const pls_svgp_lik_desc *d, const char *who) {
+  PLS_REQUIRE(d, "%s: NULL descriptor", who);
+  if (int rc = svgp_check_likelihood(d->base.likelihood, d->deg_free, who)) return rc;
+  return svgp_check_sizes(&d->base, who);
+}
+
+// the bodies of the entries, after the descriptor's own checks: `who` names the entry in the messages
+static int svgp_elbo_grad(const pls_svgp_desc *desc, const SvgpLikArgs &lik, const char *who, const double *m, const double *L_s,
+                          int64_t ldls, const double *scalars, const int64_t *idx, int64_t b, double *out, double *grad_m,
+                          double *grad_L, int64_t ldgl, void *workspace, size_t workspace_bytes, void *stream) {
+  PLS_REQUIRE(m && L_s && scalars && out, "%s: NULL pointer", who);
+  PLS_REQUIRE(ldls >= desc->m, "%s: ldls < m", who);
+  PLS_REQUIRE(b > 0 && svgp_tiles(b) <= 2147483647, "%s: bad batch length %lld", who, (long long)b);
+  PLS_REQUIRE(idx || b <= desc->n, "%s: b=%lld > n=%lld without an index list", who, (long long)b, (long long)desc->n);
+  PLS_REQUIRE(!grad_L || ldgl >= desc->m, "%s: ldgl < m", who);
+  PLS_REQUIRE(workspace, "%s: NULL workspace", who);
+  const bool grad = grad_m || grad_L;
+  const size_t need = sizeof(double) * svgp_ws_doubles(svgp_tiles(b), svgp_mp(desc->m), grad);
+  if (workspace_bytes < need)
+    return fail(PLS_ERR_WORKSPACE_TOO_SMALL, "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, need);
+  PLS_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, "%s: workspace must be 8-byte aligned", who);
+  return svgp_evaluate(desc, lik, const_cast<double *>(m), const_cast<double *>(L_s), ldls, const_cast<double *>(scalars), idx, b,
+                       grad, out, grad_m, grad_L, ldgl, 0, 0, 0.0, nullptr, static_cast<double *>(workspace), S(stream));
+}
+
+static int svgp_sgd_epoch(const pls_svgp_desc *desc, const SvgpLikArgs &lik, const char *who, double *m, double *L_s, int64_t ldls,
+                          double *scalars, const int64_t *perm, int64_t batch_size, double lr, int32_t flags, double *loss_out,
+                          void *workspace, size_t workspace_bytes, void *stream) {
+  PLS_REQUIRE(m && L_s && scalars && perm && loss_out, "%s: NULL pointer", who);
+  PLS_REQUIRE(ldls >= desc->m, "%s: ldls < m", who);
+  PLS_REQUIRE(batch_size > 0, "%s: batch_size must be positive", who);
+  PLS_REQUIRE((flags & ~(PLS_SVGP_TRAIN_MEAN | PLS_SVGP_TRAIN_NOISE)) == 0, "%s: unknown flag bits %d", who, flags);
+  PLS_REQUIRE(workspace, "%s: NULL workspace", who);
+  const int64_t bs = batch_size < desc->n ? batch_size : desc->n;
+  const size_t need = pls_svgp_workspace_bytes(desc->n, desc->m, bs);
+  if (workspace_bytes < need)
+    return fail(PLS_ERR_WORKSPACE_TOO_SMALL, "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, need);
+  PLS_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, "%s: workspace must be 8-byte aligned", who);
+  double *ws = static_cast<double *>(workspace);
+  for (int64_t first = 0; first < desc->n; first += bs) {
+    const int64_t b = desc->n - first < bs ? desc->n - first : bs;
+    if (int rc = svgp_evaluate(desc, lik, m, L_s, ldls, scalars, perm + first, b, true, nullptr, nullptr, nullptr, 0, 1, flags, lr,
+                               nullptr, ws, S(stream)))
+      return rc;
+  }
+  return svgp_evaluate(desc, lik, m, L_s, ldls, scalars, nullptr, desc->n, false, nullptr, nullptr, nullptr, 0, 0, 0, 0.0, loss_out,
+                       ws, S(stream));
+}
+
+static int svgp_predict(int likelihood, double nu, const char *who, const double *m, const double *L_s, int64_t ldls,
+                        const double *scalars, const double *At_test, int64_t ldat, const double *q_test, int64_t t, int64_t mdim,
+                        double *mean_out, double *var_out, double *obs_out, void *stream) {
+  PLS_REQUIRE(t > 0 && mdim > 0, "%s: bad sizes t=%lld m=%lld", who, (long long)t, (long long)mdim);
+  PLS_REQUIRE(mdim <= SVGP_M_MAX, "%s: %lld inducing points > %d are not supported", who, (long long)mdim, SVGP_M_MAX);
+  PLS_REQUIRE(svgp_tiles(t) <= 2147483647, "%s: t=%lld too large", who, (long long)t);
+  PLS_REQUIRE(m && L_s && scalars && At_test && q_test && mean_out && var_out, "%s: NULL pointer", who);
+  PLS_REQUIRE(ldls >= mdim && ldat >= mdim, "%s: ldls / ldat < m", who);
+  hipStream_t st = S(stream);
+  {
+    LaunchScope scope(PLS_TAG_OTHER, st);
+    int rc = PLS_OK;
+    switch (likelihood) {
+      case PLS_SVGP_BERNOULLI:
+        rc = svgp_launch_predict<PLS_SVGP_BERNOULLI>(m, L_s, ldls, scalars, At_test, ldat, q_test, t, mdim, mean_out, var_out, obs_out,
+                                                     nu, st);
+        break;
+      case PLS_SVGP_STUDENT_T:
+        rc = svgp_launch_predict<PLS_SVGP_STUDENT_T>(m, L_s, ldls, scalars, At_test, ldat, q_test, t, mdim, mean_out, var_out, obs_out,
+                                                     nu, st);
+        break;
+      default:
+        rc = svgp_launch_predict<PLS_SVGP_GAUSSIAN>(m, L_s, ldls, scalars, At_test, ldat, q_test, t, mdim, mean_out, var_out, obs_out,
+                                                    nu, st);
+    }
+    if (rc) return rc;
+  }
+  return check_launch("svgp_predict");
 }
 
 }  // namespace plship
@@ -390,67 +661,52 @@ size_t pls_svgp_workspace_bytes(int64_t n, int64_t m, int64_t batch) {
   return sizeof(double) * (value > grad ? value : grad);
 }
 
+// the Gaussian-only entries: the same bodies with the likelihood pinned
 int pls_svgp_elbo_grad(const pls_svgp_desc *desc, const double *m, const double *L_s, int64_t ldls, const double *scalars,
                        const int64_t *idx, int64_t b, double *out, double *grad_m, double *grad_L, int64_t ldgl,
                        void *workspace, size_t workspace_bytes, void *stream) {
   if (int rc = svgp_check_desc(desc, "svgp_elbo_grad")) return rc;
-  PLS_REQUIRE(m && L_s && scalars && out, "svgp_elbo_grad: NULL pointer");
-  PLS_REQUIRE(ldls >= desc->m, "svgp_elbo_grad: ldls < m");
-  PLS_REQUIRE(b > 0 && svgp_tiles(b) <= 2147483647, "svgp_elbo_grad: bad batch length %lld", (long long)b);
-  PLS_REQUIRE(idx || b <= desc->n, "svgp_elbo_grad: b=%lld > n=%lld without an index list", (long long)b, (long long)desc->n);
-  PLS_REQUIRE(!grad_L || ldgl >= desc->m, "svgp_elbo_grad: ldgl < m");
-  PLS_REQUIRE(workspace, "svgp_elbo_grad: NULL workspace");
-  const bool grad = grad_m || grad_L;
-  const size_t need = sizeof(double) * svgp_ws_doubles(svgp_tiles(b), svgp_mp(desc->m), grad);
-  if (workspace_bytes < need)
-    return fail(PLS_ERR_WORKSPACE_TOO_SMALL, "svgp_elbo_grad: workspace of %zu bytes, %zu needed", workspace_bytes, need);
-  PLS_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, "svgp_elbo_grad: workspace must be 8-byte aligned");
-  return svgp_evaluate(desc, const_cast<double *>(m), const_cast<double *>(L_s), ldls, const_cast<double *>(scalars), idx, b, grad,
-                       out, grad_m, grad_L, ldgl, 0, 0, 0.0, nullptr, static_cast<double *>(workspace), S(stream));
+  return svgp_elbo_grad(desc, SvgpLikArgs{0.0, 0.0}, "svgp_elbo_grad", m, L_s, ldls, scalars, idx, b, out, grad_m, grad_L, ldgl,
+                        workspace, workspace_bytes, stream);
 }
 
 int pls_svgp_sgd_epoch(const pls_svgp_desc *desc, double *m, double *L_s, int64_t ldls, double *scalars, const int64_t *perm,
                        int64_t batch_size, double lr, int32_t flags, double *loss_out, void *workspace, size_t workspace_bytes,
                        void *stream) {
   if (int rc = svgp_check_desc(desc, "svgp_sgd_epoch")) return rc;
-  PLS_REQUIRE(m && L_s && scalars && perm && loss_out, "svgp_sgd_epoch: NULL pointer");
-  PLS_REQUIRE(ldls >= desc->m, "svgp_sgd_epoch: ldls < m");
-  PLS_REQUIRE(batch_size > 0, "svgp_sgd_epoch: batch_size must be positive");
-  PLS_REQUIRE((flags & ~(PLS_SVGP_TRAIN_MEAN | PLS_SVGP_TRAIN_NOISE)) == 0, "svgp_sgd_epoch: unknown flag bits %d", flags);
-  PLS_REQUIRE(workspace, "svgp_sgd_epoch: NULL workspace");
-  const int64_t bs = batch_size < desc->n ? batch_size : desc->n;
-  const size_t need = pls_svgp_workspace_bytes(desc->n, desc->m, bs);
-  if (workspace_bytes < need)
-    return fail(PLS_ERR_WORKSPACE_TOO_SMALL, "svgp_sgd_epoch: workspace of %zu bytes, %zu needed", workspace_bytes, need);
-  PLS_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, "svgp_sgd_epoch: workspace must be 8-byte aligned");
-  double *ws = static_cast<double *>(workspace);
-  for (int64_t first = 0; first < desc->n; first += bs) {
-    const int64_t b = desc->n - first < bs ? desc->n - first : bs;
-    if (int rc = svgp_evaluate(desc, m, L_s, ldls, scalars, perm + first, b, true, nullptr, nullptr, nullptr, 0, 1, flags, lr,
-                               nullptr, ws, S(stream)))
-      return rc;
-  }
-  return svgp_evaluate(desc, m, L_s, ldls, scalars, nullptr, desc->n, false, nullptr, nullptr, nullptr, 0, 0, 0, 0.0, loss_out, ws,
-                       S(stream));
+  return svgp_sgd_epoch(desc, SvgpLikArgs{0.0, 0.0}, "svgp_sgd_epoch", m, L_s, ldls, scalars, perm, batch_size, lr, flags, loss_out,
+                        workspace, workspace_bytes, stream);
 }
 
 int pls_svgp_predict(const double *m, const double *L_s, int64_t ldls, const double *scalars, const double *At_test, int64_t ldat,
                      const double *q_test, int64_t t, int64_t mdim, double *mean_out, double *var_out, void *stream) {
-  PLS_REQUIRE(t > 0 && mdim > 0, "svgp_predict: bad sizes t=%lld m=%lld", (long long)t, (long long)mdim);
-  PLS_REQUIRE(mdim <= SVGP_M_MAX, "svgp_predict: %lld inducing points > %d are not supported", (long long)mdim, SVGP_M_MAX);
-  PLS_REQUIRE(svgp_tiles(t) <= 2147483647, "svgp_predict: t=%lld too large", (long long)t);
-  PLS_REQUIRE(m && L_s && scalars && At_test && q_test && mean_out && var_out, "svgp_predict: NULL pointer");
-  PLS_REQUIRE(ldls >= mdim && ldat >= mdim, "svgp_predict: ldls / ldat < m");
-  const int64_t mp = svgp_mp(mdim);
-  hipStream_t st = S(stream);
-  if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(svgp_predict_kernel), svgp_lds_bytes(SVGP_M_MAX), g_lds_predict))
-    return rc;
-  {
-    LaunchScope scope(PLS_TAG_OTHER, st);
-    hipLaunchKernelGGL(svgp_predict_kernel, dim3((unsigned)svgp_tiles(t)), dim3(256), svgp_lds_bytes(mp), st, At_test, ldat, q_test,
-                       t, (int)mdim, (int)mp, m, L_s, ldls, scalars, mean_out, var_out);
-  }
-  return check_launch("svgp_predict");
+  return svgp_predict(PLS_SVGP_GAUSSIAN, 0.0, "svgp_predict", m, L_s, ldls, scalars, At_test, ldat, q_test, t, mdim, mean_out,
+                      var_out, nullptr, stream);
+}
+
+int pls_svgp_lik_elbo_grad(const pls_svgp_lik_desc *desc, const double *m, const double *L_s, int64_t ldls, const double *scalars,
+                           const int64_t *idx, int64_t b, double *out, double *grad_m, double *grad_L, int64_t ldgl,
+                           void *workspace, size_t workspace_bytes, void *stream) {
+  if (int rc = svgp_check_lik_desc(desc, "svgp_lik_elbo_grad")) return rc;
+  return svgp_elbo_grad(&desc->base, svgp_lik_args(desc->base.likelihood, desc->deg_free), "svgp_lik_elbo_grad", m, L_s, ldls,
+                        scalars, idx, b, out, grad_m, grad_L, ldgl, workspace, workspace_bytes, stream);
+}
+
+int pls_svgp_lik_sgd_epoch(const pls_svgp_lik_desc *desc, double *m, double *L_s, int64_t ldls, double *scalars,
+                           const int64_t *perm, int64_t batch_size, double lr, int32_t flags, double *loss_out, void *workspace,
+                           size_t workspace_bytes, void *stream) {
+  if (int rc = svgp_check_lik_desc(desc, "svgp_lik_sgd_epoch")) return rc;
+  return svgp_sgd_epoch(&desc->base, svgp_lik_args(desc->base.likelihood, desc->deg_free), "svgp_lik_sgd_epoch", m, L_s, ldls,
+                        scalars, perm, batch_size, lr, flags, loss_out, workspace, workspace_bytes, stream);
+}
+
+int pls_svgp_lik_predict(const pls_svgp_lik_desc *desc, const double *m, const double *L_s, int64_t ldls, const double *scalars,
+                         const double *At_test, int64_t ldat, const double *q_test, int64_t t, int64_t mdim, double *mean_out,
+                         double *var_out, double *obs_out, void *stream) {
+  PLS_REQUIRE(desc, "svgp_lik_predict: NULL descriptor");
+  if (int rc = svgp_check_likelihood(desc->base.likelihood, desc->deg_free, "svgp_lik_predict")) return rc;
+  return svgp_predict(desc->base.likelihood, desc->deg_free, "svgp_lik_predict", m, L_s, ldls, scalars, At_test, ldat, q_test, t,
+                      mdim, mean_out, var_out, obs_out, stream);
 }
 
 }  // extern "C"

@@ -21,6 +21,7 @@ import torch
 from . import _lib as L
 from ._chol import CHOLESKY_JITTER, CHOLESKY_MAX_TRIES, NotPSDError, cholesky_factor
 from .kernel import ARDKernel, BaseKernel, MaternKernel, _dev
+from .likelihoods import GaussianLikelihood, _Likelihood
 from .trainers import EarlyStopper
 from .utils import set_seed
 
@@ -304,31 +305,43 @@ class SVGP:
     formulas; they are the contract).  Everything that depends on the kernel is computed once, in ``fit_data``; one
     evaluation is ``pls_svgp_elbo_grad``, one epoch ``pls_svgp_sgd_epoch``, a prediction ``pls_svgp_predict``.
 
+    ``likelihood``: ``"gaussian"`` or a likelihood object (likelihoods.py).  A ``BernoulliLikelihood`` (labels in {0, 1}, no
+    noise) or a ``StudentTLikelihood`` (fixed degrees of freedom, noise = softplus(rho) WITHOUT the 1e-4 floor) takes the
+    20-node Gauss-Hermite epilogue through ``pls_svgp_lik_elbo_grad`` / ``_sgd_epoch`` / ``_predict``; a
+    ``GaussianLikelihood`` is the closed-form path of ``"gaussian"``.
+
     ``kernel``: any kernel callable of the package (PLSKernel, ARDKernel, MaternKernel, LinearKernel).  ``noise``: the
-    starting likelihood noise (raw value 0 when None).  ``m`` starts at ``mean_init_std`` times standard normals from
+    starting likelihood noise (the likelihood object's own, else raw value 0, when None).  ``m`` starts at ``mean_init_std`` times standard normals from
     torch's global generator (drawn here, on the host), ``L_s`` at the identity."""
 
-    def __init__(self, kernel, x_induce: torch.Tensor, likelihood: str = "gaussian", noise: float | None = None,
+    def __init__(self, kernel, x_induce: torch.Tensor, likelihood: "str | _Likelihood" = "gaussian", noise: float | None = None,
                  mean_constant: float = 0.0, learn_inducing_locations: bool = False, jitter: float = SVGP_JITTER,
                  mean_init_std: float = 1e-3):
         if learn_inducing_locations:
             raise NotImplementedError("SVGP: learn_inducing_locations=True is not supported: the inducing points and the "
                                       "kernel are fixed (the reference's is_fixed=True); only the variational mean, the "
                                       "variational Cholesky factor, the constant mean and the noise are learned")
-        if likelihood != "gaussian":
+        if not isinstance(likelihood, _Likelihood) and likelihood != "gaussian":
             raise NotImplementedError(f"SVGP: likelihood {likelihood!r} is not supported: only 'gaussian' is "
-                                      "(Bernoulli and Student-t need a quadrature epilogue)")
+                                      "(Bernoulli and Student-t are likelihood OBJECTS: "
+                                      "BernoulliLikelihood(), StudentTLikelihood(deg_free))")
         z = x_induce.detach()
         self.x_induce = (z if z.dim() == 2 else z[:, None]).to(torch.float64)
         self.m = self.x_induce.shape[0]
         if not 1 <= self.m <= SVGP_M_MAX:
             raise ValueError(f"SVGP: {self.m} inducing points are not supported: 1 to {SVGP_M_MAX} are")
         self.kernel, self.jitter, self.likelihood = kernel, float(jitter), likelihood
+        self._lik = likelihood if isinstance(likelihood, _Likelihood) else GaussianLikelihood()
+        floor = self._lik.noise_floor
+        if noise is not None and floor is None:
+            raise AttributeError(f"SVGP: a {type(self._lik).__name__} has no noise to set")
+        if noise is None:
+            noise = self._lik.noise
         rho = 0.0
         if noise is not None:
-            if not float(noise) > NOISE_LOWER_BOUND:
-                raise ValueError(f"SVGP: the noise must exceed {NOISE_LOWER_BOUND}")
-            rho = float(_inverse_softplus(torch.tensor(float(noise) - NOISE_LOWER_BOUND, dtype=torch.float64)))
+            if not float(noise) > floor:
+                raise ValueError(f"SVGP: the noise must exceed {floor}")
+            rho = float(_inverse_softplus(torch.tensor(float(noise) - floor, dtype=torch.float64)))
         mean = torch.zeros(self.m, dtype=torch.float64)
         if mean_init_std:
             mean = float(mean_init_std) * torch.randn(self.m, dtype=torch.float64)
@@ -365,17 +378,29 @@ class SVGP:
     def fit_data(self, x: torch.Tensor, y: torch.Tensor) -> "SVGP":
         """The once-per-model setup: K_zz + jitter I = L L^T (retried with growing jitter as psd_safe_cholesky does;
         NotPSDError after the last attempt), At = (L^-1 k(Z, X))^T and q on the device."""
+        if self._lik.code == L.SVGP_BERNOULLI:
+            labels = torch.as_tensor(y).detach().reshape(-1)
+            if not bool(((labels == 0) | (labels == 1)).all()):
+                raise ValueError("SVGP: a BernoulliLikelihood needs labels in {0, 1}")
         st = self._state()
         xd = _dev(x if x.dim() == 2 else x[:, None])
         yd = _dev(y.reshape(-1))
         assert xd.shape[0] == yd.shape[0] and xd.shape[0] > 0, "x (n, d) and y (n) must share n > 0"
         self.n = xd.shape[0]
         at, q = self._whitened_rows(xd)
-        desc = L.SvgpDesc()
+        quadrature = self._lik.code != L.SVGP_GAUSSIAN
+        lik_desc = L.SvgpLikDesc()
+        lik_desc.deg_free = self._lik.deg_free
+        desc = lik_desc.base if quadrature else L.SvgpDesc()
         desc.At, desc.ldat, desc.q, desc.y = at.data_ptr(), at.stride(0), q.data_ptr(), yd.data_ptr()
-        desc.n, desc.m, desc.likelihood = self.n, self.m, L.SVGP_GAUSSIAN
-        st.update(At=at, q=q, y=yd, desc=desc, ws=None)
+        desc.n, desc.m, desc.likelihood = self.n, self.m, self._lik.code
+        st.update(At=at, q=q, y=yd, desc=lik_desc if quadrature else desc, ws=None)
         return self
+
+    def _entry(self, name: str):
+        """(the library entry ``pls_svgp[_lik]_<name>`` of this model's likelihood, its name)"""
+        full = f"pls_svgp_lik_{name}" if self._lik.code != L.SVGP_GAUSSIAN else f"pls_svgp_{name}"
+        return getattr(L.load(), full), full
 
     def _workspace(self, batch: int) -> torch.Tensor:
         st = self._state()
@@ -412,8 +437,12 @@ class SVGP:
 
     @property
     def noise(self) -> float:
+        """the likelihood's noise: softplus(rho) + 1e-4 (Gaussian), softplus(rho) (Student-t); Bernoulli has none"""
+        floor = self._lik.noise_floor
+        if floor is None:
+            raise AttributeError(f"SVGP: a {type(self._lik).__name__} has no noise")
         rho = self._state()["scalars"][1].cpu()
-        return NOISE_LOWER_BOUND + float(torch.clamp(rho, min=0.0) + torch.log1p(torch.exp(-rho.abs())))
+        return floor + float(torch.clamp(rho, min=0.0) + torch.log1p(torch.exp(-rho.abs())))
 
     # ---- the ELBO ---------------------------------------------------------------------------------------------------
     def evaluate_on_device(self, idx: torch.Tensor | None = None, gradients: bool = True
@@ -431,9 +460,10 @@ class SVGP:
         if gradients:
             gm = torch.empty(self.m, dtype=torch.float64, device=ws.device)
             gl = torch.zeros((self.m, self.m), dtype=torch.float64, device=ws.device)
-        L.check(L.load().pls_svgp_elbo_grad(ctypes.byref(st["desc"]), st["mean"].data_ptr(), st["Ls"].data_ptr(), L.ld(st["Ls"]),
-                                            st["scalars"].data_ptr(), L.ptr(idx), b, st["out"].data_ptr(), L.ptr(gm), L.ptr(gl),
-                                            self.m, ws.data_ptr(), ws.numel() * 8, L.stream_ptr()), "pls_svgp_elbo_grad")
+        fn, name = self._entry("elbo_grad")
+        L.check(fn(ctypes.byref(st["desc"]), st["mean"].data_ptr(), st["Ls"].data_ptr(), L.ld(st["Ls"]), st["scalars"].data_ptr(),
+                   L.ptr(idx), b, st["out"].data_ptr(), L.ptr(gm), L.ptr(gl), self.m, ws.data_ptr(), ws.numel() * 8,
+                   L.stream_ptr()), name)
         return st["out"], gm, gl
 
     def elbo_and_grad(self, idx: torch.Tensor | None = None) -> Tuple[float, dict]:
@@ -454,26 +484,43 @@ class SVGP:
         ws = self._workspace(min(int(batch_size), self.n))
         loss = torch.empty(1, dtype=torch.float64, device=ws.device)
         flags = (L.SVGP_TRAIN_MEAN if train_mean else 0) | (L.SVGP_TRAIN_NOISE if train_noise else 0)
-        L.check(L.load().pls_svgp_sgd_epoch(ctypes.byref(st["desc"]), st["mean"].data_ptr(), st["Ls"].data_ptr(), L.ld(st["Ls"]),
-                                            st["scalars"].data_ptr(), perm.data_ptr(), int(batch_size), float(learning_rate),
-                                            flags, loss.data_ptr(), ws.data_ptr(), ws.numel() * 8, L.stream_ptr()),
-                "pls_svgp_sgd_epoch")
+        fn, name = self._entry("sgd_epoch")
+        L.check(fn(ctypes.byref(st["desc"]), st["mean"].data_ptr(), st["Ls"].data_ptr(), L.ld(st["Ls"]), st["scalars"].data_ptr(),
+                   perm.data_ptr(), int(batch_size), float(learning_rate), flags, loss.data_ptr(), ws.data_ptr(), ws.numel() * 8,
+                   L.stream_ptr()), name)
         return loss
 
     # ---- prediction -------------------------------------------------------------------------------------------------
     def predict(self, x_test: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """(mean, latent variance, observation variance) at x_test (t, d), float64 on the device: c + a* . m,
-        q* + |L_s^T a*|^2 and that plus the noise."""
+        q* + |L_s^T a*|^2 and that plus the noise; with a Student-t likelihood the third is v + noise nu / (nu - 2), with a
+        Bernoulli likelihood p (1 - p) at p = Phi(mean / sqrt(1 + v)) (pls_svgp_lik_predict's obs_out)."""
         st = self._state()
         xt = _dev(x_test if x_test.dim() == 2 else x_test[:, None])
         at, q = self._whitened_rows(xt)
         t = xt.shape[0]
         mean = torch.empty(t, dtype=torch.float64, device=xt.device)
         var = torch.empty(t, dtype=torch.float64, device=xt.device)
+        if self._lik.code != L.SVGP_GAUSSIAN:
+            obs = torch.empty(t, dtype=torch.float64, device=xt.device)
+            desc = L.SvgpLikDesc()
+            desc.base.likelihood, desc.deg_free = self._lik.code, self._lik.deg_free
+            L.check(L.load().pls_svgp_lik_predict(ctypes.byref(desc), st["mean"].data_ptr(), st["Ls"].data_ptr(), L.ld(st["Ls"]),
+                                                  st["scalars"].data_ptr(), at.data_ptr(), at.stride(0), q.data_ptr(), t, self.m,
+                                                  mean.data_ptr(), var.data_ptr(), obs.data_ptr(), L.stream_ptr()),
+                    "pls_svgp_lik_predict")
+            return mean, var, obs
         L.check(L.load().pls_svgp_predict(st["mean"].data_ptr(), st["Ls"].data_ptr(), L.ld(st["Ls"]), st["scalars"].data_ptr(),
                                           at.data_ptr(), at.stride(0), q.data_ptr(), t, self.m, mean.data_ptr(), var.data_ptr(),
                                           L.stream_ptr()), "pls_svgp_predict")
         return mean, var, var + self.noise
+
+    def predict_proba(self, x_test: torch.Tensor) -> torch.Tensor:
+        """p(y = 1) at x_test under a BernoulliLikelihood: Phi(mean / sqrt(1 + latent variance)), float64 on the device"""
+        if self._lik.code != L.SVGP_BERNOULLI:
+            raise AttributeError("SVGP: predict_proba exists for a BernoulliLikelihood only")
+        mean, var, _ = self.predict(x_test)
+        return torch.special.ndtr(mean / torch.sqrt(1.0 + var))
 
 
 #: gpytorch's DirichletClassificationLikelihood: the Dirichlet concentration of a class that was not observed

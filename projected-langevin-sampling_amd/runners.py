@@ -260,11 +260,11 @@ def train_pls_runner(
 def train_svgp_runner(x: torch.Tensor, y: torch.Tensor, x_induce: torch.Tensor, kernel, seed: int, number_of_epochs: int,
                       batch_size: int, learning_rate_upper: float, learning_rate_lower: float,
                       number_of_learning_rate_searches: int, early_stopper_patience: float,
-                      observation_noise: float | None = None, train_noise: bool = True):
+                      observation_noise: float | None = None, train_noise: bool = True, likelihood=None):
     """The learning-rate search of experiments/runners.py:449-542 with ``is_fixed=True``, without its files and plots:
     ``number_of_learning_rate_searches`` log-spaced rates from the lower to the upper bound, ``set_seed(seed)`` before each
     candidate, candidates that returned None skipped, the best by its LAST loss kept.  Returns (model, losses,
-    best_learning_rate); (None, None, None) when no candidate survived."""
+    best_learning_rate); (None, None, None) when no candidate survived.  ``likelihood``: as in ``train_svgp``."""
     import math
 
     from .trainers import train_svgp
@@ -275,7 +275,8 @@ def train_svgp_runner(x: torch.Tensor, y: torch.Tensor, x_induce: torch.Tensor, 
                                      number_of_learning_rate_searches):
         set_seed(seed)
         model, losses = train_svgp(x, y, x_induce, kernel, seed, number_of_epochs, batch_size, float(learning_rate),
-                                   early_stopper_patience, likelihood_noise=observation_noise, train_noise=train_noise)
+                                   early_stopper_patience, likelihood_noise=observation_noise, train_noise=train_noise,
+                                   likelihood=likelihood)
         if model is None or not losses:
             continue
         if losses[-1] < best_loss:

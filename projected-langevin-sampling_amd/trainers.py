@@ -382,12 +382,15 @@ def epoch_batches(n: int, batch_size: int) -> List[torch.Tensor]:
 def train_svgp(x: torch.Tensor, y: torch.Tensor, x_induce: torch.Tensor, kernel, seed: int, number_of_epochs: int,
                batch_size: int, learning_rate: float, early_stopper_patience: float, likelihood_noise: float | None = None,
                learn_inducing_locations: bool = False, learn_kernel_parameters: bool = False, train_noise: bool = True,
-               mean_init_std: float = 1e-3):
+               mean_init_std: float = 1e-3, likelihood=None):
     """experiments/trainers.py:55-136 with ``is_fixed=True`` (what every driver of the reference runs): seed, the model, and per
     epoch every minibatch SGD step on loss = -ELBO followed by the full-data loss -- ONE library call (pls_svgp_sgd_epoch)
     and one host read --, the early-stopper check before the loss is recorded.  Returns (model, losses); (None, None) when
     a loss is not finite or k(Z, Z) stays non-PSD (the reference's ``except ValueError``).  ``train_noise=False`` freezes
-    the likelihood noise (train_svgp_for_profiler, experiments/profiler/main.py:106-107)."""
+    the likelihood noise (train_svgp_for_profiler, experiments/profiler/main.py:106-107).  ``likelihood``: None (Gaussian) or
+    a likelihood object, as the drivers pass ``BernoulliLikelihood()`` and a ``StudentTLikelihood``; ``likelihood_noise``
+    with a Bernoulli likelihood raises AttributeError (the reference sets ``likelihood.noise``), with a Student-t one it is
+    the starting scale^2."""
     from ._chol import NotPSDError
     from .gaussian_process import SVGP
     from .utils import set_seed
@@ -396,8 +399,8 @@ def train_svgp(x: torch.Tensor, y: torch.Tensor, x_induce: torch.Tensor, kernel,
         raise NotImplementedError("train_svgp: learn_kernel_parameters=True is not supported: the kernel and the inducing "
                                   "points are fixed (the reference's is_fixed=True)")
     set_seed(seed)
-    model = SVGP(kernel, x_induce, noise=likelihood_noise, learn_inducing_locations=learn_inducing_locations,
-                 mean_init_std=mean_init_std)
+    model = SVGP(kernel, x_induce, likelihood="gaussian" if likelihood is None else likelihood, noise=likelihood_noise,
+                 learn_inducing_locations=learn_inducing_locations, mean_init_std=mean_init_std)
     try:
         model.fit_data(x, y)
     except NotPSDError as e:
