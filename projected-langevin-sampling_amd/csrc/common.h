@@ -7,6 +7,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/plship.h"
@@ -82,8 +83,37 @@ inline int ensure_dynamic_lds(const void *kernel, size_t bytes, std::atomic<uint
   return PLS_OK;
 }
 
+// The one owner of that mask: a function-local static per kernel.  Every launcher of a kernel with dynamic LDS calls this
+// before it launches.  (Slot: a second, larger request for the same kernel keeps a mask of its own -- the diagnostic pad of
+// launch_gemm_cfg.)
+template <auto Kernel, int Slot = 0>
+inline int ensure_lds(size_t bytes) {
+  static std::atomic<uint64_t> done{0};
+  return ensure_dynamic_lds(reinterpret_cast<const void *>(Kernel), bytes, done);
+}
+
+// LDS bytes of the two double-buffered operand tiles behind a BI x BJ output tile, BK deep (gemm_tn_mainloop's layout)
+constexpr size_t gemm_tile_lds_bytes(int BI, int BJ, int BK) { return (size_t)2 * BK * ((BI + 16) + (BJ + 16)) * sizeof(double); }
+
 static inline hipStream_t S(void *stream) { return reinterpret_cast<hipStream_t>(stream); }
 __host__ __device__ static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// The small-rank kernels are instantiated per number KB = 1..8 of 16-function rank blocks: f(integral_constant<KB>) for a rank
+// up to 128, the error of the launcher `who` above it.
+template <class F>
+inline int for_rank_blocks(const char *who, int rank, F &&f) {
+  switch ((int)cdiv(rank, 16)) {
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 3: return f(std::integral_constant<int, 3>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    case 5: return f(std::integral_constant<int, 5>{});
+    case 6: return f(std::integral_constant<int, 6>{});
+    case 7: return f(std::integral_constant<int, 7>{});
+    case 8: return f(std::integral_constant<int, 8>{});
+    default: return fail(PLS_ERR_INVALID_ARGUMENT, "%s: rank %d > 128", who, rank);
+  }
+}
 
 }  // namespace plship

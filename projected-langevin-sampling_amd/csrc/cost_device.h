@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <type_traits>
 
 #include "fmath.h"
 
@@ -38,6 +39,22 @@ __host__ inline CostP make_costp(const pls_cost_desc *d) {
     c.mm_is2 = 1.0 / s2;
   }
   return c;
+}
+
+// THE list of the (cost, link) pairs with kernel instantiations of their own (the pairs the reference's experiments use):
+// f(integral_constant<COST>, integral_constant<LINK>) for one of them, f(-1, -1) -- the instantiation that switches at run
+// time -- for every other pair.  Every launcher that dispatches on the pair goes through here.
+template <class F>
+__host__ inline int for_cost_link(const CostP &cp, F &&f) {
+  using std::integral_constant;
+  const int c = cp.cost, l = cp.link;
+  if (c == PLS_COST_GAUSSIAN && l == PLS_LINK_IDENTITY) return f(integral_constant<int, PLS_COST_GAUSSIAN>{}, integral_constant<int, PLS_LINK_IDENTITY>{});
+  if (c == PLS_COST_POISSON && l == PLS_LINK_SQUARE) return f(integral_constant<int, PLS_COST_POISSON>{}, integral_constant<int, PLS_LINK_SQUARE>{});
+  if (c == PLS_COST_BERNOULLI && l == PLS_LINK_SIGMOID) return f(integral_constant<int, PLS_COST_BERNOULLI>{}, integral_constant<int, PLS_LINK_SIGMOID>{});
+  if (c == PLS_COST_BERNOULLI && l == PLS_LINK_PROBIT) return f(integral_constant<int, PLS_COST_BERNOULLI>{}, integral_constant<int, PLS_LINK_PROBIT>{});
+  if (c == PLS_COST_STUDENT_T && l == PLS_LINK_IDENTITY) return f(integral_constant<int, PLS_COST_STUDENT_T>{}, integral_constant<int, PLS_LINK_IDENTITY>{});
+  if (c == PLS_COST_MULTIMODAL && l == PLS_LINK_IDENTITY) return f(integral_constant<int, PLS_COST_MULTIMODAL>{}, integral_constant<int, PLS_LINK_IDENTITY>{});
+  return f(integral_constant<int, -1>{}, integral_constant<int, -1>{});
 }
 
 __device__ inline double clipd(double v, double lo, double hi) { return fmin(fmax(v, lo), hi); }

@@ -16,17 +16,15 @@ template <int BI, int BJ, int WI, int WJ, class Epi, int MINW = ((BI >= 128) ? 2
 static int launch_gemm_cfg(GemmShape g, const Epi &epi, hipStream_t st) {
   constexpr int BK = 16;  // MINW: waves per SIMD the register allocation must leave room for
   constexpr int NT = (BI / WI) * (BJ / WJ) * 64;
-  constexpr size_t lds_bytes = (size_t)2 * BK * ((BI + 16) + (BJ + 16)) * sizeof(double);
-  auto kern = gemm_tn_f64_kernel<BI, BJ, WI, WJ, BK, MINW, Epi>;
-  static std::atomic<uint64_t> lds_ready{0};
-  if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(kern), lds_bytes, lds_ready)) return rc;
+  constexpr size_t lds_bytes = gemm_tile_lds_bytes(BI, BJ, BK);
+  constexpr auto kern = gemm_tn_f64_kernel<BI, BJ, WI, WJ, BK, MINW, Epi>;
+  if (int rc = ensure_lds<kern>(lds_bytes)) return rc;
 #ifdef PLS_STAMP
   g.stamps = g_stamp_buffer;
   // diagnostic build only: PLS_STAMP_LDS_PAD=<bytes> of extra dynamic LDS (e.g. 90000: one workgroup per CU)
   static const size_t pad = getenv("PLS_STAMP_LDS_PAD") ? (size_t)atol(getenv("PLS_STAMP_LDS_PAD")) : 0;
-  static std::atomic<uint64_t> pad_ready{0};
   if (pad)
-    if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(kern), lds_bytes + pad, pad_ready)) return rc;
+    if (int rc = ensure_lds<kern, 1>(lds_bytes + pad)) return rc;
   const size_t lds_launch = lds_bytes + pad;
 #else
   const size_t lds_launch = lds_bytes;

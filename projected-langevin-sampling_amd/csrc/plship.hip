@@ -7,6 +7,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
+#include <optional>
 #include <string>
 #include <vector>
 
@@ -577,9 +578,8 @@ template <int KG, class Epi>
 static int launch_gemm_kg(GemmShape g, const Epi &epi, hipStream_t st) {
   using G = KgGeom<KG>;
   constexpr size_t lds_bytes = (size_t)G::LDS_DOUBLES * sizeof(double);
-  auto kern = gemm_tn_f64_kg_kernel<KG, Epi>;
-  static std::atomic<uint64_t> lds_ready{0};
-  if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(kern), lds_bytes, lds_ready)) return rc;
+  constexpr auto kern = gemm_tn_f64_kg_kernel<KG, Epi>;
+  if (int rc = ensure_lds<kern>(lds_bytes)) return rc;
   g.nti = (int)cdiv(g.I, 64);
   g.ntj = (int)cdiv(g.J, 64);
 #ifdef PLS_STAMP
@@ -617,9 +617,8 @@ template <class Epi>
 static int launch_gemm_kg_tri(GemmShape g, const Epi &epi, const TriScratch &sc, hipStream_t st) {
   using G = KgGeom<2>;
   constexpr size_t lds_bytes = (size_t)G::LDS_DOUBLES * sizeof(double);
-  auto kern = gemm_tn_f64_kg_tri_kernel<Epi>;
-  static std::atomic<uint64_t> lds_ready{0};
-  if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(kern), lds_bytes, lds_ready)) return rc;
+  constexpr auto kern = gemm_tn_f64_kg_tri_kernel<Epi>;
+  if (int rc = ensure_lds<kern>(lds_bytes)) return rc;
   g.nti = (int)cdiv(g.I, 64);
   g.ntj = (int)cdiv(g.J, 64);
   g.tri_flags = static_cast<unsigned *>(sc.ptr);
@@ -666,9 +665,8 @@ static bool gemm_rows_ok(const double *L, int64_t ldl, const double *R, int64_t 
 static int launch_gemm_rows(const double *L, int64_t ldl, const double *R, int64_t ldr, int64_t I, int64_t J, int64_t K,
                             const EpiStore &e, hipStream_t st, int64_t kchunk) {
   GemmShape g{L, ldl, R, ldr, I, J, K, 0, 0, kchunk, 0};
-  constexpr size_t lds_bytes = (size_t)2 * 16 * ((128 + 16) + (128 + 16)) * sizeof(double);
-  static std::atomic<uint64_t> lds_ready{0};
-  if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(gemm_tn_f64_rows_kernel), lds_bytes, lds_ready)) return rc;
+  constexpr size_t lds_bytes = gemm_tile_lds_bytes(128, 128, 16);
+  if (int rc = ensure_lds<gemm_tn_f64_rows_kernel>(lds_bytes)) return rc;
   g.nti = (int)cdiv(I, 128);
   g.ntj = (int)cdiv(J, 128);
   const int tile_rows = 16 * (int)cdiv(cdiv(I, 16), g.nti);  // equal heights: 160 rows are 80 + 80, 129 are 80 + 49
@@ -980,9 +978,8 @@ __global__ __launch_bounds__(256, 2) void wino_products_kernel(GemmShape g, EpiS
 // P_p (mh x jh, ld jh) = L_p^T R_p over K paired rows, beta = 0: write, 1: accumulate (the chunks after the first)
 static int launch_wino_products(const WinoProducts &t, int64_t mh, int64_t jh, int64_t K, int64_t kchunk, double *P, int64_t slab,
                                 double beta, hipStream_t st) {
-  constexpr size_t lds_bytes = (size_t)2 * 16 * ((128 + 16) + (128 + 16)) * sizeof(double);
-  static std::atomic<uint64_t> lds_ready{0};
-  if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(wino_products_kernel), lds_bytes, lds_ready)) return rc;
+  constexpr size_t lds_bytes = gemm_tile_lds_bytes(128, 128, 16);
+  if (int rc = ensure_lds<wino_products_kernel>(lds_bytes)) return rc;
   GemmShape g{nullptr, 0, nullptr, jh, mh, jh, K, 0, 0, kchunk, 0};
   g.nti = (int)cdiv(mh, 128);
   g.ntj = (int)cdiv(jh, 128);
@@ -1550,6 +1547,69 @@ __global__ __launch_bounds__(CV_BLOCK) void cv_update_kernel(int kind, const dou
 static unsigned rows_grid(int64_t items) { return (unsigned)(items < 1 ? 1 : (items > 1024 ? 1024 : items)); }
 
 // ---------------------------------------------------------------------------------------------------------------
+// named launches of the HBM-bound kernels: a kernel's grid formula, its timeline tag and its check_launch name in ONE place
+// (launch_chunk_sums / launch_sums16 and launch_gaussian_energy_finish follow their kernels and FastOp further down)
+// ---------------------------------------------------------------------------------------------------------------
+
+// The prior of one basis over the m rows of P (ldp), as the energy reduction and the update take it:
+//   ONB: P = U,      energy + 1/2 sum_m P_mj^2 / lam_m,  drift P_mj / lam_m
+//   IPB: P = K^-1 U, energy + (M/2) sum_m P_mj^2,        drift M P_mj
+enum class Prior : int { None = 0, Onb = 1, Ipb = 2 };  // (the values column_reduce_kernel switches on)
+struct PriorTerm {
+  Prior kind = Prior::None;
+  const double *P = nullptr;
+  int64_t ldp = 0, m = 0;
+  const double *lam = nullptr;
+  double scale = 0.0;  // IPB: M/2 (the energy's factor; the drift's is twice that)
+};
+static PriorTerm onb_prior(const double *U, int64_t ldu, const pls_onb_desc *b) { return PriorTerm{Prior::Onb, U, ldu, b->mk, b->lam, 0.0}; }
+static PriorTerm ipb_prior(const double *V, int64_t j, const pls_ipb_desc *b) {
+  return PriorTerm{Prior::Ipb, V, j, b->m, nullptr, 0.5 * (double)b->m};
+}
+
+struct PartialRows {  // n rows of J partial sums each (leading dimension J)
+  const double *p;
+  int64_t n;
+};
+
+enum class Timed { No, Yes };  // Yes: the launch records itself in the timeline (LaunchScope)
+
+// out[col] = (accumulate ? out[col] : 0) + the column sums of the partial rows + the prior term
+static int launch_column_reduce(PartialRows part, int64_t j, double *out, bool accumulate, const PriorTerm &prior, hipStream_t st,
+                                Timed timed = Timed::No) {
+  std::optional<LaunchScope> scope;
+  if (timed == Timed::Yes) scope.emplace(PLS_TAG_OTHER, st);
+  hipLaunchKernelGGL(column_reduce_kernel, dim3((unsigned)cdiv(j, 256)), dim3(256), 0, st, part.p, j, part.n, j, out,
+                     accumulate ? 1 : 0, (int)prior.kind, prior.P, prior.ldp, prior.m, prior.lam, prior.scale, 1.0,
+                     (const double *)nullptr);
+  scope.reset();
+  return check_launch("column_reduce");
+}
+
+// The data drift of an update: D (ldd) in nslab split-K slabs, slab_stride doubles apart [- dsub_scale * dsub[row]]
+struct DriftSlabs {
+  const double *D;
+  int64_t ldd;
+  int nslab;
+  int64_t slab_stride;
+  const double *dsub = nullptr;
+  double dsub_scale = 0.0;
+};
+
+// out (ldo) = [U +] -eta (data drift + prior drift) + sqrt(2 eta) noise over the prior's m rows (add_u: the step's out_mode)
+static int launch_langevin_update(double *out, int64_t ldo, int add_u, const double *U, int64_t ldu, const DriftSlabs &d,
+                                  const PriorTerm &prior, int64_t j, const EtaP &etap, const NoiseP &nz, hipStream_t st,
+                                  Timed timed = Timed::No) {
+  std::optional<LaunchScope> scope;
+  if (timed == Timed::Yes) scope.emplace(PLS_TAG_LANGEVIN_UPDATE, st);
+  hipLaunchKernelGGL(langevin_update_kernel, dim3((unsigned)cdiv(j, 256), rows_grid(cdiv(prior.m, 8) * 4)), dim3(256), 0, st, out,
+                     ldo, U, ldu, d.D, d.ldd, d.nslab, d.slab_stride, prior.P, prior.ldp, prior.lam,
+                     prior.kind == Prior::Ipb ? 2.0 * prior.scale : 0.0, prior.m, j, etap, add_u, nz, d.dsub, d.dsub_scale);
+  scope.reset();
+  return check_launch("langevin_update");
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // shared host helpers for the fused paths
 // ---------------------------------------------------------------------------------------------------------------
 static int validate_cost(const pls_cost_desc *c) {
@@ -1605,22 +1665,34 @@ struct EnergySink {
   double *partial = nullptr;  // [rows_cap][j] workspace for per-wave-row (or per-slab) cost partial sums
   int64_t rows_cap = 0;
   double *e = nullptr;  // (j,) receives cost_j + prior_j
-  int prior_kind = 0;
-  const double *P = nullptr;  // prior operand (U for the ONB, V = K^-1 U for the IPB)
-  int64_t ldp = 0, m = 0;
-  const double *lam = nullptr;
-  double scale = 0.0;
+  PriorTerm prior;      // (U for the ONB, V = K^-1 U for the IPB)
 };
 
-static int stream_drift(const double *Lf, int64_t ldlf, const double *Lb, int64_t ldlb, int64_t kdim, int64_t n,
-                        const double *V, int64_t ldv, int64_t j, const CostP &cp, const double *y, double *D,
-                        int64_t ldd, int64_t max_slabs, int64_t slab_stride, int64_t *slabs_used, double *Gbuf,
-                        int64_t n_chunk, hipStream_t st, const EnergySink *es = nullptr) {
-  auto reduce_partials = [&](int64_t rows, int accumulate, bool last) {
-    hipLaunchKernelGGL(column_reduce_kernel, dim3((unsigned)cdiv(j, 256)), dim3(256), 0, st, es->partial, j, rows, j, es->e,
-                       accumulate, last ? es->prior_kind : 0, es->P, es->ldp, es->m, es->lam, es->scale, 1.0,
-                       (const double *)nullptr);
-    return check_launch("column_reduce");
+// The operands of the streaming loops, named as in the comment above; y: the N targets
+struct StreamOperands {
+  const double *Lf;
+  int64_t ldlf;
+  const double *Lb;
+  int64_t ldlb;
+  int64_t kdim, n;
+  const double *V;
+  int64_t ldv, j;
+  const double *y;
+};
+static StreamOperands onb_operands(const pls_onb_desc *b, const double *U, int64_t ldu, int64_t j, const double *y) {
+  return StreamOperands{b->A, b->lda, b->At, b->ldat, b->mk, b->n, U, ldu, j, y};
+}
+static StreamOperands ipb_operands(const pls_ipb_desc *b, const double *V, int64_t j, const double *y) {
+  return StreamOperands{b->Kzx, b->ldkzx, b->Kxz, b->ldkxz, b->m, b->n, V, j, j, y};
+}
+
+static int stream_drift(const StreamOperands &o, const CostP &cp, double *D, int64_t ldd, int64_t max_slabs, int64_t slab_stride,
+                        int64_t *slabs_used, double *Gbuf, int64_t n_chunk, hipStream_t st, const EnergySink *es = nullptr) {
+  const double *Lf = o.Lf, *Lb = o.Lb, *V = o.V, *y = o.y;
+  const int64_t ldlf = o.ldlf, ldlb = o.ldlb, kdim = o.kdim, n = o.n, ldv = o.ldv, j = o.j;
+  // (the prior term enters with the last chunk's partial rows)
+  auto reduce_partials = [&](int64_t rows, bool accumulate, bool last) {
+    return launch_column_reduce({es->partial, rows}, j, es->e, accumulate, last ? es->prior : PriorTerm{}, st);
   };
   if (small_rank_ok(Lb, ldlb, kdim)) {  // few basis functions: G stays in registers (small_rank.h)
     int64_t rows_per_split = 0;
@@ -1630,7 +1702,7 @@ static int stream_drift(const double *Lf, int64_t ldlf, const double *Lb, int64_
       *slabs_used = ns;
       int rc = es ? launch_small_rank_drift_value(p, ns, st) : launch_small_rank_drift(p, ns, st);
       if (rc || !es) return rc;
-      return reduce_partials(ns, 0, true);
+      return reduce_partials(ns, false, true);
     }
   }
   // one split-K plan for every chunk (slab s accumulates over the chunks; the update kernel sums the slabs)
@@ -1656,7 +1728,7 @@ static int stream_drift(const double *Lf, int64_t ldlf, const double *Lb, int64_
     rc = launch_cost_deriv_gemm(Lf + r0, ldlf, V, ldv, rows, j, kdim, Gbuf, j, y + r0, cp, vp, j, st);
     if (rc) return rc;
     if (es) {
-      rc = reduce_partials(wave_rows, c == 0 ? 0 : 1, r0 + n_chunk >= n);
+      rc = reduce_partials(wave_rows, c != 0, r0 + n_chunk >= n);
       if (rc) return rc;
     }
     // slab s accumulates rows [s * kchunk, (s + 1) * kchunk) of every chunk; the first chunk has the planned row count,
@@ -1698,10 +1770,10 @@ static int stream_drift(const double *Lf, int64_t ldlf, const double *Lb, int64_
 }
 
 // c_j partials over N chunks -> cost_out[j] (deterministic)
-static int stream_cost(const double *Lf, int64_t ldlf, const double *Lb, int64_t ldlb, int64_t kdim, int64_t n,
-                       const double *V, int64_t ldv, int64_t j, const CostP &cp, const double *y, double *partial,
-                       int64_t partial_rows, int64_t n_chunk, double *e_out, int prior_kind, const double *P, int64_t ldp,
-                       int64_t m, const double *lam, double scale, hipStream_t st) {
+static int stream_cost(const StreamOperands &o, const CostP &cp, double *partial, int64_t partial_rows, int64_t n_chunk,
+                       double *e_out, const PriorTerm &prior, hipStream_t st) {
+  const double *Lf = o.Lf, *Lb = o.Lb, *V = o.V, *y = o.y;
+  const int64_t ldlf = o.ldlf, ldlb = o.ldlb, kdim = o.kdim, n = o.n, ldv = o.ldv, j = o.j;
   if (Lb && small_rank_ok(Lb, ldlb, kdim)) {  // few basis functions: one fused pass, F never written
     int64_t rows_per_split = 0;
     const int64_t ns = small_rank_splits(j, n, &rows_per_split);
@@ -1709,9 +1781,7 @@ static int stream_cost(const double *Lf, int64_t ldlf, const double *Lb, int64_t
       SmallRankP p{Lb, ldlb, V, ldv, y, n, j, (int)kdim, rows_per_split, partial, j, j, cp, nullptr, 0};
       int rc = launch_small_rank_value(p, ns, st);
       if (rc) return rc;
-      hipLaunchKernelGGL(column_reduce_kernel, dim3((unsigned)cdiv(j, 256)), dim3(256), 0, st, partial, j, ns, j, e_out, 0,
-                         prior_kind, P, ldp, m, lam, scale, 1.0, (const double *)nullptr);
-      return check_launch("column_reduce");
+      return launch_column_reduce({partial, ns}, j, e_out, false, prior, st);
     }
   }
   int64_t nchunks = cdiv(n, n_chunk);
@@ -1720,10 +1790,7 @@ static int stream_cost(const double *Lf, int64_t ldlf, const double *Lb, int64_t
     int rc = launch_cost_value_gemm(Lf + r0, ldlf, V, ldv, rows, j, kdim, partial, j, y + r0, cp, st);
     if (rc) return rc;
     const bool last = (c == nchunks - 1);
-    hipLaunchKernelGGL(column_reduce_kernel, dim3((unsigned)cdiv(j, 256)), dim3(256), 0, st, partial, j,
-                       cost_value_partial_rows(rows, j), j, e_out, c == 0 ? 0 : 1, last ? prior_kind : 0, P, ldp, m,
-                       lam, scale, 1.0, (const double *)nullptr);
-    rc = check_launch("column_reduce");
+    rc = launch_column_reduce({partial, cost_value_partial_rows(rows, j)}, j, e_out, c != 0, last ? prior : PriorTerm{}, st);
     if (rc) return rc;
   }
   return PLS_OK;
@@ -1785,6 +1852,16 @@ __global__ __launch_bounds__(256) void sums16_kernel(const double *__restrict__ 
   out[b] = s;
 }
 
+static int launch_chunk_sums(const double *e, int64_t j, double *out, hipStream_t st) {
+  hipLaunchKernelGGL(chunk_sums_kernel, dim3((unsigned)cdiv(j, 256)), dim3(256), 0, st, e, j, out);
+  return check_launch("chunk_sums");
+}
+
+static int launch_sums16(const double *e, int64_t j, double *out, hipStream_t st) {
+  hipLaunchKernelGGL(sums16_kernel, dim3((unsigned)cdiv(cdiv(j, 16), 256)), dim3(256), 0, st, e, j, out);
+  return check_launch("sums16");
+}
+
 }  // namespace plship
 
 using namespace plship;
@@ -1801,6 +1878,13 @@ struct FastOp {
   double inv_noise, yscale;
   const double *yty;
 };
+
+// e[col] = the column sums of the partial rows + op.yscale * *op.yty;  sums (optional): the 256-column chunk sums of e
+static int launch_gaussian_energy_finish(PartialRows part, int64_t j, double *e, const FastOp &op, double *sums, hipStream_t st) {
+  hipLaunchKernelGGL(gaussian_energy_finish_kernel, dim3((unsigned)cdiv(j, 256)), dim3(256), 0, st, part.p, j, part.n, j, e,
+                     op.yscale, op.yty, sums);
+  return check_launch("gaussian_energy_finish");
+}
 
 // LAGGED energies of a training loop (pls_block_desc.energy_partials ...): launch k leaves only the partial rows of its energy
 // by-product; launch k + 1 finishes them at its START (EpiLangevinGaussian::Prev), under the landing of its first operand
@@ -1845,11 +1929,8 @@ static int fast_step_launch(const FastOp &op, const double *U, int64_t ldu, int6
   // pls_energy_partials_bytes sizes it for -- and a launch that writes fewer zeroes the rest, so that whoever finishes it adds
   // the same rows whatever either launch chose.
   const int64_t lag_rows = gaussian_partial_rows(op.mk, true, true);
-  if (lag.flush) {  // no step: the partial rows of the LAST launch of a loop are finished by the finishing kernel
-    hipLaunchKernelGGL(gaussian_energy_finish_kernel, dim3((unsigned)cdiv(j, 256)), dim3(256), 0, st, lag.partials_prev, j, lag_rows, j,
-                       lag.e_prev, op.yscale, op.yty, lag.sums_prev);
-    return check_launch("gaussian_energy_finish");
-  }
+  if (lag.flush)  // no step: the partial rows of the LAST launch of a loop are finished by the finishing kernel
+    return launch_gaussian_energy_finish({lag.partials_prev, lag_rows}, j, lag.e_prev, op, lag.sums_prev, st);
   double *epart = lag.partials_out;
   if (energy_in && !epart) {
     if (!workspace || workspace_bytes < gaussian_partial_bytes(parts, j))
@@ -1866,9 +1947,7 @@ static int fast_step_launch(const FastOp &op, const double *U, int64_t ldu, int6
     e.fin = EpiLangevinGaussian::Finish{esync, energy_in, esums, op.yscale, op.yty, (int)parts, (int)cdiv(op.mk, big ? 128 : 64)};
   int rc = launch_gemm_any(op.B, op.ldb, U, ldu, op.mk, j, op.mk, e, st);
   if (rc || lagged || !energy_in || fused_finish) return rc;
-  hipLaunchKernelGGL(gaussian_energy_finish_kernel, dim3((unsigned)cdiv(j, 256)), dim3(256), 0, st, epart, j, parts, j,
-                     energy_in, op.yscale, op.yty, esums);
-  return check_launch("gaussian_energy_finish");
+  return launch_gaussian_energy_finish({epart, parts}, j, energy_in, op, esums, st);
 }
 
 // e_j = (inv_noise / 2) u^T B u - inv_noise c^T u + sum_i u_i^2 / (2 lam_i) + yscale * yty: one contraction, reduced per
@@ -1897,9 +1976,7 @@ static int fast_energy_launch(const FastOp &op, const double *U, int64_t ldu, in
     rc = launch_gemm_cfg<64, 64, 32, 32>(g, ep, st);
   }
   if (rc) return rc;
-  hipLaunchKernelGGL(gaussian_energy_finish_kernel, dim3((unsigned)cdiv(j, 256)), dim3(256), 0, st, partial, j, parts, j, e,
-                     op.yscale, op.yty, (double *)nullptr);
-  return check_launch("gaussian_energy_finish");
+  return launch_gaussian_energy_finish({partial, parts}, j, e, op, nullptr, st);
 }
 
 
@@ -2094,15 +2171,13 @@ int pls_block_means(const double *e, int64_t j, int64_t block_cols, double *out,
 int pls_sums16(const double *e, int64_t j, double *out, void *stream) {
   PLS_REQUIRE(e && out && j >= 0, "sums16: bad arguments");
   if (j == 0) return PLS_OK;
-  hipLaunchKernelGGL(sums16_kernel, dim3((unsigned)cdiv(cdiv(j, 16), 256)), dim3(256), 0, S(stream), e, j, out);
-  return check_launch("sums16");
+  return launch_sums16(e, j, out, S(stream));
 }
 
 int pls_chunk_sums(const double *e, int64_t j, double *out, void *stream) {
   PLS_REQUIRE(e && out && j >= 0, "chunk_sums: bad arguments");
   if (j == 0) return PLS_OK;
-  hipLaunchKernelGGL(chunk_sums_kernel, dim3((unsigned)cdiv(j, 256)), dim3(256), 0, S(stream), e, j, out);
-  return check_launch("chunk_sums");
+  return launch_chunk_sums(e, j, out, S(stream));
 }
 
 int pls_cost_derivative(const pls_cost_desc *cost, const double *F, int64_t ldf, const double *y, int64_t n, int64_t j,
@@ -2141,9 +2216,7 @@ int pls_cost_value(const pls_cost_desc *cost, const double *F, int64_t ldf, cons
     rc = check_launch("cost_value_partial");
     if (rc) return rc;
   }
-  hipLaunchKernelGGL(column_reduce_kernel, dim3((unsigned)cdiv(j, 256)), dim3(256), 0, S(stream), partial, j, nparts, j, c,
-                     0, 0, (const double *)nullptr, (int64_t)0, (int64_t)0, (const double *)nullptr, 0.0, 1.0, (const double *)nullptr);
-  return check_launch("column_reduce");
+  return launch_column_reduce({partial, nparts}, j, c, false, PriorTerm{}, S(stream));
 }
 
 int pls_link_transform(int32_t link, double jitter, const double *in, int64_t ldin, int64_t rows, int64_t cols,
@@ -2184,8 +2257,7 @@ int pls_row_quantiles(const double *samples, int64_t lds, int64_t rows, int64_t 
   int npad = 2;
   while (npad < cols) npad <<= 1;
   const size_t bytes = (size_t)npad * sizeof(double);
-  static std::atomic<uint64_t> lds_ready{0};
-  if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(row_quantiles_kernel), 16384 * sizeof(double), lds_ready)) return rc;
+  if (int rc = ensure_lds<row_quantiles_kernel>(16384 * sizeof(double))) return rc;
   hipLaunchKernelGGL(row_quantiles_kernel, dim3((unsigned)rows), dim3(256), bytes, S(stream), samples, lds, cols, npad, q, (int)nq,
                      out, ldout);
   return check_launch("row_quantiles");
@@ -2265,10 +2337,8 @@ int pls_onb_particle_update(const pls_onb_desc *basis, const double *U, int64_t 
   // D = A G into dU, then dU = -eta*D - eta*U/lam + sqrt(2 eta) xi in place (element-wise, race free)
   rc = pls_gemm_tn(basis->At, basis->ldat, G, ldg, dU, lddu, basis->mk, j, basis->n, 1.0, 0.0, stream);
   if (rc) return rc;
-  hipLaunchKernelGGL(langevin_update_kernel, dim3((unsigned)cdiv(j, 256), rows_grid(cdiv(basis->mk, 8) * 4)), dim3(256), 0,
-                     S(stream), dU, lddu, U, ldu, dU, lddu, 1, (int64_t)0, U, ldu, basis->lam, 0.0, basis->mk, j,
-                     make_etap(eta, nullptr), 0, make_noisep(noise));
-  return check_launch("langevin_update");
+  return launch_langevin_update(dU, lddu, 0, U, ldu, DriftSlabs{dU, lddu, 1, 0}, onb_prior(U, ldu, basis), j, make_etap(eta, nullptr),
+                                make_noisep(noise), S(stream));
 }
 
 // ---- one step call: its arguments, its validation and its route -------------------------------------------------------
@@ -2422,23 +2492,16 @@ static int sr_step_launch(const SrStepOperands &basis, const SrStepLayout &L, co
 // caller who asked for the sums gets them whatever route the descriptor and the options select.
 static int finish_energy_sums(const pls_block_desc *blocks, const double *energy_in, int64_t j, hipStream_t st) {
   if (!blocks || !energy_in) return PLS_OK;
-  if (blocks->energy_sums) {
-    hipLaunchKernelGGL(chunk_sums_kernel, dim3((unsigned)cdiv(j, 256)), dim3(256), 0, st, energy_in, j, blocks->energy_sums);
-    if (int rc = check_launch("chunk_sums")) return rc;
-  }
-  if (blocks->energy_sums16) {
-    hipLaunchKernelGGL(sums16_kernel, dim3((unsigned)cdiv(cdiv(j, 16), 256)), dim3(256), 0, st, energy_in, j, blocks->energy_sums16);
-    if (int rc = check_launch("sums16")) return rc;
-  }
-  return PLS_OK;
+  if (blocks->energy_sums)
+    if (int rc = launch_chunk_sums(energy_in, j, blocks->energy_sums, st)) return rc;
+  return blocks->energy_sums16 ? launch_sums16(energy_in, j, blocks->energy_sums16, st) : PLS_OK;
 }
 
 // pls_block_desc.energy_sums16 on the routes that finish energy_in themselves (the Gaussian/identity fast paths; not with lagged
 // energies, whose values arrive one launch later)
 static int finish_sums16(const pls_block_desc *blocks, const double *energy_in, int64_t j, hipStream_t st) {
   if (!blocks || !energy_in || !blocks->energy_sums16 || blocks->energy_partials) return PLS_OK;
-  hipLaunchKernelGGL(sums16_kernel, dim3((unsigned)cdiv(cdiv(j, 16), 256)), dim3(256), 0, st, energy_in, j, blocks->energy_sums16);
-  return check_launch("sums16");
+  return launch_sums16(energy_in, j, blocks->energy_sums16, st);
 }
 
 // the Gaussian/identity fast path's step of either basis (operator `op`), then the 16-column sums its caller asked for
@@ -2509,29 +2572,20 @@ static int onb_general_step(const pls_onb_desc *basis, const StepCall &c) {
   char *w = static_cast<char *>(c.workspace);
   double *D = reinterpret_cast<double *>(w + L.d_off);
   const int64_t slab_stride = (int64_t)(L.mj / sizeof(double));
+  const PriorTerm prior = onb_prior(c.U, c.ldu, basis);
   EnergySink sink;
   if (c.energy_in) {  // e_j = cost_j(F(U)) + 1/2 sum_m U_mj^2 / lam_m of the INPUT particles (orthonormal.py:120-125)
     sink.partial = reinterpret_cast<double *>(w + L.part_off);
     sink.rows_cap = L.part_rows;
     sink.e = c.energy_in;
-    sink.prior_kind = 1;
-    sink.P = c.U;
-    sink.ldp = c.ldu;
-    sink.m = basis->mk;
-    sink.lam = basis->lam;
+    sink.prior = prior;
   }
   int64_t nslab = 1;
-  int rc = stream_drift(basis->A, basis->lda, basis->At, basis->ldat, basis->mk, basis->n, c.U, c.ldu, c.j, make_costp(c.cost),
-                        c.y, D, c.j, L.slabs, slab_stride, &nslab, reinterpret_cast<double *>(w + L.g_off), L.n_chunk, c.st,
-                        c.energy_in ? &sink : nullptr);
+  int rc = stream_drift(onb_operands(basis, c.U, c.ldu, c.j, c.y), make_costp(c.cost), D, c.j, L.slabs, slab_stride, &nslab,
+                        reinterpret_cast<double *>(w + L.g_off), L.n_chunk, c.st, c.energy_in ? &sink : nullptr);
   if (rc) return rc;
-  {
-    LaunchScope scope(PLS_TAG_LANGEVIN_UPDATE, c.st);
-    hipLaunchKernelGGL(langevin_update_kernel, dim3((unsigned)cdiv(c.j, 256), rows_grid(cdiv(basis->mk, 8) * 4)), dim3(256), 0,
-                       c.st, c.out, c.ldo, c.U, c.ldu, D, c.j, (int)nslab, slab_stride, c.U, c.ldu, basis->lam, 0.0, basis->mk,
-                       c.j, c.etap(), c.out_mode, c.noisep());
-  }
-  rc = check_launch("langevin_update");
+  rc = launch_langevin_update(c.out, c.ldo, c.out_mode, c.U, c.ldu, DriftSlabs{D, c.j, (int)nslab, slab_stride}, prior, c.j, c.etap(),
+                              c.noisep(), c.st, Timed::Yes);
   if (rc) return rc;
   return finish_energy_sums(c.blocks, c.energy_in, c.j, c.st);
 }
@@ -2558,11 +2612,9 @@ static int onb_wino_step(const pls_onb_desc *basis, const StepCall &c, const Win
                                   c.energy_in ? part : nullptr, c.j, c.st);
     if (rc) return rc;
     if (c.energy_in) {  // e_j = cost_j(F(U)) + 1/2 sum_m U_mj^2 / lam_m of the INPUT particles, as on the general route
-      LaunchScope scope(PLS_TAG_OTHER, c.st);
-      hipLaunchKernelGGL(column_reduce_kernel, dim3((unsigned)cdiv(c.j, 256)), dim3(256), 0, c.st, part, c.j, cdiv(rows, 32), c.j,
-                         c.energy_in, ci == 0 ? 0 : 1, p0 + L.n_chunk >= nh ? 1 : 0, c.U, c.ldu, mk, basis->lam, 0.0, 1.0,
-                         (const double *)nullptr);
-      if ((rc = check_launch("column_reduce"))) return rc;
+      rc = launch_column_reduce({part, cdiv(rows, 32)}, c.j, c.energy_in, ci != 0,
+                                p0 + L.n_chunk >= nh ? onb_prior(c.U, c.ldu, basis) : PriorTerm{}, c.st, Timed::Yes);
+      if (rc) return rc;
     }
     const double *S1 = S + p0 * mh, *S2 = S1 + splane, *S3 = S2 + splane, *S4 = S3 + splane;
     const double *A11 = At + p0 * ldat, *A12 = At + (nh + p0) * ldat, *A22 = A12 + mh;
@@ -2682,9 +2734,9 @@ int pls_onb_energy(const pls_onb_desc *basis, const pls_cost_desc *cost, const d
   const EnergyLayout L = energy_plan(0, basis->mk, basis->n, j, workspace_bytes);
   if (!workspace || L.part_rows < 2)
     return fail(PLS_ERR_WORKSPACE_TOO_SMALL, "onb_energy: workspace %zu bytes too small", workspace_bytes);
-  return stream_cost(basis->A, basis->lda, basis->At, basis->ldat, basis->mk, basis->n, U, ldu, j, make_costp(cost), y,
-                     reinterpret_cast<double *>(static_cast<char *>(workspace) + L.part_off), L.part_rows, L.n_chunk, e, 1, U,
-                     ldu, basis->mk, basis->lam, 0.0, S(stream));
+  return stream_cost(onb_operands(basis, U, ldu, j, y), make_costp(cost),
+                     reinterpret_cast<double *>(static_cast<char *>(workspace) + L.part_off), L.part_rows, L.n_chunk, e,
+                     onb_prior(U, ldu, basis), S(stream));
 }
 
 int pls_onb_prior_energy(const pls_onb_desc *basis, const double *U, int64_t ldu, int64_t j, const double *cost,
@@ -2693,9 +2745,7 @@ int pls_onb_prior_energy(const pls_onb_desc *basis, const double *U, int64_t ldu
   if (rc) return rc;
   PLS_REQUIRE(U && e && j >= 0 && ldu >= j, "onb_prior_energy: bad arguments");
   if (j == 0) return PLS_OK;
-  hipLaunchKernelGGL(column_reduce_kernel, dim3((unsigned)cdiv(j, 256)), dim3(256), 0, S(stream), cost, j,
-                     (int64_t)(cost ? 1 : 0), j, e, 0, 1, U, ldu, basis->mk, basis->lam, 0.0, 1.0, (const double *)nullptr);
-  return check_launch("column_reduce");
+  return launch_column_reduce({cost, cost ? 1 : 0}, j, e, false, onb_prior(U, ldu, basis), S(stream));
 }
 
 // ---- inducing-point basis ---------------------------------------------------------------------------------------
@@ -2793,10 +2843,8 @@ static int ipb_finish(const pls_ipb_desc *basis, const double *U, int64_t ldu, c
                       const pls_block_desc *blocks = nullptr) {
   NoiseP nz = make_noisep(noise, blocks);
   if (int rc = ipb_colour_noise(basis, nz, j, xi_buf, e_buf, st)) return rc;
-  hipLaunchKernelGGL(langevin_update_kernel, dim3((unsigned)cdiv(j, 256), rows_grid(cdiv(basis->m, 8) * 4)), dim3(256), 0, st,
-                     out, ldo, U, ldu, D, j, nslab, slab_stride, V, j, (const double *)nullptr, (double)basis->m, basis->m, j,
-                     make_etap(eta, blocks), add_u, nz, dsub, dsub_scale);
-  return check_launch("langevin_update");
+  return launch_langevin_update(out, ldo, add_u, U, ldu, DriftSlabs{D, j, nslab, slab_stride, dsub, dsub_scale}, ipb_prior(V, j, basis), j,
+                                make_etap(eta, blocks), nz, st);
 }
 
 // Gaussian/identity constants of the inducing-point basis: B = Kzx Kxz (M x M), c[0..M) = Kzx y, c[M] = y^T y.
@@ -2953,16 +3001,11 @@ static int ipb_general_route(const pls_ipb_desc *basis, const StepCall &c, const
     sink.partial = reinterpret_cast<double *>(w + L.part_off);
     sink.rows_cap = L.part_rows;
     sink.e = c.energy_in;
-    sink.prior_kind = 2;
-    sink.P = V;
-    sink.ldp = c.j;
-    sink.m = basis->m;
-    sink.scale = 0.5 * (double)basis->m;
+    sink.prior = ipb_prior(V, c.j, basis);
   }
   int64_t nslab = 1;
-  rc = stream_drift(basis->Kzx, basis->ldkzx, basis->Kxz, basis->ldkxz, basis->m, basis->n, V, c.j, c.j, make_costp(c.cost), c.y,
-                    D, c.j, L.slabs, slab_stride, &nslab, reinterpret_cast<double *>(w + L.g_off), L.n_chunk, c.st,
-                    c.energy_in ? &sink : nullptr);
+  rc = stream_drift(ipb_operands(basis, V, c.j, c.y), make_costp(c.cost), D, c.j, L.slabs, slab_stride, &nslab,
+                    reinterpret_cast<double *>(w + L.g_off), L.n_chunk, c.st, c.energy_in ? &sink : nullptr);
   if (rc) return rc;
   rc = ipb_finish(basis, c.U, c.ldu, D, (int)nslab, slab_stride, V, c.j, c.eta, c.noise, c.out, c.ldo, c.out_mode, xi, e, c.st,
                   nullptr, 0.0, c.blocks);
@@ -3058,8 +3101,8 @@ int pls_ipb_energy(const pls_ipb_desc *basis, const pls_cost_desc *cost, const d
   }
   rc = ipb_apply_kinv(basis, U, ldu, j, V, stream);
   if (rc) return rc;
-  return stream_cost(basis->Kzx, basis->ldkzx, basis->Kxz, basis->ldkxz, basis->m, basis->n, V, j, j, make_costp(cost), y,
-                     partial, L.part_rows, L.n_chunk, e, 2, V, j, basis->m, nullptr, 0.5 * (double)basis->m, S(stream));
+  return stream_cost(ipb_operands(basis, V, j, y), make_costp(cost), partial, L.part_rows, L.n_chunk, e, ipb_prior(V, j, basis),
+                     S(stream));
 }
 
 int pls_ipb_prior_energy(const pls_ipb_desc *basis, const double *U, int64_t ldu, int64_t j, const double *cost,
@@ -3074,10 +3117,7 @@ int pls_ipb_prior_energy(const pls_ipb_desc *basis, const double *U, int64_t ldu
   double *V = static_cast<double *>(workspace);
   rc = ipb_apply_kinv(basis, U, ldu, j, V, stream);
   if (rc) return rc;
-  hipLaunchKernelGGL(column_reduce_kernel, dim3((unsigned)cdiv(j, 256)), dim3(256), 0, S(stream), cost, j,
-                     (int64_t)(cost ? 1 : 0), j, e, 0, 2, (const double *)V, j, basis->m, (const double *)nullptr,
-                     0.5 * (double)basis->m, 1.0, (const double *)nullptr);
-  return check_launch("column_reduce");
+  return launch_column_reduce({cost, cost ? 1 : 0}, j, e, false, ipb_prior(V, j, basis), S(stream));
 }
 
 // ---- whitened coordinates of the inducing-point basis (see ipb_whitened_ok above) ------------------------------------

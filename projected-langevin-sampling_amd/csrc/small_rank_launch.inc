@@ -8,43 +8,23 @@ namespace plship {
 
 template <int MODE, int COST, int LINK>
 static int launch_small_rank_cl(const SmallRankP &p, int64_t nsplit, hipStream_t st) {
-  const int kb = (int)cdiv(p.K, 16);
   dim3 grid((unsigned)cdiv(p.J, 64), (unsigned)nsplit);
   LaunchScope scope(MODE == SR_MODE_VALUE ? PLS_TAG_SMALL_RANK_VALUE : PLS_TAG_SMALL_RANK_DRIFT, st);
-#define PLS_SR_CASE(KB)                                                                                               \
-  case KB: {                                                                                                          \
-    static std::atomic<uint64_t> lds_ready{0};                                                                        \
-    if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(&small_rank_kernel<KB, MODE, COST, LINK>),         \
-                                    sr_lds_bytes<KB>(), lds_ready))                                                   \
-      return rc;                                                                                                      \
-    hipLaunchKernelGGL((small_rank_kernel<KB, MODE, COST, LINK>), grid, dim3(256), sr_lds_bytes<KB>(), st, p);       \
-  } break;
-  switch (kb) {
-    PLS_SR_CASE(1)
-    PLS_SR_CASE(2)
-    PLS_SR_CASE(3)
-    PLS_SR_CASE(4)
-    PLS_SR_CASE(5)
-    PLS_SR_CASE(6)
-    PLS_SR_CASE(7)
-    PLS_SR_CASE(8)
-    default: return fail(PLS_ERR_INVALID_ARGUMENT, "small_rank: rank %d > 128", p.K);
-  }
-#undef PLS_SR_CASE
-  return check_launch("small_rank");
+  const int rc = for_rank_blocks("small_rank", p.K, [&](auto kb) -> int {
+    constexpr int KB = decltype(kb)::value;
+    if (int rc = ensure_lds<small_rank_kernel<KB, MODE, COST, LINK>>(sr_lds_bytes<KB>())) return rc;
+    hipLaunchKernelGGL((small_rank_kernel<KB, MODE, COST, LINK>), grid, dim3(256), sr_lds_bytes<KB>(), st, p);
+    return PLS_OK;
+  });
+  return rc ? rc : check_launch("small_rank");
 }
 
-// the cost/link pairs the reference's experiments use get their own instantiation; anything else the run-time switch
+// one instantiation per (cost, link) pair of for_cost_link's list (cost_device.h)
 template <int MODE>
 static int launch_small_rank(const SmallRankP &p, int64_t nsplit, hipStream_t st) {
-  const int c = p.cp.cost, l = p.cp.link;
-  if (c == PLS_COST_GAUSSIAN && l == PLS_LINK_IDENTITY) return launch_small_rank_cl<MODE, PLS_COST_GAUSSIAN, PLS_LINK_IDENTITY>(p, nsplit, st);
-  if (c == PLS_COST_POISSON && l == PLS_LINK_SQUARE) return launch_small_rank_cl<MODE, PLS_COST_POISSON, PLS_LINK_SQUARE>(p, nsplit, st);
-  if (c == PLS_COST_BERNOULLI && l == PLS_LINK_SIGMOID) return launch_small_rank_cl<MODE, PLS_COST_BERNOULLI, PLS_LINK_SIGMOID>(p, nsplit, st);
-  if (c == PLS_COST_BERNOULLI && l == PLS_LINK_PROBIT) return launch_small_rank_cl<MODE, PLS_COST_BERNOULLI, PLS_LINK_PROBIT>(p, nsplit, st);
-  if (c == PLS_COST_STUDENT_T && l == PLS_LINK_IDENTITY) return launch_small_rank_cl<MODE, PLS_COST_STUDENT_T, PLS_LINK_IDENTITY>(p, nsplit, st);
-  if (c == PLS_COST_MULTIMODAL && l == PLS_LINK_IDENTITY) return launch_small_rank_cl<MODE, PLS_COST_MULTIMODAL, PLS_LINK_IDENTITY>(p, nsplit, st);
-  return launch_small_rank_cl<MODE, -1, -1>(p, nsplit, st);
+  return for_cost_link(p.cp, [&](auto c, auto l) {
+    return launch_small_rank_cl<MODE, decltype(c)::value, decltype(l)::value>(p, nsplit, st);
+  });
 }
 
 }  // namespace plship

@@ -470,26 +470,20 @@ __global__ __launch_bounds__(256) void svgp_predict_kernel(const double *__restr
   }
 }
 
-static std::atomic<uint64_t> g_lds_batch[3][2] = {}, g_lds_predict[3] = {};
+// f(integral_constant<LIK>) for the likelihood of a validated descriptor: the one switch over the kernels' LIK parameter
+template <class F>
+static int for_likelihood(int likelihood, F &&f) {
+  switch (likelihood) {
+    case PLS_SVGP_BERNOULLI: return f(std::integral_constant<int, PLS_SVGP_BERNOULLI>{});
+    case PLS_SVGP_STUDENT_T: return f(std::integral_constant<int, PLS_SVGP_STUDENT_T>{});
+    default: return f(std::integral_constant<int, PLS_SVGP_GAUSSIAN>{});
+  }
+}
 
 template <int LIK, bool GRAD>
 static int svgp_launch_batch(const SvgpBatchArgs &ba, int64_t tiles, size_t lds, hipStream_t st) {
-  auto kern = svgp_batch_kernel<LIK, GRAD>;
-  if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(kern), svgp_lds_bytes(SVGP_M_MAX), g_lds_batch[LIK][GRAD ? 1 : 0]))
-    return rc;
-  hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(256), lds, st, ba);
-  return PLS_OK;
-}
-
-template <int LIK>
-static int svgp_launch_predict(const double *m, const double *Ls, int64_t ldls, const double *scalars, const double *At, int64_t ldat,
-                               const double *q, int64_t t, int64_t mdim, double *mean_out, double *var_out, double *obs_out, double nu,
-                               hipStream_t st) {
-  const int64_t mp = svgp_mp(mdim);
-  auto kern = svgp_predict_kernel<LIK>;
-  if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(kern), svgp_lds_bytes(SVGP_M_MAX), g_lds_predict[LIK])) return rc;
-  hipLaunchKernelGGL(kern, dim3((unsigned)svgp_tiles(t)), dim3(256), svgp_lds_bytes(mp), st, At, ldat, q, t, (int)mdim, (int)mp, m, Ls,
-                     ldls, scalars, mean_out, var_out, obs_out, nu);
+  if (int rc = ensure_lds<svgp_batch_kernel<LIK, GRAD>>(svgp_lds_bytes(SVGP_M_MAX))) return rc;
+  hipLaunchKernelGGL((svgp_batch_kernel<LIK, GRAD>), dim3((unsigned)tiles), dim3(256), lds, st, ba);
   return PLS_OK;
 }
 
@@ -516,20 +510,10 @@ static int svgp_evaluate(const pls_svgp_desc *d, const SvgpLikArgs &lik, double 
   const size_t lds = svgp_lds_bytes(mp);
   {
     LaunchScope scope(PLS_TAG_OTHER, st);
-    int rc = PLS_OK;
-    switch (d->likelihood) {
-      case PLS_SVGP_BERNOULLI:
-        rc = grad ? svgp_launch_batch<PLS_SVGP_BERNOULLI, true>(ba, tiles, lds, st)
-                  : svgp_launch_batch<PLS_SVGP_BERNOULLI, false>(ba, tiles, lds, st);
-        break;
-      case PLS_SVGP_STUDENT_T:
-        rc = grad ? svgp_launch_batch<PLS_SVGP_STUDENT_T, true>(ba, tiles, lds, st)
-                  : svgp_launch_batch<PLS_SVGP_STUDENT_T, false>(ba, tiles, lds, st);
-        break;
-      default:
-        rc = grad ? svgp_launch_batch<PLS_SVGP_GAUSSIAN, true>(ba, tiles, lds, st)
-                  : svgp_launch_batch<PLS_SVGP_GAUSSIAN, false>(ba, tiles, lds, st);
-    }
+    const int rc = for_likelihood(d->likelihood, [&](auto tag) {
+      constexpr int LIK = decltype(tag)::value;
+      return grad ? svgp_launch_batch<LIK, true>(ba, tiles, lds, st) : svgp_launch_batch<LIK, false>(ba, tiles, lds, st);
+    });
     if (rc) return rc;
   }
   if (int rc = check_launch("svgp_batch")) return rc;
@@ -627,22 +611,16 @@ static int svgp_predict(int likelihood, double nu, const char *who, const double
   PLS_REQUIRE(m && L_s && scalars && At_test && q_test && mean_out && var_out, "%s: NULL pointer", who);
   PLS_REQUIRE(ldls >= mdim && ldat >= mdim, "%s: ldls / ldat < m", who);
   hipStream_t st = S(stream);
+  const int64_t mp = svgp_mp(mdim);
   {
     LaunchScope scope(PLS_TAG_OTHER, st);
-    int rc = PLS_OK;
-    switch (likelihood) {
-      case PLS_SVGP_BERNOULLI:
-        rc = svgp_launch_predict<PLS_SVGP_BERNOULLI>(m, L_s, ldls, scalars, At_test, ldat, q_test, t, mdim, mean_out, var_out, obs_out,
-                                                     nu, st);
-        break;
-      case PLS_SVGP_STUDENT_T:
-        rc = svgp_launch_predict<PLS_SVGP_STUDENT_T>(m, L_s, ldls, scalars, At_test, ldat, q_test, t, mdim, mean_out, var_out, obs_out,
-                                                     nu, st);
-        break;
-      default:
-        rc = svgp_launch_predict<PLS_SVGP_GAUSSIAN>(m, L_s, ldls, scalars, At_test, ldat, q_test, t, mdim, mean_out, var_out, obs_out,
-                                                    nu, st);
-    }
+    const int rc = for_likelihood(likelihood, [&](auto tag) -> int {
+      constexpr int LIK = decltype(tag)::value;
+      if (int rc = ensure_lds<svgp_predict_kernel<LIK>>(svgp_lds_bytes(SVGP_M_MAX))) return rc;
+      hipLaunchKernelGGL((svgp_predict_kernel<LIK>), dim3((unsigned)svgp_tiles(t)), dim3(256), svgp_lds_bytes(mp), st, At_test, ldat,
+                         q_test, t, (int)mdim, (int)mp, m, L_s, ldls, scalars, mean_out, var_out, obs_out, nu);
+      return PLS_OK;
+    });
     if (rc) return rc;
   }
   return check_launch("svgp_predict");

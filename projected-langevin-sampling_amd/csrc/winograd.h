@@ -190,10 +190,9 @@ __global__ __launch_bounds__(256, 2) void gemm_paired_kernel(GemmShape g, Epi ep
 template <class Epi>
 static int launch_gemm_paired(const double *Lf, int64_t ldlf, int64_t pair_i, const double *V, int64_t ldv, int64_t pair_j,
                               int64_t rows, int64_t K, const Epi &epi, hipStream_t st) {
-  constexpr size_t lds_bytes = (size_t)2 * 16 * ((128 + 16) + (128 + 16)) * sizeof(double);
-  auto kern = gemm_paired_kernel<Epi>;
-  static std::atomic<uint64_t> lds_ready{0};
-  if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(kern), lds_bytes, lds_ready)) return rc;
+  constexpr size_t lds_bytes = gemm_tile_lds_bytes(128, 128, 16);
+  constexpr auto kern = gemm_paired_kernel<Epi>;
+  if (int rc = ensure_lds<kern>(lds_bytes)) return rc;
   GemmShape g{Lf, ldlf, V, ldv, rows, pair_j, K, 0, 0, 0, 0};
   g.pair_i = pair_i;
   g.pair_j = pair_j;
