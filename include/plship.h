@@ -509,6 +509,26 @@ int pls_kernel_grad_sums(int32_t kernel_kind, const double *x, int64_t n, int64_
                          double outputscale, const double *alpha, const double *P, int64_t ldp,
                          double *out /* d + 1, device */, void *workspace, size_t workspace_bytes, void *stream);
 
+/* The exact-GP predictive mean at t test points WITHOUT the n x t cross-Gram matrix: replaces the mean of
+ * model(experiment_data.train.x) at experiments/uci/regression/main.py:231 (every subsample GP predicts at all N training
+ * points for estimate_student_parameters, :109-125; the variance that gpytorch computes beside it is thrown away there).
+ * With kappa the kernel WITHOUT its outputscale s, evaluated entry for entry as pls_kernel_gram evaluates it:
+ *   out[i] = mean + s * sum_j kappa(xt_i, x_j; lengthscale) alpha[j]                 i < t,  j < n
+ * A pair whose exponential underflows contributes exactly 0; a pair at distance 0 contributes alpha[j] (kappa = 1 for
+ * every kind, Matern-1/2 included: 1/t is never formed).  PLS_KERNEL_LINEAR is rejected; d <= 64.
+ * x (n x d) and xt (t x d) row-major contiguous, alpha (n), out (t): device memory.  x is read 16 bytes per lane where it
+ * is 16-byte aligned, xt where it is 16-byte aligned and d is even; one double per lane otherwise (the same bits).
+ * Summation order (no atomics, no workspace): a workgroup owns 64 test points, one per lane; wave w of its four adds
+ * the terms of the training points j = w, w + 4, w + 8, ... in ascending order into one accumulator per thread (there
+ * is no cross-lane sum, so no butterfly); the four waves' sums are added as (w0 + w1) + (w2 + w3); then
+ * out[i] = fma(s, sum, mean).  The split of j depends on j alone -- not on t, n, d or the position of the point in
+ * the batch -- so out[i] is a function of xt_i and the model: a batch can be split anywhere and gives the same bits
+ * (as pls_softmax_normal_mean), and two calls give the same bits.
+ * t == 0 returns PLS_OK and launches nothing; n >= 1.  Nothing synchronises or allocates. */
+int pls_kernel_mean(int32_t kernel_kind, const double *x, int64_t n, int64_t d, const double *lengthscale,
+                    double outputscale, double mean, const double *alpha, const double *xt, int64_t t,
+                    double *out /* t, device */, void *stream);
+
 /* One evaluation of the exact-GP marginal log-likelihood and its gradient: replaces mll(model(x), y) and
  * loss.backward() at experiments/trainers.py:45-49 (gpytorch ExactMarginalLogLikelihood, GaussianLikelihood,
  * ConstantMean, one output).  With K_y = s kappa(x, x) + (noise + jitter) I = Lc Lc^T, r = y - mean, alpha = K_y^-1 r

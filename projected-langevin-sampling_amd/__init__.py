@@ -4,8 +4,10 @@ jswu18/projected-langevin-sampling behind the reference's PLS / basis / cost / l
 All numerics run in libplship.so (hand-written HIP for gfx950, see csrc/); this package is the thin host
 side: it owns device memory through torch tensors and calls the C ABI (include/plship.h) with raw pointers."""
 from . import _lib
+from .conformalise import ConformaliseGP, ConformalisePLS, ConformalPrediction, gaussian_interval
 from .gaussian_process import (SVGP, DirichletExactGP, ExactGP, construct_average_ard_kernel, construct_average_gaussian_noise,
-                               dirichlet_targets, exact_gp_runner, nearest_subsample, softmax_normal_mean, train_exact_gp)
+                               dirichlet_targets, estimate_student_parameters, exact_gp_runner, fit_student_t, nearest_subsample,
+                               softmax_normal_mean, train_exact_gp)
 from .kernel import ARDKernel, LinearKernel, MaternKernel, PLSKernel
 from .likelihoods import BernoulliLikelihood, GaussianLikelihood, StudentTLikelihood
 from .projected_langevin_sampling import PLS
@@ -17,4 +19,5 @@ __all__ = ["PLS", "PLSKernel", "ARDKernel", "MaternKernel", "LinearKernel", "Ear
            "DirichletExactGP", "dirichlet_targets", "softmax_normal_mean",
            "train_exact_gp", "exact_gp_runner", "construct_average_ard_kernel", "construct_average_gaussian_noise",
            "nearest_subsample", "SVGP", "train_svgp", "train_svgp_runner", "epoch_batches", "TemperGP", "GaussianLikelihood",
-           "BernoulliLikelihood", "StudentTLikelihood", "_lib"]
+           "BernoulliLikelihood", "StudentTLikelihood", "fit_student_t", "estimate_student_parameters", "ConformaliseGP",
+           "ConformalisePLS", "ConformalPrediction", "gaussian_interval", "_lib"]

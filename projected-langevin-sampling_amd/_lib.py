@@ -215,6 +215,7 @@ SIGNATURES = {
     "pls_ipb_step_blocks": (C.c_int, [_ID, _CD, _P, _P, _I64, _I64, _BD, _ND, _P, _I64, _I32, _I32, _P, _P, _SZ, _P]),
     "pls_kernel_grad_sums_workspace_bytes": (_SZ, [_I64, _I64]),
     "pls_kernel_grad_sums": (C.c_int, [_I32, _P, _I64, _I64, _P, _D, _P, _P, _I64, _P, _P, _SZ, _P]),
+    "pls_kernel_mean": (C.c_int, [_I32, _P, _I64, _I64, _P, _D, _D, _P, _P, _I64, _P, _P]),
     "pls_gp_mll_workspace_bytes": (_SZ, [_I64, _I64]),
     "pls_gp_mll_grad": (C.c_int, [_I32, _P, _I64, _I64, _P, _D, _D, _D, _D, _P, _P, _P, _P, _SZ, _P]),
     "pls_gp_mll_classes_workspace_bytes": (_SZ, [_I64, _I64, _I64]),

@@ -1,4 +1,5 @@
-"""Conformal prediction intervals (drop-in for src/conformalise/base.py:9-160 and src/conformalise/pls.py:8-62).
+"""Conformal prediction intervals (drop-in for src/conformalise/base.py:9-160, src/conformalise/pls.py:8-62 and
+src/conformalise/gp.py:12-64).
 
 The per-test-point quantiles over the J particles are the J-reduction of this wrapper; they run as one LDS sort per
 test point (pls_row_quantiles).  On a J-sharded run every rank predicts its own particles' samples, the rows (test points)
@@ -14,6 +15,7 @@ import torch
 
 from . import _ops
 from .kernel import _dev
+from .likelihoods import GaussianLikelihood, StudentTLikelihood
 from .projected_langevin_sampling import PLS
 
 
@@ -25,31 +27,20 @@ class ConformalPrediction:
     upper: torch.Tensor
 
 
-class ConformalisePLS:
-    """conformalise/pls.py:8-62 on top of conformalise/base.py:19-160 (https://arxiv.org/abs/2107.07511)."""
+class _ConformaliseBase:
+    """conformalise/base.py:19-160 (https://arxiv.org/abs/2107.07511): what does not depend on the model.  A subclass
+    provides ``_predict_uncalibrated_coverage(coverage, x) -> (lower, upper)`` and ``predict_median(x)``, device vectors."""
 
-    def __init__(self, x_calibration: torch.Tensor, y_calibration: torch.Tensor, pls: PLS, particles: torch.Tensor, group=None):
-        self.pls = pls
-        self.particles = particles
-        self.group = group
+    def __init__(self, x_calibration: torch.Tensor, y_calibration: torch.Tensor):
         self.x_calibration = x_calibration
         self.y_calibration = y_calibration
         self.number_of_calibration_points = x_calibration.shape[0]
 
-    def _quantiles(self, x: torch.Tensor, q) -> torch.Tensor:
-        """(N*, len(q)) quantiles over all J particles: this rank's samples, then the sharded reduction"""
-        from .distributed import sharded_row_quantiles
-
-        samples = self.pls.predict_samples(x=x, particles=self.particles, predictive_noise=None, observation_noise=None)
-        return sharded_row_quantiles(samples, q, self.group)
-
     def _predict_uncalibrated_coverage(self, coverage: float, x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
-        """Quantiles 0.5 -/+ coverage/2 of the particle predictions (conformalise/pls.py:24-45)."""
-        q = self._quantiles(x, [0.5 - coverage / 2, 0.5 + coverage / 2])
-        return q[:, 0].contiguous(), q[:, 1].contiguous()
+        raise NotImplementedError
 
     def predict_median(self, x: torch.Tensor) -> torch.Tensor:
-        return self._quantiles(x, [0.5])[:, 0].contiguous()  # conformalise/pls.py:47-62
+        raise NotImplementedError
 
     def _calculate_calibration(self, coverage: float) -> float:
         """conformalise/base.py:58-90: the (n+1) c / n quantile of the conformity scores."""
@@ -81,3 +72,78 @@ class ConformalisePLS:
 
     def __call__(self, x: torch.Tensor, coverage: float) -> ConformalPrediction:
         return self.predict(x=x, coverage=coverage)
+
+
+class ConformalisePLS(_ConformaliseBase):
+    """conformalise/pls.py:8-62 on top of conformalise/base.py:19-160 (https://arxiv.org/abs/2107.07511)."""
+
+    def __init__(self, x_calibration: torch.Tensor, y_calibration: torch.Tensor, pls: PLS, particles: torch.Tensor, group=None):
+        self.pls = pls
+        self.particles = particles
+        self.group = group
+        super().__init__(x_calibration, y_calibration)
+
+    def _quantiles(self, x: torch.Tensor, q) -> torch.Tensor:
+        """(N*, len(q)) quantiles over all J particles: this rank's samples, then the sharded reduction"""
+        from .distributed import sharded_row_quantiles
+
+        samples = self.pls.predict_samples(x=x, particles=self.particles, predictive_noise=None, observation_noise=None)
+        return sharded_row_quantiles(samples, q, self.group)
+
+    def _predict_uncalibrated_coverage(self, coverage: float, x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Quantiles 0.5 -/+ coverage/2 of the particle predictions (conformalise/pls.py:24-45)."""
+        q = self._quantiles(x, [0.5 - coverage / 2, 0.5 + coverage / 2])
+        return q[:, 0].contiguous(), q[:, 1].contiguous()
+
+    def predict_median(self, x: torch.Tensor) -> torch.Tensor:
+        return self._quantiles(x, [0.5])[:, 0].contiguous()  # conformalise/pls.py:47-62
+
+
+def gaussian_interval(mean: torch.Tensor, variance: torch.Tensor, coverage: float) -> Tuple[torch.Tensor, torch.Tensor]:
+    """mean -/+ z sqrt(variance) with z = ndtri((1 + coverage) / 2), the upper end of ``scipy.stats.norm.interval(coverage)``
+    (conformalise/gp.py:43-49), in float64 wherever ``mean`` lives."""
+    mean = mean.to(torch.float64)
+    z = torch.special.ndtri(torch.tensor((1.0 + float(coverage)) / 2.0, dtype=torch.float64)).item()
+    half = z * torch.sqrt(variance.to(torch.float64))
+    return mean - half, mean + half
+
+
+class ConformaliseGP(_ConformaliseBase):
+    """conformalise/gp.py:12-64: the central ``coverage`` interval of the GP's predictive distribution, calibrated on the
+    calibration split.  ``gp``: an ``ExactGP`` (Gaussian noise) or an ``SVGP`` with a Gaussian or a Student-t likelihood;
+    anything else raises, as the reference's ``else`` branch does.
+
+    With ``(mean, latent, observation) = gp.predict(x)`` the uncalibrated interval is ``gaussian_interval`` of the mean and
+    * the observation variance under a Gaussian likelihood;
+    * ``observation - latent`` = noise nu / (nu - 2), the likelihood's own variance, under a Student-t likelihood.  The
+      reference averages ``f_s -/+ z sqrt(noise nu / (nu - 2))`` over the 10 function samples f_s that gpytorch draws for
+      a non-Gaussian likelihood; ours is the expectation of that average (the latent mean takes the place of the sample
+      mean), deterministic.  This is a READING of gpytorch's source, not a run of it, like every other statement about
+      gpytorch in INTEGRATION.md section A.
+    ``predict_median`` is the latent mean."""
+
+    def __init__(self, gp, x_calibration: torch.Tensor, y_calibration: torch.Tensor):
+        from .gaussian_process import SVGP, ExactGP
+
+        if isinstance(gp, ExactGP):
+            self._student = False
+        elif isinstance(gp, SVGP):
+            if not isinstance(gp._lik, (GaussianLikelihood, StudentTLikelihood)):
+                raise ValueError(f"ConformaliseGP: unknown likelihood type {type(gp._lik).__name__}: a Gaussian or a "
+                                 "Student-t likelihood is needed")
+            self._student = isinstance(gp._lik, StudentTLikelihood)
+        else:
+            raise TypeError(f"ConformaliseGP: gp must be an ExactGP or an SVGP, got {type(gp).__name__}")
+        self.gp = gp
+        super().__init__(x_calibration, y_calibration)
+
+    @property
+    def likelihood(self):
+        return getattr(self.gp, "likelihood", "gaussian")
+
+    def _predict_uncalibrated_coverage(self, coverage: float, x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        mean, latent, observation = self.gp.predict(x)
+        return gaussian_interval(mean, observation - latent if self._student else observation, coverage)
+
+    def predict_median(self, x: torch.Tensor) -> torch.Tensor:
+        return self.gp.predict(x)[0]  # conformalise/gp.py:57-64

@@ -199,6 +199,138 @@ static int grad_sums_launch(int kind, const double *x, int64_t n, int d, const d
   return check_launch("grad_sums_finish");
 }
 
+// ---- the predictive mean without the cross-Gram matrix -------------------------------------------------------------
+// kappa (the kernel without its outputscale) of one pair from its distance sum s2, evaluated as kernel_gram_kernel
+// evaluates it (plship.hip); false for a pair whose exponential underflows: the caller skips it (exactly 0).
+template <int KIND>
+__device__ __forceinline__ bool pair_kappa(double s2, double &kap) {
+  if (KIND == PLS_KERNEL_RBF_ARD) {
+    kap = exp_nonpos_unguarded(-0.5 * s2);
+    return !(-0.5 * s2 < -745.2);
+  }
+  const double t = sqrt(s2);
+  kap = matern_poly(KIND, t) * exp_nonpos_unguarded(-t);
+  return !(t > 745.2);
+}
+
+// out[i] = mean + outputscale * sum_j kappa(xt_i, x_j) alpha_j.  A workgroup owns MEAN_POINTS = 64 test points: lane l of
+// EVERY wave holds test point 64 b + l in registers (pre-scaled by 1/lengthscale, zero-padded to D_MAX); the training
+// points pass through LDS in chunks of mean_chunk(D_MAX) (pre-scaled, broadcast reads) and wave w takes the points
+// j = w, w + 4, w + 8, ... (the chunk length is a multiple of 4, so the split is j mod 4 whatever the chunk).  Each thread
+// adds its terms in ascending j into one accumulator; the four waves' sums meet in LDS as (w0 + w1) + (w2 + w3).  A lane
+// owns its test point alone -- there is no cross-lane sum -- so out[i] depends on xt_i and the model only, never on t or
+// on where the point sits in the batch.  x is staged from its flat array, 16 bytes per lane where x is 16-byte aligned
+// (a chunk starts at an even offset), one double per lane otherwise; xt rows likewise where d is even.
+template <int KIND, int D_MAX>
+__global__ __launch_bounds__(256) void kernel_mean_kernel(const double *__restrict__ x, int64_t n, int d,
+                                                           const double *__restrict__ lengthscale, double outputscale,
+                                                           double mean, const double *__restrict__ alpha,
+                                                           const double *__restrict__ xt, int64_t t,
+                                                           double *__restrict__ out) {
+  constexpr int CHUNK = mean_chunk(D_MAX);
+  __shared__ double inv_ls[D_MAX];
+  __shared__ __attribute__((aligned(16))) double a_s[CHUNK][D_MAX];
+  __shared__ double al_s[CHUNK];
+  __shared__ double red[4][MEAN_POINTS];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  if (tid < D_MAX) inv_ls[tid] = (tid < d) ? matern_t_scale(KIND) / lengthscale[tid] : 0.0;
+  if (D_MAX > 1)  // the padding coordinates stay zero: the staging below writes k < d only
+    for (int e = tid; e < CHUNK * D_MAX; e += 256) a_s[e / D_MAX][e % D_MAX] = 0.0;
+  __syncthreads();
+  const int64_t i = (int64_t)blockIdx.x * MEAN_POINTS + lane;
+  const bool live = i < t;
+  double b[D_MAX];
+  {
+    const double *row = xt + (live ? i : 0) * d;
+    if ((d & 1) == 0 && (reinterpret_cast<uintptr_t>(xt) & 15) == 0) {
+#pragma unroll
+      for (int k = 0; k < D_MAX; k += 2) {
+        const double2m v = (k < d) ? *reinterpret_cast<const double2m *>(row + k) : double2m{0.0, 0.0};
+        b[k] = v.x * inv_ls[k];
+        if (k + 1 < D_MAX) b[k + 1] = v.y * inv_ls[(k + 1) % D_MAX];
+      }
+    } else {
+#pragma unroll
+      for (int k = 0; k < D_MAX; ++k) b[k] = (k < d) ? row[k] * inv_ls[k] : 0.0;
+    }
+  }
+  const bool xvec = (reinterpret_cast<uintptr_t>(x) & 15) == 0;
+  double acc = 0.0;
+  for (int64_t j0 = 0; j0 < n; j0 += CHUNK) {
+    const int nrows = (int)((n - j0 < CHUNK) ? (n - j0) : CHUNK);
+    const int len = nrows * d;  // <= 512 * 64
+    const double *src = x + j0 * d;
+    if (xvec) {
+      for (int p = tid; 2 * p < len; p += 256) {
+        const int e = 2 * p;
+        if (e + 1 < len) {
+          const double2m v = *reinterpret_cast<const double2m *>(src + e);
+          a_s[e / d][e % d] = v.x * inv_ls[e % d];
+          a_s[(e + 1) / d][(e + 1) % d] = v.y * inv_ls[(e + 1) % d];
+        } else {
+          a_s[e / d][e % d] = src[e] * inv_ls[e % d];
+        }
+      }
+    } else {
+      for (int e = tid; e < len; e += 256) a_s[e / d][e % d] = src[e] * inv_ls[e % d];
+    }
+    for (int r = tid; r < nrows; r += 256) al_s[r] = alpha[j0 + r];
+    __syncthreads();
+#pragma unroll 2
+    for (int r = w; r < nrows; r += 4) {
+      double s2 = 0.0;
+#pragma unroll
+      for (int k = 0; k < D_MAX; ++k) {
+        const double e = a_s[r][k] - b[k];
+        s2 = fma(e, e, s2);
+      }
+      double kap;
+      if (pair_kappa<KIND>(s2, kap)) acc = fma(kap, al_s[r], acc);
+    }
+    __syncthreads();
+  }
+  red[w][lane] = acc;
+  __syncthreads();
+  if (w == 0 && live) out[i] = fma(outputscale, (red[0][lane] + red[1][lane]) + (red[2][lane] + red[3][lane]), mean);
+}
+
+// The KIND x D_MAX instantiations of a stationary kernel's per-pair loops: f(integral_constant<KIND>, integral_constant<D_MAX>)
+// with D_MAX the input dimension rounded up to 1, 2, 4, 8, 16, 32 or 64 (kind and d already validated).
+template <class F>
+static int for_kind_dmax(int kind, int d, F &&f) {
+  using std::integral_constant;
+  auto with_kind = [&](auto k) {
+    if (d <= 1) return f(k, integral_constant<int, 1>{});
+    if (d <= 2) return f(k, integral_constant<int, 2>{});
+    if (d <= 4) return f(k, integral_constant<int, 4>{});
+    if (d <= 8) return f(k, integral_constant<int, 8>{});
+    if (d <= 16) return f(k, integral_constant<int, 16>{});
+    if (d <= 32) return f(k, integral_constant<int, 32>{});
+    return f(k, integral_constant<int, 64>{});
+  };
+  switch (kind) {
+    case PLS_KERNEL_RBF_ARD: return with_kind(integral_constant<int, PLS_KERNEL_RBF_ARD>{});
+    case PLS_KERNEL_MATERN12: return with_kind(integral_constant<int, PLS_KERNEL_MATERN12>{});
+    case PLS_KERNEL_MATERN32: return with_kind(integral_constant<int, PLS_KERNEL_MATERN32>{});
+    default: return with_kind(integral_constant<int, PLS_KERNEL_MATERN52>{});
+  }
+}
+
+// the one launch of pls_kernel_mean (arguments already validated, t > 0)
+static int kernel_mean_launch(int kind, const double *x, int64_t n, int d, const double *lengthscale, double outputscale,
+                              double mean, const double *alpha, const double *xt, int64_t t, double *out, hipStream_t st) {
+  const dim3 grid((unsigned)cdiv(t, (int64_t)MEAN_POINTS));
+  {
+    LaunchScope scope(PLS_TAG_OTHER, st);
+    for_kind_dmax(kind, d, [&](auto k, auto dm) {
+      hipLaunchKernelGGL((kernel_mean_kernel<decltype(k)::value, decltype(dm)::value>), grid, dim3(256), 0, st, x, n, d,
+                         lengthscale, outputscale, mean, alpha, xt, t, out);
+      return 0;
+    });
+  }
+  return check_launch("kernel_mean");
+}
+
 // r = y - mean
 __global__ __launch_bounds__(256) void gp_center_kernel(const double *__restrict__ y, double mean, int64_t n, double *__restrict__ r) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -465,6 +597,18 @@ int pls_kernel_grad_sums(int32_t kernel_kind, const double *x, int64_t n, int64_
   PLS_REQUIRE(ldp >= n, "kernel_grad_sums: ldp < n");
   return grad_sums_launch(kernel_kind, x, n, (int)d, lengthscale, outputscale, alpha, P, ldp, out,
                           static_cast<double *>(workspace), S(stream));
+}
+
+int pls_kernel_mean(int32_t kernel_kind, const double *x, int64_t n, int64_t d, const double *lengthscale, double outputscale,
+                    double mean, const double *alpha, const double *xt, int64_t t, double *out, void *stream) {
+  PLS_REQUIRE(kernel_kind != PLS_KERNEL_LINEAR, "kernel_mean: the linear kernel has no lengthscale or outputscale to learn");
+  PLS_REQUIRE(stationary_kind(kernel_kind), "kernel_mean: unknown kernel kind %d", kernel_kind);
+  PLS_REQUIRE(n > 0 && d > 0 && t >= 0, "kernel_mean: bad sizes n=%lld d=%lld t=%lld", (long long)n, (long long)d, (long long)t);
+  PLS_REQUIRE(d <= GRAD_D_MAX, "kernel_mean: input dimension %lld > 64 is not supported", (long long)d);
+  PLS_REQUIRE(cdiv(t, (int64_t)MEAN_POINTS) <= 2147483647, "kernel_mean: t=%lld too large", (long long)t);
+  if (t == 0) return PLS_OK;
+  PLS_REQUIRE(x && lengthscale && alpha && xt && out, "kernel_mean: NULL pointer");
+  return kernel_mean_launch(kernel_kind, x, n, (int)d, lengthscale, outputscale, mean, alpha, xt, t, out, S(stream));
 }
 
 size_t pls_gp_mll_workspace_bytes(int64_t n, int64_t d) {

@@ -19,6 +19,7 @@ from typing import Callable, List, Sequence, Tuple
 import torch
 
 from . import _lib as L
+from . import _ops
 from ._chol import CHOLESKY_JITTER, CHOLESKY_MAX_TRIES, NotPSDError, cholesky_factor
 from .kernel import ARDKernel, BaseKernel, MaternKernel, _dev
 from .likelihoods import GaussianLikelihood, _Likelihood
@@ -274,6 +275,32 @@ class ExactGP(_ExactGPClasses):
         mean, var = self._predict_class(0, x_test)
         return mean, var, var + self.noise
 
+    def predict_mean(self, x_test: torch.Tensor) -> torch.Tensor:
+        """The mean of ``predict`` alone, (t,) float64 on the device: c + sum_j k(x*_i, x_j) alpha_j in ONE
+        ``pls_kernel_mean`` call -- no n x t matrix is built and no variance solve runs (the reference's
+        ``model(experiment_data.train.x)`` at experiments/uci/regression/main.py:231 computes both and
+        ``estimate_student_parameters`` keeps the mean).  alpha = K_y^-1 (y - c) is kept for the next call: the cache key
+        is a clone of the raw parameter values, compared with ``torch.equal``, so ``set_raw_parameters`` or an optimiser
+        step invalidates it."""
+        st = self._device_state()
+        cached = st.get("alpha")
+        if cached is None or not torch.equal(cached[0], self.raw.detach()):
+            mean_c, noise, s, ls = (v[0] for v in self._natural())
+            ky = self._make_kernel(ls, float(s))(st["x"], st["x"])
+            ky.diagonal().add_(float(noise))
+            alpha = cholesky_factor(ky).solve((st["y"][0] - float(mean_c))[:, None].contiguous())
+            cached = (self.raw.detach().clone(), alpha.reshape(-1).contiguous(), st["x"].new_tensor(ls.tolist()).contiguous(),
+                      float(s), float(mean_c))
+            st["alpha"] = cached
+        _, alpha, ls, s, mean_c = cached
+        xt = _dev(x_test.detach() if x_test.dim() == 2 else x_test.detach()[:, None]).contiguous()
+        assert xt.shape[1] == self.d, f"x_test has {xt.shape[1]} columns, the model {self.d}"
+        out = torch.empty(xt.shape[0], dtype=torch.float64, device=xt.device)
+        L.check(L.load().pls_kernel_mean(self.kind, st["x"].data_ptr(), self.n, self.d, ls.data_ptr(), s, mean_c,
+                                         alpha.data_ptr(), xt.data_ptr(), xt.shape[0], out.data_ptr(), L.stream_ptr()),
+                "pls_kernel_mean")
+        return out
+
 
 # ---- sparse variational GP (fixed kernel, fixed inducing points, Gaussian likelihood) ------------------------------------
 #: gpytorch's jitter on k(Z, Z) for float64 data (settings.variational_cholesky_jitter; 1e-4 for float32 data)
@@ -523,6 +550,144 @@ class SVGP:
         return torch.special.ndtr(mean / torch.sqrt(1.0 + var))
 
 
+# ---- the Student-t noise of the regression drivers --------------------------------------------------------------------
+def student_t_sums_on_device(residuals: torch.Tensor, nu: float, s: float) -> Tuple[float, float, float]:
+    """(A, B, C) = (sum log1p(u), sum u / (1 + u), sum u / (1 + u)^2), u_i = r_i^2 / (nu s^2), of device residuals from
+    entries the library already has, with the Student-t ``pls_cost_desc`` at (nu, s) on the single column F = r, y = 0:
+    the cost value is (nu + 1)/2 A (``pls_cost_value``), its derivative G_i = (nu + 1) r_i / (nu s^2 + r_i^2)
+    (``pls_cost_derivative``) gives r^T G = (nu + 1) B and G^T G = (nu + 1)^2 C / (nu s^2) (one ``pls_gemm_tn``).  One
+    read-back of three numbers."""
+    r = L.require_gpu_tensor(residuals, "residuals").reshape(-1).contiguous()
+    n = r.numel()
+    lib = L.load()
+    desc = L.CostDesc()
+    desc.cost, desc.link, desc.deriv_mode = L.COST_STUDENT_T, L.LINK_IDENTITY, L.DERIV_REFERENCE
+    desc.p[0], desc.p[1], desc.jitter = float(nu), float(s), 1e-10
+    zero = torch.zeros(n, dtype=torch.float64, device=r.device)
+    g = torch.empty((n, 1), dtype=torch.float64, device=r.device)
+    out = torch.empty(4, dtype=torch.float64, device=r.device)
+    ws_bytes = lib.pls_cost_value_workspace_bytes(n, 1)
+    ws = torch.empty(max(ws_bytes // 8, 1), dtype=torch.float64, device=r.device)
+    L.check(lib.pls_cost_value(desc, r.data_ptr(), 1, zero.data_ptr(), n, 1, out.data_ptr(), ws.data_ptr(), ws_bytes,
+                               L.stream_ptr()), "pls_cost_value")
+    L.check(lib.pls_cost_derivative(desc, r.data_ptr(), 1, zero.data_ptr(), n, 1, g.data_ptr(), 1, L.stream_ptr()),
+            "pls_cost_derivative")
+    _ops.gemm_tn(g, torch.stack([r, g[:, 0]], dim=1), out=out[2:4].view(1, 2))  # G^T [r G]: one contraction
+    c, _, rtg, gtg = out.cpu().tolist()
+    return 2.0 * c / (nu + 1.0), rtg / (nu + 1.0), nu * s * s * gtg / (nu + 1.0) ** 2
+
+
+def _trigamma(x: float) -> float:
+    """psi'(x) for x > 0: the recurrence psi'(x) = psi'(x + 1) + 1/x^2 up to x >= 15, then the asymptotic series through
+    x^-15 (truncation below 1e-18 there); torch.special.polygamma(1, .) is good to 1e-10 only"""
+    total = 0.0
+    while x < 15.0:
+        total += 1.0 / (x * x)
+        x += 1.0
+    w = 1.0 / (x * x)
+    series = w * (1.0 / 6 + w * (-1.0 / 30 + w * (1.0 / 42 + w * (-1.0 / 30 + w * (5.0 / 66 + w * (-691.0 / 2730 + w * 7.0 / 6))))))
+    return total + (1.0 / x + 0.5 * w + series / x)
+
+
+def _student_t_pieces(n: int, nu: float, a: float, b: float, c: float, log_s: float):
+    """(negative log-likelihood, its gradient and Hessian in (log nu, log s)) of n zero-location Student-t residuals from
+    the three sums: with h(nu) = lgamma((nu + 1)/2) - lgamma(nu/2) - log(nu pi)/2,
+    ll = n h - n log s - (nu + 1)/2 A;  d/dlog nu = n nu h' - nu A/2 + (nu + 1) B/2;  d/dlog s = -n + (nu + 1) B;
+    d2/dlog nu2 = n nu (h' + nu h'') - nu A/2 + nu B - (nu + 1) C/2;  d2/dlog nu dlog s = nu B - (nu + 1) C;
+    d2/dlog s2 = -2 (nu + 1) C."""
+    half = torch.tensor([0.5 * (nu + 1.0), 0.5 * nu], dtype=torch.float64)
+    psi, tri = torch.special.digamma(half).tolist(), (_trigamma(0.5 * (nu + 1.0)), _trigamma(0.5 * nu))
+    h = math.lgamma(0.5 * (nu + 1.0)) - math.lgamma(0.5 * nu) - 0.5 * math.log(nu * math.pi)
+    h1 = 0.5 * (psi[0] - psi[1]) - 0.5 / nu
+    h2 = 0.25 * (tri[0] - tri[1]) + 0.5 / (nu * nu)
+    nll = -(n * h - n * log_s - 0.5 * (nu + 1.0) * a)
+    g = (-(n * nu * h1 - 0.5 * nu * a + 0.5 * (nu + 1.0) * b), -(-n + (nu + 1.0) * b))
+    haa = -(n * nu * (h1 + nu * h2) - 0.5 * nu * a + nu * b - 0.5 * (nu + 1.0) * c)
+    hab = -(nu * b - (nu + 1.0) * c)
+    hbb = 2.0 * (nu + 1.0) * c
+    return nll, g, (haa, hab, hbb)
+
+
+def fit_student_t(residuals: torch.Tensor, deg_free_bounds: Tuple[float, float] = (1e-2, 1e6),
+                  evaluate: Callable[[torch.Tensor, float, float], Tuple[float, float, float]] | None = None
+                  ) -> Tuple[float, float]:
+    """(deg_free, scale): the maximum-likelihood parameters of a zero-location Student-t for the residuals -- what
+    ``scipy.stats.t.fit(residuals, floc=0)`` approximates with Nelder-Mead at experiments/uci/regression/main.py:124.
+
+    Damped Newton in (log nu, log s) from nu = 1, s = rms(r): the Newton step (steepest descent of unit length where the
+    Hessian of the negative log-likelihood is not positive definite; no step longer than 2 in either coordinate) is halved
+    until the negative log-likelihood does not rise by more than its own rounding noise (1e-12 relative to |nll| + n);
+    it stops when both steps are at or below 1e-12 or after 100 iterations.  The data enter through three sums per
+    evaluation (``student_t_sums_on_device``: existing library entries, one read-back); ``evaluate(residuals, nu, s) ->
+    (A, B, C)`` replaces that evaluation (a host helper drives the same loop without a device).  Where log nu reaches a bound
+    (Gaussian residuals: the likelihood has no finite maximiser in nu) nu is clamped there, the one-dimensional Newton
+    iteration in log s is finished and ONE warning is emitted.
+
+    The maximiser may lie at or below nu = 2, where the Student-t variance does not exist and ``StudentTLikelihood``
+    raises; the reference has the same limit (gpytorch's variance is infinite there)."""
+    evaluate = evaluate if evaluate is not None else student_t_sums_on_device
+    r = residuals.detach().reshape(-1).to(torch.float64)
+    n = r.numel()
+    rms = float(r.square().mean().sqrt())
+    if not (n > 0 and math.isfinite(rms) and rms > 0.0):
+        raise ValueError("fit_student_t: the residuals must be finite and not all zero")
+    lo, hi = math.log(deg_free_bounds[0]), math.log(deg_free_bounds[1])
+    if not lo <= 0.0 <= hi:
+        raise ValueError("fit_student_t: deg_free_bounds must contain the starting value 1")
+
+    def pieces(a_, b_):
+        nu_, s_ = math.exp(a_), math.exp(b_)
+        return _student_t_pieces(n, nu_, *evaluate(r, nu_, s_), b_)
+
+    a, b, pinned = 0.0, math.log(rms), False
+    nll, g, hess = pieces(a, b)
+    for _ in range(100):
+        haa, hab, hbb = hess
+        if pinned:
+            da, db = 0.0, -g[1] / hbb
+        else:
+            det = haa * hbb - hab * hab
+            if haa > 0.0 and det > 0.0:
+                da, db = -(hbb * g[0] - hab * g[1]) / det, -(haa * g[1] - hab * g[0]) / det
+            else:
+                norm = math.hypot(g[0], g[1])
+                da, db = -g[0] / norm, -g[1] / norm
+        shrink = max(1.0, abs(da) / 2.0, abs(db) / 2.0)
+        da, db = da / shrink, db / shrink
+        if not pinned and not lo < a + da < hi:
+            pinned, a = True, (lo if a + da <= lo else hi)
+            warnings.warn(f"fit_student_t: the degrees of freedom reached the bound {math.exp(a):.3g}; they are clamped "
+                          "there and only the scale is fitted", RuntimeWarning, stacklevel=2)
+            nll, g, hess = pieces(a, b)
+            continue
+        for _ in range(60):
+            new = pieces(a + da, b + db)
+            if new[0] <= nll + 1e-12 * (abs(nll) + n):
+                break
+            da, db = 0.5 * da, 0.5 * db
+        a, b = a + da, b + db
+        nll, g, hess = new
+        if abs(da) <= 1e-12 and abs(db) <= 1e-12:
+            break
+    return math.exp(a), math.exp(b)
+
+
+def estimate_student_parameters(y_actual: torch.Tensor, predictions: Sequence, deg_free_bounds: Tuple[float, float] = (1e-2, 1e6),
+                                evaluate=None) -> Tuple[float, float]:
+    """experiments/uci/regression/main.py:109-125: the residuals ``y_actual - mean_k`` are averaged over the models and a
+    zero-location Student-t is fitted to them (``fit_student_t``; the reference calls ``scipy.stats.t.fit(.., floc=0)``).
+    ``predictions``: one mean tensor per model (``ExactGP.predict_mean`` at all N training points); a tuple as ``predict``
+    returns it stands for its first element.  The averaging runs where the means live (on the device).  The result
+    feeds ``StudentTCost(deg_free, y, link, scale)``, ``StudentTLikelihood(deg_free)`` and the predictive noise of
+    ``OrthonormalBasis``; it may lie at or below 2, where ``StudentTLikelihood`` raises (see ``fit_student_t``)."""
+    means = [p[0] if isinstance(p, (tuple, list)) else p for p in predictions]
+    if not means:
+        raise ValueError("estimate_student_parameters: no predictions")
+    y = torch.as_tensor(y_actual).detach().reshape(-1).to(device=means[0].device, dtype=torch.float64)
+    residuals = torch.stack([y - m.detach().reshape(-1).to(torch.float64) for m in means], dim=1).mean(dim=1)
+    return fit_student_t(residuals, deg_free_bounds, evaluate)
+
+
 #: gpytorch's DirichletClassificationLikelihood: the Dirichlet concentration of a class that was not observed
 ALPHA_EPSILON = 0.01
 
@@ -709,4 +874,4 @@ def exact_gp_runner(x: torch.Tensor, y: torch.Tensor, kernel, subsample_size: in
 
 
 __all__ = ["ExactGP", "SVGP", "DirichletExactGP", "dirichlet_targets", "softmax_normal_mean", "train_exact_gp", "construct_average_ard_kernel", "construct_average_gaussian_noise", "nearest_subsample",
-           "exact_gp_runner", "NotPSDError"]
+           "exact_gp_runner", "NotPSDError", "fit_student_t", "estimate_student_parameters", "student_t_sums_on_device"]

@@ -1,5 +1,5 @@
-"""The metrics the step-size search optimises (drop-in for experiments/metrics.py:23-125, the branches that apply to
-PLS predictions).  Inputs are per-test-point vectors: host-side arithmetic on N* numbers."""
+"""The metrics the step-size search optimises (drop-in for experiments/metrics.py:23-146, the branches that apply to
+PLS and conformal predictions).  Inputs are per-test-point vectors: host-side arithmetic on N* numbers."""
 from __future__ import annotations
 
 import math
@@ -46,4 +46,27 @@ def calculate_nll(prediction, y: torch.Tensor) -> float:
         return torch.nn.functional.poisson_nll_loss(prediction.rate, y.to(prediction.rate), reduction="mean").item()
     if isinstance(prediction, torch.distributions.StudentT):
         return prediction.log_prob(y.to(prediction.loc)).mean().item()  # metrics.py:98-99 (sign as in the reference)
+    if isinstance(prediction, ConformalPrediction):
+        # metrics.py:100-117: half the width of the 2/3 interval as the standard deviation of a normal around the median
+        assert prediction.coverage == 2 / 3, f"NLL calculation needs 2/3 coverage, got {prediction.coverage=}"
+        std = ((prediction.upper - prediction.lower) / 2).to(torch.float64)
+        z = (y.to(std) - prediction.mean.to(std)) / std
+        return (0.5 * z.square() + torch.log(std) + 0.5 * math.log(2 * math.pi)).mean().item()
     raise ValueError(f"Prediction type {type(prediction)} not supported")
+
+
+def calculate_coverage(prediction: ConformalPrediction, y: torch.Tensor) -> float:
+    """metrics.py:122-126: the share of targets inside [lower, upper] (a float32 mean, as the reference's ``.float()``)."""
+    yy = y.to(prediction.lower)
+    return ((prediction.lower <= yy) & (yy <= prediction.upper)).float().mean().item()
+
+
+def calculate_average_interval_width(model, x: torch.Tensor, coverage: float) -> float:
+    """metrics.py:129-137: ``model`` is a ConformalisePLS or a ConformaliseGP."""
+    return model.calculate_average_interval_width(x=x, coverage=coverage)
+
+
+def calculate_median_interval_width(model, x: torch.Tensor, coverage: float) -> float:
+    """metrics.py:140-146."""
+    lower, upper = model.predict_coverage(x=x, coverage=coverage)
+    return torch.median(upper - lower).item()
