@@ -731,6 +731,34 @@ int pls_svgp_lik_predict(const pls_svgp_lik_desc *desc, const double *m, const d
                          int64_t mdim, double *mean_out, double *var_out, double *obs_out, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Symmetric eigendecomposition (csrc/sym_eigh.hip: two-sided cyclic Jacobi, blocked, fp64 MFMA)
+ * ------------------------------------------------------------------------------------------- */
+
+/* A = V diag(lam) V^T for the symmetric m x m matrix whose LOWER triangle A holds (row-major, pitch lda; the strict upper
+ * triangle is never read, as torch.linalg.eigh reads by default; A is not written).  Replaces `torch.linalg.eigh` at
+ * orthonormal.py:46-48 (k(Z,Z) / M of the orthonormal basis) and samplers.py:27 (the indefinite predictive covariance).
+ * lam: m doubles, ascending.  V (m x m, pitch ldv): column k is the eigenvector of lam[k]; its largest-magnitude
+ * component (the first one on ties) is positive, so the result has ONE gauge: the same bits on every call of a build.
+ * info (HOST memory): 0 = converged; 1 = the sweep cap (30) was reached -- lam and V are the last iterate, and the call
+ * still returns PLS_OK.
+ * m <= 64: one workgroup diagonalises the matrix in LDS.  m > 64: blocks of 32, a round-robin over block pairs, three
+ * launches per round.  A pair (p, q) rotates only while |s_pq| > eps ||A||_F / m.
+ * m == 0 returns PLS_OK and touches nothing.  NULL pointers, lda < m, ldv < m, m < 0 and a workspace shorter than
+ * pls_sym_eigh_workspace_bytes(m) return PLS_ERR_INVALID_ARGUMENT before any HIP call; a NaN or an infinity in the lower
+ * triangle returns PLS_ERR_INVALID_ARGUMENT ("non-finite") after the first reduction, without sweeping.
+ * SYNCHRONISES `stream`: once after that reduction and once per outer sweep (the host reads the sweep's rotation count
+ * from pinned memory).  The call can therefore not be captured in a graph.  It allocates 64 pinned bytes on a thread's
+ * first call and nothing afterwards.  workspace: device memory, 8-byte aligned. */
+size_t pls_sym_eigh_workspace_bytes(int64_t m);
+int pls_sym_eigh(const double *A, int64_t lda, int64_t m, double *lam, double *V, int64_t ldv, int32_t *info,
+                 void *workspace, size_t workspace_bytes, void *stream);
+/* The block pairs (I < J) of one round of the solver's schedule for nblocks >= 2 blocks, round in [0, nblocks - 1) for an
+ * even and [0, nblocks) for an odd count: pairs[2 k], pairs[2 k + 1] for k < the returned count (room for nblocks / 2
+ * pairs).  The pairs of a round are disjoint; every unordered pair occurs once per sweep; with an odd count one block per
+ * round has a bye.  Pure host code; 0 for arguments outside those ranges. */
+int64_t pls_sym_eigh_round_pairs(int64_t nblocks, int64_t round, int64_t *pairs);
+
+/* ---------------------------------------------------------------------------------------------
  * Orthonormal basis: setup + step
  * ------------------------------------------------------------------------------------------- */
 

@@ -2,7 +2,9 @@
 jswu18/projected-langevin-sampling behind the reference's PLS / basis / cost / link-function API.
 
 All numerics run in libplship.so (hand-written HIP for gfx950, see csrc/); this package is the thin host
-side: it owns device memory through torch tensors and calls the C ABI (include/plship.h) with raw pointers."""
+side: it owns device memory through torch tensors and calls the C ABI (include/plship.h) with raw pointers.
+The one exception is the eigendecomposition of setup and prediction, torch.linalg.eigh by default as in the reference;
+eigh_device="plship" runs it in the library as well (pls_sym_eigh)."""
 from . import _lib
 from .conformalise import ConformaliseGP, ConformalisePLS, ConformalPrediction, gaussian_interval
 from .gaussian_process import (SVGP, DirichletExactGP, ExactGP, construct_average_ard_kernel, construct_average_gaussian_noise,

@@ -163,6 +163,9 @@ SIGNATURES = {
     "pls_normal_fill": (C.c_int, [_P, _I64, _I64, _I64, _U64, _U64, _I64, _P]),
     "pls_step_sync_words": (_SZ, [_I64]),
     "pls_sums16": (C.c_int, [_P, _I64, _P, _P]),
+    "pls_sym_eigh_workspace_bytes": (_SZ, [_I64]),
+    "pls_sym_eigh": (C.c_int, [_P, _I64, _I64, _P, _P, _I64, C.POINTER(C.c_int32), _P, _SZ, _P]),
+    "pls_sym_eigh_round_pairs": (C.c_int64, [_I64, _I64, C.POINTER(C.c_int64)]),
     "pls_onb_build_projection": (C.c_int, [_P, _I64, _P, _I64, _I64, _I64, _I64, _P, _I64, _P, _I64, _P]),
     "pls_onb_build_gaussian": (C.c_int, [_OD, _P, _P, _I64, _P, _P]),
     "pls_onb_forward": (C.c_int, [_OD, _P, _I64, _I64, _P, _I64, _P]),

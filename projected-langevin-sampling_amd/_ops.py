@@ -1,6 +1,8 @@
 """Small wrappers over libplship's primitive entry points, shared by the prediction-side code."""
 from __future__ import annotations
 
+import ctypes
+
 import torch
 
 from . import _lib as L
@@ -25,6 +27,35 @@ def gemm_tn(lm: torch.Tensor, rm: torch.Tensor, alpha: float = 1.0, beta: float 
         "pls_gemm_tn",
     )
     return out
+
+
+def sym_eigh(matrix: torch.Tensor, return_info: bool = False):
+    """(eigenvalues ascending, eigenvectors as columns) of the symmetric device matrix whose LOWER triangle ``matrix`` holds
+    (pls_sym_eigh: libplship's blocked Jacobi solver; the drop-in for torch.linalg.eigh at orthonormal.py:46-48 and
+    samplers.py:27 of the reference).  Each eigenvector's largest-magnitude component is positive (canonicalise_signs of
+    basis/spectrum.py is the identity on the result).  The call synchronises the stream.  ``return_info``: also the
+    solver's info (0 converged, 1 sweep cap reached); without it a result that did not converge warns."""
+    a = L.require_gpu_tensor(matrix, "matrix", promote=True)
+    assert a.dim() == 2 and a.shape[0] == a.shape[1], f"square matrix expected, got {tuple(a.shape)}"
+    a = a if a.stride(1) == 1 else a.contiguous()
+    m = a.shape[0]
+    lam = torch.empty(m, dtype=torch.float64, device=a.device)
+    vec = torch.empty((m, m), dtype=torch.float64, device=a.device)
+    info = ctypes.c_int32(0)
+    if m:
+        lib = L.load()
+        nbytes = lib.pls_sym_eigh_workspace_bytes(m)
+        ws = torch.empty(nbytes // 8, dtype=torch.float64, device=a.device)
+        L.check(lib.pls_sym_eigh(a.data_ptr(), L.ld(a), m, lam.data_ptr(), vec.data_ptr(), m, ctypes.byref(info), ws.data_ptr(),
+                                 nbytes, L.stream_ptr()), "pls_sym_eigh")
+    if return_info:
+        return lam, vec, int(info.value)
+    if info.value:
+        import warnings
+
+        warnings.warn(f"pls_sym_eigh: the sweep cap was reached for a {m} x {m} matrix (info = {info.value}); the result is the "
+                      "last iterate")
+    return lam, vec
 
 
 def row_power_sums(s: torch.Tensor, power: int, shift: torch.Tensor | None = None) -> torch.Tensor:

@@ -15,7 +15,8 @@ class OrthonormalBasis(PLSBasis):
 
     Setup (once): k(Z,Z), k(Z,X) on the GPU; torch.linalg.eigh like the reference, on the device the Gram matrix lives on
     (``eigh_device="cpu"`` / ``samplers.DEFAULT_EIGH_DEVICE`` select host LAPACK, the reference's CPU path; the
-    eigenvector gauge is implementation defined, so parity runs may pass ``spectrum=(eigenvalues, eigenvectors)``); then the projection
+    eigenvector gauge is implementation defined, so parity runs may pass ``spectrum=(eigenvalues, eigenvectors)``;
+    ``eigh_device="plship"`` runs libplship's own solver, pls_sym_eigh: one gauge, the same bits on every rank); then the projection
     A = V~^T k(Z,X) and its transpose are built once on the GPU instead of re-associating three matrices per step
     (orthonormal.py:106-108, :151-155)."""
 

@@ -93,9 +93,11 @@ def shared_spectrum(gram_scaled: torch.Tensor, eigh_where: str, group=None, src:
     """(eigenvalues, eigenvectors) of ``gram_scaled`` = k(Z,Z) / M as float64 CPU tensors (ascending, like torch.linalg.eigh).
     ``group`` None: this process's own eigh, no collective.  ``group`` True (default process group) or a ProcessGroup:
     identical on every rank of the group, after a check that the ranks hold the same matrix (assert_same_matrix).
-    ``eigh_where``: "cpu" (host LAPACK) or "cuda" (the device ``gram_scaled`` lives on).  ``src`` is a rank of ``group``.
-    ``canonical_signs`` None = True for the device route, False for the host route."""
-    assert eigh_where in ("cpu", "cuda")
+    ``eigh_where``: "cpu" (host LAPACK), "cuda" (the device ``gram_scaled`` lives on) or "plship" (libplship's own solver,
+    pls_sym_eigh).  ``src`` is a rank of ``group``.
+    ``canonical_signs`` None = True for the device route, False for the host route; the "plship" route returns canonical
+    signs by itself (the same rule, applied in its finish kernel), so nothing is applied to it."""
+    assert eigh_where in ("cpu", "cuda", "plship")
     m = gram_scaled.shape[0]
     active, group = _resolve_group(group)
     if active:
@@ -108,9 +110,15 @@ def shared_spectrum(gram_scaled: torch.Tensor, eigh_where: str, group=None, src:
         g = gram_scaled.detach().to(torch.float64)
         from ..samplers import host_eigh
 
-        lam, vec = host_eigh(g) if eigh_where == "cpu" else torch.linalg.eigh(g)  # orthonormal.py:46-48
+        if eigh_where == "plship":
+            from .._ops import sym_eigh
+            from ..kernel import _dev
+
+            lam, vec = sym_eigh(_dev(g))
+        else:
+            lam, vec = host_eigh(g) if eigh_where == "cpu" else torch.linalg.eigh(g)  # orthonormal.py:46-48
         lam, vec = lam.cpu(), vec.cpu()
-        if canonical_signs:
+        if canonical_signs and eigh_where != "plship":
             vec = canonicalise_signs(vec)
         packed = torch.cat([lam.reshape(1, m), vec], dim=0).contiguous()  # (M + 1, M)
     if active:

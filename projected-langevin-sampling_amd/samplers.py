@@ -22,6 +22,9 @@ from .kernel import _dev
 #: the host share of a GPU box for 2 000 test points and 0.05 s on the device; k(Z,Z)/M at M = 4096 takes 21 s against
 #: 0.15 s (tools/eigh_probe.py, tools/predict_probe.py).  Every choice gives a valid factor Q sqrt(Lambda) of the same
 #: matrix; the SAMPLE differs (another eigenvector gauge).
+#: "plship" = libplship's own solver on the device (pls_sym_eigh: blocked two-sided Jacobi, csrc/sym_eigh.hip): no torch
+#: solver at all, a fixed operation order and canonical signs, so every rank and every resume of a build holds the same
+#: bits.  Opt-in: "auto" never resolves to it.
 DEFAULT_EIGH_DEVICE = "auto"
 
 #: ... except for SMALL matrices: under "auto" an n x n matrix with n <= this goes to host LAPACK wherever it lives.  The
@@ -32,10 +35,10 @@ EIGH_HOST_BELOW = 128
 
 
 def resolve_eigh_device(requested: str | None, matrix: torch.Tensor) -> str:
-    """'cpu' or 'cuda' for an eigh of `matrix`: the explicit request, else DEFAULT_EIGH_DEVICE; 'auto' = where it lives,
-    small matrices (EIGH_HOST_BELOW) on the host"""
+    """'cpu', 'cuda' or 'plship' for an eigh of `matrix`: the explicit request, else DEFAULT_EIGH_DEVICE; 'auto' = where it
+    lives, small matrices (EIGH_HOST_BELOW) on the host -- never 'plship', which only a request selects"""
     where = requested or DEFAULT_EIGH_DEVICE
-    assert where in ("auto", "cpu", "cuda"), "eigh_device must be 'auto', 'cpu' or 'cuda'"
+    assert where in ("auto", "cpu", "cuda", "plship"), "eigh_device must be 'auto', 'cpu', 'cuda' or 'plship'"
     if where == "auto":
         where = "cuda" if (matrix.is_cuda and matrix.shape[-1] > EIGH_HOST_BELOW) else "cpu"
     return where
@@ -107,7 +110,12 @@ def spectral_factor(cov: torch.Tensor, eigh_device: str | None = None) -> torch.
     Cholesky factor -- with whatever jitter -- has that law."""
     where = resolve_eigh_device(eigh_device, cov)
     c64 = cov.detach().to(torch.float64)
-    eigenvalues, eigenvectors = host_eigh(c64) if where == "cpu" else torch.linalg.eigh(_dev(c64))  # samplers.py:27
+    if where == "plship":
+        from ._ops import sym_eigh
+
+        eigenvalues, eigenvectors = sym_eigh(_dev(c64))
+    else:
+        eigenvalues, eigenvectors = host_eigh(c64) if where == "cpu" else torch.linalg.eigh(_dev(c64))  # samplers.py:27
     eigenvalues = torch.clip(eigenvalues, 0, None)
     # (Q sqrt(Lambda))^T stored k-major: L[k][i] = Q[i][k] * sqrt(lam_k)
     return _dev((eigenvectors * torch.sqrt(eigenvalues)[None, :]).T)
