@@ -685,109 +685,9 @@ static int launch_gemm_rows(const double *L, int64_t ldl, const double *R, int64
 // cost-value GEMM (tile geometry is part of the epilogue type); returns the number of partial rows written
 static int64_t cost_value_partial_rows(int64_t I, int64_t J) { return use_big_tiles(I, J) ? cdiv(I, 128) : cdiv(I, 64); }
 
-
 // ---------------------------------------------------------------------------------------------------------------
 // HBM-bound kernels
 // ---------------------------------------------------------------------------------------------------------------
-
-// exp_nonpos, matern_t_scale, matern_poly: kernel_math.h (shared with the gradient reduction of gp_mll.hip)
-template <int KIND>
-__device__ __forceinline__ double matern_from_t2(double t2, double outputscale) {
-  const double t = sqrt(t2);
-  const double k = outputscale * (matern_poly(KIND, t) * exp_nonpos_unguarded(-t));
-  return (t > 745.2) ? 0.0 : k;
-}
-
-// k(x1, x2): a block covers GRAM_ROWS rows x 512 columns; a thread owns one PAIR of columns (its two x2 points stay in
-// registers, pre-scaled by 1/lengthscale) and walks down the rows, whose pre-scaled x1 points sit in LDS (broadcast
-// reads).  Writes are 16 B per lane, 4 KiB contiguous per row and block: the kernel is bound by the 8*n1*n2 bytes it
-// writes once the per-element work is ~35 fp64 instructions (D = 8).
-constexpr int GRAM_ROWS = 64;
-// D_MAX: the input dimension rounded up to a power of two; the padding coordinates are zero on both sides, so the
-// unrolled coordinate loops need no `k < d` test.
-template <int KIND, int D_MAX>
-__global__ __launch_bounds__(256) void kernel_gram_kernel(const double *__restrict__ x1, int64_t n1,
-                                                           const double *__restrict__ x2, int64_t n2, int d,
-                                                           const double *__restrict__ lengthscale, double outputscale,
-                                                           double *__restrict__ out, int64_t ldout) {
-  __shared__ double inv_ls[D_MAX];
-  __shared__ __attribute__((aligned(16))) double a_s[GRAM_ROWS][D_MAX];  // rows of x1 (pre-scaled, zero-padded)
-  const int t = threadIdx.x;
-  const int64_t row0 = (int64_t)blockIdx.y * GRAM_ROWS;
-  const int nrows = (int)((n1 - row0 < GRAM_ROWS) ? (n1 - row0) : GRAM_ROWS);
-  if (t < D_MAX) inv_ls[t] = (t < d) ? ((KIND != PLS_KERNEL_LINEAR) ? matern_t_scale(KIND) / lengthscale[t] : 1.0) : 0.0;
-  __syncthreads();
-  for (int e = t; e < nrows * D_MAX; e += 256) {
-    const int r = e / D_MAX, k = e % D_MAX;
-    a_s[r][k] = (k < d) ? x1[(row0 + r) * d + k] * inv_ls[k] : 0.0;
-  }
-  __syncthreads();
-  const int64_t col = ((int64_t)blockIdx.x * 256 + t) * 2;
-  if (col >= n2) return;
-  const bool two = col + 1 < n2;
-  double b0[D_MAX], b1[D_MAX];
-#pragma unroll
-  for (int k = 0; k < D_MAX; ++k) {
-    b0[k] = (k < d) ? x2[col * d + k] * inv_ls[k] : 0.0;
-    b1[k] = (k < d && two) ? x2[(col + 1) * d + k] * inv_ls[k] : 0.0;
-  }
-  const bool vec = two && ((ldout & 1) == 0) && ((reinterpret_cast<uintptr_t>(out) & 15) == 0);
-  double *dst = out + row0 * ldout + col;
-#pragma unroll 2
-  for (int r = 0; r < nrows; ++r, dst += ldout) {
-    double s0 = 0.0, s1 = 0.0;
-    if (KIND == PLS_KERNEL_RBF_ARD) {
-#pragma unroll
-      for (int k = 0; k < D_MAX; ++k) {
-        const double a = a_s[r][k];
-        const double e0 = a - b0[k], e1 = a - b1[k];
-        s0 = fma(e0, e0, s0);
-        s1 = fma(e1, e1, s1);
-      }
-      s0 = outputscale * exp_nonpos(-0.5 * s0);
-      s1 = outputscale * exp_nonpos(-0.5 * s1);
-    } else if (KIND != PLS_KERNEL_LINEAR) {  // Matern: the same distance sum as RBF, of t^2 (inv_ls holds sqrt(2 nu))
-#pragma unroll
-      for (int k = 0; k < D_MAX; ++k) {
-        const double a = a_s[r][k];
-        const double e0 = a - b0[k], e1 = a - b1[k];
-        s0 = fma(e0, e0, s0);
-        s1 = fma(e1, e1, s1);
-      }
-      s0 = matern_from_t2<KIND>(s0, outputscale);
-      s1 = matern_from_t2<KIND>(s1, outputscale);
-    } else {
-#pragma unroll
-      for (int k = 0; k < D_MAX; ++k) {
-        const double a = a_s[r][k];
-        s0 = fma(a, b0[k], s0);
-        s1 = fma(a, b1[k], s1);
-      }
-    }
-    if (vec) {
-      *reinterpret_cast<double2_t *>(dst) = double2_t{s0, s1};
-    } else {
-      dst[0] = s0;
-      if (two) dst[1] = s1;
-    }
-  }
-}
-
-template <int KIND>
-static void launch_gram(dim3 grid, hipStream_t st, const double *x1, int64_t rows, const double *x2, int64_t n2, int d,
-                        const double *lengthscale, double outputscale, double *out, int64_t ldout) {
-#define PLS_GRAM_CASE(DM)                                                                                         \
-  hipLaunchKernelGGL((kernel_gram_kernel<KIND, DM>), grid, dim3(256), 0, st, x1, rows, x2, n2, d, lengthscale, \
-                     outputscale, out, ldout)
-  if (d <= 1) PLS_GRAM_CASE(1);
-  else if (d <= 2) PLS_GRAM_CASE(2);
-  else if (d <= 4) PLS_GRAM_CASE(4);
-  else if (d <= 8) PLS_GRAM_CASE(8);
-  else if (d <= 16) PLS_GRAM_CASE(16);
-  else if (d <= 32) PLS_GRAM_CASE(32);
-  else PLS_GRAM_CASE(64);
-#undef PLS_GRAM_CASE
-}
 
 __global__ __launch_bounds__(256) void debug_math_kernel(int op, const double *__restrict__ x, double *__restrict__ out,
                                                          int64_t n) {
@@ -1377,7 +1277,9 @@ __device__ inline double cv_kernel_eval(int kind, const double *__restrict__ x, 
     }
     return outputscale * exp(-0.5 * s);
   }
-  if (kind != PLS_KERNEL_LINEAR) {  // Matern (see matern_from_t2)
+  // Matern.  Not pair_kappa (kernel_math.h): this differences before it scales, multiplies sqrt(2 nu) in after the root and
+  // uses the library exp; the selector's pivots are pinned to the reference's indices, and 1 ulp can flip a tie.
+  if (kind != PLS_KERNEL_LINEAR) {
     for (int k = 0; k < d; ++k) {
       const double e = (x[a * d + k] - x[b * d + k]) * inv_ls[k];
       s = fma(e, e, s);
@@ -2119,36 +2021,6 @@ int pls_timeline_end(float *ms, int32_t *tags, int32_t capacity, int32_t *count)
   g_tl.ev.clear();
   if (count) *count = g_tl.count;
   return rc;
-}
-
-int pls_kernel_gram(int32_t kernel_kind, const double *x1, int64_t n1, const double *x2, int64_t n2, int64_t d,
-                    const double *lengthscale, double outputscale, double *out, int64_t ldout, void *stream) {
-  PLS_REQUIRE(kernel_kind >= PLS_KERNEL_RBF_ARD && kernel_kind <= PLS_KERNEL_MATERN52, "unknown kernel kind %d", kernel_kind);
-  PLS_REQUIRE(x1 && x2 && out, "kernel_gram: NULL pointer");
-  PLS_REQUIRE(n1 >= 0 && n2 >= 0 && d >= 1, "kernel_gram: bad sizes n1=%lld n2=%lld d=%lld", (long long)n1, (long long)n2, (long long)d);
-  PLS_REQUIRE(d <= 64, "kernel_gram: input dimension %lld > 64 is not supported", (long long)d);
-  PLS_REQUIRE(ldout >= n2, "kernel_gram: ldout < n2");
-  PLS_REQUIRE(kernel_kind == PLS_KERNEL_LINEAR || lengthscale, "kernel_gram: kernel kind %d needs lengthscale", kernel_kind);
-  if (n1 == 0 || n2 == 0) return PLS_OK;
-  PLS_REQUIRE(cdiv(n2, 512) <= 0x7fffffff, "kernel_gram: n2 too large");
-  const int64_t max_rows = 65535LL * GRAM_ROWS;  // gridDim.y <= 65535: taller Gram matrices go in row slabs
-  for (int64_t r0 = 0; r0 < n1; r0 += max_rows) {
-    const int64_t rows = (n1 - r0 < max_rows) ? n1 - r0 : max_rows;
-    dim3 g2((unsigned)cdiv(n2, 512), (unsigned)cdiv(rows, GRAM_ROWS));
-    LaunchScope scope(PLS_TAG_KERNEL_GRAM, S(stream));
-    const double *a = x1 + r0 * d;
-    double *o = out + r0 * ldout;
-    switch (kernel_kind) {
-      case PLS_KERNEL_RBF_ARD: launch_gram<PLS_KERNEL_RBF_ARD>(g2, S(stream), a, rows, x2, n2, (int)d, lengthscale, outputscale, o, ldout); break;
-      case PLS_KERNEL_LINEAR: launch_gram<PLS_KERNEL_LINEAR>(g2, S(stream), a, rows, x2, n2, (int)d, lengthscale, outputscale, o, ldout); break;
-      case PLS_KERNEL_MATERN12: launch_gram<PLS_KERNEL_MATERN12>(g2, S(stream), a, rows, x2, n2, (int)d, lengthscale, outputscale, o, ldout); break;
-      case PLS_KERNEL_MATERN32: launch_gram<PLS_KERNEL_MATERN32>(g2, S(stream), a, rows, x2, n2, (int)d, lengthscale, outputscale, o, ldout); break;
-      default: launch_gram<PLS_KERNEL_MATERN52>(g2, S(stream), a, rows, x2, n2, (int)d, lengthscale, outputscale, o, ldout); break;
-    }
-    int rc = check_launch("kernel_gram");
-    if (rc) return rc;
-  }
-  return PLS_OK;
 }
 
 int pls_gemm_tn(const double *L, int64_t ldl, const double *R, int64_t ldr, double *C, int64_t ldc, int64_t I, int64_t J,

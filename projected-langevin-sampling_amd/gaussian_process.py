@@ -6,8 +6,8 @@ Replaces ``src/gaussian_process/exact_gp.py`` as it is used by ``train_exact_gp`
 (experiments/constructors.py:9-53).  The reference builds these on gpytorch (ConstantMean, ScaleKernel(RBFKernel |
 MaternKernel), GaussianLikelihood, ExactMarginalLogLikelihood); here the model is a plain parameter holder and one
 evaluation of the marginal log-likelihood with its gradient is ONE library call, ``pls_gp_mll_grad_classes``
-(csrc/gp_mll.hip).  One output with a Gaussian likelihood (``ExactGP``: one class, no fixed noise), or classification with the
-Dirichlet likelihood of Milios et al. 2018 as the reference's two classification drivers use it (``DirichletExactGP``: one
+(csrc/gp_mll.hip; its pairwise kernels: csrc/base_kernel.hip).  One output with a Gaussian likelihood (``ExactGP``: one
+class, no fixed noise), or classification with the Dirichlet likelihood of Milios et al. 2018 as the reference's two classification drivers use it (``DirichletExactGP``: one
 GP per class); both are one private base class; no gpytorch objects anywhere."""
 from __future__ import annotations
 
