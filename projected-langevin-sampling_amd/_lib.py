@@ -14,6 +14,7 @@ LIB_PATH = os.environ.get("PLSHIP_LIBRARY") or os.path.join(_HERE, "libplship.so
 # enums (include/plship.h)
 KERNEL_RBF_ARD, KERNEL_LINEAR = 0, 1
 KERNEL_MATERN12, KERNEL_MATERN32, KERNEL_MATERN52 = 2, 3, 4
+KERNEL_RQ = 6  # (5 is not a kind: every entry refuses it as unknown)
 COST_GAUSSIAN, COST_POISSON, COST_BERNOULLI, COST_STUDENT_T, COST_MULTIMODAL = range(5)
 LINK_IDENTITY, LINK_SQUARE, LINK_SIGMOID, LINK_PROBIT = range(4)
 DERIV_REFERENCE, DERIV_AUTOGRAD = 0, 1
@@ -217,11 +218,14 @@ SIGNATURES = {
     "pls_onb_step_blocks_wg": (C.c_int, [_OD, _CD, _P, _P, _I64, _I64, _BD, _ND, _P, _I64, _I32, _I32, _P, _SZ, _P, _P, _SZ, _P]),
     "pls_ipb_step_blocks": (C.c_int, [_ID, _CD, _P, _P, _I64, _I64, _BD, _ND, _P, _I64, _I32, _I32, _P, _P, _SZ, _P]),
     "pls_kernel_grad_sums_workspace_bytes": (_SZ, [_I64, _I64]),
+    "pls_kernel_grad_sums_workspace_bytes_kind": (_SZ, [_I32, _I64, _I64]),
     "pls_kernel_grad_sums": (C.c_int, [_I32, _P, _I64, _I64, _P, _D, _P, _P, _I64, _P, _P, _SZ, _P]),
     "pls_kernel_mean": (C.c_int, [_I32, _P, _I64, _I64, _P, _D, _D, _P, _P, _I64, _P, _P]),
     "pls_gp_mll_workspace_bytes": (_SZ, [_I64, _I64]),
+    "pls_gp_mll_workspace_bytes_kind": (_SZ, [_I32, _I64, _I64]),
     "pls_gp_mll_grad": (C.c_int, [_I32, _P, _I64, _I64, _P, _D, _D, _D, _D, _P, _P, _P, _P, _SZ, _P]),
     "pls_gp_mll_classes_workspace_bytes": (_SZ, [_I64, _I64, _I64]),
+    "pls_gp_mll_classes_workspace_bytes_kind": (_SZ, [_I32, _I64, _I64, _I64]),
     "pls_gp_mll_grad_classes": (C.c_int, [_I32, _P, _I64, _I64, _I64, _P, _P, _P, _P, _P, _I64, _P, _I64, _D, _P, _P, _P, _SZ, _P]),
     "pls_softmax_normal_mean": (C.c_int, [_P, _I64, _P, _I64, _I64, _I64, _I64, _U64, _U64, _P, _I64, _P]),
     "pls_svgp_workspace_bytes": (_SZ, [_I64, _I64, _I64]),

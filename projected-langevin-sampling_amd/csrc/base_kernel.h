@@ -15,12 +15,20 @@ constexpr int PAIR_ROWS = 64, PAIR_COLS = 512, PAIR_D_MAX = 64;
 constexpr int MEAN_POINTS = 64;
 constexpr int mean_chunk(int d_max) { return 4096 / d_max < 512 ? 4096 / d_max : 512; }
 
-// workgroups of the reduction over an n x n matrix = partial rows of d + 1 doubles in its workspace
+// shape parameters of a kind: they follow the d lengthscales in its `lengthscale` argument (RQ: alpha)
+static inline int64_t kind_shape_params(int32_t kind) { return kind == PLS_KERNEL_RQ ? 1 : 0; }
+// sums of the reduction: the kappa sum, one per lengthscale, one per shape parameter
+static inline int64_t grad_sums_count(int32_t kind, int64_t d) { return d + 1 + kind_shape_params(kind); }
+
+// workgroups of the reduction over an n x n matrix = partial rows of grad_sums_count doubles in its workspace
 static inline int64_t grad_sums_blocks(int64_t n) { return cdiv(n, PAIR_COLS) * cdiv(n, PAIR_ROWS); }
-static inline size_t grad_sums_workspace_bytes(int64_t n, int64_t d) { return (size_t)grad_sums_blocks(n) * (size_t)(d + 1) * sizeof(double); }
+static inline size_t grad_sums_workspace_bytes(int32_t kind, int64_t n, int64_t d) {
+  return (size_t)grad_sums_blocks(n) * (size_t)grad_sums_count(kind, d) * sizeof(double);
+}
 
 static inline bool stationary_kind(int32_t kind) {
-  return kind == PLS_KERNEL_RBF_ARD || kind == PLS_KERNEL_MATERN12 || kind == PLS_KERNEL_MATERN32 || kind == PLS_KERNEL_MATERN52;
+  return kind == PLS_KERNEL_RBF_ARD || kind == PLS_KERNEL_MATERN12 || kind == PLS_KERNEL_MATERN32 || kind == PLS_KERNEL_MATERN52 ||
+         kind == PLS_KERNEL_RQ;
 }
 
 // What pls_kernel_grad_sums, pls_gp_mll_grad and pls_gp_mll_grad_classes check alike, each under its own name `who`: the
@@ -52,11 +60,13 @@ static int for_kind_dmax(int kind, int d, F &&f) {
     case PLS_KERNEL_RBF_ARD: return with_kind(integral_constant<int, PLS_KERNEL_RBF_ARD>{});
     case PLS_KERNEL_MATERN12: return with_kind(integral_constant<int, PLS_KERNEL_MATERN12>{});
     case PLS_KERNEL_MATERN32: return with_kind(integral_constant<int, PLS_KERNEL_MATERN32>{});
+    case PLS_KERNEL_RQ: return with_kind(integral_constant<int, PLS_KERNEL_RQ>{});
     default: return with_kind(integral_constant<int, PLS_KERNEL_MATERN52>{});
   }
 }
 
-// inv_ls[k] = sqrt(2 nu) / l_k for a stationary kind (the distance sum is then r^2 or t^2 itself), 1 for the linear kernel,
+// inv_ls[k] = sqrt(2 nu) / l_k for a stationary kind (the distance sum is then r^2 or t^2 itself; RQ keeps r^2 and divides by
+// 2 alpha per pair, so that its derivative factors are the header's), 1 for the linear kernel,
 // 0 for the padding k >= d: zero on both sides of a pair, so the unrolled coordinate loops need no `k < d` test.
 template <int KIND, int D_MAX>
 __device__ __forceinline__ void stage_inv_lengthscale(double (&inv_ls)[D_MAX], const double *lengthscale, int d) {

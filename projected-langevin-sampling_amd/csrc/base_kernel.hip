@@ -1,4 +1,4 @@
-// The pairwise kernels of the base kernel (RBF-ARD, Matern 1/2, 3/2, 5/2; the Gram build also the linear kernel):
+// The pairwise kernels of the base kernel (RBF-ARD, Matern 1/2, 3/2, 5/2, rational quadratic; the Gram build also the linear kernel):
 // pls_kernel_gram, pls_kernel_grad_sums, pls_kernel_mean.  The exact-GP path builds K with the first, differentiates with
 // the second and predicts with the third, so the three evaluate a pair alike: the same pre-scaled points and distance
 // sum (base_kernel.h), the same kappa (kernel_math.h).
@@ -27,6 +27,7 @@ __global__ __launch_bounds__(256) void kernel_gram_kernel(const double *__restri
   const int64_t row0 = (int64_t)blockIdx.y * PAIR_ROWS;
   const int nrows = (int)((n1 - row0 < PAIR_ROWS) ? (n1 - row0) : PAIR_ROWS);
   stage_inv_lengthscale<KIND>(inv_ls, lengthscale, d);
+  const PairShape sh = load_pair_shape<KIND>(lengthscale, d);
   __syncthreads();
   stage_rows(a_s, x1, row0, nrows, d, inv_ls);
   __syncthreads();
@@ -46,8 +47,8 @@ __global__ __launch_bounds__(256) void kernel_gram_kernel(const double *__restri
     double s0 = 0.0, s1 = 0.0;
     if (KIND != PLS_KERNEL_LINEAR) {
       pair_dist2(a_s[r], b0, b1, s0, s1);
-      s0 = gram_entry<KIND>(s0, outputscale);
-      s1 = gram_entry<KIND>(s1, outputscale);
+      s0 = gram_entry<KIND>(s0, sh, outputscale);
+      s1 = gram_entry<KIND>(s1, sh, outputscale);
     } else {
 #pragma unroll
       for (int k = 0; k < D_MAX; ++k) {
@@ -66,10 +67,13 @@ __global__ __launch_bounds__(256) void kernel_gram_kernel(const double *__restri
 }
 
 // The reduction over the n x n pair matrix, laid out as kernel_gram_kernel (a thread owns a PAIR of columns and walks down
-// the rows in LDS).  P is read once, 16 B per lane where ldp is even and P is 16-byte aligned.  D_MAX + 1 accumulators per thread.
+// the rows in LDS).  P is read once, 16 B per lane where ldp is even and P is 16-byte aligned.  D_MAX + 1 accumulators per
+// thread, one more for RQ.
 //   out[0]     = sum_ij W_ij kappa_ij                  (kappa: the kernel without its outputscale)
 //   out[1 + k] = sum_ij W_ij dK_ij / d log l_k         (RBF: s exp(-r^2/2) e_k^2;  Matern: s q(t) exp(-t) 2 nu e_k^2 with
-//                                                       q = 1/t, 1, (1 + t)/3 for nu = 1/2, 3/2, 5/2;  e_k = (x_ik - x_jk)/l_k)
+//                                                       q = 1/t, 1, (1 + t)/3 for nu = 1/2, 3/2, 5/2;  RQ: s kappa / (1 + u) e_k^2;
+//                                                       e_k = (x_ik - x_jk)/l_k)
+//   out[1 + d] = sum_ij W_ij dK_ij / d log alpha       (RQ only: s alpha kappa (u / (1 + u) - log1p(u)), u = r^2 / (2 alpha))
 // with W = alpha alpha^T - P; no atomics: per thread down its rows, then the workgroup sum below, then the workgroups'
 // partial rows in ascending order (a second one-workgroup launch).
 template <int KIND, int D_MAX>
@@ -80,20 +84,23 @@ __global__ __launch_bounds__(256) void kernel_grad_sums_kernel(const double *__r
   __shared__ double inv_ls[D_MAX];
   __shared__ __attribute__((aligned(16))) double a_s[PAIR_ROWS][D_MAX];
   __shared__ double al_s[PAIR_ROWS];
-  __shared__ double red[4][D_MAX + 1];
+  constexpr bool SHAPE = KIND == PLS_KERNEL_RQ;
+  constexpr int NACC = D_MAX + 1 + (SHAPE ? 1 : 0);  // (the shape sum is kept last: acc[D_MAX + 1], written to slot d + 1)
+  __shared__ double red[4][NACC];
   const int t = threadIdx.x;
   const int64_t row0 = (int64_t)blockIdx.y * PAIR_ROWS;
   const int nrows = (int)((n - row0 < PAIR_ROWS) ? (n - row0) : PAIR_ROWS);
   stage_inv_lengthscale<KIND>(inv_ls, lengthscale, d);
+  const PairShape sh = load_pair_shape<KIND>(lengthscale, d);
   if (t < PAIR_ROWS) al_s[t] = (t < nrows) ? alpha[row0 + t] : 0.0;
   __syncthreads();
   stage_rows(a_s, x, row0, nrows, d, inv_ls);
   __syncthreads();
   const int64_t col = ((int64_t)blockIdx.x * 256 + t) * 2;
   const bool one = col < n, two = col + 1 < n;
-  double acc[D_MAX + 1];
+  double acc[NACC];
 #pragma unroll
-  for (int k = 0; k <= D_MAX; ++k) acc[k] = 0.0;
+  for (int k = 0; k < NACC; ++k) acc[k] = 0.0;
   if (one) {
     double b0[D_MAX], b1[D_MAX];
 #pragma unroll
@@ -118,12 +125,13 @@ __global__ __launch_bounds__(256) void kernel_grad_sums_kernel(const double *__r
       const double w0 = __dsub_rn(__dmul_rn(ai, aj0), p0), w1 = __dsub_rn(__dmul_rn(ai, aj1), p1);  // W_ij, two roundings
       double s0, s1;
       pair_dist2(a_s[r], b0, b1, s0, s1);
-      double kap0, g0, kap1, g1;
-      const bool live0 = pair_factors<KIND>(s0, kap0, g0);
-      const bool live1 = pair_factors<KIND>(s1, kap1, g1) && two;
+      double kap0, g0, ga0, kap1, g1, ga1;
+      const bool live0 = pair_factors<KIND>(s0, sh, kap0, g0, ga0);
+      const bool live1 = pair_factors<KIND>(s1, sh, kap1, g1, ga1) && two;
       if (live0) {
         const double gw = w0 * (outputscale * g0);
         acc[0] = fma(w0, kap0, acc[0]);
+        if constexpr (SHAPE) acc[D_MAX + 1] = fma(w0, outputscale * ga0, acc[D_MAX + 1]);
 #pragma unroll
         for (int k = 0; k < D_MAX; ++k) {
           const double e = a_s[r][k] - b0[k];
@@ -133,6 +141,7 @@ __global__ __launch_bounds__(256) void kernel_grad_sums_kernel(const double *__r
       if (live1) {
         const double gw = w1 * (outputscale * g1);
         acc[0] = fma(w1, kap1, acc[0]);
+        if constexpr (SHAPE) acc[D_MAX + 1] = fma(w1, outputscale * ga1, acc[D_MAX + 1]);
 #pragma unroll
         for (int k = 0; k < D_MAX; ++k) {
           const double e = a_s[r][k] - b1[k];
@@ -143,26 +152,28 @@ __global__ __launch_bounds__(256) void kernel_grad_sums_kernel(const double *__r
   }
   // workgroup sum in a fixed order: xor butterfly inside each wave, then (w0 + w1) + (w2 + w3)
 #pragma unroll
-  for (int k = 0; k <= D_MAX; ++k) {
+  for (int k = 0; k < NACC; ++k) {
     double v = acc[k];
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
     if ((t & 63) == 0) red[t >> 6][k] = v;
   }
   __syncthreads();
-  if (t <= d) {
+  const int nsums = d + 1 + (SHAPE ? 1 : 0);
+  if (t < nsums) {
     const int64_t blk = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
-    partials[blk * (d + 1) + t] = (red[0][t] + red[1][t]) + (red[2][t] + red[3][t]);
+    const int k = (SHAPE && t == d + 1) ? D_MAX + 1 : t;
+    partials[blk * nsums + t] = (red[0][k] + red[1][k]) + (red[2][k] + red[3][k]);
   }
 }
 
 // out[k] = the partial rows of the workgroups added in ascending order
-__global__ __launch_bounds__(128) void grad_sums_finish_kernel(const double *__restrict__ partials, int64_t nblocks, int d,
+__global__ __launch_bounds__(128) void grad_sums_finish_kernel(const double *__restrict__ partials, int64_t nblocks, int nsums,
                                                                 double *__restrict__ out) {
   const int k = threadIdx.x;
-  if (k > d) return;
+  if (k >= nsums) return;
   double s = 0.0;
-  for (int64_t b = 0; b < nblocks; ++b) s += partials[b * (d + 1) + k];
+  for (int64_t b = 0; b < nblocks; ++b) s += partials[b * nsums + k];
   out[k] = s;
 }
 
@@ -180,7 +191,8 @@ int grad_sums_launch(int kind, const double *x, int64_t n, int d, const double *
   if (int rc = check_launch("kernel_grad_sums")) return rc;
   {
     LaunchScope scope(PLS_TAG_OTHER, st);
-    hipLaunchKernelGGL(grad_sums_finish_kernel, dim3(1), dim3(128), 0, st, partials, grad_sums_blocks(n), d, out);
+    hipLaunchKernelGGL(grad_sums_finish_kernel, dim3(1), dim3(128), 0, st, partials, grad_sums_blocks(n),
+                       (int)grad_sums_count(kind, d), out);
   }
   return check_launch("grad_sums_finish");
 }
@@ -207,6 +219,7 @@ __global__ __launch_bounds__(256) void kernel_mean_kernel(const double *__restri
   __shared__ double red[4][MEAN_POINTS];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   stage_inv_lengthscale<KIND>(inv_ls, lengthscale, d);
+  const PairShape sh = load_pair_shape<KIND>(lengthscale, d);
   if (D_MAX > 1)  // the padding coordinates stay zero: the staging below writes k < d only
     for (int e = tid; e < CHUNK * D_MAX; e += 256) a_s[e / D_MAX][e % D_MAX] = 0.0;
   __syncthreads();
@@ -252,7 +265,7 @@ __global__ __launch_bounds__(256) void kernel_mean_kernel(const double *__restri
 #pragma unroll 2
     for (int r = w; r < nrows; r += 4) {
       double kap;
-      if (pair_kappa<KIND>(pair_dist2(a_s[r], b), kap)) acc = fma(kap, al_s[r], acc);
+      if (pair_kappa<KIND>(pair_dist2(a_s[r], b), sh, kap)) acc = fma(kap, al_s[r], acc);
     }
     __syncthreads();
   }
@@ -302,7 +315,7 @@ extern "C" {
 
 int pls_kernel_gram(int32_t kernel_kind, const double *x1, int64_t n1, const double *x2, int64_t n2, int64_t d,
                     const double *lengthscale, double outputscale, double *out, int64_t ldout, void *stream) {
-  PLS_REQUIRE(kernel_kind >= PLS_KERNEL_RBF_ARD && kernel_kind <= PLS_KERNEL_MATERN52, "unknown kernel kind %d", kernel_kind);
+  PLS_REQUIRE(kernel_kind == PLS_KERNEL_LINEAR || stationary_kind(kernel_kind), "unknown kernel kind %d", kernel_kind);
   PLS_REQUIRE(x1 && x2 && out, "kernel_gram: NULL pointer");
   PLS_REQUIRE(n1 >= 0 && n2 >= 0 && d >= 1, "kernel_gram: bad sizes n1=%lld n2=%lld d=%lld", (long long)n1, (long long)n2, (long long)d);
   PLS_REQUIRE(d <= PAIR_D_MAX, "kernel_gram: input dimension %lld > 64 is not supported", (long long)d);
@@ -326,15 +339,18 @@ int pls_kernel_gram(int32_t kernel_kind, const double *x1, int64_t n1, const dou
   return PLS_OK;
 }
 
+size_t pls_kernel_grad_sums_workspace_bytes_kind(int32_t kernel_kind, int64_t n, int64_t d) {
+  return (stationary_kind(kernel_kind) && n > 0 && d > 0 && d <= PAIR_D_MAX) ? grad_sums_workspace_bytes(kernel_kind, n, d) : 0;
+}
 size_t pls_kernel_grad_sums_workspace_bytes(int64_t n, int64_t d) {
-  return (n > 0 && d > 0 && d <= PAIR_D_MAX) ? grad_sums_workspace_bytes(n, d) : 0;
+  return pls_kernel_grad_sums_workspace_bytes_kind(PLS_KERNEL_RBF_ARD, n, d);
 }
 
 int pls_kernel_grad_sums(int32_t kernel_kind, const double *x, int64_t n, int64_t d, const double *lengthscale,
                          double outputscale, const double *alpha, const double *P, int64_t ldp, double *out, void *workspace,
                          size_t workspace_bytes, void *stream) {
   if (int rc = gp_check_shared("kernel_grad_sums", kernel_kind, n, d, nullptr, workspace, workspace_bytes,
-                               pls_kernel_grad_sums_workspace_bytes(n, d), 8))
+                               pls_kernel_grad_sums_workspace_bytes_kind(kernel_kind, n, d), 8))
     return rc;
   PLS_REQUIRE(x && lengthscale && alpha && P && out, "kernel_grad_sums: NULL pointer");
   PLS_REQUIRE(ldp >= n, "kernel_grad_sums: ldp < n");

@@ -107,8 +107,13 @@ __device__ __forceinline__ double fast_div(double a, double b) {
 // a double (TAIL) -- the uniform deviates of the noise generator, (n + 1/2) 2^-53 with 0 <= n < 2^53: from n = 2^52 on they
 // have 54 significant bits, and rounded to one double their logarithm is off by 2^-54 / (1 - u) relative, without bound as
 // u -> 1 (and log 1 = 0 for n = 2^53 - 1).  The tail enters f = m - 1, which stays exact; everything after f is shared.
+// The pieces of that evaluation, for a caller that needs more than the logarithm (kernel_math.h: the rational-quadratic
+// kernel's alpha derivative): x + e = 2^k (1 + f), s = f / (2 + f), hfsq = f^2 / 2, R = R(s^2).
+struct LogPieces {
+  double dk, f, s, hfsq, R;
+};
 template <bool TAIL>
-__device__ __forceinline__ double fast_log_unit_pieces(double x, double e) {
+__device__ __forceinline__ LogPieces fast_log_unit_reduce(double x, double e) {
   // (contraction written out: the noise generator is inlined into several kernels, and left to the compiler `t2 + t1` or
   // `dk * ln2 - ...` became an fma in one and a multiply-add pair in another -- 1 ulp apart in one normal deviate per ~6000,
   // so a particle's noise depended on the tiling its shard happened to take)
@@ -119,17 +124,28 @@ __device__ __forceinline__ double fast_log_unit_pieces(double x, double e) {
   m = low ? m + m : m;
   k = low ? k - 1 : k;
   double f = m - 1.0;
-  if constexpr (TAIL) f = f + ldexp(e, -k);  // (m - 1 is exact, and so is the sum: the pieces' f has at most 53 bits)
-  const double dk = (double)k;
-  const double s = fast_div_normal(f, 2.0 + f);
-  const double z = s * s, w = z * z;
+  // (m - 1 is exact, and so is the sum where the pieces' f has at most 53 bits; any other tail costs f one rounding)
+  if constexpr (TAIL) f = f + ldexp(e, -k);
+  LogPieces q;
+  q.dk = (double)k;
+  q.f = f;
+  q.s = fast_div_normal(f, 2.0 + f);
+  const double z = q.s * q.s, w = z * z;
   const double t1 = w * fma_k(w, fma_k(w, 1.531383769920937332e-01, 2.222219843214978396e-01), 3.999999999940941908e-01);
   const double p2 =
       fma_k(w, fma_k(w, fma_k(w, 1.479819860511658591e-01, 1.818357216161805012e-01), 2.857142874366239149e-01),
             6.666666666666735130e-01);
-  const double R = fma(z, p2, t1);
-  const double hfsq = 0.5 * f * f;
-  return fma(dk, 6.93147180369123816490e-01, -((hfsq - fma(s, hfsq + R, dk * 1.90821492927058770002e-10)) - f));
+  q.R = fma(z, p2, t1);
+  q.hfsq = 0.5 * f * f;
+  return q;
+}
+__device__ __forceinline__ double fast_log_unit_combine(const LogPieces &q) {
+#pragma clang fp contract(off)
+  return fma(q.dk, 6.93147180369123816490e-01, -((q.hfsq - fma(q.s, q.hfsq + q.R, q.dk * 1.90821492927058770002e-10)) - q.f));
+}
+template <bool TAIL>
+__device__ __forceinline__ double fast_log_unit_pieces(double x, double e) {
+  return fast_log_unit_combine(fast_log_unit_reduce<TAIL>(x, e));
 }
 
 __device__ __forceinline__ double fast_log_unit(double x) { return fast_log_unit_pieces<false>(x, 0.0); }

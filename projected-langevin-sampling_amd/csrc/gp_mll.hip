@@ -1,7 +1,7 @@
 // Exact-GP marginal log-likelihood and its gradient with respect to the base-kernel hyper-parameters.
 //
 // Reference: mll(model(x), y) and loss.backward() of train_exact_gp (experiments/trainers.py:45-49), i.e. gpytorch's
-// ExactMarginalLogLikelihood of ScaleKernel(RBFKernel | MaternKernel) + GaussianLikelihood with a constant mean.
+// ExactMarginalLogLikelihood of ScaleKernel(RBFKernel | MaternKernel | RQKernel) + GaussianLikelihood with a constant mean.
 //
 //   K_y = s kappa(x, x) + (noise + jitter) I = Lc Lc^T,   r = y - mean,   alpha = K_y^-1 r,   W = alpha alpha^T - K_y^-1
 //   mll = -1/2 r^T alpha - sum_i log Lc_ii - n/2 log 2 pi,                d mll / d theta = 1/2 sum_ij W_ij dK_ij / d theta
@@ -9,7 +9,7 @@
 // The Gram build, the factorisation, the solve, the inverse factor and K_y^-1 = Linv^T Linv are the library's existing
 // kernels; the reduction over all n^2 pairs is kernel_grad_sums_kernel (base_kernel.hip): one pass over P (= K_y^-1) that
 // recomputes kappa and its lengthscale derivatives from x and leaves the d + 1 sums sum_ij W_ij kappa_ij and
-// sum_ij W_ij dK_ij / d log l_k in a fixed summation order.
+// sum_ij W_ij dK_ij / d log l_k in a fixed summation order (RQ: d + 2, the last is sum_ij W_ij dK_ij / d log alpha).
 //
 // Classification (gpytorch's DirichletClassificationLikelihood, Milios et al. 2018): one such GP per class on the shared
 // x, K_y,c = s_c kappa(x, x; l_c) + diag(v_c) + sigma_c I with a fixed noise v_c per point -- pls_gp_mll_grad_classes runs
@@ -45,8 +45,9 @@ __device__ __forceinline__ double block256_sum(double v, double (*ws)[4], int sl
 }
 
 // The value and the 3 + d derivatives from the pieces (one workgroup): thread t adds entries t, t + 256, ... in ascending
-// order, then block256_sum.  sums: the d + 1 outputs of the reduction with P = K_y^-1.
-__global__ __launch_bounds__(256) void gp_mll_finish_kernel(int64_t n, int d, double outputscale, const double *__restrict__ r,
+// order, then block256_sum.  sums: the nsums outputs of the reduction with P = K_y^-1 (d + 1; RQ: d + 2, whose last becomes
+// the derivative with respect to log alpha, out[4 + d]).
+__global__ __launch_bounds__(256) void gp_mll_finish_kernel(int64_t n, int nsums, double outputscale, const double *__restrict__ r,
                                                              const double *__restrict__ alpha, const double *__restrict__ Lc,
                                                              int64_t ldlc, const double *__restrict__ P, int64_t ldp,
                                                              const double *__restrict__ sums, double *__restrict__ out) {
@@ -69,21 +70,21 @@ __global__ __launch_bounds__(256) void gp_mll_finish_kernel(int64_t n, int d, do
     out[2] = 0.5 * tw;
     out[3] = 0.5 * outputscale * sums[0];
   }
-  if ((int)threadIdx.x < d) out[4 + threadIdx.x] = 0.5 * sums[1 + threadIdx.x];
+  if ((int)threadIdx.x < nsums - 1) out[4 + threadIdx.x] = 0.5 * sums[1 + threadIdx.x];
 }
 
 struct GpMllPlan {  // offsets in doubles into the workspace of pls_gp_mll_grad
   int64_t ld, plane, r, alpha, partials, sums, total;
 };
-static GpMllPlan gp_mll_plan(int64_t n, int64_t d) {
+static GpMllPlan gp_mll_plan(int32_t kind, int64_t n, int64_t d) {
   GpMllPlan p;
   p.ld = gp_mll_ld(n);
   p.plane = n * p.ld;
   p.r = 7 * p.plane;
   p.alpha = p.r + gp_mll_vec(n);
   p.partials = p.alpha + gp_mll_vec(n);
-  p.sums = p.partials + gp_mll_vec(grad_sums_blocks(n) * (d + 1));
-  p.total = p.sums + gp_mll_vec(d + 1);
+  p.sums = p.partials + gp_mll_vec(grad_sums_blocks(n) * grad_sums_count(kind, d));
+  p.total = p.sums + gp_mll_vec(grad_sums_count(kind, d));
   return p;
 }
 
@@ -106,7 +107,7 @@ static int gp_mll_evaluate(int32_t kernel_kind, const double *x, int64_t n, int6
                            double outputscale, double noise, double mean, double jitter, const double *fixed, const double *y,
                            double *out, int32_t *info, double *w, void *stream) {
   hipStream_t st = S(stream);
-  const GpMllPlan p = gp_mll_plan(n, d);
+  const GpMllPlan p = gp_mll_plan(kernel_kind, n, d);
   double *Ky = w, *Lc = w + p.plane, *LcT = w + 2 * p.plane, *Sf = w + 3 * p.plane, *Sb = w + 4 * p.plane;
   double *Linv = w + 5 * p.plane, *LinvT = w + 6 * p.plane;
   double *r = w + p.r, *al = w + p.alpha, *partials = w + p.partials, *sums = w + p.sums;
@@ -138,23 +139,26 @@ static int gp_mll_evaluate(int32_t kernel_kind, const double *x, int64_t n, int6
   if (rc) return rc;
   rc = gemm_tn_ex(Linv, p.ld, Linv, p.ld, Ky, p.ld, n, n, n, 1.0, 0.0, 2, st);
   if (rc) return rc;
-  // 5. the d + 1 sums with P = K_y^-1
+  // 5. the d + 1 sums (RQ: d + 2) with P = K_y^-1
   rc = grad_sums_launch(kernel_kind, x, n, (int)d, lengthscale, outputscale, al, Ky, p.ld, sums, partials, st);
   if (rc) return rc;
   // 6. value and derivatives
-  hipLaunchKernelGGL(gp_mll_finish_kernel, dim3(1), dim3(256), 0, st, n, (int)d, outputscale, r, al, Lc, p.ld, Ky, p.ld, sums, out);
+  hipLaunchKernelGGL(gp_mll_finish_kernel, dim3(1), dim3(256), 0, st, n, (int)grad_sums_count(kernel_kind, d), outputscale, r,
+                     al, Lc, p.ld, Ky, p.ld, sums, out);
   return check_launch("gp_mll_finish");
 }
 
 // The C >= 1 evaluations of both pls_gp_mll_grad entries, one after another in the shared workspace w (arguments already
-// validated); fixed == NULL: no fixed noise
+// validated); fixed == NULL: no fixed noise.  A class's row of `lengthscale` holds its shape parameters behind its d
+// lengthscales, its row of `out` their derivatives behind the d lengthscale derivatives.
 static int gp_mll_evaluate_classes(int32_t kernel_kind, const double *x, int64_t n, int64_t d, int64_t classes,
                                    const double *lengthscale, const double *outputscale, const double *noise, const double *mean,
                                    const double *fixed, int64_t ldf, const double *y, int64_t ldy, double jitter, double *out,
                                    int32_t *info, double *w, void *stream) {
+  const int64_t extra = kind_shape_params(kernel_kind);
   for (int64_t c = 0; c < classes; ++c) {
-    const int rc = gp_mll_evaluate(kernel_kind, x, n, d, lengthscale + c * d, outputscale[c], noise[c], mean[c], jitter,
-                                   fixed ? fixed + c * ldf : nullptr, y + c * ldy, out + c * (4 + d), info + c, w, stream);
+    const int rc = gp_mll_evaluate(kernel_kind, x, n, d, lengthscale + c * (d + extra), outputscale[c], noise[c], mean[c], jitter,
+                                   fixed ? fixed + c * ldf : nullptr, y + c * ldy, out + c * (4 + d + extra), info + c, w, stream);
     if (rc) return rc;
   }
   return PLS_OK;
@@ -256,16 +260,19 @@ using namespace plship;
 
 extern "C" {
 
-size_t pls_gp_mll_workspace_bytes(int64_t n, int64_t d) {
-  return (n > 0 && d > 0 && d <= PAIR_D_MAX) ? (size_t)gp_mll_plan(n, d).total * sizeof(double) : 0;
+size_t pls_gp_mll_workspace_bytes_kind(int32_t kernel_kind, int64_t n, int64_t d) {
+  return (stationary_kind(kernel_kind) && n > 0 && d > 0 && d <= PAIR_D_MAX)
+             ? (size_t)gp_mll_plan(kernel_kind, n, d).total * sizeof(double)
+             : 0;
 }
+size_t pls_gp_mll_workspace_bytes(int64_t n, int64_t d) { return pls_gp_mll_workspace_bytes_kind(PLS_KERNEL_RBF_ARD, n, d); }
 
 // pls_gp_mll_grad_classes with one class and no fixed noise: the scalars go in as arrays of one
 int pls_gp_mll_grad(int32_t kernel_kind, const double *x, int64_t n, int64_t d, const double *lengthscale, double outputscale,
                     double noise, double mean, double jitter, const double *y, double *out, int32_t *info, void *workspace,
                     size_t workspace_bytes, void *stream) {
   if (int rc = gp_check_shared("gp_mll_grad", kernel_kind, n, d, nullptr, workspace, workspace_bytes,
-                               pls_gp_mll_workspace_bytes(n, d), 16))
+                               pls_gp_mll_workspace_bytes_kind(kernel_kind, n, d), 16))
     return rc;
   PLS_REQUIRE(x && lengthscale && y && out && info, "gp_mll_grad: NULL pointer");
   PLS_REQUIRE(jitter >= 0.0, "gp_mll_grad: jitter must be >= 0");
@@ -274,8 +281,11 @@ int pls_gp_mll_grad(int32_t kernel_kind, const double *x, int64_t n, int64_t d, 
                                  info, static_cast<double *>(workspace), stream);
 }
 
+size_t pls_gp_mll_classes_workspace_bytes_kind(int32_t kernel_kind, int64_t n, int64_t d, int64_t classes) {
+  return classes > 0 ? pls_gp_mll_workspace_bytes_kind(kernel_kind, n, d) : 0;  // the classes run one after another and share the planes
+}
 size_t pls_gp_mll_classes_workspace_bytes(int64_t n, int64_t d, int64_t classes) {
-  return classes > 0 ? pls_gp_mll_workspace_bytes(n, d) : 0;  // the classes run one after another and share the planes
+  return pls_gp_mll_classes_workspace_bytes_kind(PLS_KERNEL_RBF_ARD, n, d, classes);
 }
 
 int pls_gp_mll_grad_classes(int32_t kernel_kind, const double *x, int64_t n, int64_t d, int64_t classes,
@@ -283,7 +293,7 @@ int pls_gp_mll_grad_classes(int32_t kernel_kind, const double *x, int64_t n, int
                             const double *fixed_noise, int64_t ldf, const double *y, int64_t ldy, double jitter, double *out,
                             int32_t *info, void *workspace, size_t workspace_bytes, void *stream) {
   if (int rc = gp_check_shared("gp_mll_grad_classes", kernel_kind, n, d, &classes, workspace, workspace_bytes,
-                               pls_gp_mll_classes_workspace_bytes(n, d, classes), 16))
+                               pls_gp_mll_classes_workspace_bytes_kind(kernel_kind, n, d, classes), 16))
     return rc;
   PLS_REQUIRE(x && lengthscale && outputscale && noise && mean && y && out && info, "gp_mll_grad_classes: NULL pointer");
   PLS_REQUIRE(ldy >= n, "gp_mll_grad_classes: ldy < n");

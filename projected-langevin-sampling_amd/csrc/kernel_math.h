@@ -50,11 +50,56 @@ __device__ __forceinline__ double matern_poly(int kind, double t) {
   return (kind == PLS_KERNEL_MATERN12) ? 1.0 : (kind == PLS_KERNEL_MATERN32) ? 1.0 + t : fma(t, fma(t, 1.0 / 3.0, 1.0), 1.0);
 }
 
-// One pair from its distance sum s2 (RBF: r^2; Matern: t^2 = 2 nu r^2): kap = kappa, the kernel without its outputscale;
-// t = sqrt(s2) (Matern only) and ex, the exponential inside kappa, for pair_factors.  Returns false for a pair whose
-// exponential underflows: kap is meaningless then and the caller lets the pair contribute exactly 0.  A NaN stays NaN.
+// The shape parameter of a kind that has one -- RQ's alpha, which follows the d lengthscales in every `lengthscale`
+// argument -- read once per thread; empty for the other kinds.
+struct PairShape {
+  double alpha, inv_2alpha;
+};
+template <int KIND>
+__device__ __forceinline__ PairShape load_pair_shape(const double *__restrict__ lengthscale, int d) {
+  if (KIND != PLS_KERNEL_RQ) return PairShape{0.0, 0.0};
+  const double alpha = lengthscale[d];
+  return PairShape{alpha, 0.5 / alpha};
+}
+
+// Rational quadratic (gpytorch's RQKernel times the outputscale): u = r^2 / (2 alpha), kappa = (1 + u)^-alpha =
+// exp(-alpha log1p(u)).  log1p: w = fl(1 + u) and e, the exact rounding error of that sum (TwoSum), go to the two-piece
+// logarithm of fmath.h -- about 1 ulp down to u -> 0, and log1p(0) = 0, so that kappa = 1 exactly at distance 0.  Dead where
+// the exponent underflows or 1 + u overflows (r = inf included): only a large alpha kills a pair, at alpha = ln 2 a point
+// 1e4 lengthscales away still has kappa = 3e-6.  q: the pieces of the logarithm, L: log1p(u), for rq_factors.
+__device__ __forceinline__ bool rq_kappa(double s2, const PairShape &sh, double &kap, double &u, double &w, LogPieces &q,
+                                         double &L) {
+  u = s2 * sh.inv_2alpha;
+  w = 1.0 + u;
+  const double bb = w - 1.0;
+  const double e = (1.0 - (w - bb)) + (u - bb);
+  q = fast_log_unit_reduce<true>(w, e);
+  L = fast_log_unit_combine(q);
+  const double x = -sh.alpha * L;
+  kap = exp_nonpos_unguarded(x);
+  return !(x < -745.2) && w != __builtin_huge_val();
+}
+// g: dK_ij / d log l_k = outputscale * g * e_k^2 with g = kappa / (1 + u);  ga: dK_ij / d log alpha = outputscale * ga with
+// ga = alpha kappa h, h = u / (1 + u) - log1p(u).  h is -u^2 / 2 for small u, where its two terms cancel; there (w < sqrt 2:
+// the logarithm's k = 0 and f = u) it is put together from the logarithm's own pieces, log1p(u) = f - hfsq + s (hfsq + R) and
+// u / (1 + u) = f - f^2 / (1 + f), so h = hfsq - f^2 / (1 + f) - s (hfsq + R): three terms of size f^2 that cancel to a
+// quarter of their sum at the worst, and exactly 0 at distance 0.  From sqrt 2 on the plain difference loses at most 4 bits.
+__device__ __forceinline__ void rq_factors(const PairShape &sh, double kap, double u, double w, const LogPieces &q, double L,
+                                           double &g, double &ga) {
+#pragma clang fp contract(off)
+  const double rw = fast_div_normal(1.0, w);
+  g = kap * rw;
+  const double h = (q.dk == 0.0) ? (q.hfsq - (q.f * q.f) * rw) - q.s * (q.hfsq + q.R) : u * rw - L;
+  ga = sh.alpha * kap * h;
+}
+
+// One pair from its distance sum s2 (RBF: r^2; Matern: t^2 = 2 nu r^2; RQ: r^2, with its shape sh): kap = kappa, the kernel
+// without its outputscale; t = sqrt(s2) (Matern only) and ex, the exponential inside kappa, for pair_factors.  Returns
+// false for a pair whose exponential underflows: kap is meaningless then and the caller lets the pair contribute exactly
+// 0.  A NaN stays NaN.
 template <int KIND>
 __device__ __forceinline__ bool pair_kappa(double s2, double &kap, double &t, double &ex) {
+  static_assert(KIND != PLS_KERNEL_RQ, "the rational-quadratic pair goes through rq_kappa");
   t = (KIND == PLS_KERNEL_RBF_ARD) ? 0.0 : sqrt(s2);
   const double x = (KIND == PLS_KERNEL_RBF_ARD) ? -0.5 * s2 : -t;  // the exponent
   const double p = (KIND == PLS_KERNEL_RBF_ARD) ? 1.0 : matern_poly(KIND, t);
@@ -63,29 +108,45 @@ __device__ __forceinline__ bool pair_kappa(double s2, double &kap, double &t, do
   return !(x < -745.2);
 }
 template <int KIND>
-__device__ __forceinline__ bool pair_kappa(double s2, double &kap) {
-  double t, ex;
-  return pair_kappa<KIND>(s2, kap, t, ex);
+__device__ __forceinline__ bool pair_kappa(double s2, const PairShape &sh, double &kap) {
+  if constexpr (KIND == PLS_KERNEL_RQ) {
+    double u, w, L;
+    LogPieces q;
+    return rq_kappa(s2, sh, kap, u, w, q, L);
+  } else {
+    double t, ex;
+    return pair_kappa<KIND>(s2, kap, t, ex);
+  }
 }
 
-// pair_kappa plus g: dK_ij / d log l_k = outputscale * g * e'_k^2 with e'_k the pre-scaled difference.  A dead pair's
-// e'_k^2 may be inf (0 * inf would be NaN), so the caller skips it.
+// pair_kappa plus g: dK_ij / d log l_k = outputscale * g * e'_k^2 with e'_k the pre-scaled difference, and ga (RQ; 0
+// otherwise): dK_ij / d log alpha = outputscale * ga.  A dead pair's e'_k^2 may be inf (0 * inf would be NaN), so the
+// caller skips it.
 template <int KIND>
-__device__ __forceinline__ bool pair_factors(double s2, double &kap, double &g) {
-  double t, ex;
-  const bool live = pair_kappa<KIND>(s2, kap, t, ex);
-  if (KIND == PLS_KERNEL_RBF_ARD || KIND == PLS_KERNEL_MATERN32) g = ex;
-  else if (KIND == PLS_KERNEL_MATERN12) g = (t > 0.0) ? ex / t : 0.0;  // r = 0: every e_k is 0 and the pair contributes 0
-  else g = ex * ((1.0 + t) * (1.0 / 3.0));
-  return live;
+__device__ __forceinline__ bool pair_factors(double s2, const PairShape &sh, double &kap, double &g, double &ga) {
+  ga = 0.0;
+  if constexpr (KIND == PLS_KERNEL_RQ) {
+    double u, w, L;
+    LogPieces q;
+    const bool live = rq_kappa(s2, sh, kap, u, w, q, L);
+    rq_factors(sh, kap, u, w, q, L, g, ga);
+    return live;
+  } else {
+    double t, ex;
+    const bool live = pair_kappa<KIND>(s2, kap, t, ex);
+    if (KIND == PLS_KERNEL_RBF_ARD || KIND == PLS_KERNEL_MATERN32) g = ex;
+    else if (KIND == PLS_KERNEL_MATERN12) g = (t > 0.0) ? ex / t : 0.0;  // r = 0: every e_k is 0 and the pair contributes 0
+    else g = ex * ((1.0 + t) * (1.0 / 3.0));
+    return live;
+  }
 }
 
-// The Gram entry: outputscale * kappa, 0 for a dead pair.  RBF multiplies the outputscale into the selected 0 and Matern
-// selects after the multiply, so a negative outputscale leaves -0 (RBF) or +0 (Matern) there, as it always has.
+// The Gram entry: outputscale * kappa, 0 for a dead pair.  RBF multiplies the outputscale into the selected 0 and the
+// others select after the multiply, so a negative outputscale leaves -0 (RBF) or +0 there, as it always has.
 template <int KIND>
-__device__ __forceinline__ double gram_entry(double s2, double outputscale) {
+__device__ __forceinline__ double gram_entry(double s2, const PairShape &sh, double outputscale) {
   double kap;
-  const bool live = pair_kappa<KIND>(s2, kap);
+  const bool live = pair_kappa<KIND>(s2, sh, kap);
   if (KIND == PLS_KERNEL_RBF_ARD) return outputscale * (live ? kap : 0.0);
   return live ? outputscale * kap : 0.0;
 }

@@ -1268,8 +1268,17 @@ struct CvState {       // device-resident scalars of the selection loop
 };
 
 __device__ inline double cv_kernel_eval(int kind, const double *__restrict__ x, int64_t a, int64_t b, int d,
-                                        const double *__restrict__ inv_ls, double outputscale) {
+                                        const double *__restrict__ inv_ls, double shape, double outputscale) {
   double s = 0.0;
+  if (kind == PLS_KERNEL_RQ) {  // shape = alpha; library log1p and exp as below: exactly the outputscale at distance 0
+    for (int k = 0; k < d; ++k) {
+      const double e = (x[a * d + k] - x[b * d + k]) * inv_ls[k];
+      s = fma(e, e, s);
+    }
+    const double ex = -shape * log1p(s / (2.0 * shape));
+    const double v = outputscale * exp(ex);
+    return (ex < -745.2 || s == __builtin_huge_val()) ? 0.0 : v;
+  }
   if (kind == PLS_KERNEL_RBF_ARD) {
     for (int k = 0; k < d; ++k) {
       const double e = (x[a * d + k] - x[b * d + k]) * inv_ls[k];
@@ -1301,6 +1310,7 @@ __global__ __launch_bounds__(CV_BLOCK) void cv_init_kernel(int kind, const doubl
                                                             unsigned char *__restrict__ chosen, CvState *st) {
   __shared__ double inv_ls[64];
   if ((int)threadIdx.x < d) inv_ls[threadIdx.x] = (kind != PLS_KERNEL_LINEAR) ? 1.0 / lengthscale[threadIdx.x] : 1.0;
+  const double shape = (kind == PLS_KERNEL_RQ) ? lengthscale[d] : 0.0;
   __syncthreads();
   const int64_t i = (int64_t)blockIdx.x * CV_BLOCK + threadIdx.x;
   if (i == 0) {
@@ -1308,7 +1318,7 @@ __global__ __launch_bounds__(CV_BLOCK) void cv_init_kernel(int kind, const doubl
     st->stopped = 0;
   }
   if (i >= n) return;
-  di[i] = cv_kernel_eval(kind, x, i, i, d, inv_ls, outputscale) + jitter;
+  di[i] = cv_kernel_eval(kind, x, i, i, d, inv_ls, shape, outputscale) + jitter;
   chosen[i] = 0;
 }
 
@@ -1416,6 +1426,7 @@ __global__ __launch_bounds__(CV_BLOCK) void cv_update_kernel(int kind, const dou
   __shared__ double inv_ls[64];
   __shared__ double part[NSL][CV_COLS];
   if ((int)threadIdx.x < d) inv_ls[threadIdx.x] = (kind != PLS_KERNEL_LINEAR) ? 1.0 / lengthscale[threadIdx.x] : 1.0;
+  const double shape = (kind == PLS_KERNEL_RQ) ? lengthscale[d] : 0.0;
   __syncthreads();
   if (st->stopped || st->count != iter + 1) return;  // (stopped early, or ran out of candidates; uniform)
   const int64_t j = st->pivot;
@@ -1437,7 +1448,7 @@ __global__ __launch_bounds__(CV_BLOCK) void cv_update_kernel(int kind, const dou
   double dot = part[0][c];
 #pragma unroll
   for (int k = 1; k < NSL; ++k) dot += part[k][c];
-  double g = cv_kernel_eval(kind, x, col, j, d, inv_ls, outputscale);
+  double g = cv_kernel_eval(kind, x, col, j, d, inv_ls, shape, outputscale);
   g = rint(g * 1e20) / 1e20;  // np.round(., 20) (conditional_variance.py:93)
   if (col == j) g += jitter;
   const double e = (g - dot) / dj;
@@ -3179,7 +3190,8 @@ int pls_select_inducing_conditional_variance(int32_t kernel_kind, const double *
                                              const double *lengthscale, double outputscale, int64_t m, double jitter,
                                              double threshold, int64_t *indices, int64_t *count, void *workspace,
                                              size_t workspace_bytes, void *stream) {
-  PLS_REQUIRE(kernel_kind >= PLS_KERNEL_RBF_ARD && kernel_kind <= PLS_KERNEL_MATERN52, "unknown kernel kind %d", kernel_kind);
+  PLS_REQUIRE((kernel_kind >= PLS_KERNEL_RBF_ARD && kernel_kind <= PLS_KERNEL_MATERN52) || kernel_kind == PLS_KERNEL_RQ,
+              "unknown kernel kind %d", kernel_kind);
   PLS_REQUIRE(x && indices && count, "select_inducing: NULL pointer");
   PLS_REQUIRE(m > 1, "select_inducing: Must have at least 2 inducing points");  // conditional_variance.py:57
   PLS_REQUIRE(n >= m && d >= 1 && d <= 64, "select_inducing: need n >= m and 1 <= d <= 64");

@@ -4,7 +4,7 @@ hyper-parameters, inducing points, PLS, metrics).
 Replaces ``src/gaussian_process/exact_gp.py`` as it is used by ``train_exact_gp`` (experiments/trainers.py:15-52),
 ``exact_gp_runner`` / ``load_subsample_data`` (experiments/runners.py:66-187) and the two averaging constructors
 (experiments/constructors.py:9-53).  The reference builds these on gpytorch (ConstantMean, ScaleKernel(RBFKernel |
-MaternKernel), GaussianLikelihood, ExactMarginalLogLikelihood); here the model is a plain parameter holder and one
+MaternKernel | RQKernel), GaussianLikelihood, ExactMarginalLogLikelihood); here the model is a plain parameter holder and one
 evaluation of the marginal log-likelihood with its gradient is ONE library call, ``pls_gp_mll_grad_classes``
 (csrc/gp_mll.hip; its pairwise kernels: csrc/base_kernel.hip).  One output with a Gaussian likelihood (``ExactGP``: one
 class, no fixed noise), or classification with the Dirichlet likelihood of Milios et al. 2018 as the reference's two classification drivers use it (``DirichletExactGP``: one
@@ -21,7 +21,7 @@ import torch
 from . import _lib as L
 from . import _ops
 from ._chol import CHOLESKY_JITTER, CHOLESKY_MAX_TRIES, NotPSDError, cholesky_factor
-from .kernel import ARDKernel, BaseKernel, MaternKernel, _dev
+from .kernel import ARDKernel, BaseKernel, MaternKernel, RQKernel, _dev
 from .likelihoods import GaussianLikelihood, _Likelihood
 from .trainers import EarlyStopper
 from .utils import set_seed
@@ -30,7 +30,7 @@ from .utils import set_seed
 NOISE_LOWER_BOUND = 1e-4
 
 _KERNEL_NAMES = {"rbf": ("rbf", None), "matern": ("matern", None), "matern12": ("matern", 0.5), "matern32": ("matern", 1.5),
-                 "matern52": ("matern", 2.5)}
+                 "matern52": ("matern", 2.5), "rq": ("rq", None)}
 
 
 def _softplus(v: torch.Tensor) -> torch.Tensor:
@@ -46,10 +46,11 @@ def _kernel_choice(who: str, kernel, nu: float, ard: bool, d: int):
     the raw parameters start from, or None"""
     start = None
     if isinstance(kernel, BaseKernel):
-        if not isinstance(kernel, (ARDKernel, MaternKernel)):
-            raise TypeError(f"{who}: the kernel must be an ARDKernel or a MaternKernel (a lengthscale and an outputscale to learn)")
+        if not isinstance(kernel, (ARDKernel, MaternKernel, RQKernel)):
+            raise TypeError(f"{who}: the kernel must be an ARDKernel, a MaternKernel or an RQKernel (a lengthscale and an "
+                            "outputscale to learn)")
         start = kernel
-        name, nu = ("matern", kernel.nu) if isinstance(kernel, MaternKernel) else ("rbf", nu)
+        name, nu = ("matern", kernel.nu) if isinstance(kernel, MaternKernel) else ("rq" if isinstance(kernel, RQKernel) else "rbf", nu)
         ard = kernel.lengthscale.numel() > 1 or d == 1 and ard
     else:
         if kernel not in _KERNEL_NAMES:
@@ -66,7 +67,8 @@ class _ExactGPClasses:
     K_c = s_c kappa(x, x; l_c) and K_y,c = K_c + diag(v_c) + sigma_c I, parametrised as gpytorch does: ``lengthscale =
     softplus(raw)``, ``outputscale = softplus(raw)``, ``noise = 1e-4 + softplus(raw)``, the mean constant itself; every raw
     value starts at 0.  ``raw`` is seen as (C, 3 + nls) rows: mean, raw noise, raw outputscale, raw lengthscales (d of
-    them, or one shared by all dimensions).  x (n, d), the targets (C, n) and the fixed noise v (C, n), or None, are kept
+    them, or one shared by all dimensions); the rational-quadratic kernel has (C, 4 + nls): raw alpha, ``alpha =
+    softplus(raw)``, is its LAST column.  x (n, d), the targets (C, n) and the fixed noise v (C, n), or None, are kept
     as given and uploaded once, on the first evaluation on the device.  One evaluation of all classes is ONE library call
     with one read-back, ``pls_gp_mll_grad_classes``."""
 
@@ -78,13 +80,16 @@ class _ExactGPClasses:
         self._targets, self.fixed_noise = targets, fixed_noise
         name, nu, ard, start = _kernel_choice(who, kernel, nu, ard, self.d)
         self.kernel_name, self.ard, self.nu = name, ard, nu
-        self.kind = MaternKernel.KINDS[self.nu] if name == "matern" else L.KERNEL_RBF_ARD
+        self.kind = MaternKernel.KINDS[self.nu] if name == "matern" else L.KERNEL_RQ if name == "rq" else L.KERNEL_RBF_ARD
         nls = self.d if self.ard else 1
-        raw = torch.zeros(targets.shape[0], 3 + nls, dtype=torch.float64)
+        self._nshape = 1 if name == "rq" else 0  # shape parameters behind the lengthscales: raw alpha
+        raw = torch.zeros(targets.shape[0], 3 + nls + self._nshape, dtype=torch.float64)
         if start is not None:
             assert start.lengthscale.numel() in (1, nls), "the kernel's lengthscales do not fit the data"
             raw[:, 2] = _inverse_softplus(torch.tensor(start.outputscale, dtype=torch.float64))
-            raw[:, 3:] = _inverse_softplus(start.lengthscale.expand(nls) if start.lengthscale.numel() == 1 else start.lengthscale)
+            raw[:, 3:3 + nls] = _inverse_softplus(start.lengthscale.expand(nls) if start.lengthscale.numel() == 1 else start.lengthscale)
+            if self._nshape:
+                raw[:, -1] = _inverse_softplus(torch.tensor(start.alpha, dtype=torch.float64))
         self.raw = torch.nn.Parameter(raw)
         self._dev: dict = {}
 
@@ -103,9 +108,25 @@ class _ExactGPClasses:
     def _natural(self) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
         """(mean constant (C), noise (C), outputscale (C), lengthscale (C, d): a shared one repeated)"""
         raw = self.raw.detach().reshape(self._targets.shape[0], -1)
-        ls = _softplus(raw[:, 3:])
+        ls = _softplus(raw[:, 3:raw.shape[1] - self._nshape])
         ls = ls.expand(-1, self.d).clone() if ls.shape[1] == 1 and self.d > 1 else ls
         return raw[:, 0].clone(), NOISE_LOWER_BOUND + _softplus(raw[:, 1]), _softplus(raw[:, 2]), ls
+
+    def _alpha(self) -> torch.Tensor:
+        """(C) the rational-quadratic shape alpha = softplus(raw alpha)"""
+        if not self._nshape:
+            raise AttributeError(f"the {self.kernel_name} kernel has no alpha")
+        return _softplus(self.raw.detach().reshape(self._targets.shape[0], -1)[:, -1])
+
+    @property
+    def alpha(self) -> torch.Tensor:
+        """(C) the shape of the rational-quadratic kernel; AttributeError for the other kernels"""
+        return self._alpha()
+
+    def _library_lengthscale(self) -> torch.Tensor:
+        """(C, d) lengthscales as the library reads them; rational quadratic: (C, d + 1), alpha last"""
+        ls = self._natural()[3]
+        return torch.cat([ls, self._alpha()[:, None]], dim=1) if self._nshape else ls
 
     @property
     def mean_constant(self) -> torch.Tensor:
@@ -125,49 +146,60 @@ class _ExactGPClasses:
         """(C, d) lengthscales (a shared one repeated)."""
         return self._natural()[3]
 
-    def _make_kernel(self, lengthscale: torch.Tensor, outputscale: float) -> BaseKernel:
+    def _make_kernel(self, lengthscale: torch.Tensor, outputscale: float, alpha: float | None = None) -> BaseKernel:
         if self.kernel_name == "matern":
             return MaternKernel(lengthscale, outputscale, nu=self.nu)
+        if self.kernel_name == "rq":
+            return RQKernel(lengthscale, outputscale, alpha=alpha)
         return ARDKernel(lengthscale, outputscale)
+
+    def _class_kernel(self, c: int) -> BaseKernel:
+        """the kernel of class c at the current parameters"""
+        _, _, s, ls = self._natural()
+        return self._make_kernel(ls[c], float(s[c]), float(self._alpha()[c]) if self._nshape else None)
 
     # ---- the loss ---------------------------------------------------------------------------------------------------
     def chain_rule(self, out: torch.Tensor) -> Tuple[float, torch.Tensor]:
         """(-sum_c mll_c / n, its gradient with respect to ``raw``, in the shape of ``raw``) from the (C, 4 + d) outputs of
-        pls_gp_mll_grad_classes (per class: value, d/d mean, d/d noise, d/d log outputscale, d/d log lengthscale_k) at the
-        current parameters: host arithmetic only."""
+        pls_gp_mll_grad_classes (per class: value, d/d mean, d/d noise, d/d log outputscale, d/d log lengthscale_k; rational
+        quadratic: (C, 5 + d), d/d log alpha last) at the current parameters: host arithmetic only."""
         raw = self.raw.detach().reshape(self._targets.shape[0], -1)
         out = torch.as_tensor(out, dtype=torch.float64)
-        assert out.numel() == raw.shape[0] * (4 + self.d)
-        out = out.reshape(raw.shape[0], 4 + self.d)
+        width, nls = 4 + self.d + self._nshape, raw.shape[1] - 3 - self._nshape
+        assert out.numel() == raw.shape[0] * width
+        out = out.reshape(raw.shape[0], width)
         slope = torch.sigmoid(raw)  # d softplus(raw) / d raw
         g = torch.empty_like(raw)
         g[:, 0] = out[:, 1]
         g[:, 1] = out[:, 2] * slope[:, 1]
         g[:, 2] = out[:, 3] / _softplus(raw[:, 2]) * slope[:, 2]
-        per_dim = out[:, 4:] / self._natural()[3]
-        g[:, 3:] = (per_dim if self.ard else per_dim.sum(dim=1, keepdim=True)) * slope[:, 3:]
+        per_dim = out[:, 4:4 + self.d] / self._natural()[3]
+        g[:, 3:3 + nls] = (per_dim if self.ard else per_dim.sum(dim=1, keepdim=True)) * slope[:, 3:3 + nls]
+        if self._nshape:
+            g[:, -1] = out[:, -1] / self._alpha() * slope[:, -1]
         return -float(out[:, 0].sum()) / self.n, (-g / self.n).reshape(self.raw.shape)
 
     def _device_state(self) -> dict:
         if not self._dev:
             x = _dev(self.x)
-            c, width = self._targets.shape[0], 4 + self.d
-            nbytes = int(L.load().pls_gp_mll_classes_workspace_bytes(self.n, self.d, c))
+            c, width = self._targets.shape[0], 4 + self.d + self._nshape
+            nbytes = int(L.load().pls_gp_mll_classes_workspace_bytes_kind(self.kind, self.n, self.d, c))
             self._dev = {
                 "x": x, "y": _dev(self._targets.contiguous()),
                 "fixed": _dev(self.fixed_noise.contiguous()) if self.fixed_noise is not None else None,
                 "ws": torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=x.device),
-                # the C (4 + d) outputs and behind them the C int32 info words: one read-back per evaluation
+                # the C (4 + d) outputs (rational quadratic: 5 + d) and behind them the C int32 info words: one read-back per evaluation
                 "out": torch.zeros(c * width + (c + 1) // 2, dtype=torch.float64, device=x.device),
             }
         return self._dev
 
     def _evaluate(self, jitter: float) -> Tuple[torch.Tensor, torch.Tensor]:
-        """One pls_gp_mll_grad_classes call at the current parameters: (the (C, 4 + d) outputs on the CPU, info (C))."""
+        """One pls_gp_mll_grad_classes call at the current parameters: (the (C, 4 + d) outputs on the CPU -- rational
+        quadratic: (C, 5 + d) --, info (C))."""
         st = self._device_state()
-        c, width = self._targets.shape[0], 4 + self.d
-        mean, noise, s, ls = self._natural()
-        ls = st["x"].new_tensor(ls.tolist()).contiguous()
+        c, width = self._targets.shape[0], 4 + self.d + self._nshape
+        mean, noise, s, _ = self._natural()
+        ls = st["x"].new_tensor(self._library_lengthscale().tolist()).contiguous()
         host = (ctypes.c_double * c)
         s, noise, mean = host(*s.tolist()), host(*noise.tolist()), host(*mean.tolist())
         out, ws, fixed = st["out"], st["ws"], st["fixed"]
@@ -200,9 +232,9 @@ class _ExactGPClasses:
         """(latent mean, latent variance) of class c at x_test (t, d), float64 on the device: m_c + k*^T alpha_c and
         k** - |Lc^-1 k*|^2 with K_y,c = Lc Lc^T and alpha_c = K_y,c^-1 (y_c - m_c)."""
         st = self._device_state()
-        mean_c, noise, s, ls = (v[c] for v in self._natural())
+        mean_c, noise, s, _ = (v[c] for v in self._natural())
         mean_c, noise, s = float(mean_c), float(noise), float(s)
-        kern = self._make_kernel(ls, s)
+        kern = self._class_kernel(c)
         ky = kern(st["x"], st["x"])
         ky.diagonal().add_(st["fixed"][c] + noise if st["fixed"] is not None else noise)
         factor = cholesky_factor(ky)
@@ -226,9 +258,10 @@ class ExactGP(_ExactGPClasses):
         raw[1]   raw noise
         raw[2]   raw outputscale
         raw[3:]  raw lengthscales: d of them (``ard=True``) or one shared by all dimensions (``ard=False``)
+        raw[-1]  raw alpha, for the rational-quadratic kernel only (behind the lengthscales)
 
-    ``kernel``: "rbf" or "matern" (with ``nu``); "matern12" / "matern32" / "matern52" name nu as well; an ARDKernel /
-    MaternKernel instance gives the kind and the starting values (as the reference's ``deepcopy(kernel)``).
+    ``kernel``: "rbf", "rq" or "matern" (with ``nu``); "matern12" / "matern32" / "matern52" name nu as well; an ARDKernel /
+    MaternKernel / RQKernel instance gives the kind and the starting values (as the reference's ``deepcopy(kernel)``).
     x (n, d) and y (n) are kept as given."""
 
     def __init__(self, x: torch.Tensor, y: torch.Tensor, kernel="rbf", nu: float = 2.5, ard: bool = True):
@@ -260,12 +293,18 @@ class ExactGP(_ExactGPClasses):
         return self._natural()[3][0]
 
     @property
+    def alpha(self) -> float:
+        """the shape of the rational-quadratic kernel; AttributeError for the other kernels"""
+        return float(self._alpha()[0])
+
+    @property
     def kernel(self) -> BaseKernel:
         """The fitted base kernel: goes straight into PLSKernel and the inducing-point selectors."""
-        return self._make_kernel(self.lengthscale, self.outputscale)
+        return self._class_kernel(0)
 
     def evaluate_on_device(self, jitter: float = 0.0) -> Tuple[torch.Tensor, int]:
-        """One pls_gp_mll_grad_classes call (one class) at the current parameters: (the 4 + d outputs on the CPU, info)."""
+        """One pls_gp_mll_grad_classes call (one class) at the current parameters: (the 4 + d outputs on the CPU -- rational
+        quadratic: 5 + d --, info)."""
         out, info = self._evaluate(jitter)
         return out[0], int(info[0])
 
@@ -285,10 +324,11 @@ class ExactGP(_ExactGPClasses):
         st = self._device_state()
         cached = st.get("alpha")
         if cached is None or not torch.equal(cached[0], self.raw.detach()):
-            mean_c, noise, s, ls = (v[0] for v in self._natural())
-            ky = self._make_kernel(ls, float(s))(st["x"], st["x"])
+            mean_c, noise, s, _ = (v[0] for v in self._natural())
+            ky = self._class_kernel(0)(st["x"], st["x"])
             ky.diagonal().add_(float(noise))
             alpha = cholesky_factor(ky).solve((st["y"][0] - float(mean_c))[:, None].contiguous())
+            ls = self._library_lengthscale()[0]
             cached = (self.raw.detach().clone(), alpha.reshape(-1).contiguous(), st["x"].new_tensor(ls.tolist()).contiguous(),
                       float(s), float(mean_c))
             st["alpha"] = cached
@@ -337,7 +377,7 @@ class SVGP:
     20-node Gauss-Hermite epilogue through ``pls_svgp_lik_elbo_grad`` / ``_sgd_epoch`` / ``_predict``; a
     ``GaussianLikelihood`` is the closed-form path of ``"gaussian"``.
 
-    ``kernel``: any kernel callable of the package (PLSKernel, ARDKernel, MaternKernel, LinearKernel).  ``noise``: the
+    ``kernel``: any kernel callable of the package (PLSKernel, ARDKernel, MaternKernel, RQKernel, LinearKernel).  ``noise``: the
     starting likelihood noise (the likelihood object's own, else raw value 0, when None).  ``m`` starts at ``mean_init_std`` times standard normals from
     torch's global generator (drawn here, on the host), ``L_s`` at the identity."""
 
@@ -725,7 +765,7 @@ class DirichletExactGP(_ExactGPClasses):
     gpytorch model of experiments/curves/classification/main.py:162-192 and experiments/uci/classification/main.py:133-163.
 
     ``raw`` is ONE (C, 3 + nls) float64 CPU parameter, row c in ExactGP's column order (mean, raw noise, raw outputscale,
-    raw lengthscales); every raw value starts at 0.  ``transformed_targets`` and ``fixed_noise`` are (C, n);
+    raw lengthscales; (C, 4 + nls) with raw alpha last for the rational-quadratic kernel); every raw value starts at 0.  ``transformed_targets`` and ``fixed_noise`` are (C, n);
     ``fixed_noise=False`` leaves the fixed part out (``self.fixed_noise`` is then None): what the reference trains on
     when its subsample is smaller than its data.
     One evaluation of all classes is ONE library call with one read-back, ``pls_gp_mll_grad_classes``."""
@@ -742,8 +782,7 @@ class DirichletExactGP(_ExactGPClasses):
     @property
     def kernels(self) -> List[BaseKernel]:
         """The fitted kernel of every class."""
-        ls, s = self.lengthscale, self.outputscale
-        return [self._make_kernel(ls[c], float(s[c])) for c in range(self.number_of_classes)]
+        return [self._class_kernel(c) for c in range(self.number_of_classes)]
 
     @property
     def kernel(self) -> BaseKernel:
@@ -752,7 +791,8 @@ class DirichletExactGP(_ExactGPClasses):
         return construct_average_ard_kernel([self])
 
     def evaluate_on_device(self, jitter: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor]:
-        """One pls_gp_mll_grad_classes call at the current parameters: (the (C, 4 + d) outputs on the CPU, info (C))."""
+        """One pls_gp_mll_grad_classes call at the current parameters: (the (C, 4 + d) outputs on the CPU -- rational
+        quadratic: (C, 5 + d) --, info (C))."""
         return self._evaluate(jitter)
 
     def predict(self, x_test: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -817,15 +857,14 @@ def train_exact_gp(x: torch.Tensor, y: torch.Tensor, kernel, seed: int, number_o
 def construct_average_ard_kernel(models: Sequence[ExactGP]) -> BaseKernel:
     """The kernel of the AVERAGED RAW parameters, softplus applied afterwards (constructors.py:28-53 averages the
     entries of ``state_dict()``, which are the raw values).  A DirichletExactGP holds one row of raw values per class: its
-    rows are averaged first (the reference's ``mean(dim=0)`` over the batch), then the models."""
+    rows are averaged first (the reference's ``mean(dim=0)`` over the batch), then the models.  The rational-quadratic
+    kernel's raw alpha is averaged like the other raw values and the result is an RQKernel."""
     first = models[0]
     per_model = [m.raw_parameters() for m in models]
     raw = torch.stack([(r.mean(dim=0) if r.dim() == 2 else r)[2:] for r in per_model]).mean(dim=0)
-    outputscale, ls = float(_softplus(raw[0])), _softplus(raw[1:])
+    outputscale, ls = float(_softplus(raw[0])), _softplus(raw[1:raw.numel() - first._nshape])
     ls = ls.expand(first.d).clone() if ls.numel() == 1 and first.d > 1 else ls
-    if first.kernel_name == "matern":
-        return MaternKernel(ls, outputscale, nu=first.nu)
-    return ARDKernel(ls, outputscale)
+    return first._make_kernel(ls, outputscale, float(_softplus(raw[-1])) if first._nshape else None)
 
 
 def construct_average_gaussian_noise(models: Sequence[ExactGP]) -> float:

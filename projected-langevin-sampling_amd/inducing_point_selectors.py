@@ -42,9 +42,9 @@ class ConditionalVarianceInducingPointSelector(InducingPointSelector):
             # the reference would select on r = k(., S) k(S, .)^T / |S| (an N x N Gram of the PLS kernel); its experiments
             # always pass the base ScaleKernel(RBFKernel) (experiments/uci/regression/main.py:203), and so must callers here
             raise TypeError("ConditionalVarianceInducingPointSelector selects on a base kernel (ARDKernel / MaternKernel / "
-                            "LinearKernel / a gpytorch ScaleKernel(RBFKernel) or ScaleKernel(MaternKernel)); pass "
+                            "RQKernel / LinearKernel / a gpytorch ScaleKernel(RBFKernel | MaternKernel | RQKernel)); pass "
                             "pls_kernel.base_kernel, not the PLSKernel")
-        # ARDKernel / MaternKernel / LinearKernel as is; ScaleKernel(RBFKernel | MaternKernel): lengthscale AND outputscale (and nu)
+        # our kernels as is; ScaleKernel(RBFKernel | MaternKernel | RQKernel): lengthscale AND outputscale (and nu or alpha)
         base = as_base_kernel(kernel)
         n = x.shape[0]
         perm = np.random.permutation(n)  # permute entries so tie-breaking is random (:58-61)

@@ -2,8 +2,8 @@
 
 The reference takes a gpytorch kernel object; gpytorch is a host-side hyper-parameter container there.
 Here kernels are plain parameter holders whose Gram matrices are built by libplship on the MI355X.
-A gpytorch ScaleKernel(RBFKernel) or ScaleKernel(MaternKernel) instance is accepted wherever a base kernel is
-expected: its lengthscale / outputscale (and nu) are read once (``as_base_kernel``)."""
+A gpytorch ScaleKernel(RBFKernel), ScaleKernel(MaternKernel) or ScaleKernel(RQKernel) instance is accepted wherever a
+base kernel is expected: its lengthscale / outputscale (and nu or alpha) are read once (``as_base_kernel``)."""
 from __future__ import annotations
 
 import torch
@@ -94,6 +94,36 @@ class MaternKernel(_StationaryKernel):
         self.kind = self.KINDS[nu]
 
 
+class RQKernel(_StationaryKernel):
+    """ScaleKernel(RQKernel(ard_num_dims=D)), the rational-quadratic kernel: with r^2 = sum_d ((a_d-b_d)/lengthscale_d)^2,
+    k(a,b) = outputscale * (1 + r^2 / (2 alpha))^(-alpha),
+    gpytorch's RQKernel as recalled (include/plship.h states the formula; it is the contract).  ``alpha`` > 0 is the shape:
+    heavy tails for a small alpha, the RBF kernel as alpha -> inf.  ``lengthscale`` holds d (or one shared) values as in
+    ARDKernel; the library reads alpha behind the lengthscales, so the device array has d + 1 entries."""
+
+    kind = L.KERNEL_RQ
+
+    def __init__(self, lengthscale, outputscale: float = 1.0, alpha: float = 1.0):
+        alpha = float(torch.as_tensor(alpha, dtype=torch.float64).detach().reshape(-1)[0])  # (gpytorch's: a one-element tensor)
+        if not alpha > 0.0:
+            raise ValueError(f"RQKernel: alpha must be positive, got {alpha}")
+        super().__init__(lengthscale, outputscale)
+        self.alpha = alpha
+
+    def _lengthscale_host(self, d: int) -> torch.Tensor:
+        """the d + 1 values the library reads: the lengthscales (a shared one repeated), then alpha"""
+        ls = self.lengthscale
+        if ls.numel() == 1:
+            ls = ls.expand(d)
+        assert ls.numel() == d, f"lengthscale has {ls.numel()} entries, data has {d} dims"
+        return torch.cat([ls, torch.tensor([self.alpha], dtype=torch.float64)])
+
+    def _lengthscale_dev(self, d: int) -> torch.Tensor:
+        if d not in self._ls_dev:
+            self._ls_dev[d] = _dev(self._lengthscale_host(d))
+        return self._ls_dev[d]
+
+
 class LinearKernel(BaseKernel):
     """k(x1, x2) = x1 x2^T: the reference's test double (mockers/kernel.py:8-23)."""
 
@@ -101,8 +131,9 @@ class LinearKernel(BaseKernel):
 
 
 def as_base_kernel(kernel) -> BaseKernel:
-    """Accept our kernels, or read the hyper-parameters of a gpytorch ScaleKernel(RBFKernel) or
-    ScaleKernel(MaternKernel) (an inner kernel with a ``nu`` attribute; nu outside {0.5, 1.5, 2.5} raises ValueError)."""
+    """Accept our kernels, or read the hyper-parameters of a gpytorch ScaleKernel(RBFKernel), ScaleKernel(MaternKernel) (an
+    inner kernel with a ``nu`` attribute; nu outside {0.5, 1.5, 2.5} raises ValueError) or ScaleKernel(RQKernel) (an inner
+    kernel with an ``alpha`` attribute)."""
     if isinstance(kernel, BaseKernel):
         return kernel
     inner = getattr(kernel, "base_kernel", None)
@@ -111,8 +142,10 @@ def as_base_kernel(kernel) -> BaseKernel:
         outputscale = float(torch.as_tensor(kernel.outputscale).detach())
         if hasattr(inner, "nu"):
             return MaternKernel(lengthscale=lengthscale, outputscale=outputscale, nu=inner.nu)
+        if hasattr(inner, "alpha"):
+            return RQKernel(lengthscale=lengthscale, outputscale=outputscale, alpha=inner.alpha)
         return ARDKernel(lengthscale=lengthscale, outputscale=outputscale)
-    raise TypeError(f"unsupported base kernel {type(kernel).__name__}: use ARDKernel / MaternKernel / LinearKernel")
+    raise TypeError(f"unsupported base kernel {type(kernel).__name__}: use ARDKernel / MaternKernel / RQKernel / LinearKernel")
 
 
 class PLSKernel:

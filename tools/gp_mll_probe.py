@@ -24,7 +24,8 @@ import projected_langevin_sampling_amd as pkg  # noqa: E402
 
 L = pkg._lib
 F64 = torch.float64
-KINDS = {"rbf": L.KERNEL_RBF_ARD, "matern52": L.KERNEL_MATERN52}
+KINDS = {"rbf": L.KERNEL_RBF_ARD, "matern52": L.KERNEL_MATERN52, "rq": L.KERNEL_RQ}
+RQ_ALPHA = math.log(2.0)  # behind the lengthscales in the library's array; its derivative is the last output
 
 
 def timed(fn, repeats):
@@ -51,11 +52,12 @@ def library_stages(kind, x, y, ls, s, noise, mean, repeats):
     ky, lc, lct, sf, sb, linv, linvt = planes
     r, alpha = (y - mean).contiguous(), torch.empty(n, dtype=F64, device="cuda")
     info = torch.zeros(1, dtype=torch.int32, device="cuda")
-    out = torch.empty(4 + d, dtype=F64, device="cuda")
-    nbytes = lib.pls_gp_mll_workspace_bytes(n, d)
+    extra = 1 if kind == L.KERNEL_RQ else 0
+    out = torch.empty(4 + d + extra, dtype=F64, device="cuda")
+    nbytes = lib.pls_gp_mll_workspace_bytes_kind(kind, n, d)
     ws = torch.empty(nbytes // 8, dtype=F64, device="cuda")
-    rbytes = lib.pls_kernel_grad_sums_workspace_bytes(n, d)
-    rws, sums = torch.empty(rbytes // 8 + 1, dtype=F64, device="cuda"), torch.empty(d + 1, dtype=F64, device="cuda")
+    rbytes = lib.pls_kernel_grad_sums_workspace_bytes_kind(kind, n, d)
+    rws, sums = torch.empty(rbytes // 8 + 1, dtype=F64, device="cuda"), torch.empty(d + 1 + extra, dtype=F64, device="cuda")
     desc = L.CholDesc()
     desc.m = n
     desc.Lc, desc.ldlc, desc.LcT, desc.ldlct = lc.data_ptr(), ld, lct.data_ptr(), ld
@@ -95,14 +97,16 @@ def library_stages(kind, x, y, ls, s, noise, mean, repeats):
 
 
 def torch_route(kind, x, y, ls, s, noise, mean, repeats):
-    """-> (ms, the same 4 + d numbers): value and gradient by autograd through torch.linalg.cholesky, fp64, same device"""
+    """-> (ms, the same 4 + d numbers, 5 + d for RQ): value and gradient by autograd through torch.linalg.cholesky, fp64,
+    same device"""
     n, d = x.shape
     leaves = [torch.tensor(v, dtype=F64, device="cuda", requires_grad=True) for v in (mean, noise, math.log(s))]
-    log_ls = ls.log().clone().requires_grad_(True)
+    log_ls = ls[:d].log().clone().requires_grad_(True)
+    log_alpha = torch.tensor(math.log(RQ_ALPHA), dtype=F64, device="cuda", requires_grad=True)
     result = {}
 
     def run():
-        for t in leaves + [log_ls]:
+        for t in leaves + [log_ls, log_alpha]:
             t.grad = None
         e2 = torch.zeros((n, n), dtype=F64, device="cuda")
         for k in range(d):
@@ -110,6 +114,8 @@ def torch_route(kind, x, y, ls, s, noise, mean, repeats):
             e2 = e2 + (a[:, None] - a[None, :]).square()
         if kind == L.KERNEL_RBF_ARD:
             kap = torch.exp(-0.5 * e2)
+        elif kind == L.KERNEL_RQ:
+            kap = torch.exp(-log_alpha.exp() * torch.log1p(e2 / (2.0 * log_alpha.exp())))
         else:  # sqrt has no derivative at 0: the diagonal is taken out before it
             off = ~torch.eye(n, dtype=torch.bool, device="cuda")
             t = torch.sqrt(5.0 * torch.where(off, e2, torch.ones_like(e2)))
@@ -120,7 +126,8 @@ def torch_route(kind, x, y, ls, s, noise, mean, repeats):
         alpha = torch.cholesky_solve(r[:, None], low)[:, 0]
         mll = -0.5 * r @ alpha - torch.log(low.diagonal()).sum() - 0.5 * n * math.log(2.0 * math.pi)
         mll.backward()
-        result["out"] = torch.cat([mll.detach().reshape(1), torch.stack([t.grad for t in leaves]), log_ls.grad])
+        tail = [log_alpha.grad.reshape(1)] if kind == L.KERNEL_RQ else []
+        result["out"] = torch.cat([mll.detach().reshape(1), torch.stack([t.grad for t in leaves]), log_ls.grad] + tail)
 
     return timed(run, repeats), result["out"].cpu()
 
@@ -145,7 +152,7 @@ def main():
                 g = torch.Generator().manual_seed(n + d)
                 x = torch.randn(n, d, generator=g, dtype=F64).cuda()
                 y = (torch.sin(x.sum(dim=1)) + 0.3 * torch.randn(n, generator=g, dtype=F64).cuda()).contiguous()
-                ls = ((0.5 + torch.rand(d, generator=g, dtype=F64)) * d**0.5).cuda()
+                ls = torch.cat([(0.5 + torch.rand(d, generator=g, dtype=F64)) * d**0.5, torch.tensor([RQ_ALPHA], dtype=F64)]).cuda()
                 res, out = library_stages(kind, x, y, ls, 1.3, 0.1, 0.2, args.repeats)
                 row = (f"{name:9s} {n:5d} {d:2d} {res['whole']:8.3f} {res['gram']:7.3f} {res['factor']:7.3f} {res['solve']:7.3f} "
                        f"{res['inverse']:7.3f} {res['product+small']:13.3f} {res['reduction']:9.3f} "
