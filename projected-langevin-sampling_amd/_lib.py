@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get("PLSHIP_LIBRARY") or os.path.join(_HERE, "libplship.so
 KERNEL_RBF_ARD, KERNEL_LINEAR = 0, 1
 KERNEL_MATERN12, KERNEL_MATERN32, KERNEL_MATERN52 = 2, 3, 4
 KERNEL_RQ = 6  # (5 is not a kind: every entry refuses it as unknown)
+KERNEL_PERIODIC = 8  # (nor is 7)
 COST_GAUSSIAN, COST_POISSON, COST_BERNOULLI, COST_STUDENT_T, COST_MULTIMODAL = range(5)
 LINK_IDENTITY, LINK_SQUARE, LINK_SIGMOID, LINK_PROBIT = range(4)
 DERIV_REFERENCE, DERIV_AUTOGRAD = 0, 1

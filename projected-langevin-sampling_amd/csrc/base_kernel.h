@@ -1,5 +1,7 @@
 // What the pairwise kernels of base_kernel.hip share (Gram build, gradient reduction, fused predictive mean): tile geometry,
 // the pre-scaled staging of the points, the distance sum of a pair, the KIND x D_MAX dispatch.  The pair's value: kernel_math.h.
+// The periodic kind is not a function of one distance sum: its points are staged UNSCALED, its two scales per coordinate
+// sit in LDS, and its pair loop (periodic_exponent, periodic_factors) evaluates every coordinate on its own.
 #pragma once
 #include "common.h"
 #include "kernel_math.h"
@@ -9,16 +11,22 @@ namespace plship {
 // A workgroup of the Gram build or of the reduction covers PAIR_ROWS rows x PAIR_COLS columns of the pair matrix: 256
 // threads, a pair of columns each, walking down the rows.  PAIR_D_MAX: the largest input dimension of every pairwise kernel.
 constexpr int PAIR_ROWS = 64, PAIR_COLS = 512, PAIR_D_MAX = 64;
+// the periodic kind's own limit: its reduction carries 2 D_MAX + 1 accumulators per thread, at 16 what RBF carries at 32
+constexpr int PERIODIC_D_MAX = 16;
+static inline int64_t kind_d_max(int32_t kind) { return kind == PLS_KERNEL_PERIODIC ? PERIODIC_D_MAX : PAIR_D_MAX; }
 
 // pls_kernel_mean: test points of a workgroup (one per lane, the four waves split the training points), and the training
 // points staged in LDS at a time: 32 KiB of pre-scaled coordinates, 512 points at the most; a multiple of 4 for every D_MAX
 constexpr int MEAN_POINTS = 64;
 constexpr int mean_chunk(int d_max) { return 4096 / d_max < 512 ? 4096 / d_max : 512; }
 
-// shape parameters of a kind: they follow the d lengthscales in its `lengthscale` argument (RQ: alpha)
-static inline int64_t kind_shape_params(int32_t kind) { return kind == PLS_KERNEL_RQ ? 1 : 0; }
+// shape parameters of a kind: they follow the d lengthscales in its `lengthscale` argument (RQ: alpha; periodic: the d
+// period lengths)
+static inline int64_t kind_shape_params(int32_t kind, int64_t d) {
+  return kind == PLS_KERNEL_RQ ? 1 : kind == PLS_KERNEL_PERIODIC ? d : 0;
+}
 // sums of the reduction: the kappa sum, one per lengthscale, one per shape parameter
-static inline int64_t grad_sums_count(int32_t kind, int64_t d) { return d + 1 + kind_shape_params(kind); }
+static inline int64_t grad_sums_count(int32_t kind, int64_t d) { return d + 1 + kind_shape_params(kind, d); }
 
 // workgroups of the reduction over an n x n matrix = partial rows of grad_sums_count doubles in its workspace
 static inline int64_t grad_sums_blocks(int64_t n) { return cdiv(n, PAIR_COLS) * cdiv(n, PAIR_ROWS); }
@@ -28,7 +36,14 @@ static inline size_t grad_sums_workspace_bytes(int32_t kind, int64_t n, int64_t 
 
 static inline bool stationary_kind(int32_t kind) {
   return kind == PLS_KERNEL_RBF_ARD || kind == PLS_KERNEL_MATERN12 || kind == PLS_KERNEL_MATERN32 || kind == PLS_KERNEL_MATERN52 ||
-         kind == PLS_KERNEL_RQ;
+         kind == PLS_KERNEL_RQ || kind == PLS_KERNEL_PERIODIC;
+}
+// what every entry checks after the kind and d >= 1: the kind's largest input dimension, under the entry's name `who`
+static inline int check_kind_dim(const char *who, int32_t kind, int64_t d) {
+  PLS_REQUIRE(kind != PLS_KERNEL_PERIODIC || d <= PERIODIC_D_MAX,
+              "%s: input dimension %lld > 16 is not supported for the periodic kernel", who, (long long)d);
+  PLS_REQUIRE(d <= PAIR_D_MAX, "%s: input dimension %lld > 64 is not supported", who, (long long)d);
+  return PLS_OK;
 }
 
 // What pls_kernel_grad_sums, pls_gp_mll_grad and pls_gp_mll_grad_classes check alike, each under its own name `who`: the
@@ -42,7 +57,8 @@ int grad_sums_launch(int kind, const double *x, int64_t n, int d, const double *
                      const double *alpha, const double *P, int64_t ldp, double *out, double *partials, hipStream_t st);
 
 // The KIND x D_MAX instantiations of a base kernel's per-pair loops: f(integral_constant<KIND>, integral_constant<D_MAX>), D_MAX
-// the input dimension rounded up to 1, 2, 4, ..., 64 (kind and d already validated).  LINEAR: with the linear kind (the Gram build).
+// the input dimension rounded up to 1, 2, 4, ..., 64 (periodic: ..., 16; kind and d already validated).  LINEAR: with the linear
+// kind (the Gram build).
 template <bool LINEAR, class F>
 static int for_kind_dmax(int kind, int d, F &&f) {
   using std::integral_constant;
@@ -56,6 +72,14 @@ static int for_kind_dmax(int kind, int d, F &&f) {
     return f(k, integral_constant<int, 64>{});
   };
   if constexpr (LINEAR) if (kind == PLS_KERNEL_LINEAR) return with_kind(integral_constant<int, PLS_KERNEL_LINEAR>{});
+  if (kind == PLS_KERNEL_PERIODIC) {
+    const integral_constant<int, PLS_KERNEL_PERIODIC> k{};
+    if (d <= 1) return f(k, integral_constant<int, 1>{});
+    if (d <= 2) return f(k, integral_constant<int, 2>{});
+    if (d <= 4) return f(k, integral_constant<int, 4>{});
+    if (d <= 8) return f(k, integral_constant<int, 8>{});
+    return f(k, integral_constant<int, PERIODIC_D_MAX>{});
+  }
   switch (kind) {
     case PLS_KERNEL_RBF_ARD: return with_kind(integral_constant<int, PLS_KERNEL_RBF_ARD>{});
     case PLS_KERNEL_MATERN12: return with_kind(integral_constant<int, PLS_KERNEL_MATERN12>{});
@@ -68,19 +92,36 @@ static int for_kind_dmax(int kind, int d, F &&f) {
 // inv_ls[k] = sqrt(2 nu) / l_k for a stationary kind (the distance sum is then r^2 or t^2 itself; RQ keeps r^2 and divides by
 // 2 alpha per pair, so that its derivative factors are the header's), 1 for the linear kernel,
 // 0 for the padding k >= d: zero on both sides of a pair, so the unrolled coordinate loops need no `k < d` test.
-template <int KIND, int D_MAX>
-__device__ __forceinline__ void stage_inv_lengthscale(double (&inv_ls)[D_MAX], const double *lengthscale, int d) {
+// Periodic: inv_ls[k] = 1 / p_k (the period lengths follow the d lengthscales) and two_inv_l[k] = 2 / lambda_k, both 0 for the
+// padding; the points themselves stay unscaled (pair_scaled).  The other kinds leave two_inv_l, an array of one, alone.
+template <int KIND>
+constexpr int periodic_len(int d_max) { return KIND == PLS_KERNEL_PERIODIC ? d_max : 1; }
+template <int KIND, int D_MAX, int NP>
+__device__ __forceinline__ void stage_inv_lengthscale(double (&inv_ls)[D_MAX], double (&two_inv_l)[NP], const double *lengthscale,
+                                                      int d) {
   const int t = threadIdx.x;
-  if (t < D_MAX) inv_ls[t] = (t < d) ? ((KIND != PLS_KERNEL_LINEAR) ? matern_t_scale(KIND) / lengthscale[t] : 1.0) : 0.0;
+  if constexpr (KIND == PLS_KERNEL_PERIODIC) {
+    if (t < D_MAX) {
+      inv_ls[t] = (t < d) ? 1.0 / lengthscale[d + t] : 0.0;
+      two_inv_l[t] = (t < d) ? 2.0 / lengthscale[t] : 0.0;
+    }
+  } else {
+    if (t < D_MAX) inv_ls[t] = (t < d) ? ((KIND != PLS_KERNEL_LINEAR) ? matern_t_scale(KIND) / lengthscale[t] : 1.0) : 0.0;
+  }
+}
+// a coordinate as a pairwise kernel holds it: times its inverse lengthscale, or as it is for the periodic kind
+template <int KIND>
+__device__ __forceinline__ double pair_scaled(double v, double inv_ls) {
+  return KIND == PLS_KERNEL_PERIODIC ? v : v * inv_ls;
 }
 
 // a_s[r] = row row0 + r of x (n x d, flat), pre-scaled and zero-padded, for r < nrows; 256 threads
-template <int D_MAX>
+template <int KIND, int D_MAX>
 __device__ __forceinline__ void stage_rows(double (&a_s)[PAIR_ROWS][D_MAX], const double *x, int64_t row0,
                                            int nrows, int d, const double (&inv_ls)[D_MAX]) {
   for (int e = threadIdx.x; e < nrows * D_MAX; e += 256) {
     const int r = e / D_MAX, k = e % D_MAX;
-    a_s[r][k] = (k < d) ? x[(row0 + r) * d + k] * inv_ls[k] : 0.0;
+    a_s[r][k] = (k < d) ? pair_scaled<KIND>(x[(row0 + r) * d + k], inv_ls[k]) : 0.0;
   }
 }
 
@@ -105,6 +146,43 @@ __device__ __forceinline__ void pair_dist2(const double (&a)[D_MAX], const doubl
     s0 = fma(e0, e0, s0);
     s1 = fma(e1, e1, s1);
   }
+}
+
+// The periodic pair loops (kernel_math.h: periodic_coord): the negated exponent of a staged row a and one point b, and of a
+// and a thread's pair of columns; inv_p and two_inv_l are read from LDS (broadcast), once for both columns.
+template <int D_MAX>
+__device__ __forceinline__ double periodic_exponent(const double (&a)[D_MAX], const double (&b)[D_MAX],
+                                                    const double (&inv_p)[D_MAX], const double (&two_inv_l)[D_MAX]) {
+  double q = 0.0, unused;
+#pragma unroll
+  for (int k = 0; k < D_MAX; ++k) q = __dadd_rn(q, periodic_coord<false>(a[k] - b[k], inv_p[k], two_inv_l[k], unused));
+  return q;
+}
+template <int D_MAX>
+__device__ __forceinline__ void periodic_exponent(const double (&a)[D_MAX], const double (&b0)[D_MAX], const double (&b1)[D_MAX],
+                                                  const double (&inv_p)[D_MAX], const double (&two_inv_l)[D_MAX], double &q0,
+                                                  double &q1) {
+  double unused;
+  q0 = q1 = 0.0;
+#pragma unroll
+  for (int k = 0; k < D_MAX; ++k) {
+    const double ak = a[k], ip = inv_p[k], tl = two_inv_l[k];
+    q0 = __dadd_rn(q0, periodic_coord<false>(ak - b0[k], ip, tl, unused));
+    q1 = __dadd_rn(q1, periodic_coord<false>(ak - b1[k], ip, tl, unused));
+  }
+}
+// the same sum with the pair's factors kept: fl[k] = (2 / lambda_k) sin^2(pi e_k), fp[k] = (2 / lambda_k) pi e_k sin(2 pi e_k);
+// dK / d log lambda_k = s kappa fl[k], dK / d log p_k = s kappa fp[k]
+template <int D_MAX>
+__device__ __forceinline__ double periodic_factors(const double (&a)[D_MAX], const double (&b)[D_MAX], const double (&inv_p)[D_MAX],
+                                                   const double (&two_inv_l)[D_MAX], double (&fl)[D_MAX], double (&fp)[D_MAX]) {
+  double q = 0.0;
+#pragma unroll
+  for (int k = 0; k < D_MAX; ++k) {
+    fl[k] = periodic_coord<true>(a[k] - b[k], inv_p[k], two_inv_l[k], fp[k]);
+    q = __dadd_rn(q, fl[k]);
+  }
+  return q;
 }
 
 }  // namespace plship

@@ -1,7 +1,9 @@
-// The pairwise kernels of the base kernel (RBF-ARD, Matern 1/2, 3/2, 5/2, rational quadratic; the Gram build also the linear kernel):
+// The pairwise kernels of the base kernel (RBF-ARD, Matern 1/2, 3/2, 5/2, rational quadratic, periodic; the Gram build also the
+// linear kernel):
 // pls_kernel_gram, pls_kernel_grad_sums, pls_kernel_mean.  The exact-GP path builds K with the first, differentiates with
 // the second and predicts with the third, so the three evaluate a pair alike: the same pre-scaled points and distance
-// sum (base_kernel.h), the same kappa (kernel_math.h).
+// sum (base_kernel.h), the same kappa (kernel_math.h).  The periodic kind has no distance sum: unscaled points, 1 / p_k and
+// 2 / lambda_k in LDS, one sincospi per coordinate (base_kernel.h: periodic_exponent, periodic_factors).
 #include <hip/hip_runtime.h>
 
 #define PLS_SCALAR_POLY_CONSTANTS 1  // (fmath.h: the exp polynomial's constants as scalar operands)
@@ -21,15 +23,17 @@ __global__ __launch_bounds__(256) void kernel_gram_kernel(const double *__restri
                                                            const double *__restrict__ x2, int64_t n2, int d,
                                                            const double *__restrict__ lengthscale, double outputscale,
                                                            double *__restrict__ out, int64_t ldout) {
-  __shared__ double inv_ls[D_MAX];
+  constexpr bool PERIODIC = KIND == PLS_KERNEL_PERIODIC;
+  __shared__ double inv_ls[D_MAX];                        // (periodic: 1 / p_k)
+  __shared__ double two_inv_l[periodic_len<KIND>(D_MAX)];  // (periodic: 2 / lambda_k)
   __shared__ __attribute__((aligned(16))) double a_s[PAIR_ROWS][D_MAX];  // rows of x1 (pre-scaled, zero-padded)
   const int t = threadIdx.x;
   const int64_t row0 = (int64_t)blockIdx.y * PAIR_ROWS;
   const int nrows = (int)((n1 - row0 < PAIR_ROWS) ? (n1 - row0) : PAIR_ROWS);
-  stage_inv_lengthscale<KIND>(inv_ls, lengthscale, d);
+  stage_inv_lengthscale<KIND>(inv_ls, two_inv_l, lengthscale, d);
   const PairShape sh = load_pair_shape<KIND>(lengthscale, d);
   __syncthreads();
-  stage_rows(a_s, x1, row0, nrows, d, inv_ls);
+  stage_rows<KIND>(a_s, x1, row0, nrows, d, inv_ls);
   __syncthreads();
   const int64_t col = ((int64_t)blockIdx.x * 256 + t) * 2;
   if (col >= n2) return;
@@ -37,15 +41,21 @@ __global__ __launch_bounds__(256) void kernel_gram_kernel(const double *__restri
   double b0[D_MAX], b1[D_MAX];
 #pragma unroll
   for (int k = 0; k < D_MAX; ++k) {
-    b0[k] = (k < d) ? x2[col * d + k] * inv_ls[k] : 0.0;
-    b1[k] = (k < d && two) ? x2[(col + 1) * d + k] * inv_ls[k] : 0.0;
+    b0[k] = (k < d) ? pair_scaled<KIND>(x2[col * d + k], inv_ls[k]) : 0.0;
+    b1[k] = (k < d && two) ? pair_scaled<KIND>(x2[(col + 1) * d + k], inv_ls[k]) : 0.0;
   }
   const bool vec = two && ((ldout & 1) == 0) && ((reinterpret_cast<uintptr_t>(out) & 15) == 0);
   double *dst = out + row0 * ldout + col;
 #pragma unroll 2
   for (int r = 0; r < nrows; ++r, dst += ldout) {
     double s0 = 0.0, s1 = 0.0;
-    if (KIND != PLS_KERNEL_LINEAR) {
+    if constexpr (PERIODIC) {
+      periodic_exponent(a_s[r], b0, b1, inv_ls, two_inv_l, s0, s1);
+      double kap0, kap1;
+      const bool live0 = periodic_kappa(s0, kap0), live1 = periodic_kappa(s1, kap1);
+      s0 = live0 ? outputscale * kap0 : 0.0;
+      s1 = live1 ? outputscale * kap1 : 0.0;
+    } else if (KIND != PLS_KERNEL_LINEAR) {
       pair_dist2(a_s[r], b0, b1, s0, s1);
       s0 = gram_entry<KIND>(s0, sh, outputscale);
       s1 = gram_entry<KIND>(s1, sh, outputscale);
@@ -68,12 +78,14 @@ __global__ __launch_bounds__(256) void kernel_gram_kernel(const double *__restri
 
 // The reduction over the n x n pair matrix, laid out as kernel_gram_kernel (a thread owns a PAIR of columns and walks down
 // the rows in LDS).  P is read once, 16 B per lane where ldp is even and P is 16-byte aligned.  D_MAX + 1 accumulators per
-// thread, one more for RQ.
+// thread, one more for RQ; periodic: 2 D_MAX + 1, the period sums behind the lengthscale sums.
 //   out[0]     = sum_ij W_ij kappa_ij                  (kappa: the kernel without its outputscale)
 //   out[1 + k] = sum_ij W_ij dK_ij / d log l_k         (RBF: s exp(-r^2/2) e_k^2;  Matern: s q(t) exp(-t) 2 nu e_k^2 with
 //                                                       q = 1/t, 1, (1 + t)/3 for nu = 1/2, 3/2, 5/2;  RQ: s kappa / (1 + u) e_k^2;
 //                                                       e_k = (x_ik - x_jk)/l_k)
+//                                                       periodic: s kappa (2 / lambda_k) sin^2(pi e_k), e_k = (x_ik - x_jk)/p_k
 //   out[1 + d] = sum_ij W_ij dK_ij / d log alpha       (RQ only: s alpha kappa (u / (1 + u) - log1p(u)), u = r^2 / (2 alpha))
+//   out[1 + d + k] = sum_ij W_ij dK_ij / d log p_k     (periodic only: s kappa (2 / lambda_k) pi e_k sin(2 pi e_k))
 // with W = alpha alpha^T - P; no atomics: per thread down its rows, then the workgroup sum below, then the workgroups'
 // partial rows in ascending order (a second one-workgroup launch).
 template <int KIND, int D_MAX>
@@ -81,20 +93,23 @@ __global__ __launch_bounds__(256) void kernel_grad_sums_kernel(const double *__r
                                                                 const double *__restrict__ lengthscale, double outputscale,
                                                                 const double *__restrict__ alpha, const double *__restrict__ P,
                                                                 int64_t ldp, double *__restrict__ partials) {
-  __shared__ double inv_ls[D_MAX];
+  constexpr bool PERIODIC = KIND == PLS_KERNEL_PERIODIC;
+  __shared__ double inv_ls[D_MAX];                        // (periodic: 1 / p_k)
+  __shared__ double two_inv_l[periodic_len<KIND>(D_MAX)];  // (periodic: 2 / lambda_k)
   __shared__ __attribute__((aligned(16))) double a_s[PAIR_ROWS][D_MAX];
   __shared__ double al_s[PAIR_ROWS];
   constexpr bool SHAPE = KIND == PLS_KERNEL_RQ;
-  constexpr int NACC = D_MAX + 1 + (SHAPE ? 1 : 0);  // (the shape sum is kept last: acc[D_MAX + 1], written to slot d + 1)
+  // (the shape sums are kept last: acc[D_MAX + 1 + j], written to slot d + 1 + j)
+  constexpr int NACC = D_MAX + 1 + (SHAPE ? 1 : 0) + (PERIODIC ? D_MAX : 0);
   __shared__ double red[4][NACC];
   const int t = threadIdx.x;
   const int64_t row0 = (int64_t)blockIdx.y * PAIR_ROWS;
   const int nrows = (int)((n - row0 < PAIR_ROWS) ? (n - row0) : PAIR_ROWS);
-  stage_inv_lengthscale<KIND>(inv_ls, lengthscale, d);
+  stage_inv_lengthscale<KIND>(inv_ls, two_inv_l, lengthscale, d);
   const PairShape sh = load_pair_shape<KIND>(lengthscale, d);
   if (t < PAIR_ROWS) al_s[t] = (t < nrows) ? alpha[row0 + t] : 0.0;
   __syncthreads();
-  stage_rows(a_s, x, row0, nrows, d, inv_ls);
+  stage_rows<KIND>(a_s, x, row0, nrows, d, inv_ls);
   __syncthreads();
   const int64_t col = ((int64_t)blockIdx.x * 256 + t) * 2;
   const bool one = col < n, two = col + 1 < n;
@@ -105,8 +120,8 @@ __global__ __launch_bounds__(256) void kernel_grad_sums_kernel(const double *__r
     double b0[D_MAX], b1[D_MAX];
 #pragma unroll
     for (int k = 0; k < D_MAX; ++k) {
-      b0[k] = (k < d) ? x[col * d + k] * inv_ls[k] : 0.0;
-      b1[k] = (k < d && two) ? x[(col + 1) * d + k] * inv_ls[k] : 0.0;
+      b0[k] = (k < d) ? pair_scaled<KIND>(x[col * d + k], inv_ls[k]) : 0.0;
+      b1[k] = (k < d && two) ? pair_scaled<KIND>(x[(col + 1) * d + k], inv_ls[k]) : 0.0;
     }
     const double aj0 = alpha[col], aj1 = two ? alpha[col + 1] : 0.0;
     const bool vec = two && ((ldp & 1) == 0) && ((reinterpret_cast<uintptr_t>(P) & 15) == 0);
@@ -123,29 +138,48 @@ __global__ __launch_bounds__(256) void kernel_grad_sums_kernel(const double *__r
       }
       const double ai = al_s[r];
       const double w0 = __dsub_rn(__dmul_rn(ai, aj0), p0), w1 = __dsub_rn(__dmul_rn(ai, aj1), p1);  // W_ij, two roundings
-      double s0, s1;
-      pair_dist2(a_s[r], b0, b1, s0, s1);
-      double kap0, g0, ga0, kap1, g1, ga1;
-      const bool live0 = pair_factors<KIND>(s0, sh, kap0, g0, ga0);
-      const bool live1 = pair_factors<KIND>(s1, sh, kap1, g1, ga1) && two;
-      if (live0) {
-        const double gw = w0 * (outputscale * g0);
-        acc[0] = fma(w0, kap0, acc[0]);
-        if constexpr (SHAPE) acc[D_MAX + 1] = fma(w0, outputscale * ga0, acc[D_MAX + 1]);
+      if constexpr (PERIODIC) {
+        // one column at a time: its 2 D_MAX factors live in registers between the exponent sum and the accumulation
+        auto column = [&](const double (&b)[D_MAX], double w, bool have) {
+          double fl[D_MAX], fp[D_MAX], kap;
+          const bool live = periodic_kappa(periodic_factors(a_s[r], b, inv_ls, two_inv_l, fl, fp), kap) && have;
+          if (live) {
+            const double gw = w * (outputscale * kap);
+            acc[0] = fma(w, kap, acc[0]);
 #pragma unroll
-        for (int k = 0; k < D_MAX; ++k) {
-          const double e = a_s[r][k] - b0[k];
-          acc[1 + k] = fma(gw, e * e, acc[1 + k]);
+            for (int k = 0; k < D_MAX; ++k) {
+              acc[1 + k] = fma(gw, fl[k], acc[1 + k]);
+              acc[1 + D_MAX + k] = fma(gw, fp[k], acc[1 + D_MAX + k]);
+            }
+          }
+        };
+        column(b0, w0, true);
+        column(b1, w1, two);
+      } else {
+        double s0, s1;
+        pair_dist2(a_s[r], b0, b1, s0, s1);
+        double kap0, g0, ga0, kap1, g1, ga1;
+        const bool live0 = pair_factors<KIND>(s0, sh, kap0, g0, ga0);
+        const bool live1 = pair_factors<KIND>(s1, sh, kap1, g1, ga1) && two;
+        if (live0) {
+          const double gw = w0 * (outputscale * g0);
+          acc[0] = fma(w0, kap0, acc[0]);
+          if constexpr (SHAPE) acc[D_MAX + 1] = fma(w0, outputscale * ga0, acc[D_MAX + 1]);
+#pragma unroll
+          for (int k = 0; k < D_MAX; ++k) {
+            const double e = a_s[r][k] - b0[k];
+            acc[1 + k] = fma(gw, e * e, acc[1 + k]);
+          }
         }
-      }
-      if (live1) {
-        const double gw = w1 * (outputscale * g1);
-        acc[0] = fma(w1, kap1, acc[0]);
-        if constexpr (SHAPE) acc[D_MAX + 1] = fma(w1, outputscale * ga1, acc[D_MAX + 1]);
+        if (live1) {
+          const double gw = w1 * (outputscale * g1);
+          acc[0] = fma(w1, kap1, acc[0]);
+          if constexpr (SHAPE) acc[D_MAX + 1] = fma(w1, outputscale * ga1, acc[D_MAX + 1]);
 #pragma unroll
-        for (int k = 0; k < D_MAX; ++k) {
-          const double e = a_s[r][k] - b1[k];
-          acc[1 + k] = fma(gw, e * e, acc[1 + k]);
+          for (int k = 0; k < D_MAX; ++k) {
+            const double e = a_s[r][k] - b1[k];
+            acc[1 + k] = fma(gw, e * e, acc[1 + k]);
+          }
         }
       }
     }
@@ -159,10 +193,10 @@ __global__ __launch_bounds__(256) void kernel_grad_sums_kernel(const double *__r
     if ((t & 63) == 0) red[t >> 6][k] = v;
   }
   __syncthreads();
-  const int nsums = d + 1 + (SHAPE ? 1 : 0);
+  const int nsums = d + 1 + (SHAPE ? 1 : 0) + (PERIODIC ? d : 0);
   if (t < nsums) {
     const int64_t blk = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
-    const int k = (SHAPE && t == d + 1) ? D_MAX + 1 : t;
+    const int k = PERIODIC ? ((t > d) ? D_MAX + (t - d) : t) : (SHAPE && t == d + 1) ? D_MAX + 1 : t;
     partials[blk * nsums + t] = (red[0][k] + red[1][k]) + (red[2][k] + red[3][k]);
   }
 }
@@ -213,12 +247,14 @@ __global__ __launch_bounds__(256) void kernel_mean_kernel(const double *__restri
                                                            const double *__restrict__ xt, int64_t t,
                                                            double *__restrict__ out) {
   constexpr int CHUNK = mean_chunk(D_MAX);
-  __shared__ double inv_ls[D_MAX];
+  constexpr bool PERIODIC = KIND == PLS_KERNEL_PERIODIC;
+  __shared__ double inv_ls[D_MAX];                        // (periodic: 1 / p_k)
+  __shared__ double two_inv_l[periodic_len<KIND>(D_MAX)];  // (periodic: 2 / lambda_k)
   __shared__ __attribute__((aligned(16))) double a_s[CHUNK][D_MAX];
   __shared__ double al_s[CHUNK];
   __shared__ double red[4][MEAN_POINTS];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  stage_inv_lengthscale<KIND>(inv_ls, lengthscale, d);
+  stage_inv_lengthscale<KIND>(inv_ls, two_inv_l, lengthscale, d);
   const PairShape sh = load_pair_shape<KIND>(lengthscale, d);
   if (D_MAX > 1)  // the padding coordinates stay zero: the staging below writes k < d only
     for (int e = tid; e < CHUNK * D_MAX; e += 256) a_s[e / D_MAX][e % D_MAX] = 0.0;
@@ -232,12 +268,12 @@ __global__ __launch_bounds__(256) void kernel_mean_kernel(const double *__restri
 #pragma unroll
       for (int k = 0; k < D_MAX; k += 2) {
         const double2m v = (k < d) ? *reinterpret_cast<const double2m *>(row + k) : double2m{0.0, 0.0};
-        b[k] = v.x * inv_ls[k];
-        if (k + 1 < D_MAX) b[k + 1] = v.y * inv_ls[(k + 1) % D_MAX];
+        b[k] = pair_scaled<KIND>(v.x, inv_ls[k]);
+        if (k + 1 < D_MAX) b[k + 1] = pair_scaled<KIND>(v.y, inv_ls[(k + 1) % D_MAX]);
       }
     } else {
 #pragma unroll
-      for (int k = 0; k < D_MAX; ++k) b[k] = (k < d) ? row[k] * inv_ls[k] : 0.0;
+      for (int k = 0; k < D_MAX; ++k) b[k] = (k < d) ? pair_scaled<KIND>(row[k], inv_ls[k]) : 0.0;
     }
   }
   const bool xvec = (reinterpret_cast<uintptr_t>(x) & 15) == 0;
@@ -251,21 +287,24 @@ __global__ __launch_bounds__(256) void kernel_mean_kernel(const double *__restri
         const int e = 2 * p;
         if (e + 1 < len) {
           const double2m v = *reinterpret_cast<const double2m *>(src + e);
-          a_s[e / d][e % d] = v.x * inv_ls[e % d];
-          a_s[(e + 1) / d][(e + 1) % d] = v.y * inv_ls[(e + 1) % d];
+          a_s[e / d][e % d] = pair_scaled<KIND>(v.x, inv_ls[e % d]);
+          a_s[(e + 1) / d][(e + 1) % d] = pair_scaled<KIND>(v.y, inv_ls[(e + 1) % d]);
         } else {
-          a_s[e / d][e % d] = src[e] * inv_ls[e % d];
+          a_s[e / d][e % d] = pair_scaled<KIND>(src[e], inv_ls[e % d]);
         }
       }
     } else {
-      for (int e = tid; e < len; e += 256) a_s[e / d][e % d] = src[e] * inv_ls[e % d];
+      for (int e = tid; e < len; e += 256) a_s[e / d][e % d] = pair_scaled<KIND>(src[e], inv_ls[e % d]);
     }
     for (int r = tid; r < nrows; r += 256) al_s[r] = alpha[j0 + r];
     __syncthreads();
 #pragma unroll 2
     for (int r = w; r < nrows; r += 4) {
       double kap;
-      if (pair_kappa<KIND>(pair_dist2(a_s[r], b), sh, kap)) acc = fma(kap, al_s[r], acc);
+      bool alive;
+      if constexpr (PERIODIC) alive = periodic_kappa(periodic_exponent(a_s[r], b, inv_ls, two_inv_l), kap);
+      else alive = pair_kappa<KIND>(pair_dist2(a_s[r], b), sh, kap);
+      if (alive) acc = fma(kap, al_s[r], acc);
     }
     __syncthreads();
   }
@@ -297,7 +336,7 @@ int gp_check_shared(const char *who, int32_t kernel_kind, int64_t n, int64_t d, 
     PLS_REQUIRE(n > 0 && d > 0 && *classes > 0, "%s: bad sizes n=%lld d=%lld classes=%lld", who, (long long)n, (long long)d,
                 (long long)*classes);
   PLS_REQUIRE(n > 0 && d > 0, "%s: bad sizes n=%lld d=%lld", who, (long long)n, (long long)d);
-  PLS_REQUIRE(d <= PAIR_D_MAX, "%s: input dimension %lld > 64 is not supported", who, (long long)d);
+  if (int rc = check_kind_dim(who, kernel_kind, d)) return rc;
   PLS_REQUIRE(cdiv(n, PAIR_ROWS) <= 65535, "%s: n=%lld too large", who, (long long)n);
   PLS_REQUIRE(workspace, "%s: NULL workspace", who);
   if (workspace_bytes < need)
@@ -318,7 +357,7 @@ int pls_kernel_gram(int32_t kernel_kind, const double *x1, int64_t n1, const dou
   PLS_REQUIRE(kernel_kind == PLS_KERNEL_LINEAR || stationary_kind(kernel_kind), "unknown kernel kind %d", kernel_kind);
   PLS_REQUIRE(x1 && x2 && out, "kernel_gram: NULL pointer");
   PLS_REQUIRE(n1 >= 0 && n2 >= 0 && d >= 1, "kernel_gram: bad sizes n1=%lld n2=%lld d=%lld", (long long)n1, (long long)n2, (long long)d);
-  PLS_REQUIRE(d <= PAIR_D_MAX, "kernel_gram: input dimension %lld > 64 is not supported", (long long)d);
+  if (int rc = check_kind_dim("kernel_gram", kernel_kind, d)) return rc;
   PLS_REQUIRE(ldout >= n2, "kernel_gram: ldout < n2");
   PLS_REQUIRE(kernel_kind == PLS_KERNEL_LINEAR || lengthscale, "kernel_gram: kernel kind %d needs lengthscale", kernel_kind);
   if (n1 == 0 || n2 == 0) return PLS_OK;
@@ -340,7 +379,7 @@ int pls_kernel_gram(int32_t kernel_kind, const double *x1, int64_t n1, const dou
 }
 
 size_t pls_kernel_grad_sums_workspace_bytes_kind(int32_t kernel_kind, int64_t n, int64_t d) {
-  return (stationary_kind(kernel_kind) && n > 0 && d > 0 && d <= PAIR_D_MAX) ? grad_sums_workspace_bytes(kernel_kind, n, d) : 0;
+  return (stationary_kind(kernel_kind) && n > 0 && d > 0 && d <= kind_d_max(kernel_kind)) ? grad_sums_workspace_bytes(kernel_kind, n, d) : 0;
 }
 size_t pls_kernel_grad_sums_workspace_bytes(int64_t n, int64_t d) {
   return pls_kernel_grad_sums_workspace_bytes_kind(PLS_KERNEL_RBF_ARD, n, d);
@@ -363,7 +402,7 @@ int pls_kernel_mean(int32_t kernel_kind, const double *x, int64_t n, int64_t d, 
   PLS_REQUIRE(kernel_kind != PLS_KERNEL_LINEAR, "kernel_mean: the linear kernel has no lengthscale or outputscale to learn");
   PLS_REQUIRE(stationary_kind(kernel_kind), "kernel_mean: unknown kernel kind %d", kernel_kind);
   PLS_REQUIRE(n > 0 && d > 0 && t >= 0, "kernel_mean: bad sizes n=%lld d=%lld t=%lld", (long long)n, (long long)d, (long long)t);
-  PLS_REQUIRE(d <= PAIR_D_MAX, "kernel_mean: input dimension %lld > 64 is not supported", (long long)d);
+  if (int rc = check_kind_dim("kernel_mean", kernel_kind, d)) return rc;
   PLS_REQUIRE(cdiv(t, (int64_t)MEAN_POINTS) <= 2147483647, "kernel_mean: t=%lld too large", (long long)t);
   if (t == 0) return PLS_OK;
   PLS_REQUIRE(x && lengthscale && alpha && xt && out, "kernel_mean: NULL pointer");

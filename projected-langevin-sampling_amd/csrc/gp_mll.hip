@@ -155,7 +155,7 @@ static int gp_mll_evaluate_classes(int32_t kernel_kind, const double *x, int64_t
                                    const double *lengthscale, const double *outputscale, const double *noise, const double *mean,
                                    const double *fixed, int64_t ldf, const double *y, int64_t ldy, double jitter, double *out,
                                    int32_t *info, double *w, void *stream) {
-  const int64_t extra = kind_shape_params(kernel_kind);
+  const int64_t extra = kind_shape_params(kernel_kind, d);
   for (int64_t c = 0; c < classes; ++c) {
     const int rc = gp_mll_evaluate(kernel_kind, x, n, d, lengthscale + c * (d + extra), outputscale[c], noise[c], mean[c], jitter,
                                    fixed ? fixed + c * ldf : nullptr, y + c * ldy, out + c * (4 + d + extra), info + c, w, stream);
@@ -261,7 +261,7 @@ using namespace plship;
 extern "C" {
 
 size_t pls_gp_mll_workspace_bytes_kind(int32_t kernel_kind, int64_t n, int64_t d) {
-  return (stationary_kind(kernel_kind) && n > 0 && d > 0 && d <= PAIR_D_MAX)
+  return (stationary_kind(kernel_kind) && n > 0 && d > 0 && d <= kind_d_max(kernel_kind))
              ? (size_t)gp_mll_plan(kernel_kind, n, d).total * sizeof(double)
              : 0;
 }

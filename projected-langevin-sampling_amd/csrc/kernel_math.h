@@ -93,6 +93,65 @@ __device__ __forceinline__ void rq_factors(const PairShape &sh, double kap, doub
   ga = sh.alpha * kap * h;
 }
 
+// sin(pi r) and cos(pi r) for |r| <= 1/2 (gfx950 has no fp64 sine instruction, and the library's sincospi spends most of its
+// instructions on an argument reduction that the periodic pair has already done).  u = |r| for |r| <= 1/4, else 1/2 - |r|
+// (exact), which swaps the two; on u <= 1/4 the Taylor polynomials of sin(pi u) / u - pi (degree 8 in u^2: truncation 1e-19
+// relative) and of cos(pi u) - 1 (degree 8: 3e-18).  pi enters as its two-piece value in ONE fma, u pi_hi + u (pi_lo + ...),
+// so the sine is within 0.8 ulp (measured on the CPU against 64-bit-mantissa arithmetic; the cosine's 1 + z q about 1 ulp).
+// sin(pi 0) = 0 exactly (with the sign of r), cos(pi / 2) = 0 exactly; a NaN stays NaN.
+__device__ __forceinline__ void sincospi_half(double r, double &s, double &c) {
+#pragma clang fp contract(off)
+  const double a = fabs(r);
+  const bool big = a > 0.25;
+  const double u = big ? 0.5 - a : a;
+  const double z = u * u;
+  double p = 7.9520540014755126e-07;  // (-1)^k pi^(2k+1) / (2k+1)!, k = 8 ... 1
+  p = fma_k(p, z, -2.1915353447830217e-05);
+  p = fma_k(p, z, 4.6630280576761255e-04);
+  p = fma_k(p, z, -7.3704309457143504e-03);
+  p = fma_k(p, z, 8.2145886611128233e-02);
+  p = fma_k(p, z, -5.9926452932079211e-01);
+  p = fma_k(p, z, 2.5501640398773455e+00);
+  p = fma_k(p, z, -5.1677127800499703e+00);
+  const double su = fma(u, 3.1415926535897931, u * fma(p, z, 1.2246467991473532e-16));
+  double q = 4.3030695870329473e-06;  // (-1)^k pi^(2k) / (2k)!, k = 8 ... 1
+  q = fma_k(q, z, -1.0463810492484570e-04);
+  q = fma_k(q, z, 1.9295743094039231e-03);
+  q = fma_k(q, z, -2.5806891390014061e-02);
+  q = fma_k(q, z, 2.3533063035889321e-01);
+  q = fma_k(q, z, -1.3352627688545895e+00);
+  q = fma_k(q, z, 4.0587121264167685e+00);
+  q = fma_k(q, z, -4.9348022005446790e+00);
+  const double cu = fma(q, z, 1.0);
+  s = copysign(big ? cu : su, r);
+  c = big ? su : cu;
+}
+
+// Periodic (gpytorch's PeriodicKernel times the outputscale, as recalled): kappa = exp(-2 sum_k sin^2(pi e_k) / lambda_k),
+// e_k = (a_k - b_k) / p_k.  One coordinate from its UNSCALED difference delta, inv_p = 1 / p_k and two_inv_l = 2 / lambda_k:
+// difference first, then e = delta inv_p, r = e - rint(e) (|r| <= 1/2, exact), sin and cos of pi r from sincospi_half.
+// Returns the coordinate's share of the NEGATED exponent, (2 / lambda_k) sin^2(pi e_k) -- which is also its factor of
+// dK / d log lambda_k = s kappa (2 / lambda_k) sin^2(pi e_k) -- and, GRAD only, per = (2 / lambda_k) pi e_k sin(2 pi e_k), its
+// factor of dK / d log p_k, with sin(2 pi e) = 2 sin cos of the same evaluation and e itself, unreduced, in front.  Every
+// quantity is even in delta, so a pair and its transpose agree bit for bit; a padding coordinate (delta = 0, both scales
+// 0) gives 0; a non-finite delta gives NaN (inf - rint(inf)): the kernel has no limit at infinity.
+template <bool GRAD>
+__device__ __forceinline__ double periodic_coord(double delta, double inv_p, double two_inv_l, double &per) {
+#pragma clang fp contract(off)
+  const double e = delta * inv_p;
+  const double r = e - rint(e);
+  double s, c;
+  sincospi_half(r, s, c);
+  if (GRAD) per = two_inv_l * ((3.1415926535897931 * e) * (2.0 * (s * c)));
+  return two_inv_l * (s * s);
+}
+// kappa from the negated exponent q = sum_k (2 / lambda_k) sin^2(pi e_k) >= 0 (added in ascending k); false: a dead pair
+__device__ __forceinline__ bool periodic_kappa(double q, double &kap) {
+  const double x = -q;
+  kap = exp_nonpos_unguarded(x);
+  return !(x < -745.2);
+}
+
 // One pair from its distance sum s2 (RBF: r^2; Matern: t^2 = 2 nu r^2; RQ: r^2, with its shape sh): kap = kappa, the kernel
 // without its outputscale; t = sqrt(s2) (Matern only) and ex, the exponential inside kappa, for pair_factors.  Returns
 // false for a pair whose exponential underflows: kap is meaningless then and the caller lets the pair contribute exactly

@@ -4,7 +4,7 @@ hyper-parameters, inducing points, PLS, metrics).
 Replaces ``src/gaussian_process/exact_gp.py`` as it is used by ``train_exact_gp`` (experiments/trainers.py:15-52),
 ``exact_gp_runner`` / ``load_subsample_data`` (experiments/runners.py:66-187) and the two averaging constructors
 (experiments/constructors.py:9-53).  The reference builds these on gpytorch (ConstantMean, ScaleKernel(RBFKernel |
-MaternKernel | RQKernel), GaussianLikelihood, ExactMarginalLogLikelihood); here the model is a plain parameter holder and one
+MaternKernel | RQKernel | PeriodicKernel), GaussianLikelihood, ExactMarginalLogLikelihood); here the model is a plain parameter holder and one
 evaluation of the marginal log-likelihood with its gradient is ONE library call, ``pls_gp_mll_grad_classes``
 (csrc/gp_mll.hip; its pairwise kernels: csrc/base_kernel.hip).  One output with a Gaussian likelihood (``ExactGP``: one
 class, no fixed noise), or classification with the Dirichlet likelihood of Milios et al. 2018 as the reference's two classification drivers use it (``DirichletExactGP``: one
@@ -21,7 +21,7 @@ import torch
 from . import _lib as L
 from . import _ops
 from ._chol import CHOLESKY_JITTER, CHOLESKY_MAX_TRIES, NotPSDError, cholesky_factor
-from .kernel import ARDKernel, BaseKernel, MaternKernel, RQKernel, _dev
+from .kernel import ARDKernel, BaseKernel, MaternKernel, PeriodicKernel, RQKernel, _dev
 from .likelihoods import GaussianLikelihood, _Likelihood
 from .trainers import EarlyStopper
 from .utils import set_seed
@@ -31,6 +31,9 @@ NOISE_LOWER_BOUND = 1e-4
 
 _KERNEL_NAMES = {"rbf": ("rbf", None), "matern": ("matern", None), "matern12": ("matern", 0.5), "matern32": ("matern", 1.5),
                  "matern52": ("matern", 2.5), "rq": ("rq", None)}
+#: a kernel CLASS names its family too, every raw value at 0.  It is the only way to ask the model classes for the periodic
+#: family without starting values: they keep refusing the bare name "periodic" (train_exact_gp and exact_gp_runner take it)
+_KERNEL_CLASSES = {ARDKernel: "rbf", MaternKernel: "matern", RQKernel: "rq", PeriodicKernel: "periodic"}
 
 
 def _softplus(v: torch.Tensor) -> torch.Tensor:
@@ -45,16 +48,23 @@ def _kernel_choice(who: str, kernel, nu: float, ard: bool, d: int):
     """(name, nu, ard, start) of the ``kernel`` argument of ExactGP / DirichletExactGP; start: the kernel object whose values
     the raw parameters start from, or None"""
     start = None
-    if isinstance(kernel, BaseKernel):
-        if not isinstance(kernel, (ARDKernel, MaternKernel, RQKernel)):
-            raise TypeError(f"{who}: the kernel must be an ARDKernel, a MaternKernel or an RQKernel (a lengthscale and an "
-                            "outputscale to learn)")
+    if isinstance(kernel, type) and kernel in _KERNEL_CLASSES:
+        name = _KERNEL_CLASSES[kernel]
+    elif isinstance(kernel, BaseKernel):
+        if not isinstance(kernel, (ARDKernel, MaternKernel, RQKernel, PeriodicKernel)):
+            raise TypeError(f"{who}: the kernel must be an ARDKernel, a MaternKernel, an RQKernel or a PeriodicKernel (a "
+                            "lengthscale and an outputscale to learn)")
         start = kernel
-        name, nu = ("matern", kernel.nu) if isinstance(kernel, MaternKernel) else ("rq" if isinstance(kernel, RQKernel) else "rbf", nu)
+        if isinstance(kernel, MaternKernel):
+            name, nu = "matern", kernel.nu
+        else:
+            name = "rq" if isinstance(kernel, RQKernel) else "periodic" if isinstance(kernel, PeriodicKernel) else "rbf"
         ard = kernel.lengthscale.numel() > 1 or d == 1 and ard
+        if name == "periodic":  # per-dimension period lengths need per-dimension raw values too
+            ard = ard or kernel.period_length.numel() > 1
     else:
         if kernel not in _KERNEL_NAMES:
-            raise ValueError(f"{who}: kernel must be one of {sorted(_KERNEL_NAMES)} or a kernel object, got {kernel!r}")
+            raise ValueError(f"{who}: kernel must be one of {sorted(_KERNEL_NAMES)}, a kernel class or a kernel object, got {kernel!r}")
         name, named_nu = _KERNEL_NAMES[kernel]
         nu = named_nu if named_nu is not None else nu
     if name == "matern" and float(nu) not in MaternKernel.KINDS:
@@ -68,7 +78,8 @@ class _ExactGPClasses:
     softplus(raw)``, ``outputscale = softplus(raw)``, ``noise = 1e-4 + softplus(raw)``, the mean constant itself; every raw
     value starts at 0.  ``raw`` is seen as (C, 3 + nls) rows: mean, raw noise, raw outputscale, raw lengthscales (d of
     them, or one shared by all dimensions); the rational-quadratic kernel has (C, 4 + nls): raw alpha, ``alpha =
-    softplus(raw)``, is its LAST column.  x (n, d), the targets (C, n) and the fixed noise v (C, n), or None, are kept
+    softplus(raw)``, is its LAST column; the periodic kernel has (C, 3 + 2 nls): the nls raw period lengths, ``period_length =
+    softplus(raw)``, behind the nls raw lengthscales.  x (n, d), the targets (C, n) and the fixed noise v (C, n), or None, are kept
     as given and uploaded once, on the first evaluation on the device.  One evaluation of all classes is ONE library call
     with one read-back, ``pls_gp_mll_grad_classes``."""
 
@@ -80,16 +91,24 @@ class _ExactGPClasses:
         self._targets, self.fixed_noise = targets, fixed_noise
         name, nu, ard, start = _kernel_choice(who, kernel, nu, ard, self.d)
         self.kernel_name, self.ard, self.nu = name, ard, nu
-        self.kind = MaternKernel.KINDS[self.nu] if name == "matern" else L.KERNEL_RQ if name == "rq" else L.KERNEL_RBF_ARD
+        self.kind = (MaternKernel.KINDS[self.nu] if name == "matern" else L.KERNEL_RQ if name == "rq"
+                     else L.KERNEL_PERIODIC if name == "periodic" else L.KERNEL_RBF_ARD)
         nls = self.d if self.ard else 1
-        self._nshape = 1 if name == "rq" else 0  # shape parameters behind the lengthscales: raw alpha
+        # raw shape columns behind the raw lengthscales (raw alpha; the nls raw period lengths), and the shape values per
+        # class as the library reads and differentiates them (alpha; the d period lengths)
+        self._nshape = 1 if name == "rq" else nls if name == "periodic" else 0
+        self._nshape_lib = 1 if name == "rq" else self.d if name == "periodic" else 0
         raw = torch.zeros(targets.shape[0], 3 + nls + self._nshape, dtype=torch.float64)
         if start is not None:
             assert start.lengthscale.numel() in (1, nls), "the kernel's lengthscales do not fit the data"
             raw[:, 2] = _inverse_softplus(torch.tensor(start.outputscale, dtype=torch.float64))
             raw[:, 3:3 + nls] = _inverse_softplus(start.lengthscale.expand(nls) if start.lengthscale.numel() == 1 else start.lengthscale)
-            if self._nshape:
+            if name == "rq":
                 raw[:, -1] = _inverse_softplus(torch.tensor(start.alpha, dtype=torch.float64))
+            if name == "periodic":
+                period = start.period_length
+                assert period.numel() in (1, nls), "the kernel's period lengths do not fit the data"
+                raw[:, 3 + nls:] = _inverse_softplus(period.expand(nls) if period.numel() == 1 else period)
         self.raw = torch.nn.Parameter(raw)
         self._dev: dict = {}
 
@@ -114,7 +133,7 @@ class _ExactGPClasses:
 
     def _alpha(self) -> torch.Tensor:
         """(C) the rational-quadratic shape alpha = softplus(raw alpha)"""
-        if not self._nshape:
+        if self.kernel_name != "rq":
             raise AttributeError(f"the {self.kernel_name} kernel has no alpha")
         return _softplus(self.raw.detach().reshape(self._targets.shape[0], -1)[:, -1])
 
@@ -123,10 +142,28 @@ class _ExactGPClasses:
         """(C) the shape of the rational-quadratic kernel; AttributeError for the other kernels"""
         return self._alpha()
 
+    def _period(self) -> torch.Tensor:
+        """(C, d) the periodic kernel's period lengths = softplus(raw), a shared one repeated"""
+        if self.kernel_name != "periodic":
+            raise AttributeError(f"the {self.kernel_name} kernel has no period_length")
+        raw = self.raw.detach().reshape(self._targets.shape[0], -1)
+        p = _softplus(raw[:, raw.shape[1] - self._nshape:])
+        return p.expand(-1, self.d).clone() if p.shape[1] == 1 and self.d > 1 else p
+
+    @property
+    def period_length(self) -> torch.Tensor:
+        """(C, d) the period lengths of the periodic kernel (a shared one repeated); AttributeError for the other kernels"""
+        return self._period()
+
     def _library_lengthscale(self) -> torch.Tensor:
-        """(C, d) lengthscales as the library reads them; rational quadratic: (C, d + 1), alpha last"""
+        """(C, d) lengthscales as the library reads them; rational quadratic: (C, d + 1), alpha last; periodic: (C, 2 d), the
+        period lengths behind the lengthscales"""
         ls = self._natural()[3]
-        return torch.cat([ls, self._alpha()[:, None]], dim=1) if self._nshape else ls
+        if self.kernel_name == "rq":
+            return torch.cat([ls, self._alpha()[:, None]], dim=1)
+        if self.kernel_name == "periodic":
+            return torch.cat([ls, self._period()], dim=1)
+        return ls
 
     @property
     def mean_constant(self) -> torch.Tensor:
@@ -146,26 +183,32 @@ class _ExactGPClasses:
         """(C, d) lengthscales (a shared one repeated)."""
         return self._natural()[3]
 
-    def _make_kernel(self, lengthscale: torch.Tensor, outputscale: float, alpha: float | None = None) -> BaseKernel:
+    def _make_kernel(self, lengthscale: torch.Tensor, outputscale: float, shape=None) -> BaseKernel:
+        """``shape``: alpha (rational quadratic) or the d period lengths (periodic)"""
         if self.kernel_name == "matern":
             return MaternKernel(lengthscale, outputscale, nu=self.nu)
         if self.kernel_name == "rq":
-            return RQKernel(lengthscale, outputscale, alpha=alpha)
+            return RQKernel(lengthscale, outputscale, alpha=shape)
+        if self.kernel_name == "periodic":
+            return PeriodicKernel(lengthscale, outputscale, period_length=shape)
         return ARDKernel(lengthscale, outputscale)
 
     def _class_kernel(self, c: int) -> BaseKernel:
         """the kernel of class c at the current parameters"""
         _, _, s, ls = self._natural()
-        return self._make_kernel(ls[c], float(s[c]), float(self._alpha()[c]) if self._nshape else None)
+        shape = float(self._alpha()[c]) if self.kernel_name == "rq" else self._period()[c] if self.kernel_name == "periodic" else None
+        return self._make_kernel(ls[c], float(s[c]), shape)
 
     # ---- the loss ---------------------------------------------------------------------------------------------------
     def chain_rule(self, out: torch.Tensor) -> Tuple[float, torch.Tensor]:
         """(-sum_c mll_c / n, its gradient with respect to ``raw``, in the shape of ``raw``) from the (C, 4 + d) outputs of
         pls_gp_mll_grad_classes (per class: value, d/d mean, d/d noise, d/d log outputscale, d/d log lengthscale_k; rational
-        quadratic: (C, 5 + d), d/d log alpha last) at the current parameters: host arithmetic only."""
+        quadratic: (C, 5 + d), d/d log alpha last; periodic: (C, 4 + 2 d), the d/d log period_length_k behind the lengthscale
+        derivatives) at the current parameters: host arithmetic only.  ``ard=False``: the per-dimension derivatives of the
+        shared lengthscale, and of the shared period length, are summed."""
         raw = self.raw.detach().reshape(self._targets.shape[0], -1)
         out = torch.as_tensor(out, dtype=torch.float64)
-        width, nls = 4 + self.d + self._nshape, raw.shape[1] - 3 - self._nshape
+        width, nls = 4 + self.d + self._nshape_lib, raw.shape[1] - 3 - self._nshape
         assert out.numel() == raw.shape[0] * width
         out = out.reshape(raw.shape[0], width)
         slope = torch.sigmoid(raw)  # d softplus(raw) / d raw
@@ -175,29 +218,32 @@ class _ExactGPClasses:
         g[:, 2] = out[:, 3] / _softplus(raw[:, 2]) * slope[:, 2]
         per_dim = out[:, 4:4 + self.d] / self._natural()[3]
         g[:, 3:3 + nls] = (per_dim if self.ard else per_dim.sum(dim=1, keepdim=True)) * slope[:, 3:3 + nls]
-        if self._nshape:
+        if self.kernel_name == "rq":
             g[:, -1] = out[:, -1] / self._alpha() * slope[:, -1]
+        if self.kernel_name == "periodic":
+            per_dim = out[:, 4 + self.d:] / self._period()
+            g[:, 3 + nls:] = (per_dim if self.ard else per_dim.sum(dim=1, keepdim=True)) * slope[:, 3 + nls:]
         return -float(out[:, 0].sum()) / self.n, (-g / self.n).reshape(self.raw.shape)
 
     def _device_state(self) -> dict:
         if not self._dev:
             x = _dev(self.x)
-            c, width = self._targets.shape[0], 4 + self.d + self._nshape
+            c, width = self._targets.shape[0], 4 + self.d + self._nshape_lib
             nbytes = int(L.load().pls_gp_mll_classes_workspace_bytes_kind(self.kind, self.n, self.d, c))
             self._dev = {
                 "x": x, "y": _dev(self._targets.contiguous()),
                 "fixed": _dev(self.fixed_noise.contiguous()) if self.fixed_noise is not None else None,
                 "ws": torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=x.device),
-                # the C (4 + d) outputs (rational quadratic: 5 + d) and behind them the C int32 info words: one read-back per evaluation
+                # the C (4 + d) outputs (rational quadratic: 5 + d; periodic: 4 + 2 d) and behind them the C int32 info words: one read-back per evaluation
                 "out": torch.zeros(c * width + (c + 1) // 2, dtype=torch.float64, device=x.device),
             }
         return self._dev
 
     def _evaluate(self, jitter: float) -> Tuple[torch.Tensor, torch.Tensor]:
         """One pls_gp_mll_grad_classes call at the current parameters: (the (C, 4 + d) outputs on the CPU -- rational
-        quadratic: (C, 5 + d) --, info (C))."""
+        quadratic: (C, 5 + d), periodic: (C, 4 + 2 d) --, info (C))."""
         st = self._device_state()
-        c, width = self._targets.shape[0], 4 + self.d + self._nshape
+        c, width = self._targets.shape[0], 4 + self.d + self._nshape_lib
         mean, noise, s, _ = self._natural()
         ls = st["x"].new_tensor(self._library_lengthscale().tolist()).contiguous()
         host = (ctypes.c_double * c)
@@ -259,9 +305,11 @@ class ExactGP(_ExactGPClasses):
         raw[2]   raw outputscale
         raw[3:]  raw lengthscales: d of them (``ard=True``) or one shared by all dimensions (``ard=False``)
         raw[-1]  raw alpha, for the rational-quadratic kernel only (behind the lengthscales)
+        raw[3 + nls:]  the nls raw period lengths, for the periodic kernel only (behind the nls raw lengthscales)
 
-    ``kernel``: "rbf", "rq" or "matern" (with ``nu``); "matern12" / "matern32" / "matern52" name nu as well; an ARDKernel /
-    MaternKernel / RQKernel instance gives the kind and the starting values (as the reference's ``deepcopy(kernel)``).
+    ``kernel``: "rbf", "rq" or "matern" (with ``nu``); "matern12" / "matern32" / "matern52" name nu as well; one of the classes
+    ARDKernel / MaternKernel / RQKernel / PeriodicKernel names its family likewise (the periodic family has no name here:
+    ``kernel=PeriodicKernel``; ``train_exact_gp`` and ``exact_gp_runner`` take "periodic"); an instance of them gives the kind and the starting values (as the reference's ``deepcopy(kernel)``).
     x (n, d) and y (n) are kept as given."""
 
     def __init__(self, x: torch.Tensor, y: torch.Tensor, kernel="rbf", nu: float = 2.5, ard: bool = True):
@@ -298,13 +346,18 @@ class ExactGP(_ExactGPClasses):
         return float(self._alpha()[0])
 
     @property
+    def period_length(self) -> torch.Tensor:
+        """the d period lengths of the periodic kernel (a shared one repeated); AttributeError for the other kernels"""
+        return self._period()[0]
+
+    @property
     def kernel(self) -> BaseKernel:
         """The fitted base kernel: goes straight into PLSKernel and the inducing-point selectors."""
         return self._class_kernel(0)
 
     def evaluate_on_device(self, jitter: float = 0.0) -> Tuple[torch.Tensor, int]:
         """One pls_gp_mll_grad_classes call (one class) at the current parameters: (the 4 + d outputs on the CPU -- rational
-        quadratic: 5 + d --, info)."""
+        quadratic: 5 + d, periodic: 4 + 2 d --, info)."""
         out, info = self._evaluate(jitter)
         return out[0], int(info[0])
 
@@ -377,7 +430,7 @@ class SVGP:
     20-node Gauss-Hermite epilogue through ``pls_svgp_lik_elbo_grad`` / ``_sgd_epoch`` / ``_predict``; a
     ``GaussianLikelihood`` is the closed-form path of ``"gaussian"``.
 
-    ``kernel``: any kernel callable of the package (PLSKernel, ARDKernel, MaternKernel, RQKernel, LinearKernel).  ``noise``: the
+    ``kernel``: any kernel callable of the package (PLSKernel, ARDKernel, MaternKernel, RQKernel, PeriodicKernel, LinearKernel).  ``noise``: the
     starting likelihood noise (the likelihood object's own, else raw value 0, when None).  ``m`` starts at ``mean_init_std`` times standard normals from
     torch's global generator (drawn here, on the host), ``L_s`` at the identity."""
 
@@ -765,7 +818,8 @@ class DirichletExactGP(_ExactGPClasses):
     gpytorch model of experiments/curves/classification/main.py:162-192 and experiments/uci/classification/main.py:133-163.
 
     ``raw`` is ONE (C, 3 + nls) float64 CPU parameter, row c in ExactGP's column order (mean, raw noise, raw outputscale,
-    raw lengthscales; (C, 4 + nls) with raw alpha last for the rational-quadratic kernel); every raw value starts at 0.  ``transformed_targets`` and ``fixed_noise`` are (C, n);
+    raw lengthscales; (C, 4 + nls) with raw alpha last for the rational-quadratic kernel, (C, 3 + 2 nls) with the raw period
+    lengths last for the periodic kernel); every raw value starts at 0.  ``transformed_targets`` and ``fixed_noise`` are (C, n);
     ``fixed_noise=False`` leaves the fixed part out (``self.fixed_noise`` is then None): what the reference trains on
     when its subsample is smaller than its data.
     One evaluation of all classes is ONE library call with one read-back, ``pls_gp_mll_grad_classes``."""
@@ -792,7 +846,7 @@ class DirichletExactGP(_ExactGPClasses):
 
     def evaluate_on_device(self, jitter: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor]:
         """One pls_gp_mll_grad_classes call at the current parameters: (the (C, 4 + d) outputs on the CPU -- rational
-        quadratic: (C, 5 + d) --, info (C))."""
+        quadratic: (C, 5 + d), periodic: (C, 4 + 2 d) --, info (C))."""
         return self._evaluate(jitter)
 
     def predict(self, x_test: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -830,8 +884,10 @@ def train_exact_gp(x: torch.Tensor, y: torch.Tensor, kernel, seed: int, number_o
     loss, the early-stopper check BEFORE the loss is recorded and before the step, then the step.  ``evaluate(model) ->
     (loss, gradient)`` replaces ``model.loss_and_grad`` (a host evaluation drives the same loop without a device).
     ``likelihood="dirichlet"``: y holds integer labels and the model is a DirichletExactGP (``number_of_classes`` and
-    ``fixed_noise`` go to it); the loss is then summed over the classes, as the reference's ``.sum()`` over the batch."""
+    ``fixed_noise`` go to it); the loss is then summed over the classes, as the reference's ``.sum()`` over the batch.
+    ``kernel``: as the model classes take it, and also "periodic" (the model classes' ``kernel=PeriodicKernel``)."""
     set_seed(seed)
+    kernel = PeriodicKernel if isinstance(kernel, str) and kernel == "periodic" else kernel
     if likelihood == "gaussian":
         model = ExactGP(x, y, kernel)
     elif likelihood == "dirichlet":
@@ -858,13 +914,20 @@ def construct_average_ard_kernel(models: Sequence[ExactGP]) -> BaseKernel:
     """The kernel of the AVERAGED RAW parameters, softplus applied afterwards (constructors.py:28-53 averages the
     entries of ``state_dict()``, which are the raw values).  A DirichletExactGP holds one row of raw values per class: its
     rows are averaged first (the reference's ``mean(dim=0)`` over the batch), then the models.  The rational-quadratic
-    kernel's raw alpha is averaged like the other raw values and the result is an RQKernel."""
+    kernel's raw alpha is averaged like the other raw values and the result is an RQKernel; the periodic kernel's raw period
+    lengths are averaged like its raw lengthscales and the result is a PeriodicKernel."""
     first = models[0]
     per_model = [m.raw_parameters() for m in models]
     raw = torch.stack([(r.mean(dim=0) if r.dim() == 2 else r)[2:] for r in per_model]).mean(dim=0)
     outputscale, ls = float(_softplus(raw[0])), _softplus(raw[1:raw.numel() - first._nshape])
     ls = ls.expand(first.d).clone() if ls.numel() == 1 and first.d > 1 else ls
-    return first._make_kernel(ls, outputscale, float(_softplus(raw[-1])) if first._nshape else None)
+    shape = None
+    if first.kernel_name == "rq":
+        shape = float(_softplus(raw[-1]))
+    if first.kernel_name == "periodic":
+        shape = _softplus(raw[raw.numel() - first._nshape:])
+        shape = shape.expand(first.d).clone() if shape.numel() == 1 and first.d > 1 else shape
+    return first._make_kernel(ls, outputscale, shape)
 
 
 def construct_average_gaussian_noise(models: Sequence[ExactGP]) -> float:

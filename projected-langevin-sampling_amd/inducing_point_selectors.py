@@ -42,9 +42,10 @@ class ConditionalVarianceInducingPointSelector(InducingPointSelector):
             # the reference would select on r = k(., S) k(S, .)^T / |S| (an N x N Gram of the PLS kernel); its experiments
             # always pass the base ScaleKernel(RBFKernel) (experiments/uci/regression/main.py:203), and so must callers here
             raise TypeError("ConditionalVarianceInducingPointSelector selects on a base kernel (ARDKernel / MaternKernel / "
-                            "RQKernel / LinearKernel / a gpytorch ScaleKernel(RBFKernel | MaternKernel | RQKernel)); pass "
+                            "RQKernel / PeriodicKernel / LinearKernel / a gpytorch ScaleKernel(RBFKernel | MaternKernel | RQKernel | "
+                            "PeriodicKernel)); pass "
                             "pls_kernel.base_kernel, not the PLSKernel")
-        # our kernels as is; ScaleKernel(RBFKernel | MaternKernel | RQKernel): lengthscale AND outputscale (and nu or alpha)
+        # our kernels as is; ScaleKernel(RBFKernel | MaternKernel | RQKernel | PeriodicKernel): lengthscale AND outputscale (and nu, alpha or period_length)
         base = as_base_kernel(kernel)
         n = x.shape[0]
         perm = np.random.permutation(n)  # permute entries so tie-breaking is random (:58-61)

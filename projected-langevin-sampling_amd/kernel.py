@@ -2,8 +2,9 @@
 
 The reference takes a gpytorch kernel object; gpytorch is a host-side hyper-parameter container there.
 Here kernels are plain parameter holders whose Gram matrices are built by libplship on the MI355X.
-A gpytorch ScaleKernel(RBFKernel), ScaleKernel(MaternKernel) or ScaleKernel(RQKernel) instance is accepted wherever a
-base kernel is expected: its lengthscale / outputscale (and nu or alpha) are read once (``as_base_kernel``)."""
+A gpytorch ScaleKernel(RBFKernel), ScaleKernel(MaternKernel), ScaleKernel(RQKernel) or ScaleKernel(PeriodicKernel) instance
+is accepted wherever a base kernel is expected: its lengthscale / outputscale (and nu, alpha or period_length) are read
+once (``as_base_kernel``)."""
 from __future__ import annotations
 
 import torch
@@ -124,6 +125,40 @@ class RQKernel(_StationaryKernel):
         return self._ls_dev[d]
 
 
+class PeriodicKernel(_StationaryKernel):
+    """ScaleKernel(PeriodicKernel(ard_num_dims=D)), the periodic kernel: with e_d = (a_d - b_d) / period_length_d,
+    k(a,b) = outputscale * exp(-2 sum_d sin^2(pi e_d) / lengthscale_d),
+    gpytorch's PeriodicKernel as recalled (include/plship.h states the formula; it is the contract): the lengthscale divides
+    and is NOT squared -- MacKay's l^2 is this lengthscale.  ``lengthscale`` and ``period_length`` each hold d (or one
+    shared) positive values; the library reads the period lengths behind the lengthscales, so the device array has 2 d
+    entries.  d <= 16."""
+
+    kind = L.KERNEL_PERIODIC
+
+    def __init__(self, lengthscale, outputscale: float = 1.0, period_length=1.0):
+        period = torch.as_tensor(period_length, dtype=torch.float64).detach().reshape(-1).cpu()
+        if period.numel() == 0 or not bool((period > 0.0).all()):
+            raise ValueError(f"PeriodicKernel: every period length must be positive, got {period.tolist()}")
+        super().__init__(lengthscale, outputscale)
+        if not bool((self.lengthscale > 0.0).all()):
+            raise ValueError(f"PeriodicKernel: every lengthscale must be positive, got {self.lengthscale.tolist()}")
+        self.period_length = period
+
+    def _lengthscale_host(self, d: int) -> torch.Tensor:
+        """the 2 d values the library reads: the lengthscales, then the period lengths (a shared one repeated)"""
+        parts = []
+        for name, v in (("lengthscale", self.lengthscale), ("period_length", self.period_length)):
+            v = v.expand(d) if v.numel() == 1 else v
+            assert v.numel() == d, f"{name} has {v.numel()} entries, data has {d} dims"
+            parts.append(v)
+        return torch.cat(parts)
+
+    def _lengthscale_dev(self, d: int) -> torch.Tensor:
+        if d not in self._ls_dev:
+            self._ls_dev[d] = _dev(self._lengthscale_host(d))
+        return self._ls_dev[d]
+
+
 class LinearKernel(BaseKernel):
     """k(x1, x2) = x1 x2^T: the reference's test double (mockers/kernel.py:8-23)."""
 
@@ -132,8 +167,8 @@ class LinearKernel(BaseKernel):
 
 def as_base_kernel(kernel) -> BaseKernel:
     """Accept our kernels, or read the hyper-parameters of a gpytorch ScaleKernel(RBFKernel), ScaleKernel(MaternKernel) (an
-    inner kernel with a ``nu`` attribute; nu outside {0.5, 1.5, 2.5} raises ValueError) or ScaleKernel(RQKernel) (an inner
-    kernel with an ``alpha`` attribute)."""
+    inner kernel with a ``nu`` attribute; nu outside {0.5, 1.5, 2.5} raises ValueError), ScaleKernel(RQKernel) (an inner
+    kernel with an ``alpha`` attribute) or ScaleKernel(PeriodicKernel) (an inner kernel with a ``period_length`` attribute)."""
     if isinstance(kernel, BaseKernel):
         return kernel
     inner = getattr(kernel, "base_kernel", None)
@@ -144,8 +179,11 @@ def as_base_kernel(kernel) -> BaseKernel:
             return MaternKernel(lengthscale=lengthscale, outputscale=outputscale, nu=inner.nu)
         if hasattr(inner, "alpha"):
             return RQKernel(lengthscale=lengthscale, outputscale=outputscale, alpha=inner.alpha)
+        if hasattr(inner, "period_length"):
+            return PeriodicKernel(lengthscale=lengthscale, outputscale=outputscale,
+                                  period_length=torch.as_tensor(inner.period_length).detach().reshape(-1))
         return ARDKernel(lengthscale=lengthscale, outputscale=outputscale)
-    raise TypeError(f"unsupported base kernel {type(kernel).__name__}: use ARDKernel / MaternKernel / RQKernel / LinearKernel")
+    raise TypeError(f"unsupported base kernel {type(kernel).__name__}: use ARDKernel / MaternKernel / RQKernel / PeriodicKernel / LinearKernel")
 
 
 class PLSKernel:

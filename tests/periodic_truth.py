@@ -1,0 +1,157 @@
+"""The yardstick of the periodic exact-GP tests, modelled on rq_truth.py: the closed-form kernel and its derivatives with
+respect to the lengthscales and the period lengths, the 2 d + 1 pair sums of pls_kernel_grad_sums, and the marginal
+log-likelihood with its 4 + 2 d derivatives through LAPACK -- float64 on the CPU, sums by math.fsum -- together with the
+tables of tests/golden/periodic_truth.npz (50-digit values, written by tests/golden/make_periodic_truth.py).
+
+With e_k = (x_ik - x_jk) / p_k and kappa = exp(-2 sum_k sin^2(pi e_k) / lambda_k) the kernel without its outputscale s:
+    dK / d log lambda_k = s kappa (2 / lambda_k) sin^2(pi e_k)
+    dK / d log p_k      = s kappa (2 / lambda_k) pi e_k sin(2 pi e_k)
+A pair at distance 0 has both derivatives 0; a pair whose kappa is 0 contributes 0 everywhere."""
+import math
+import os
+
+import numpy as np
+import torch
+
+from exact_gp_truth import EPS, MEAN, NOISE, OUTPUTSCALE, fsum_rows  # noqa: F401
+from periodic_closed_form import periodic_factors_numpy, sensitivity
+from truth_common import _normal, _uniform, checksum, fixture_truth, relative_error  # noqa: F401
+
+PERIODIC = 8  # pls_kernel_kind
+TRUTH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "periodic_truth.npz")
+
+
+def _np(v):
+    return (v.detach().double().numpy() if torch.is_tensor(v) else np.asarray(v, dtype=np.float64))
+
+
+def factors(x, ls, period):
+    """(kappa (n, n), fl (n, n, d), fp (n, n, d), e (n, n, d)) of all pairs of x, numpy"""
+    x = _np(x)
+    x = x if x.ndim == 2 else x[:, None]
+    return periodic_factors_numpy(x[:, None, :] - x[None, :, :], _np(ls), _np(period))
+
+
+def kappa(x, ls, period):
+    return torch.from_numpy(factors(x, ls, period)[0])
+
+
+def pair_terms(x, ls, period, s, alpha, p, majorant=False):
+    """(2 d + 1, n, n): the terms W_ij kappa_ij, W_ij dK_ij / d log lambda_k and W_ij dK_ij / d log p_k, W = alpha alpha^T - P.
+    ``majorant``: instead of each term what bounds its first-order error budget -- |W| kappa, |W| s kappa fl_k and
+    |W| s kappa (2 / lambda_k) pi |e_k| (the period term with |sin(2 pi e)| replaced by 1), each times the pair's sensitivity
+    c_ij = 1 + sum_k (2 pi / lambda_k) |e_k| (periodic_closed_form.sensitivity)."""
+    w = _np(alpha)[:, None] * _np(alpha)[None, :] - _np(p)
+    kap, fl, fp, e = factors(x, ls, period)
+    lam = _np(ls).reshape(-1)
+    if majorant:
+        c = sensitivity(e, lam)
+        aw = np.abs(w) * kap * c
+        per = (2.0 / lam) * np.pi * np.abs(e)
+        terms = [aw] + [aw * s * fl[..., k] for k in range(lam.size)] + [aw * s * per[..., k] for k in range(lam.size)]
+    else:
+        wk = np.where(kap == 0.0, 0.0, w * kap)
+        terms = [wk] + [wk * (s * fl[..., k]) for k in range(lam.size)] + [wk * (s * fp[..., k]) for k in range(lam.size)]
+    return torch.from_numpy(np.stack(terms))
+
+
+def grad_sums(x, ls, period, s, alpha, p):
+    """what pls_kernel_grad_sums computes for PLS_KERNEL_PERIODIC (2 d + 1 sums), and per output the scale sum_ij |term|"""
+    return fsum_rows(pair_terms(x, ls, period, s, alpha, p))
+
+
+def grad_sums_majorant(x, ls, period, s, alpha, p):
+    """per output the scale S of the reduction test: the fsum of the majorant of its terms"""
+    return fsum_rows(pair_terms(x, ls, period, s, alpha, p, majorant=True))[0]
+
+
+def mll_and_grad(x, y, ls, period, s, noise, mean, fixed=None):
+    """The 4 + 2 d outputs of pls_gp_mll_grad for PLS_KERNEL_PERIODIC through LAPACK and, per output, its sum-of-magnitudes
+    scale (exact_gp_truth.mll_and_grad with the period derivatives behind the lengthscale derivatives)"""
+    x = x if x.dim() == 2 else x[:, None]
+    n, d = x.shape
+    diag = torch.full((n,), float(noise), dtype=torch.float64) if fixed is None else fixed.double() + float(noise)
+    ky = s * kappa(x, ls, period) + torch.diag(diag)
+    low = torch.linalg.cholesky(ky)
+    r = y.double() - mean
+    alpha = torch.cholesky_solve(r[:, None], low)[:, 0]
+    p = torch.cholesky_inverse(low)
+    p = 0.5 * (p + p.T)
+    logs = torch.log(low.diagonal())
+    quad = math.fsum((r * alpha).tolist())
+    sums, scale = grad_sums(x, ls, period, s, alpha, p)
+    wdiag = alpha * alpha - p.diagonal()
+    out = np.empty(4 + 2 * d)
+    mag = np.empty_like(out)
+    out[0] = -0.5 * quad - math.fsum(logs.tolist()) - 0.5 * n * math.log(2.0 * math.pi)
+    mag[0] = 0.5 * abs(quad) + math.fsum(logs.abs().tolist())
+    out[1], mag[1] = math.fsum(alpha.tolist()), math.fsum(alpha.abs().tolist())
+    out[2], mag[2] = 0.5 * math.fsum(wdiag.tolist()), 0.5 * math.fsum(wdiag.abs().tolist())
+    out[3], mag[3] = 0.5 * s * sums[0], 0.5 * s * scale[0]
+    out[4:], mag[4:] = 0.5 * sums[1:], 0.5 * scale[1:]
+    return out, mag
+
+
+def host_evaluate(model):
+    """``evaluate`` for train_exact_gp: the model's loss and raw gradient from this module's LAPACK evaluation"""
+    out, _ = mll_and_grad(model.x, model.y, model.lengthscale, model.period_length, model.outputscale, model.noise,
+                          model.mean_constant)
+    return model.chain_rule(torch.from_numpy(out))
+
+
+# ---- the fixture's per-pair table (d = 1) -------------------------------------------------------------------------------
+#: e = delta / p: 0, the small-argument range, the swap of sine and cosine at 1/4, the rounding boundary at 1/2 and its two
+#: neighbours, whole periods, large arguments (exact quarter, spacing 1, spacing 1/8) and ordinary values
+PAIR_E = np.array([0.0, 1e-300, 1e-16, 1e-9, 0.25, np.nextafter(0.5, 0.0), 0.5, np.nextafter(0.5, 1.0), 1.0, 1000.25, 2.0**52,
+                   1e15 + 0.5, 0.1, 0.3, 0.77, 1.4, 2.6, -0.37, 7.125, 33.3])
+PAIR_PERIODS = (1.0, 0.7, 2.0**-3)
+PAIR_LENGTHSCALE = 0.8
+
+
+def pair_deltas():
+    """(len(PAIR_PERIODS), len(PAIR_E)): the differences fl(e p) the table is evaluated at"""
+    return np.stack([PAIR_E * p for p in PAIR_PERIODS])
+
+
+def pair_truth():
+    """(hi, lo) of shape (len(PAIR_PERIODS), 3, len(PAIR_E)): 50-digit kappa, fl and fp per period and difference"""
+    return fixture_truth(TRUTH, "pairs", [torch.from_numpy(pair_deltas()), torch.tensor(PAIR_PERIODS + (PAIR_LENGTHSCALE,),
+                                                                                       dtype=torch.float64)])
+
+
+# ---- the fixture's whole-evaluation cases: name -> (n, d, seed) -----------------------------------------------------------
+CASES = {"periodic-n70-d1": (70, 1, 810701), "periodic-n65-d3": (65, 3, 810653), "periodic-n130-d8": (130, 8, 811308)}
+
+
+def case_inputs(name):
+    """x ~ N(0, I) (n, d), y = 2 t / (1 + t^2) + 0.3 N(0, 1) with t = sum_k x_k, lengthscale = (0.5 + U) d, period length =
+    0.5 + 2.5 U"""
+    n, d, seed = CASES[name]
+    g = torch.Generator().manual_seed(seed)
+    x = _normal(g, (n, d))
+    t = torch.zeros(n, dtype=torch.float64)
+    for k in range(d):
+        t = t + x[:, k]
+    y = 2.0 * t / (1.0 + t * t) + 0.3 * _normal(g, (n,))
+    ls = (0.5 + _uniform(g, (d,))) * d
+    period = 0.5 + 2.5 * _uniform(g, (d,))
+    return x, y, ls, period
+
+
+def truth(name):
+    """the 50-digit outputs (4 + 2 d) of a case as (hi, lo) float64 pairs, after checking that the inputs are the recorded ones"""
+    return fixture_truth(TRUTH, name, list(case_inputs(name)))
+
+
+_cpu_cache = {}
+
+
+def cpu_case(name):
+    """(out, scale, e_cpu) of a case: this module's LAPACK evaluation, its scales, and per output its error against the
+    50-digit truth relative to the scale -- computed once and shared"""
+    if name not in _cpu_cache:
+        x, y, ls, period = case_inputs(name)
+        out, mag = mll_and_grad(x, y, ls, period, OUTPUTSCALE, NOISE, MEAN)
+        hi, lo = truth(name)
+        _cpu_cache[name] = (out, mag, relative_error(out, hi, lo, mag))
+    return _cpu_cache[name]

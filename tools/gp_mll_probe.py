@@ -24,7 +24,7 @@ import projected_langevin_sampling_amd as pkg  # noqa: E402
 
 L = pkg._lib
 F64 = torch.float64
-KINDS = {"rbf": L.KERNEL_RBF_ARD, "matern52": L.KERNEL_MATERN52, "rq": L.KERNEL_RQ}
+KINDS = {"rbf": L.KERNEL_RBF_ARD, "matern52": L.KERNEL_MATERN52, "rq": L.KERNEL_RQ, "periodic": L.KERNEL_PERIODIC}
 RQ_ALPHA = math.log(2.0)  # behind the lengthscales in the library's array; its derivative is the last output
 
 
@@ -52,7 +52,7 @@ def library_stages(kind, x, y, ls, s, noise, mean, repeats):
     ky, lc, lct, sf, sb, linv, linvt = planes
     r, alpha = (y - mean).contiguous(), torch.empty(n, dtype=F64, device="cuda")
     info = torch.zeros(1, dtype=torch.int32, device="cuda")
-    extra = 1 if kind == L.KERNEL_RQ else 0
+    extra = 1 if kind == L.KERNEL_RQ else d if kind == L.KERNEL_PERIODIC else 0  # (shape values behind the lengthscales)
     out = torch.empty(4 + d + extra, dtype=F64, device="cuda")
     nbytes = lib.pls_gp_mll_workspace_bytes_kind(kind, n, d)
     ws = torch.empty(nbytes // 8, dtype=F64, device="cuda")
@@ -97,22 +97,29 @@ def library_stages(kind, x, y, ls, s, noise, mean, repeats):
 
 
 def torch_route(kind, x, y, ls, s, noise, mean, repeats):
-    """-> (ms, the same 4 + d numbers, 5 + d for RQ): value and gradient by autograd through torch.linalg.cholesky, fp64,
+    """-> (ms, the same 4 + d numbers, 5 + d for RQ, 4 + 2 d for periodic): value and gradient by autograd through torch.linalg.cholesky, fp64,
     same device"""
     n, d = x.shape
     leaves = [torch.tensor(v, dtype=F64, device="cuda", requires_grad=True) for v in (mean, noise, math.log(s))]
     log_ls = ls[:d].log().clone().requires_grad_(True)
     log_alpha = torch.tensor(math.log(RQ_ALPHA), dtype=F64, device="cuda", requires_grad=True)
+    log_p = (ls[d:2 * d] if kind == L.KERNEL_PERIODIC else ls[:d]).log().clone().requires_grad_(True)  # (periodic only)
     result = {}
 
     def run():
-        for t in leaves + [log_ls, log_alpha]:
+        for t in leaves + [log_ls, log_alpha, log_p]:
             t.grad = None
         e2 = torch.zeros((n, n), dtype=F64, device="cuda")
         for k in range(d):
+            if kind == L.KERNEL_PERIODIC:  # (e2 holds the negated exponent, sum_k 2 sin^2(pi e_k) / lambda_k)
+                e = (x[:, k][:, None] - x[:, k][None, :]) / log_p[k].exp()
+                e2 = e2 + 2.0 * torch.sin(math.pi * e).square() / log_ls[k].exp()
+                continue
             a = x[:, k] / log_ls[k].exp()
             e2 = e2 + (a[:, None] - a[None, :]).square()
-        if kind == L.KERNEL_RBF_ARD:
+        if kind == L.KERNEL_PERIODIC:
+            kap = torch.exp(-e2)
+        elif kind == L.KERNEL_RBF_ARD:
             kap = torch.exp(-0.5 * e2)
         elif kind == L.KERNEL_RQ:
             kap = torch.exp(-log_alpha.exp() * torch.log1p(e2 / (2.0 * log_alpha.exp())))
@@ -126,7 +133,7 @@ def torch_route(kind, x, y, ls, s, noise, mean, repeats):
         alpha = torch.cholesky_solve(r[:, None], low)[:, 0]
         mll = -0.5 * r @ alpha - torch.log(low.diagonal()).sum() - 0.5 * n * math.log(2.0 * math.pi)
         mll.backward()
-        tail = [log_alpha.grad.reshape(1)] if kind == L.KERNEL_RQ else []
+        tail = [log_alpha.grad.reshape(1)] if kind == L.KERNEL_RQ else [log_p.grad] if kind == L.KERNEL_PERIODIC else []
         result["out"] = torch.cat([mll.detach().reshape(1), torch.stack([t.grad for t in leaves]), log_ls.grad] + tail)
 
     return timed(run, repeats), result["out"].cpu()
@@ -153,6 +160,8 @@ def main():
                 x = torch.randn(n, d, generator=g, dtype=F64).cuda()
                 y = (torch.sin(x.sum(dim=1)) + 0.3 * torch.randn(n, generator=g, dtype=F64).cuda()).contiguous()
                 ls = torch.cat([(0.5 + torch.rand(d, generator=g, dtype=F64)) * d**0.5, torch.tensor([RQ_ALPHA], dtype=F64)]).cuda()
+                if kind == L.KERNEL_PERIODIC:  # (lengthscales (0.5 + U) d, then the period lengths 0.5 + 2.5 U)
+                    ls = torch.cat([(0.5 + torch.rand(d, generator=g, dtype=F64)) * d, 0.5 + 2.5 * torch.rand(d, generator=g, dtype=F64)]).cuda()
                 res, out = library_stages(kind, x, y, ls, 1.3, 0.1, 0.2, args.repeats)
                 row = (f"{name:9s} {n:5d} {d:2d} {res['whole']:8.3f} {res['gram']:7.3f} {res['factor']:7.3f} {res['solve']:7.3f} "
                        f"{res['inverse']:7.3f} {res['product+small']:13.3f} {res['reduction']:9.3f} "

@@ -5,7 +5,8 @@
   fused         pls_kernel_mean: out = c + s sum_j kappa(x*_i, x_j) alpha_j, no matrix
   materialised  pls_kernel_gram into an n x t plane, then pls_gemm_tn (plane^T alpha): what ExactGP.predict does for its mean
 
-for RBF, Matern-5/2 and the rational-quadratic kernel (alpha = ln 2) at (n, t, d) = (500, 1000, 1), (2000, 6500, 8), (5000, 36000, 8).  After a warm-up of each route the
+for RBF, Matern-5/2, the rational-quadratic kernel (alpha = ln 2) and the periodic kernel (lengthscales (0.5 + U) d, period
+lengths 0.5 + 2.5 U) at (n, t, d) = (500, 1000, 1), (2000, 6500, 8), (5000, 36000, 8).  After a warm-up of each route the
 timed calls alternate between the routes, each between its own pair of HIP events on torch's stream (the protocol of
 tools/matern_gram_probe.py), so that drifts of clock or temperature fall on both alike.  Prints per route the median and
 the 10th-90th percentile, the largest |fused - materialised| relative to the outputscale, the peak device memory of each
@@ -21,7 +22,7 @@ import torch
 import projected_langevin_sampling_amd as pkg
 
 L = pkg._lib
-KINDS = {L.KERNEL_RBF_ARD: "rbf", L.KERNEL_MATERN52: "matern52", L.KERNEL_RQ: "rq"}
+KINDS = {L.KERNEL_RBF_ARD: "rbf", L.KERNEL_MATERN52: "matern52", L.KERNEL_RQ: "rq", L.KERNEL_PERIODIC: "periodic"}
 SHAPES = [(500, 1000, 1), (2000, 6500, 8), (5000, 36000, 8)]
 S, MEAN = 1.7, 0.3
 
@@ -44,7 +45,11 @@ def main():
         ls = torch.cat([(0.5 + torch.rand(d, generator=g, dtype=torch.float64)) * d**0.5,
                         torch.tensor([0.6931471805599453], dtype=torch.float64)]).cuda()  # (+ RQ's alpha, behind the lengthscales)
         alpha = torch.randn(n, generator=g, dtype=torch.float64).cuda()
+        ls_all = ls
+        ls_periodic = torch.cat([(0.5 + torch.rand(d, generator=g, dtype=torch.float64)) * d,
+                                 0.5 + 2.5 * torch.rand(d, generator=g, dtype=torch.float64)]).cuda()  # (lengthscales, period lengths)
         for kind, kind_name in KINDS.items():
+            ls = ls_periodic if kind == L.KERNEL_PERIODIC else ls_all
             torch.cuda.synchronize()
             torch.cuda.reset_peak_memory_stats()
             floor = torch.cuda.memory_allocated()

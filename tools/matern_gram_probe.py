@@ -4,7 +4,8 @@
 
 Shapes: k(Z, X) of configs[1] (1024 x 1e5, D = 8) and of configs[2] (512 x 5e4, D = 8).  Every library is loaded into this
 one process (ctypes, RTLD_LOCAL); the RBF-ARD kind is timed for all of them, the Matern kinds for those whose ABI version is
-7 or later, the rational-quadratic kind (alpha = ln 2, behind the lengthscales) for those that export the kind-aware workspace queries.  After a warm-up of each (library, kind), the timed launches go round-robin over all (library, kind) pairs, each
+7 or later, the rational-quadratic kind (alpha = ln 2, behind the lengthscales) for those that export the kind-aware workspace queries,
+the periodic kind (period lengths 0.5 + 2.5 U behind the lengthscales) for those that do not call kind 8 unknown.  After a warm-up of each (library, kind), the timed launches go round-robin over all (library, kind) pairs, each
 between its own pair of HIP events on torch's stream, so that drifts of clock or temperature fall on every pair alike.
 Prints one line per pair (median, 10th-90th percentile, min, max, median / first library's RBF median) and a JSON line."""
 import argparse
@@ -14,7 +15,7 @@ import statistics
 
 import torch
 
-KINDS = {0: "rbf", 2: "matern12", 3: "matern32", 4: "matern52", 6: "rq"}
+KINDS = {0: "rbf", 2: "matern12", 3: "matern32", 4: "matern52", 6: "rq", 8: "periodic"}
 SHAPES = [("configs[1] k(Z,X)", 1024, 100_000, 8), ("configs[2] k(Z,X)", 512, 50_000, 8)]
 
 
@@ -38,7 +39,9 @@ def main():
     for spec in args.libs:
         name, path = spec.split("=", 1)
         lib = load(path)
-        libs.append((name, lib, [0] + ([2, 3, 4] if lib.pls_abi_version() >= 7 else []) + ([6] if hasattr(lib, "pls_gp_mll_workspace_bytes_kind") else [])))
+        kinds = [0] + ([2, 3, 4] if lib.pls_abi_version() >= 7 else []) + ([6] if hasattr(lib, "pls_gp_mll_workspace_bytes_kind") else [])
+        lib.pls_kernel_gram(8, 8, 1, 8, 1, 1, None, 1.0, 8, 1, None)  # (refused before any launch: unknown, or "needs lengthscale")
+        libs.append((name, lib, kinds + ([8] if b"unknown" not in lib.pls_last_error() else [])))
     torch.cuda.init()
     stream = torch.cuda.current_stream()
     sp = stream.cuda_stream
@@ -48,11 +51,13 @@ def main():
         z = (torch.rand(n1, d, generator=g, dtype=torch.float64) * 2 - 1).cuda()
         x = (torch.rand(n2, d, generator=g, dtype=torch.float64) * 2 - 1).cuda()
         ls = torch.cat([0.5 + torch.rand(d, generator=g, dtype=torch.float64), torch.tensor([0.6931471805599453], dtype=torch.float64)]).cuda()  # (+ RQ's alpha)
+        ls_periodic = torch.cat([ls[:d].cpu(), 0.5 + 2.5 * torch.rand(d, generator=g, dtype=torch.float64)]).cuda()  # (+ the period lengths)
         out = torch.empty(n1, n2, dtype=torch.float64, device="cuda")
         pairs = [(name, lib, kind) for name, lib, kinds in libs for kind in kinds]
 
         def launch(lib, kind):
-            rc = lib.pls_kernel_gram(kind, z.data_ptr(), n1, x.data_ptr(), n2, d, ls.data_ptr(), 1.7, out.data_ptr(), n2, sp)
+            rc = lib.pls_kernel_gram(kind, z.data_ptr(), n1, x.data_ptr(), n2, d, (ls_periodic if kind == 8 else ls).data_ptr(), 1.7,
+                                     out.data_ptr(), n2, sp)
             if rc:
                 raise RuntimeError(f"pls_kernel_gram(kind {kind}): {lib.pls_last_error().decode()}")
 
