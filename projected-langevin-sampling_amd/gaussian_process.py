@@ -21,7 +21,7 @@ import torch
 from . import _lib as L
 from . import _ops
 from ._chol import CHOLESKY_JITTER, CHOLESKY_MAX_TRIES, NotPSDError, cholesky_factor
-from .kernel import ARDKernel, BaseKernel, MaternKernel, PeriodicKernel, RQKernel, _dev
+from .kernel import STATIONARY_KERNELS, BaseKernel, MaternKernel, PeriodicKernel, _dev
 from .likelihoods import GaussianLikelihood, _Likelihood
 from .trainers import EarlyStopper
 from .utils import set_seed
@@ -29,11 +29,12 @@ from .utils import set_seed
 #: gpytorch's GaussianLikelihood keeps its noise above this bound (GreaterThan(1e-4)): noise = 1e-4 + softplus(raw)
 NOISE_LOWER_BOUND = 1e-4
 
+#: the name table: what ``kernel`` may be as a string -> (the family of a class of kernel.STATIONARY_KERNELS, the nu it names).
+#: A kernel CLASS names its family too, every raw value at 0.  It is the only way to ask the model classes for the periodic
+#: family without starting values: they keep refusing the bare name "periodic" (train_exact_gp and exact_gp_runner take it)
 _KERNEL_NAMES = {"rbf": ("rbf", None), "matern": ("matern", None), "matern12": ("matern", 0.5), "matern32": ("matern", 1.5),
                  "matern52": ("matern", 2.5), "rq": ("rq", None)}
-#: a kernel CLASS names its family too, every raw value at 0.  It is the only way to ask the model classes for the periodic
-#: family without starting values: they keep refusing the bare name "periodic" (train_exact_gp and exact_gp_runner take it)
-_KERNEL_CLASSES = {ARDKernel: "rbf", MaternKernel: "matern", RQKernel: "rq", PeriodicKernel: "periodic"}
+_FAMILIES = {cls.family: cls for cls in STATIONARY_KERNELS}
 
 
 def _softplus(v: torch.Tensor) -> torch.Tensor:
@@ -44,44 +45,47 @@ def _inverse_softplus(v: torch.Tensor) -> torch.Tensor:
     return v + torch.log(-torch.expm1(-v))
 
 
+def _repeated(v: torch.Tensor, width: int) -> torch.Tensor:
+    """``v`` with ``width`` entries along its last dimension: one value shared by all dimensions is repeated"""
+    return v.expand(*v.shape[:-1], width).clone() if v.shape[-1] == 1 and width > 1 else v
+
+
 def _kernel_choice(who: str, kernel, nu: float, ard: bool, d: int):
-    """(name, nu, ard, start) of the ``kernel`` argument of ExactGP / DirichletExactGP; start: the kernel object whose values
-    the raw parameters start from, or None"""
+    """(family: a class of STATIONARY_KERNELS, nu, ard, start) of the ``kernel`` argument of ExactGP / DirichletExactGP;
+    start: the kernel object whose values the raw parameters start from, or None"""
     start = None
-    if isinstance(kernel, type) and kernel in _KERNEL_CLASSES:
-        name = _KERNEL_CLASSES[kernel]
+    if isinstance(kernel, type) and kernel in STATIONARY_KERNELS:
+        family = kernel
     elif isinstance(kernel, BaseKernel):
-        if not isinstance(kernel, (ARDKernel, MaternKernel, RQKernel, PeriodicKernel)):
+        if not isinstance(kernel, STATIONARY_KERNELS):
             raise TypeError(f"{who}: the kernel must be an ARDKernel, a MaternKernel, an RQKernel or a PeriodicKernel (a "
                             "lengthscale and an outputscale to learn)")
-        start = kernel
-        if isinstance(kernel, MaternKernel):
-            name, nu = "matern", kernel.nu
-        else:
-            name = "rq" if isinstance(kernel, RQKernel) else "periodic" if isinstance(kernel, PeriodicKernel) else "rbf"
+        start, family = kernel, _FAMILIES[kernel.family]
+        nu = getattr(kernel, "nu", nu)
         ard = kernel.lengthscale.numel() > 1 or d == 1 and ard
-        if name == "periodic":  # per-dimension period lengths need per-dimension raw values too
-            ard = ard or kernel.period_length.numel() > 1
+        if family.shape_per_dim:  # per-dimension shape values need per-dimension raw values too
+            ard = ard or getattr(kernel, family.shape_attr).numel() > 1
     else:
         if kernel not in _KERNEL_NAMES:
             raise ValueError(f"{who}: kernel must be one of {sorted(_KERNEL_NAMES)}, a kernel class or a kernel object, got {kernel!r}")
         name, named_nu = _KERNEL_NAMES[kernel]
-        nu = named_nu if named_nu is not None else nu
-    if name == "matern" and float(nu) not in MaternKernel.KINDS:
+        family, nu = _FAMILIES[name], named_nu if named_nu is not None else nu
+    if family is MaternKernel and float(nu) not in MaternKernel.KINDS:
         raise ValueError(f"{who}: nu must be 0.5, 1.5 or 2.5, got {nu}")
-    return name, (float(nu) if name == "matern" else None), bool(ard), start
+    return family, (float(nu) if family is MaternKernel else None), bool(ard), start
 
 
 class _ExactGPClasses:
     """What ExactGP and DirichletExactGP share: C independent exact GPs on the shared x, class c with a constant mean m_c,
     K_c = s_c kappa(x, x; l_c) and K_y,c = K_c + diag(v_c) + sigma_c I, parametrised as gpytorch does: ``lengthscale =
     softplus(raw)``, ``outputscale = softplus(raw)``, ``noise = 1e-4 + softplus(raw)``, the mean constant itself; every raw
-    value starts at 0.  ``raw`` is seen as (C, 3 + nls) rows: mean, raw noise, raw outputscale, raw lengthscales (d of
-    them, or one shared by all dimensions); the rational-quadratic kernel has (C, 4 + nls): raw alpha, ``alpha =
-    softplus(raw)``, is its LAST column; the periodic kernel has (C, 3 + 2 nls): the nls raw period lengths, ``period_length =
-    softplus(raw)``, behind the nls raw lengthscales.  x (n, d), the targets (C, n) and the fixed noise v (C, n), or None, are kept
-    as given and uploaded once, on the first evaluation on the device.  One evaluation of all classes is ONE library call
-    with one read-back, ``pls_gp_mll_grad_classes``."""
+    value starts at 0.  ``raw`` is seen as (C, 3 + nls + shape columns) rows: mean, raw noise, raw outputscale, the nls raw
+    lengthscales (d of them, or one shared by all dimensions), then the family's raw shape values, ``softplus(raw)`` each:
+    none for RBF and Matern, raw alpha for the rational-quadratic kernel, the nls raw period lengths for the periodic kernel
+    -- _lib.kernel_shape_params with the nls raw lengthscales in the place of the library's d.  x (n, d), the targets (C, n)
+    and the fixed noise v (C, n), or None, are kept as given and uploaded once, on the first evaluation on the device.  One
+    evaluation of all classes is ONE library call with one read-back, ``pls_gp_mll_grad_classes``: 4 + d + shape
+    parameters outputs per class."""
 
     def __init__(self, who: str, x: torch.Tensor, targets: torch.Tensor, fixed_noise: torch.Tensor | None, kernel, nu: float,
                  ard: bool):
@@ -89,26 +93,18 @@ class _ExactGPClasses:
         self.x = (x if x.dim() == 2 else x[:, None]).to(torch.float64)
         self.n, self.d = self.x.shape
         self._targets, self.fixed_noise = targets, fixed_noise
-        name, nu, ard, start = _kernel_choice(who, kernel, nu, ard, self.d)
-        self.kernel_name, self.ard, self.nu = name, ard, nu
-        self.kind = (MaternKernel.KINDS[self.nu] if name == "matern" else L.KERNEL_RQ if name == "rq"
-                     else L.KERNEL_PERIODIC if name == "periodic" else L.KERNEL_RBF_ARD)
-        nls = self.d if self.ard else 1
-        # raw shape columns behind the raw lengthscales (raw alpha; the nls raw period lengths), and the shape values per
-        # class as the library reads and differentiates them (alpha; the d period lengths)
-        self._nshape = 1 if name == "rq" else nls if name == "periodic" else 0
-        self._nshape_lib = 1 if name == "rq" else self.d if name == "periodic" else 0
-        raw = torch.zeros(targets.shape[0], 3 + nls + self._nshape, dtype=torch.float64)
+        self._family, self.nu, self.ard, start = _kernel_choice(who, kernel, nu, ard, self.d)
+        self.kernel_name = self._family.family
+        self.kind = self._family.kind if self.nu is None else MaternKernel.KINDS[self.nu]
+        self._nls = nls = self.d if self.ard else 1
+        raw = torch.zeros(targets.shape[0], 3 + nls + L.kernel_shape_params(self.kind, nls), dtype=torch.float64)
         if start is not None:
-            assert start.lengthscale.numel() in (1, nls), "the kernel's lengthscales do not fit the data"
             raw[:, 2] = _inverse_softplus(torch.tensor(start.outputscale, dtype=torch.float64))
-            raw[:, 3:3 + nls] = _inverse_softplus(start.lengthscale.expand(nls) if start.lengthscale.numel() == 1 else start.lengthscale)
-            if name == "rq":
-                raw[:, -1] = _inverse_softplus(torch.tensor(start.alpha, dtype=torch.float64))
-            if name == "periodic":
-                period = start.period_length
-                assert period.numel() in (1, nls), "the kernel's period lengths do not fit the data"
-                raw[:, 3 + nls:] = _inverse_softplus(period.expand(nls) if period.numel() == 1 else period)
+            for name, columns in (("lengthscale", raw[:, 3:3 + nls]), (self._family.shape_attr, raw[:, 3 + nls:])):
+                if name is not None:
+                    v = torch.as_tensor(getattr(start, name), dtype=torch.float64).reshape(-1)
+                    assert v.numel() in (1, columns.shape[1]), f"the kernel's {name.replace('_', ' ')}s do not fit the data"
+                    columns[:] = _inverse_softplus(_repeated(v, columns.shape[1]))
         self.raw = torch.nn.Parameter(raw)
         self._dev: dict = {}
 
@@ -127,43 +123,31 @@ class _ExactGPClasses:
     def _natural(self) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
         """(mean constant (C), noise (C), outputscale (C), lengthscale (C, d): a shared one repeated)"""
         raw = self.raw.detach().reshape(self._targets.shape[0], -1)
-        ls = _softplus(raw[:, 3:raw.shape[1] - self._nshape])
-        ls = ls.expand(-1, self.d).clone() if ls.shape[1] == 1 and self.d > 1 else ls
+        ls = _repeated(_softplus(raw[:, 3:3 + self._nls]), self.d)
         return raw[:, 0].clone(), NOISE_LOWER_BOUND + _softplus(raw[:, 1]), _softplus(raw[:, 2]), ls
 
-    def _alpha(self) -> torch.Tensor:
-        """(C) the rational-quadratic shape alpha = softplus(raw alpha)"""
-        if self.kernel_name != "rq":
-            raise AttributeError(f"the {self.kernel_name} kernel has no alpha")
-        return _softplus(self.raw.detach().reshape(self._targets.shape[0], -1)[:, -1])
+    def _shape(self, attr: str | None = None) -> torch.Tensor:
+        """(C, shape parameters) the family's shape values as the library reads and differentiates them, softplus(raw) with
+        a value shared by all dimensions repeated; (C, 0) for a family without.  ``attr``: the public property that asks;
+        AttributeError when the family's shape is not called that"""
+        if attr is not None and attr != self._family.shape_attr:
+            raise AttributeError(f"the {self.kernel_name} kernel has no {attr}")
+        raw = self.raw.detach().reshape(self._targets.shape[0], -1)
+        return _repeated(_softplus(raw[:, 3 + self._nls:]), L.kernel_shape_params(self.kind, self.d))
 
     @property
     def alpha(self) -> torch.Tensor:
         """(C) the shape of the rational-quadratic kernel; AttributeError for the other kernels"""
-        return self._alpha()
-
-    def _period(self) -> torch.Tensor:
-        """(C, d) the periodic kernel's period lengths = softplus(raw), a shared one repeated"""
-        if self.kernel_name != "periodic":
-            raise AttributeError(f"the {self.kernel_name} kernel has no period_length")
-        raw = self.raw.detach().reshape(self._targets.shape[0], -1)
-        p = _softplus(raw[:, raw.shape[1] - self._nshape:])
-        return p.expand(-1, self.d).clone() if p.shape[1] == 1 and self.d > 1 else p
+        return self._shape("alpha")[:, 0]
 
     @property
     def period_length(self) -> torch.Tensor:
         """(C, d) the period lengths of the periodic kernel (a shared one repeated); AttributeError for the other kernels"""
-        return self._period()
+        return self._shape("period_length")
 
     def _library_lengthscale(self) -> torch.Tensor:
-        """(C, d) lengthscales as the library reads them; rational quadratic: (C, d + 1), alpha last; periodic: (C, 2 d), the
-        period lengths behind the lengthscales"""
-        ls = self._natural()[3]
-        if self.kernel_name == "rq":
-            return torch.cat([ls, self._alpha()[:, None]], dim=1)
-        if self.kernel_name == "periodic":
-            return torch.cat([ls, self._period()], dim=1)
-        return ls
+        """(C, d + shape parameters): the lengthscales, then the shape values, as the library reads them"""
+        return torch.cat([self._natural()[3], self._shape()], dim=1)
 
     @property
     def mean_constant(self) -> torch.Tensor:
@@ -183,67 +167,66 @@ class _ExactGPClasses:
         """(C, d) lengthscales (a shared one repeated)."""
         return self._natural()[3]
 
-    def _make_kernel(self, lengthscale: torch.Tensor, outputscale: float, shape=None) -> BaseKernel:
-        """``shape``: alpha (rational quadratic) or the d period lengths (periodic)"""
-        if self.kernel_name == "matern":
-            return MaternKernel(lengthscale, outputscale, nu=self.nu)
-        if self.kernel_name == "rq":
-            return RQKernel(lengthscale, outputscale, alpha=shape)
-        if self.kernel_name == "periodic":
-            return PeriodicKernel(lengthscale, outputscale, period_length=shape)
-        return ARDKernel(lengthscale, outputscale)
+    def _make_kernel(self, lengthscale: torch.Tensor, outputscale: float, shape: torch.Tensor) -> BaseKernel:
+        """``shape``: the family's shape values (a row of ``_shape()``; empty for a family without)"""
+        keywords = {} if self.nu is None else {"nu": self.nu}
+        if self._family.shape_attr is not None:
+            keywords[self._family.shape_attr] = shape
+        return self._family(lengthscale, outputscale, **keywords)
 
     def _class_kernel(self, c: int) -> BaseKernel:
         """the kernel of class c at the current parameters"""
         _, _, s, ls = self._natural()
-        shape = float(self._alpha()[c]) if self.kernel_name == "rq" else self._period()[c] if self.kernel_name == "periodic" else None
-        return self._make_kernel(ls[c], float(s[c]), shape)
+        return self._make_kernel(ls[c], float(s[c]), self._shape()[c])
 
     # ---- the loss ---------------------------------------------------------------------------------------------------
     def chain_rule(self, out: torch.Tensor) -> Tuple[float, torch.Tensor]:
-        """(-sum_c mll_c / n, its gradient with respect to ``raw``, in the shape of ``raw``) from the (C, 4 + d) outputs of
-        pls_gp_mll_grad_classes (per class: value, d/d mean, d/d noise, d/d log outputscale, d/d log lengthscale_k; rational
-        quadratic: (C, 5 + d), d/d log alpha last; periodic: (C, 4 + 2 d), the d/d log period_length_k behind the lengthscale
-        derivatives) at the current parameters: host arithmetic only.  ``ard=False``: the per-dimension derivatives of the
-        shared lengthscale, and of the shared period length, are summed."""
+        """(-sum_c mll_c / n, its gradient with respect to ``raw``, in the shape of ``raw``) from the (C, 4 + d + shape
+        parameters) outputs of pls_gp_mll_grad_classes (per class: value, d/d mean, d/d noise, d/d log outputscale,
+        d/d log lengthscale_k, then d/d log of every shape value) at the current parameters: host arithmetic only.  The
+        derivatives of a raw value that the library reads repeated, once per dimension (``ard=False``: the shared
+        lengthscale, the shared period length), are summed."""
         raw = self.raw.detach().reshape(self._targets.shape[0], -1)
         out = torch.as_tensor(out, dtype=torch.float64)
-        width, nls = 4 + self.d + self._nshape_lib, raw.shape[1] - 3 - self._nshape
-        assert out.numel() == raw.shape[0] * width
-        out = out.reshape(raw.shape[0], width)
+        assert out.numel() == raw.shape[0] * self._outputs
+        out = out.reshape(raw.shape[0], self._outputs)
         slope = torch.sigmoid(raw)  # d softplus(raw) / d raw
         g = torch.empty_like(raw)
         g[:, 0] = out[:, 1]
         g[:, 1] = out[:, 2] * slope[:, 1]
         g[:, 2] = out[:, 3] / _softplus(raw[:, 2]) * slope[:, 2]
-        per_dim = out[:, 4:4 + self.d] / self._natural()[3]
-        g[:, 3:3 + nls] = (per_dim if self.ard else per_dim.sum(dim=1, keepdim=True)) * slope[:, 3:3 + nls]
-        if self.kernel_name == "rq":
-            g[:, -1] = out[:, -1] / self._alpha() * slope[:, -1]
-        if self.kernel_name == "periodic":
-            per_dim = out[:, 4 + self.d:] / self._period()
-            g[:, 3 + nls:] = (per_dim if self.ard else per_dim.sum(dim=1, keepdim=True)) * slope[:, 3 + nls:]
+        split = 3 + self._nls
+        for columns, d_log, natural in ((slice(3, split), out[:, 4:4 + self.d], self._natural()[3]),
+                                        (slice(split, None), out[:, 4 + self.d:], self._shape())):
+            d_natural = d_log / natural
+            shared = d_natural.shape[1] != g[:, columns].shape[1]
+            g[:, columns] = (d_natural.sum(dim=1, keepdim=True) if shared else d_natural) * slope[:, columns]
         return -float(out[:, 0].sum()) / self.n, (-g / self.n).reshape(self.raw.shape)
+
+    @property
+    def _outputs(self) -> int:
+        """outputs of one class of pls_gp_mll_grad_classes"""
+        return 4 + self.d + L.kernel_shape_params(self.kind, self.d)
 
     def _device_state(self) -> dict:
         if not self._dev:
             x = _dev(self.x)
-            c, width = self._targets.shape[0], 4 + self.d + self._nshape_lib
+            c, width = self._targets.shape[0], self._outputs
             nbytes = int(L.load().pls_gp_mll_classes_workspace_bytes_kind(self.kind, self.n, self.d, c))
             self._dev = {
                 "x": x, "y": _dev(self._targets.contiguous()),
                 "fixed": _dev(self.fixed_noise.contiguous()) if self.fixed_noise is not None else None,
                 "ws": torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=x.device),
-                # the C (4 + d) outputs (rational quadratic: 5 + d; periodic: 4 + 2 d) and behind them the C int32 info words: one read-back per evaluation
+                # the C rows of outputs and behind them the C int32 info words: one read-back per evaluation
                 "out": torch.zeros(c * width + (c + 1) // 2, dtype=torch.float64, device=x.device),
             }
         return self._dev
 
     def _evaluate(self, jitter: float) -> Tuple[torch.Tensor, torch.Tensor]:
-        """One pls_gp_mll_grad_classes call at the current parameters: (the (C, 4 + d) outputs on the CPU -- rational
-        quadratic: (C, 5 + d), periodic: (C, 4 + 2 d) --, info (C))."""
+        """One pls_gp_mll_grad_classes call at the current parameters: (the (C, 4 + d + shape parameters) outputs on the
+        CPU, info (C))."""
         st = self._device_state()
-        c, width = self._targets.shape[0], 4 + self.d + self._nshape_lib
+        c, width = self._targets.shape[0], self._outputs
         mean, noise, s, _ = self._natural()
         ls = st["x"].new_tensor(self._library_lengthscale().tolist()).contiguous()
         host = (ctypes.c_double * c)
@@ -303,12 +286,11 @@ class ExactGP(_ExactGPClasses):
         raw[0]   the mean constant
         raw[1]   raw noise
         raw[2]   raw outputscale
-        raw[3:]  raw lengthscales: d of them (``ard=True``) or one shared by all dimensions (``ard=False``)
-        raw[-1]  raw alpha, for the rational-quadratic kernel only (behind the lengthscales)
-        raw[3 + nls:]  the nls raw period lengths, for the periodic kernel only (behind the nls raw lengthscales)
+        raw[3:3 + nls]  raw lengthscales: nls = d of them (``ard=True``) or one shared by all dimensions (``ard=False``)
+        raw[3 + nls:]   the family's raw shape values: raw alpha (rational quadratic), the nls raw period lengths (periodic)
 
     ``kernel``: "rbf", "rq" or "matern" (with ``nu``); "matern12" / "matern32" / "matern52" name nu as well; one of the classes
-    ARDKernel / MaternKernel / RQKernel / PeriodicKernel names its family likewise (the periodic family has no name here:
+    kernel.STATIONARY_KERNELS names its family likewise (the periodic family has no name here:
     ``kernel=PeriodicKernel``; ``train_exact_gp`` and ``exact_gp_runner`` take "periodic"); an instance of them gives the kind and the starting values (as the reference's ``deepcopy(kernel)``).
     x (n, d) and y (n) are kept as given."""
 
@@ -343,12 +325,12 @@ class ExactGP(_ExactGPClasses):
     @property
     def alpha(self) -> float:
         """the shape of the rational-quadratic kernel; AttributeError for the other kernels"""
-        return float(self._alpha()[0])
+        return float(self._shape("alpha")[0, 0])
 
     @property
     def period_length(self) -> torch.Tensor:
         """the d period lengths of the periodic kernel (a shared one repeated); AttributeError for the other kernels"""
-        return self._period()[0]
+        return self._shape("period_length")[0]
 
     @property
     def kernel(self) -> BaseKernel:
@@ -356,8 +338,8 @@ class ExactGP(_ExactGPClasses):
         return self._class_kernel(0)
 
     def evaluate_on_device(self, jitter: float = 0.0) -> Tuple[torch.Tensor, int]:
-        """One pls_gp_mll_grad_classes call (one class) at the current parameters: (the 4 + d outputs on the CPU -- rational
-        quadratic: 5 + d, periodic: 4 + 2 d --, info)."""
+        """One pls_gp_mll_grad_classes call (one class) at the current parameters: (the 4 + d + shape parameters outputs on
+        the CPU, info)."""
         out, info = self._evaluate(jitter)
         return out[0], int(info[0])
 
@@ -817,9 +799,8 @@ class DirichletExactGP(_ExactGPClasses):
     (``learn_additional_noise=True``); regression targets are the transformed labels.  Replaces the batch-of-classes
     gpytorch model of experiments/curves/classification/main.py:162-192 and experiments/uci/classification/main.py:133-163.
 
-    ``raw`` is ONE (C, 3 + nls) float64 CPU parameter, row c in ExactGP's column order (mean, raw noise, raw outputscale,
-    raw lengthscales; (C, 4 + nls) with raw alpha last for the rational-quadratic kernel, (C, 3 + 2 nls) with the raw period
-    lengths last for the periodic kernel); every raw value starts at 0.  ``transformed_targets`` and ``fixed_noise`` are (C, n);
+    ``raw`` is ONE (C, 3 + nls + shape columns) float64 CPU parameter, row c in ExactGP's column order (mean, raw noise, raw
+    outputscale, raw lengthscales, the family's raw shape values); every raw value starts at 0.  ``transformed_targets`` and ``fixed_noise`` are (C, n);
     ``fixed_noise=False`` leaves the fixed part out (``self.fixed_noise`` is then None): what the reference trains on
     when its subsample is smaller than its data.
     One evaluation of all classes is ONE library call with one read-back, ``pls_gp_mll_grad_classes``."""
@@ -845,8 +826,8 @@ class DirichletExactGP(_ExactGPClasses):
         return construct_average_ard_kernel([self])
 
     def evaluate_on_device(self, jitter: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor]:
-        """One pls_gp_mll_grad_classes call at the current parameters: (the (C, 4 + d) outputs on the CPU -- rational
-        quadratic: (C, 5 + d), periodic: (C, 4 + 2 d) --, info (C))."""
+        """One pls_gp_mll_grad_classes call at the current parameters: (the (C, 4 + d + shape parameters) outputs on the
+        CPU, info (C))."""
         return self._evaluate(jitter)
 
     def predict(self, x_test: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -913,21 +894,16 @@ def train_exact_gp(x: torch.Tensor, y: torch.Tensor, kernel, seed: int, number_o
 def construct_average_ard_kernel(models: Sequence[ExactGP]) -> BaseKernel:
     """The kernel of the AVERAGED RAW parameters, softplus applied afterwards (constructors.py:28-53 averages the
     entries of ``state_dict()``, which are the raw values).  A DirichletExactGP holds one row of raw values per class: its
-    rows are averaged first (the reference's ``mean(dim=0)`` over the batch), then the models.  The rational-quadratic
-    kernel's raw alpha is averaged like the other raw values and the result is an RQKernel; the periodic kernel's raw period
-    lengths are averaged like its raw lengthscales and the result is a PeriodicKernel."""
+    rows are averaged first (the reference's ``mean(dim=0)`` over the batch), then the models.  The family's raw shape
+    values (raw alpha, the raw period lengths) are averaged like the raw lengthscales and the result is a kernel of the
+    models' family."""
     first = models[0]
     per_model = [m.raw_parameters() for m in models]
     raw = torch.stack([(r.mean(dim=0) if r.dim() == 2 else r)[2:] for r in per_model]).mean(dim=0)
-    outputscale, ls = float(_softplus(raw[0])), _softplus(raw[1:raw.numel() - first._nshape])
-    ls = ls.expand(first.d).clone() if ls.numel() == 1 and first.d > 1 else ls
-    shape = None
-    if first.kernel_name == "rq":
-        shape = float(_softplus(raw[-1]))
-    if first.kernel_name == "periodic":
-        shape = _softplus(raw[raw.numel() - first._nshape:])
-        shape = shape.expand(first.d).clone() if shape.numel() == 1 and first.d > 1 else shape
-    return first._make_kernel(ls, outputscale, shape)
+    split = 1 + first._nls
+    ls = _repeated(_softplus(raw[1:split]), first.d)
+    shape = _repeated(_softplus(raw[split:]), L.kernel_shape_params(first.kind, first.d))
+    return first._make_kernel(ls, float(_softplus(raw[0])), shape)
 
 
 def construct_average_gaussian_noise(models: Sequence[ExactGP]) -> float:

@@ -10,7 +10,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .kernel import PLSKernel, _dev, as_base_kernel
+from .kernel import STATIONARY_KERNEL_NAMES, PLSKernel, _dev, as_base_kernel
 
 
 class InducingPointSelector(ABC):
@@ -41,11 +41,11 @@ class ConditionalVarianceInducingPointSelector(InducingPointSelector):
         if isinstance(kernel, PLSKernel):
             # the reference would select on r = k(., S) k(S, .)^T / |S| (an N x N Gram of the PLS kernel); its experiments
             # always pass the base ScaleKernel(RBFKernel) (experiments/uci/regression/main.py:203), and so must callers here
-            raise TypeError("ConditionalVarianceInducingPointSelector selects on a base kernel (ARDKernel / MaternKernel / "
-                            "RQKernel / PeriodicKernel / LinearKernel / a gpytorch ScaleKernel(RBFKernel | MaternKernel | RQKernel | "
-                            "PeriodicKernel)); pass "
+            gpytorch_names = STATIONARY_KERNEL_NAMES.replace("ARDKernel", "RBFKernel").replace(" / ", " | ")
+            raise TypeError(f"ConditionalVarianceInducingPointSelector selects on a base kernel ({STATIONARY_KERNEL_NAMES} / "
+                            f"LinearKernel / a gpytorch ScaleKernel({gpytorch_names})); pass "
                             "pls_kernel.base_kernel, not the PLSKernel")
-        # our kernels as is; ScaleKernel(RBFKernel | MaternKernel | RQKernel | PeriodicKernel): lengthscale AND outputscale (and nu, alpha or period_length)
+        # our kernels as is; a gpytorch ScaleKernel of a stationary family: lengthscale AND outputscale (and the family's keyword)
         base = as_base_kernel(kernel)
         n = x.shape[0]
         perm = np.random.permutation(n)  # permute entries so tie-breaking is random (:58-61)

@@ -52,21 +52,40 @@ class BaseKernel:
 
 
 class _StationaryKernel(BaseKernel):
-    """Holds per-dimension (or one shared) lengthscales and the outputscale; the lengthscales are cached per D on the
-    device."""
+    """Holds per-dimension (or one shared) lengthscales and the outputscale; what the library reads is cached per D on the
+    device.  A subclass declares its family: ``family`` is its name as the exact-GP classes and trainers take it,
+    ``shape_attr`` the attribute that holds the shape values the library reads behind the d lengthscales
+    (_lib.kernel_shape_params of them; None: the family has none), ``shape_per_dim`` whether that attribute holds one value
+    per dimension (or one shared by all), as the lengthscale does; ``keyword`` the constructor's argument beyond the
+    lengthscale and the outputscale, which a gpytorch kernel of the family carries as an attribute of the same name."""
+
+    family: str
+    keyword: str | None = None
+    shape_attr: str | None = None
+    shape_per_dim: bool = False
 
     def __init__(self, lengthscale, outputscale: float = 1.0):
         self.lengthscale = torch.as_tensor(lengthscale, dtype=torch.float64).reshape(-1).cpu()
         self.outputscale = float(outputscale)
         self._ls_dev: dict[int, torch.Tensor] = {}
 
+    def _lengthscale_host(self, d: int) -> torch.Tensor:
+        """the d + kernel_shape_params(kind, d) values the library reads: the lengthscales, then the shape values (a value
+        shared by all dimensions repeated)"""
+        parts = []
+        for name, per_dim in (("lengthscale", True), (self.shape_attr, self.shape_per_dim)):
+            if name is None:
+                continue
+            v = torch.as_tensor(getattr(self, name), dtype=torch.float64).reshape(-1)
+            if per_dim:
+                v = v.expand(d) if v.numel() == 1 else v
+                assert v.numel() == d, f"{name} has {v.numel()} entries, data has {d} dims"
+            parts.append(v)
+        return torch.cat(parts)
+
     def _lengthscale_dev(self, d: int) -> torch.Tensor:
         if d not in self._ls_dev:
-            ls = self.lengthscale
-            if ls.numel() == 1:
-                ls = ls.expand(d)
-            assert ls.numel() == d, f"lengthscale has {ls.numel()} entries, data has {d} dims"
-            self._ls_dev[d] = _dev(ls)
+            self._ls_dev[d] = _dev(self._lengthscale_host(d))
         return self._ls_dev[d]
 
 
@@ -74,7 +93,7 @@ class ARDKernel(_StationaryKernel):
     """ScaleKernel(RBFKernel(ard_num_dims=D)): k(a,b) = outputscale * exp(-0.5 sum_d ((a_d-b_d)/lengthscale_d)^2)
     (constructed in the reference at experiments/uci/regression/main.py:171-173, README.md:144-146)."""
 
-    kind = L.KERNEL_RBF_ARD
+    kind, family = L.KERNEL_RBF_ARD, "rbf"
 
 
 class MaternKernel(_StationaryKernel):
@@ -84,6 +103,7 @@ class MaternKernel(_StationaryKernel):
            = outputscale * (1 + sqrt5 r + 5 r^2 / 3) exp(-sqrt5 r) (nu = 5/2),
     gpytorch's MaternKernel; nu is one of the three it offers.  Lengthscale handling as ARDKernel."""
 
+    family, keyword = "matern", "nu"
     KINDS = {0.5: L.KERNEL_MATERN12, 1.5: L.KERNEL_MATERN32, 2.5: L.KERNEL_MATERN52}
 
     def __init__(self, lengthscale, outputscale: float = 1.0, nu: float = 2.5):
@@ -102,7 +122,8 @@ class RQKernel(_StationaryKernel):
     heavy tails for a small alpha, the RBF kernel as alpha -> inf.  ``lengthscale`` holds d (or one shared) values as in
     ARDKernel; the library reads alpha behind the lengthscales, so the device array has d + 1 entries."""
 
-    kind = L.KERNEL_RQ
+    kind, family = L.KERNEL_RQ, "rq"
+    keyword = shape_attr = "alpha"
 
     def __init__(self, lengthscale, outputscale: float = 1.0, alpha: float = 1.0):
         alpha = float(torch.as_tensor(alpha, dtype=torch.float64).detach().reshape(-1)[0])  # (gpytorch's: a one-element tensor)
@@ -110,19 +131,6 @@ class RQKernel(_StationaryKernel):
             raise ValueError(f"RQKernel: alpha must be positive, got {alpha}")
         super().__init__(lengthscale, outputscale)
         self.alpha = alpha
-
-    def _lengthscale_host(self, d: int) -> torch.Tensor:
-        """the d + 1 values the library reads: the lengthscales (a shared one repeated), then alpha"""
-        ls = self.lengthscale
-        if ls.numel() == 1:
-            ls = ls.expand(d)
-        assert ls.numel() == d, f"lengthscale has {ls.numel()} entries, data has {d} dims"
-        return torch.cat([ls, torch.tensor([self.alpha], dtype=torch.float64)])
-
-    def _lengthscale_dev(self, d: int) -> torch.Tensor:
-        if d not in self._ls_dev:
-            self._ls_dev[d] = _dev(self._lengthscale_host(d))
-        return self._ls_dev[d]
 
 
 class PeriodicKernel(_StationaryKernel):
@@ -133,7 +141,9 @@ class PeriodicKernel(_StationaryKernel):
     shared) positive values; the library reads the period lengths behind the lengthscales, so the device array has 2 d
     entries.  d <= 16."""
 
-    kind = L.KERNEL_PERIODIC
+    kind, family = L.KERNEL_PERIODIC, "periodic"
+    keyword = shape_attr = "period_length"
+    shape_per_dim = True
 
     def __init__(self, lengthscale, outputscale: float = 1.0, period_length=1.0):
         period = torch.as_tensor(period_length, dtype=torch.float64).detach().reshape(-1).cpu()
@@ -144,25 +154,17 @@ class PeriodicKernel(_StationaryKernel):
             raise ValueError(f"PeriodicKernel: every lengthscale must be positive, got {self.lengthscale.tolist()}")
         self.period_length = period
 
-    def _lengthscale_host(self, d: int) -> torch.Tensor:
-        """the 2 d values the library reads: the lengthscales, then the period lengths (a shared one repeated)"""
-        parts = []
-        for name, v in (("lengthscale", self.lengthscale), ("period_length", self.period_length)):
-            v = v.expand(d) if v.numel() == 1 else v
-            assert v.numel() == d, f"{name} has {v.numel()} entries, data has {d} dims"
-            parts.append(v)
-        return torch.cat(parts)
-
-    def _lengthscale_dev(self, d: int) -> torch.Tensor:
-        if d not in self._ls_dev:
-            self._ls_dev[d] = _dev(self._lengthscale_host(d))
-        return self._ls_dev[d]
-
 
 class LinearKernel(BaseKernel):
     """k(x1, x2) = x1 x2^T: the reference's test double (mockers/kernel.py:8-23)."""
 
     kind = L.KERNEL_LINEAR
+
+
+#: the stationary families, in the order ``as_base_kernel`` asks a gpytorch kernel for their keywords: nu, alpha, period_length
+STATIONARY_KERNELS = (ARDKernel, MaternKernel, RQKernel, PeriodicKernel)
+#: "ARDKernel / MaternKernel / RQKernel / PeriodicKernel", as the error messages of the package list them
+STATIONARY_KERNEL_NAMES = " / ".join(cls.__name__ for cls in STATIONARY_KERNELS)
 
 
 def as_base_kernel(kernel) -> BaseKernel:
@@ -175,15 +177,11 @@ def as_base_kernel(kernel) -> BaseKernel:
     if inner is not None and hasattr(inner, "lengthscale") and hasattr(kernel, "outputscale"):
         lengthscale = torch.as_tensor(inner.lengthscale).detach().reshape(-1)
         outputscale = float(torch.as_tensor(kernel.outputscale).detach())
-        if hasattr(inner, "nu"):
-            return MaternKernel(lengthscale=lengthscale, outputscale=outputscale, nu=inner.nu)
-        if hasattr(inner, "alpha"):
-            return RQKernel(lengthscale=lengthscale, outputscale=outputscale, alpha=inner.alpha)
-        if hasattr(inner, "period_length"):
-            return PeriodicKernel(lengthscale=lengthscale, outputscale=outputscale,
-                                  period_length=torch.as_tensor(inner.period_length).detach().reshape(-1))
+        for cls in STATIONARY_KERNELS:
+            if cls.keyword is not None and hasattr(inner, cls.keyword):
+                return cls(lengthscale=lengthscale, outputscale=outputscale, **{cls.keyword: getattr(inner, cls.keyword)})
         return ARDKernel(lengthscale=lengthscale, outputscale=outputscale)
-    raise TypeError(f"unsupported base kernel {type(kernel).__name__}: use ARDKernel / MaternKernel / RQKernel / PeriodicKernel / LinearKernel")
+    raise TypeError(f"unsupported base kernel {type(kernel).__name__}: use {STATIONARY_KERNEL_NAMES} / LinearKernel")
 
 
 class PLSKernel:

@@ -80,15 +80,15 @@ def grad_sums(kind, x, ls, s, alpha, p):
     return fsum_rows(pair_terms(kind, x, ls, s, alpha, p))
 
 
-def mll_and_grad(kind, x, y, ls, s, noise, mean, fixed=None):
-    """The 4 + d outputs of pls_gp_mll_grad (of a row of pls_gp_mll_grad_classes when ``fixed`` (n) joins the noise on the
-    diagonal) through LAPACK (Cholesky, cholesky_solve, cholesky_inverse) and, per output, its sum-of-magnitudes scale:
-    1/2 |r^T alpha| + sum |log L_ii| for the value, sum |alpha_i| for d/d mean, and S_theta = 1/2 sum_ij |W_ij dK_ij / d theta|
-    for the rest."""
-    x = x if x.dim() == 2 else x[:, None]
-    n = x.shape[0]
+def lapack_mll_and_grad(kap, family_grad_sums, y, s, noise, mean, fixed=None):
+    """The one LAPACK evaluation (Cholesky, cholesky_solve, cholesky_inverse) behind every family's ``mll_and_grad``: the
+    outputs of pls_gp_mll_grad (of a row of pls_gp_mll_grad_classes when ``fixed`` (n) joins the noise on the diagonal) and,
+    per output, its sum-of-magnitudes scale: 1/2 |r^T alpha| + sum |log L_ii| for the value, sum |alpha_i| for d/d mean, and
+    S_theta = 1/2 sum_ij |W_ij dK_ij / d theta| for the rest.  The family supplies ``kap`` = kappa(x, x) (n, n) and
+    ``family_grad_sums(alpha, p)`` -> (its pair sums, their scales): one output per sum, behind value, d/d mean, d/d noise."""
+    n = kap.shape[0]
     diag = torch.full((n,), float(noise), dtype=torch.float64) if fixed is None else fixed.double() + float(noise)
-    ky = s * kappa(kind, x, ls) + torch.diag(diag)
+    ky = s * kap + torch.diag(diag)
     low = torch.linalg.cholesky(ky)
     r = y.double() - mean
     alpha = torch.cholesky_solve(r[:, None], low)[:, 0]
@@ -96,9 +96,9 @@ def mll_and_grad(kind, x, y, ls, s, noise, mean, fixed=None):
     p = 0.5 * (p + p.T)
     logs = torch.log(low.diagonal())
     quad = math.fsum((r * alpha).tolist())
-    sums, scale = grad_sums(kind, x, ls, s, alpha, p)
+    sums, scale = family_grad_sums(alpha, p)
     wdiag = alpha * alpha - p.diagonal()
-    out = np.empty(4 + x.shape[1])
+    out = np.empty(3 + sums.size)
     mag = np.empty_like(out)
     out[0] = -0.5 * quad - math.fsum(logs.tolist()) - 0.5 * n * math.log(2.0 * math.pi)
     mag[0] = 0.5 * abs(quad) + math.fsum(logs.abs().tolist())
@@ -107,6 +107,12 @@ def mll_and_grad(kind, x, y, ls, s, noise, mean, fixed=None):
     out[3], mag[3] = 0.5 * s * sums[0], 0.5 * s * scale[0]
     out[4:], mag[4:] = 0.5 * sums[1:], 0.5 * scale[1:]
     return out, mag
+
+
+def mll_and_grad(kind, x, y, ls, s, noise, mean, fixed=None):
+    """The 4 + d outputs of pls_gp_mll_grad for RBF and Matern through LAPACK and their scales (``lapack_mll_and_grad``)"""
+    x = x if x.dim() == 2 else x[:, None]
+    return lapack_mll_and_grad(kappa(kind, x, ls), lambda alpha, p: grad_sums(kind, x, ls, s, alpha, p), y, s, noise, mean, fixed)
 
 
 def host_evaluate(model):

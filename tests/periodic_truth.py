@@ -7,13 +7,12 @@ With e_k = (x_ik - x_jk) / p_k and kappa = exp(-2 sum_k sin^2(pi e_k) / lambda_k
     dK / d log lambda_k = s kappa (2 / lambda_k) sin^2(pi e_k)
     dK / d log p_k      = s kappa (2 / lambda_k) pi e_k sin(2 pi e_k)
 A pair at distance 0 has both derivatives 0; a pair whose kappa is 0 contributes 0 everywhere."""
-import math
 import os
 
 import numpy as np
 import torch
 
-from exact_gp_truth import EPS, MEAN, NOISE, OUTPUTSCALE, fsum_rows  # noqa: F401
+from exact_gp_truth import EPS, MEAN, NOISE, OUTPUTSCALE, fsum_rows, lapack_mll_and_grad  # noqa: F401
 from periodic_closed_form import periodic_factors_numpy, sensitivity
 from truth_common import _normal, _uniform, checksum, fixture_truth, relative_error  # noqa: F401
 
@@ -67,29 +66,9 @@ def grad_sums_majorant(x, ls, period, s, alpha, p):
 
 def mll_and_grad(x, y, ls, period, s, noise, mean, fixed=None):
     """The 4 + 2 d outputs of pls_gp_mll_grad for PLS_KERNEL_PERIODIC through LAPACK and, per output, its sum-of-magnitudes
-    scale (exact_gp_truth.mll_and_grad with the period derivatives behind the lengthscale derivatives)"""
+    scale (exact_gp_truth.lapack_mll_and_grad with the period derivatives behind the lengthscale derivatives)"""
     x = x if x.dim() == 2 else x[:, None]
-    n, d = x.shape
-    diag = torch.full((n,), float(noise), dtype=torch.float64) if fixed is None else fixed.double() + float(noise)
-    ky = s * kappa(x, ls, period) + torch.diag(diag)
-    low = torch.linalg.cholesky(ky)
-    r = y.double() - mean
-    alpha = torch.cholesky_solve(r[:, None], low)[:, 0]
-    p = torch.cholesky_inverse(low)
-    p = 0.5 * (p + p.T)
-    logs = torch.log(low.diagonal())
-    quad = math.fsum((r * alpha).tolist())
-    sums, scale = grad_sums(x, ls, period, s, alpha, p)
-    wdiag = alpha * alpha - p.diagonal()
-    out = np.empty(4 + 2 * d)
-    mag = np.empty_like(out)
-    out[0] = -0.5 * quad - math.fsum(logs.tolist()) - 0.5 * n * math.log(2.0 * math.pi)
-    mag[0] = 0.5 * abs(quad) + math.fsum(logs.abs().tolist())
-    out[1], mag[1] = math.fsum(alpha.tolist()), math.fsum(alpha.abs().tolist())
-    out[2], mag[2] = 0.5 * math.fsum(wdiag.tolist()), 0.5 * math.fsum(wdiag.abs().tolist())
-    out[3], mag[3] = 0.5 * s * sums[0], 0.5 * s * scale[0]
-    out[4:], mag[4:] = 0.5 * sums[1:], 0.5 * scale[1:]
-    return out, mag
+    return lapack_mll_and_grad(kappa(x, ls, period), lambda alpha, p: grad_sums(x, ls, period, s, alpha, p), y, s, noise, mean, fixed)
 
 
 def host_evaluate(model):

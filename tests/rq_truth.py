@@ -9,13 +9,12 @@ outputscale s:
     dK / d log alpha = s alpha kappa (u / (1 + u) - log1p(u))
 A pair with r = 0 has both derivatives 0; a pair whose kappa is 0 contributes 0 everywhere.  ``shape`` is the kernel's
 alpha throughout; ``alpha`` stays the solve's vector K_y^-1 (y - mean), as in exact_gp_truth.py."""
-import math
 import os
 
 import numpy as np
 import torch
 
-from exact_gp_truth import EPS, MEAN, NOISE, OUTPUTSCALE, _scaled_differences, fsum_rows  # noqa: F401
+from exact_gp_truth import EPS, MEAN, NOISE, OUTPUTSCALE, _scaled_differences, fsum_rows, lapack_mll_and_grad  # noqa: F401
 from rq_closed_form import ALPHAS, LN2, rq_factors_numpy
 from truth_common import _normal, _uniform, checksum, fixture_truth, relative_error  # noqa: F401
 
@@ -54,29 +53,9 @@ def grad_sums(x, ls, shape, s, alpha, p):
 
 def mll_and_grad(x, y, ls, shape, s, noise, mean, fixed=None):
     """The 5 + d outputs of pls_gp_mll_grad for PLS_KERNEL_RQ through LAPACK and, per output, its sum-of-magnitudes scale
-    (exact_gp_truth.mll_and_grad with the alpha derivative behind the lengthscale derivatives)"""
+    (exact_gp_truth.lapack_mll_and_grad with the alpha derivative behind the lengthscale derivatives)"""
     x = x if x.dim() == 2 else x[:, None]
-    n, d = x.shape
-    diag = torch.full((n,), float(noise), dtype=torch.float64) if fixed is None else fixed.double() + float(noise)
-    ky = s * kappa(x, ls, shape) + torch.diag(diag)
-    low = torch.linalg.cholesky(ky)
-    r = y.double() - mean
-    alpha = torch.cholesky_solve(r[:, None], low)[:, 0]
-    p = torch.cholesky_inverse(low)
-    p = 0.5 * (p + p.T)
-    logs = torch.log(low.diagonal())
-    quad = math.fsum((r * alpha).tolist())
-    sums, scale = grad_sums(x, ls, shape, s, alpha, p)
-    wdiag = alpha * alpha - p.diagonal()
-    out = np.empty(5 + d)
-    mag = np.empty_like(out)
-    out[0] = -0.5 * quad - math.fsum(logs.tolist()) - 0.5 * n * math.log(2.0 * math.pi)
-    mag[0] = 0.5 * abs(quad) + math.fsum(logs.abs().tolist())
-    out[1], mag[1] = math.fsum(alpha.tolist()), math.fsum(alpha.abs().tolist())
-    out[2], mag[2] = 0.5 * math.fsum(wdiag.tolist()), 0.5 * math.fsum(wdiag.abs().tolist())
-    out[3], mag[3] = 0.5 * s * sums[0], 0.5 * s * scale[0]
-    out[4:], mag[4:] = 0.5 * sums[1:], 0.5 * scale[1:]
-    return out, mag
+    return lapack_mll_and_grad(kappa(x, ls, shape), lambda alpha, p: grad_sums(x, ls, shape, s, alpha, p), y, s, noise, mean, fixed)
 
 
 def host_evaluate(model):

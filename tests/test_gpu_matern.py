@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import torch
 
+from base_kernel_calls import gram_into as _gram_into
 from matern_closed_form import NUS, matern_numpy, matern_torch
 from oracle import pls_oracle as O
 from test_gpu_parity import P, TOL, _f64_default, cu, make_costs, make_problem, relerr, step_tolerance  # noqa: F401
@@ -12,15 +13,6 @@ from test_gpu_parity import P, TOL, _f64_default, cu, make_costs, make_problem, 
 pytestmark = pytest.mark.gpu
 
 GRAM_DIMS = [1, 2, 3, 5, 8, 13, 33, 64]  # every D_MAX of the Gram kernel: 1, 2, 4, 8, 16, 32, 64, padded and exact
-
-
-def _gram_into(P, kernel, x1, x2, out_view, ldout):
-    """pls_kernel_gram through the C ABI into a strided (possibly unaligned) view."""
-    L = P.pkg._lib
-    a, b = cu(x1).contiguous(), cu(x2).contiguous()
-    ls = kernel._lengthscale_dev(a.shape[1])
-    L.check(L.load().pls_kernel_gram(kernel.kind, a.data_ptr(), a.shape[0], b.data_ptr(), b.shape[0], a.shape[1], ls.data_ptr(),
-                                     float(kernel.outputscale), out_view.data_ptr(), ldout, L.stream_ptr()), "pls_kernel_gram")
 
 
 @pytest.mark.parametrize("nu", NUS)

@@ -11,8 +11,10 @@ import numpy as np
 import pytest
 import torch
 
+import base_kernel_calls as C
 import rq_truth as T
 import svgp_truth as ST
+from base_kernel_calls import gram_into as _gram_into, lib_params as lib_ls, offset_copy, p_views
 from oracle import pls_oracle as O
 from rq_closed_form import ALPHAS, LN2, rq_numpy, rq_torch
 from test_gpu_parity import P, TOL, _f64_default, cu, make_costs, make_problem, relerr, step_tolerance  # noqa: F401
@@ -23,18 +25,7 @@ F64 = torch.float64
 DIMS = [1, 2, 3, 5, 8, 13, 33, 64]  # every D_MAX of the pairwise kernels: 1, 2, 4, 8, 16, 32, 64, padded and exact
 ALPHA_IDS = [f"alpha={a:g}" for a in ALPHAS]
 RQ = T.RQ
-worst = {}
-
-
-def note(test, tag, ratio):
-    """print a case's err / bar and the largest of its test so far"""
-    worst[test] = max(worst.get(test, 0.0), float(ratio))
-    print(f"{test} {tag}: err/bar {float(ratio):.2e} (largest so far {worst[test]:.2e})")
-
-
-def lib_ls(ls, shape):
-    """the d + 1 doubles the library reads for PLS_KERNEL_RQ on the device: the lengthscales, then alpha"""
-    return torch.cat([ls.double().reshape(-1), torch.tensor([shape], dtype=F64)]).cuda().contiguous()
+note = C.make_note()
 
 
 def draw(g, n, d):
@@ -43,15 +34,6 @@ def draw(g, n, d):
 
 
 # ---- 1. the Gram build ---------------------------------------------------------------------------------------------------
-def _gram_into(P, kernel, x1, x2, out_view, ldout):
-    L = P.pkg._lib
-    a, b = cu(x1).contiguous(), cu(x2).contiguous()
-    ls = kernel._lengthscale_dev(a.shape[1])
-    assert ls.numel() == a.shape[1] + 1
-    L.check(L.load().pls_kernel_gram(kernel.kind, a.data_ptr(), a.shape[0], b.data_ptr(), b.shape[0], a.shape[1], ls.data_ptr(),
-                                     float(kernel.outputscale), out_view.data_ptr(), ldout, L.stream_ptr()), "pls_kernel_gram")
-
-
 @pytest.mark.parametrize("alpha", ALPHAS, ids=ALPHA_IDS)
 @pytest.mark.parametrize("d", DIMS)
 def test_gram_against_the_closed_form(P, d, alpha):
@@ -121,19 +103,8 @@ def test_a_far_point_dies_only_for_a_large_alpha(P):
 
 # ---- 2. the reduction ----------------------------------------------------------------------------------------------------
 def grad_sums(P, x, ls, shape, s, alpha, p_view, ldp):
-    """pls_kernel_grad_sums for PLS_KERNEL_RQ through the C ABI; p_view: a device (n, n) view with leading dimension ldp"""
-    L = P.pkg._lib
-    lib = L.load()
-    n, d = x.shape
-    xd, lsd, ad = cu(x).contiguous(), lib_ls(ls, shape), cu(alpha).contiguous()
-    nbytes = lib.pls_kernel_grad_sums_workspace_bytes_kind(RQ, n, d)
-    ws = torch.full((nbytes // 8 + 1,), float("nan"), dtype=F64, device="cuda")
-    out = torch.full((d + 3,), float("nan"), dtype=F64, device="cuda")
-    L.check(lib.pls_kernel_grad_sums(RQ, xd.data_ptr(), n, d, lsd.data_ptr(), float(s), ad.data_ptr(), p_view.data_ptr(), ldp,
-                                     out.data_ptr(), ws.data_ptr(), nbytes, L.stream_ptr()), "pls_kernel_grad_sums")
-    host = out.cpu()
-    assert torch.isnan(host[d + 2]) and torch.isnan(ws[-1]).item(), "the reduction wrote past its d + 2 outputs or its workspace"
-    return host[: d + 2]
+    """pls_kernel_grad_sums for PLS_KERNEL_RQ: the d + 2 sums"""
+    return C.grad_sums(P, RQ, x, lib_ls(ls, shape), s, alpha, p_view, ldp)
 
 
 def reduction_problem(n, d, seed):
@@ -142,20 +113,6 @@ def reduction_problem(n, d, seed):
     alpha = torch.randn(n, generator=g, dtype=F64)
     a = torch.randn(n, n, generator=g, dtype=F64)
     return x, ls, alpha, a + a.T
-
-
-def p_views(p):
-    """(even ldp on a 16-byte boundary), (odd ldp, 8 bytes off): the two load paths"""
-    n = p.shape[0]
-    ldp = (n + 1) // 2 * 2
-    buf = torch.full((n, ldp), float("nan"), dtype=F64, device="cuda")
-    buf[:, :n] = cu(p)
-    ldo = n + 1 + (n % 2)
-    raw = torch.full((1 + n * ldo,), float("nan"), dtype=F64, device="cuda")
-    view = raw[1:].view(n, ldo)
-    view[:, :n] = cu(p)
-    assert buf.data_ptr() % 16 == 0 and view.data_ptr() % 16 == 8 and ldo % 2 == 1
-    return (buf, ldp), (view, ldo)
 
 
 def check_sums(tag, got, want, scale):
@@ -202,22 +159,8 @@ def test_reduction_with_a_duplicated_point(P, alpha):
 
 # ---- 3. the whole evaluation -------------------------------------------------------------------------------------------
 def gp_mll(P, x, y, ls, shape, s, noise, mean, jitter=0.0, fill=None):
-    """pls_gp_mll_grad for PLS_KERNEL_RQ through the C ABI: (the 5 + d outputs on the CPU, info, status)"""
-    L = P.pkg._lib
-    lib = L.load()
-    n, d = x.shape
-    xd, yd, lsd = cu(x).contiguous(), cu(y).contiguous(), lib_ls(ls, shape)
-    nbytes = lib.pls_gp_mll_workspace_bytes_kind(RQ, n, d)
-    ws = torch.empty(nbytes // 8, dtype=F64, device="cuda")
-    if fill is not None:
-        ws.fill_(fill)
-    out = torch.full((5 + d + 1,), float("nan"), dtype=F64, device="cuda")
-    info = torch.full((1,), -7, dtype=torch.int32, device="cuda")
-    rc = lib.pls_gp_mll_grad(RQ, xd.data_ptr(), n, d, lsd.data_ptr(), float(s), float(noise), float(mean), float(jitter),
-                             yd.data_ptr(), out.data_ptr(), info.data_ptr(), ws.data_ptr(), nbytes, L.stream_ptr())
-    host = out.cpu()
-    assert torch.isnan(host[5 + d]), "the evaluation wrote past its 5 + d outputs"
-    return host[: 5 + d], int(info.item()), rc
+    """pls_gp_mll_grad for PLS_KERNEL_RQ: (the 5 + d outputs on the CPU, info, status)"""
+    return C.gp_mll(P, RQ, x, y, lib_ls(ls, shape), s, noise, mean, jitter, fill)
 
 
 @pytest.mark.parametrize("name", list(T.CASES))
@@ -309,14 +252,7 @@ S_MEAN, MEAN = 1.7, 0.3
 
 
 def kernel_mean(P, xd, lsd, ad, xtd, s=S_MEAN, mean=MEAN):
-    L = P.pkg._lib
-    (n, d), t = xd.shape, xtd.shape[0]
-    out = torch.full((t + 1,), float("nan"), dtype=F64, device="cuda")
-    L.check(L.load().pls_kernel_mean(RQ, xd.data_ptr(), n, d, lsd.data_ptr(), float(s), float(mean), ad.data_ptr(), xtd.data_ptr(), t,
-                                     out.data_ptr(), L.stream_ptr()), "pls_kernel_mean")
-    host = out.cpu()
-    assert torch.isnan(host[t]), "pls_kernel_mean wrote past its t outputs"
-    return host[:t]
+    return C.kernel_mean(P, RQ, xd, lsd, ad, xtd, s, mean)
 
 
 def mean_truth(x, ls, shape, s, mean, alpha, xt):
@@ -324,14 +260,6 @@ def mean_truth(x, ls, shape, s, mean, alpha, xt):
     terms = (rq_torch(ls, s, shape)(xt, x) * alpha[None, :]).numpy()
     want = np.array([math.fsum([float(mean)] + row.tolist()) for row in terms])
     return want, np.array([abs(float(mean)) + math.fsum(np.abs(row).tolist()) for row in terms])
-
-
-def offset_copy(m):
-    raw = torch.full((1 + m.numel(),), float("nan"), dtype=F64, device="cuda")
-    view = raw[1:].view(m.shape)
-    view.copy_(m)
-    assert view.data_ptr() % 16 == 8 and view.is_contiguous()
-    return view
 
 
 def mean_problem(n, t, d, seed):

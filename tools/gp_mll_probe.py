@@ -43,6 +43,15 @@ def timed(fn, repeats):
     return statistics.median(ms)
 
 
+def probe_kernel(kind, d, g):
+    """The kernel whose parameters are timed: lengthscales (0.5 + U) sqrt(d), drawn for every kind; RQ: alpha = ln 2; periodic:
+    lengthscales (0.5 + U) d and period lengths 0.5 + 2.5 U, drawn after them."""
+    ls = (0.5 + torch.rand(d, generator=g, dtype=F64)) * d**0.5
+    if kind == L.KERNEL_PERIODIC:
+        return pkg.PeriodicKernel((0.5 + torch.rand(d, generator=g, dtype=F64)) * d, period_length=0.5 + 2.5 * torch.rand(d, generator=g, dtype=F64))
+    return {L.KERNEL_RBF_ARD: pkg.ARDKernel(ls), L.KERNEL_MATERN52: pkg.MaternKernel(ls, nu=2.5), L.KERNEL_RQ: pkg.RQKernel(ls, alpha=RQ_ALPHA)}[kind]
+
+
 def library_stages(kind, x, y, ls, s, noise, mean, repeats):
     lib = L.load()
     n, d = x.shape
@@ -52,7 +61,8 @@ def library_stages(kind, x, y, ls, s, noise, mean, repeats):
     ky, lc, lct, sf, sb, linv, linvt = planes
     r, alpha = (y - mean).contiguous(), torch.empty(n, dtype=F64, device="cuda")
     info = torch.zeros(1, dtype=torch.int32, device="cuda")
-    extra = 1 if kind == L.KERNEL_RQ else d if kind == L.KERNEL_PERIODIC else 0  # (shape values behind the lengthscales)
+    extra = L.kernel_shape_params(kind, d)  # (shape values behind the lengthscales)
+    assert ls.numel() == d + extra
     out = torch.empty(4 + d + extra, dtype=F64, device="cuda")
     nbytes = lib.pls_gp_mll_workspace_bytes_kind(kind, n, d)
     ws = torch.empty(nbytes // 8, dtype=F64, device="cuda")
@@ -97,7 +107,7 @@ def library_stages(kind, x, y, ls, s, noise, mean, repeats):
 
 
 def torch_route(kind, x, y, ls, s, noise, mean, repeats):
-    """-> (ms, the same 4 + d numbers, 5 + d for RQ, 4 + 2 d for periodic): value and gradient by autograd through torch.linalg.cholesky, fp64,
+    """-> (ms, the same 4 + d + shape parameters numbers): value and gradient by autograd through torch.linalg.cholesky, fp64,
     same device"""
     n, d = x.shape
     leaves = [torch.tensor(v, dtype=F64, device="cuda", requires_grad=True) for v in (mean, noise, math.log(s))]
@@ -159,9 +169,7 @@ def main():
                 g = torch.Generator().manual_seed(n + d)
                 x = torch.randn(n, d, generator=g, dtype=F64).cuda()
                 y = (torch.sin(x.sum(dim=1)) + 0.3 * torch.randn(n, generator=g, dtype=F64).cuda()).contiguous()
-                ls = torch.cat([(0.5 + torch.rand(d, generator=g, dtype=F64)) * d**0.5, torch.tensor([RQ_ALPHA], dtype=F64)]).cuda()
-                if kind == L.KERNEL_PERIODIC:  # (lengthscales (0.5 + U) d, then the period lengths 0.5 + 2.5 U)
-                    ls = torch.cat([(0.5 + torch.rand(d, generator=g, dtype=F64)) * d, 0.5 + 2.5 * torch.rand(d, generator=g, dtype=F64)]).cuda()
+                ls = probe_kernel(kind, d, g)._lengthscale_host(d).cuda()
                 res, out = library_stages(kind, x, y, ls, 1.3, 0.1, 0.2, args.repeats)
                 row = (f"{name:9s} {n:5d} {d:2d} {res['whole']:8.3f} {res['gram']:7.3f} {res['factor']:7.3f} {res['solve']:7.3f} "
                        f"{res['inverse']:7.3f} {res['product+small']:13.3f} {res['reduction']:9.3f} "

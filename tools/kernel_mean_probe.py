@@ -42,14 +42,14 @@ def main():
         g = torch.Generator().manual_seed(0)
         x = torch.randn(n, d, generator=g, dtype=torch.float64).cuda()
         xt = torch.randn(t, d, generator=g, dtype=torch.float64).cuda()
-        ls = torch.cat([(0.5 + torch.rand(d, generator=g, dtype=torch.float64)) * d**0.5,
-                        torch.tensor([0.6931471805599453], dtype=torch.float64)]).cuda()  # (+ RQ's alpha, behind the lengthscales)
+        ls = (0.5 + torch.rand(d, generator=g, dtype=torch.float64)) * d**0.5
         alpha = torch.randn(n, generator=g, dtype=torch.float64).cuda()
-        ls_all = ls
-        ls_periodic = torch.cat([(0.5 + torch.rand(d, generator=g, dtype=torch.float64)) * d,
-                                 0.5 + 2.5 * torch.rand(d, generator=g, dtype=torch.float64)]).cuda()  # (lengthscales, period lengths)
-        for kind, kind_name in KINDS.items():
-            ls = ls_periodic if kind == L.KERNEL_PERIODIC else ls_all
+        kernels = [pkg.ARDKernel(ls), pkg.MaternKernel(ls, nu=2.5), pkg.RQKernel(ls, alpha=0.6931471805599453),
+                   pkg.PeriodicKernel((0.5 + torch.rand(d, generator=g, dtype=torch.float64)) * d,
+                                      period_length=0.5 + 2.5 * torch.rand(d, generator=g, dtype=torch.float64))]
+        for kernel in kernels:
+            kind, kind_name = kernel.kind, KINDS[kernel.kind]
+            ls = kernel._lengthscale_host(d).cuda()  # (the lengthscales, then the family's shape values)
             torch.cuda.synchronize()
             torch.cuda.reset_peak_memory_stats()
             floor = torch.cuda.memory_allocated()

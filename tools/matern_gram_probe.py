@@ -11,9 +11,14 @@ Prints one line per pair (median, 10th-90th percentile, min, max, median / first
 import argparse
 import ctypes as C
 import json
+import os
 import statistics
+import sys
 
 import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from projected_langevin_sampling_amd import kernel as K  # noqa: E402  (parameter holders only: no library is loaded through it)
 
 KINDS = {0: "rbf", 2: "matern12", 3: "matern32", 4: "matern52", 6: "rq", 8: "periodic"}
 SHAPES = [("configs[1] k(Z,X)", 1024, 100_000, 8), ("configs[2] k(Z,X)", 512, 50_000, 8)]
@@ -50,13 +55,15 @@ def main():
         g = torch.Generator().manual_seed(0)
         z = (torch.rand(n1, d, generator=g, dtype=torch.float64) * 2 - 1).cuda()
         x = (torch.rand(n2, d, generator=g, dtype=torch.float64) * 2 - 1).cuda()
-        ls = torch.cat([0.5 + torch.rand(d, generator=g, dtype=torch.float64), torch.tensor([0.6931471805599453], dtype=torch.float64)]).cuda()  # (+ RQ's alpha)
-        ls_periodic = torch.cat([ls[:d].cpu(), 0.5 + 2.5 * torch.rand(d, generator=g, dtype=torch.float64)]).cuda()  # (+ the period lengths)
+        ls = 0.5 + torch.rand(d, generator=g, dtype=torch.float64)
+        kernels = [K.ARDKernel(ls)] + [K.MaternKernel(ls, nu=nu) for nu in (0.5, 1.5, 2.5)] + [
+            K.RQKernel(ls, alpha=0.6931471805599453), K.PeriodicKernel(ls, period_length=0.5 + 2.5 * torch.rand(d, generator=g, dtype=torch.float64))]
+        params = {k.kind: k._lengthscale_host(d).cuda() for k in kernels}  # (per kind: the lengthscales, then its shape values)
         out = torch.empty(n1, n2, dtype=torch.float64, device="cuda")
         pairs = [(name, lib, kind) for name, lib, kinds in libs for kind in kinds]
 
         def launch(lib, kind):
-            rc = lib.pls_kernel_gram(kind, z.data_ptr(), n1, x.data_ptr(), n2, d, (ls_periodic if kind == 8 else ls).data_ptr(), 1.7,
+            rc = lib.pls_kernel_gram(kind, z.data_ptr(), n1, x.data_ptr(), n2, d, params[kind].data_ptr(), 1.7,
                                      out.data_ptr(), n2, sp)
             if rc:
                 raise RuntimeError(f"pls_kernel_gram(kind {kind}): {lib.pls_last_error().decode()}")
