@@ -68,7 +68,28 @@ typedef enum {
  * front of the period term, the terms of the exponent added in ascending k.  So kappa is exactly 1 at distance 0 and for
  * any pair an exact whole number of periods apart (a power-of-two period makes e exact), k is exactly symmetric, and k
  * does not change by a bit under a translation of all points that is exact in fp64.  A pair whose exponent is below -745.2
- * is exactly 0 and skipped in every sum.  The kernel has NO limit at infinity: a non-finite difference gives NaN. */
+ * is exactly 0 and skipped in every sum.  The kernel has NO limit at infinity: a non-finite difference gives NaN.
+ * LOCALLY_PERIODIC: gpytorch ScaleKernel(RBFKernel(ard_num_dims = d) * PeriodicKernel(ard_num_dims = d)) AS RECALLED, the
+ * locally periodic (quasi-periodic) kernel -- a reading, not a run of gpytorch; the formula here is the contract and it is what
+ * the tests hold.  An addition within ABI 7 (no export is added or changed); its value is 10, because 9 stays a value that
+ * every entry refuses as unknown, like 5 and 7.  With envelope lengthscales l_k > 0, periodic lengthscales lambda_k > 0 (they
+ * divide and are not squared, as PERIODIC's), period lengths p_k > 0 and e_k = (a_k - b_k) / p_k, the two factors share one
+ * exponential:
+ *   kappa                  = exp(-(1/2 sum_k ((a_k - b_k) / l_k)^2 + 2 sum_k sin^2(pi e_k) / lambda_k)),   k = outputscale * kappa
+ *   dk / d log l_k         = outputscale * kappa * ((a_k - b_k) / l_k)^2
+ *   dk / d log lambda_k    = outputscale * kappa * (2 / lambda_k) sin^2(pi e_k)
+ *   dk / d log p_k         = outputscale * kappa * (2 / lambda_k) * pi e_k * sin(2 pi e_k)
+ * For this kind EVERY `lengthscale` argument of this header points to 3 d doubles: the d envelope lengthscales l_k, then the
+ * d periodic lengthscales lambda_k, then the d period lengths p_k (pls_gp_mll_grad_classes: 3 d per class), and
+ * 1 <= d <= 16, PERIODIC's limit; the workspace queries return 0 for d > 16.  The reduction returns 3 d + 1 sums in the order
+ * kappa, l, lambda, p, and an evaluation 4 + 3 d outputs.  Evaluation, the same in the Gram build, the gradient reduction, the
+ * fused mean and the selector: the points are not pre-scaled; per coordinate the difference first, then z = (a_k - b_k) *
+ * (1 / l_k) and PERIODIC's evaluation of (2 / lambda_k) sin^2(pi e_k); the coordinate's two shares are added first, in one
+ * fused multiply-add (z / 2) * z + (2 / lambda_k) sin^2(pi e_k), then the coordinates in ascending k; ONE exponential of the
+ * negated sum.  So kappa is exactly 1 at distance 0, k is exactly symmetric, and k does not change by a bit under a
+ * translation of all points that is exact in fp64.  A pair whose exponent is below -745.2 is exactly 0 and skipped in every
+ * sum.  A non-finite difference gives NaN.  NOT guaranteed, unlike PERIODIC: kappa = 1 a whole number of periods apart -- the
+ * envelope forbids it. */
 typedef enum {
   PLS_KERNEL_RBF_ARD = 0,
   PLS_KERNEL_LINEAR = 1,
@@ -76,7 +97,8 @@ typedef enum {
   PLS_KERNEL_MATERN32 = 3,
   PLS_KERNEL_MATERN52 = 4,
   PLS_KERNEL_RQ = 6, /* (5 is not a kind) */
-  PLS_KERNEL_PERIODIC = 8 /* (7 is not a kind) */
+  PLS_KERNEL_PERIODIC = 8, /* (7 is not a kind) */
+  PLS_KERNEL_LOCALLY_PERIODIC = 10 /* (9 is not a kind) */
 } pls_kernel_kind;
 
 /* src/projected_langevin_sampling/costs/{gaussian,poisson,bernoulli,student_t,multimodal}.py */
@@ -402,7 +424,7 @@ int pls_timeline_end(float *ms, int32_t *tags, int32_t capacity, int32_t *count)
 
 /* out(n1 x n2) = k(x1, x2); x1 (n1 x d), x2 (n2 x d) row-major contiguous.
  * Replaces kernel.base_kernel(x1=.., x2=..) at orthonormal.py:36-41, inducing_point.py:41-46.
- * lengthscale: d values (every kind except LINEAR needs it; ignored for LINEAR); RQ: d + 1, alpha last; PERIODIC: 2 d, the
+ * lengthscale: d values (every kind except LINEAR needs it; ignored for LINEAR); RQ: d + 1, alpha last; LOCALLY_PERIODIC: 3 d (l, lambda, p; d <= 16); PERIODIC: 2 d, the
  * period lengths behind the lengthscales, and d <= 16. */
 int pls_kernel_gram(int32_t kernel_kind, const double *x1, int64_t n1, const double *x2, int64_t n2,
                     int64_t d, const double *lengthscale, double outputscale, double *out, int64_t ldout,
@@ -530,22 +552,24 @@ int pls_tri_multiply(const double *LcT, int64_t ldlct, int64_t m, const double *
  *       PERIODIC: dK_ij / d log lambda_k = s kappa 2 sin^2(pi e_k) / lambda_k,  e_k = (x_ik - x_jk) / p_k
  *   out[1 + d] = sum_ij W_ij dK_ij / d log alpha = sum_ij W_ij s alpha kappa (u / (1 + u) - log1p(u))          (RQ only)
  *   out[1 + d + k] = sum_ij W_ij dK_ij / d log p_k = sum_ij W_ij s kappa (2 / lambda_k) pi e_k sin(2 pi e_k)   (PERIODIC only)
+ *   LOCALLY_PERIODIC (3 d + 1 sums, kappa the product's): out[1 + k] = sum_ij W_ij s kappa ((x_ik - x_jk) / l_k)^2, then
+ *       out[1 + d + k] = sum_ij W_ij dK_ij / d log lambda_k and out[1 + 2 d + k] = sum_ij W_ij dK_ij / d log p_k as PERIODIC's two
  * A pair with r = 0 (the diagonal, duplicated points) contributes exactly 0 to every out[1 + k]; a pair whose
  * exponential underflows contributes exactly 0 to every sum; a pair with r = 0 contributes exactly 0 to out[1 + d] too.
  * PLS_KERNEL_LINEAR is rejected.
  * x (n x d) row-major contiguous, alpha (n; the solve's vector, not RQ's shape), P (n x n, SYMMETRIC, leading dimension
- * ldp; read once -- 16 bytes per lane where ldp is even and P is 16-byte aligned), out (d + 1, device; RQ: d + 2; PERIODIC:
+ * ldp; read once -- 16 bytes per lane where ldp is even and P is 16-byte aligned), out (d + 1, device; RQ: d + 2; LOCALLY_PERIODIC: 3 d + 1; PERIODIC:
  * 2 d + 1).  kappa is
  * recomputed from x; no Gram matrix is read.
  * Deterministic summation order (no atomics): two calls give the same bits.
  * workspace: pls_kernel_grad_sums_workspace_bytes_kind(kind, n, d) = 8 S ceil(n / 512) ceil(n / 64) bytes with S = d + 1
- * sums (RQ: d + 2; PERIODIC: 2 d + 1, and 0 bytes for d > 16); pls_kernel_grad_sums_workspace_bytes(n, d) is the S = d + 1
- * value (every kind but RQ and PERIODIC). */
+ * sums (RQ: d + 2; PERIODIC: 2 d + 1, LOCALLY_PERIODIC: 3 d + 1, and 0 bytes for d > 16); pls_kernel_grad_sums_workspace_bytes(n, d)
+ * is the S = d + 1 value (every kind but RQ, PERIODIC and LOCALLY_PERIODIC). */
 size_t pls_kernel_grad_sums_workspace_bytes(int64_t n, int64_t d);
 size_t pls_kernel_grad_sums_workspace_bytes_kind(int32_t kernel_kind, int64_t n, int64_t d);
 int pls_kernel_grad_sums(int32_t kernel_kind, const double *x, int64_t n, int64_t d, const double *lengthscale,
                          double outputscale, const double *alpha, const double *P, int64_t ldp,
-                         double *out /* d + 1 (RQ: d + 2; PERIODIC: 2 d + 1), device */, void *workspace, size_t workspace_bytes, void *stream);
+                         double *out /* d + 1 (RQ: d + 2; PERIODIC: 2 d + 1; LOCALLY_PERIODIC: 3 d + 1), device */, void *workspace, size_t workspace_bytes, void *stream);
 
 /* The exact-GP predictive mean at t test points WITHOUT the n x t cross-Gram matrix: replaces the mean of
  * model(experiment_data.train.x) at experiments/uci/regression/main.py:231 (every subsample GP predicts at all N training
@@ -578,21 +602,23 @@ int pls_kernel_mean(int32_t kernel_kind, const double *x, int64_t n, int64_t d, 
  *   out[4 + k] = d mll / d log lengthscale_k                            (d mll / d theta = 1/2 sum_ij W_ij dK_ij / d theta)
  *   out[4 + d] = d mll / d log alpha                                    (RQ only: its out has 5 + d doubles)
  *   out[4 + d + k] = d mll / d log p_k                                  (PERIODIC only: its out has 4 + 2 d doubles)
+ *   LOCALLY_PERIODIC (4 + 3 d doubles): out[4 + k] = d mll / d log l_k, out[4 + d + k] = d mll / d log lambda_k,
+ *       out[4 + 2 d + k] = d mll / d log p_k
  * Steps: pls_kernel_gram, the diagonal, pls_chol_factor, pls_chol_solve, pls_chol_build_inverse, K_y^-1 = Linv^T Linv on
  * the MFMA contraction, pls_kernel_grad_sums with P = K_y^-1, a one-workgroup finishing kernel (fixed-order sums).
- * out: 4 + d doubles (RQ: 5 + d; PERIODIC: 4 + 2 d), device memory or pinned host memory mapped into the device.  info (DEVICE int32): as
+ * out: 4 + d doubles (RQ: 5 + d; PERIODIC: 4 + 2 d; LOCALLY_PERIODIC: 4 + 3 d), device memory or pinned host memory mapped into the device.  info (DEVICE int32): as
  * pls_chol_factor -- 0, or the 1-based index of the first pivot that was not positive; the outputs are then unspecified
  * and the caller retries with a larger jitter.  Nothing synchronises or allocates.
  * workspace (16-byte aligned): with ld = n rounded up to even and v(k) = k rounded up to even,
  *   pls_gp_mll_workspace_bytes_kind(kind, n, d) = 8 (7 n ld + 2 v(n) + v(S ceil(n / 512) ceil(n / 64)) + v(S)) bytes:
  * seven n x ld planes (K_y, reused for K_y^-1; Lc; Lc^T; Sf; Sb; Linv, which first holds the Gram matrix; Linv^T), r,
- * alpha, the partial rows of the reduction and its S sums, S = d + 1 (RQ: d + 2; PERIODIC: 2 d + 1, and 0 bytes for d > 16).
- * pls_gp_mll_workspace_bytes(n, d) is the S = d + 1 value: what every kind but RQ and PERIODIC needs.  The entry checks against the kind-aware value. */
+ * alpha, the partial rows of the reduction and its S sums, S = d + 1 (RQ: d + 2; PERIODIC: 2 d + 1, LOCALLY_PERIODIC: 3 d + 1, and 0 bytes for d > 16).
+ * pls_gp_mll_workspace_bytes(n, d) is the S = d + 1 value: what every kind but RQ, PERIODIC and LOCALLY_PERIODIC needs.  The entry checks against the kind-aware value. */
 size_t pls_gp_mll_workspace_bytes(int64_t n, int64_t d);
 size_t pls_gp_mll_workspace_bytes_kind(int32_t kernel_kind, int64_t n, int64_t d);
 int pls_gp_mll_grad(int32_t kernel_kind, const double *x, int64_t n, int64_t d, const double *lengthscale,
                     double outputscale, double noise, double mean, double jitter, const double *y,
-                    double *out /* 4 + d (RQ: 5 + d; PERIODIC: 4 + 2 d), device or mapped pinned host */, int32_t *info /* device */,
+                    double *out /* 4 + d (RQ: 5 + d; PERIODIC: 4 + 2 d; LOCALLY_PERIODIC: 4 + 3 d), device or mapped pinned host */, int32_t *info /* device */,
                     void *workspace, size_t workspace_bytes, void *stream);
 
 /* The same evaluation for `classes` independent GPs on the shared x, in ONE call: the per-epoch work of exact-GP
@@ -601,9 +627,9 @@ int pls_gp_mll_grad(int32_t kernel_kind, const double *x, int64_t n, int64_t d, 
  * lengthscales, outputscale s_c, constant mean, learned noise sigma_c and a FIXED noise per point:
  *   K_y,c = s_c kappa(x, x; l_c) + diag(fixed_noise[c][.] + noise[c] + jitter)
  * fixed_noise == NULL: no fixed part (row c is then exactly pls_gp_mll_grad with class c's parameters).
- *   lengthscale (classes x d, contiguous; RQ: classes x (d + 1), alpha last in each row; PERIODIC: classes x 2 d) DEVICE;  outputscale, noise, mean (classes each) HOST arrays, read before the
+ *   lengthscale (classes x d, contiguous; RQ: classes x (d + 1), alpha last in each row; PERIODIC: classes x 2 d; LOCALLY_PERIODIC: classes x 3 d) DEVICE;  outputscale, noise, mean (classes each) HOST arrays, read before the
  *   call returns;  fixed_noise (classes x n, leading dimension ldf) and y (classes x n, leading dimension ldy) DEVICE.
- *   out (classes x (4 + d), RQ: classes x (5 + d), PERIODIC: classes x (4 + 2 d), contiguous; device or mapped pinned host): row c laid out as the out of pls_gp_mll_grad,
+ *   out (classes x (4 + d), RQ: classes x (5 + d), PERIODIC: classes x (4 + 2 d), LOCALLY_PERIODIC: classes x (4 + 3 d), contiguous; device or mapped pinned host): row c laid out as the out of pls_gp_mll_grad,
  *   out[c][2] the derivative with respect to noise[c];  info (classes, DEVICE int32): per class as pls_gp_mll_grad.
  * A non-positive pivot in class c is reported in info[c] alone: the call returns PLS_OK and the rows of the other classes
  * are valid.  The classes run one after another on `stream` and share the workspace of ONE evaluation:
@@ -615,7 +641,7 @@ int pls_gp_mll_grad_classes(int32_t kernel_kind, const double *x, int64_t n, int
                             const double *lengthscale /* device */, const double *outputscale /* host */,
                             const double *noise /* host */, const double *mean /* host */,
                             const double *fixed_noise /* device, may be NULL */, int64_t ldf, const double *y, int64_t ldy,
-                            double jitter, double *out /* classes x (4 + d), RQ: (5 + d), PERIODIC: (4 + 2 d) */, int32_t *info /* classes, device */,
+                            double jitter, double *out /* classes x (4 + d), RQ: (5 + d), PERIODIC: (4 + 2 d), LOCALLY_PERIODIC: (4 + 3 d) */, int32_t *info /* classes, device */,
                             void *workspace, size_t workspace_bytes, void *stream);
 
 /* Class probabilities of the Dirichlet GP at t test points from the latent means mu and variances var (classes x t,
@@ -997,7 +1023,7 @@ int pls_ipb_prior_energy(const pls_ipb_desc *basis, const double *U, int64_t ldu
  * (:108-113).  No N x N Gram matrix is formed (the reference builds one just to read its diagonal, :64-69).
  * indices: m int64 (device), count: 1 int64 (device) = number of points selected (m unless the threshold stopped it).
  * Nothing synchronises: the pivot of every iteration stays on the device.  Ties are broken towards the smaller index.
- * kernel_kind: any pls_kernel_kind; lengthscale: d values (every kind except LINEAR needs it; ignored for LINEAR; RQ: d + 1; PERIODIC: 2 d, d <= 16).
+ * kernel_kind: any pls_kernel_kind; lengthscale: d values (every kind except LINEAR needs it; ignored for LINEAR; RQ: d + 1; PERIODIC: 2 d, d <= 16; LOCALLY_PERIODIC: 3 d, d <= 16).
  * workspace: pls_select_inducing_workspace_bytes(n, m) bytes. */
 size_t pls_select_inducing_workspace_bytes(int64_t n, int64_t m);
 int pls_select_inducing_conditional_variance(int32_t kernel_kind, const double *x, int64_t n, int64_t d,

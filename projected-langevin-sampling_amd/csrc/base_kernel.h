@@ -1,7 +1,9 @@
 // What the pairwise kernels of base_kernel.hip share (Gram build, gradient reduction, fused predictive mean): tile geometry,
 // the pre-scaled staging of the points, the distance sum of a pair, the KIND x D_MAX dispatch.  The pair's value: kernel_math.h.
 // The periodic kind is not a function of one distance sum: its points are staged UNSCALED, its two scales per coordinate
-// sit in LDS, and its pair loop (periodic_exponent, periodic_factors) evaluates every coordinate on its own.
+// sit in LDS, and its pair loop (periodic_exponent, periodic_factors) evaluates every coordinate on its own.  The locally
+// periodic kind does the same with a third scale per coordinate, the envelope's 1 / l_k (locally_periodic_exponent,
+// locally_periodic_factors).
 #pragma once
 #include "common.h"
 #include "kernel_math.h"
@@ -13,7 +15,10 @@ namespace plship {
 constexpr int PAIR_ROWS = 64, PAIR_COLS = 512, PAIR_D_MAX = 64;
 // the periodic kind's own limit: its reduction carries 2 D_MAX + 1 accumulators per thread, at 16 what RBF carries at 32
 constexpr int PERIODIC_D_MAX = 16;
-static inline int64_t kind_d_max(int32_t kind) { return kind == PLS_KERNEL_PERIODIC ? PERIODIC_D_MAX : PAIR_D_MAX; }
+// the kinds whose points are staged unscaled and whose coordinates go through periodic_coord; they share PERIODIC_D_MAX (the
+// locally periodic reduction carries 3 D_MAX + 1 accumulators and splits a column's coordinates in two halves above 8)
+constexpr bool periodic_like(int kind) { return kind == PLS_KERNEL_PERIODIC || kind == PLS_KERNEL_LOCALLY_PERIODIC; }
+static inline int64_t kind_d_max(int32_t kind) { return periodic_like(kind) ? PERIODIC_D_MAX : PAIR_D_MAX; }
 
 // pls_kernel_mean: test points of a workgroup (one per lane, the four waves split the training points), and the training
 // points staged in LDS at a time: 32 KiB of pre-scaled coordinates, 512 points at the most; a multiple of 4 for every D_MAX
@@ -21,9 +26,9 @@ constexpr int MEAN_POINTS = 64;
 constexpr int mean_chunk(int d_max) { return 4096 / d_max < 512 ? 4096 / d_max : 512; }
 
 // shape parameters of a kind: they follow the d lengthscales in its `lengthscale` argument (RQ: alpha; periodic: the d
-// period lengths)
+// period lengths; locally periodic: the d periodic lengthscales, then the d period lengths)
 static inline int64_t kind_shape_params(int32_t kind, int64_t d) {
-  return kind == PLS_KERNEL_RQ ? 1 : kind == PLS_KERNEL_PERIODIC ? d : 0;
+  return kind == PLS_KERNEL_RQ ? 1 : kind == PLS_KERNEL_PERIODIC ? d : kind == PLS_KERNEL_LOCALLY_PERIODIC ? 2 * d : 0;
 }
 // sums of the reduction: the kappa sum, one per lengthscale, one per shape parameter
 static inline int64_t grad_sums_count(int32_t kind, int64_t d) { return d + 1 + kind_shape_params(kind, d); }
@@ -36,12 +41,14 @@ static inline size_t grad_sums_workspace_bytes(int32_t kind, int64_t n, int64_t 
 
 static inline bool stationary_kind(int32_t kind) {
   return kind == PLS_KERNEL_RBF_ARD || kind == PLS_KERNEL_MATERN12 || kind == PLS_KERNEL_MATERN32 || kind == PLS_KERNEL_MATERN52 ||
-         kind == PLS_KERNEL_RQ || kind == PLS_KERNEL_PERIODIC;
+         kind == PLS_KERNEL_RQ || periodic_like(kind);
 }
 // what every entry checks after the kind and d >= 1: the kind's largest input dimension, under the entry's name `who`
 static inline int check_kind_dim(const char *who, int32_t kind, int64_t d) {
   PLS_REQUIRE(kind != PLS_KERNEL_PERIODIC || d <= PERIODIC_D_MAX,
               "%s: input dimension %lld > 16 is not supported for the periodic kernel", who, (long long)d);
+  PLS_REQUIRE(kind != PLS_KERNEL_LOCALLY_PERIODIC || d <= PERIODIC_D_MAX,
+              "%s: input dimension %lld > 16 is not supported for the locally periodic kernel", who, (long long)d);
   PLS_REQUIRE(d <= PAIR_D_MAX, "%s: input dimension %lld > 64 is not supported", who, (long long)d);
   return PLS_OK;
 }
@@ -57,7 +64,7 @@ int grad_sums_launch(int kind, const double *x, int64_t n, int d, const double *
                      const double *alpha, const double *P, int64_t ldp, double *out, double *partials, hipStream_t st);
 
 // The KIND x D_MAX instantiations of a base kernel's per-pair loops: f(integral_constant<KIND>, integral_constant<D_MAX>), D_MAX
-// the input dimension rounded up to 1, 2, 4, ..., 64 (periodic: ..., 16; kind and d already validated).  LINEAR: with the linear
+// the input dimension rounded up to 1, 2, 4, ..., 64 (periodic and locally periodic: ..., 16; kind and d already validated).  LINEAR: with the linear
 // kind (the Gram build).
 template <bool LINEAR, class F>
 static int for_kind_dmax(int kind, int d, F &&f) {
@@ -72,14 +79,15 @@ static int for_kind_dmax(int kind, int d, F &&f) {
     return f(k, integral_constant<int, 64>{});
   };
   if constexpr (LINEAR) if (kind == PLS_KERNEL_LINEAR) return with_kind(integral_constant<int, PLS_KERNEL_LINEAR>{});
-  if (kind == PLS_KERNEL_PERIODIC) {
-    const integral_constant<int, PLS_KERNEL_PERIODIC> k{};
+  auto with_periodic_kind = [&](auto k) {
     if (d <= 1) return f(k, integral_constant<int, 1>{});
     if (d <= 2) return f(k, integral_constant<int, 2>{});
     if (d <= 4) return f(k, integral_constant<int, 4>{});
     if (d <= 8) return f(k, integral_constant<int, 8>{});
     return f(k, integral_constant<int, PERIODIC_D_MAX>{});
-  }
+  };
+  if (kind == PLS_KERNEL_PERIODIC) return with_periodic_kind(integral_constant<int, PLS_KERNEL_PERIODIC>{});
+  if (kind == PLS_KERNEL_LOCALLY_PERIODIC) return with_periodic_kind(integral_constant<int, PLS_KERNEL_LOCALLY_PERIODIC>{});
   switch (kind) {
     case PLS_KERNEL_RBF_ARD: return with_kind(integral_constant<int, PLS_KERNEL_RBF_ARD>{});
     case PLS_KERNEL_MATERN12: return with_kind(integral_constant<int, PLS_KERNEL_MATERN12>{});
@@ -94,13 +102,23 @@ static int for_kind_dmax(int kind, int d, F &&f) {
 // 0 for the padding k >= d: zero on both sides of a pair, so the unrolled coordinate loops need no `k < d` test.
 // Periodic: inv_ls[k] = 1 / p_k (the period lengths follow the d lengthscales) and two_inv_l[k] = 2 / lambda_k, both 0 for the
 // padding; the points themselves stay unscaled (pair_scaled).  The other kinds leave two_inv_l, an array of one, alone.
+// Locally periodic (l, lambda, p in blocks of d): inv_env[k] = 1 / l_k, inv_ls[k] = 1 / p_k and two_inv_l[k] = 2 / lambda_k as
+// for periodic, all three 0 for the padding.  Every other kind leaves inv_env, an array of one, alone.
 template <int KIND>
-constexpr int periodic_len(int d_max) { return KIND == PLS_KERNEL_PERIODIC ? d_max : 1; }
-template <int KIND, int D_MAX, int NP>
-__device__ __forceinline__ void stage_inv_lengthscale(double (&inv_ls)[D_MAX], double (&two_inv_l)[NP], const double *lengthscale,
-                                                      int d) {
+constexpr int periodic_len(int d_max) { return periodic_like(KIND) ? d_max : 1; }
+template <int KIND>
+constexpr int envelope_len(int d_max) { return KIND == PLS_KERNEL_LOCALLY_PERIODIC ? d_max : 1; }
+template <int KIND, int D_MAX, int NP, int NE>
+__device__ __forceinline__ void stage_inv_lengthscale(double (&inv_ls)[D_MAX], double (&two_inv_l)[NP], double (&inv_env)[NE],
+                                                      const double *lengthscale, int d) {
   const int t = threadIdx.x;
-  if constexpr (KIND == PLS_KERNEL_PERIODIC) {
+  if constexpr (KIND == PLS_KERNEL_LOCALLY_PERIODIC) {
+    if (t < D_MAX) {
+      inv_env[t] = (t < d) ? 1.0 / lengthscale[t] : 0.0;
+      two_inv_l[t] = (t < d) ? 2.0 / lengthscale[d + t] : 0.0;
+      inv_ls[t] = (t < d) ? 1.0 / lengthscale[2 * d + t] : 0.0;
+    }
+  } else if constexpr (KIND == PLS_KERNEL_PERIODIC) {
     if (t < D_MAX) {
       inv_ls[t] = (t < d) ? 1.0 / lengthscale[d + t] : 0.0;
       two_inv_l[t] = (t < d) ? 2.0 / lengthscale[t] : 0.0;
@@ -109,10 +127,10 @@ __device__ __forceinline__ void stage_inv_lengthscale(double (&inv_ls)[D_MAX], d
     if (t < D_MAX) inv_ls[t] = (t < d) ? ((KIND != PLS_KERNEL_LINEAR) ? matern_t_scale(KIND) / lengthscale[t] : 1.0) : 0.0;
   }
 }
-// a coordinate as a pairwise kernel holds it: times its inverse lengthscale, or as it is for the periodic kind
+// a coordinate as a pairwise kernel holds it: times its inverse lengthscale, or as it is for the periodic kinds
 template <int KIND>
 __device__ __forceinline__ double pair_scaled(double v, double inv_ls) {
-  return KIND == PLS_KERNEL_PERIODIC ? v : v * inv_ls;
+  return periodic_like(KIND) ? v : v * inv_ls;
 }
 
 // a_s[r] = row row0 + r of x (n x d, flat), pre-scaled and zero-padded, for r < nrows; 256 threads
@@ -181,6 +199,55 @@ __device__ __forceinline__ double periodic_factors(const double (&a)[D_MAX], con
   for (int k = 0; k < D_MAX; ++k) {
     fl[k] = periodic_coord<true>(a[k] - b[k], inv_p[k], two_inv_l[k], fp[k]);
     q = __dadd_rn(q, fl[k]);
+  }
+  return q;
+}
+
+// The locally periodic pair loops (kernel_math.h: locally_periodic_coord), laid out as the periodic ones: the negated
+// exponent, each coordinate's two shares added first, then the coordinates in ascending k.
+template <int D_MAX>
+__device__ __forceinline__ double locally_periodic_exponent(const double (&a)[D_MAX], const double (&b)[D_MAX],
+                                                            const double (&inv_l)[D_MAX], const double (&inv_p)[D_MAX],
+                                                            const double (&two_inv_lam)[D_MAX]) {
+  double q = 0.0, u0, u1, u2;
+#pragma unroll
+  for (int k = 0; k < D_MAX; ++k)
+    q = __dadd_rn(q, locally_periodic_coord<false>(a[k] - b[k], inv_l[k], inv_p[k], two_inv_lam[k], u0, u1, u2));
+  return q;
+}
+template <int D_MAX>
+__device__ __forceinline__ void locally_periodic_exponent(const double (&a)[D_MAX], const double (&b0)[D_MAX],
+                                                          const double (&b1)[D_MAX], const double (&inv_l)[D_MAX],
+                                                          const double (&inv_p)[D_MAX], const double (&two_inv_lam)[D_MAX],
+                                                          double &q0, double &q1) {
+  double u0, u1, u2;
+  q0 = q1 = 0.0;
+#pragma unroll
+  for (int k = 0; k < D_MAX; ++k) {
+    const double ak = a[k], il = inv_l[k], ip = inv_p[k], tl = two_inv_lam[k];
+    q0 = __dadd_rn(q0, locally_periodic_coord<false>(ak - b0[k], il, ip, tl, u0, u1, u2));
+    q1 = __dadd_rn(q1, locally_periodic_coord<false>(ak - b1[k], il, ip, tl, u0, u1, u2));
+  }
+}
+// The reduction keeps the factors of a column's first KEEP coordinates between the exponent sum and the accumulation and
+// evaluates the others a second time afterwards (the same function of the same operands: the same bits), so that at
+// D_MAX = 16 no more than 24 factors are live beside the 49 accumulators.
+constexpr int locally_periodic_keep(int d_max) { return d_max > 8 ? d_max / 2 : d_max; }
+// the same sum with the factors of the coordinates k < KEEP kept: fe[k] = ((a_k - b_k) / l_k)^2, fl[k] and fp[k] as
+// periodic_factors'; dK / d log l_k = s kappa fe[k], dK / d log lambda_k = s kappa fl[k], dK / d log p_k = s kappa fp[k]
+template <int D_MAX, int KEEP>
+__device__ __forceinline__ double locally_periodic_factors(const double (&a)[D_MAX], const double (&b)[D_MAX],
+                                                           const double (&inv_l)[D_MAX], const double (&inv_p)[D_MAX],
+                                                           const double (&two_inv_lam)[D_MAX], double (&fe)[KEEP],
+                                                           double (&fl)[KEEP], double (&fp)[KEEP]) {
+  double q = 0.0, u0, u1, u2;
+#pragma unroll
+  for (int k = 0; k < D_MAX; ++k) {
+    if (k < KEEP)
+      q = __dadd_rn(q, locally_periodic_coord<true>(a[k] - b[k], inv_l[k], inv_p[k], two_inv_lam[k], fe[k % KEEP], fl[k % KEEP],
+                                                    fp[k % KEEP]));
+    else
+      q = __dadd_rn(q, locally_periodic_coord<false>(a[k] - b[k], inv_l[k], inv_p[k], two_inv_lam[k], u0, u1, u2));
   }
   return q;
 }

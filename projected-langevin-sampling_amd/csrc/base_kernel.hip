@@ -1,9 +1,11 @@
-// The pairwise kernels of the base kernel (RBF-ARD, Matern 1/2, 3/2, 5/2, rational quadratic, periodic; the Gram build also the
-// linear kernel):
+// The pairwise kernels of the base kernel (RBF-ARD, Matern 1/2, 3/2, 5/2, rational quadratic, periodic, locally periodic; the
+// Gram build also the linear kernel):
 // pls_kernel_gram, pls_kernel_grad_sums, pls_kernel_mean.  The exact-GP path builds K with the first, differentiates with
 // the second and predicts with the third, so the three evaluate a pair alike: the same pre-scaled points and distance
 // sum (base_kernel.h), the same kappa (kernel_math.h).  The periodic kind has no distance sum: unscaled points, 1 / p_k and
-// 2 / lambda_k in LDS, one sincospi per coordinate (base_kernel.h: periodic_exponent, periodic_factors).
+// 2 / lambda_k in LDS, one sincospi per coordinate (base_kernel.h: periodic_exponent, periodic_factors).  The locally periodic
+// kind is the periodic one with the envelope's 1 / l_k as a third scale in LDS and both shares of a coordinate in the one
+// exponent (locally_periodic_exponent, locally_periodic_factors).
 #include <hip/hip_runtime.h>
 
 #define PLS_SCALAR_POLY_CONSTANTS 1  // (fmath.h: the exp polynomial's constants as scalar operands)
@@ -23,14 +25,15 @@ __global__ __launch_bounds__(256) void kernel_gram_kernel(const double *__restri
                                                            const double *__restrict__ x2, int64_t n2, int d,
                                                            const double *__restrict__ lengthscale, double outputscale,
                                                            double *__restrict__ out, int64_t ldout) {
-  constexpr bool PERIODIC = KIND == PLS_KERNEL_PERIODIC;
-  __shared__ double inv_ls[D_MAX];                        // (periodic: 1 / p_k)
-  __shared__ double two_inv_l[periodic_len<KIND>(D_MAX)];  // (periodic: 2 / lambda_k)
+  constexpr bool PERIODIC = KIND == PLS_KERNEL_PERIODIC, LOCAL = KIND == PLS_KERNEL_LOCALLY_PERIODIC;
+  __shared__ double inv_ls[D_MAX];                        // (periodic, locally periodic: 1 / p_k)
+  __shared__ double two_inv_l[periodic_len<KIND>(D_MAX)];  // (periodic, locally periodic: 2 / lambda_k)
+  __shared__ double inv_env[envelope_len<KIND>(D_MAX)];    // (locally periodic: 1 / l_k)
   __shared__ __attribute__((aligned(16))) double a_s[PAIR_ROWS][D_MAX];  // rows of x1 (pre-scaled, zero-padded)
   const int t = threadIdx.x;
   const int64_t row0 = (int64_t)blockIdx.y * PAIR_ROWS;
   const int nrows = (int)((n1 - row0 < PAIR_ROWS) ? (n1 - row0) : PAIR_ROWS);
-  stage_inv_lengthscale<KIND>(inv_ls, two_inv_l, lengthscale, d);
+  stage_inv_lengthscale<KIND>(inv_ls, two_inv_l, inv_env, lengthscale, d);
   const PairShape sh = load_pair_shape<KIND>(lengthscale, d);
   __syncthreads();
   stage_rows<KIND>(a_s, x1, row0, nrows, d, inv_ls);
@@ -49,8 +52,9 @@ __global__ __launch_bounds__(256) void kernel_gram_kernel(const double *__restri
 #pragma unroll 2
   for (int r = 0; r < nrows; ++r, dst += ldout) {
     double s0 = 0.0, s1 = 0.0;
-    if constexpr (PERIODIC) {
-      periodic_exponent(a_s[r], b0, b1, inv_ls, two_inv_l, s0, s1);
+    if constexpr (PERIODIC || LOCAL) {
+      if constexpr (LOCAL) locally_periodic_exponent(a_s[r], b0, b1, inv_env, inv_ls, two_inv_l, s0, s1);
+      else periodic_exponent(a_s[r], b0, b1, inv_ls, two_inv_l, s0, s1);
       double kap0, kap1;
       const bool live0 = periodic_kappa(s0, kap0), live1 = periodic_kappa(s1, kap1);
       s0 = live0 ? outputscale * kap0 : 0.0;
@@ -78,7 +82,8 @@ __global__ __launch_bounds__(256) void kernel_gram_kernel(const double *__restri
 
 // The reduction over the n x n pair matrix, laid out as kernel_gram_kernel (a thread owns a PAIR of columns and walks down
 // the rows in LDS).  P is read once, 16 B per lane where ldp is even and P is 16-byte aligned.  D_MAX + 1 accumulators per
-// thread, one more for RQ; periodic: 2 D_MAX + 1, the period sums behind the lengthscale sums.
+// thread, one more for RQ; periodic: 2 D_MAX + 1, the period sums behind the lengthscale sums; locally periodic: 3 D_MAX + 1,
+// the sums of l, lambda and p in blocks.
 //   out[0]     = sum_ij W_ij kappa_ij                  (kappa: the kernel without its outputscale)
 //   out[1 + k] = sum_ij W_ij dK_ij / d log l_k         (RBF: s exp(-r^2/2) e_k^2;  Matern: s q(t) exp(-t) 2 nu e_k^2 with
 //                                                       q = 1/t, 1, (1 + t)/3 for nu = 1/2, 3/2, 5/2;  RQ: s kappa / (1 + u) e_k^2;
@@ -86,6 +91,8 @@ __global__ __launch_bounds__(256) void kernel_gram_kernel(const double *__restri
 //                                                       periodic: s kappa (2 / lambda_k) sin^2(pi e_k), e_k = (x_ik - x_jk)/p_k
 //   out[1 + d] = sum_ij W_ij dK_ij / d log alpha       (RQ only: s alpha kappa (u / (1 + u) - log1p(u)), u = r^2 / (2 alpha))
 //   out[1 + d + k] = sum_ij W_ij dK_ij / d log p_k     (periodic only: s kappa (2 / lambda_k) pi e_k sin(2 pi e_k))
+//   locally periodic: out[1 + k] = sum_ij W_ij s kappa ((x_ik - x_jk) / l_k)^2, out[1 + d + k] and out[1 + 2 d + k] the periodic
+//   kind's sums for lambda_k and p_k, with kappa the product's
 // with W = alpha alpha^T - P; no atomics: per thread down its rows, then the workgroup sum below, then the workgroups'
 // partial rows in ascending order (a second one-workgroup launch).
 template <int KIND, int D_MAX>
@@ -93,19 +100,20 @@ __global__ __launch_bounds__(256) void kernel_grad_sums_kernel(const double *__r
                                                                 const double *__restrict__ lengthscale, double outputscale,
                                                                 const double *__restrict__ alpha, const double *__restrict__ P,
                                                                 int64_t ldp, double *__restrict__ partials) {
-  constexpr bool PERIODIC = KIND == PLS_KERNEL_PERIODIC;
-  __shared__ double inv_ls[D_MAX];                        // (periodic: 1 / p_k)
-  __shared__ double two_inv_l[periodic_len<KIND>(D_MAX)];  // (periodic: 2 / lambda_k)
+  constexpr bool PERIODIC = KIND == PLS_KERNEL_PERIODIC, LOCAL = KIND == PLS_KERNEL_LOCALLY_PERIODIC;
+  __shared__ double inv_ls[D_MAX];                        // (periodic, locally periodic: 1 / p_k)
+  __shared__ double two_inv_l[periodic_len<KIND>(D_MAX)];  // (periodic, locally periodic: 2 / lambda_k)
+  __shared__ double inv_env[envelope_len<KIND>(D_MAX)];    // (locally periodic: 1 / l_k)
   __shared__ __attribute__((aligned(16))) double a_s[PAIR_ROWS][D_MAX];
   __shared__ double al_s[PAIR_ROWS];
   constexpr bool SHAPE = KIND == PLS_KERNEL_RQ;
   // (the shape sums are kept last: acc[D_MAX + 1 + j], written to slot d + 1 + j)
-  constexpr int NACC = D_MAX + 1 + (SHAPE ? 1 : 0) + (PERIODIC ? D_MAX : 0);
+  constexpr int NACC = D_MAX + 1 + (SHAPE ? 1 : 0) + (PERIODIC ? D_MAX : 0) + (LOCAL ? 2 * D_MAX : 0);
   __shared__ double red[4][NACC];
   const int t = threadIdx.x;
   const int64_t row0 = (int64_t)blockIdx.y * PAIR_ROWS;
   const int nrows = (int)((n - row0 < PAIR_ROWS) ? (n - row0) : PAIR_ROWS);
-  stage_inv_lengthscale<KIND>(inv_ls, two_inv_l, lengthscale, d);
+  stage_inv_lengthscale<KIND>(inv_ls, two_inv_l, inv_env, lengthscale, d);
   const PairShape sh = load_pair_shape<KIND>(lengthscale, d);
   if (t < PAIR_ROWS) al_s[t] = (t < nrows) ? alpha[row0 + t] : 0.0;
   __syncthreads();
@@ -138,7 +146,38 @@ __global__ __launch_bounds__(256) void kernel_grad_sums_kernel(const double *__r
       }
       const double ai = al_s[r];
       const double w0 = __dsub_rn(__dmul_rn(ai, aj0), p0), w1 = __dsub_rn(__dmul_rn(ai, aj1), p1);  // W_ij, two roundings
-      if constexpr (PERIODIC) {
+      if constexpr (LOCAL) {
+        // one column at a time, and of its coordinates the first KEEP with their 3 KEEP factors in registers; the others
+        // are evaluated again after the exponent (base_kernel.h: locally_periodic_keep)
+        constexpr int KEEP = locally_periodic_keep(D_MAX);
+        auto column = [&](const double (&b)[D_MAX], double w, bool have) {
+          double fe[KEEP], fl[KEEP], fp[KEEP], kap;
+          const bool live =
+              periodic_kappa(locally_periodic_factors(a_s[r], b, inv_env, inv_ls, two_inv_l, fe, fl, fp), kap) && have;
+          if (live) {
+            const double gw = w * (outputscale * kap);
+            acc[0] = fma(w, kap, acc[0]);
+#pragma unroll
+            for (int k = 0; k < KEEP; ++k) {
+              acc[1 + k] = fma(gw, fe[k], acc[1 + k]);
+              acc[1 + D_MAX + k] = fma(gw, fl[k], acc[1 + D_MAX + k]);
+              acc[1 + 2 * D_MAX + k] = fma(gw, fp[k], acc[1 + 2 * D_MAX + k]);
+            }
+#pragma unroll
+            for (int k = KEEP; k < D_MAX; ++k) {
+              double e, l, p, delta = a_s[r][k] - b[k];
+              // (opaque to the optimiser: merged with the first evaluation, its values would stay live after all)
+              asm volatile("" : "+v"(delta));
+              locally_periodic_coord<true>(delta, inv_env[k], inv_ls[k], two_inv_l[k], e, l, p);
+              acc[1 + k] = fma(gw, e, acc[1 + k]);
+              acc[1 + D_MAX + k] = fma(gw, l, acc[1 + D_MAX + k]);
+              acc[1 + 2 * D_MAX + k] = fma(gw, p, acc[1 + 2 * D_MAX + k]);
+            }
+          }
+        };
+        column(b0, w0, true);
+        column(b1, w1, two);
+      } else if constexpr (PERIODIC) {
         // one column at a time: its 2 D_MAX factors live in registers between the exponent sum and the accumulation
         auto column = [&](const double (&b)[D_MAX], double w, bool have) {
           double fl[D_MAX], fp[D_MAX], kap;
@@ -193,10 +232,12 @@ __global__ __launch_bounds__(256) void kernel_grad_sums_kernel(const double *__r
     if ((t & 63) == 0) red[t >> 6][k] = v;
   }
   __syncthreads();
-  const int nsums = d + 1 + (SHAPE ? 1 : 0) + (PERIODIC ? d : 0);
+  const int nsums = d + 1 + (SHAPE ? 1 : 0) + (PERIODIC ? d : 0) + (LOCAL ? 2 * d : 0);
   if (t < nsums) {
     const int64_t blk = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
-    const int k = PERIODIC ? ((t > d) ? D_MAX + (t - d) : t) : (SHAPE && t == d + 1) ? D_MAX + 1 : t;
+    const int k = LOCAL      ? ((t > 2 * d) ? 2 * D_MAX + (t - 2 * d) : (t > d) ? D_MAX + (t - d) : t)
+                  : PERIODIC ? ((t > d) ? D_MAX + (t - d) : t)
+                  : (SHAPE && t == d + 1) ? D_MAX + 1 : t;
     partials[blk * nsums + t] = (red[0][k] + red[1][k]) + (red[2][k] + red[3][k]);
   }
 }
@@ -247,14 +288,15 @@ __global__ __launch_bounds__(256) void kernel_mean_kernel(const double *__restri
                                                            const double *__restrict__ xt, int64_t t,
                                                            double *__restrict__ out) {
   constexpr int CHUNK = mean_chunk(D_MAX);
-  constexpr bool PERIODIC = KIND == PLS_KERNEL_PERIODIC;
-  __shared__ double inv_ls[D_MAX];                        // (periodic: 1 / p_k)
-  __shared__ double two_inv_l[periodic_len<KIND>(D_MAX)];  // (periodic: 2 / lambda_k)
+  constexpr bool PERIODIC = KIND == PLS_KERNEL_PERIODIC, LOCAL = KIND == PLS_KERNEL_LOCALLY_PERIODIC;
+  __shared__ double inv_ls[D_MAX];                        // (periodic, locally periodic: 1 / p_k)
+  __shared__ double two_inv_l[periodic_len<KIND>(D_MAX)];  // (periodic, locally periodic: 2 / lambda_k)
+  __shared__ double inv_env[envelope_len<KIND>(D_MAX)];    // (locally periodic: 1 / l_k)
   __shared__ __attribute__((aligned(16))) double a_s[CHUNK][D_MAX];
   __shared__ double al_s[CHUNK];
   __shared__ double red[4][MEAN_POINTS];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  stage_inv_lengthscale<KIND>(inv_ls, two_inv_l, lengthscale, d);
+  stage_inv_lengthscale<KIND>(inv_ls, two_inv_l, inv_env, lengthscale, d);
   const PairShape sh = load_pair_shape<KIND>(lengthscale, d);
   if (D_MAX > 1)  // the padding coordinates stay zero: the staging below writes k < d only
     for (int e = tid; e < CHUNK * D_MAX; e += 256) a_s[e / D_MAX][e % D_MAX] = 0.0;
@@ -302,7 +344,8 @@ __global__ __launch_bounds__(256) void kernel_mean_kernel(const double *__restri
     for (int r = w; r < nrows; r += 4) {
       double kap;
       bool alive;
-      if constexpr (PERIODIC) alive = periodic_kappa(periodic_exponent(a_s[r], b, inv_ls, two_inv_l), kap);
+      if constexpr (LOCAL) alive = periodic_kappa(locally_periodic_exponent(a_s[r], b, inv_env, inv_ls, two_inv_l), kap);
+      else if constexpr (PERIODIC) alive = periodic_kappa(periodic_exponent(a_s[r], b, inv_ls, two_inv_l), kap);
       else alive = pair_kappa<KIND>(pair_dist2(a_s[r], b), sh, kap);
       if (alive) acc = fma(kap, al_s[r], acc);
     }

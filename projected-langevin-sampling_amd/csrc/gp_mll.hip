@@ -139,7 +139,7 @@ static int gp_mll_evaluate(int32_t kernel_kind, const double *x, int64_t n, int6
   if (rc) return rc;
   rc = gemm_tn_ex(Linv, p.ld, Linv, p.ld, Ky, p.ld, n, n, n, 1.0, 0.0, 2, st);
   if (rc) return rc;
-  // 5. the d + 1 sums (RQ: d + 2) with P = K_y^-1
+  // 5. the d + 1 sums (RQ: d + 2; periodic: 2 d + 1; locally periodic: 3 d + 1) with P = K_y^-1
   rc = grad_sums_launch(kernel_kind, x, n, (int)d, lengthscale, outputscale, al, Ky, p.ld, sums, partials, st);
   if (rc) return rc;
   // 6. value and derivatives

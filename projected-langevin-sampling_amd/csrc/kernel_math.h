@@ -152,6 +152,26 @@ __device__ __forceinline__ bool periodic_kappa(double q, double &kap) {
   return !(x < -745.2);
 }
 
+// Locally periodic (gpytorch's RBFKernel * PeriodicKernel times the outputscale, as recalled): kappa = exp(-(1/2 sum_k
+// ((a_k - b_k) / l_k)^2 + 2 sum_k sin^2(pi e_k) / lambda_k)): both factors share the one exponential.  One coordinate from
+// its UNSCALED difference delta, inv_l = 1 / l_k and periodic_coord's two scales: z = delta inv_l, the periodic share
+// from periodic_coord, and the two shares of the coordinate added in ONE explicit fma, (z / 2) z + share (z / 2 is exact).
+// Returns the coordinate's share of the NEGATED exponent; GRAD only: env = z^2, the factor of dK / d log l_k, lam = the
+// periodic share, the factor of dK / d log lambda_k, per as periodic_coord's.  Even in delta like periodic_coord; a padding
+// coordinate (delta = 0, all scales 0) gives 0; a non-finite delta gives NaN (inf + NaN).
+template <bool GRAD>
+__device__ __forceinline__ double locally_periodic_coord(double delta, double inv_l, double inv_p, double two_inv_lam,
+                                                         double &env, double &lam, double &per) {
+#pragma clang fp contract(off)
+  const double z = delta * inv_l;
+  const double share = periodic_coord<GRAD>(delta, inv_p, two_inv_lam, per);
+  if (GRAD) {
+    env = z * z;
+    lam = share;
+  }
+  return fma(0.5 * z, z, share);
+}
+
 // One pair from its distance sum s2 (RBF: r^2; Matern: t^2 = 2 nu r^2; RQ: r^2, with its shape sh): kap = kappa, the kernel
 // without its outputscale; t = sqrt(s2) (Matern only) and ex, the exponential inside kappa, for pair_factors.  Returns
 // false for a pair whose exponential underflows: kap is meaningless then and the caller lets the pair contribute exactly

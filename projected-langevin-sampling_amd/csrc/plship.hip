@@ -1271,6 +1271,12 @@ __device__ inline double cv_kernel_eval(int kind, const double *__restrict__ x, 
                                         const double *__restrict__ inv_ls, const double *__restrict__ inv_p, double shape,
                                         double outputscale) {
   double s = 0.0;
+  if (kind == PLS_KERNEL_LOCALLY_PERIODIC) {  // as periodic below, with inv_ls[k] = 1 / l_k and 2 / lambda_k at inv_p[16 + k]
+    double u0, u1, u2, kap;
+    for (int k = 0; k < d; ++k)
+      s = __dadd_rn(s, locally_periodic_coord<false>(x[a * d + k] - x[b * d + k], inv_ls[k], inv_p[k], inv_p[16 + k], u0, u1, u2));
+    return periodic_kappa(s, kap) ? outputscale * kap : 0.0;
+  }
   if (kind == PLS_KERNEL_PERIODIC) {  // the pairwise kernels' own evaluation, coordinate by coordinate (kernel_math.h);
     double unused, kap;               // inv_p[k] = 1 / p_k, and 2 inv_ls[k] is 2 / lambda_k to the bit
     for (int k = 0; k < d; ++k)
@@ -1316,9 +1322,15 @@ __global__ __launch_bounds__(CV_BLOCK) void cv_init_kernel(int kind, const doubl
                                                             double jitter, double *__restrict__ di,
                                                             unsigned char *__restrict__ chosen, CvState *st) {
   __shared__ double inv_ls[64];
-  __shared__ double inv_p[16];  // (periodic: the period lengths follow the d <= 16 lengthscales)
+  // (periodic: the period lengths follow the d <= 16 lengthscales; locally periodic: l, lambda, p in blocks of d, 1 / p_k in
+  // front and 2 / lambda_k behind it)
+  __shared__ double inv_p[32];
   if ((int)threadIdx.x < d) inv_ls[threadIdx.x] = (kind != PLS_KERNEL_LINEAR) ? 1.0 / lengthscale[threadIdx.x] : 1.0;
   if (kind == PLS_KERNEL_PERIODIC && (int)threadIdx.x < d) inv_p[threadIdx.x] = 1.0 / lengthscale[d + threadIdx.x];
+  if (kind == PLS_KERNEL_LOCALLY_PERIODIC && (int)threadIdx.x < d) {
+    inv_p[threadIdx.x] = 1.0 / lengthscale[2 * d + threadIdx.x];
+    inv_p[16 + threadIdx.x] = 2.0 / lengthscale[d + threadIdx.x];
+  }
   const double shape = (kind == PLS_KERNEL_RQ) ? lengthscale[d] : 0.0;
   __syncthreads();
   const int64_t i = (int64_t)blockIdx.x * CV_BLOCK + threadIdx.x;
@@ -1434,9 +1446,15 @@ __global__ __launch_bounds__(CV_BLOCK) void cv_update_kernel(int kind, const dou
   constexpr int NSL = CV_BLOCK / CV_COLS;
   __shared__ double inv_ls[64];
   __shared__ double part[NSL][CV_COLS];
-  __shared__ double inv_p[16];  // (periodic: the period lengths follow the d <= 16 lengthscales)
+  // (periodic: the period lengths follow the d <= 16 lengthscales; locally periodic: l, lambda, p in blocks of d, 1 / p_k in
+  // front and 2 / lambda_k behind it)
+  __shared__ double inv_p[32];
   if ((int)threadIdx.x < d) inv_ls[threadIdx.x] = (kind != PLS_KERNEL_LINEAR) ? 1.0 / lengthscale[threadIdx.x] : 1.0;
   if (kind == PLS_KERNEL_PERIODIC && (int)threadIdx.x < d) inv_p[threadIdx.x] = 1.0 / lengthscale[d + threadIdx.x];
+  if (kind == PLS_KERNEL_LOCALLY_PERIODIC && (int)threadIdx.x < d) {
+    inv_p[threadIdx.x] = 1.0 / lengthscale[2 * d + threadIdx.x];
+    inv_p[16 + threadIdx.x] = 2.0 / lengthscale[d + threadIdx.x];
+  }
   const double shape = (kind == PLS_KERNEL_RQ) ? lengthscale[d] : 0.0;
   __syncthreads();
   if (st->stopped || st->count != iter + 1) return;  // (stopped early, or ran out of candidates; uniform)
@@ -3202,13 +3220,15 @@ int pls_select_inducing_conditional_variance(int32_t kernel_kind, const double *
                                              double threshold, int64_t *indices, int64_t *count, void *workspace,
                                              size_t workspace_bytes, void *stream) {
   PLS_REQUIRE((kernel_kind >= PLS_KERNEL_RBF_ARD && kernel_kind <= PLS_KERNEL_MATERN52) || kernel_kind == PLS_KERNEL_RQ ||
-                  kernel_kind == PLS_KERNEL_PERIODIC,
+                  kernel_kind == PLS_KERNEL_PERIODIC || kernel_kind == PLS_KERNEL_LOCALLY_PERIODIC,
               "unknown kernel kind %d", kernel_kind);
   PLS_REQUIRE(x && indices && count, "select_inducing: NULL pointer");
   PLS_REQUIRE(m > 1, "select_inducing: Must have at least 2 inducing points");  // conditional_variance.py:57
   PLS_REQUIRE(n >= m && d >= 1 && d <= 64, "select_inducing: need n >= m and 1 <= d <= 64");
   PLS_REQUIRE(kernel_kind != PLS_KERNEL_PERIODIC || d <= 16,
               "select_inducing: input dimension %lld > 16 is not supported for the periodic kernel", (long long)d);
+  PLS_REQUIRE(kernel_kind != PLS_KERNEL_LOCALLY_PERIODIC || d <= 16,
+              "select_inducing: input dimension %lld > 16 is not supported for the locally periodic kernel", (long long)d);
   PLS_REQUIRE(kernel_kind == PLS_KERNEL_LINEAR || lengthscale, "select_inducing: kernel kind %d needs lengthscale", kernel_kind);
   const size_t need = pls_select_inducing_workspace_bytes(n, m);
   if (!workspace || workspace_bytes < need)

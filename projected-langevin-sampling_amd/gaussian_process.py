@@ -21,7 +21,7 @@ import torch
 from . import _lib as L
 from . import _ops
 from ._chol import CHOLESKY_JITTER, CHOLESKY_MAX_TRIES, NotPSDError, cholesky_factor
-from .kernel import STATIONARY_KERNELS, BaseKernel, MaternKernel, PeriodicKernel, _dev
+from .kernel import STATIONARY_KERNELS, BaseKernel, LocallyPeriodicKernel, MaternKernel, PeriodicKernel, _dev
 from .likelihoods import GaussianLikelihood, _Likelihood
 from .trainers import EarlyStopper
 from .utils import set_seed
@@ -63,8 +63,8 @@ def _kernel_choice(who: str, kernel, nu: float, ard: bool, d: int):
         start, family = kernel, _FAMILIES[kernel.family]
         nu = getattr(kernel, "nu", nu)
         ard = kernel.lengthscale.numel() > 1 or d == 1 and ard
-        if family.shape_per_dim:  # per-dimension shape values need per-dimension raw values too
-            ard = ard or getattr(kernel, family.shape_attr).numel() > 1
+        for attr, per_dim in family.shape_blocks:  # per-dimension shape values need per-dimension raw values too
+            ard = ard or per_dim and getattr(kernel, attr).numel() > 1
     else:
         if kernel not in _KERNEL_NAMES:
             raise ValueError(f"{who}: kernel must be one of {sorted(_KERNEL_NAMES)}, a kernel class or a kernel object, got {kernel!r}")
@@ -81,7 +81,9 @@ class _ExactGPClasses:
     softplus(raw)``, ``outputscale = softplus(raw)``, ``noise = 1e-4 + softplus(raw)``, the mean constant itself; every raw
     value starts at 0.  ``raw`` is seen as (C, 3 + nls + shape columns) rows: mean, raw noise, raw outputscale, the nls raw
     lengthscales (d of them, or one shared by all dimensions), then the family's raw shape values, ``softplus(raw)`` each:
-    none for RBF and Matern, raw alpha for the rational-quadratic kernel, the nls raw period lengths for the periodic kernel
+    none for RBF and Matern, raw alpha for the rational-quadratic kernel, the nls raw period lengths for the periodic kernel,
+    the nls raw periodic lengthscales and then the nls raw period lengths for the locally periodic kernel (a family's shape
+    blocks in their declared order, kernel._StationaryKernel.shape_blocks)
     -- _lib.kernel_shape_params with the nls raw lengthscales in the place of the library's d.  x (n, d), the targets (C, n)
     and the fixed noise v (C, n), or None, are kept as given and uploaded once, on the first evaluation on the device.  One
     evaluation of all classes is ONE library call with one read-back, ``pls_gp_mll_grad_classes``: 4 + d + shape
@@ -100,13 +102,22 @@ class _ExactGPClasses:
         raw = torch.zeros(targets.shape[0], 3 + nls + L.kernel_shape_params(self.kind, nls), dtype=torch.float64)
         if start is not None:
             raw[:, 2] = _inverse_softplus(torch.tensor(start.outputscale, dtype=torch.float64))
-            for name, columns in (("lengthscale", raw[:, 3:3 + nls]), (self._family.shape_attr, raw[:, 3 + nls:])):
-                if name is not None:
-                    v = torch.as_tensor(getattr(start, name), dtype=torch.float64).reshape(-1)
-                    assert v.numel() in (1, columns.shape[1]), f"the kernel's {name.replace('_', ' ')}s do not fit the data"
-                    columns[:] = _inverse_softplus(_repeated(v, columns.shape[1]))
+            for name, columns, _ in self._raw_blocks():
+                v = torch.as_tensor(getattr(start, name), dtype=torch.float64).reshape(-1)
+                assert v.numel() in (1, raw[:, columns].shape[1]), f"the kernel's {name.replace('_', ' ')}s do not fit the data"
+                raw[:, columns] = _inverse_softplus(_repeated(v, raw[:, columns].shape[1]))
         self.raw = torch.nn.Parameter(raw)
         self._dev: dict = {}
+
+    def _raw_blocks(self) -> list:
+        """[(attribute, its columns of ``raw``, per_dim)]: the lengthscale block, then the family's shape blocks in their
+        declared order; a per-dimension block has nls columns and the library reads d values of it, any other has one"""
+        blocks, at = [], 3
+        for name, per_dim in (("lengthscale", True),) + tuple(self._family.shape_blocks):
+            width = self._nls if per_dim else 1
+            blocks.append((name, slice(at, at + width), per_dim))
+            at += width
+        return blocks
 
     # ---- parameters -------------------------------------------------------------------------------------------------
     def raw_parameters(self) -> torch.Tensor:
@@ -127,13 +138,16 @@ class _ExactGPClasses:
         return raw[:, 0].clone(), NOISE_LOWER_BOUND + _softplus(raw[:, 1]), _softplus(raw[:, 2]), ls
 
     def _shape(self, attr: str | None = None) -> torch.Tensor:
-        """(C, shape parameters) the family's shape values as the library reads and differentiates them, softplus(raw) with
-        a value shared by all dimensions repeated; (C, 0) for a family without.  ``attr``: the public property that asks;
-        AttributeError when the family's shape is not called that"""
-        if attr is not None and attr != self._family.shape_attr:
+        """(C, shape parameters) the family's shape values as the library reads and differentiates them, block after block:
+        softplus(raw) with a value shared by all dimensions repeated within its block; (C, 0) for a family without.
+        ``attr``: the public property that asks, and gets its block alone; AttributeError when the family has no block of
+        that name"""
+        if attr is not None and attr not in dict(self._family.shape_blocks):
             raise AttributeError(f"the {self.kernel_name} kernel has no {attr}")
         raw = self.raw.detach().reshape(self._targets.shape[0], -1)
-        return _repeated(_softplus(raw[:, 3 + self._nls:]), L.kernel_shape_params(self.kind, self.d))
+        blocks = [_repeated(_softplus(raw[:, columns]), self.d if per_dim else 1)
+                  for name, columns, per_dim in self._raw_blocks()[1:] if attr in (None, name)]
+        return torch.cat(blocks, dim=1) if blocks else raw[:, :0].clone()
 
     @property
     def alpha(self) -> torch.Tensor:
@@ -142,8 +156,15 @@ class _ExactGPClasses:
 
     @property
     def period_length(self) -> torch.Tensor:
-        """(C, d) the period lengths of the periodic kernel (a shared one repeated); AttributeError for the other kernels"""
+        """(C, d) the period lengths of the periodic and the locally periodic kernel (a shared one repeated); AttributeError
+        for the other kernels"""
         return self._shape("period_length")
+
+    @property
+    def periodic_lengthscale(self) -> torch.Tensor:
+        """(C, d) the lengthscales of the locally periodic kernel's periodic factor (a shared one repeated); AttributeError
+        for the other kernels"""
+        return self._shape("periodic_lengthscale")
 
     def _library_lengthscale(self) -> torch.Tensor:
         """(C, d + shape parameters): the lengthscales, then the shape values, as the library reads them"""
@@ -169,9 +190,11 @@ class _ExactGPClasses:
 
     def _make_kernel(self, lengthscale: torch.Tensor, outputscale: float, shape: torch.Tensor) -> BaseKernel:
         """``shape``: the family's shape values (a row of ``_shape()``; empty for a family without)"""
-        keywords = {} if self.nu is None else {"nu": self.nu}
-        if self._family.shape_attr is not None:
-            keywords[self._family.shape_attr] = shape
+        keywords, at = {} if self.nu is None else {"nu": self.nu}, 0
+        for name, per_dim in self._family.shape_blocks:
+            width = self.d if per_dim else 1
+            keywords[name] = shape[at:at + width]
+            at += width
         return self._family(lengthscale, outputscale, **keywords)
 
     def _class_kernel(self, c: int) -> BaseKernel:
@@ -185,7 +208,7 @@ class _ExactGPClasses:
         parameters) outputs of pls_gp_mll_grad_classes (per class: value, d/d mean, d/d noise, d/d log outputscale,
         d/d log lengthscale_k, then d/d log of every shape value) at the current parameters: host arithmetic only.  The
         derivatives of a raw value that the library reads repeated, once per dimension (``ard=False``: the shared
-        lengthscale, the shared period length), are summed."""
+        lengthscale, the shared period length), are summed, block by block."""
         raw = self.raw.detach().reshape(self._targets.shape[0], -1)
         out = torch.as_tensor(out, dtype=torch.float64)
         assert out.numel() == raw.shape[0] * self._outputs
@@ -195,12 +218,13 @@ class _ExactGPClasses:
         g[:, 0] = out[:, 1]
         g[:, 1] = out[:, 2] * slope[:, 1]
         g[:, 2] = out[:, 3] / _softplus(raw[:, 2]) * slope[:, 2]
-        split = 3 + self._nls
-        for columns, d_log, natural in ((slice(3, split), out[:, 4:4 + self.d], self._natural()[3]),
-                                        (slice(split, None), out[:, 4 + self.d:], self._shape())):
-            d_natural = d_log / natural
-            shared = d_natural.shape[1] != g[:, columns].shape[1]
+        natural, at = self._library_lengthscale(), 0
+        for _, columns, per_dim in self._raw_blocks():
+            width = self.d if per_dim else 1
+            d_natural = out[:, 4 + at:4 + at + width] / natural[:, at:at + width]
+            shared = width != g[:, columns].shape[1]
             g[:, columns] = (d_natural.sum(dim=1, keepdim=True) if shared else d_natural) * slope[:, columns]
+            at += width
         return -float(out[:, 0].sum()) / self.n, (-g / self.n).reshape(self.raw.shape)
 
     @property
@@ -287,11 +311,13 @@ class ExactGP(_ExactGPClasses):
         raw[1]   raw noise
         raw[2]   raw outputscale
         raw[3:3 + nls]  raw lengthscales: nls = d of them (``ard=True``) or one shared by all dimensions (``ard=False``)
-        raw[3 + nls:]   the family's raw shape values: raw alpha (rational quadratic), the nls raw period lengths (periodic)
+        raw[3 + nls:]   the family's raw shape values: raw alpha (rational quadratic), the nls raw period lengths (periodic),
+                        the nls raw periodic lengthscales and then the nls raw period lengths (locally periodic)
 
     ``kernel``: "rbf", "rq" or "matern" (with ``nu``); "matern12" / "matern32" / "matern52" name nu as well; one of the classes
-    kernel.STATIONARY_KERNELS names its family likewise (the periodic family has no name here:
-    ``kernel=PeriodicKernel``; ``train_exact_gp`` and ``exact_gp_runner`` take "periodic"); an instance of them gives the kind and the starting values (as the reference's ``deepcopy(kernel)``).
+    kernel.STATIONARY_KERNELS names its family likewise (the periodic and the locally periodic family have no name here:
+    ``kernel=PeriodicKernel``, ``kernel=LocallyPeriodicKernel``; ``train_exact_gp`` and ``exact_gp_runner`` take "periodic"
+    and "locally_periodic"); an instance of them gives the kind and the starting values (as the reference's ``deepcopy(kernel)``).
     x (n, d) and y (n) are kept as given."""
 
     def __init__(self, x: torch.Tensor, y: torch.Tensor, kernel="rbf", nu: float = 2.5, ard: bool = True):
@@ -329,8 +355,15 @@ class ExactGP(_ExactGPClasses):
 
     @property
     def period_length(self) -> torch.Tensor:
-        """the d period lengths of the periodic kernel (a shared one repeated); AttributeError for the other kernels"""
+        """the d period lengths of the periodic and the locally periodic kernel (a shared one repeated); AttributeError for
+        the other kernels"""
         return self._shape("period_length")[0]
+
+    @property
+    def periodic_lengthscale(self) -> torch.Tensor:
+        """the d lengthscales of the locally periodic kernel's periodic factor (a shared one repeated); AttributeError for the
+        other kernels"""
+        return self._shape("periodic_lengthscale")[0]
 
     @property
     def kernel(self) -> BaseKernel:
@@ -866,9 +899,10 @@ def train_exact_gp(x: torch.Tensor, y: torch.Tensor, kernel, seed: int, number_o
     (loss, gradient)`` replaces ``model.loss_and_grad`` (a host evaluation drives the same loop without a device).
     ``likelihood="dirichlet"``: y holds integer labels and the model is a DirichletExactGP (``number_of_classes`` and
     ``fixed_noise`` go to it); the loss is then summed over the classes, as the reference's ``.sum()`` over the batch.
-    ``kernel``: as the model classes take it, and also "periodic" (the model classes' ``kernel=PeriodicKernel``)."""
+    ``kernel``: as the model classes take it, and also "periodic" and "locally_periodic" (the model classes'
+    ``kernel=PeriodicKernel`` and ``kernel=LocallyPeriodicKernel``)."""
     set_seed(seed)
-    kernel = PeriodicKernel if isinstance(kernel, str) and kernel == "periodic" else kernel
+    kernel = {"periodic": PeriodicKernel, "locally_periodic": LocallyPeriodicKernel}.get(kernel, kernel) if isinstance(kernel, str) else kernel
     if likelihood == "gaussian":
         model = ExactGP(x, y, kernel)
     elif likelihood == "dirichlet":
@@ -894,16 +928,14 @@ def train_exact_gp(x: torch.Tensor, y: torch.Tensor, kernel, seed: int, number_o
 def construct_average_ard_kernel(models: Sequence[ExactGP]) -> BaseKernel:
     """The kernel of the AVERAGED RAW parameters, softplus applied afterwards (constructors.py:28-53 averages the
     entries of ``state_dict()``, which are the raw values).  A DirichletExactGP holds one row of raw values per class: its
-    rows are averaged first (the reference's ``mean(dim=0)`` over the batch), then the models.  The family's raw shape
-    values (raw alpha, the raw period lengths) are averaged like the raw lengthscales and the result is a kernel of the
-    models' family."""
+    rows are averaged first (the reference's ``mean(dim=0)`` over the batch), then the models.  Every block of the family's
+    raw shape values (raw alpha, the raw period lengths, the raw periodic lengthscales) is averaged like the raw lengthscales
+    and the result is a kernel of the models' family."""
     first = models[0]
     per_model = [m.raw_parameters() for m in models]
-    raw = torch.stack([(r.mean(dim=0) if r.dim() == 2 else r)[2:] for r in per_model]).mean(dim=0)
-    split = 1 + first._nls
-    ls = _repeated(_softplus(raw[1:split]), first.d)
-    shape = _repeated(_softplus(raw[split:]), L.kernel_shape_params(first.kind, first.d))
-    return first._make_kernel(ls, float(_softplus(raw[0])), shape)
+    raw = torch.stack([r.mean(dim=0) if r.dim() == 2 else r for r in per_model]).mean(dim=0)
+    blocks = [_repeated(_softplus(raw[columns]), first.d if per_dim else 1) for _, columns, per_dim in first._raw_blocks()]
+    return first._make_kernel(blocks[0], float(_softplus(raw[2])), torch.cat(blocks[1:]) if blocks[1:] else raw[:0])
 
 
 def construct_average_gaussian_noise(models: Sequence[ExactGP]) -> float:

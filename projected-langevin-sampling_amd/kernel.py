@@ -2,9 +2,9 @@
 
 The reference takes a gpytorch kernel object; gpytorch is a host-side hyper-parameter container there.
 Here kernels are plain parameter holders whose Gram matrices are built by libplship on the MI355X.
-A gpytorch ScaleKernel(RBFKernel), ScaleKernel(MaternKernel), ScaleKernel(RQKernel) or ScaleKernel(PeriodicKernel) instance
-is accepted wherever a base kernel is expected: its lengthscale / outputscale (and nu, alpha or period_length) are read
-once (``as_base_kernel``)."""
+A gpytorch ScaleKernel(RBFKernel), ScaleKernel(MaternKernel), ScaleKernel(RQKernel), ScaleKernel(PeriodicKernel) or
+ScaleKernel(RBFKernel * PeriodicKernel) instance is accepted wherever a base kernel is expected: its lengthscale /
+outputscale (and nu, alpha or period_length) are read once (``as_base_kernel``)."""
 from __future__ import annotations
 
 import torch
@@ -54,15 +54,16 @@ class BaseKernel:
 class _StationaryKernel(BaseKernel):
     """Holds per-dimension (or one shared) lengthscales and the outputscale; what the library reads is cached per D on the
     device.  A subclass declares its family: ``family`` is its name as the exact-GP classes and trainers take it,
-    ``shape_attr`` the attribute that holds the shape values the library reads behind the d lengthscales
-    (_lib.kernel_shape_params of them; None: the family has none), ``shape_per_dim`` whether that attribute holds one value
-    per dimension (or one shared by all), as the lengthscale does; ``keyword`` the constructor's argument beyond the
-    lengthscale and the outputscale, which a gpytorch kernel of the family carries as an attribute of the same name."""
+    ``shape_blocks`` the ordered (attribute, per_dim) pairs of the shape values the library reads behind the d lengthscales,
+    block after block (_lib.kernel_shape_params of them in all; empty: the family has none): the attribute that holds a
+    block, which is also the constructor's argument for it, and whether it holds one value per dimension (or one shared by
+    all), as the lengthscale does; ``keyword`` the constructor's argument beyond the lengthscale and the outputscale which a
+    gpytorch kernel of the family carries as an attribute of the same name (None: ``as_base_kernel`` does not find the
+    family that way)."""
 
     family: str
     keyword: str | None = None
-    shape_attr: str | None = None
-    shape_per_dim: bool = False
+    shape_blocks: tuple = ()
 
     def __init__(self, lengthscale, outputscale: float = 1.0):
         self.lengthscale = torch.as_tensor(lengthscale, dtype=torch.float64).reshape(-1).cpu()
@@ -70,12 +71,10 @@ class _StationaryKernel(BaseKernel):
         self._ls_dev: dict[int, torch.Tensor] = {}
 
     def _lengthscale_host(self, d: int) -> torch.Tensor:
-        """the d + kernel_shape_params(kind, d) values the library reads: the lengthscales, then the shape values (a value
-        shared by all dimensions repeated)"""
+        """the d + kernel_shape_params(kind, d) values the library reads: the lengthscales, then the shape blocks in their
+        declared order (a value shared by all dimensions repeated per block)"""
         parts = []
-        for name, per_dim in (("lengthscale", True), (self.shape_attr, self.shape_per_dim)):
-            if name is None:
-                continue
+        for name, per_dim in (("lengthscale", True),) + tuple(self.shape_blocks):
             v = torch.as_tensor(getattr(self, name), dtype=torch.float64).reshape(-1)
             if per_dim:
                 v = v.expand(d) if v.numel() == 1 else v
@@ -123,7 +122,7 @@ class RQKernel(_StationaryKernel):
     ARDKernel; the library reads alpha behind the lengthscales, so the device array has d + 1 entries."""
 
     kind, family = L.KERNEL_RQ, "rq"
-    keyword = shape_attr = "alpha"
+    keyword, shape_blocks = "alpha", (("alpha", False),)
 
     def __init__(self, lengthscale, outputscale: float = 1.0, alpha: float = 1.0):
         alpha = float(torch.as_tensor(alpha, dtype=torch.float64).detach().reshape(-1)[0])  # (gpytorch's: a one-element tensor)
@@ -142,8 +141,7 @@ class PeriodicKernel(_StationaryKernel):
     entries.  d <= 16."""
 
     kind, family = L.KERNEL_PERIODIC, "periodic"
-    keyword = shape_attr = "period_length"
-    shape_per_dim = True
+    keyword, shape_blocks = "period_length", (("period_length", True),)
 
     def __init__(self, lengthscale, outputscale: float = 1.0, period_length=1.0):
         period = torch.as_tensor(period_length, dtype=torch.float64).detach().reshape(-1).cpu()
@@ -155,6 +153,28 @@ class PeriodicKernel(_StationaryKernel):
         self.period_length = period
 
 
+class LocallyPeriodicKernel(_StationaryKernel):
+    """ScaleKernel(RBFKernel(ard_num_dims=D) * PeriodicKernel(ard_num_dims=D)), the locally periodic (quasi-periodic) kernel: a
+    periodic kernel under an RBF envelope, so that the repeating shape may drift.  With e_d = (a_d - b_d) / period_length_d,
+    k(a,b) = outputscale * exp(-(1/2 sum_d ((a_d - b_d) / lengthscale_d)^2 + 2 sum_d sin^2(pi e_d) / periodic_lengthscale_d)),
+    gpytorch's product as recalled (include/plship.h states the formula; it is the contract).  ``lengthscale`` is the
+    envelope's, ``periodic_lengthscale`` divides and is not squared, as PeriodicKernel's lengthscale.  Each of the three holds
+    d (or one shared) positive values; the library reads them in that order, so the device array has 3 d entries.  d <= 16."""
+
+    kind, family = L.KERNEL_LOCALLY_PERIODIC, "locally_periodic"
+    shape_blocks = (("periodic_lengthscale", True), ("period_length", True))
+
+    def __init__(self, lengthscale, outputscale: float = 1.0, periodic_lengthscale=1.0, period_length=1.0):
+        super().__init__(lengthscale, outputscale)
+        values = {"lengthscale": self.lengthscale}
+        for name, given in (("periodic_lengthscale", periodic_lengthscale), ("period_length", period_length)):
+            values[name] = torch.as_tensor(given, dtype=torch.float64).detach().reshape(-1).cpu()
+        for name, v in values.items():
+            if v.numel() == 0 or not bool((v > 0.0).all()):
+                raise ValueError(f"LocallyPeriodicKernel: every {name.replace('_', ' ')} must be positive, got {v.tolist()}")
+        self.periodic_lengthscale, self.period_length = values["periodic_lengthscale"], values["period_length"]
+
+
 class LinearKernel(BaseKernel):
     """k(x1, x2) = x1 x2^T: the reference's test double (mockers/kernel.py:8-23)."""
 
@@ -162,19 +182,32 @@ class LinearKernel(BaseKernel):
 
 
 #: the stationary families, in the order ``as_base_kernel`` asks a gpytorch kernel for their keywords: nu, alpha, period_length
-STATIONARY_KERNELS = (ARDKernel, MaternKernel, RQKernel, PeriodicKernel)
-#: "ARDKernel / MaternKernel / RQKernel / PeriodicKernel", as the error messages of the package list them
+STATIONARY_KERNELS = (ARDKernel, MaternKernel, RQKernel, PeriodicKernel, LocallyPeriodicKernel)
+#: "ARDKernel / MaternKernel / RQKernel / PeriodicKernel / LocallyPeriodicKernel", as the error messages of the package list them
 STATIONARY_KERNEL_NAMES = " / ".join(cls.__name__ for cls in STATIONARY_KERNELS)
 
 
 def as_base_kernel(kernel) -> BaseKernel:
     """Accept our kernels, or read the hyper-parameters of a gpytorch ScaleKernel(RBFKernel), ScaleKernel(MaternKernel) (an
     inner kernel with a ``nu`` attribute; nu outside {0.5, 1.5, 2.5} raises ValueError), ScaleKernel(RQKernel) (an inner
-    kernel with an ``alpha`` attribute) or ScaleKernel(PeriodicKernel) (an inner kernel with a ``period_length`` attribute)."""
+    kernel with an ``alpha`` attribute), ScaleKernel(PeriodicKernel) (an inner kernel with a ``period_length`` attribute) or
+    ScaleKernel(RBFKernel * PeriodicKernel) (gpytorch's product as recalled: an inner kernel with a ``kernels`` sequence of
+    two members that both have a ``lengthscale``, exactly one of them a ``period_length``; the other, which must have none of
+    ``nu``, ``alpha`` and ``period_length``, is the envelope)."""
     if isinstance(kernel, BaseKernel):
         return kernel
     inner = getattr(kernel, "base_kernel", None)
-    if inner is not None and hasattr(inner, "lengthscale") and hasattr(kernel, "outputscale"):
+    members = getattr(inner, "kernels", None)
+    if members is not None and hasattr(kernel, "outputscale"):
+        members = list(members)
+        periodic = [m for m in members if hasattr(m, "period_length")]
+        envelope = [m for m in members if not any(hasattr(m, cls.keyword) for cls in STATIONARY_KERNELS if cls.keyword)]  # (no nu, alpha, period_length: RBF)
+        if len(members) == 2 and len(periodic) == len(envelope) == 1 and all(getattr(m, "lengthscale", None) is not None for m in members):
+            envelope = envelope[0]
+            flat = lambda v: torch.as_tensor(v).detach().reshape(-1)  # noqa: E731
+            return LocallyPeriodicKernel(lengthscale=flat(envelope.lengthscale), outputscale=float(torch.as_tensor(kernel.outputscale).detach()),
+                                         periodic_lengthscale=flat(periodic[0].lengthscale), period_length=flat(periodic[0].period_length))
+    elif inner is not None and hasattr(inner, "lengthscale") and hasattr(kernel, "outputscale"):
         lengthscale = torch.as_tensor(inner.lengthscale).detach().reshape(-1)
         outputscale = float(torch.as_tensor(kernel.outputscale).detach())
         for cls in STATIONARY_KERNELS:

@@ -24,7 +24,8 @@ import projected_langevin_sampling_amd as pkg  # noqa: E402
 
 L = pkg._lib
 F64 = torch.float64
-KINDS = {"rbf": L.KERNEL_RBF_ARD, "matern52": L.KERNEL_MATERN52, "rq": L.KERNEL_RQ, "periodic": L.KERNEL_PERIODIC}
+KINDS = {"rbf": L.KERNEL_RBF_ARD, "matern52": L.KERNEL_MATERN52, "rq": L.KERNEL_RQ, "periodic": L.KERNEL_PERIODIC,
+         "locally_periodic": L.KERNEL_LOCALLY_PERIODIC}
 RQ_ALPHA = math.log(2.0)  # behind the lengthscales in the library's array; its derivative is the last output
 
 
@@ -45,10 +46,14 @@ def timed(fn, repeats):
 
 def probe_kernel(kind, d, g):
     """The kernel whose parameters are timed: lengthscales (0.5 + U) sqrt(d), drawn for every kind; RQ: alpha = ln 2; periodic:
-    lengthscales (0.5 + U) d and period lengths 0.5 + 2.5 U, drawn after them."""
+    lengthscales (0.5 + U) d and period lengths 0.5 + 2.5 U, drawn after them; locally periodic: the periodic kind's draws under
+    envelope lengthscales (1 + U) sqrt(d), drawn last."""
     ls = (0.5 + torch.rand(d, generator=g, dtype=F64)) * d**0.5
-    if kind == L.KERNEL_PERIODIC:
-        return pkg.PeriodicKernel((0.5 + torch.rand(d, generator=g, dtype=F64)) * d, period_length=0.5 + 2.5 * torch.rand(d, generator=g, dtype=F64))
+    if kind in (L.KERNEL_PERIODIC, L.KERNEL_LOCALLY_PERIODIC):
+        lam, period = (0.5 + torch.rand(d, generator=g, dtype=F64)) * d, 0.5 + 2.5 * torch.rand(d, generator=g, dtype=F64)
+        if kind == L.KERNEL_PERIODIC:
+            return pkg.PeriodicKernel(lam, period_length=period)
+        return pkg.LocallyPeriodicKernel((1.0 + torch.rand(d, generator=g, dtype=F64)) * d**0.5, periodic_lengthscale=lam, period_length=period)
     return {L.KERNEL_RBF_ARD: pkg.ARDKernel(ls), L.KERNEL_MATERN52: pkg.MaternKernel(ls, nu=2.5), L.KERNEL_RQ: pkg.RQKernel(ls, alpha=RQ_ALPHA)}[kind]
 
 
@@ -113,11 +118,13 @@ def torch_route(kind, x, y, ls, s, noise, mean, repeats):
     leaves = [torch.tensor(v, dtype=F64, device="cuda", requires_grad=True) for v in (mean, noise, math.log(s))]
     log_ls = ls[:d].log().clone().requires_grad_(True)
     log_alpha = torch.tensor(math.log(RQ_ALPHA), dtype=F64, device="cuda", requires_grad=True)
-    log_p = (ls[d:2 * d] if kind == L.KERNEL_PERIODIC else ls[:d]).log().clone().requires_grad_(True)  # (periodic only)
+    local = kind == L.KERNEL_LOCALLY_PERIODIC  # (l, lambda, p in blocks of d; log_ls is then the envelope's)
+    log_p = (ls[2 * d:] if local else ls[d:2 * d] if kind == L.KERNEL_PERIODIC else ls[:d]).log().clone().requires_grad_(True)  # (periodic kinds only)
+    log_lam = (ls[d:2 * d] if local else ls[:d]).log().clone().requires_grad_(True)  # (locally periodic only)
     result = {}
 
     def run():
-        for t in leaves + [log_ls, log_alpha, log_p]:
+        for t in leaves + [log_ls, log_alpha, log_p, log_lam]:
             t.grad = None
         e2 = torch.zeros((n, n), dtype=F64, device="cuda")
         for k in range(d):
@@ -125,9 +132,13 @@ def torch_route(kind, x, y, ls, s, noise, mean, repeats):
                 e = (x[:, k][:, None] - x[:, k][None, :]) / log_p[k].exp()
                 e2 = e2 + 2.0 * torch.sin(math.pi * e).square() / log_ls[k].exp()
                 continue
+            if local:  # (the negated exponent again, the envelope's share added)
+                delta = x[:, k][:, None] - x[:, k][None, :]
+                e2 = e2 + 0.5 * (delta / log_ls[k].exp()).square() + 2.0 * torch.sin(math.pi * delta / log_p[k].exp()).square() / log_lam[k].exp()
+                continue
             a = x[:, k] / log_ls[k].exp()
             e2 = e2 + (a[:, None] - a[None, :]).square()
-        if kind == L.KERNEL_PERIODIC:
+        if kind == L.KERNEL_PERIODIC or local:
             kap = torch.exp(-e2)
         elif kind == L.KERNEL_RBF_ARD:
             kap = torch.exp(-0.5 * e2)
@@ -143,7 +154,7 @@ def torch_route(kind, x, y, ls, s, noise, mean, repeats):
         alpha = torch.cholesky_solve(r[:, None], low)[:, 0]
         mll = -0.5 * r @ alpha - torch.log(low.diagonal()).sum() - 0.5 * n * math.log(2.0 * math.pi)
         mll.backward()
-        tail = [log_alpha.grad.reshape(1)] if kind == L.KERNEL_RQ else [log_p.grad] if kind == L.KERNEL_PERIODIC else []
+        tail = [log_alpha.grad.reshape(1)] if kind == L.KERNEL_RQ else [log_p.grad] if kind == L.KERNEL_PERIODIC else [log_lam.grad, log_p.grad] if local else []
         result["out"] = torch.cat([mll.detach().reshape(1), torch.stack([t.grad for t in leaves]), log_ls.grad] + tail)
 
     return timed(run, repeats), result["out"].cpu()
@@ -155,15 +166,16 @@ def main():
     ap.add_argument("--sizes", type=int, nargs="+", default=[2000, 5000])
     ap.add_argument("--dims", type=int, nargs="+", default=[2, 8])
     ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--kinds", nargs="+", default=list(KINDS), choices=list(KINDS))
     args = ap.parse_args()
     assert torch.cuda.is_available(), "the probe needs the MI355X"
     lines = [f"# tools/gp_mll_probe.py on {torch.cuda.get_device_name(0)}: one exact-GP marginal-likelihood evaluation, milliseconds",
              f"# (device events, median of {args.repeats} after a warm-up call); product+small = whole - the other stages",
              "# torch = the same value and gradient by torch.linalg.cholesky + autograd, fp64, same card; agree = the largest",
              "# difference of the 4 + d outputs relative to the largest output",
-             f"{'kind':9s} {'n':>5s} {'d':>2s} {'whole':>8s} {'gram':>7s} {'factor':>7s} {'solve':>7s} {'inverse':>7s} {'product+small':>13s} "
+             f"{'kind':16s} {'n':>5s} {'d':>2s} {'whole':>8s} {'gram':>7s} {'factor':>7s} {'solve':>7s} {'inverse':>7s} {'product+small':>13s} "
              f"{'reduction':>9s} {'red/whole':>9s} {'torch':>8s} {'torch/whole':>11s} {'agree':>8s}"]
-    for name, kind in KINDS.items():
+    for name, kind in ((k, KINDS[k]) for k in args.kinds):
         for n in args.sizes:
             for d in args.dims:
                 g = torch.Generator().manual_seed(n + d)
@@ -171,7 +183,7 @@ def main():
                 y = (torch.sin(x.sum(dim=1)) + 0.3 * torch.randn(n, generator=g, dtype=F64).cuda()).contiguous()
                 ls = probe_kernel(kind, d, g)._lengthscale_host(d).cuda()
                 res, out = library_stages(kind, x, y, ls, 1.3, 0.1, 0.2, args.repeats)
-                row = (f"{name:9s} {n:5d} {d:2d} {res['whole']:8.3f} {res['gram']:7.3f} {res['factor']:7.3f} {res['solve']:7.3f} "
+                row = (f"{name:16s} {n:5d} {d:2d} {res['whole']:8.3f} {res['gram']:7.3f} {res['factor']:7.3f} {res['solve']:7.3f} "
                        f"{res['inverse']:7.3f} {res['product+small']:13.3f} {res['reduction']:9.3f} "
                        f"{res['reduction'] / res['whole']:9.3f}")
                 try:

@@ -5,8 +5,9 @@
   fused         pls_kernel_mean: out = c + s sum_j kappa(x*_i, x_j) alpha_j, no matrix
   materialised  pls_kernel_gram into an n x t plane, then pls_gemm_tn (plane^T alpha): what ExactGP.predict does for its mean
 
-for RBF, Matern-5/2, the rational-quadratic kernel (alpha = ln 2) and the periodic kernel (lengthscales (0.5 + U) d, period
-lengths 0.5 + 2.5 U) at (n, t, d) = (500, 1000, 1), (2000, 6500, 8), (5000, 36000, 8).  After a warm-up of each route the
+for RBF, Matern-5/2, the rational-quadratic kernel (alpha = ln 2), the periodic kernel (lengthscales (0.5 + U) d, period
+lengths 0.5 + 2.5 U) and the locally periodic kernel (the periodic kernel's parameters under envelope lengthscales
+(1 + U) sqrt(d)) at (n, t, d) = (500, 1000, 1), (2000, 6500, 8), (5000, 36000, 8).  After a warm-up of each route the
 timed calls alternate between the routes, each between its own pair of HIP events on torch's stream (the protocol of
 tools/matern_gram_probe.py), so that drifts of clock or temperature fall on both alike.  Prints per route the median and
 the 10th-90th percentile, the largest |fused - materialised| relative to the outputscale, the peak device memory of each
@@ -22,7 +23,8 @@ import torch
 import projected_langevin_sampling_amd as pkg
 
 L = pkg._lib
-KINDS = {L.KERNEL_RBF_ARD: "rbf", L.KERNEL_MATERN52: "matern52", L.KERNEL_RQ: "rq", L.KERNEL_PERIODIC: "periodic"}
+KINDS = {L.KERNEL_RBF_ARD: "rbf", L.KERNEL_MATERN52: "matern52", L.KERNEL_RQ: "rq", L.KERNEL_PERIODIC: "periodic",
+         L.KERNEL_LOCALLY_PERIODIC: "locally_periodic"}
 SHAPES = [(500, 1000, 1), (2000, 6500, 8), (5000, 36000, 8)]
 S, MEAN = 1.7, 0.3
 
@@ -44,9 +46,12 @@ def main():
         xt = torch.randn(t, d, generator=g, dtype=torch.float64).cuda()
         ls = (0.5 + torch.rand(d, generator=g, dtype=torch.float64)) * d**0.5
         alpha = torch.randn(n, generator=g, dtype=torch.float64).cuda()
+        lam = (0.5 + torch.rand(d, generator=g, dtype=torch.float64)) * d
+        period = 0.5 + 2.5 * torch.rand(d, generator=g, dtype=torch.float64)
+        envelope = (1.0 + torch.rand(d, generator=g, dtype=torch.float64)) * d**0.5
         kernels = [pkg.ARDKernel(ls), pkg.MaternKernel(ls, nu=2.5), pkg.RQKernel(ls, alpha=0.6931471805599453),
-                   pkg.PeriodicKernel((0.5 + torch.rand(d, generator=g, dtype=torch.float64)) * d,
-                                      period_length=0.5 + 2.5 * torch.rand(d, generator=g, dtype=torch.float64))]
+                   pkg.PeriodicKernel(lam, period_length=period),
+                   pkg.LocallyPeriodicKernel(envelope, periodic_lengthscale=lam, period_length=period)]
         for kernel in kernels:
             kind, kind_name = kernel.kind, KINDS[kernel.kind]
             ls = kernel._lengthscale_host(d).cuda()  # (the lengthscales, then the family's shape values)
