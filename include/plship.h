@@ -89,7 +89,34 @@ typedef enum {
  * negated sum.  So kappa is exactly 1 at distance 0, k is exactly symmetric, and k does not change by a bit under a
  * translation of all points that is exact in fp64.  A pair whose exponent is below -745.2 is exactly 0 and skipped in every
  * sum.  A non-finite difference gives NaN.  NOT guaranteed, unlike PERIODIC: kappa = 1 a whole number of periods apart -- the
- * envelope forbids it. */
+ * envelope forbids it.
+ * TREND_SEASONAL: gpytorch ScaleKernel(RBFKernel(ard_num_dims = d)) + ScaleKernel(RBFKernel(ard_num_dims = d) *
+ * PeriodicKernel(ard_num_dims = d)) AS RECALLED, a slow trend ADDED to a locally periodic seasonal part -- a reading, not a run
+ * of gpytorch; the formula here is the contract and it is what the tests hold.  An addition within ABI 7 (no export is added
+ * or changed); its value is 12, because 11 stays a value that every entry refuses as unknown, like 5, 7 and 9.  The sum is ONE
+ * kind whose second outputscale is a shape value.  With trend lengthscales l_k > 0, the seasonal term's envelope lengthscales
+ * m_k > 0, periodic lengthscales lambda_k > 0 (they divide and are not squared), period lengths p_k > 0, e_k = (a_k - b_k) / p_k,
+ * the trend outputscale s_t (the `outputscale` argument of every entry) and the seasonal outputscale s_s > 0:
+ *   kappa_t = exp(-1/2 sum_k ((a_k - b_k) / l_k)^2)
+ *   kappa_s = exp(-(1/2 sum_k ((a_k - b_k) / m_k)^2 + 2 sum_k sin^2(pi e_k) / lambda_k))          (LOCALLY_PERIODIC's kappa)
+ *   k                      = s_t * kappa_t + s_s * kappa_s
+ *   dk / d log l_k         = s_t * kappa_t * ((a_k - b_k) / l_k)^2
+ *   dk / d log m_k, d log lambda_k, d log p_k = LOCALLY_PERIODIC's three, with s_s * kappa_s in front
+ *   dk / d log s_s         = s_s * kappa_s
+ * For this kind EVERY `lengthscale` argument of this header points to 4 d + 1 doubles: the d trend lengthscales l_k, then the d
+ * envelope lengthscales m_k, then the d periodic lengthscales lambda_k, then the d period lengths p_k, then s_s
+ * (pls_gp_mll_grad_classes: 4 d + 1 per class), and 1 <= d <= 8: the reduction carries 4 d + 2 accumulators per thread, at 8
+ * fewer than LOCALLY_PERIODIC carries at 16.  A larger d is refused ("> 8 is not supported for the trend-plus-seasonal
+ * kernel") and the workspace queries return 0 for it.  The reduction returns 4 d + 2 sums in the order kappa_t, l, m, lambda,
+ * p, s_s, and an evaluation 4 + 4 d + 1 outputs.  Evaluation, the same in the Gram build, the gradient reduction, the fused
+ * mean and the selector: the points are not pre-scaled; per coordinate the difference first; the seasonal term is
+ * LOCALLY_PERIODIC's evaluation with (m, lambda, p), bit for bit; the trend's distance sum takes the same difference times
+ * (1 / l_k), squared and accumulated by fused multiply-add in ascending k, and one exponential of minus half of it.  Each
+ * term takes its own underflow decision: a term whose exponent is below -745.2 is exactly 0 and skipped in every sum.  The
+ * entry is fma(s_t, kappa_t, s_s * kappa_s): k(x, x) is s_t + s_s rounded once, a pair with a dead trend has exactly
+ * LOCALLY_PERIODIC's entry for (m, lambda, p, s_s), a pair with a dead seasonal term exactly s_t * kappa_t.  k is exactly
+ * symmetric and does not change by a bit under a translation of all points that is exact in fp64.  A non-finite difference
+ * gives NaN. */
 typedef enum {
   PLS_KERNEL_RBF_ARD = 0,
   PLS_KERNEL_LINEAR = 1,
@@ -98,7 +125,8 @@ typedef enum {
   PLS_KERNEL_MATERN52 = 4,
   PLS_KERNEL_RQ = 6, /* (5 is not a kind) */
   PLS_KERNEL_PERIODIC = 8, /* (7 is not a kind) */
-  PLS_KERNEL_LOCALLY_PERIODIC = 10 /* (9 is not a kind) */
+  PLS_KERNEL_LOCALLY_PERIODIC = 10, /* (9 is not a kind) */
+  PLS_KERNEL_TREND_SEASONAL = 12    /* (11 is not a kind) */
 } pls_kernel_kind;
 
 /* src/projected_langevin_sampling/costs/{gaussian,poisson,bernoulli,student_t,multimodal}.py */
@@ -424,7 +452,7 @@ int pls_timeline_end(float *ms, int32_t *tags, int32_t capacity, int32_t *count)
 
 /* out(n1 x n2) = k(x1, x2); x1 (n1 x d), x2 (n2 x d) row-major contiguous.
  * Replaces kernel.base_kernel(x1=.., x2=..) at orthonormal.py:36-41, inducing_point.py:41-46.
- * lengthscale: d values (every kind except LINEAR needs it; ignored for LINEAR); RQ: d + 1, alpha last; LOCALLY_PERIODIC: 3 d (l, lambda, p; d <= 16); PERIODIC: 2 d, the
+ * lengthscale: d values (every kind except LINEAR needs it; ignored for LINEAR); RQ: d + 1, alpha last; LOCALLY_PERIODIC: 3 d (l, lambda, p; d <= 16); TREND_SEASONAL: 4 d + 1 (l, m, lambda, p, s_s; d <= 8); PERIODIC: 2 d, the
  * period lengths behind the lengthscales, and d <= 16. */
 int pls_kernel_gram(int32_t kernel_kind, const double *x1, int64_t n1, const double *x2, int64_t n2,
                     int64_t d, const double *lengthscale, double outputscale, double *out, int64_t ldout,
@@ -554,6 +582,10 @@ int pls_tri_multiply(const double *LcT, int64_t ldlct, int64_t m, const double *
  *   out[1 + d + k] = sum_ij W_ij dK_ij / d log p_k = sum_ij W_ij s kappa (2 / lambda_k) pi e_k sin(2 pi e_k)   (PERIODIC only)
  *   LOCALLY_PERIODIC (3 d + 1 sums, kappa the product's): out[1 + k] = sum_ij W_ij s kappa ((x_ik - x_jk) / l_k)^2, then
  *       out[1 + d + k] = sum_ij W_ij dK_ij / d log lambda_k and out[1 + 2 d + k] = sum_ij W_ij dK_ij / d log p_k as PERIODIC's two
+ *   TREND_SEASONAL (4 d + 2 sums; s = s_t, the `outputscale` argument): out[0] = sum_ij W_ij kappa_t,
+ *       out[1 + k] = sum_ij W_ij s_t kappa_t ((x_ik - x_jk) / l_k)^2, out[1 + d + k], out[1 + 2 d + k] and out[1 + 3 d + k]
+ *       LOCALLY_PERIODIC's sums for its envelope lengthscale (here m_k), lambda_k and p_k with s_s kappa_s in the place of
+ *       s kappa, out[1 + 4 d] = sum_ij W_ij s_s kappa_s = sum_ij W_ij dK_ij / d log s_s; d <= 8, and 0 workspace bytes above
  * A pair with r = 0 (the diagonal, duplicated points) contributes exactly 0 to every out[1 + k]; a pair whose
  * exponential underflows contributes exactly 0 to every sum; a pair with r = 0 contributes exactly 0 to out[1 + d] too.
  * PLS_KERNEL_LINEAR is rejected.
@@ -583,7 +615,8 @@ int pls_kernel_grad_sums(int32_t kernel_kind, const double *x, int64_t n, int64_
  * Summation order (no atomics, no workspace): a workgroup owns 64 test points, one per lane; wave w of its four adds
  * the terms of the training points j = w, w + 4, w + 8, ... in ascending order into one accumulator per thread (there
  * is no cross-lane sum, so no butterfly); the four waves' sums are added as (w0 + w1) + (w2 + w3); then
- * out[i] = fma(s, sum, mean).  The split of j depends on j alone -- not on t, n, d or the position of the point in
+ * out[i] = fma(s, sum, mean) (TREND_SEASONAL: two accumulators per thread, A_t of kappa_t and A_s of kappa_s, each summed
+ * that way, and out[i] = fma(s_t, A_t, fma(s_s, A_s, mean))).  The split of j depends on j alone -- not on t, n, d or the position of the point in
  * the batch -- so out[i] is a function of xt_i and the model: a batch can be split anywhere and gives the same bits
  * (as pls_softmax_normal_mean), and two calls give the same bits.
  * t == 0 returns PLS_OK and launches nothing; n >= 1.  Nothing synchronises or allocates. */
@@ -604,6 +637,9 @@ int pls_kernel_mean(int32_t kernel_kind, const double *x, int64_t n, int64_t d, 
  *   out[4 + d + k] = d mll / d log p_k                                  (PERIODIC only: its out has 4 + 2 d doubles)
  *   LOCALLY_PERIODIC (4 + 3 d doubles): out[4 + k] = d mll / d log l_k, out[4 + d + k] = d mll / d log lambda_k,
  *       out[4 + 2 d + k] = d mll / d log p_k
+ *   TREND_SEASONAL (4 + 4 d + 1 doubles, S = 4 d + 2 sums, d <= 8): out[3] = d mll / d log s_t, out[4 + k] = d mll / d log l_k,
+ *       out[4 + d + k] = d mll / d log m_k, out[4 + 2 d + k] = d mll / d log lambda_k, out[4 + 3 d + k] = d mll / d log p_k,
+ *       out[4 + 4 d] = d mll / d log s_s
  * Steps: pls_kernel_gram, the diagonal, pls_chol_factor, pls_chol_solve, pls_chol_build_inverse, K_y^-1 = Linv^T Linv on
  * the MFMA contraction, pls_kernel_grad_sums with P = K_y^-1, a one-workgroup finishing kernel (fixed-order sums).
  * out: 4 + d doubles (RQ: 5 + d; PERIODIC: 4 + 2 d; LOCALLY_PERIODIC: 4 + 3 d), device memory or pinned host memory mapped into the device.  info (DEVICE int32): as
@@ -1023,7 +1059,7 @@ int pls_ipb_prior_energy(const pls_ipb_desc *basis, const double *U, int64_t ldu
  * (:108-113).  No N x N Gram matrix is formed (the reference builds one just to read its diagonal, :64-69).
  * indices: m int64 (device), count: 1 int64 (device) = number of points selected (m unless the threshold stopped it).
  * Nothing synchronises: the pivot of every iteration stays on the device.  Ties are broken towards the smaller index.
- * kernel_kind: any pls_kernel_kind; lengthscale: d values (every kind except LINEAR needs it; ignored for LINEAR; RQ: d + 1; PERIODIC: 2 d, d <= 16; LOCALLY_PERIODIC: 3 d, d <= 16).
+ * kernel_kind: any pls_kernel_kind; lengthscale: d values (every kind except LINEAR needs it; ignored for LINEAR; RQ: d + 1; PERIODIC: 2 d, d <= 16; LOCALLY_PERIODIC: 3 d, d <= 16; TREND_SEASONAL: 4 d + 1, d <= 8).
  * workspace: pls_select_inducing_workspace_bytes(n, m) bytes. */
 size_t pls_select_inducing_workspace_bytes(int64_t n, int64_t m);
 int pls_select_inducing_conditional_variance(int32_t kernel_kind, const double *x, int64_t n, int64_t d,

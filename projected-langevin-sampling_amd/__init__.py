@@ -10,14 +10,15 @@ from .conformalise import ConformaliseGP, ConformalisePLS, ConformalPrediction, 
 from .gaussian_process import (SVGP, DirichletExactGP, ExactGP, construct_average_ard_kernel, construct_average_gaussian_noise,
                                dirichlet_targets, estimate_student_parameters, exact_gp_runner, fit_student_t, nearest_subsample,
                                softmax_normal_mean, train_exact_gp)
-from .kernel import ARDKernel, LinearKernel, LocallyPeriodicKernel, MaternKernel, PeriodicKernel, PLSKernel, RQKernel
+from .kernel import (ARDKernel, LinearKernel, LocallyPeriodicKernel, MaternKernel, PeriodicKernel, PLSKernel, RQKernel,
+                     TrendSeasonalKernel)
 from .likelihoods import BernoulliLikelihood, GaussianLikelihood, StudentTLikelihood
 from .projected_langevin_sampling import PLS
 from .runners import train_svgp_runner
 from .temper import TemperGP
 from .trainers import EarlyStopper, epoch_batches, train_pls, train_pls_captured, train_svgp
 
-__all__ = ["PLS", "PLSKernel", "ARDKernel", "MaternKernel", "RQKernel", "PeriodicKernel", "LocallyPeriodicKernel", "LinearKernel", "EarlyStopper", "train_pls", "train_pls_captured", "ExactGP",
+__all__ = ["PLS", "PLSKernel", "ARDKernel", "MaternKernel", "RQKernel", "PeriodicKernel", "LocallyPeriodicKernel", "TrendSeasonalKernel", "LinearKernel", "EarlyStopper", "train_pls", "train_pls_captured", "ExactGP",
            "DirichletExactGP", "dirichlet_targets", "softmax_normal_mean",
            "train_exact_gp", "exact_gp_runner", "construct_average_ard_kernel", "construct_average_gaussian_noise",
            "nearest_subsample", "SVGP", "train_svgp", "train_svgp_runner", "epoch_batches", "TemperGP", "GaussianLikelihood",

@@ -17,15 +17,17 @@ KERNEL_MATERN12, KERNEL_MATERN32, KERNEL_MATERN52 = 2, 3, 4
 KERNEL_RQ = 6  # (5 is not a kind: every entry refuses it as unknown)
 KERNEL_PERIODIC = 8  # (nor is 7)
 KERNEL_LOCALLY_PERIODIC = 10  # (nor is 9)
+KERNEL_TREND_SEASONAL = 12  # (nor is 11)
 
 
 def kernel_shape_params(kind: int, d: int) -> int:
     """How many shape values follow the d lengthscales in the library's parameter array of a kind -- kind_shape_params of
     csrc/base_kernel.h: alpha for the rational-quadratic kind, the d period lengths for the periodic kind, the d periodic
-    lengthscales and then the d period lengths for the locally periodic kind.  The library
+    lengthscales and then the d period lengths for the locally periodic kind; for the trend-plus-seasonal kind the seasonal
+    term's d envelope lengthscales, d periodic lengthscales and d period lengths, then its outputscale.  The library
     differentiates with respect to each, so the gradient reduction has d + 1 + this many sums and an evaluation of the
     marginal likelihood 4 + d + this many outputs."""
-    return 1 if kind == KERNEL_RQ else d if kind == KERNEL_PERIODIC else 2 * d if kind == KERNEL_LOCALLY_PERIODIC else 0
+    return 1 if kind == KERNEL_RQ else d if kind == KERNEL_PERIODIC else 2 * d if kind == KERNEL_LOCALLY_PERIODIC else 3 * d + 1 if kind == KERNEL_TREND_SEASONAL else 0
 
 
 COST_GAUSSIAN, COST_POISSON, COST_BERNOULLI, COST_STUDENT_T, COST_MULTIMODAL = range(5)

@@ -1,11 +1,13 @@
-// The pairwise kernels of the base kernel (RBF-ARD, Matern 1/2, 3/2, 5/2, rational quadratic, periodic, locally periodic; the
-// Gram build also the linear kernel):
+// The pairwise kernels of the base kernel (RBF-ARD, Matern 1/2, 3/2, 5/2, rational quadratic, periodic, locally periodic, trend
+// plus seasonal; the Gram build also the linear kernel):
 // pls_kernel_gram, pls_kernel_grad_sums, pls_kernel_mean.  The exact-GP path builds K with the first, differentiates with
 // the second and predicts with the third, so the three evaluate a pair alike: the same pre-scaled points and distance
 // sum (base_kernel.h), the same kappa (kernel_math.h).  The periodic kind has no distance sum: unscaled points, 1 / p_k and
 // 2 / lambda_k in LDS, one sincospi per coordinate (base_kernel.h: periodic_exponent, periodic_factors).  The locally periodic
 // kind is the periodic one with the envelope's 1 / l_k as a third scale in LDS and both shares of a coordinate in the one
-// exponent (locally_periodic_exponent, locally_periodic_factors).
+// exponent (locally_periodic_exponent, locally_periodic_factors).  The trend-plus-seasonal kind adds an RBF term with its own
+// outputscale to the locally periodic one: the trend's 1 / l_k as a fourth scale in LDS, its distance sum beside the seasonal
+// exponent, two exponentials and two underflow decisions per pair (trend_seasonal_exponents, trend_seasonal_factors).
 #include <hip/hip_runtime.h>
 
 #define PLS_SCALAR_POLY_CONSTANTS 1  // (fmath.h: the exp polynomial's constants as scalar operands)
@@ -25,15 +27,17 @@ __global__ __launch_bounds__(256) void kernel_gram_kernel(const double *__restri
                                                            const double *__restrict__ x2, int64_t n2, int d,
                                                            const double *__restrict__ lengthscale, double outputscale,
                                                            double *__restrict__ out, int64_t ldout) {
-  constexpr bool PERIODIC = KIND == PLS_KERNEL_PERIODIC, LOCAL = KIND == PLS_KERNEL_LOCALLY_PERIODIC;
-  __shared__ double inv_ls[D_MAX];                        // (periodic, locally periodic: 1 / p_k)
-  __shared__ double two_inv_l[periodic_len<KIND>(D_MAX)];  // (periodic, locally periodic: 2 / lambda_k)
-  __shared__ double inv_env[envelope_len<KIND>(D_MAX)];    // (locally periodic: 1 / l_k)
+  constexpr bool PERIODIC = KIND == PLS_KERNEL_PERIODIC, LOCAL = KIND == PLS_KERNEL_LOCALLY_PERIODIC,
+                 TREND = KIND == PLS_KERNEL_TREND_SEASONAL;
+  __shared__ double inv_ls[D_MAX];                        // (the periodic kinds: 1 / p_k)
+  __shared__ double two_inv_l[periodic_len<KIND>(D_MAX)];  // (the periodic kinds: 2 / lambda_k)
+  __shared__ double inv_env[envelope_len<KIND>(D_MAX)];    // (locally periodic: 1 / l_k; trend plus seasonal: 1 / m_k)
+  __shared__ double inv_trend[trend_len<KIND>(D_MAX)];     // (trend plus seasonal: 1 / l_k)
   __shared__ __attribute__((aligned(16))) double a_s[PAIR_ROWS][D_MAX];  // rows of x1 (pre-scaled, zero-padded)
   const int t = threadIdx.x;
   const int64_t row0 = (int64_t)blockIdx.y * PAIR_ROWS;
   const int nrows = (int)((n1 - row0 < PAIR_ROWS) ? (n1 - row0) : PAIR_ROWS);
-  stage_inv_lengthscale<KIND>(inv_ls, two_inv_l, inv_env, lengthscale, d);
+  stage_inv_lengthscale<KIND>(inv_ls, two_inv_l, inv_env, inv_trend, lengthscale, d);
   const PairShape sh = load_pair_shape<KIND>(lengthscale, d);
   __syncthreads();
   stage_rows<KIND>(a_s, x1, row0, nrows, d, inv_ls);
@@ -52,7 +56,12 @@ __global__ __launch_bounds__(256) void kernel_gram_kernel(const double *__restri
 #pragma unroll 2
   for (int r = 0; r < nrows; ++r, dst += ldout) {
     double s0 = 0.0, s1 = 0.0;
-    if constexpr (PERIODIC || LOCAL) {
+    if constexpr (TREND) {
+      double q0, q1;
+      trend_seasonal_exponents(a_s[r], b0, b1, inv_trend, inv_env, inv_ls, two_inv_l, s0, q0, s1, q1);
+      s0 = trend_seasonal_entry(s0, q0, outputscale, sh.alpha);
+      s1 = trend_seasonal_entry(s1, q1, outputscale, sh.alpha);
+    } else if constexpr (PERIODIC || LOCAL) {
       if constexpr (LOCAL) locally_periodic_exponent(a_s[r], b0, b1, inv_env, inv_ls, two_inv_l, s0, s1);
       else periodic_exponent(a_s[r], b0, b1, inv_ls, two_inv_l, s0, s1);
       double kap0, kap1;
@@ -93,6 +102,9 @@ __global__ __launch_bounds__(256) void kernel_gram_kernel(const double *__restri
 //   out[1 + d + k] = sum_ij W_ij dK_ij / d log p_k     (periodic only: s kappa (2 / lambda_k) pi e_k sin(2 pi e_k))
 //   locally periodic: out[1 + k] = sum_ij W_ij s kappa ((x_ik - x_jk) / l_k)^2, out[1 + d + k] and out[1 + 2 d + k] the periodic
 //   kind's sums for lambda_k and p_k, with kappa the product's
+//   trend plus seasonal (4 D_MAX + 2 accumulators): out[0] = sum_ij W_ij kappa_t, out[1 + k] = sum_ij W_ij s_t kappa_t ((x_ik -
+//   x_jk) / l_k)^2, out[1 + d + k], out[1 + 2 d + k], out[1 + 3 d + k] the locally periodic kind's three sums of (m, lambda, p) with
+//   s_s kappa_s, out[1 + 4 d] = sum_ij W_ij s_s kappa_s
 // with W = alpha alpha^T - P; no atomics: per thread down its rows, then the workgroup sum below, then the workgroups'
 // partial rows in ascending order (a second one-workgroup launch).
 template <int KIND, int D_MAX>
@@ -100,20 +112,23 @@ __global__ __launch_bounds__(256) void kernel_grad_sums_kernel(const double *__r
                                                                 const double *__restrict__ lengthscale, double outputscale,
                                                                 const double *__restrict__ alpha, const double *__restrict__ P,
                                                                 int64_t ldp, double *__restrict__ partials) {
-  constexpr bool PERIODIC = KIND == PLS_KERNEL_PERIODIC, LOCAL = KIND == PLS_KERNEL_LOCALLY_PERIODIC;
-  __shared__ double inv_ls[D_MAX];                        // (periodic, locally periodic: 1 / p_k)
-  __shared__ double two_inv_l[periodic_len<KIND>(D_MAX)];  // (periodic, locally periodic: 2 / lambda_k)
-  __shared__ double inv_env[envelope_len<KIND>(D_MAX)];    // (locally periodic: 1 / l_k)
+  constexpr bool PERIODIC = KIND == PLS_KERNEL_PERIODIC, LOCAL = KIND == PLS_KERNEL_LOCALLY_PERIODIC,
+                 TREND = KIND == PLS_KERNEL_TREND_SEASONAL;
+  __shared__ double inv_ls[D_MAX];                        // (the periodic kinds: 1 / p_k)
+  __shared__ double two_inv_l[periodic_len<KIND>(D_MAX)];  // (the periodic kinds: 2 / lambda_k)
+  __shared__ double inv_env[envelope_len<KIND>(D_MAX)];    // (locally periodic: 1 / l_k; trend plus seasonal: 1 / m_k)
+  __shared__ double inv_trend[trend_len<KIND>(D_MAX)];     // (trend plus seasonal: 1 / l_k)
   __shared__ __attribute__((aligned(16))) double a_s[PAIR_ROWS][D_MAX];
   __shared__ double al_s[PAIR_ROWS];
   constexpr bool SHAPE = KIND == PLS_KERNEL_RQ;
   // (the shape sums are kept last: acc[D_MAX + 1 + j], written to slot d + 1 + j)
-  constexpr int NACC = D_MAX + 1 + (SHAPE ? 1 : 0) + (PERIODIC ? D_MAX : 0) + (LOCAL ? 2 * D_MAX : 0);
+  // (trend plus seasonal: the sums of l, m, lambda and p in blocks of D_MAX, then the seasonal term's own kappa sum)
+  constexpr int NACC = D_MAX + 1 + (SHAPE ? 1 : 0) + (PERIODIC ? D_MAX : 0) + (LOCAL ? 2 * D_MAX : 0) + (TREND ? 3 * D_MAX + 1 : 0);
   __shared__ double red[4][NACC];
   const int t = threadIdx.x;
   const int64_t row0 = (int64_t)blockIdx.y * PAIR_ROWS;
   const int nrows = (int)((n - row0 < PAIR_ROWS) ? (n - row0) : PAIR_ROWS);
-  stage_inv_lengthscale<KIND>(inv_ls, two_inv_l, inv_env, lengthscale, d);
+  stage_inv_lengthscale<KIND>(inv_ls, two_inv_l, inv_env, inv_trend, lengthscale, d);
   const PairShape sh = load_pair_shape<KIND>(lengthscale, d);
   if (t < PAIR_ROWS) al_s[t] = (t < nrows) ? alpha[row0 + t] : 0.0;
   __syncthreads();
@@ -146,7 +161,33 @@ __global__ __launch_bounds__(256) void kernel_grad_sums_kernel(const double *__r
       }
       const double ai = al_s[r];
       const double w0 = __dsub_rn(__dmul_rn(ai, aj0), p0), w1 = __dsub_rn(__dmul_rn(ai, aj1), p1);  // W_ij, two roundings
-      if constexpr (LOCAL) {
+      if constexpr (TREND) {
+        // one column at a time: its 4 D_MAX factors live in registers between the two sums and the accumulation; each term
+        // takes its own underflow decision, and a dead one adds nothing to its sums
+        auto column = [&](const double (&b)[D_MAX], double w, bool have) {
+          double ft[D_MAX], fe[D_MAX], fl[D_MAX], fp[D_MAX], s2, q, kt, ks;
+          trend_seasonal_factors(a_s[r], b, inv_trend, inv_env, inv_ls, two_inv_l, s2, q, ft, fe, fl, fp);
+          const bool live_t = trend_kappa(s2, kt) && have, live_s = periodic_kappa(q, ks) && have;
+          if (live_t) {
+            const double gw = w * (outputscale * kt);
+            acc[0] = fma(w, kt, acc[0]);
+#pragma unroll
+            for (int k = 0; k < D_MAX; ++k) acc[1 + k] = fma(gw, ft[k], acc[1 + k]);
+          }
+          if (live_s) {
+            const double gw = w * (sh.alpha * ks);
+            acc[1 + 4 * D_MAX] = fma(w, sh.alpha * ks, acc[1 + 4 * D_MAX]);
+#pragma unroll
+            for (int k = 0; k < D_MAX; ++k) {
+              acc[1 + D_MAX + k] = fma(gw, fe[k], acc[1 + D_MAX + k]);
+              acc[1 + 2 * D_MAX + k] = fma(gw, fl[k], acc[1 + 2 * D_MAX + k]);
+              acc[1 + 3 * D_MAX + k] = fma(gw, fp[k], acc[1 + 3 * D_MAX + k]);
+            }
+          }
+        };
+        column(b0, w0, true);
+        column(b1, w1, two);
+      } else if constexpr (LOCAL) {
         // one column at a time, and of its coordinates the first KEEP with their 3 KEEP factors in registers; the others
         // are evaluated again after the exponent (base_kernel.h: locally_periodic_keep)
         constexpr int KEEP = locally_periodic_keep(D_MAX);
@@ -232,10 +273,11 @@ __global__ __launch_bounds__(256) void kernel_grad_sums_kernel(const double *__r
     if ((t & 63) == 0) red[t >> 6][k] = v;
   }
   __syncthreads();
-  const int nsums = d + 1 + (SHAPE ? 1 : 0) + (PERIODIC ? d : 0) + (LOCAL ? 2 * d : 0);
+  const int nsums = d + 1 + (SHAPE ? 1 : 0) + (PERIODIC ? d : 0) + (LOCAL ? 2 * d : 0) + (TREND ? 3 * d + 1 : 0);
   if (t < nsums) {
     const int64_t blk = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
-    const int k = LOCAL      ? ((t > 2 * d) ? 2 * D_MAX + (t - 2 * d) : (t > d) ? D_MAX + (t - d) : t)
+    const int k = TREND      ? ((t > 4 * d) ? 4 * D_MAX + 1 : (t > 0) ? 1 + ((t - 1) / d) * D_MAX + (t - 1) % d : 0)
+                  : LOCAL    ? ((t > 2 * d) ? 2 * D_MAX + (t - 2 * d) : (t > d) ? D_MAX + (t - d) : t)
                   : PERIODIC ? ((t > d) ? D_MAX + (t - d) : t)
                   : (SHAPE && t == d + 1) ? D_MAX + 1 : t;
     partials[blk * nsums + t] = (red[0][k] + red[1][k]) + (red[2][k] + red[3][k]);
@@ -277,7 +319,8 @@ int grad_sums_launch(int kind, const double *x, int64_t n, int d, const double *
 // EVERY wave holds test point 64 b + l in registers (pre-scaled by 1/lengthscale, zero-padded to D_MAX); the training
 // points pass through LDS in chunks of mean_chunk(D_MAX) (pre-scaled, broadcast reads) and wave w takes the points
 // j = w, w + 4, w + 8, ... (the chunk length is a multiple of 4, so the split is j mod 4 whatever the chunk).  Each thread
-// adds its terms in ascending j into one accumulator; the four waves' sums meet in LDS as (w0 + w1) + (w2 + w3).  A lane
+// adds its terms in ascending j into one accumulator (trend plus seasonal: one per term, out[i] = fma(s_t, A_t, fma(s_s, A_s,
+// mean))); the four waves' sums meet in LDS as (w0 + w1) + (w2 + w3).  A lane
 // owns its test point alone -- there is no cross-lane sum -- so out[i] depends on xt_i and the model only, never on t or
 // on where the point sits in the batch.  x is staged from its flat array, 16 bytes per lane where x is 16-byte aligned
 // (a chunk starts at an even offset), one double per lane otherwise; xt rows likewise where d is even.
@@ -288,15 +331,18 @@ __global__ __launch_bounds__(256) void kernel_mean_kernel(const double *__restri
                                                            const double *__restrict__ xt, int64_t t,
                                                            double *__restrict__ out) {
   constexpr int CHUNK = mean_chunk(D_MAX);
-  constexpr bool PERIODIC = KIND == PLS_KERNEL_PERIODIC, LOCAL = KIND == PLS_KERNEL_LOCALLY_PERIODIC;
-  __shared__ double inv_ls[D_MAX];                        // (periodic, locally periodic: 1 / p_k)
-  __shared__ double two_inv_l[periodic_len<KIND>(D_MAX)];  // (periodic, locally periodic: 2 / lambda_k)
-  __shared__ double inv_env[envelope_len<KIND>(D_MAX)];    // (locally periodic: 1 / l_k)
+  constexpr bool PERIODIC = KIND == PLS_KERNEL_PERIODIC, LOCAL = KIND == PLS_KERNEL_LOCALLY_PERIODIC,
+                 TREND = KIND == PLS_KERNEL_TREND_SEASONAL;
+  __shared__ double inv_ls[D_MAX];                        // (the periodic kinds: 1 / p_k)
+  __shared__ double two_inv_l[periodic_len<KIND>(D_MAX)];  // (the periodic kinds: 2 / lambda_k)
+  __shared__ double inv_env[envelope_len<KIND>(D_MAX)];    // (locally periodic: 1 / l_k; trend plus seasonal: 1 / m_k)
+  __shared__ double inv_trend[trend_len<KIND>(D_MAX)];     // (trend plus seasonal: 1 / l_k)
   __shared__ __attribute__((aligned(16))) double a_s[CHUNK][D_MAX];
   __shared__ double al_s[CHUNK];
   __shared__ double red[4][MEAN_POINTS];
+  __shared__ double red_s[TREND ? 4 : 1][MEAN_POINTS];  // (trend plus seasonal: the seasonal term's sums)
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  stage_inv_lengthscale<KIND>(inv_ls, two_inv_l, inv_env, lengthscale, d);
+  stage_inv_lengthscale<KIND>(inv_ls, two_inv_l, inv_env, inv_trend, lengthscale, d);
   const PairShape sh = load_pair_shape<KIND>(lengthscale, d);
   if (D_MAX > 1)  // the padding coordinates stay zero: the staging below writes k < d only
     for (int e = tid; e < CHUNK * D_MAX; e += 256) a_s[e / D_MAX][e % D_MAX] = 0.0;
@@ -320,6 +366,7 @@ __global__ __launch_bounds__(256) void kernel_mean_kernel(const double *__restri
   }
   const bool xvec = (reinterpret_cast<uintptr_t>(x) & 15) == 0;
   double acc = 0.0;
+  [[maybe_unused]] double acc_s = 0.0;  // (trend plus seasonal: acc holds the trend's sum A_t, acc_s the seasonal A_s)
   for (int64_t j0 = 0; j0 < n; j0 += CHUNK) {
     const int nrows = (int)((n - j0 < CHUNK) ? (n - j0) : CHUNK);
     const int len = nrows * d;  // <= 512 * 64
@@ -344,7 +391,12 @@ __global__ __launch_bounds__(256) void kernel_mean_kernel(const double *__restri
     for (int r = w; r < nrows; r += 4) {
       double kap;
       bool alive;
-      if constexpr (LOCAL) alive = periodic_kappa(locally_periodic_exponent(a_s[r], b, inv_env, inv_ls, two_inv_l), kap);
+      if constexpr (TREND) {
+        double s2, q, ks;
+        trend_seasonal_exponents(a_s[r], b, inv_trend, inv_env, inv_ls, two_inv_l, s2, q);
+        alive = trend_kappa(s2, kap);
+        if (periodic_kappa(q, ks)) acc_s = fma(ks, al_s[r], acc_s);
+      } else if constexpr (LOCAL) alive = periodic_kappa(locally_periodic_exponent(a_s[r], b, inv_env, inv_ls, two_inv_l), kap);
       else if constexpr (PERIODIC) alive = periodic_kappa(periodic_exponent(a_s[r], b, inv_ls, two_inv_l), kap);
       else alive = pair_kappa<KIND>(pair_dist2(a_s[r], b), sh, kap);
       if (alive) acc = fma(kap, al_s[r], acc);
@@ -352,8 +404,13 @@ __global__ __launch_bounds__(256) void kernel_mean_kernel(const double *__restri
     __syncthreads();
   }
   red[w][lane] = acc;
+  if constexpr (TREND) red_s[w][lane] = acc_s;
   __syncthreads();
-  if (w == 0 && live) out[i] = fma(outputscale, (red[0][lane] + red[1][lane]) + (red[2][lane] + red[3][lane]), mean);
+  if constexpr (TREND) {
+    if (w == 0 && live)
+      out[i] = fma(outputscale, (red[0][lane] + red[1][lane]) + (red[2][lane] + red[3][lane]),
+                   fma(sh.alpha, (red_s[0][lane] + red_s[1][lane]) + (red_s[2][lane] + red_s[3][lane]), mean));
+  } else if (w == 0 && live) out[i] = fma(outputscale, (red[0][lane] + red[1][lane]) + (red[2][lane] + red[3][lane]), mean);
 }
 
 // the one launch of pls_kernel_mean (arguments already validated, t > 0)

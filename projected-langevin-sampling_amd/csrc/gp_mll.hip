@@ -46,7 +46,8 @@ __device__ __forceinline__ double block256_sum(double v, double (*ws)[4], int sl
 
 // The value and the 3 + d derivatives from the pieces (one workgroup): thread t adds entries t, t + 256, ... in ascending
 // order, then block256_sum.  sums: the nsums outputs of the reduction with P = K_y^-1 (d + 1; RQ: d + 2, whose last becomes
-// the derivative with respect to log alpha, out[4 + d]).
+// the derivative with respect to log alpha, out[4 + d]; trend plus seasonal: 4 d + 2, sums[0] the trend's kappa sum, so out[3]
+// is the derivative with respect to log s_t, and the last the one with respect to log s_s, out[4 + 4 d]).
 __global__ __launch_bounds__(256) void gp_mll_finish_kernel(int64_t n, int nsums, double outputscale, const double *__restrict__ r,
                                                              const double *__restrict__ alpha, const double *__restrict__ Lc,
                                                              int64_t ldlc, const double *__restrict__ P, int64_t ldp,
@@ -139,7 +140,7 @@ static int gp_mll_evaluate(int32_t kernel_kind, const double *x, int64_t n, int6
   if (rc) return rc;
   rc = gemm_tn_ex(Linv, p.ld, Linv, p.ld, Ky, p.ld, n, n, n, 1.0, 0.0, 2, st);
   if (rc) return rc;
-  // 5. the d + 1 sums (RQ: d + 2; periodic: 2 d + 1; locally periodic: 3 d + 1) with P = K_y^-1
+  // 5. the d + 1 sums (RQ: d + 2; periodic: 2 d + 1; locally periodic: 3 d + 1; trend plus seasonal: 4 d + 2) with P = K_y^-1
   rc = grad_sums_launch(kernel_kind, x, n, (int)d, lengthscale, outputscale, al, Ky, p.ld, sums, partials, st);
   if (rc) return rc;
   // 6. value and derivatives

@@ -51,12 +51,14 @@ __device__ __forceinline__ double matern_poly(int kind, double t) {
 }
 
 // The shape parameter of a kind that has one -- RQ's alpha, which follows the d lengthscales in every `lengthscale`
-// argument -- read once per thread; empty for the other kinds.
+// argument -- read once per thread; empty for the other kinds.  The trend-plus-seasonal kind's one scalar shape value, the
+// seasonal outputscale s_s behind its 4 d per-dimension values, travels in `alpha`.
 struct PairShape {
   double alpha, inv_2alpha;
 };
 template <int KIND>
 __device__ __forceinline__ PairShape load_pair_shape(const double *__restrict__ lengthscale, int d) {
+  if (KIND == PLS_KERNEL_TREND_SEASONAL) return PairShape{lengthscale[4 * d], 0.0};
   if (KIND != PLS_KERNEL_RQ) return PairShape{0.0, 0.0};
   const double alpha = lengthscale[d];
   return PairShape{alpha, 0.5 / alpha};
@@ -170,6 +172,36 @@ __device__ __forceinline__ double locally_periodic_coord(double delta, double in
     lam = share;
   }
   return fma(0.5 * z, z, share);
+}
+
+// Trend plus seasonal (gpytorch's ScaleKernel(RBFKernel) + ScaleKernel(RBFKernel * PeriodicKernel), as recalled): k = s_t kappa_t +
+// s_s kappa_s with kappa_t = exp(-1/2 sum_k ((a_k - b_k) / l_k)^2) and kappa_s the locally periodic kappa of (m, lambda, p).
+// One coordinate from its UNSCALED difference delta: the seasonal share of the NEGATED seasonal exponent is
+// locally_periodic_coord's of the same operands (returned; env, lam, per as there), so the seasonal term has the locally
+// periodic kind's bits; the trend's distance sum takes z = delta inv_t in one explicit fma, s2 = z z + s2 (GRAD only: tr = z^2,
+// the factor of dK / d log l_k).  Even in delta; a padding coordinate (delta = 0, all scales 0) leaves s2 alone and gives 0.
+template <bool GRAD>
+__device__ __forceinline__ double trend_seasonal_coord(double delta, double inv_t, double inv_m, double inv_p, double two_inv_lam,
+                                                       double &s2, double &tr, double &env, double &lam, double &per) {
+#pragma clang fp contract(off)
+  const double z = delta * inv_t;
+  s2 = fma(z, z, s2);
+  if (GRAD) tr = z * z;
+  return locally_periodic_coord<GRAD>(delta, inv_m, inv_p, two_inv_lam, env, lam, per);
+}
+// kappa_t from the trend's distance sum s2 >= 0: the RBF exponent -s2 / 2 under the 745.2 rule; false: a dead term
+__device__ __forceinline__ bool trend_kappa(double s2, double &kap) {
+  const double x = -0.5 * s2;
+  kap = exp_nonpos_unguarded(x);
+  return !(x < -745.2);
+}
+// The Gram entry from the trend's distance sum s2 and the seasonal term's negated exponent q: each term takes its own underflow
+// decision and a dead one contributes exactly 0; fma(s_t, kappa_t, s_s kappa_s), so that the entry is s_t + s_s rounded once
+// at distance 0, the locally periodic entry s_s kappa_s where the trend is dead and s_t kappa_t where the seasonal term is.
+__device__ __forceinline__ double trend_seasonal_entry(double s2, double q, double s_t, double s_s) {
+  double kt, ks;
+  const bool live_t = trend_kappa(s2, kt), live_s = periodic_kappa(q, ks);
+  return fma(s_t, live_t ? kt : 0.0, live_s ? s_s * ks : 0.0);
 }
 
 // One pair from its distance sum s2 (RBF: r^2; Matern: t^2 = 2 nu r^2; RQ: r^2, with its shape sh): kap = kappa, the kernel

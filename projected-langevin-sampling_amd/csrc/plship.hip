@@ -1271,6 +1271,19 @@ __device__ inline double cv_kernel_eval(int kind, const double *__restrict__ x, 
                                         const double *__restrict__ inv_ls, const double *__restrict__ inv_p, double shape,
                                         double outputscale) {
   double s = 0.0;
+  if (kind == PLS_KERNEL_TREND_SEASONAL) {  // the pairwise kernels' own evaluation (kernel_math.h): inv_ls[k] = 1 / l_k, inv_p[k] =
+    double q = 0.0, u0, u1, u2, kap;        // 1 / p_k, 2 / lambda_k at inv_p[8 + k], 1 / m_k at inv_p[16 + k], shape = s_s
+    // trend_seasonal_coord and trend_seasonal_entry term after term -- the same operations on the same operands, the same
+    // bits --, so that one exponential is live at a time and the kernels keep the registers the other kinds need
+    for (int k = 0; k < d; ++k)
+      q = __dadd_rn(q, locally_periodic_coord<false>(x[a * d + k] - x[b * d + k], inv_p[16 + k], inv_p[k], inv_p[8 + k], u0, u1, u2));
+    const double seasonal = periodic_kappa(q, kap) ? shape * kap : 0.0;
+    for (int k = 0; k < d; ++k) {
+      const double z = (x[a * d + k] - x[b * d + k]) * inv_ls[k];
+      s = fma(z, z, s);
+    }
+    return fma(outputscale, trend_kappa(s, kap) ? kap : 0.0, seasonal);
+  }
   if (kind == PLS_KERNEL_LOCALLY_PERIODIC) {  // as periodic below, with inv_ls[k] = 1 / l_k and 2 / lambda_k at inv_p[16 + k]
     double u0, u1, u2, kap;
     for (int k = 0; k < d; ++k)
@@ -1323,7 +1336,7 @@ __global__ __launch_bounds__(CV_BLOCK) void cv_init_kernel(int kind, const doubl
                                                             unsigned char *__restrict__ chosen, CvState *st) {
   __shared__ double inv_ls[64];
   // (periodic: the period lengths follow the d <= 16 lengthscales; locally periodic: l, lambda, p in blocks of d, 1 / p_k in
-  // front and 2 / lambda_k behind it)
+  // front and 2 / lambda_k behind it; trend plus seasonal: 1 / p_k, 2 / lambda_k and 1 / m_k in thirds of 8)
   __shared__ double inv_p[32];
   if ((int)threadIdx.x < d) inv_ls[threadIdx.x] = (kind != PLS_KERNEL_LINEAR) ? 1.0 / lengthscale[threadIdx.x] : 1.0;
   if (kind == PLS_KERNEL_PERIODIC && (int)threadIdx.x < d) inv_p[threadIdx.x] = 1.0 / lengthscale[d + threadIdx.x];
@@ -1331,7 +1344,12 @@ __global__ __launch_bounds__(CV_BLOCK) void cv_init_kernel(int kind, const doubl
     inv_p[threadIdx.x] = 1.0 / lengthscale[2 * d + threadIdx.x];
     inv_p[16 + threadIdx.x] = 2.0 / lengthscale[d + threadIdx.x];
   }
-  const double shape = (kind == PLS_KERNEL_RQ) ? lengthscale[d] : 0.0;
+  if (kind == PLS_KERNEL_TREND_SEASONAL && (int)threadIdx.x < d) {  // (l, m, lambda, p in blocks of d <= 8, then s_s)
+    inv_p[threadIdx.x] = 1.0 / lengthscale[3 * d + threadIdx.x];
+    inv_p[8 + threadIdx.x] = 2.0 / lengthscale[2 * d + threadIdx.x];
+    inv_p[16 + threadIdx.x] = 1.0 / lengthscale[d + threadIdx.x];
+  }
+  const double shape = (kind == PLS_KERNEL_RQ) ? lengthscale[d] : (kind == PLS_KERNEL_TREND_SEASONAL) ? lengthscale[4 * d] : 0.0;
   __syncthreads();
   const int64_t i = (int64_t)blockIdx.x * CV_BLOCK + threadIdx.x;
   if (i == 0) {
@@ -1447,7 +1465,7 @@ __global__ __launch_bounds__(CV_BLOCK) void cv_update_kernel(int kind, const dou
   __shared__ double inv_ls[64];
   __shared__ double part[NSL][CV_COLS];
   // (periodic: the period lengths follow the d <= 16 lengthscales; locally periodic: l, lambda, p in blocks of d, 1 / p_k in
-  // front and 2 / lambda_k behind it)
+  // front and 2 / lambda_k behind it; trend plus seasonal: 1 / p_k, 2 / lambda_k and 1 / m_k in thirds of 8)
   __shared__ double inv_p[32];
   if ((int)threadIdx.x < d) inv_ls[threadIdx.x] = (kind != PLS_KERNEL_LINEAR) ? 1.0 / lengthscale[threadIdx.x] : 1.0;
   if (kind == PLS_KERNEL_PERIODIC && (int)threadIdx.x < d) inv_p[threadIdx.x] = 1.0 / lengthscale[d + threadIdx.x];
@@ -1455,7 +1473,12 @@ __global__ __launch_bounds__(CV_BLOCK) void cv_update_kernel(int kind, const dou
     inv_p[threadIdx.x] = 1.0 / lengthscale[2 * d + threadIdx.x];
     inv_p[16 + threadIdx.x] = 2.0 / lengthscale[d + threadIdx.x];
   }
-  const double shape = (kind == PLS_KERNEL_RQ) ? lengthscale[d] : 0.0;
+  if (kind == PLS_KERNEL_TREND_SEASONAL && (int)threadIdx.x < d) {  // (l, m, lambda, p in blocks of d <= 8, then s_s)
+    inv_p[threadIdx.x] = 1.0 / lengthscale[3 * d + threadIdx.x];
+    inv_p[8 + threadIdx.x] = 2.0 / lengthscale[2 * d + threadIdx.x];
+    inv_p[16 + threadIdx.x] = 1.0 / lengthscale[d + threadIdx.x];
+  }
+  const double shape = (kind == PLS_KERNEL_RQ) ? lengthscale[d] : (kind == PLS_KERNEL_TREND_SEASONAL) ? lengthscale[4 * d] : 0.0;
   __syncthreads();
   if (st->stopped || st->count != iter + 1) return;  // (stopped early, or ran out of candidates; uniform)
   const int64_t j = st->pivot;
@@ -3220,7 +3243,8 @@ int pls_select_inducing_conditional_variance(int32_t kernel_kind, const double *
                                              double threshold, int64_t *indices, int64_t *count, void *workspace,
                                              size_t workspace_bytes, void *stream) {
   PLS_REQUIRE((kernel_kind >= PLS_KERNEL_RBF_ARD && kernel_kind <= PLS_KERNEL_MATERN52) || kernel_kind == PLS_KERNEL_RQ ||
-                  kernel_kind == PLS_KERNEL_PERIODIC || kernel_kind == PLS_KERNEL_LOCALLY_PERIODIC,
+                  kernel_kind == PLS_KERNEL_PERIODIC || kernel_kind == PLS_KERNEL_LOCALLY_PERIODIC ||
+                  kernel_kind == PLS_KERNEL_TREND_SEASONAL,
               "unknown kernel kind %d", kernel_kind);
   PLS_REQUIRE(x && indices && count, "select_inducing: NULL pointer");
   PLS_REQUIRE(m > 1, "select_inducing: Must have at least 2 inducing points");  // conditional_variance.py:57
@@ -3229,6 +3253,8 @@ int pls_select_inducing_conditional_variance(int32_t kernel_kind, const double *
               "select_inducing: input dimension %lld > 16 is not supported for the periodic kernel", (long long)d);
   PLS_REQUIRE(kernel_kind != PLS_KERNEL_LOCALLY_PERIODIC || d <= 16,
               "select_inducing: input dimension %lld > 16 is not supported for the locally periodic kernel", (long long)d);
+  PLS_REQUIRE(kernel_kind != PLS_KERNEL_TREND_SEASONAL || d <= 8,
+              "select_inducing: input dimension %lld > 8 is not supported for the trend-plus-seasonal kernel", (long long)d);
   PLS_REQUIRE(kernel_kind == PLS_KERNEL_LINEAR || lengthscale, "select_inducing: kernel kind %d needs lengthscale", kernel_kind);
   const size_t need = pls_select_inducing_workspace_bytes(n, m);
   if (!workspace || workspace_bytes < need)

@@ -21,7 +21,7 @@ import torch
 from . import _lib as L
 from . import _ops
 from ._chol import CHOLESKY_JITTER, CHOLESKY_MAX_TRIES, NotPSDError, cholesky_factor
-from .kernel import STATIONARY_KERNELS, BaseKernel, LocallyPeriodicKernel, MaternKernel, PeriodicKernel, _dev
+from .kernel import STATIONARY_KERNELS, BaseKernel, LocallyPeriodicKernel, MaternKernel, PeriodicKernel, TrendSeasonalKernel, _dev
 from .likelihoods import GaussianLikelihood, _Likelihood
 from .trainers import EarlyStopper
 from .utils import set_seed
@@ -34,6 +34,8 @@ NOISE_LOWER_BOUND = 1e-4
 #: family without starting values: they keep refusing the bare name "periodic" (train_exact_gp and exact_gp_runner take it)
 _KERNEL_NAMES = {"rbf": ("rbf", None), "matern": ("matern", None), "matern12": ("matern", 0.5), "matern32": ("matern", 1.5),
                  "matern52": ("matern", 2.5), "rq": ("rq", None)}
+#: the names that train_exact_gp and exact_gp_runner take beyond those: the families that the model classes take as a class
+_TRAINER_KERNEL_NAMES = {"periodic": PeriodicKernel, "locally_periodic": LocallyPeriodicKernel, "trend_seasonal": TrendSeasonalKernel}
 _FAMILIES = {cls.family: cls for cls in STATIONARY_KERNELS}
 
 
@@ -58,8 +60,8 @@ def _kernel_choice(who: str, kernel, nu: float, ard: bool, d: int):
         family = kernel
     elif isinstance(kernel, BaseKernel):
         if not isinstance(kernel, STATIONARY_KERNELS):
-            raise TypeError(f"{who}: the kernel must be an ARDKernel, a MaternKernel, an RQKernel or a PeriodicKernel (a "
-                            "lengthscale and an outputscale to learn)")
+            raise TypeError(f"{who}: the kernel must be an ARDKernel, a MaternKernel, an RQKernel, a PeriodicKernel, a "
+                            "LocallyPeriodicKernel or a TrendSeasonalKernel (a lengthscale and an outputscale to learn)")
         start, family = kernel, _FAMILIES[kernel.family]
         nu = getattr(kernel, "nu", nu)
         ard = kernel.lengthscale.numel() > 1 or d == 1 and ard
@@ -82,8 +84,9 @@ class _ExactGPClasses:
     value starts at 0.  ``raw`` is seen as (C, 3 + nls + shape columns) rows: mean, raw noise, raw outputscale, the nls raw
     lengthscales (d of them, or one shared by all dimensions), then the family's raw shape values, ``softplus(raw)`` each:
     none for RBF and Matern, raw alpha for the rational-quadratic kernel, the nls raw period lengths for the periodic kernel,
-    the nls raw periodic lengthscales and then the nls raw period lengths for the locally periodic kernel (a family's shape
-    blocks in their declared order, kernel._StationaryKernel.shape_blocks)
+    the nls raw periodic lengthscales and then the nls raw period lengths for the locally periodic kernel, the nls raw
+    seasonal lengthscales, periodic lengthscales and period lengths and then the raw seasonal outputscale for the
+    trend-plus-seasonal kernel (a family's shape blocks in their declared order, kernel._StationaryKernel.shape_blocks)
     -- _lib.kernel_shape_params with the nls raw lengthscales in the place of the library's d.  x (n, d), the targets (C, n)
     and the fixed noise v (C, n), or None, are kept as given and uploaded once, on the first evaluation on the device.  One
     evaluation of all classes is ONE library call with one read-back, ``pls_gp_mll_grad_classes``: 4 + d + shape
@@ -156,15 +159,26 @@ class _ExactGPClasses:
 
     @property
     def period_length(self) -> torch.Tensor:
-        """(C, d) the period lengths of the periodic and the locally periodic kernel (a shared one repeated); AttributeError
-        for the other kernels"""
+        """(C, d) the period lengths of the periodic, the locally periodic and the trend-plus-seasonal kernel (a shared one
+        repeated); AttributeError for the other kernels"""
         return self._shape("period_length")
 
     @property
     def periodic_lengthscale(self) -> torch.Tensor:
-        """(C, d) the lengthscales of the locally periodic kernel's periodic factor (a shared one repeated); AttributeError
-        for the other kernels"""
+        """(C, d) the lengthscales of the periodic factor of the locally periodic and the trend-plus-seasonal kernel (a shared
+        one repeated); AttributeError for the other kernels"""
         return self._shape("periodic_lengthscale")
+
+    @property
+    def seasonal_lengthscale(self) -> torch.Tensor:
+        """(C, d) the envelope lengthscales of the trend-plus-seasonal kernel's seasonal term (a shared one repeated);
+        AttributeError for the other kernels"""
+        return self._shape("seasonal_lengthscale")
+
+    @property
+    def seasonal_outputscale(self) -> torch.Tensor:
+        """(C) the outputscale of the trend-plus-seasonal kernel's seasonal term; AttributeError for the other kernels"""
+        return self._shape("seasonal_outputscale")[:, 0]
 
     def _library_lengthscale(self) -> torch.Tensor:
         """(C, d + shape parameters): the lengthscales, then the shape values, as the library reads them"""
@@ -283,10 +297,10 @@ class _ExactGPClasses:
     # ---- prediction -------------------------------------------------------------------------------------------------
     def _predict_class(self, c: int, x_test: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
         """(latent mean, latent variance) of class c at x_test (t, d), float64 on the device: m_c + k*^T alpha_c and
-        k** - |Lc^-1 k*|^2 with K_y,c = Lc Lc^T and alpha_c = K_y,c^-1 (y_c - m_c)."""
+        k** - |Lc^-1 k*|^2 with K_y,c = Lc Lc^T, alpha_c = K_y,c^-1 (y_c - m_c) and k** the kernel's prior variance."""
         st = self._device_state()
-        mean_c, noise, s, _ = (v[c] for v in self._natural())
-        mean_c, noise, s = float(mean_c), float(noise), float(s)
+        mean_c, noise, _, _ = (v[c] for v in self._natural())
+        mean_c, noise = float(mean_c), float(noise)
         kern = self._class_kernel(c)
         ky = kern(st["x"], st["x"])
         ky.diagonal().add_(st["fixed"][c] + noise if st["fixed"] is not None else noise)
@@ -298,7 +312,7 @@ class _ExactGPClasses:
         L.check(L.load().pls_gemm_tn(ks.data_ptr(), L.ld(ks), alpha.data_ptr(), 1, mean.data_ptr(), 1, t, 1, self.n, 1.0, 0.0,
                                      L.stream_ptr()), "pls_gemm_tn")
         v = factor.forward_solve(ks)
-        return mean[:, 0] + mean_c, s - v.square().sum(dim=0)
+        return mean[:, 0] + mean_c, kern.prior_variance - v.square().sum(dim=0)
 
 
 class ExactGP(_ExactGPClasses):
@@ -312,12 +326,14 @@ class ExactGP(_ExactGPClasses):
         raw[2]   raw outputscale
         raw[3:3 + nls]  raw lengthscales: nls = d of them (``ard=True``) or one shared by all dimensions (``ard=False``)
         raw[3 + nls:]   the family's raw shape values: raw alpha (rational quadratic), the nls raw period lengths (periodic),
-                        the nls raw periodic lengthscales and then the nls raw period lengths (locally periodic)
+                        the nls raw periodic lengthscales and then the nls raw period lengths (locally periodic), the nls raw
+                        seasonal lengthscales, periodic lengthscales, period lengths and then the raw seasonal outputscale
+                        (trend plus seasonal)
 
     ``kernel``: "rbf", "rq" or "matern" (with ``nu``); "matern12" / "matern32" / "matern52" name nu as well; one of the classes
-    kernel.STATIONARY_KERNELS names its family likewise (the periodic and the locally periodic family have no name here:
-    ``kernel=PeriodicKernel``, ``kernel=LocallyPeriodicKernel``; ``train_exact_gp`` and ``exact_gp_runner`` take "periodic"
-    and "locally_periodic"); an instance of them gives the kind and the starting values (as the reference's ``deepcopy(kernel)``).
+    kernel.STATIONARY_KERNELS names its family likewise (the periodic, the locally periodic and the trend-plus-seasonal family
+    have no name here: ``kernel=PeriodicKernel``, ``kernel=LocallyPeriodicKernel``, ``kernel=TrendSeasonalKernel``;
+    ``train_exact_gp`` and ``exact_gp_runner`` take "periodic", "locally_periodic" and "trend_seasonal"); an instance of them gives the kind and the starting values (as the reference's ``deepcopy(kernel)``).
     x (n, d) and y (n) are kept as given."""
 
     def __init__(self, x: torch.Tensor, y: torch.Tensor, kernel="rbf", nu: float = 2.5, ard: bool = True):
@@ -361,9 +377,20 @@ class ExactGP(_ExactGPClasses):
 
     @property
     def periodic_lengthscale(self) -> torch.Tensor:
-        """the d lengthscales of the locally periodic kernel's periodic factor (a shared one repeated); AttributeError for the
-        other kernels"""
+        """the d lengthscales of the periodic factor of the locally periodic and the trend-plus-seasonal kernel (a shared one
+        repeated); AttributeError for the other kernels"""
         return self._shape("periodic_lengthscale")[0]
+
+    @property
+    def seasonal_lengthscale(self) -> torch.Tensor:
+        """the d envelope lengthscales of the trend-plus-seasonal kernel's seasonal term (a shared one repeated); AttributeError
+        for the other kernels"""
+        return self._shape("seasonal_lengthscale")[0]
+
+    @property
+    def seasonal_outputscale(self) -> float:
+        """the outputscale of the trend-plus-seasonal kernel's seasonal term; AttributeError for the other kernels"""
+        return float(self._shape("seasonal_outputscale")[0, 0])
 
     @property
     def kernel(self) -> BaseKernel:
@@ -421,7 +448,7 @@ def _kernel_diagonal(kernel, x: torch.Tensor) -> torch.Tensor:
     from .kernel import LinearKernel, PLSKernel, _StationaryKernel
 
     if isinstance(kernel, _StationaryKernel):
-        return torch.full((x.shape[0],), float(kernel.outputscale), dtype=torch.float64, device=x.device)
+        return torch.full((x.shape[0],), float(kernel.prior_variance), dtype=torch.float64, device=x.device)
     if isinstance(kernel, LinearKernel):
         return x.square().sum(dim=1)
     if isinstance(kernel, PLSKernel):
@@ -899,10 +926,10 @@ def train_exact_gp(x: torch.Tensor, y: torch.Tensor, kernel, seed: int, number_o
     (loss, gradient)`` replaces ``model.loss_and_grad`` (a host evaluation drives the same loop without a device).
     ``likelihood="dirichlet"``: y holds integer labels and the model is a DirichletExactGP (``number_of_classes`` and
     ``fixed_noise`` go to it); the loss is then summed over the classes, as the reference's ``.sum()`` over the batch.
-    ``kernel``: as the model classes take it, and also "periodic" and "locally_periodic" (the model classes'
-    ``kernel=PeriodicKernel`` and ``kernel=LocallyPeriodicKernel``)."""
+    ``kernel``: as the model classes take it, and also "periodic", "locally_periodic" and "trend_seasonal" (the model classes'
+    ``kernel=PeriodicKernel``, ``kernel=LocallyPeriodicKernel`` and ``kernel=TrendSeasonalKernel``)."""
     set_seed(seed)
-    kernel = {"periodic": PeriodicKernel, "locally_periodic": LocallyPeriodicKernel}.get(kernel, kernel) if isinstance(kernel, str) else kernel
+    kernel = _TRAINER_KERNEL_NAMES.get(kernel, kernel) if isinstance(kernel, str) else kernel
     if likelihood == "gaussian":
         model = ExactGP(x, y, kernel)
     elif likelihood == "dirichlet":
@@ -929,8 +956,8 @@ def construct_average_ard_kernel(models: Sequence[ExactGP]) -> BaseKernel:
     """The kernel of the AVERAGED RAW parameters, softplus applied afterwards (constructors.py:28-53 averages the
     entries of ``state_dict()``, which are the raw values).  A DirichletExactGP holds one row of raw values per class: its
     rows are averaged first (the reference's ``mean(dim=0)`` over the batch), then the models.  Every block of the family's
-    raw shape values (raw alpha, the raw period lengths, the raw periodic lengthscales) is averaged like the raw lengthscales
-    and the result is a kernel of the models' family."""
+    raw shape values (raw alpha, the raw period lengths, the raw periodic and seasonal lengthscales, the raw seasonal
+    outputscale) is averaged like the raw lengthscales and the result is a kernel of the models' family."""
     first = models[0]
     per_model = [m.raw_parameters() for m in models]
     raw = torch.stack([r.mean(dim=0) if r.dim() == 2 else r for r in per_model]).mean(dim=0)

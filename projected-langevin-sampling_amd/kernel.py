@@ -3,8 +3,9 @@
 The reference takes a gpytorch kernel object; gpytorch is a host-side hyper-parameter container there.
 Here kernels are plain parameter holders whose Gram matrices are built by libplship on the MI355X.
 A gpytorch ScaleKernel(RBFKernel), ScaleKernel(MaternKernel), ScaleKernel(RQKernel), ScaleKernel(PeriodicKernel) or
-ScaleKernel(RBFKernel * PeriodicKernel) instance is accepted wherever a base kernel is expected: its lengthscale /
-outputscale (and nu, alpha or period_length) are read once (``as_base_kernel``)."""
+ScaleKernel(RBFKernel * PeriodicKernel) instance, or the sum ScaleKernel(RBFKernel) + ScaleKernel(RBFKernel * PeriodicKernel), is
+accepted wherever a base kernel is expected: its lengthscale / outputscale (and nu, alpha or period_length) are read once
+(``as_base_kernel``)."""
 from __future__ import annotations
 
 import torch
@@ -24,6 +25,12 @@ class BaseKernel:
 
     kind: int
     outputscale: float = 1.0
+
+    @property
+    def prior_variance(self) -> float:
+        """k(x, x) of a stationary kernel, the same at every x: the outputscale, for a sum of scaled terms the sum of their
+        outputscales.  (The linear kernel's k(x, x) depends on x: this value is not its diagonal.)"""
+        return float(self.outputscale)
 
     def _lengthscale_dev(self, d: int) -> torch.Tensor | None:
         return None
@@ -175,6 +182,41 @@ class LocallyPeriodicKernel(_StationaryKernel):
         self.periodic_lengthscale, self.period_length = values["periodic_lengthscale"], values["period_length"]
 
 
+class TrendSeasonalKernel(_StationaryKernel):
+    """ScaleKernel(RBFKernel(ard_num_dims=D)) + ScaleKernel(RBFKernel(ard_num_dims=D) * PeriodicKernel(ard_num_dims=D)): a slow
+    trend added to a locally periodic seasonal part.  With e_d = (a_d - b_d) / period_length_d,
+    k(a,b) = outputscale * exp(-1/2 sum_d ((a_d - b_d) / lengthscale_d)^2)
+           + seasonal_outputscale * exp(-(1/2 sum_d ((a_d - b_d) / seasonal_lengthscale_d)^2
+                                          + 2 sum_d sin^2(pi e_d) / periodic_lengthscale_d)),
+    gpytorch's sum as recalled (include/plship.h states the formula; it is the contract).  ``lengthscale`` and ``outputscale``
+    are the trend's; ``seasonal_lengthscale`` is the envelope of the seasonal term, ``periodic_lengthscale`` divides and is not
+    squared, as PeriodicKernel's lengthscale.  Each of the four per-dimension blocks holds d (or one shared) positive values;
+    the library reads them in that order and the seasonal outputscale behind them, so the device array has 4 d + 1 entries.
+    k(x, x) = outputscale + seasonal_outputscale (``prior_variance``).  d <= 8."""
+
+    kind, family = L.KERNEL_TREND_SEASONAL, "trend_seasonal"
+    shape_blocks = (("seasonal_lengthscale", True), ("periodic_lengthscale", True), ("period_length", True),
+                    ("seasonal_outputscale", False))
+
+    def __init__(self, lengthscale, outputscale: float = 1.0, seasonal_lengthscale=1.0, periodic_lengthscale=1.0,
+                 period_length=1.0, seasonal_outputscale: float = 1.0):
+        super().__init__(lengthscale, outputscale)
+        values = {"lengthscale": self.lengthscale}  # (the trend's outputscale is as free as every family's)
+        for name, given in (("seasonal_lengthscale", seasonal_lengthscale), ("periodic_lengthscale", periodic_lengthscale),
+                            ("period_length", period_length), ("seasonal_outputscale", seasonal_outputscale)):
+            values[name] = torch.as_tensor(given, dtype=torch.float64).detach().reshape(-1).cpu()
+        for name, v in values.items():
+            if v.numel() == 0 or not bool((v > 0.0).all()):
+                raise ValueError(f"TrendSeasonalKernel: every {name.replace('_', ' ')} must be positive, got {v.tolist()}")
+        self.seasonal_lengthscale, self.periodic_lengthscale = values["seasonal_lengthscale"], values["periodic_lengthscale"]
+        self.period_length = values["period_length"]
+        self.seasonal_outputscale = float(values["seasonal_outputscale"][0])  # (a one-element tensor is taken as its value)
+
+    @property
+    def prior_variance(self) -> float:
+        return self.outputscale + self.seasonal_outputscale
+
+
 class LinearKernel(BaseKernel):
     """k(x1, x2) = x1 x2^T: the reference's test double (mockers/kernel.py:8-23)."""
 
@@ -182,8 +224,8 @@ class LinearKernel(BaseKernel):
 
 
 #: the stationary families, in the order ``as_base_kernel`` asks a gpytorch kernel for their keywords: nu, alpha, period_length
-STATIONARY_KERNELS = (ARDKernel, MaternKernel, RQKernel, PeriodicKernel, LocallyPeriodicKernel)
-#: "ARDKernel / MaternKernel / RQKernel / PeriodicKernel / LocallyPeriodicKernel", as the error messages of the package list them
+STATIONARY_KERNELS = (ARDKernel, MaternKernel, RQKernel, PeriodicKernel, LocallyPeriodicKernel, TrendSeasonalKernel)
+#: "ARDKernel / MaternKernel / RQKernel / PeriodicKernel / LocallyPeriodicKernel / TrendSeasonalKernel", as the error messages of the package list them
 STATIONARY_KERNEL_NAMES = " / ".join(cls.__name__ for cls in STATIONARY_KERNELS)
 
 
@@ -193,9 +235,28 @@ def as_base_kernel(kernel) -> BaseKernel:
     kernel with an ``alpha`` attribute), ScaleKernel(PeriodicKernel) (an inner kernel with a ``period_length`` attribute) or
     ScaleKernel(RBFKernel * PeriodicKernel) (gpytorch's product as recalled: an inner kernel with a ``kernels`` sequence of
     two members that both have a ``lengthscale``, exactly one of them a ``period_length``; the other, which must have none of
-    ``nu``, ``alpha`` and ``period_length``, is the envelope)."""
+    ``nu``, ``alpha`` and ``period_length``, is the envelope).  One sum is read as well, gpytorch's as recalled:
+    ScaleKernel(RBFKernel) + ScaleKernel(RBFKernel * PeriodicKernel) -- an object without a ``base_kernel`` whose ``kernels``
+    sequence has exactly two members, each with a ``base_kernel`` and an ``outputscale``, of which one reads as an ARDKernel
+    and the other as a LocallyPeriodicKernel by the rules above, in either order; every other sum raises TypeError."""
     if isinstance(kernel, BaseKernel):
         return kernel
+    terms = getattr(kernel, "kernels", None)
+    if terms is not None and not hasattr(kernel, "base_kernel"):
+        terms = list(terms)
+        if len(terms) == 2 and all(hasattr(m, "base_kernel") and hasattr(m, "outputscale") for m in terms):
+            try:
+                read = [as_base_kernel(m) for m in terms]
+            except TypeError:
+                read = []
+            trend = [k for k in read if type(k) is ARDKernel]
+            seasonal = [k for k in read if type(k) is LocallyPeriodicKernel]
+            if len(trend) == len(seasonal) == 1:
+                trend, seasonal = trend[0], seasonal[0]
+                return TrendSeasonalKernel(lengthscale=trend.lengthscale, outputscale=trend.outputscale,
+                                           seasonal_lengthscale=seasonal.lengthscale, periodic_lengthscale=seasonal.periodic_lengthscale,
+                                           period_length=seasonal.period_length, seasonal_outputscale=seasonal.outputscale)
+        raise TypeError(f"unsupported base kernel {type(kernel).__name__}: use {STATIONARY_KERNEL_NAMES} / LinearKernel")
     inner = getattr(kernel, "base_kernel", None)
     members = getattr(inner, "kernels", None)
     if members is not None and hasattr(kernel, "outputscale"):

@@ -25,7 +25,7 @@ import projected_langevin_sampling_amd as pkg  # noqa: E402
 L = pkg._lib
 F64 = torch.float64
 KINDS = {"rbf": L.KERNEL_RBF_ARD, "matern52": L.KERNEL_MATERN52, "rq": L.KERNEL_RQ, "periodic": L.KERNEL_PERIODIC,
-         "locally_periodic": L.KERNEL_LOCALLY_PERIODIC}
+         "locally_periodic": L.KERNEL_LOCALLY_PERIODIC, "trend_seasonal": L.KERNEL_TREND_SEASONAL}
 RQ_ALPHA = math.log(2.0)  # behind the lengthscales in the library's array; its derivative is the last output
 
 
@@ -47,13 +47,18 @@ def timed(fn, repeats):
 def probe_kernel(kind, d, g):
     """The kernel whose parameters are timed: lengthscales (0.5 + U) sqrt(d), drawn for every kind; RQ: alpha = ln 2; periodic:
     lengthscales (0.5 + U) d and period lengths 0.5 + 2.5 U, drawn after them; locally periodic: the periodic kind's draws under
-    envelope lengthscales (1 + U) sqrt(d), drawn last."""
+    envelope lengthscales (1 + U) sqrt(d), drawn last; trend plus seasonal: the locally periodic kind's draws as the seasonal
+    term (s_s = 0.9) under trend lengthscales (2 + U) sqrt(d), drawn after them."""
     ls = (0.5 + torch.rand(d, generator=g, dtype=F64)) * d**0.5
-    if kind in (L.KERNEL_PERIODIC, L.KERNEL_LOCALLY_PERIODIC):
+    if kind in (L.KERNEL_PERIODIC, L.KERNEL_LOCALLY_PERIODIC, L.KERNEL_TREND_SEASONAL):
         lam, period = (0.5 + torch.rand(d, generator=g, dtype=F64)) * d, 0.5 + 2.5 * torch.rand(d, generator=g, dtype=F64)
         if kind == L.KERNEL_PERIODIC:
             return pkg.PeriodicKernel(lam, period_length=period)
-        return pkg.LocallyPeriodicKernel((1.0 + torch.rand(d, generator=g, dtype=F64)) * d**0.5, periodic_lengthscale=lam, period_length=period)
+        envelope = (1.0 + torch.rand(d, generator=g, dtype=F64)) * d**0.5
+        if kind == L.KERNEL_TREND_SEASONAL:
+            return pkg.TrendSeasonalKernel((2.0 + torch.rand(d, generator=g, dtype=F64)) * d**0.5, seasonal_lengthscale=envelope,
+                                           periodic_lengthscale=lam, period_length=period, seasonal_outputscale=0.9)
+        return pkg.LocallyPeriodicKernel(envelope, periodic_lengthscale=lam, period_length=period)
     return {L.KERNEL_RBF_ARD: pkg.ARDKernel(ls), L.KERNEL_MATERN52: pkg.MaternKernel(ls, nu=2.5), L.KERNEL_RQ: pkg.RQKernel(ls, alpha=RQ_ALPHA)}[kind]
 
 
@@ -118,14 +123,19 @@ def torch_route(kind, x, y, ls, s, noise, mean, repeats):
     leaves = [torch.tensor(v, dtype=F64, device="cuda", requires_grad=True) for v in (mean, noise, math.log(s))]
     log_ls = ls[:d].log().clone().requires_grad_(True)
     log_alpha = torch.tensor(math.log(RQ_ALPHA), dtype=F64, device="cuda", requires_grad=True)
-    local = kind == L.KERNEL_LOCALLY_PERIODIC  # (l, lambda, p in blocks of d; log_ls is then the envelope's)
-    log_p = (ls[2 * d:] if local else ls[d:2 * d] if kind == L.KERNEL_PERIODIC else ls[:d]).log().clone().requires_grad_(True)  # (periodic kinds only)
-    log_lam = (ls[d:2 * d] if local else ls[:d]).log().clone().requires_grad_(True)  # (locally periodic only)
+    trend = kind == L.KERNEL_TREND_SEASONAL  # (l, m, lambda, p in blocks of d, then s_s; log_ls is then the trend's)
+    local = kind == L.KERNEL_LOCALLY_PERIODIC or trend  # (l, lambda, p in blocks of d; log_ls is then the envelope's)
+    o = d if trend else 0  # (where the locally periodic blocks start)
+    log_p = (ls[o + 2 * d:o + 3 * d] if local else ls[d:2 * d] if kind == L.KERNEL_PERIODIC else ls[:d]).log().clone().requires_grad_(True)  # (periodic kinds only)
+    log_lam = (ls[o + d:o + 2 * d] if local else ls[:d]).log().clone().requires_grad_(True)  # (locally periodic, trend plus seasonal)
+    log_env = ls[o:o + d].log().clone().requires_grad_(True)  # (trend plus seasonal: the seasonal term's envelope)
+    log_ss = ls[-1].log().clone().requires_grad_(True)  # (trend plus seasonal: the seasonal outputscale)
     result = {}
 
     def run():
-        for t in leaves + [log_ls, log_alpha, log_p, log_lam]:
+        for t in leaves + [log_ls, log_alpha, log_p, log_lam, log_env, log_ss]:
             t.grad = None
+        e2t = torch.zeros((n, n), dtype=F64, device="cuda")  # (trend plus seasonal: the trend's squared distance)
         e2 = torch.zeros((n, n), dtype=F64, device="cuda")
         for k in range(d):
             if kind == L.KERNEL_PERIODIC:  # (e2 holds the negated exponent, sum_k 2 sin^2(pi e_k) / lambda_k)
@@ -134,7 +144,9 @@ def torch_route(kind, x, y, ls, s, noise, mean, repeats):
                 continue
             if local:  # (the negated exponent again, the envelope's share added)
                 delta = x[:, k][:, None] - x[:, k][None, :]
-                e2 = e2 + 0.5 * (delta / log_ls[k].exp()).square() + 2.0 * torch.sin(math.pi * delta / log_p[k].exp()).square() / log_lam[k].exp()
+                if trend:
+                    e2t = e2t + (delta / log_ls[k].exp()).square()
+                e2 = e2 + 0.5 * (delta / (log_env if trend else log_ls)[k].exp()).square() + 2.0 * torch.sin(math.pi * delta / log_p[k].exp()).square() / log_lam[k].exp()
                 continue
             a = x[:, k] / log_ls[k].exp()
             e2 = e2 + (a[:, None] - a[None, :]).square()
@@ -148,13 +160,15 @@ def torch_route(kind, x, y, ls, s, noise, mean, repeats):
             off = ~torch.eye(n, dtype=torch.bool, device="cuda")
             t = torch.sqrt(5.0 * torch.where(off, e2, torch.ones_like(e2)))
             kap = torch.where(off, (1.0 + t + t * t / 3.0) * torch.exp(-t), torch.ones_like(e2))
-        ky = leaves[2].exp() * kap + leaves[1] * torch.eye(n, dtype=F64, device="cuda")
+        ky = leaves[2].exp() * (torch.exp(-0.5 * e2t) if trend else kap) + leaves[1] * torch.eye(n, dtype=F64, device="cuda")
+        if trend:
+            ky = ky + log_ss.exp() * kap
         low = torch.linalg.cholesky(ky)
         r = y - leaves[0]
         alpha = torch.cholesky_solve(r[:, None], low)[:, 0]
         mll = -0.5 * r @ alpha - torch.log(low.diagonal()).sum() - 0.5 * n * math.log(2.0 * math.pi)
         mll.backward()
-        tail = [log_alpha.grad.reshape(1)] if kind == L.KERNEL_RQ else [log_p.grad] if kind == L.KERNEL_PERIODIC else [log_lam.grad, log_p.grad] if local else []
+        tail = [log_alpha.grad.reshape(1)] if kind == L.KERNEL_RQ else [log_p.grad] if kind == L.KERNEL_PERIODIC else [log_env.grad, log_lam.grad, log_p.grad, log_ss.grad.reshape(1)] if trend else [log_lam.grad, log_p.grad] if local else []
         result["out"] = torch.cat([mll.detach().reshape(1), torch.stack([t.grad for t in leaves]), log_ls.grad] + tail)
 
     return timed(run, repeats), result["out"].cpu()

@@ -6,8 +6,9 @@
   materialised  pls_kernel_gram into an n x t plane, then pls_gemm_tn (plane^T alpha): what ExactGP.predict does for its mean
 
 for RBF, Matern-5/2, the rational-quadratic kernel (alpha = ln 2), the periodic kernel (lengthscales (0.5 + U) d, period
-lengths 0.5 + 2.5 U) and the locally periodic kernel (the periodic kernel's parameters under envelope lengthscales
-(1 + U) sqrt(d)) at (n, t, d) = (500, 1000, 1), (2000, 6500, 8), (5000, 36000, 8).  After a warm-up of each route the
+lengths 0.5 + 2.5 U), the locally periodic kernel (the periodic kernel's parameters under envelope lengthscales
+(1 + U) sqrt(d)) and the trend-plus-seasonal kernel (the locally periodic kernel as the seasonal term, s_s = 0.9, under trend
+lengthscales (2 + U) sqrt(d)) at (n, t, d) = (500, 1000, 1), (2000, 6500, 8), (5000, 36000, 8).  After a warm-up of each route the
 timed calls alternate between the routes, each between its own pair of HIP events on torch's stream (the protocol of
 tools/matern_gram_probe.py), so that drifts of clock or temperature fall on both alike.  Prints per route the median and
 the 10th-90th percentile, the largest |fused - materialised| relative to the outputscale, the peak device memory of each
@@ -24,7 +25,7 @@ import projected_langevin_sampling_amd as pkg
 
 L = pkg._lib
 KINDS = {L.KERNEL_RBF_ARD: "rbf", L.KERNEL_MATERN52: "matern52", L.KERNEL_RQ: "rq", L.KERNEL_PERIODIC: "periodic",
-         L.KERNEL_LOCALLY_PERIODIC: "locally_periodic"}
+         L.KERNEL_LOCALLY_PERIODIC: "locally_periodic", L.KERNEL_TREND_SEASONAL: "trend_seasonal"}
 SHAPES = [(500, 1000, 1), (2000, 6500, 8), (5000, 36000, 8)]
 S, MEAN = 1.7, 0.3
 
@@ -52,6 +53,9 @@ def main():
         kernels = [pkg.ARDKernel(ls), pkg.MaternKernel(ls, nu=2.5), pkg.RQKernel(ls, alpha=0.6931471805599453),
                    pkg.PeriodicKernel(lam, period_length=period),
                    pkg.LocallyPeriodicKernel(envelope, periodic_lengthscale=lam, period_length=period)]
+        trend = (2.0 + torch.rand(d, generator=g, dtype=torch.float64)) * d**0.5  # (drawn last: the other kernels keep their draws)
+        kernels.append(pkg.TrendSeasonalKernel(trend, seasonal_lengthscale=envelope, periodic_lengthscale=lam, period_length=period,
+                                               seasonal_outputscale=0.9))
         for kernel in kernels:
             kind, kind_name = kernel.kind, KINDS[kernel.kind]
             ls = kernel._lengthscale_host(d).cuda()  # (the lengthscales, then the family's shape values)

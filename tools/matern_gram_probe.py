@@ -7,7 +7,8 @@ one process (ctypes, RTLD_LOCAL); the RBF-ARD kind is timed for all of them, the
 7 or later, the rational-quadratic kind (alpha = ln 2, behind the lengthscales) for those that export the kind-aware workspace queries,
 the periodic kind (period lengths 0.5 + 2.5 U behind the lengthscales) for those that do not call kind 8 unknown, the locally
 periodic kind (the same periodic parameters behind envelope lengthscales (1 + U) sqrt(D)) for those that do not call kind 10
-unknown.  After a warm-up of each (library, kind), the timed launches go round-robin over all (library, kind) pairs, each
+unknown, the trend-plus-seasonal kind (the locally periodic parameters behind trend lengthscales (2 + U) sqrt(D), s_s = 0.9) for
+those that do not call kind 12 unknown.  After a warm-up of each (library, kind), the timed launches go round-robin over all (library, kind) pairs, each
 between its own pair of HIP events on torch's stream, so that drifts of clock or temperature fall on every pair alike.
 Prints one line per pair (median, 10th-90th percentile, min, max, median / first library's RBF median) and a JSON line."""
 import argparse
@@ -22,7 +23,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from projected_langevin_sampling_amd import kernel as K  # noqa: E402  (parameter holders only: no library is loaded through it)
 
-KINDS = {0: "rbf", 2: "matern12", 3: "matern32", 4: "matern52", 6: "rq", 8: "periodic", 10: "locally_periodic"}
+KINDS = {0: "rbf", 2: "matern12", 3: "matern32", 4: "matern52", 6: "rq", 8: "periodic", 10: "locally_periodic", 12: "trend_seasonal"}
 SHAPES = [("configs[1] k(Z,X)", 1024, 100_000, 8), ("configs[2] k(Z,X)", 512, 50_000, 8)]
 
 
@@ -47,7 +48,7 @@ def main():
         name, path = spec.split("=", 1)
         lib = load(path)
         kinds = [0] + ([2, 3, 4] if lib.pls_abi_version() >= 7 else []) + ([6] if hasattr(lib, "pls_gp_mll_workspace_bytes_kind") else [])
-        for kind in (8, 10):
+        for kind in (8, 10, 12):
             lib.pls_kernel_gram(kind, 8, 1, 8, 1, 1, None, 1.0, 8, 1, None)  # (refused before any launch: unknown, or "needs lengthscale")
             kinds += [kind] if b"unknown" not in lib.pls_last_error() else []
         libs.append((name, lib, kinds))
@@ -65,6 +66,9 @@ def main():
         kernels = [K.ARDKernel(ls)] + [K.MaternKernel(ls, nu=nu) for nu in (0.5, 1.5, 2.5)] + [
             K.RQKernel(ls, alpha=0.6931471805599453), K.PeriodicKernel(ls, period_length=period),
             K.LocallyPeriodicKernel(envelope, periodic_lengthscale=ls, period_length=period)]
+        trend = (2.0 + torch.rand(d, generator=g, dtype=torch.float64)) * d**0.5  # (drawn last: the other kinds keep their draws)
+        kernels.append(K.TrendSeasonalKernel(trend, seasonal_lengthscale=envelope, periodic_lengthscale=ls, period_length=period,
+                                             seasonal_outputscale=0.9))
         params = {k.kind: k._lengthscale_host(d).cuda() for k in kernels}  # (per kind: the lengthscales, then its shape values)
         out = torch.empty(n1, n2, dtype=torch.float64, device="cuda")
         pairs = [(name, lib, kind) for name, lib, kinds in libs for kind in kinds]
