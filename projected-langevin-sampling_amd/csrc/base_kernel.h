@@ -1,10 +1,11 @@
 // What the pairwise kernels of base_kernel.hip share (Gram build, gradient reduction, fused predictive mean): tile geometry,
-// the pre-scaled staging of the points, the distance sum of a pair, the KIND x D_MAX dispatch.  The pair's value: kernel_math.h.
-// The periodic kind is not a function of one distance sum: its points are staged UNSCALED, its two scales per coordinate
-// sit in LDS, and its pair loop (periodic_exponent, periodic_factors) evaluates every coordinate on its own.  The locally
-// periodic kind does the same with a third scale per coordinate, the envelope's 1 / l_k (locally_periodic_exponent,
-// locally_periodic_factors).  The trend-plus-seasonal kind is the locally periodic one with a fourth scale per coordinate, the
-// trend's 1 / l_k, and a second sum beside the exponent (trend_seasonal_exponents, trend_seasonal_factors).
+// the table of kind facts and what follows from it, the staging of the scales and of the points, the loops over the
+// coordinates of a pair, the KIND x D_MAX dispatch.  The pair's value: kernel_math.h.
+// Two schemes.  A distance-sum kind (RBF, Matern, RQ) stages its points times 1 / l_k and evaluates a pair from one sum of
+// squares (pair_dist2).  A per-coordinate kind (periodic, locally periodic, trend plus seasonal) stages its points UNSCALED,
+// keeps one scale per coordinate and parameter block in LDS, and evaluates every coordinate on its own (kernel_math.h:
+// pair_coord; here pair_exponents and pair_factors_kept).  Such a kind is its row of kind_facts, its coordinate function and
+// its entry function (kernel_math.h); everything else in this file and in base_kernel.hip is derived from the row.
 #pragma once
 #include "common.h"
 #include "kernel_math.h"
@@ -14,33 +15,46 @@ namespace plship {
 // A workgroup of the Gram build or of the reduction covers PAIR_ROWS rows x PAIR_COLS columns of the pair matrix: 256
 // threads, a pair of columns each, walking down the rows.  PAIR_D_MAX: the largest input dimension of every pairwise kernel.
 constexpr int PAIR_ROWS = 64, PAIR_COLS = 512, PAIR_D_MAX = 64;
-// the periodic kind's own limit: its reduction carries 2 D_MAX + 1 accumulators per thread, at 16 what RBF carries at 32
-constexpr int PERIODIC_D_MAX = 16;
-// the kinds whose points are staged unscaled and whose coordinates go through periodic_coord; the first two share
-// PERIODIC_D_MAX (the locally periodic reduction carries 3 D_MAX + 1 accumulators and splits a column's coordinates in two
-// halves above 8)
-constexpr bool periodic_like(int kind) {
-  return kind == PLS_KERNEL_PERIODIC || kind == PLS_KERNEL_LOCALLY_PERIODIC || kind == PLS_KERNEL_TREND_SEASONAL;
+
+// What the library knows of a kernel kind.  Its `lengthscale` argument holds the d lengthscales, then `blocks` blocks of d
+// values, then `scalars` values: RQ alpha; periodic lambda | p (the lengthscales ARE lambda); locally periodic l | lambda | p;
+// trend plus seasonal l | m | lambda | p, then s_s.
+// d_max: the reduction carries (1 + blocks) D_MAX + 1 + scalars accumulators per thread -- periodic 33 at 16, what RBF carries
+// at 32; locally periodic 49 at 16; trend plus seasonal 34 at 8, and it would carry 66 beside the factors at 16.
+struct KindFacts {
+  int blocks;        // per-dimension blocks behind the d lengthscales
+  int scalars;       // scalars behind those blocks
+  int d_max;         // the largest input dimension
+  bool per_coord;    // points staged unscaled, every coordinate evaluated on its own
+  int terms;         // kappas of a pair, each with its own outputscale and underflow decision; 0: not a kind
+  const char *noun;  // of check_kind_dim's message, where d_max is the kind's own
+};
+constexpr KindFacts kind_facts(int kind) {
+  switch (kind) {
+    case PLS_KERNEL_RBF_ARD:
+    case PLS_KERNEL_LINEAR:
+    case PLS_KERNEL_MATERN12:
+    case PLS_KERNEL_MATERN32:
+    case PLS_KERNEL_MATERN52: return {0, 0, PAIR_D_MAX, false, 1, nullptr};
+    case PLS_KERNEL_RQ: return {0, 1, PAIR_D_MAX, false, 1, nullptr};
+    case PLS_KERNEL_PERIODIC: return {1, 0, 16, true, 1, "periodic"};
+    case PLS_KERNEL_LOCALLY_PERIODIC: return {2, 0, 16, true, 1, "locally periodic"};
+    case PLS_KERNEL_TREND_SEASONAL: return {3, 1, 8, true, 2, "trend-plus-seasonal"};
+    default: return {0, 0, PAIR_D_MAX, false, 0, nullptr};
+  }
 }
-// the trend-plus-seasonal kind's own limit: its reduction carries 4 D_MAX + 2 accumulators per thread, 34 at 8 (the locally
-// periodic kind carries 49 at 16); at 16 they would be 66 beside the factors
-constexpr int TREND_SEASONAL_D_MAX = 8;
-static inline int64_t kind_d_max(int32_t kind) {
-  return kind == PLS_KERNEL_TREND_SEASONAL ? TREND_SEASONAL_D_MAX : periodic_like(kind) ? PERIODIC_D_MAX : PAIR_D_MAX;
-}
+constexpr bool periodic_like(int kind) { return kind_facts(kind).per_coord; }
+static inline int64_t kind_d_max(int32_t kind) { return kind_facts(kind).d_max; }
+// rows of a kind's scale block in LDS: one per parameter block of a per-coordinate kind, else the one of 1 / l_k
+constexpr int scale_rows(int kind) { return periodic_like(kind) ? 1 + kind_facts(kind).blocks : 1; }
 
 // pls_kernel_mean: test points of a workgroup (one per lane, the four waves split the training points), and the training
 // points staged in LDS at a time: 32 KiB of pre-scaled coordinates, 512 points at the most; a multiple of 4 for every D_MAX
 constexpr int MEAN_POINTS = 64;
 constexpr int mean_chunk(int d_max) { return 4096 / d_max < 512 ? 4096 / d_max : 512; }
 
-// shape parameters of a kind: they follow the d lengthscales in its `lengthscale` argument (RQ: alpha; periodic: the d
-// period lengths; locally periodic: the d periodic lengthscales, then the d period lengths; trend plus seasonal: the seasonal
-// term's d envelope lengthscales, d periodic lengthscales and d period lengths, then its outputscale)
-static inline int64_t kind_shape_params(int32_t kind, int64_t d) {
-  return kind == PLS_KERNEL_RQ ? 1 : kind == PLS_KERNEL_PERIODIC ? d : kind == PLS_KERNEL_LOCALLY_PERIODIC ? 2 * d :
-         kind == PLS_KERNEL_TREND_SEASONAL ? 3 * d + 1 : 0;
-}
+// shape parameters of a kind: what follows the d lengthscales in its `lengthscale` argument
+static inline int64_t kind_shape_params(int32_t kind, int64_t d) { return kind_facts(kind).blocks * d + kind_facts(kind).scalars; }
 // sums of the reduction: the kappa sum, one per lengthscale, one per shape parameter
 static inline int64_t grad_sums_count(int32_t kind, int64_t d) { return d + 1 + kind_shape_params(kind, d); }
 
@@ -50,19 +64,12 @@ static inline size_t grad_sums_workspace_bytes(int32_t kind, int64_t n, int64_t 
   return (size_t)grad_sums_blocks(n) * (size_t)grad_sums_count(kind, d) * sizeof(double);
 }
 
-static inline bool stationary_kind(int32_t kind) {
-  return kind == PLS_KERNEL_RBF_ARD || kind == PLS_KERNEL_MATERN12 || kind == PLS_KERNEL_MATERN32 || kind == PLS_KERNEL_MATERN52 ||
-         kind == PLS_KERNEL_RQ || periodic_like(kind);
-}
+static inline bool stationary_kind(int32_t kind) { return kind != PLS_KERNEL_LINEAR && kind_facts(kind).terms > 0; }
 // what every entry checks after the kind and d >= 1: the kind's largest input dimension, under the entry's name `who`
 static inline int check_kind_dim(const char *who, int32_t kind, int64_t d) {
-  PLS_REQUIRE(kind != PLS_KERNEL_PERIODIC || d <= PERIODIC_D_MAX,
-              "%s: input dimension %lld > 16 is not supported for the periodic kernel", who, (long long)d);
-  PLS_REQUIRE(kind != PLS_KERNEL_LOCALLY_PERIODIC || d <= PERIODIC_D_MAX,
-              "%s: input dimension %lld > 16 is not supported for the locally periodic kernel", who, (long long)d);
-  PLS_REQUIRE(kind != PLS_KERNEL_TREND_SEASONAL || d <= TREND_SEASONAL_D_MAX,
-              "%s: input dimension %lld > 8 is not supported for the trend-plus-seasonal kernel", who, (long long)d);
-  PLS_REQUIRE(d <= PAIR_D_MAX, "%s: input dimension %lld > 64 is not supported", who, (long long)d);
+  const KindFacts f = kind_facts(kind);
+  PLS_REQUIRE(d <= f.d_max, "%s: input dimension %lld > %d is not supported%s%s%s", who, (long long)d, f.d_max,
+              f.noun ? " for the " : "", f.noun ? f.noun : "", f.noun ? " kernel" : "");
   return PLS_OK;
 }
 
@@ -77,91 +84,49 @@ int grad_sums_launch(int kind, const double *x, int64_t n, int d, const double *
                      const double *alpha, const double *P, int64_t ldp, double *out, double *partials, hipStream_t st);
 
 // The KIND x D_MAX instantiations of a base kernel's per-pair loops: f(integral_constant<KIND>, integral_constant<D_MAX>), D_MAX
-// the input dimension rounded up to 1, 2, 4, ..., 64 (periodic and locally periodic: ..., 16; trend plus seasonal: ..., 8; kind
-// and d already validated).  LINEAR: with the linear
+// the input dimension rounded up to 1, 2, 4, ..., the kind's d_max (kind and d already validated).  LINEAR: with the linear
 // kind (the Gram build).
+template <int D_MAX, class K, class F>
+static int for_dmax_from(int d, K k, F &&f) {
+  if constexpr (D_MAX < kind_facts(K::value).d_max)
+    if (d > D_MAX) return for_dmax_from<2 * D_MAX>(d, k, f);
+  return f(k, std::integral_constant<int, D_MAX>{});
+}
 template <bool LINEAR, class F>
 static int for_kind_dmax(int kind, int d, F &&f) {
   using std::integral_constant;
-  auto with_kind = [&](auto k) {
-    if (d <= 1) return f(k, integral_constant<int, 1>{});
-    if (d <= 2) return f(k, integral_constant<int, 2>{});
-    if (d <= 4) return f(k, integral_constant<int, 4>{});
-    if (d <= 8) return f(k, integral_constant<int, 8>{});
-    if (d <= 16) return f(k, integral_constant<int, 16>{});
-    if (d <= 32) return f(k, integral_constant<int, 32>{});
-    return f(k, integral_constant<int, 64>{});
-  };
-  if constexpr (LINEAR) if (kind == PLS_KERNEL_LINEAR) return with_kind(integral_constant<int, PLS_KERNEL_LINEAR>{});
-  auto with_periodic_kind = [&](auto k) {
-    if (d <= 1) return f(k, integral_constant<int, 1>{});
-    if (d <= 2) return f(k, integral_constant<int, 2>{});
-    if (d <= 4) return f(k, integral_constant<int, 4>{});
-    if (d <= 8) return f(k, integral_constant<int, 8>{});
-    return f(k, integral_constant<int, PERIODIC_D_MAX>{});
-  };
-  if (kind == PLS_KERNEL_PERIODIC) return with_periodic_kind(integral_constant<int, PLS_KERNEL_PERIODIC>{});
-  if (kind == PLS_KERNEL_LOCALLY_PERIODIC) return with_periodic_kind(integral_constant<int, PLS_KERNEL_LOCALLY_PERIODIC>{});
-  if (kind == PLS_KERNEL_TREND_SEASONAL) {
-    const integral_constant<int, PLS_KERNEL_TREND_SEASONAL> k{};
-    if (d <= 1) return f(k, integral_constant<int, 1>{});
-    if (d <= 2) return f(k, integral_constant<int, 2>{});
-    if (d <= 4) return f(k, integral_constant<int, 4>{});
-    return f(k, integral_constant<int, TREND_SEASONAL_D_MAX>{});
-  }
+  if constexpr (LINEAR)
+    if (kind == PLS_KERNEL_LINEAR) return for_dmax_from<1>(d, integral_constant<int, PLS_KERNEL_LINEAR>{}, f);
   switch (kind) {
-    case PLS_KERNEL_RBF_ARD: return with_kind(integral_constant<int, PLS_KERNEL_RBF_ARD>{});
-    case PLS_KERNEL_MATERN12: return with_kind(integral_constant<int, PLS_KERNEL_MATERN12>{});
-    case PLS_KERNEL_MATERN32: return with_kind(integral_constant<int, PLS_KERNEL_MATERN32>{});
-    case PLS_KERNEL_RQ: return with_kind(integral_constant<int, PLS_KERNEL_RQ>{});
-    default: return with_kind(integral_constant<int, PLS_KERNEL_MATERN52>{});
+    case PLS_KERNEL_RBF_ARD: return for_dmax_from<1>(d, integral_constant<int, PLS_KERNEL_RBF_ARD>{}, f);
+    case PLS_KERNEL_MATERN12: return for_dmax_from<1>(d, integral_constant<int, PLS_KERNEL_MATERN12>{}, f);
+    case PLS_KERNEL_MATERN32: return for_dmax_from<1>(d, integral_constant<int, PLS_KERNEL_MATERN32>{}, f);
+    case PLS_KERNEL_RQ: return for_dmax_from<1>(d, integral_constant<int, PLS_KERNEL_RQ>{}, f);
+    case PLS_KERNEL_PERIODIC: return for_dmax_from<1>(d, integral_constant<int, PLS_KERNEL_PERIODIC>{}, f);
+    case PLS_KERNEL_LOCALLY_PERIODIC: return for_dmax_from<1>(d, integral_constant<int, PLS_KERNEL_LOCALLY_PERIODIC>{}, f);
+    case PLS_KERNEL_TREND_SEASONAL: return for_dmax_from<1>(d, integral_constant<int, PLS_KERNEL_TREND_SEASONAL>{}, f);
+    default: return for_dmax_from<1>(d, integral_constant<int, PLS_KERNEL_MATERN52>{}, f);
   }
 }
 
-// inv_ls[k] = sqrt(2 nu) / l_k for a stationary kind (the distance sum is then r^2 or t^2 itself; RQ keeps r^2 and divides by
-// 2 alpha per pair, so that its derivative factors are the header's), 1 for the linear kernel,
-// 0 for the padding k >= d: zero on both sides of a pair, so the unrolled coordinate loops need no `k < d` test.
-// Periodic: inv_ls[k] = 1 / p_k (the period lengths follow the d lengthscales) and two_inv_l[k] = 2 / lambda_k, both 0 for the
-// padding; the points themselves stay unscaled (pair_scaled).  The other kinds leave two_inv_l, an array of one, alone.
-// Locally periodic (l, lambda, p in blocks of d): inv_env[k] = 1 / l_k, inv_ls[k] = 1 / p_k and two_inv_l[k] = 2 / lambda_k as
-// for periodic, all three 0 for the padding.  Every other kind leaves inv_env, an array of one, alone.
-// Trend plus seasonal (l, m, lambda, p in blocks of d, then s_s): inv_trend[k] = 1 / l_k, and the locally periodic kind's three
-// arrays from (m, lambda, p), all four 0 for the padding.  Every other kind leaves inv_trend, an array of one, alone.
-template <int KIND>
-constexpr int periodic_len(int d_max) { return periodic_like(KIND) ? d_max : 1; }
-template <int KIND>
-constexpr int envelope_len(int d_max) {
-  return (KIND == PLS_KERNEL_LOCALLY_PERIODIC || KIND == PLS_KERNEL_TREND_SEASONAL) ? d_max : 1;
-}
-template <int KIND>
-constexpr int trend_len(int d_max) { return KIND == PLS_KERNEL_TREND_SEASONAL ? d_max : 1; }
-template <int KIND, int D_MAX, int NP, int NE, int NT>
-__device__ __forceinline__ void stage_inv_lengthscale(double (&inv_ls)[D_MAX], double (&two_inv_l)[NP], double (&inv_env)[NE],
-                                                      double (&inv_trend)[NT], const double *lengthscale, int d) {
+// The scale block of a workgroup, scale_rows(KIND) rows of D_MAX, and the only statement of what it holds: row j is block j of
+// the `lengthscale` argument as numerator / value, 0 for the padding k >= d -- zero on both sides of a pair, so the unrolled
+// coordinate loops need no `k < d` test.  Distance-sum kinds: sqrt(2 nu) / l_k (the distance sum is then r^2 or t^2 itself; RQ
+// keeps r^2 and divides by 2 alpha per pair, so that its derivative factors are the header's); the linear kernel: 1.
+// Per-coordinate kinds: 2 over lambda_k, the last block but one, and 1 over every other value (kernel_math.h: pair_coord).
+template <int KIND, int D_MAX>
+__device__ __forceinline__ void stage_scales(double (&scales)[scale_rows(KIND)][D_MAX], const double *lengthscale, int d) {
+  constexpr int NS = scale_rows(KIND);
   const int t = threadIdx.x;
-  if constexpr (KIND == PLS_KERNEL_TREND_SEASONAL) {
-    if (t < D_MAX) {
-      inv_trend[t] = (t < d) ? 1.0 / lengthscale[t] : 0.0;
-      inv_env[t] = (t < d) ? 1.0 / lengthscale[d + t] : 0.0;
-      two_inv_l[t] = (t < d) ? 2.0 / lengthscale[2 * d + t] : 0.0;
-      inv_ls[t] = (t < d) ? 1.0 / lengthscale[3 * d + t] : 0.0;
+  if (t < D_MAX) {
+#pragma unroll
+    for (int j = 0; j < NS; ++j) {
+      const double numerator = periodic_like(KIND) ? (j == NS - 2 ? 2.0 : 1.0) : matern_t_scale(KIND);
+      scales[j][t] = (t < d) ? ((KIND != PLS_KERNEL_LINEAR) ? numerator / lengthscale[j * d + t] : 1.0) : 0.0;
     }
-  } else if constexpr (KIND == PLS_KERNEL_LOCALLY_PERIODIC) {
-    if (t < D_MAX) {
-      inv_env[t] = (t < d) ? 1.0 / lengthscale[t] : 0.0;
-      two_inv_l[t] = (t < d) ? 2.0 / lengthscale[d + t] : 0.0;
-      inv_ls[t] = (t < d) ? 1.0 / lengthscale[2 * d + t] : 0.0;
-    }
-  } else if constexpr (KIND == PLS_KERNEL_PERIODIC) {
-    if (t < D_MAX) {
-      inv_ls[t] = (t < d) ? 1.0 / lengthscale[d + t] : 0.0;
-      two_inv_l[t] = (t < d) ? 2.0 / lengthscale[t] : 0.0;
-    }
-  } else {
-    if (t < D_MAX) inv_ls[t] = (t < d) ? ((KIND != PLS_KERNEL_LINEAR) ? matern_t_scale(KIND) / lengthscale[t] : 1.0) : 0.0;
   }
 }
-// a coordinate as a pairwise kernel holds it: times its inverse lengthscale, or as it is for the periodic kinds
+// a coordinate as a pairwise kernel holds it: times its inverse lengthscale, or as it is for the per-coordinate kinds
 template <int KIND>
 __device__ __forceinline__ double pair_scaled(double v, double inv_ls) {
   return periodic_like(KIND) ? v : v * inv_ls;
@@ -200,134 +165,62 @@ __device__ __forceinline__ void pair_dist2(const double (&a)[D_MAX], const doubl
   }
 }
 
-// The periodic pair loops (kernel_math.h: periodic_coord): the negated exponent of a staged row a and one point b, and of a
-// and a thread's pair of columns; inv_p and two_inv_l are read from LDS (broadcast), once for both columns.
-template <int D_MAX>
-__device__ __forceinline__ double periodic_exponent(const double (&a)[D_MAX], const double (&b)[D_MAX],
-                                                    const double (&inv_p)[D_MAX], const double (&two_inv_l)[D_MAX]) {
-  double q = 0.0, unused;
+// The coordinate loops of the per-coordinate kinds (kernel_math.h: pair_coord): q, the negated exponent, and s, the trend's
+// distance sum (0 where the kind has none), both added in ascending k, of a staged row a and one point b, and of a and a
+// thread's pair of columns; a[k] and column k of the scales are read from LDS (broadcast) once for both columns.
+template <int NS, int D_MAX>
+__device__ __forceinline__ void scale_column(const double (&scales)[NS][D_MAX], int k, double (&sc)[NS]) {
 #pragma unroll
-  for (int k = 0; k < D_MAX; ++k) q = __dadd_rn(q, periodic_coord<false>(a[k] - b[k], inv_p[k], two_inv_l[k], unused));
-  return q;
+  for (int j = 0; j < NS; ++j) sc[j] = scales[j][k];
 }
-template <int D_MAX>
-__device__ __forceinline__ void periodic_exponent(const double (&a)[D_MAX], const double (&b0)[D_MAX], const double (&b1)[D_MAX],
-                                                  const double (&inv_p)[D_MAX], const double (&two_inv_l)[D_MAX], double &q0,
-                                                  double &q1) {
-  double unused;
-  q0 = q1 = 0.0;
-#pragma unroll
-  for (int k = 0; k < D_MAX; ++k) {
-    const double ak = a[k], ip = inv_p[k], tl = two_inv_l[k];
-    q0 = __dadd_rn(q0, periodic_coord<false>(ak - b0[k], ip, tl, unused));
-    q1 = __dadd_rn(q1, periodic_coord<false>(ak - b1[k], ip, tl, unused));
-  }
-}
-// the same sum with the pair's factors kept: fl[k] = (2 / lambda_k) sin^2(pi e_k), fp[k] = (2 / lambda_k) pi e_k sin(2 pi e_k);
-// dK / d log lambda_k = s kappa fl[k], dK / d log p_k = s kappa fp[k]
-template <int D_MAX>
-__device__ __forceinline__ double periodic_factors(const double (&a)[D_MAX], const double (&b)[D_MAX], const double (&inv_p)[D_MAX],
-                                                   const double (&two_inv_l)[D_MAX], double (&fl)[D_MAX], double (&fp)[D_MAX]) {
-  double q = 0.0;
-#pragma unroll
-  for (int k = 0; k < D_MAX; ++k) {
-    fl[k] = periodic_coord<true>(a[k] - b[k], inv_p[k], two_inv_l[k], fp[k]);
-    q = __dadd_rn(q, fl[k]);
-  }
-  return q;
-}
-
-// The locally periodic pair loops (kernel_math.h: locally_periodic_coord), laid out as the periodic ones: the negated
-// exponent, each coordinate's two shares added first, then the coordinates in ascending k.
-template <int D_MAX>
-__device__ __forceinline__ double locally_periodic_exponent(const double (&a)[D_MAX], const double (&b)[D_MAX],
-                                                            const double (&inv_l)[D_MAX], const double (&inv_p)[D_MAX],
-                                                            const double (&two_inv_lam)[D_MAX]) {
-  double q = 0.0, u0, u1, u2;
-#pragma unroll
-  for (int k = 0; k < D_MAX; ++k)
-    q = __dadd_rn(q, locally_periodic_coord<false>(a[k] - b[k], inv_l[k], inv_p[k], two_inv_lam[k], u0, u1, u2));
-  return q;
-}
-template <int D_MAX>
-__device__ __forceinline__ void locally_periodic_exponent(const double (&a)[D_MAX], const double (&b0)[D_MAX],
-                                                          const double (&b1)[D_MAX], const double (&inv_l)[D_MAX],
-                                                          const double (&inv_p)[D_MAX], const double (&two_inv_lam)[D_MAX],
-                                                          double &q0, double &q1) {
-  double u0, u1, u2;
-  q0 = q1 = 0.0;
-#pragma unroll
-  for (int k = 0; k < D_MAX; ++k) {
-    const double ak = a[k], il = inv_l[k], ip = inv_p[k], tl = two_inv_lam[k];
-    q0 = __dadd_rn(q0, locally_periodic_coord<false>(ak - b0[k], il, ip, tl, u0, u1, u2));
-    q1 = __dadd_rn(q1, locally_periodic_coord<false>(ak - b1[k], il, ip, tl, u0, u1, u2));
-  }
-}
-// The reduction keeps the factors of a column's first KEEP coordinates between the exponent sum and the accumulation and
-// evaluates the others a second time afterwards (the same function of the same operands: the same bits), so that at
-// D_MAX = 16 no more than 24 factors are live beside the 49 accumulators.
-constexpr int locally_periodic_keep(int d_max) { return d_max > 8 ? d_max / 2 : d_max; }
-// the same sum with the factors of the coordinates k < KEEP kept: fe[k] = ((a_k - b_k) / l_k)^2, fl[k] and fp[k] as
-// periodic_factors'; dK / d log l_k = s kappa fe[k], dK / d log lambda_k = s kappa fl[k], dK / d log p_k = s kappa fp[k]
-template <int D_MAX, int KEEP>
-__device__ __forceinline__ double locally_periodic_factors(const double (&a)[D_MAX], const double (&b)[D_MAX],
-                                                           const double (&inv_l)[D_MAX], const double (&inv_p)[D_MAX],
-                                                           const double (&two_inv_lam)[D_MAX], double (&fe)[KEEP],
-                                                           double (&fl)[KEEP], double (&fp)[KEEP]) {
-  double q = 0.0, u0, u1, u2;
-#pragma unroll
-  for (int k = 0; k < D_MAX; ++k) {
-    if (k < KEEP)
-      q = __dadd_rn(q, locally_periodic_coord<true>(a[k] - b[k], inv_l[k], inv_p[k], two_inv_lam[k], fe[k % KEEP], fl[k % KEEP],
-                                                    fp[k % KEEP]));
-    else
-      q = __dadd_rn(q, locally_periodic_coord<false>(a[k] - b[k], inv_l[k], inv_p[k], two_inv_lam[k], u0, u1, u2));
-  }
-  return q;
-}
-
-// The trend-plus-seasonal pair loops (kernel_math.h: trend_seasonal_coord), laid out as the locally periodic ones: q, the
-// seasonal term's negated exponent, is locally_periodic_exponent's of (inv_m, inv_p, two_inv_lam) bit for bit; s, the trend's
-// distance sum, is accumulated beside it from the same differences, in ascending k.
-template <int D_MAX>
-__device__ __forceinline__ void trend_seasonal_exponents(const double (&a)[D_MAX], const double (&b)[D_MAX],
-                                                         const double (&inv_t)[D_MAX], const double (&inv_m)[D_MAX],
-                                                         const double (&inv_p)[D_MAX], const double (&two_inv_lam)[D_MAX],
-                                                         double &s, double &q) {
-  double u0, u1, u2, u3;
+template <int KIND, int NS, int D_MAX>
+__device__ __forceinline__ void pair_exponents(const double (&a)[D_MAX], const double (&b)[D_MAX],
+                                               const double (&scales)[NS][D_MAX], double &s, double &q) {
+  double sc[NS], unused[NS];
   s = q = 0.0;
 #pragma unroll
-  for (int k = 0; k < D_MAX; ++k)
-    q = __dadd_rn(q, trend_seasonal_coord<false>(a[k] - b[k], inv_t[k], inv_m[k], inv_p[k], two_inv_lam[k], s, u0, u1, u2, u3));
+  for (int k = 0; k < D_MAX; ++k) {
+    scale_column(scales, k, sc);
+    q = __dadd_rn(q, pair_coord<KIND, false>(a[k] - b[k], sc, s, unused));
+  }
 }
-template <int D_MAX>
-__device__ __forceinline__ void trend_seasonal_exponents(const double (&a)[D_MAX], const double (&b0)[D_MAX],
-                                                         const double (&b1)[D_MAX], const double (&inv_t)[D_MAX],
-                                                         const double (&inv_m)[D_MAX], const double (&inv_p)[D_MAX],
-                                                         const double (&two_inv_lam)[D_MAX], double &s0, double &q0, double &s1,
-                                                         double &q1) {
-  double u0, u1, u2, u3;
+template <int KIND, int NS, int D_MAX>
+__device__ __forceinline__ void pair_exponents(const double (&a)[D_MAX], const double (&b0)[D_MAX], const double (&b1)[D_MAX],
+                                               const double (&scales)[NS][D_MAX], double &s0, double &q0, double &s1,
+                                               double &q1) {
+  double sc[NS], unused[NS];
   s0 = q0 = s1 = q1 = 0.0;
 #pragma unroll
   for (int k = 0; k < D_MAX; ++k) {
-    const double ak = a[k], it = inv_t[k], im = inv_m[k], ip = inv_p[k], tl = two_inv_lam[k];
-    q0 = __dadd_rn(q0, trend_seasonal_coord<false>(ak - b0[k], it, im, ip, tl, s0, u0, u1, u2, u3));
-    q1 = __dadd_rn(q1, trend_seasonal_coord<false>(ak - b1[k], it, im, ip, tl, s1, u0, u1, u2, u3));
+    const double ak = a[k];
+    scale_column(scales, k, sc);
+    q0 = __dadd_rn(q0, pair_coord<KIND, false>(ak - b0[k], sc, s0, unused));
+    q1 = __dadd_rn(q1, pair_coord<KIND, false>(ak - b1[k], sc, s1, unused));
   }
 }
-// the same two sums with the pair's factors kept: ft[k] = ((a_k - b_k) / l_k)^2, dK / d log l_k = s_t kappa_t ft[k]; fe, fl and
-// fp as locally_periodic_factors', dK / d log m_k, lambda_k, p_k = s_s kappa_s fe[k], fl[k], fp[k]
-template <int D_MAX>
-__device__ __forceinline__ void trend_seasonal_factors(const double (&a)[D_MAX], const double (&b)[D_MAX],
-                                                       const double (&inv_t)[D_MAX], const double (&inv_m)[D_MAX],
-                                                       const double (&inv_p)[D_MAX], const double (&two_inv_lam)[D_MAX],
-                                                       double &s, double &q, double (&ft)[D_MAX], double (&fe)[D_MAX],
-                                                       double (&fl)[D_MAX], double (&fp)[D_MAX]) {
+// The reduction keeps the factors of a column's first KEEP coordinates between the sums and the accumulation and evaluates
+// the others a second time afterwards (the same function of the same operands: the same bits), so that no more than 32
+// factors are live beside the accumulators: every coordinate's except at locally periodic's D_MAX = 16, 24 beside 49.
+constexpr int factors_kept(int kind, int d_max) { return scale_rows(kind) * d_max > 32 ? d_max / 2 : d_max; }
+// the same sums with the factors of the coordinates k < KEEP kept: f[j][k], coordinate k's factor of dK / d log of block j's
+// parameter (kernel_math.h: pair_coord)
+template <int KIND, int KEEP, int NS, int D_MAX>
+__device__ __forceinline__ void pair_factors_kept(const double (&a)[D_MAX], const double (&b)[D_MAX],
+                                                  const double (&scales)[NS][D_MAX], double &s, double &q,
+                                                  double (&f)[NS][KEEP]) {
+  double sc[NS], fk[NS];
   s = q = 0.0;
 #pragma unroll
-  for (int k = 0; k < D_MAX; ++k)
-    q = __dadd_rn(q, trend_seasonal_coord<true>(a[k] - b[k], inv_t[k], inv_m[k], inv_p[k], two_inv_lam[k], s, ft[k], fe[k], fl[k],
-                                                fp[k]));
+  for (int k = 0; k < D_MAX; ++k) {
+    scale_column(scales, k, sc);
+    if (k < KEEP) {
+      q = __dadd_rn(q, pair_coord<KIND, true>(a[k] - b[k], sc, s, fk));
+#pragma unroll
+      for (int j = 0; j < NS; ++j) f[j][k % KEEP] = fk[j];
+    } else {
+      q = __dadd_rn(q, pair_coord<KIND, false>(a[k] - b[k], sc, s, fk));
+    }
+  }
 }
 
 }  // namespace plship

@@ -2,12 +2,10 @@
 // plus seasonal; the Gram build also the linear kernel):
 // pls_kernel_gram, pls_kernel_grad_sums, pls_kernel_mean.  The exact-GP path builds K with the first, differentiates with
 // the second and predicts with the third, so the three evaluate a pair alike: the same pre-scaled points and distance
-// sum (base_kernel.h), the same kappa (kernel_math.h).  The periodic kind has no distance sum: unscaled points, 1 / p_k and
-// 2 / lambda_k in LDS, one sincospi per coordinate (base_kernel.h: periodic_exponent, periodic_factors).  The locally periodic
-// kind is the periodic one with the envelope's 1 / l_k as a third scale in LDS and both shares of a coordinate in the one
-// exponent (locally_periodic_exponent, locally_periodic_factors).  The trend-plus-seasonal kind adds an RBF term with its own
-// outputscale to the locally periodic one: the trend's 1 / l_k as a fourth scale in LDS, its distance sum beside the seasonal
-// exponent, two exponentials and two underflow decisions per pair (trend_seasonal_exponents, trend_seasonal_factors).
+// sum (base_kernel.h), the same kappa (kernel_math.h).  The per-coordinate kinds (periodic, locally periodic, trend plus
+// seasonal) have no single distance sum: unscaled points, one row of scales per parameter block in LDS, one sincospi per
+// coordinate (base_kernel.h: pair_exponents, pair_factors_kept), and per term of the kind one exponential, one outputscale and
+// one underflow decision.  Each kernel holds ONE branch for all of them, written over the kind's row of kind_facts.
 #include <hip/hip_runtime.h>
 
 #define PLS_SCALAR_POLY_CONSTANTS 1  // (fmath.h: the exp polynomial's constants as scalar operands)
@@ -27,17 +25,13 @@ __global__ __launch_bounds__(256) void kernel_gram_kernel(const double *__restri
                                                            const double *__restrict__ x2, int64_t n2, int d,
                                                            const double *__restrict__ lengthscale, double outputscale,
                                                            double *__restrict__ out, int64_t ldout) {
-  constexpr bool PERIODIC = KIND == PLS_KERNEL_PERIODIC, LOCAL = KIND == PLS_KERNEL_LOCALLY_PERIODIC,
-                 TREND = KIND == PLS_KERNEL_TREND_SEASONAL;
-  __shared__ double inv_ls[D_MAX];                        // (the periodic kinds: 1 / p_k)
-  __shared__ double two_inv_l[periodic_len<KIND>(D_MAX)];  // (the periodic kinds: 2 / lambda_k)
-  __shared__ double inv_env[envelope_len<KIND>(D_MAX)];    // (locally periodic: 1 / l_k; trend plus seasonal: 1 / m_k)
-  __shared__ double inv_trend[trend_len<KIND>(D_MAX)];     // (trend plus seasonal: 1 / l_k)
+  __shared__ double scales[scale_rows(KIND)][D_MAX];                    // (base_kernel.h: stage_scales)
   __shared__ __attribute__((aligned(16))) double a_s[PAIR_ROWS][D_MAX];  // rows of x1 (pre-scaled, zero-padded)
+  const double(&inv_ls)[D_MAX] = scales[0];
   const int t = threadIdx.x;
   const int64_t row0 = (int64_t)blockIdx.y * PAIR_ROWS;
   const int nrows = (int)((n1 - row0 < PAIR_ROWS) ? (n1 - row0) : PAIR_ROWS);
-  stage_inv_lengthscale<KIND>(inv_ls, two_inv_l, inv_env, inv_trend, lengthscale, d);
+  stage_scales<KIND>(scales, lengthscale, d);
   const PairShape sh = load_pair_shape<KIND>(lengthscale, d);
   __syncthreads();
   stage_rows<KIND>(a_s, x1, row0, nrows, d, inv_ls);
@@ -56,18 +50,11 @@ __global__ __launch_bounds__(256) void kernel_gram_kernel(const double *__restri
 #pragma unroll 2
   for (int r = 0; r < nrows; ++r, dst += ldout) {
     double s0 = 0.0, s1 = 0.0;
-    if constexpr (TREND) {
+    if constexpr (periodic_like(KIND)) {
       double q0, q1;
-      trend_seasonal_exponents(a_s[r], b0, b1, inv_trend, inv_env, inv_ls, two_inv_l, s0, q0, s1, q1);
-      s0 = trend_seasonal_entry(s0, q0, outputscale, sh.alpha);
-      s1 = trend_seasonal_entry(s1, q1, outputscale, sh.alpha);
-    } else if constexpr (PERIODIC || LOCAL) {
-      if constexpr (LOCAL) locally_periodic_exponent(a_s[r], b0, b1, inv_env, inv_ls, two_inv_l, s0, s1);
-      else periodic_exponent(a_s[r], b0, b1, inv_ls, two_inv_l, s0, s1);
-      double kap0, kap1;
-      const bool live0 = periodic_kappa(s0, kap0), live1 = periodic_kappa(s1, kap1);
-      s0 = live0 ? outputscale * kap0 : 0.0;
-      s1 = live1 ? outputscale * kap1 : 0.0;
+      pair_exponents<KIND>(a_s[r], b0, b1, scales, s0, q0, s1, q1);
+      s0 = coord_entry<KIND>(s0, q0, outputscale, sh);
+      s1 = coord_entry<KIND>(s1, q1, outputscale, sh);
     } else if (KIND != PLS_KERNEL_LINEAR) {
       pair_dist2(a_s[r], b0, b1, s0, s1);
       s0 = gram_entry<KIND>(s0, sh, outputscale);
@@ -90,21 +77,16 @@ __global__ __launch_bounds__(256) void kernel_gram_kernel(const double *__restri
 }
 
 // The reduction over the n x n pair matrix, laid out as kernel_gram_kernel (a thread owns a PAIR of columns and walks down
-// the rows in LDS).  P is read once, 16 B per lane where ldp is even and P is 16-byte aligned.  D_MAX + 1 accumulators per
-// thread, one more for RQ; periodic: 2 D_MAX + 1, the period sums behind the lengthscale sums; locally periodic: 3 D_MAX + 1,
-// the sums of l, lambda and p in blocks.
+// the rows in LDS).  P is read once, 16 B per lane where ldp is even and P is 16-byte aligned.  With B = 1 + the kind's
+// per-dimension blocks a thread carries 1 + B D_MAX + scalars accumulators: the kappa sum, B blocks of D_MAX, the scalars.
 //   out[0]     = sum_ij W_ij kappa_ij                  (kappa: the kernel without its outputscale)
 //   out[1 + k] = sum_ij W_ij dK_ij / d log l_k         (RBF: s exp(-r^2/2) e_k^2;  Matern: s q(t) exp(-t) 2 nu e_k^2 with
 //                                                       q = 1/t, 1, (1 + t)/3 for nu = 1/2, 3/2, 5/2;  RQ: s kappa / (1 + u) e_k^2;
 //                                                       e_k = (x_ik - x_jk)/l_k)
-//                                                       periodic: s kappa (2 / lambda_k) sin^2(pi e_k), e_k = (x_ik - x_jk)/p_k
 //   out[1 + d] = sum_ij W_ij dK_ij / d log alpha       (RQ only: s alpha kappa (u / (1 + u) - log1p(u)), u = r^2 / (2 alpha))
-//   out[1 + d + k] = sum_ij W_ij dK_ij / d log p_k     (periodic only: s kappa (2 / lambda_k) pi e_k sin(2 pi e_k))
-//   locally periodic: out[1 + k] = sum_ij W_ij s kappa ((x_ik - x_jk) / l_k)^2, out[1 + d + k] and out[1 + 2 d + k] the periodic
-//   kind's sums for lambda_k and p_k, with kappa the product's
-//   trend plus seasonal (4 D_MAX + 2 accumulators): out[0] = sum_ij W_ij kappa_t, out[1 + k] = sum_ij W_ij s_t kappa_t ((x_ik -
-//   x_jk) / l_k)^2, out[1 + d + k], out[1 + 2 d + k], out[1 + 3 d + k] the locally periodic kind's three sums of (m, lambda, p) with
-//   s_s kappa_s, out[1 + 4 d] = sum_ij W_ij s_s kappa_s
+//   per-coordinate kinds: out[1 + j d + k] = sum_ij W_ij s kappa f_jk, f_jk coordinate k's factor of block j's parameter
+//   (kernel_math.h: pair_coord), s kappa the term's that the block belongs to.  Trend plus seasonal: block 0 (l) with s_t kappa_t,
+//   which is also out[0]'s kappa; blocks 1 to 3 (m, lambda, p) with s_s kappa_s, and out[1 + 4 d] = sum_ij W_ij s_s kappa_s
 // with W = alpha alpha^T - P; no atomics: per thread down its rows, then the workgroup sum below, then the workgroups'
 // partial rows in ascending order (a second one-workgroup launch).
 template <int KIND, int D_MAX>
@@ -112,23 +94,19 @@ __global__ __launch_bounds__(256) void kernel_grad_sums_kernel(const double *__r
                                                                 const double *__restrict__ lengthscale, double outputscale,
                                                                 const double *__restrict__ alpha, const double *__restrict__ P,
                                                                 int64_t ldp, double *__restrict__ partials) {
-  constexpr bool PERIODIC = KIND == PLS_KERNEL_PERIODIC, LOCAL = KIND == PLS_KERNEL_LOCALLY_PERIODIC,
-                 TREND = KIND == PLS_KERNEL_TREND_SEASONAL;
-  __shared__ double inv_ls[D_MAX];                        // (the periodic kinds: 1 / p_k)
-  __shared__ double two_inv_l[periodic_len<KIND>(D_MAX)];  // (the periodic kinds: 2 / lambda_k)
-  __shared__ double inv_env[envelope_len<KIND>(D_MAX)];    // (locally periodic: 1 / l_k; trend plus seasonal: 1 / m_k)
-  __shared__ double inv_trend[trend_len<KIND>(D_MAX)];     // (trend plus seasonal: 1 / l_k)
+  constexpr KindFacts FACTS = kind_facts(KIND);
+  __shared__ double scales[scale_rows(KIND)][D_MAX];  // (base_kernel.h: stage_scales)
   __shared__ __attribute__((aligned(16))) double a_s[PAIR_ROWS][D_MAX];
   __shared__ double al_s[PAIR_ROWS];
+  const double(&inv_ls)[D_MAX] = scales[0];
   constexpr bool SHAPE = KIND == PLS_KERNEL_RQ;
-  // (the shape sums are kept last: acc[D_MAX + 1 + j], written to slot d + 1 + j)
-  // (trend plus seasonal: the sums of l, m, lambda and p in blocks of D_MAX, then the seasonal term's own kappa sum)
-  constexpr int NACC = D_MAX + 1 + (SHAPE ? 1 : 0) + (PERIODIC ? D_MAX : 0) + (LOCAL ? 2 * D_MAX : 0) + (TREND ? 3 * D_MAX + 1 : 0);
+  // the sums of the B per-dimension blocks, D_MAX apart, then the scalars': acc[1 + B D_MAX + j], written to slot 1 + B d + j
+  constexpr int B = 1 + FACTS.blocks, NACC = 1 + B * D_MAX + FACTS.scalars;
   __shared__ double red[4][NACC];
   const int t = threadIdx.x;
   const int64_t row0 = (int64_t)blockIdx.y * PAIR_ROWS;
   const int nrows = (int)((n - row0 < PAIR_ROWS) ? (n - row0) : PAIR_ROWS);
-  stage_inv_lengthscale<KIND>(inv_ls, two_inv_l, inv_env, inv_trend, lengthscale, d);
+  stage_scales<KIND>(scales, lengthscale, d);
   const PairShape sh = load_pair_shape<KIND>(lengthscale, d);
   if (t < PAIR_ROWS) al_s[t] = (t < nrows) ? alpha[row0 + t] : 0.0;
   __syncthreads();
@@ -161,75 +139,44 @@ __global__ __launch_bounds__(256) void kernel_grad_sums_kernel(const double *__r
       }
       const double ai = al_s[r];
       const double w0 = __dsub_rn(__dmul_rn(ai, aj0), p0), w1 = __dsub_rn(__dmul_rn(ai, aj1), p1);  // W_ij, two roundings
-      if constexpr (TREND) {
-        // one column at a time: its 4 D_MAX factors live in registers between the two sums and the accumulation; each term
-        // takes its own underflow decision, and a dead one adds nothing to its sums
+      if constexpr (FACTS.per_coord) {
+        // One column at a time: the factors of its first KEEP coordinates live in registers between the sums and the
+        // accumulation, the others are evaluated again afterwards (base_kernel.h: factors_kept).  The kind's last term is
+        // the periodic one, over the blocks from FIRST on; the term in front of it, if any, is the trend's, over block 0.
+        // Each term takes its own underflow decision, and a dead one adds nothing to its sums.
+        constexpr int KEEP = factors_kept(KIND, D_MAX), FIRST = FACTS.terms - 1;
         auto column = [&](const double (&b)[D_MAX], double w, bool have) {
-          double ft[D_MAX], fe[D_MAX], fl[D_MAX], fp[D_MAX], s2, q, kt, ks;
-          trend_seasonal_factors(a_s[r], b, inv_trend, inv_env, inv_ls, two_inv_l, s2, q, ft, fe, fl, fp);
-          const bool live_t = trend_kappa(s2, kt) && have, live_s = periodic_kappa(q, ks) && have;
-          if (live_t) {
-            const double gw = w * (outputscale * kt);
-            acc[0] = fma(w, kt, acc[0]);
+          double f[B][KEEP], s2, q, kt, ks;
+          pair_factors_kept<KIND, KEEP>(a_s[r], b, scales, s2, q, f);
+          const bool live_t = FIRST > 0 && trend_kappa(s2, kt) && have, live_s = periodic_kappa(q, ks) && have;
+          if constexpr (FIRST > 0) {
+            static_assert(KEEP == D_MAX && FACTS.scalars == 1, "every factor of the trend's is kept; the last term's outputscale");
+            if (live_t) {
+              const double gw = w * (outputscale * kt);
+              acc[0] = fma(w, kt, acc[0]);
 #pragma unroll
-            for (int k = 0; k < D_MAX; ++k) acc[1 + k] = fma(gw, ft[k], acc[1 + k]);
+              for (int k = 0; k < D_MAX; ++k) acc[1 + k] = fma(gw, f[0][k], acc[1 + k]);
+            }
           }
           if (live_s) {
-            const double gw = w * (sh.alpha * ks);
-            acc[1 + 4 * D_MAX] = fma(w, sh.alpha * ks, acc[1 + 4 * D_MAX]);
+            // s kappa of the term: under the kind's outputscale, or under its own, which has its kappa sum behind the blocks
+            const double sk = (FIRST > 0 ? sh.alpha : outputscale) * ks;
+            const double gw = w * sk;
+            if constexpr (FIRST > 0) acc[1 + B * D_MAX] = fma(w, sk, acc[1 + B * D_MAX]);
+            else acc[0] = fma(w, ks, acc[0]);
 #pragma unroll
-            for (int k = 0; k < D_MAX; ++k) {
-              acc[1 + D_MAX + k] = fma(gw, fe[k], acc[1 + D_MAX + k]);
-              acc[1 + 2 * D_MAX + k] = fma(gw, fl[k], acc[1 + 2 * D_MAX + k]);
-              acc[1 + 3 * D_MAX + k] = fma(gw, fp[k], acc[1 + 3 * D_MAX + k]);
-            }
-          }
-        };
-        column(b0, w0, true);
-        column(b1, w1, two);
-      } else if constexpr (LOCAL) {
-        // one column at a time, and of its coordinates the first KEEP with their 3 KEEP factors in registers; the others
-        // are evaluated again after the exponent (base_kernel.h: locally_periodic_keep)
-        constexpr int KEEP = locally_periodic_keep(D_MAX);
-        auto column = [&](const double (&b)[D_MAX], double w, bool have) {
-          double fe[KEEP], fl[KEEP], fp[KEEP], kap;
-          const bool live =
-              periodic_kappa(locally_periodic_factors(a_s[r], b, inv_env, inv_ls, two_inv_l, fe, fl, fp), kap) && have;
-          if (live) {
-            const double gw = w * (outputscale * kap);
-            acc[0] = fma(w, kap, acc[0]);
+            for (int k = 0; k < KEEP; ++k)
 #pragma unroll
-            for (int k = 0; k < KEEP; ++k) {
-              acc[1 + k] = fma(gw, fe[k], acc[1 + k]);
-              acc[1 + D_MAX + k] = fma(gw, fl[k], acc[1 + D_MAX + k]);
-              acc[1 + 2 * D_MAX + k] = fma(gw, fp[k], acc[1 + 2 * D_MAX + k]);
-            }
+              for (int j = FIRST; j < B; ++j) acc[1 + j * D_MAX + k] = fma(gw, f[j][k], acc[1 + j * D_MAX + k]);
 #pragma unroll
             for (int k = KEEP; k < D_MAX; ++k) {
-              double e, l, p, delta = a_s[r][k] - b[k];
+              double sc[B], fk[B], unused = 0.0, delta = a_s[r][k] - b[k];
               // (opaque to the optimiser: merged with the first evaluation, its values would stay live after all)
               asm volatile("" : "+v"(delta));
-              locally_periodic_coord<true>(delta, inv_env[k], inv_ls[k], two_inv_l[k], e, l, p);
-              acc[1 + k] = fma(gw, e, acc[1 + k]);
-              acc[1 + D_MAX + k] = fma(gw, l, acc[1 + D_MAX + k]);
-              acc[1 + 2 * D_MAX + k] = fma(gw, p, acc[1 + 2 * D_MAX + k]);
-            }
-          }
-        };
-        column(b0, w0, true);
-        column(b1, w1, two);
-      } else if constexpr (PERIODIC) {
-        // one column at a time: its 2 D_MAX factors live in registers between the exponent sum and the accumulation
-        auto column = [&](const double (&b)[D_MAX], double w, bool have) {
-          double fl[D_MAX], fp[D_MAX], kap;
-          const bool live = periodic_kappa(periodic_factors(a_s[r], b, inv_ls, two_inv_l, fl, fp), kap) && have;
-          if (live) {
-            const double gw = w * (outputscale * kap);
-            acc[0] = fma(w, kap, acc[0]);
+              scale_column(scales, k, sc);
+              pair_coord<KIND, true>(delta, sc, unused, fk);
 #pragma unroll
-            for (int k = 0; k < D_MAX; ++k) {
-              acc[1 + k] = fma(gw, fl[k], acc[1 + k]);
-              acc[1 + D_MAX + k] = fma(gw, fp[k], acc[1 + D_MAX + k]);
+              for (int j = FIRST; j < B; ++j) acc[1 + j * D_MAX + k] = fma(gw, fk[j], acc[1 + j * D_MAX + k]);
             }
           }
         };
@@ -273,13 +220,15 @@ __global__ __launch_bounds__(256) void kernel_grad_sums_kernel(const double *__r
     if ((t & 63) == 0) red[t >> 6][k] = v;
   }
   __syncthreads();
-  const int nsums = d + 1 + (SHAPE ? 1 : 0) + (PERIODIC ? d : 0) + (LOCAL ? 2 * d : 0) + (TREND ? 3 * d + 1 : 0);
+  const int nsums = 1 + B * d + FACTS.scalars;
   if (t < nsums) {
     const int64_t blk = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
-    const int k = TREND      ? ((t > 4 * d) ? 4 * D_MAX + 1 : (t > 0) ? 1 + ((t - 1) / d) * D_MAX + (t - 1) % d : 0)
-                  : LOCAL    ? ((t > 2 * d) ? 2 * D_MAX + (t - 2 * d) : (t > d) ? D_MAX + (t - d) : t)
-                  : PERIODIC ? ((t > d) ? D_MAX + (t - d) : t)
-                  : (SHAPE && t == d + 1) ? D_MAX + 1 : t;
+    // slot t of the partial row: the kappa sum, the blocks d apart (D_MAX apart in acc), the scalars.  The distance-sum kinds
+    // (B = 1) keep that formula's values in the form their machine code was built from.
+    const int k = !FACTS.per_coord ? ((SHAPE && t == d + 1) ? D_MAX + 1 : t)
+                  : (t > B * d)    ? 1 + B * D_MAX + (t - 1 - B * d)
+                  : (t > 0)        ? 1 + ((t - 1) / d) * D_MAX + (t - 1) % d
+                                   : 0;
     partials[blk * nsums + t] = (red[0][k] + red[1][k]) + (red[2][k] + red[3][k]);
   }
 }
@@ -331,18 +280,15 @@ __global__ __launch_bounds__(256) void kernel_mean_kernel(const double *__restri
                                                            const double *__restrict__ xt, int64_t t,
                                                            double *__restrict__ out) {
   constexpr int CHUNK = mean_chunk(D_MAX);
-  constexpr bool PERIODIC = KIND == PLS_KERNEL_PERIODIC, LOCAL = KIND == PLS_KERNEL_LOCALLY_PERIODIC,
-                 TREND = KIND == PLS_KERNEL_TREND_SEASONAL;
-  __shared__ double inv_ls[D_MAX];                        // (the periodic kinds: 1 / p_k)
-  __shared__ double two_inv_l[periodic_len<KIND>(D_MAX)];  // (the periodic kinds: 2 / lambda_k)
-  __shared__ double inv_env[envelope_len<KIND>(D_MAX)];    // (locally periodic: 1 / l_k; trend plus seasonal: 1 / m_k)
-  __shared__ double inv_trend[trend_len<KIND>(D_MAX)];     // (trend plus seasonal: 1 / l_k)
+  constexpr bool TWO_TERMS = kind_facts(KIND).terms == 2;
+  __shared__ double scales[scale_rows(KIND)][D_MAX];  // (base_kernel.h: stage_scales)
   __shared__ __attribute__((aligned(16))) double a_s[CHUNK][D_MAX];
   __shared__ double al_s[CHUNK];
   __shared__ double red[4][MEAN_POINTS];
-  __shared__ double red_s[TREND ? 4 : 1][MEAN_POINTS];  // (trend plus seasonal: the seasonal term's sums)
+  __shared__ double red_s[TWO_TERMS ? 4 : 1][MEAN_POINTS];  // (trend plus seasonal: the seasonal term's sums)
+  const double(&inv_ls)[D_MAX] = scales[0];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  stage_inv_lengthscale<KIND>(inv_ls, two_inv_l, inv_env, inv_trend, lengthscale, d);
+  stage_scales<KIND>(scales, lengthscale, d);
   const PairShape sh = load_pair_shape<KIND>(lengthscale, d);
   if (D_MAX > 1)  // the padding coordinates stay zero: the staging below writes k < d only
     for (int e = tid; e < CHUNK * D_MAX; e += 256) a_s[e / D_MAX][e % D_MAX] = 0.0;
@@ -391,22 +337,23 @@ __global__ __launch_bounds__(256) void kernel_mean_kernel(const double *__restri
     for (int r = w; r < nrows; r += 4) {
       double kap;
       bool alive;
-      if constexpr (TREND) {
-        double s2, q, ks;
-        trend_seasonal_exponents(a_s[r], b, inv_trend, inv_env, inv_ls, two_inv_l, s2, q);
-        alive = trend_kappa(s2, kap);
-        if (periodic_kappa(q, ks)) acc_s = fma(ks, al_s[r], acc_s);
-      } else if constexpr (LOCAL) alive = periodic_kappa(locally_periodic_exponent(a_s[r], b, inv_env, inv_ls, two_inv_l), kap);
-      else if constexpr (PERIODIC) alive = periodic_kappa(periodic_exponent(a_s[r], b, inv_ls, two_inv_l), kap);
-      else alive = pair_kappa<KIND>(pair_dist2(a_s[r], b), sh, kap);
+      if constexpr (periodic_like(KIND)) {
+        double s2, q;
+        pair_exponents<KIND>(a_s[r], b, scales, s2, q);
+        if constexpr (TWO_TERMS) {
+          double ks;
+          alive = trend_kappa(s2, kap);
+          if (periodic_kappa(q, ks)) acc_s = fma(ks, al_s[r], acc_s);
+        } else alive = periodic_kappa(q, kap);
+      } else alive = pair_kappa<KIND>(pair_dist2(a_s[r], b), sh, kap);
       if (alive) acc = fma(kap, al_s[r], acc);
     }
     __syncthreads();
   }
   red[w][lane] = acc;
-  if constexpr (TREND) red_s[w][lane] = acc_s;
+  if constexpr (TWO_TERMS) red_s[w][lane] = acc_s;
   __syncthreads();
-  if constexpr (TREND) {
+  if constexpr (TWO_TERMS) {
     if (w == 0 && live)
       out[i] = fma(outputscale, (red[0][lane] + red[1][lane]) + (red[2][lane] + red[3][lane]),
                    fma(sh.alpha, (red_s[0][lane] + red_s[1][lane]) + (red_s[2][lane] + red_s[3][lane]), mean));

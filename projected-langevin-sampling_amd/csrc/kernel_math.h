@@ -204,6 +204,39 @@ __device__ __forceinline__ double trend_seasonal_entry(double s2, double q, doub
   return fma(s_t, live_t ? kt : 0.0, live_s ? s_s * ks : 0.0);
 }
 
+// The one front over the three coordinate functions, for every loop over the coordinates of a pair (base_kernel.h, the
+// selector): delta is the UNSCALED difference and sc column k of the kind's scale block, one value per parameter block in
+// the order of the `lengthscale` argument -- periodic (2 / lambda_k, 1 / p_k), locally periodic (1 / l_k, 2 / lambda_k, 1 / p_k),
+// trend plus seasonal (1 / l_k, 1 / m_k, 2 / lambda_k, 1 / p_k).  Returns the coordinate's share of the negated exponent q, adds
+// into the trend's distance sum s2 where the kind has one, and (GRAD only) writes f[j], the coordinate's factor of
+// dK / d log of block j's parameter.
+template <int KIND, bool GRAD, int NS>
+__device__ __forceinline__ double pair_coord(double delta, const double (&sc)[NS], double &s2, double (&f)[NS]) {
+  if constexpr (KIND == PLS_KERNEL_PERIODIC) {
+    static_assert(NS == 2, "periodic: lambda, p");
+    const double share = periodic_coord<GRAD>(delta, sc[1], sc[0], f[1]);
+    if (GRAD) f[0] = share;
+    return share;
+  } else if constexpr (KIND == PLS_KERNEL_LOCALLY_PERIODIC) {
+    static_assert(NS == 3, "locally periodic: l, lambda, p");
+    return locally_periodic_coord<GRAD>(delta, sc[0], sc[2], sc[1], f[0], f[1], f[2]);
+  } else {
+    static_assert(KIND == PLS_KERNEL_TREND_SEASONAL && NS == 4, "trend plus seasonal: l, m, lambda, p");
+    return trend_seasonal_coord<GRAD>(delta, sc[0], sc[1], sc[3], sc[2], s2, f[0], f[1], f[2], f[3]);
+  }
+}
+// The entry of such a kind from the sums of pair_coord over its coordinates: one term, s kappa(q) or 0 for a dead pair; trend
+// plus seasonal, its two (sh.alpha holds s_s).
+template <int KIND>
+__device__ __forceinline__ double coord_entry(double s2, double q, double outputscale, const PairShape &sh) {
+  if constexpr (KIND == PLS_KERNEL_TREND_SEASONAL) {
+    return trend_seasonal_entry(s2, q, outputscale, sh.alpha);
+  } else {
+    double kap;
+    return periodic_kappa(q, kap) ? outputscale * kap : 0.0;
+  }
+}
+
 // One pair from its distance sum s2 (RBF: r^2; Matern: t^2 = 2 nu r^2; RQ: r^2, with its shape sh): kap = kappa, the kernel
 // without its outputscale; t = sqrt(s2) (Matern only) and ex, the exponential inside kappa, for pair_factors.  Returns
 // false for a pair whose exponential underflows: kap is meaningless then and the caller lets the pair contribute exactly

@@ -27,7 +27,7 @@
 #include "small_rank_launch.h"
 #include "small_rank_step.h"
 #include "ipb_prep.h"
-#include "kernel_math.h"
+#include "base_kernel.h"
 #include "small_rank_step_launch.h"
 #include "step_params.h"
 #include "winograd.h"
@@ -1267,35 +1267,79 @@ struct CvState {       // device-resident scalars of the selection loop
   int64_t stopped;     // the threshold test fired: later iterations are no-ops
 };
 
-__device__ inline double cv_kernel_eval(int kind, const double *__restrict__ x, int64_t a, int64_t b, int d,
-                                        const double *__restrict__ inv_ls, const double *__restrict__ inv_p, double shape,
-                                        double outputscale) {
-  double s = 0.0;
-  if (kind == PLS_KERNEL_TREND_SEASONAL) {  // the pairwise kernels' own evaluation (kernel_math.h): inv_ls[k] = 1 / l_k, inv_p[k] =
-    double q = 0.0, u0, u1, u2, kap;        // 1 / p_k, 2 / lambda_k at inv_p[8 + k], 1 / m_k at inv_p[16 + k], shape = s_s
-    // trend_seasonal_coord and trend_seasonal_entry term after term -- the same operations on the same operands, the same
-    // bits --, so that one exponential is live at a time and the kernels keep the registers the other kinds need
-    for (int k = 0; k < d; ++k)
-      q = __dadd_rn(q, locally_periodic_coord<false>(x[a * d + k] - x[b * d + k], inv_p[16 + k], inv_p[k], inv_p[8 + k], u0, u1, u2));
-    const double seasonal = periodic_kappa(q, kap) ? shape * kap : 0.0;
+// The selector's scales: PAIR_D_MAX values of 1 / l_k, or a per-coordinate kind's block as the pairwise kernels lay it out
+// (base_kernel.h: stage_scales), at the kind's own d_max.
+constexpr int CV_SCALES = PAIR_D_MAX;
+template <int KIND>
+using CvScaleBlock = double[scale_rows(KIND)][kind_facts(KIND).d_max];
+
+// Stages them (the caller synchronises) and returns the kind's scalar: RQ's alpha, the seasonal outputscale, else 0.  A kind
+// that is not per-coordinate gets 1 / l_k, the linear kernel 1 -- not stage_scales' row, which folds sqrt(2 nu) into a Matern
+// kind's (cv_kernel_eval says why the selector's Matern does not).
+__device__ inline double cv_stage_scales(int kind, double (&scales)[CV_SCALES], const double *__restrict__ lengthscale, int d) {
+  switch (kind) {
+    case PLS_KERNEL_PERIODIC:
+      stage_scales<PLS_KERNEL_PERIODIC>(*reinterpret_cast<CvScaleBlock<PLS_KERNEL_PERIODIC> *>(scales), lengthscale, d);
+      break;
+    case PLS_KERNEL_LOCALLY_PERIODIC:
+      stage_scales<PLS_KERNEL_LOCALLY_PERIODIC>(*reinterpret_cast<CvScaleBlock<PLS_KERNEL_LOCALLY_PERIODIC> *>(scales), lengthscale, d);
+      break;
+    case PLS_KERNEL_TREND_SEASONAL:
+      stage_scales<PLS_KERNEL_TREND_SEASONAL>(*reinterpret_cast<CvScaleBlock<PLS_KERNEL_TREND_SEASONAL> *>(scales), lengthscale, d);
+      break;
+    default:
+      if ((int)threadIdx.x < d) scales[threadIdx.x] = (kind != PLS_KERNEL_LINEAR) ? 1.0 / lengthscale[threadIdx.x] : 1.0;
+  }
+  const KindFacts f = kind_facts(kind);
+  return f.scalars ? lengthscale[(1 + f.blocks) * d] : 0.0;
+}
+
+// a pair of a per-coordinate kind as the pairwise kernels evaluate it (kernel_math.h: pair_coord, coord_entry): the same
+// operations on the same operands in the same order, the same bits; shape: the seasonal outputscale where the kind has one
+template <int KIND>
+__device__ inline double cv_coord_eval(const double *__restrict__ x, int64_t a, int64_t b, int d,
+                                       const double *__restrict__ scales, double shape, double outputscale) {
+  static_assert(sizeof(CvScaleBlock<KIND>) <= CV_SCALES * sizeof(double), "the kind's block fits the selector's scales");
+  constexpr int NS = scale_rows(KIND);
+  const CvScaleBlock<KIND> &block = *reinterpret_cast<const CvScaleBlock<KIND> *>(scales);
+  double s = 0.0, q = 0.0, sc[NS], unused[NS];
+  if constexpr (kind_facts(KIND).terms == 2) {
+    // Term after term, not pair_coord's fused loop and coord_entry: the seasonal term is the locally periodic kind's of rows 1
+    // to 3 (m, lambda, p), then the trend's distance sum from row 0 and trend_seasonal_entry's fma -- the same operations on the
+    // same operands, the same bits --, so that one exponential is live at a time: fused, cv_init_kernel and cv_update_kernel
+    // take 56 VGPRs instead of 54.
+    constexpr int LOCAL = PLS_KERNEL_LOCALLY_PERIODIC;
+    static_assert(KIND == PLS_KERNEL_TREND_SEASONAL && scale_rows(LOCAL) == NS - 1, "the only kind of two terms");
+    const auto &seasonal = reinterpret_cast<const double(&)[NS - 1][kind_facts(KIND).d_max]>(block[1]);
+    double kap, sc3[NS - 1], unused3[NS - 1];
     for (int k = 0; k < d; ++k) {
-      const double z = (x[a * d + k] - x[b * d + k]) * inv_ls[k];
+      scale_column(seasonal, k, sc3);
+      q = __dadd_rn(q, pair_coord<LOCAL, false>(x[a * d + k] - x[b * d + k], sc3, s, unused3));
+    }
+    const double term = periodic_kappa(q, kap) ? shape * kap : 0.0;
+    for (int k = 0; k < d; ++k) {
+      const double z = (x[a * d + k] - x[b * d + k]) * block[0][k];
       s = fma(z, z, s);
     }
-    return fma(outputscale, trend_kappa(s, kap) ? kap : 0.0, seasonal);
+    return fma(outputscale, trend_kappa(s, kap) ? kap : 0.0, term);
+  } else {
+    for (int k = 0; k < d; ++k) {
+      scale_column(block, k, sc);
+      q = __dadd_rn(q, pair_coord<KIND, false>(x[a * d + k] - x[b * d + k], sc, s, unused));
+    }
+    return coord_entry<KIND>(s, q, outputscale, PairShape{shape, 0.0});
   }
-  if (kind == PLS_KERNEL_LOCALLY_PERIODIC) {  // as periodic below, with inv_ls[k] = 1 / l_k and 2 / lambda_k at inv_p[16 + k]
-    double u0, u1, u2, kap;
-    for (int k = 0; k < d; ++k)
-      s = __dadd_rn(s, locally_periodic_coord<false>(x[a * d + k] - x[b * d + k], inv_ls[k], inv_p[k], inv_p[16 + k], u0, u1, u2));
-    return periodic_kappa(s, kap) ? outputscale * kap : 0.0;
+}
+
+__device__ inline double cv_kernel_eval(int kind, const double *__restrict__ x, int64_t a, int64_t b, int d,
+                                        const double *__restrict__ inv_ls, double shape, double outputscale) {
+  switch (kind) {  // (inv_ls: the kind's scale block)
+    case PLS_KERNEL_PERIODIC: return cv_coord_eval<PLS_KERNEL_PERIODIC>(x, a, b, d, inv_ls, shape, outputscale);
+    case PLS_KERNEL_LOCALLY_PERIODIC: return cv_coord_eval<PLS_KERNEL_LOCALLY_PERIODIC>(x, a, b, d, inv_ls, shape, outputscale);
+    case PLS_KERNEL_TREND_SEASONAL: return cv_coord_eval<PLS_KERNEL_TREND_SEASONAL>(x, a, b, d, inv_ls, shape, outputscale);
+    default: break;
   }
-  if (kind == PLS_KERNEL_PERIODIC) {  // the pairwise kernels' own evaluation, coordinate by coordinate (kernel_math.h);
-    double unused, kap;               // inv_p[k] = 1 / p_k, and 2 inv_ls[k] is 2 / lambda_k to the bit
-    for (int k = 0; k < d; ++k)
-      s = __dadd_rn(s, periodic_coord<false>(x[a * d + k] - x[b * d + k], inv_p[k], 2.0 * inv_ls[k], unused));
-    return periodic_kappa(s, kap) ? outputscale * kap : 0.0;
-  }
+  double s = 0.0;
   if (kind == PLS_KERNEL_RQ) {  // shape = alpha; library log1p and exp as below: exactly the outputscale at distance 0
     for (int k = 0; k < d; ++k) {
       const double e = (x[a * d + k] - x[b * d + k]) * inv_ls[k];
@@ -1334,22 +1378,8 @@ __global__ __launch_bounds__(CV_BLOCK) void cv_init_kernel(int kind, const doubl
                                                             const double *__restrict__ lengthscale, double outputscale,
                                                             double jitter, double *__restrict__ di,
                                                             unsigned char *__restrict__ chosen, CvState *st) {
-  __shared__ double inv_ls[64];
-  // (periodic: the period lengths follow the d <= 16 lengthscales; locally periodic: l, lambda, p in blocks of d, 1 / p_k in
-  // front and 2 / lambda_k behind it; trend plus seasonal: 1 / p_k, 2 / lambda_k and 1 / m_k in thirds of 8)
-  __shared__ double inv_p[32];
-  if ((int)threadIdx.x < d) inv_ls[threadIdx.x] = (kind != PLS_KERNEL_LINEAR) ? 1.0 / lengthscale[threadIdx.x] : 1.0;
-  if (kind == PLS_KERNEL_PERIODIC && (int)threadIdx.x < d) inv_p[threadIdx.x] = 1.0 / lengthscale[d + threadIdx.x];
-  if (kind == PLS_KERNEL_LOCALLY_PERIODIC && (int)threadIdx.x < d) {
-    inv_p[threadIdx.x] = 1.0 / lengthscale[2 * d + threadIdx.x];
-    inv_p[16 + threadIdx.x] = 2.0 / lengthscale[d + threadIdx.x];
-  }
-  if (kind == PLS_KERNEL_TREND_SEASONAL && (int)threadIdx.x < d) {  // (l, m, lambda, p in blocks of d <= 8, then s_s)
-    inv_p[threadIdx.x] = 1.0 / lengthscale[3 * d + threadIdx.x];
-    inv_p[8 + threadIdx.x] = 2.0 / lengthscale[2 * d + threadIdx.x];
-    inv_p[16 + threadIdx.x] = 1.0 / lengthscale[d + threadIdx.x];
-  }
-  const double shape = (kind == PLS_KERNEL_RQ) ? lengthscale[d] : (kind == PLS_KERNEL_TREND_SEASONAL) ? lengthscale[4 * d] : 0.0;
+  __shared__ double scales[CV_SCALES];
+  const double shape = cv_stage_scales(kind, scales, lengthscale, d);
   __syncthreads();
   const int64_t i = (int64_t)blockIdx.x * CV_BLOCK + threadIdx.x;
   if (i == 0) {
@@ -1357,7 +1387,7 @@ __global__ __launch_bounds__(CV_BLOCK) void cv_init_kernel(int kind, const doubl
     st->stopped = 0;
   }
   if (i >= n) return;
-  di[i] = cv_kernel_eval(kind, x, i, i, d, inv_ls, inv_p, shape, outputscale) + jitter;
+  di[i] = cv_kernel_eval(kind, x, i, i, d, scales, shape, outputscale) + jitter;
   chosen[i] = 0;
 }
 
@@ -1462,23 +1492,9 @@ __global__ __launch_bounds__(CV_BLOCK) void cv_update_kernel(int kind, const dou
                                                               double jitter, int64_t iter, double *__restrict__ ci,
                                                               double *__restrict__ di, const CvState *__restrict__ st) {
   constexpr int NSL = CV_BLOCK / CV_COLS;
-  __shared__ double inv_ls[64];
+  __shared__ double scales[CV_SCALES];
   __shared__ double part[NSL][CV_COLS];
-  // (periodic: the period lengths follow the d <= 16 lengthscales; locally periodic: l, lambda, p in blocks of d, 1 / p_k in
-  // front and 2 / lambda_k behind it; trend plus seasonal: 1 / p_k, 2 / lambda_k and 1 / m_k in thirds of 8)
-  __shared__ double inv_p[32];
-  if ((int)threadIdx.x < d) inv_ls[threadIdx.x] = (kind != PLS_KERNEL_LINEAR) ? 1.0 / lengthscale[threadIdx.x] : 1.0;
-  if (kind == PLS_KERNEL_PERIODIC && (int)threadIdx.x < d) inv_p[threadIdx.x] = 1.0 / lengthscale[d + threadIdx.x];
-  if (kind == PLS_KERNEL_LOCALLY_PERIODIC && (int)threadIdx.x < d) {
-    inv_p[threadIdx.x] = 1.0 / lengthscale[2 * d + threadIdx.x];
-    inv_p[16 + threadIdx.x] = 2.0 / lengthscale[d + threadIdx.x];
-  }
-  if (kind == PLS_KERNEL_TREND_SEASONAL && (int)threadIdx.x < d) {  // (l, m, lambda, p in blocks of d <= 8, then s_s)
-    inv_p[threadIdx.x] = 1.0 / lengthscale[3 * d + threadIdx.x];
-    inv_p[8 + threadIdx.x] = 2.0 / lengthscale[2 * d + threadIdx.x];
-    inv_p[16 + threadIdx.x] = 1.0 / lengthscale[d + threadIdx.x];
-  }
-  const double shape = (kind == PLS_KERNEL_RQ) ? lengthscale[d] : (kind == PLS_KERNEL_TREND_SEASONAL) ? lengthscale[4 * d] : 0.0;
+  const double shape = cv_stage_scales(kind, scales, lengthscale, d);
   __syncthreads();
   if (st->stopped || st->count != iter + 1) return;  // (stopped early, or ran out of candidates; uniform)
   const int64_t j = st->pivot;
@@ -1500,7 +1516,7 @@ __global__ __launch_bounds__(CV_BLOCK) void cv_update_kernel(int kind, const dou
   double dot = part[0][c];
 #pragma unroll
   for (int k = 1; k < NSL; ++k) dot += part[k][c];
-  double g = cv_kernel_eval(kind, x, col, j, d, inv_ls, inv_p, shape, outputscale);
+  double g = cv_kernel_eval(kind, x, col, j, d, scales, shape, outputscale);
   g = rint(g * 1e20) / 1e20;  // np.round(., 20) (conditional_variance.py:93)
   if (col == j) g += jitter;
   const double e = (g - dot) / dj;
@@ -3242,19 +3258,11 @@ int pls_select_inducing_conditional_variance(int32_t kernel_kind, const double *
                                              const double *lengthscale, double outputscale, int64_t m, double jitter,
                                              double threshold, int64_t *indices, int64_t *count, void *workspace,
                                              size_t workspace_bytes, void *stream) {
-  PLS_REQUIRE((kernel_kind >= PLS_KERNEL_RBF_ARD && kernel_kind <= PLS_KERNEL_MATERN52) || kernel_kind == PLS_KERNEL_RQ ||
-                  kernel_kind == PLS_KERNEL_PERIODIC || kernel_kind == PLS_KERNEL_LOCALLY_PERIODIC ||
-                  kernel_kind == PLS_KERNEL_TREND_SEASONAL,
-              "unknown kernel kind %d", kernel_kind);
+  PLS_REQUIRE(kernel_kind == PLS_KERNEL_LINEAR || stationary_kind(kernel_kind), "unknown kernel kind %d", kernel_kind);
   PLS_REQUIRE(x && indices && count, "select_inducing: NULL pointer");
   PLS_REQUIRE(m > 1, "select_inducing: Must have at least 2 inducing points");  // conditional_variance.py:57
   PLS_REQUIRE(n >= m && d >= 1 && d <= 64, "select_inducing: need n >= m and 1 <= d <= 64");
-  PLS_REQUIRE(kernel_kind != PLS_KERNEL_PERIODIC || d <= 16,
-              "select_inducing: input dimension %lld > 16 is not supported for the periodic kernel", (long long)d);
-  PLS_REQUIRE(kernel_kind != PLS_KERNEL_LOCALLY_PERIODIC || d <= 16,
-              "select_inducing: input dimension %lld > 16 is not supported for the locally periodic kernel", (long long)d);
-  PLS_REQUIRE(kernel_kind != PLS_KERNEL_TREND_SEASONAL || d <= 8,
-              "select_inducing: input dimension %lld > 8 is not supported for the trend-plus-seasonal kernel", (long long)d);
+  if (int rc = check_kind_dim("select_inducing", kernel_kind, d)) return rc;
   PLS_REQUIRE(kernel_kind == PLS_KERNEL_LINEAR || lengthscale, "select_inducing: kernel kind %d needs lengthscale", kernel_kind);
   const size_t need = pls_select_inducing_workspace_bytes(n, m);
   if (!workspace || workspace_bytes < need)
