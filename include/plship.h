@@ -898,10 +898,15 @@ int pls_onb_particle_update(const pls_onb_desc *basis, const double *U, int64_t 
  * `particles += update`, trainers.py:157, fused).  out must not alias U: other workgroups still read U as
  * the GEMM operand, so callers ping-pong two particle buffers.
  * energy_in (may be NULL): receives e_j(U) of the INPUT particles -- the value pls_onb_energy returns -- as a
- * by-product: on the fast path from the same B U product (it then needs 2 * cdiv(mk, 128) * j workspace doubles), otherwise
+ * by-product: on the fast path from the same B U product (2 * cdiv(mk, 128) * j workspace doubles hold every tiling; a launch of
+ * 64-row tiles leaves cdiv(mk, 64) partial rows and takes a workspace of that many, never fewer), otherwise
  * from the same F tile the cost derivative is taken of, so a train loop (trainers.py:153-159, which recomputes F for the
  * energy) pays no separate energy pass.
- * workspace: pls_onb_step_workspace_bytes(...) bytes (any larger size lets it use bigger N chunks). */
+ * workspace: pls_onb_step_workspace_bytes(...) bytes (any larger size lets it use bigger N chunks).  The query covers every
+ * route the call may take: for a basis of at most 128 functions it is the larger of the general route's layout for chunks of
+ * n_chunk rows and the one-launch step's (its row slabs, and its counters where the caller brings none).  A smaller workspace
+ * is not refused while it holds the layout of a route that applies -- the one-launch step first, else the general route in
+ * chunks of at least min(n, 128) rows -- and PLS_ERR_WORKSPACE_TOO_SMALL means that it holds neither. */
 size_t pls_onb_step_workspace_bytes(const pls_onb_desc *basis, int64_t j, int64_t n_chunk);
 int pls_onb_step(const pls_onb_desc *basis, const pls_cost_desc *cost, const double *y, double *U, int64_t ldu,
                  int64_t j, double eta, const pls_noise_desc *noise, double *out, int64_t ldo, int32_t out_mode,
@@ -1018,7 +1023,8 @@ int pls_ipb_whiten(const pls_ipb_desc *basis, const double *U, int64_t ldu, int6
 int pls_ipb_unwhiten(const pls_ipb_desc *basis, const double *S, int64_t lds, int64_t j, double *U, int64_t ldu, void *stream);
 /* One Langevin step of the whitened particles: out = dS (out_mode 0) or S + dS (out_mode 1); Philox noise draws the xi
  * of the reference's e = Lc xi (same counters as pls_ipb_step), injected noise is used as xi (NOT coloured).  energy_in
- * (optional): energy of the INPUT particles; it needs pls_ipb_whitened_workspace_bytes(basis, J) workspace bytes. */
+ * (optional): energy of the INPUT particles; pls_ipb_whitened_workspace_bytes(basis, J) = 2 cdiv(M, 128) J doubles hold its
+ * partial rows under every tiling (a launch of 64-row tiles takes cdiv(M, 64) J doubles, as pls_onb_step's fast path). */
 size_t pls_ipb_whitened_workspace_bytes(const pls_ipb_desc *basis, int64_t j);
 int pls_ipb_whitened_step(const pls_ipb_desc *basis, const pls_cost_desc *cost, const double *S, int64_t lds, int64_t j,
                           double eta, const pls_noise_desc *noise, double *out, int64_t ldo, int32_t out_mode, double *energy_in,
