@@ -129,21 +129,37 @@ typedef enum {
   PLS_KERNEL_TREND_SEASONAL = 12    /* (11 is not a kind) */
 } pls_kernel_kind;
 
-/* src/projected_langevin_sampling/costs/{gaussian,poisson,bernoulli,student_t,multimodal}.py */
+/* src/projected_langevin_sampling/costs/{gaussian,poisson,bernoulli,student_t,multimodal}.py
+ * NEGATIVE_BINOMIAL is not in the reference: an addition within ABI 7 (no export is added or changed), for over-dispersed
+ * counts.  p[0] = r, the dispersion, 0 < r < inf; mean mu = link(f), variance mu + mu^2 / r.  The value is the negative
+ * log-likelihood WITHOUT its f-independent terms (so energies are comparable between runs with the same r only):
+ *   cost(y, f)      = r log1p(mu / r) + y log1p(r / mu)                 (the second term is exactly 0 for y == 0)
+ *   d cost / d f    = r (mu - y) / (mu (r + mu)) * d mu / d f
+ * y >= 0 need not be an integer.  Both derivative modes return the same bits: there is no reference closed form to tell
+ * them apart.  Under PLS_LINK_EXP, with t = f - log r (log r taken on the host), mu is never formed:
+ *   cost(y, f)      = r softplus(t) + y softplus(-t),    softplus(+-t) = max(+-t, 0) + log1p(exp(-|t|))
+ *   d cost / d f    = r sigma(t) - y sigma(-t)           in [-y, r]
+ * so value and derivative are finite where exp(f) overflows or underflows (about r t for large t, about -y t for large -t).
+ * This pair has kernel instantiations of its own on every step route; under any other link the formulas in mu are evaluated
+ * by the chain rule. */
 typedef enum {
   PLS_COST_GAUSSIAN = 0,
   PLS_COST_POISSON = 1,
   PLS_COST_BERNOULLI = 2,
   PLS_COST_STUDENT_T = 3,
-  PLS_COST_MULTIMODAL = 4
+  PLS_COST_MULTIMODAL = 4,
+  PLS_COST_NEGATIVE_BINOMIAL = 5
 } pls_cost_kind;
 
-/* src/projected_langevin_sampling/link_functions.py:30-80 */
+/* src/projected_langevin_sampling/link_functions.py:30-80
+ * EXP is not in the reference (an addition within ABI 7): p = exp(f), slope p, no clip -- the jitter is ignored; +inf above
+ * the fp64 range, gradual underflow below it.  Under a cost other than NEGATIVE_BINOMIAL it runs by the generic chain rule. */
 typedef enum {
   PLS_LINK_IDENTITY = 0,
   PLS_LINK_SQUARE = 1,
   PLS_LINK_SIGMOID = 2,
-  PLS_LINK_PROBIT = 3
+  PLS_LINK_PROBIT = 3,
+  PLS_LINK_EXP = 4
 } pls_link_kind;
 
 /* How d cost / d f is evaluated.
@@ -162,6 +178,7 @@ typedef struct {
   /* p[0..3]: gaussian {observation_noise (a VARIANCE, gaussian.py:71,86)};
    *          student_t {degrees_of_freedom, scale};
    *          multimodal {observation_noise (a STD, multimodal.py:56), shift, bernoulli_noise};
+   *          negative_binomial {dispersion r};
    *          poisson / bernoulli: unused */
   double p[4];
   double jitter; /* clip of sigmoid / probit links (link_functions.py:36, :64), default 1e-10 */

@@ -30,8 +30,8 @@ def kernel_shape_params(kind: int, d: int) -> int:
     return 1 if kind == KERNEL_RQ else d if kind == KERNEL_PERIODIC else 2 * d if kind == KERNEL_LOCALLY_PERIODIC else 3 * d + 1 if kind == KERNEL_TREND_SEASONAL else 0
 
 
-COST_GAUSSIAN, COST_POISSON, COST_BERNOULLI, COST_STUDENT_T, COST_MULTIMODAL = range(5)
-LINK_IDENTITY, LINK_SQUARE, LINK_SIGMOID, LINK_PROBIT = range(4)
+COST_GAUSSIAN, COST_POISSON, COST_BERNOULLI, COST_STUDENT_T, COST_MULTIMODAL, COST_NEGATIVE_BINOMIAL = range(6)
+LINK_IDENTITY, LINK_SQUARE, LINK_SIGMOID, LINK_PROBIT, LINK_EXP = range(5)
 DERIV_REFERENCE, DERIV_AUTOGRAD = 0, 1
 NOISE_NONE, NOISE_INJECTED, NOISE_PHILOX = 0, 1, 2
 OUT_DELTA, OUT_NEW_STATE = 0, 1

@@ -4,7 +4,8 @@ The reference stores a trained sampler as ``torch.save({"particles", "observatio
 "number_of_epochs"}, path)`` (experiments/uci/regression/main.py:300-308) and restores it with ``load_pls``
 (experiments/loaders.py:10-28).  Files written by either implementation load in the other.  Two optional extra keys
 make a J-sharded run exactly resumable: ``noise_step`` (the step counter of the Philox stream) and
-``number_of_particles`` (the global J a shard belongs to); the reference ignores unknown keys.
+``number_of_particles`` (the global J a shard belongs to); the reference ignores unknown keys.  A cost with a
+``dispersion`` (NegativeBinomialCost) has it stored under that key and restored from it, as ``observation_noise`` is.
 
 Particles of the orthonormal basis are COORDINATES in the eigenvector gauge of the basis they were trained with
 (orthonormal.py:46-68), and an eigendecomposition is defined only up to signs and rotations inside clusters: the file
@@ -41,6 +42,9 @@ def save_pls(pls: PLS, particles: torch.Tensor, model_path: str, best_lr: Option
         state["noise_step"] = int(noise_step)
     if number_of_particles is not None:
         state["number_of_particles"] = int(number_of_particles)
+    dispersion = getattr(getattr(pls, "cost", None), "dispersion", None)
+    if dispersion is not None:
+        state["dispersion"] = float(dispersion)
     fingerprint = _basis_fingerprint(pls)
     if fingerprint is not None:
         state["spectrum_fingerprint"] = fingerprint
@@ -68,6 +72,8 @@ def load_pls(pls: PLS, model_path: str, on_gauge_mismatch: str = "raise") -> Tup
             warnings.warn(message)
     particles = _dev(model_config["particles"])
     pls.observation_noise = model_config["observation_noise"]
+    if "dispersion" in model_config and hasattr(getattr(pls, "cost", None), "dispersion"):
+        pls.cost.dispersion = float(model_config["dispersion"])
     print(f"Loaded particles and observation_noise from {model_path=}.")
     best_lr = model_config.get("best_lr")
     number_of_epochs = model_config.get("number_of_epochs")

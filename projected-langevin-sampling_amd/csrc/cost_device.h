@@ -17,6 +17,7 @@ struct CostP {
   double p0, p1, p2, p3, jitter;
   double ip0;  // 1 / p0 (Gaussian: 1 / sigma2), computed on the host
   double mm_l1, mm_l2, mm_norm, mm_is2;  // multimodal: log p2, log(1 - p2), 0.5 log(2 pi s2), 1 / s2 (host)
+                                         // negative binomial: mm_l1 = log r (host), the others unused
 };
 
 __host__ inline CostP make_costp(const pls_cost_desc *d) {
@@ -38,10 +39,12 @@ __host__ inline CostP make_costp(const pls_cost_desc *d) {
     c.mm_norm = 0.5 * std::log(2.0 * 3.14159265358979323846 * s2);
     c.mm_is2 = 1.0 / s2;
   }
+  if (d->cost == PLS_COST_NEGATIVE_BINOMIAL) c.mm_l1 = std::log(d->p[0]);
   return c;
 }
 
-// THE list of the (cost, link) pairs with kernel instantiations of their own (the pairs the reference's experiments use):
+// THE list of the (cost, link) pairs with kernel instantiations of their own (the pairs the reference's experiments use, and
+// negative binomial/exp):
 // f(integral_constant<COST>, integral_constant<LINK>) for one of them, f(-1, -1) -- the instantiation that switches at run
 // time -- for every other pair.  Every launcher that dispatches on the pair goes through here.
 template <class F>
@@ -54,6 +57,7 @@ __host__ inline int for_cost_link(const CostP &cp, F &&f) {
   if (c == PLS_COST_BERNOULLI && l == PLS_LINK_PROBIT) return f(integral_constant<int, PLS_COST_BERNOULLI>{}, integral_constant<int, PLS_LINK_PROBIT>{});
   if (c == PLS_COST_STUDENT_T && l == PLS_LINK_IDENTITY) return f(integral_constant<int, PLS_COST_STUDENT_T>{}, integral_constant<int, PLS_LINK_IDENTITY>{});
   if (c == PLS_COST_MULTIMODAL && l == PLS_LINK_IDENTITY) return f(integral_constant<int, PLS_COST_MULTIMODAL>{}, integral_constant<int, PLS_LINK_IDENTITY>{});
+  if (c == PLS_COST_NEGATIVE_BINOMIAL && l == PLS_LINK_EXP) return f(integral_constant<int, PLS_COST_NEGATIVE_BINOMIAL>{}, integral_constant<int, PLS_LINK_EXP>{});
   return f(integral_constant<int, -1>{}, integral_constant<int, -1>{});
 }
 
@@ -80,13 +84,69 @@ __device__ inline double link_eval(int link, double f, double jit, double *slope
       *slope = inside ? ex * raw * raw : 0.0;
       return clipd(raw, jit, 1.0 - jit);
     }
-    default: {  // PLS_LINK_PROBIT :39-45
+    case PLS_LINK_PROBIT: {  // :39-45
       double raw = 0.5 * (1.0 + erf(f * 0.70710678118654752440));
       bool inside = (raw >= jit) && (raw <= 1.0 - jit);
       *slope = inside ? 0.39894228040143267794 * fast_exp(-0.5 * f * f) : 0.0;
       return clipd(raw, jit, 1.0 - jit);
     }
+    case PLS_LINK_EXP: {  // not in the reference: p = exp(f), no clip (+inf above the fp64 range, gradual underflow)
+      const double p = fast_exp(f);
+      *slope = p;
+      return p;
+    }
+    default:  // (the host entries refuse every other id)
+      *slope = __builtin_nan("");
+      return __builtin_nan("");
   }
+}
+
+// log(1 + x) for x >= 0 (+inf included; NaN for NaN and for x < -1): the sum 1 + x held in two pieces, so the bits of x below
+// ulp(1) reach the logarithm (log1p(x) = x for x < 2^-53, and no cancellation against log 1 = 0)
+__device__ inline double log1p_pos(double x) {
+#pragma clang fp contract(off)
+  const double hi = fmax(x, 1.0), lo = fmin(x, 1.0);
+  const double s = hi + lo;
+  const double e = lo - (s - hi);
+  const double v = fast_log_unit_tail(s, e);
+  return (x < __builtin_huge_val() && s > 0.0) ? v : (x == -1.0 ? -__builtin_huge_val() : x >= 0.0 ? x : __builtin_nan(""));
+}
+
+// The negative binomial under the exponential link, in t = f - log r (mu / r = e^t; mu itself is never formed: it overflows
+// from f = 709.8 and underflows from f = -745.2, where value and derivative are finite):
+//   cost  = r log1p(e^t) + y log1p(e^-t) = r softplus(t) + y softplus(-t),   softplus(+-t) = max(+-t, 0) + log1p(e^-|t|)
+//   cost' = r sigma(t) - y sigma(-t),   sigma(|t|) = 1 / (1 + e^-|t|),   sigma(-|t|) = e^-|t| / (1 + e^-|t|)
+// One exponential e = e^-|t| in (0, 1]; 1 + e in two pieces (s, tail) for the logarithm.  The value is r t for large t and
+// -y t for large -t (0 * max(-t, 0) = 0 for y = 0 however large -t is); the derivative stays in [-y, r].
+struct NbExp {
+  double e, s, tail;
+  bool pos;
+};
+__device__ inline NbExp nb_exp_reduce(double t) {
+#pragma clang fp contract(off)
+  NbExp q;
+  q.e = fast_exp(-fabs(t));
+  q.s = 1.0 + q.e;
+  q.tail = q.e - (q.s - 1.0);
+  q.pos = t >= 0.0;
+  return q;
+}
+__device__ inline double nb_exp_value(const CostP &c, double y, double f) {
+#pragma clang fp contract(off)
+  const double t = f - c.mm_l1;
+  const NbExp q = nb_exp_reduce(t);
+  const double l = fast_log_unit_tail(q.s, q.tail);  // log1p(e^-|t|) in [0, log 2]
+  const double up = q.pos ? t + l : l, dn = q.pos ? l : l - t;  // softplus(t), softplus(-t)
+  const double a = c.p0 * up, b = y * dn;
+  return (y == 0.0) ? a : a + b;  // (y = 0: the second term is exactly 0, also where softplus(-t) is +inf)
+}
+__device__ inline double nb_exp_deriv(const CostP &c, double y, double f) {
+#pragma clang fp contract(off)
+  const double t = f - c.mm_l1;
+  const NbExp q = nb_exp_reduce(t);
+  const double big = fast_div_normal(1.0, q.s), small = q.e * big;  // sigma(|t|), sigma(-|t|); 1 <= s <= 2
+  const double a = c.p0 * (q.pos ? big : small), b = y * (q.pos ? small : big);
+  return a - b;
 }
 
 // cost(y, f) for one (n, j) entry; summed over n by the callers.
@@ -118,13 +178,20 @@ __device__ inline double cost_value(const CostP &c, double y, double f) {
       double e = p - y;
       return 0.5 * (c.p0 + 1.0) * fast_log(1.0 + e * e / (c.p0 * c.p1 * c.p1));
     }
-    default: {  // PLS_COST_MULTIMODAL multimodal.py:37-77, p0 = sigma (std), p1 = shift, p2 = bernoulli_noise
+    case PLS_COST_MULTIMODAL: {  // multimodal.py:37-77, p0 = sigma (std), p1 = shift, p2 = bernoulli_noise
       double e1 = y - p + c.p1, e2 = y - p;
       double a1 = c.mm_l1 - 0.5 * e1 * e1 * c.mm_is2 - c.mm_norm;
       double a2 = c.mm_l2 - 0.5 * e2 * e2 * c.mm_is2 - c.mm_norm;
       double m = fmax(a1, a2);
       return -(m + fast_log(fast_exp(a1 - m) + fast_exp(a2 - m)));
     }
+    case PLS_COST_NEGATIVE_BINOMIAL: {  // not in the reference (plship.h): p0 = r, mu = p
+      if (c.link == PLS_LINK_EXP) return nb_exp_value(c, y, f);
+      const double a = c.p0 * log1p_pos(p * c.ip0);
+      return (y == 0.0) ? a : a + y * log1p_pos(fast_div(c.p0, p));
+    }
+    default:  // (the host entries refuse every other id)
+      return __builtin_nan("");
   }
 }
 
@@ -151,7 +218,7 @@ __device__ inline double cost_deriv(const CostP &c, double y, double f) {
       double e = p - y;
       return fast_div((c.p0 + 1.0) * e, c.p0 * c.p1 * c.p1 + e * e) * slope;
     }
-    default: {  // multimodal.py:79-91: always the autograd value
+    case PLS_COST_MULTIMODAL: {  // multimodal.py:79-91: always the autograd value
       double e1 = y - p + c.p1, e2 = y - p;
       double a1 = c.mm_l1 - 0.5 * e1 * e1 * c.mm_is2;
       double a2 = c.mm_l2 - 0.5 * e2 * e2 * c.mm_is2;
@@ -159,6 +226,11 @@ __device__ inline double cost_deriv(const CostP &c, double y, double f) {
       double w1 = fast_exp(a1 - m), w2 = fast_exp(a2 - m);
       return -fast_div(w1 * e1 + w2 * e2, w1 + w2) * c.mm_is2 * slope;
     }
+    case PLS_COST_NEGATIVE_BINOMIAL:  // one value for both modes: there is no reference closed form to tell them apart
+      if (c.link == PLS_LINK_EXP) return nb_exp_deriv(c, y, f);
+      return fast_div(c.p0 * (p - y), p * (c.p0 + p)) * slope;
+    default:  // (the host entries refuse every other id)
+      return __builtin_nan("");
   }
 }
 

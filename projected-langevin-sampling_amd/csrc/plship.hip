@@ -1595,8 +1595,8 @@ static int launch_langevin_update(double *out, int64_t ldo, int add_u, const dou
 // ---------------------------------------------------------------------------------------------------------------
 static int validate_cost(const pls_cost_desc *c) {
   PLS_REQUIRE(c != nullptr, "cost descriptor is NULL");
-  PLS_REQUIRE(c->cost >= PLS_COST_GAUSSIAN && c->cost <= PLS_COST_MULTIMODAL, "unknown cost kind %d", c->cost);
-  PLS_REQUIRE(c->link >= PLS_LINK_IDENTITY && c->link <= PLS_LINK_PROBIT, "unknown link kind %d", c->link);
+  PLS_REQUIRE(c->cost >= PLS_COST_GAUSSIAN && c->cost <= PLS_COST_NEGATIVE_BINOMIAL, "unknown cost kind %d", c->cost);
+  PLS_REQUIRE(c->link >= PLS_LINK_IDENTITY && c->link <= PLS_LINK_EXP, "unknown link kind %d", c->link);
   PLS_REQUIRE(c->deriv_mode == PLS_DERIV_REFERENCE || c->deriv_mode == PLS_DERIV_AUTOGRAD, "unknown deriv_mode %d",
               c->deriv_mode);
   if (c->cost == PLS_COST_GAUSSIAN) PLS_REQUIRE(c->p[0] > 0.0, "gaussian cost needs observation_noise > 0");
@@ -1604,6 +1604,8 @@ static int validate_cost(const pls_cost_desc *c) {
     PLS_REQUIRE(c->p[0] > 0.0 && c->p[1] > 0.0, "student-t cost needs degrees_of_freedom > 0 and scale > 0");
   if (c->cost == PLS_COST_MULTIMODAL)
     PLS_REQUIRE(c->p[0] > 0.0 && c->p[2] > 0.0 && c->p[2] < 1.0, "multimodal cost needs sigma > 0, 0 < bernoulli_noise < 1");
+  if (c->cost == PLS_COST_NEGATIVE_BINOMIAL)
+    PLS_REQUIRE(c->p[0] > 0.0 && std::isfinite(c->p[0]), "negative-binomial cost needs a finite dispersion > 0");
   return PLS_OK;
 }
 
@@ -2172,7 +2174,7 @@ int pls_cost_value(const pls_cost_desc *cost, const double *F, int64_t ldf, cons
 
 int pls_link_transform(int32_t link, double jitter, const double *in, int64_t ldin, int64_t rows, int64_t cols,
                        const double *col_offset, double *out, int64_t ldout, void *stream) {
-  PLS_REQUIRE(link >= PLS_LINK_IDENTITY && link <= PLS_LINK_PROBIT, "link_transform: unknown link %d", link);
+  PLS_REQUIRE(link >= PLS_LINK_IDENTITY && link <= PLS_LINK_EXP, "link_transform: unknown link %d", link);
   PLS_REQUIRE(in && out && rows >= 0 && cols >= 0 && ldin >= cols && ldout >= cols, "link_transform: bad arguments");
   if (rows == 0 || cols == 0) return PLS_OK;
   hipLaunchKernelGGL(link_transform_kernel, dim3((unsigned)cdiv(cols, 256), rows_grid(rows)), dim3(256), 0, S(stream),

@@ -70,6 +70,15 @@ class SigmoidLinkFunction(PLSLinkFunction):
         return self._native_transform(y)
 
 
+class ExponentialLinkFunction(PLSLinkFunction):
+    """exp(f), the log link of count models (not in the reference): no clip, +inf above the fp64 range."""
+
+    kind = L.LINK_EXP
+
+    def transform(self, y: torch.Tensor) -> torch.Tensor:
+        return self._native_transform(y)
+
+
 class ProbitLinkFunction(PLSLinkFunction):
     """link_functions.py:30-45.  sqrt(2) is exact fp64 here; the reference evaluates it in torch's default
     dtype (identical under the float64 default its experiments set)."""

@@ -1,0 +1,133 @@
+"""GPU: the element-wise entries for the count-model pairs -- pls_cost_derivative (both derivative modes, which must be the
+same bits), pls_cost_value and pls_link_transform -- against the per-element mpmath truth of tests/count_cost_truth.py on
+its whole grid, dense and strided: bulk, the root where the derivative cancels, both tails, the far columns where e^f leaves
+the fp64 range while the negative binomial stays finite, +-0 and subnormals.
+
+The bound is tests/test_gpu_cost_elements.py's, unchanged: per (pair, parameter set, kind, regime) the larger of 4x the host
+restatement's recorded error (tests/golden/count_cost_reference_errors.json) and 4 units; IEEE specials must match exactly.
+PLS_COST_TRUTH_DUMP=<file> appends the measured maxima as JSON lines (the rows of DESIGN.md section 3 are made from them)."""
+import json
+import math
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import count_cost_truth as CT
+from test_gpu_parity import P, _f64_default  # noqa: F401  (fixtures)
+
+pytestmark = pytest.mark.gpu
+
+
+def _dump(record):
+    path = os.environ.get("PLS_COST_TRUTH_DUMP")
+    if path:
+        with open(path, "a") as fh:
+            fh.write(json.dumps(record) + "\n")
+
+
+def gpu_eval(P, pair, pset, kind, strided=False):
+    """the library on the grid, per element (N, J); ``strided``: the samples are the left columns of a wider matrix"""
+    y, f, _ = CT.grid(pair, pset)
+    yt, ft = torch.as_tensor(y), torch.as_tensor(f).cuda()
+    if strided:
+        wide = torch.full((f.shape[0], f.shape[1] + 3), float("nan"), device="cuda")
+        wide[:, :f.shape[1]] = ft
+        ft = wide[:, :f.shape[1]]
+    if kind == "link":
+        return CT.gpu_cost(P, pair, pset, yt).link_function(ft).cpu().numpy()
+    if kind == "value":  # the entry sums over rows: one row at a time
+        rows = [CT.gpu_cost(P, pair, pset, yt[a:a + 1]).calculate_cost(ft[a:a + 1]) for a in range(len(y))]
+        return torch.stack(rows).cpu().numpy()
+    return CT.gpu_cost(P, pair, pset, yt).calculate_cost_derivative(ft, force_autograd=kind == "deriv_autograd").cpu().numpy()
+
+
+@pytest.mark.parametrize("pair,pset", CT.cells())
+def test_elements_against_truth(P, pair, pset):
+    rec = CT.reference_errors()[pair][pset]
+    regimes = CT.grid(pair, pset)[2]
+    missed = []
+    for strided in (False, True):
+        got = {kind: gpu_eval(P, pair, pset, kind, strided) for kind in CT.KINDS}
+        assert np.array_equal(got["deriv_reference"], got["deriv_autograd"], equal_nan=True), "the two derivative modes differ"
+        for kind in CT.KINDS:
+            err = CT.by_regime(CT.errors(got[kind], CT.truth(pair, pset, kind)), regimes)
+            for regime, v in err.items():
+                bound = CT.bound(rec[kind][regime])
+                print(f"{pair} {pset} {kind:16s} {regime:10s} gpu {v:10.3g}  host {rec[kind][regime]!s:>10}  bound {bound:.3g}")
+                if not strided:
+                    _dump({"pair": pair, "pset": pset, "kind": kind, "regime": regime, "gpu": v if math.isfinite(v) else "inf",
+                           "oracle": rec[kind][regime]})
+                if not v <= bound:
+                    missed.append((kind, regime, "strided" if strided else "dense", v, bound))
+    assert not missed, f"{pair} {pset}: cells over their bound (kind, regime, layout, error, bound): {missed}"
+
+
+@pytest.mark.parametrize("pair,pset", CT.cells())
+def test_value_column_sums(P, pair, pset):
+    """calculate_cost on the whole matrix: the sum over rows against fsum of the truth, at the cells' bounds plus the N
+    roundings of the sum"""
+    y, f, regimes = CT.grid(pair, pset)
+    rec = CT.reference_errors()[pair][pset]["value"]
+    tr = CT.truth(pair, pset, "value")
+    got = CT.gpu_cost(P, pair, pset, torch.as_tensor(y)).calculate_cost(torch.as_tensor(f).cuda()).cpu().numpy()
+    n = len(y)
+    for b, regime in enumerate(regimes):
+        hi = tr["hi"][:, b]
+        if not np.isfinite(hi).all():
+            with np.errstate(invalid="ignore"):
+                want = hi.sum()
+            assert (np.isnan(want) and np.isnan(got[b])) or got[b] == want, (pair, pset, regime, b, got[b], want)
+            continue
+        want = math.fsum(hi) + math.fsum(tr["lo"][:, b])
+        tol = CT.bound(rec[regime]) * float(tr["unit"][:, b].sum()) + n * 2.0 ** -53 * float(np.abs(hi).sum())
+        assert abs(got[b] - want) <= tol, (pair, pset, regime, b, got[b], want, abs(got[b] - want) / tol)
+
+
+def test_predict_samples_with_a_column_offset(P):
+    """predict_samples = exp(f + eps_j) in one kernel: against the link entry on the host-formed sum (the same bits), and
+    against the truth of the link at that sum"""
+    y, f, regimes = CT.grid("negative_binomial/exp", "a")
+    cost = CT.gpu_cost(P, "negative_binomial/exp", "a", torch.as_tensor(y))
+    g = torch.Generator().manual_seed(5)
+    eps = torch.randn(f.shape[1], generator=g, dtype=torch.float64)
+    ft = torch.as_tensor(f)
+    got = cost.predict_samples(ft.cuda(), observation_noise=eps.cuda()).cpu()
+    shifted = ft + eps[None, :]
+    assert torch.equal(got, cost.link_function(shifted.cuda()).cpu())
+    fin = shifted.abs() < 700
+    want = torch.tensor([[float(mp_exp(v)) for v in row] for row in shifted.tolist()], dtype=torch.float64)
+    assert ((got - want).abs()[fin] <= 4 * 2.0 ** -52 * want[fin]).all()
+    assert (got[shifted > 710] == math.inf).all() and (got[shifted < -746] == 0).all()
+    assert cost.sample_observation_noise(7).abs().sum() == 0  # observation_noise is None: no draw, as for Poisson
+
+
+def test_negative_binomial_under_another_link(P):
+    """The square link: the header's formula in mu = f^2 by the generic chain rule (run-time-switch code only), in the bulk,
+    against mpmath.  Units: 2^-53 x the sizes of the two terms of value and derivative; bound 16 -- two log1p of a
+    two-piece sum (each: a division or a product by 1 / r, the logarithm), two products and the sum for the value, one
+    division of products and the slope for the derivative, every primitive <= 1 ulp."""
+    import mpmath as mp
+
+    y = torch.tensor([0.0, 1.0, 3.0, 25.0, 1e6, 0.5, 1.0 / 3.0], dtype=torch.float64)
+    f = torch.tensor([0.3, -0.3, 0.9, -0.9, 1.3, -1.3, 2.6, -2.6, 2.95, -2.95, 17.0], dtype=torch.float64).repeat(len(y), 1)
+    for r in (0.7, 50.0):
+        cost = P.costs.NegativeBinomialCost(y, P.links.SquareLinkFunction(), r)
+        d = cost.calculate_cost_derivative(f.cuda()).cpu()
+        assert torch.equal(d, cost.calculate_cost_derivative(f.cuda(), force_autograd=True).cpu())
+        for a in range(len(y)):
+            v = P.costs.NegativeBinomialCost(y[a:a + 1], P.links.SquareLinkFunction(), r).calculate_cost(f[a:a + 1].cuda()).cpu()
+            for b in range(f.shape[1]):
+                rr, yy, ff = mp.mpf(r), mp.mpf(float(y[a])), mp.mpf(float(f[a, b]))
+                mu = ff * ff
+                t1, t2 = rr * mp.log1p(mu / rr), yy * mp.log1p(rr / mu)
+                assert abs(mp.mpf(float(v[b])) - (t1 + t2)) <= 16 * CT.U * (abs(t1) + abs(t2)), (r, a, b, float(v[b]), t1 + t2)
+                g1, g2 = rr * mu / (mu * (rr + mu)) * 2 * ff, rr * yy / (mu * (rr + mu)) * 2 * ff
+                assert abs(mp.mpf(float(d[a, b])) - (g1 - g2)) <= 16 * CT.U * (abs(g1) + abs(g2)), (r, a, b, float(d[a, b]), g1 - g2)
+
+
+def mp_exp(v):
+    import mpmath as mp
+
+    return mp.exp(mp.mpf(v)) if abs(v) < 1e4 else (mp.inf if v > 0 else mp.mpf(0))
