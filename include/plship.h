@@ -141,14 +141,31 @@ typedef enum {
  *   d cost / d f    = r sigma(t) - y sigma(-t)           in [-y, r]
  * so value and derivative are finite where exp(f) overflows or underflows (about r t for large t, about -y t for large -t).
  * This pair has kernel instantiations of its own on every step route; under any other link the formulas in mu are evaluated
- * by the chain rule. */
+ * by the chain rule.
+ * BETA is not in the reference either (an addition within ABI 7), for proportions in (0, 1).  Mean-precision form:
+ * mu = link(f), a = phi mu, b = phi (1 - mu), p[0] = phi, the precision, 0 < phi < inf.  The library's y argument holds
+ * z_n = logit(y_n) = log y_n - log1p(-y_n), NOT y_n: any finite z is valid (a proportion next to 0 or 1 keeps its bits).
+ * The value is the negative log-likelihood WITHOUT its f-independent terms lgamma(phi), log y, phi log(1 - y) (so energies
+ * are comparable between runs with the same phi only):
+ *   cost(z, f)      = lgamma(a) + lgamma(b) - a z
+ *   d cost / d f    = phi [psi(a) - psi(b) - z] * d mu / d f
+ * Both derivative modes return the same bits.  Under PLS_LINK_SIGMOID the pair is evaluated in f without the link's clip
+ * (the jitter is ignored, as EXP ignores it).  With e = exp(-|f|), mu_s = e / (1 + e), mu_b = 1 / (1 + e), a_s = phi mu_s,
+ * a_b = phi mu_b, w = phi mu_s mu_b, X(x) = x psi(x) (= -1 + x psi(1 + x) for small x) and sg = sign(f) (+1 at +-0):
+ *   cost(z, f)      = [lgamma(1 + a_s) - (log phi - |f| - log1p(e))] + lgamma(a_b) - (f >= 0 ? a_b : a_s) z
+ *   d cost / d f    = sg (w psi(a_b) - mu_b X(a_s)) - w z
+ * The bracket is lgamma(a_s) with log a_s formed from its parts, finite where a_s underflows; X(a_s) -> -1 keeps the
+ * derivative finite in the tails: it tends to +-1 as f -> +-inf (exactly +-1 at f = +-1e300), a bounded drift.  This pair
+ * has kernel instantiations of its own on every step route; under any other link the first two formulas are evaluated in
+ * the clipped p = link(f) by the chain rule. */
 typedef enum {
   PLS_COST_GAUSSIAN = 0,
   PLS_COST_POISSON = 1,
   PLS_COST_BERNOULLI = 2,
   PLS_COST_STUDENT_T = 3,
   PLS_COST_MULTIMODAL = 4,
-  PLS_COST_NEGATIVE_BINOMIAL = 5
+  PLS_COST_NEGATIVE_BINOMIAL = 5,
+  PLS_COST_BETA = 7 /* (6 is not a kind) */
 } pls_cost_kind;
 
 /* src/projected_langevin_sampling/link_functions.py:30-80
@@ -179,6 +196,7 @@ typedef struct {
    *          student_t {degrees_of_freedom, scale};
    *          multimodal {observation_noise (a STD, multimodal.py:56), shift, bernoulli_noise};
    *          negative_binomial {dispersion r};
+   *          beta {precision phi};
    *          poisson / bernoulli: unused */
   double p[4];
   double jitter; /* clip of sigmoid / probit links (link_functions.py:36, :64), default 1e-10 */
@@ -437,7 +455,8 @@ typedef enum pls_option {
 } pls_option;
 /* Diagnostic: out[i] = op(x[i]) with the device exp (op 0) / log (op 1) the per-element kernels use (csrc/fmath.h), or
  * out[i] = x[i] / x[n + i] with their division (op 2: fast_div, IEEE special cases restored; op 3: fast_div_normal), so
- * that their accuracy can be pinned against libm.  Not on the step path. */
+ * that their accuracy can be pinned against libm; op 4: lgamma(x), op 5: digamma(x), op 6: x digamma(x), for x > 0, as the
+ * Beta cost evaluates them (csrc/special_device.h).  Not on the step path. */
 int pls_debug_math(int32_t op, const double *x, double *out, int64_t n, void *stream);
 int pls_set_option(int32_t option, int64_t value);
 int64_t pls_get_option(int32_t option); /* -1 for an unknown option */

@@ -1,5 +1,6 @@
 from .base import PLSCost
 from .bernoulli import BernoulliCost
+from .beta import BetaCost
 from .gaussian import GaussianCost
 from .multimodal import MultiModalCost
 from .negative_binomial import NegativeBinomialCost
@@ -7,4 +8,4 @@ from .poisson import PoissonCost
 from .student_t import StudentTCost
 
 __all__ = ["PLSCost", "BernoulliCost", "GaussianCost", "PoissonCost", "StudentTCost", "MultiModalCost",
-           "NegativeBinomialCost"]
+           "NegativeBinomialCost", "BetaCost"]

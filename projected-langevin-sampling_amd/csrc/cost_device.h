@@ -7,6 +7,7 @@
 #include <type_traits>
 
 #include "fmath.h"
+#include "special_device.h"
 
 #include "../../include/plship.h"
 
@@ -18,6 +19,7 @@ struct CostP {
   double ip0;  // 1 / p0 (Gaussian: 1 / sigma2), computed on the host
   double mm_l1, mm_l2, mm_norm, mm_is2;  // multimodal: log p2, log(1 - p2), 0.5 log(2 pi s2), 1 / s2 (host)
                                          // negative binomial: mm_l1 = log r (host), the others unused
+                                         // beta: mm_l1 = log phi (host), the others unused
 };
 
 __host__ inline CostP make_costp(const pls_cost_desc *d) {
@@ -39,14 +41,15 @@ __host__ inline CostP make_costp(const pls_cost_desc *d) {
     c.mm_norm = 0.5 * std::log(2.0 * 3.14159265358979323846 * s2);
     c.mm_is2 = 1.0 / s2;
   }
-  if (d->cost == PLS_COST_NEGATIVE_BINOMIAL) c.mm_l1 = std::log(d->p[0]);
+  if (d->cost == PLS_COST_NEGATIVE_BINOMIAL || d->cost == PLS_COST_BETA) c.mm_l1 = std::log(d->p[0]);
   return c;
 }
 
 // THE list of the (cost, link) pairs with kernel instantiations of their own (the pairs the reference's experiments use, and
-// negative binomial/exp):
+// negative binomial/exp and beta/sigmoid):
 // f(integral_constant<COST>, integral_constant<LINK>) for one of them, f(-1, -1) -- the instantiation that switches at run
-// time -- for every other pair.  Every launcher that dispatches on the pair goes through here.
+// time -- for every other pair; Beta under another link gets f(PLS_COST_BETA, -1), which switches the link only (the
+// run-time-switch instantiation does not carry the Beta code).  Every launcher that dispatches on the pair goes through here.
 template <class F>
 __host__ inline int for_cost_link(const CostP &cp, F &&f) {
   using std::integral_constant;
@@ -58,6 +61,8 @@ __host__ inline int for_cost_link(const CostP &cp, F &&f) {
   if (c == PLS_COST_STUDENT_T && l == PLS_LINK_IDENTITY) return f(integral_constant<int, PLS_COST_STUDENT_T>{}, integral_constant<int, PLS_LINK_IDENTITY>{});
   if (c == PLS_COST_MULTIMODAL && l == PLS_LINK_IDENTITY) return f(integral_constant<int, PLS_COST_MULTIMODAL>{}, integral_constant<int, PLS_LINK_IDENTITY>{});
   if (c == PLS_COST_NEGATIVE_BINOMIAL && l == PLS_LINK_EXP) return f(integral_constant<int, PLS_COST_NEGATIVE_BINOMIAL>{}, integral_constant<int, PLS_LINK_EXP>{});
+  if (c == PLS_COST_BETA && l == PLS_LINK_SIGMOID) return f(integral_constant<int, PLS_COST_BETA>{}, integral_constant<int, PLS_LINK_SIGMOID>{});
+  if (c == PLS_COST_BETA) return f(integral_constant<int, PLS_COST_BETA>{}, integral_constant<int, -1>{});  // (the link at run time)
   return f(integral_constant<int, -1>{}, integral_constant<int, -1>{});
 }
 
@@ -149,6 +154,76 @@ __device__ inline double nb_exp_deriv(const CostP &c, double y, double f) {
   return a - b;
 }
 
+// The Beta cost (mean-precision form, plship.h) under the sigmoid link, evaluated in f without the link's clip.  y holds
+// z = logit of the observed proportion.  One exponential e = e^-|f| in (0, 1]: mu_s = e / (1 + e) <= 1/2 <= mu_b = 1 / (1 + e)
+// are the smaller and the bigger of (mu, 1 - mu), a_s = phi mu_s, a_b = phi mu_b the two shapes, w = phi mu_s mu_b:
+//   cost  = [lgamma(1 + a_s) - log a_s] + lgamma(a_b) - (f >= 0 ? a_b : a_s) z
+//           log a_s = log phi - |f| - log1p(e) from its parts: finite where a_s underflows (the cost grows like |f|)
+//   cost' = sg (mu_s X(a_b) - mu_b X(a_s)) - w z,   X(x) = x psi(x) = -1 + x psi(1 + x) below 1,  sg = +1 for f >= +-0
+//           (mu_s X(a_b) = w psi(a_b)); X(a_s) -> -1 in the tails, so cost' -> sg exactly: the drift is bounded
+// The two lgamma and the two X calls run as two rounds of one loop: one copy of the special-function code per function.
+// A kernel that asks for value and derivative calls both functions with the same arguments: the reduction (the exponential
+// and the division) is the same expression in both and is evaluated once.
+// The Beta code is NOT a case of cost_value / cost_deriv: those two, and with them every kernel of every other pair and the
+// run-time-switch instantiations, are what they were without it (the special functions in their switch made them spill).
+// Kernels reach it through cost_value_of<COST> / cost_deriv_of<COST> below, and for_cost_link sends Beta under ANY link to a
+// COST = PLS_COST_BETA instantiation.
+struct BetaLogit {
+  double e, mu_s, mu_b, a_s, a_b;
+  bool pos;
+};
+__device__ __forceinline__ BetaLogit beta_logit_reduce(double phi, double f) {
+#pragma clang fp contract(off)
+  BetaLogit q;
+  q.e = fast_exp(-fabs(f));
+  q.mu_b = fast_div_normal(1.0, 1.0 + q.e);  // 1 <= 1 + e <= 2
+  q.mu_s = q.e * q.mu_b;
+  q.a_s = phi * q.mu_s;
+  q.a_b = phi * q.mu_b;
+  q.pos = f >= 0.0;
+  return q;
+}
+__device__ __forceinline__ double beta_logit_value(double phi, double log_phi, double z, double f) {
+#pragma clang fp contract(off)
+  const BetaLogit q = beta_logit_reduce(phi, f);
+  const double s = 1.0 + q.e, tail = q.e - (s - 1.0);
+  const double log_as = (log_phi - fabs(f)) - fast_log_unit_tail(s, tail);
+  double lg = -log_as;
+#pragma nounroll
+  for (int i = 0; i < 2; ++i) lg += lgamma_pos(i ? q.a_b : q.a_s, i == 0);
+  return lg - (q.pos ? q.a_b : q.a_s) * z;
+}
+__device__ __forceinline__ double beta_logit_deriv(double phi, double z, double f) {
+#pragma clang fp contract(off)
+  const BetaLogit q = beta_logit_reduce(phi, f);
+  double d = 0.0;
+#pragma nounroll
+  for (int i = 0; i < 2; ++i) {
+    const double x = xdigamma_pos(i ? q.a_s : q.a_b);
+    d = i ? d - q.mu_b * x : q.mu_s * x;
+  }
+  return (q.pos ? d : -d) - (q.a_s * q.mu_b) * z;
+}
+// any other link: the header's two formulas in the clipped p = link(f) (the derivative without the link's slope)
+__device__ __forceinline__ double beta_link_value(double phi, double z, double p) {
+#pragma clang fp contract(off)
+  const double a = phi * p, b = phi * (1.0 - p);
+  double lg = 0.0;
+#pragma nounroll
+  for (int i = 0; i < 2; ++i) lg += lgamma_pos(i ? b : a);
+  return lg - a * z;
+}
+__device__ __forceinline__ double beta_link_deriv(double phi, double z, double p) {
+#pragma clang fp contract(off)
+  double d = -z;
+#pragma nounroll
+  for (int i = 0; i < 2; ++i) {
+    const double x = digamma_pos(i ? phi * (1.0 - p) : phi * p);
+    d = i ? d - x : d + x;
+  }
+  return phi * d;
+}
+
 // cost(y, f) for one (n, j) entry; summed over n by the callers.
 __device__ inline double cost_value(const CostP &c, double y, double f) {
 #pragma clang fp contract(off)
@@ -232,6 +307,33 @@ __device__ inline double cost_deriv(const CostP &c, double y, double f) {
     default:  // (the host entries refuse every other id)
       return __builtin_nan("");
   }
+}
+
+// The per-element calls of the kernels that are instantiated per pair: COST as for_cost_link passed it (a kernel with
+// COST >= 0 sets c.cost = COST, and c.link = LINK where LINK >= 0).  p0 = phi, y = logit of the observation.
+__device__ __forceinline__ double beta_cost_value(const CostP &c, double y, double f) {
+#pragma clang fp contract(off)
+  if (c.link == PLS_LINK_SIGMOID) return beta_logit_value(c.p0, c.mm_l1, y, f);  // (in f: no clip)
+  double slope;
+  const double p = link_eval(c.link, f, c.jitter, &slope);
+  return beta_link_value(c.p0, y, p);
+}
+__device__ __forceinline__ double beta_cost_deriv(const CostP &c, double y, double f) {  // one value for both modes
+#pragma clang fp contract(off)
+  if (c.link == PLS_LINK_SIGMOID) return beta_logit_deriv(c.p0, y, f);  // (in f: no clip)
+  double slope;
+  const double p = link_eval(c.link, f, c.jitter, &slope);
+  return beta_link_deriv(c.p0, y, p) * slope;
+}
+template <int COST>
+__device__ __forceinline__ double cost_value_of(const CostP &c, double y, double f) {
+  if constexpr (COST == PLS_COST_BETA) return beta_cost_value(c, y, f);
+  else return cost_value(c, y, f);
+}
+template <int COST>
+__device__ __forceinline__ double cost_deriv_of(const CostP &c, double y, double f) {
+  if constexpr (COST == PLS_COST_BETA) return beta_cost_deriv(c, y, f);
+  else return cost_deriv(c, y, f);
 }
 
 }  // namespace plship

@@ -29,24 +29,24 @@ struct EpiCostDeriv {
     CostP cp = this->cp;
     if constexpr (COST >= 0) {
       cp.cost = COST;
-      cp.link = LINK;
+      if constexpr (LINK >= 0) cp.link = LINK;
     }
     if (!vpart) {
       epilogue_row_pairs<TI, TJ, 1>(acc, iw, jw, lane, wave, I, J, lds, yl, 0.0,
                                  [&](int64_t i, int64_t j, double v0, bool hi, double v1, const RowConsts &rc) {
-                                   G[i * ldg + j] = cost_deriv(cp, rc.k0_lo, v0);
-                                   if (hi) G[(i + 4) * ldg + j] = cost_deriv(cp, rc.k0_hi, v1);
+                                   G[i * ldg + j] = cost_deriv_of<COST>(cp, rc.k0_lo, v0);
+                                   if (hi) G[(i + 4) * ldg + j] = cost_deriv_of<COST>(cp, rc.k0_hi, v1);
                                  });
       return;
     }
     double s = 0.0;
     epilogue_row_pairs<TI, TJ, 1>(acc, iw, jw, lane, wave, I, J, lds, yl, 0.0,
                                [&](int64_t i, int64_t j, double v0, bool hi, double v1, const RowConsts &rc) {
-                                 G[i * ldg + j] = cost_deriv(cp, rc.k0_lo, v0);
-                                 s += cost_value(cp, rc.k0_lo, v0);
+                                 G[i * ldg + j] = cost_deriv_of<COST>(cp, rc.k0_lo, v0);
+                                 s += cost_value_of<COST>(cp, rc.k0_lo, v0);
                                  if (hi) {
-                                   G[(i + 4) * ldg + j] = cost_deriv(cp, rc.k0_hi, v1);
-                                   s += cost_value(cp, rc.k0_hi, v1);
+                                   G[(i + 4) * ldg + j] = cost_deriv_of<COST>(cp, rc.k0_hi, v1);
+                                   s += cost_value_of<COST>(cp, rc.k0_hi, v1);
                                  }
                                });
     constexpr int WJ = TJ * 16;
@@ -146,13 +146,13 @@ struct EpiCostValue {
     CostP cp = this->cp;
     if constexpr (COST >= 0) {
       cp.cost = COST;
-      cp.link = LINK;
+      if constexpr (LINK >= 0) cp.link = LINK;
     }
     const double yl = load_row_constants(y, iw, lane, I);
     epilogue_row_pairs<TI, TJ, 1>(acc, iw, jw, lane, wave, I, J, lds, yl, 0.0,
                                [&](int64_t, int64_t, double v0, bool hi, double v1, const RowConsts &rc) {
-                                 s += cost_value(cp, rc.k0_lo, v0);
-                                 if (hi) s += cost_value(cp, rc.k0_hi, v1);
+                                 s += cost_value_of<COST>(cp, rc.k0_lo, v0);
+                                 if (hi) s += cost_value_of<COST>(cp, rc.k0_hi, v1);
                                });
     if (WJ == 32) s += __shfl_xor(s, 32);  // two lane halves share the 32 columns
     constexpr int NWJ = BJ / WJ, NWI = BI / WI;

@@ -696,7 +696,10 @@ __global__ __launch_bounds__(256) void debug_math_kernel(int op, const double *_
   if (op == 0) out[i] = fast_exp(x[i]);
   else if (op == 1) out[i] = fast_log(x[i]);
   else if (op == 2) out[i] = fast_div(x[i], x[n + i]);         // numerators x[0 .. n), denominators x[n .. 2 n)
-  else out[i] = fast_div_normal(x[i], x[n + i]);
+  else if (op == 3) out[i] = fast_div_normal(x[i], x[n + i]);
+  else if (op == 4) out[i] = lgamma_pos(x[i]);       // x > 0
+  else if (op == 5) out[i] = digamma_pos(x[i]);      // x > 0
+  else out[i] = xdigamma_pos(x[i]);                  // x >= 0
 }
 
 // elementwise cost derivative (un-fused entry point)
@@ -705,7 +708,10 @@ __global__ __launch_bounds__(256) void cost_deriv_kernel(CostP cp, const double 
                                                           double *__restrict__ G, int64_t ldg) {
   const int64_t col = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (col >= j) return;
-  for (int64_t row = blockIdx.y; row < n; row += gridDim.y) G[row * ldg + col] = cost_deriv(cp, y[row], F[row * ldf + col]);
+  for (int64_t row = blockIdx.y; row < n; row += gridDim.y) {
+    const double yv = y[row], f = F[row * ldf + col];
+    G[row * ldg + col] = (cp.cost == PLS_COST_BETA) ? beta_cost_deriv(cp, yv, f) : cost_deriv(cp, yv, f);
+  }
 }
 
 // stage 1 of the column sums: partial[rb][col] = sum over rows [rb*RB, rb*RB + RB) of cost(y, F)
@@ -721,7 +727,10 @@ __global__ __launch_bounds__(256) void cost_value_partial_kernel(CostP cp, const
   if (col < j) {
     for (int rr = ty; rr < COST_RB; rr += 4) {
       const int64_t row = r0 + rr;
-      if (row < n) s += cost_value(cp, y[row], F[row * ldf + col]);
+      if (row < n) {
+        const double yv = y[row], f = F[row * ldf + col];
+        s += (cp.cost == PLS_COST_BETA) ? beta_cost_value(cp, yv, f) : cost_value(cp, yv, f);
+      }
     }
   }
   red[ty][tx] = s;
@@ -1595,7 +1604,8 @@ static int launch_langevin_update(double *out, int64_t ldo, int add_u, const dou
 // ---------------------------------------------------------------------------------------------------------------
 static int validate_cost(const pls_cost_desc *c) {
   PLS_REQUIRE(c != nullptr, "cost descriptor is NULL");
-  PLS_REQUIRE(c->cost >= PLS_COST_GAUSSIAN && c->cost <= PLS_COST_NEGATIVE_BINOMIAL, "unknown cost kind %d", c->cost);
+  PLS_REQUIRE((c->cost >= PLS_COST_GAUSSIAN && c->cost <= PLS_COST_NEGATIVE_BINOMIAL) || c->cost == PLS_COST_BETA,
+              "unknown cost kind %d", c->cost);
   PLS_REQUIRE(c->link >= PLS_LINK_IDENTITY && c->link <= PLS_LINK_EXP, "unknown link kind %d", c->link);
   PLS_REQUIRE(c->deriv_mode == PLS_DERIV_REFERENCE || c->deriv_mode == PLS_DERIV_AUTOGRAD, "unknown deriv_mode %d",
               c->deriv_mode);
@@ -1606,6 +1616,7 @@ static int validate_cost(const pls_cost_desc *c) {
     PLS_REQUIRE(c->p[0] > 0.0 && c->p[2] > 0.0 && c->p[2] < 1.0, "multimodal cost needs sigma > 0, 0 < bernoulli_noise < 1");
   if (c->cost == PLS_COST_NEGATIVE_BINOMIAL)
     PLS_REQUIRE(c->p[0] > 0.0 && std::isfinite(c->p[0]), "negative-binomial cost needs a finite dispersion > 0");
+  if (c->cost == PLS_COST_BETA) PLS_REQUIRE(c->p[0] > 0.0 && std::isfinite(c->p[0]), "beta cost needs a finite precision > 0");
   return PLS_OK;
 }
 
@@ -2038,7 +2049,8 @@ int pls_set_option(int32_t option, int64_t value) {
 }
 
 int pls_debug_math(int32_t op, const double *x, double *out, int64_t n, void *stream) {
-  PLS_REQUIRE(op >= 0 && op <= 3, "debug_math: op must be 0 (exp), 1 (log), 2 (fast_div) or 3 (fast_div_normal)");
+  PLS_REQUIRE(op >= 0 && op <= 6,
+              "debug_math: op must be 0 (exp), 1 (log), 2 (fast_div), 3 (fast_div_normal), 4 (lgamma), 5 (digamma) or 6 (x digamma)");
   PLS_REQUIRE(x && out && n >= 0, "debug_math: bad arguments");
   if (n == 0) return PLS_OK;
   hipLaunchKernelGGL(debug_math_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, S(stream), op, x, out, n);

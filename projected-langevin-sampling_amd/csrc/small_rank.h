@@ -74,7 +74,7 @@ __global__ __launch_bounds__(256, 2) void small_rank_kernel(SmallRankP p) {
   CostP cp = p.cp;
   if constexpr (COST >= 0) {
     cp.cost = COST;
-    cp.link = LINK;
+    if constexpr (LINK >= 0) cp.link = LINK;
   }
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int q = lane >> 4, c = lane & 15;
@@ -225,11 +225,11 @@ __global__ __launch_bounds__(256, 2) void small_rank_kernel(SmallRankP p) {
         const double yr = (KB <= 6) ? yv[b][r] : Y[row];
         const bool valid = !LAST || (n0 + row < nend);
         if (MODE != SR_MODE_DRIFT) {
-          const double cval = cost_value(cp, yr, f[r]);
+          const double cval = cost_value_of<COST>(cp, yr, f[r]);
           vsum += valid ? cval : 0.0;
         }
         if (MODE != SR_MODE_VALUE) {
-          const double gval = cost_deriv(cp, yr, f[r]);
+          const double gval = cost_deriv_of<COST>(cp, yr, f[r]);
           f[r] = valid ? gval : 0.0;
         }
       }

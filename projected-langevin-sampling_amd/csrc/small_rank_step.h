@@ -167,7 +167,7 @@ __global__ __launch_bounds__(256, 2) void small_rank_step_kernel(SrStepP p) {
   CostP cp = p.cp;
   if constexpr (COST >= 0) {
     cp.cost = COST;
-    cp.link = LINK;
+    if constexpr (LINK >= 0) cp.link = LINK;
   }
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -305,10 +305,10 @@ __global__ __launch_bounds__(256, 2) void small_rank_step_kernel(SrStepP p) {
       for (int r = 0; r < 4; ++r) {
         const bool valid = n0w + q + 4 * r < nend;
         if constexpr (VALUE) {
-          const double cval = cost_value(cp, yv[r], f[r]);
+          const double cval = cost_value_of<COST>(cp, yv[r], f[r]);
           vsum += valid ? cval : 0.0;
         }
-        const double gval = cost_deriv(cp, yv[r], f[r]);
+        const double gval = cost_deriv_of<COST>(cp, yv[r], f[r]);
         f[r] = valid ? gval : 0.0;
       }
     } else {  // a tile with prior rows (at most cdiv(K, 16) + 1 tiles of the last slab): f^2 / 2 and f for those
@@ -317,10 +317,10 @@ __global__ __launch_bounds__(256, 2) void small_rank_step_kernel(SrStepP p) {
         const bool valid = n0w + q + 4 * r < nend;
         const bool prow = n0w + q + 4 * r >= p.Ndata;
         if constexpr (VALUE) {
-          const double cval = prow ? 0.5 * (f[r] * f[r]) : cost_value(cp, yv[r], f[r]);
+          const double cval = prow ? 0.5 * (f[r] * f[r]) : cost_value_of<COST>(cp, yv[r], f[r]);
           vsum += valid ? cval : 0.0;
         }
-        const double gval = prow ? f[r] : cost_deriv(cp, yv[r], f[r]);
+        const double gval = prow ? f[r] : cost_deriv_of<COST>(cp, yv[r], f[r]);
         f[r] = valid ? gval : 0.0;
       }
     }

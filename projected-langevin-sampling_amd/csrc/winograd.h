@@ -111,7 +111,7 @@ struct EpiWinoCost {
     CostP cp = this->cp;
     if constexpr (COST >= 0) {
       cp.cost = COST;
-      cp.link = LINK;
+      if constexpr (LINK >= 0) cp.link = LINK;
     }
     const int q = lane >> 4, c16 = lane & 15;
     double *w = lds + wave * 16 * STRIDE;
@@ -149,8 +149,8 @@ struct EpiWinoCost {
         const double yv = __shfl(yl, ta * 16 + rr);
         double &x = w[rr * STRIDE + lane];
         const double f = x;
-        x = cost_deriv(cp, yv, f);
-        if (vpart && prow0 + 16 * (ta & 1) + rr < I) s += cost_value(cp, yv, f);
+        x = cost_deriv_of<COST>(cp, yv, f);
+        if (vpart && prow0 + 16 * (ta & 1) + rr < I) s += cost_value_of<COST>(cp, yv, f);
       }
       __builtin_amdgcn_wave_barrier();
       pass(ta, false);

@@ -1,0 +1,124 @@
+"""GPU: the element-wise entries for the Beta pairs -- pls_cost_derivative (both derivative modes, which must be the same
+bits) and pls_cost_value -- against the per-element mpmath truth of tests/beta_cost_truth.py on its whole grid, dense and
+strided: bulk, the centre and the root where the derivative cancels, both tails, the far columns where exp(-|f|) underflows
+while value and derivative stay finite, +-0 and subnormals; beta/probit on both sides of the clip.  And the device special
+functions themselves (pls_debug_math ops 4-6) per element against mpmath.
+
+The bound is tests/test_gpu_cost_elements.py's, unchanged: per cell the larger of 4x the host restatement's recorded error
+(tests/golden/beta_cost_reference_errors.json) and 4 units.  PLS_COST_TRUTH_DUMP=<file> appends the measured maxima as JSON
+lines (the rows of DESIGN.md section 3 are made from them)."""
+import json
+import math
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import beta_cost_truth as BT
+from test_gpu_parity import P, _f64_default  # noqa: F401  (fixtures)
+
+pytestmark = pytest.mark.gpu
+
+
+def _dump(record):
+    path = os.environ.get("PLS_COST_TRUTH_DUMP")
+    if path:
+        with open(path, "a") as fh:
+            fh.write(json.dumps(record) + "\n")
+
+
+def gpu_eval(P, pair, pset, kind, strided=False):
+    """the library on the grid, per element (N, J); ``strided``: the samples are the left columns of a wider matrix"""
+    z, f, _ = BT.grid(pair, pset)
+    zt, ft = torch.as_tensor(z), torch.as_tensor(f).cuda()
+    if strided:
+        wide = torch.full((f.shape[0], f.shape[1] + 3), float("nan"), device="cuda")
+        wide[:, :f.shape[1]] = ft
+        ft = wide[:, :f.shape[1]]
+    if kind == "value":  # the entry sums over rows: one row at a time
+        rows = [BT.gpu_cost(P, pair, pset, zt[a:a + 1]).calculate_cost(ft[a:a + 1]) for a in range(len(z))]
+        return torch.stack(rows).cpu().numpy()
+    return BT.gpu_cost(P, pair, pset, zt).calculate_cost_derivative(ft, force_autograd=kind == "deriv_autograd").cpu().numpy()
+
+
+@pytest.mark.parametrize("pair,pset", BT.cells())
+def test_elements_against_truth(P, pair, pset):
+    rec = BT.reference_errors()[pair][pset]
+    regimes = BT.grid(pair, pset)[2]
+    missed = []
+    for strided in (False, True):
+        got = {kind: gpu_eval(P, pair, pset, kind, strided) for kind in BT.KINDS}
+        assert np.array_equal(got["deriv_reference"], got["deriv_autograd"], equal_nan=True), "the two derivative modes differ"
+        for kind in BT.KINDS:
+            err = BT.by_regime(BT.errors(got[kind], BT.truth(pair, pset, kind)), regimes)
+            for regime, v in err.items():
+                bound = BT.bound(rec[kind][regime])
+                print(f"{pair} {pset} {kind:16s} {regime:10s} gpu {v:10.3g}  host {rec[kind][regime]!s:>10}  bound {bound:.3g}")
+                if not strided:
+                    _dump({"pair": pair, "pset": pset, "kind": kind, "regime": regime, "gpu": v if math.isfinite(v) else "inf",
+                           "oracle": rec[kind][regime]})
+                if not v <= bound:
+                    missed.append((kind, regime, "strided" if strided else "dense", v, bound))
+    assert not missed, f"{pair} {pset}: cells over their bound (kind, regime, layout, error, bound): {missed}"
+
+
+def test_the_tails_stay_finite_and_the_drift_is_exactly_one(P):
+    """the issue's two examples: the value at f = 745, phi = 0.3 (lgamma(phi exp(-745)) itself is +inf), and the derivative at
+    f = +-1e300, exactly +-1 for any phi and z"""
+    z = torch.tensor([0.0], dtype=torch.float64)
+    v = BT.gpu_cost(P, "beta/sigmoid", "a", z).calculate_cost(torch.tensor([[745.0]], device="cuda")).item()
+    assert math.isfinite(v) and abs(v - 747.3) < 0.05
+    for pset in BT.PARAMS:
+        cost = BT.gpu_cost(P, "beta/sigmoid", pset, torch.tensor(BT.Z_ROWS))
+        f = torch.tensor([[1e300, -1e300, 1e10, -1e10]], device="cuda").repeat(len(BT.Z_ROWS), 1)
+        d = cost.calculate_cost_derivative(f).cpu()
+        assert torch.equal(d[:, :2], torch.tensor([[1.0, -1.0]]).repeat(len(BT.Z_ROWS), 1).double())
+        assert torch.equal(d[:, 2:], d[:, :2])
+
+
+@pytest.mark.parametrize("pair,pset", BT.cells())
+def test_value_column_sums(P, pair, pset):
+    """calculate_cost on the whole matrix: the sum over rows against fsum of the truth, at the cells' bounds plus the N
+    roundings of the sum"""
+    z, f, regimes = BT.grid(pair, pset)
+    rec = BT.reference_errors()[pair][pset]["value"]
+    tr = BT.truth(pair, pset, "value")
+    got = BT.gpu_cost(P, pair, pset, torch.as_tensor(z)).calculate_cost(torch.as_tensor(f).cuda()).cpu().numpy()
+    n = len(z)
+    for b, regime in enumerate(regimes):
+        hi = tr["hi"][:, b]
+        want = math.fsum(hi) + math.fsum(tr["lo"][:, b])
+        tol = BT.bound(rec[regime]) * float(tr["unit"][:, b].sum()) + n * 2.0 ** -53 * float(np.abs(hi).sum())
+        assert abs(got[b] - want) <= tol, (pair, pset, regime, b, got[b], want, abs(got[b] - want) / tol)
+
+
+@pytest.mark.parametrize("name", list(BT.SPECIALS))
+def test_special_functions_against_mpmath(P, name):
+    """pls_debug_math ops 4-6 per element: log-spaced over the fp64 range, across the seams of the pieces, and dense around 1,
+    the zero of psi and 2"""
+    x, regimes = BT.special_points(name)
+    xt = torch.as_tensor(x).cuda()
+    out = torch.empty_like(xt)
+    lib = P.pkg._lib.load()
+    P.pkg._lib.check(lib.pls_debug_math(BT.SPECIALS[name], xt.data_ptr(), out.data_ptr(), xt.numel(), None), "pls_debug_math")
+    torch.cuda.synchronize()
+    err = BT.special_by_regime(BT.errors(out.cpu().numpy().reshape(-1, 1), BT.special_truth(name)), regimes)
+    rec = BT.reference_errors()["special"][name]
+    missed = []
+    for regime, v in err.items():
+        bound = BT.bound(rec[regime])
+        print(f"{name:9s} {regime:10s} gpu {v:10.3g}  host {rec[regime]!s:>10}  bound {bound:.3g}")
+        _dump({"pair": "special", "pset": name, "kind": "value", "regime": regime, "gpu": v if math.isfinite(v) else "inf", "oracle": rec[regime]})
+        if not v <= bound:
+            missed.append((regime, v, bound))
+    assert not missed, f"{name}: regimes over their bound (regime, error, bound): {missed}"
+    # X(0) = -1 exactly (no pole), and lgamma's exact zeros
+    probe = torch.tensor([0.0, 1.0, 2.0], device="cuda")
+    res = torch.empty_like(probe)
+    P.pkg._lib.check(lib.pls_debug_math(BT.SPECIALS[name], probe.data_ptr(), res.data_ptr(), 3, None), "pls_debug_math")
+    res = res.cpu()
+    if name == "xdigamma":
+        assert res[0].item() == -1.0
+    if name == "lgamma":
+        assert res[0].item() == math.inf and res[1].item() == 0.0 and res[2].item() == 0.0
