@@ -157,7 +157,21 @@ typedef enum {
  * The bracket is lgamma(a_s) with log a_s formed from its parts, finite where a_s underflows; X(a_s) -> -1 keeps the
  * derivative finite in the tails: it tends to +-1 as f -> +-inf (exactly +-1 at f = +-1e300), a bounded drift.  This pair
  * has kernel instantiations of its own on every step route; under any other link the first two formulas are evaluated in
- * the clipped p = link(f) by the chain rule. */
+ * the clipped p = link(f) by the chain rule.
+ * ORDINAL is not in the reference either (an addition within ABI 7), for ordered categories 0 .. K-1, 2 <= K <= 5: the
+ * cumulative-logit (proportional-odds) model P(y <= k | f) = sigma(b_(k+1) - f).  p[0..3] hold the cutpoints b_1 < b_2 < ...
+ * in ascending order, the unused trailing entries +inf, so K = 1 + the number of finite entries; p[0] is finite.  b_0 = -inf
+ * and b_K = +inf.  The library's y argument holds the category index as a double.  For label k write lo = b_k, hi = b_(k+1).
+ * The value is the negative log-likelihood WITHOUT its f-independent term -log(1 - exp(-(hi - lo))) (so energies are
+ * comparable between runs with the same cutpoints only):
+ *   cost(k, f)      = softplus(f - hi) + softplus(lo - f),    softplus(t) = max(t, 0) + log1p(exp(-|t|))
+ *   d cost / d f    = sigma(f - hi) - sigma(lo - f)           in (-1, 1)
+ * with sigma(|t|) = 1 / (1 + exp(-|t|)), sigma(-|t|) = exp(-|t|) / (1 + exp(-|t|)): each term is evaluated in t = f - cutpoint
+ * with one exponential.  The top category's upper term and the bottom category's lower term (an infinite cutpoint on its own
+ * side) are exactly 0.  Both derivative modes return the same bits; the jitter is ignored.  A y that is not one of 0, 1, 2,
+ * 3, 4 (NaN included) gives NaN for value and derivative; a label >= K (its lower cutpoint is +inf) gives the value +inf and
+ * the derivative -1: callers validate their labels.  Only PLS_LINK_IDENTITY is accepted (ordered probit is not provided);
+ * the pair has kernel instantiations of its own on every step route. */
 typedef enum {
   PLS_COST_GAUSSIAN = 0,
   PLS_COST_POISSON = 1,
@@ -165,7 +179,8 @@ typedef enum {
   PLS_COST_STUDENT_T = 3,
   PLS_COST_MULTIMODAL = 4,
   PLS_COST_NEGATIVE_BINOMIAL = 5,
-  PLS_COST_BETA = 7 /* (6 is not a kind) */
+  PLS_COST_BETA = 7, /* (6 is not a kind) */
+  PLS_COST_ORDINAL = 9 /* (8 is not a kind) */
 } pls_cost_kind;
 
 /* src/projected_langevin_sampling/link_functions.py:30-80
@@ -197,6 +212,7 @@ typedef struct {
    *          multimodal {observation_noise (a STD, multimodal.py:56), shift, bernoulli_noise};
    *          negative_binomial {dispersion r};
    *          beta {precision phi};
+   *          ordinal {up to four ascending cutpoints, +inf for the unused trailing ones};
    *          poisson / bernoulli: unused */
   double p[4];
   double jitter; /* clip of sigmoid / probit links (link_functions.py:36, :64), default 1e-10 */

@@ -5,8 +5,8 @@ The reference stores a trained sampler as ``torch.save({"particles", "observatio
 (experiments/loaders.py:10-28).  Files written by either implementation load in the other.  Two optional extra keys
 make a J-sharded run exactly resumable: ``noise_step`` (the step counter of the Philox stream) and
 ``number_of_particles`` (the global J a shard belongs to); the reference ignores unknown keys.  A cost with a
-``dispersion`` (NegativeBinomialCost) or a ``precision`` (BetaCost) has it stored under that key and restored from it, as
-``observation_noise`` is.
+``dispersion`` (NegativeBinomialCost), a ``precision`` (BetaCost) or ``cutpoints`` (OrdinalCost, a list of floats) has it
+stored under that key and restored from it, as ``observation_noise`` is.
 
 Particles of the orthonormal basis are COORDINATES in the eigenvector gauge of the basis they were trained with
 (orthonormal.py:46-68), and an eigendecomposition is defined only up to signs and rotations inside clusters: the file
@@ -49,6 +49,9 @@ def save_pls(pls: PLS, particles: torch.Tensor, model_path: str, best_lr: Option
     precision = getattr(getattr(pls, "cost", None), "precision", None)
     if precision is not None:
         state["precision"] = float(precision)
+    cutpoints = getattr(getattr(pls, "cost", None), "cutpoints", None)
+    if cutpoints is not None:
+        state["cutpoints"] = [float(c) for c in cutpoints]
     fingerprint = _basis_fingerprint(pls)
     if fingerprint is not None:
         state["spectrum_fingerprint"] = fingerprint
@@ -80,6 +83,8 @@ def load_pls(pls: PLS, model_path: str, on_gauge_mismatch: str = "raise") -> Tup
         pls.cost.dispersion = float(model_config["dispersion"])
     if "precision" in model_config and hasattr(getattr(pls, "cost", None), "precision"):
         pls.cost.precision = float(model_config["precision"])
+    if "cutpoints" in model_config and hasattr(getattr(pls, "cost", None), "cutpoints"):
+        pls.cost.cutpoints = [float(c) for c in model_config["cutpoints"]]
     print(f"Loaded particles and observation_noise from {model_path=}.")
     best_lr = model_config.get("best_lr")
     number_of_epochs = model_config.get("number_of_epochs")

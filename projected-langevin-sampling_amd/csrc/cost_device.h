@@ -46,7 +46,7 @@ __host__ inline CostP make_costp(const pls_cost_desc *d) {
 }
 
 // THE list of the (cost, link) pairs with kernel instantiations of their own (the pairs the reference's experiments use, and
-// negative binomial/exp and beta/sigmoid):
+// negative binomial/exp, beta/sigmoid and ordinal/identity -- the only link the ordinal cost is accepted with):
 // f(integral_constant<COST>, integral_constant<LINK>) for one of them, f(-1, -1) -- the instantiation that switches at run
 // time -- for every other pair; Beta under another link gets f(PLS_COST_BETA, -1), which switches the link only (the
 // run-time-switch instantiation does not carry the Beta code).  Every launcher that dispatches on the pair goes through here.
@@ -63,6 +63,7 @@ __host__ inline int for_cost_link(const CostP &cp, F &&f) {
   if (c == PLS_COST_NEGATIVE_BINOMIAL && l == PLS_LINK_EXP) return f(integral_constant<int, PLS_COST_NEGATIVE_BINOMIAL>{}, integral_constant<int, PLS_LINK_EXP>{});
   if (c == PLS_COST_BETA && l == PLS_LINK_SIGMOID) return f(integral_constant<int, PLS_COST_BETA>{}, integral_constant<int, PLS_LINK_SIGMOID>{});
   if (c == PLS_COST_BETA) return f(integral_constant<int, PLS_COST_BETA>{}, integral_constant<int, -1>{});  // (the link at run time)
+  if (c == PLS_COST_ORDINAL && l == PLS_LINK_IDENTITY) return f(integral_constant<int, PLS_COST_ORDINAL>{}, integral_constant<int, PLS_LINK_IDENTITY>{});
   return f(integral_constant<int, -1>{}, integral_constant<int, -1>{});
 }
 
@@ -224,6 +225,65 @@ __device__ __forceinline__ double beta_link_deriv(double phi, double z, double p
   return phi * d;
 }
 
+// The ordinal cost (cumulative logit / proportional odds, plship.h) under the identity link.  y holds the category index
+// 0 .. 4, p0 .. p3 the ascending cutpoints (+inf for the unused trailing ones); b_0 = -inf and b_5 = +inf complete them, and
+// label k lies between lo = b_k and hi = b_(k+1):
+//   cost  = softplus(f - hi) + softplus(lo - f),   softplus(t) = max(t, 0) + log1p(e^-|t|)
+//   cost' = sigma(f - hi) - sigma(lo - f),   sigma(|t|) = 1 / (1 + e^-|t|),   sigma(-|t|) = e^-|t| / (1 + e^-|t|)
+// One exponential per term, the reduction of the negative binomial (nb_exp_reduce); a term with an infinite cutpoint on its own
+// side (the top category's upper, the bottom category's lower term) is exactly 0, whatever f is.  lo = +inf (a label >= K) gives
+// the value +inf and the derivative -1; a y that is not one of 0 .. 4 selects NaN cutpoints, and the result is that NaN.
+// (lo, hi) come from compares of y against 0 .. 4: scalar work where y is uniform across the wave (the row-walking epilogues).
+// A kernel that asks for value and derivative calls both functions with the same arguments: the two reductions are the same
+// expressions in both and are evaluated once.  Like the Beta code this is NOT a case of cost_value / cost_deriv.
+struct OrdinalCuts {
+  double lo, hi;
+};
+__device__ __forceinline__ OrdinalCuts ordinal_cuts(const CostP &c, double y) {
+  // (one select per line on values already in registers: a nested ?: chain over the loads of c.p0 .. c.p3 becomes control flow
+  // whose merges value and derivative do not share, and then they do not share the exponentials either)
+  const double p0 = c.p0, p1 = c.p1, p2 = c.p2, p3 = c.p3, inf = __builtin_huge_val();
+  const bool y0 = y == 0.0, y1 = y == 1.0, y2 = y == 2.0, y3 = y == 3.0, y4 = y == 4.0;
+  OrdinalCuts k;
+  k.lo = __builtin_nan("");
+  k.lo = y4 ? p3 : k.lo;
+  k.lo = y3 ? p2 : k.lo;
+  k.lo = y2 ? p1 : k.lo;
+  k.lo = y1 ? p0 : k.lo;
+  k.lo = y0 ? -inf : k.lo;
+  k.hi = __builtin_nan("");
+  k.hi = y4 ? inf : k.hi;
+  k.hi = y3 ? p3 : k.hi;
+  k.hi = y2 ? p2 : k.hi;
+  k.hi = y1 ? p1 : k.hi;
+  k.hi = y0 ? p0 : k.hi;
+  return k;
+}
+__device__ __forceinline__ double ordinal_value(const CostP &c, double y, double f) {
+#pragma clang fp contract(off)
+  const OrdinalCuts k = ordinal_cuts(c, y);
+  const double tu = f - k.hi, td = k.lo - f;
+  const NbExp u = nb_exp_reduce(tu), d = nb_exp_reduce(td);
+  const double lu = fast_log_unit_tail(u.s, u.tail), ld = fast_log_unit_tail(d.s, d.tail);  // log1p(e^-|t|) in [0, log 2]
+  double up = u.pos ? tu + lu : lu, dn = d.pos ? td + ld : ld;  // softplus(f - hi), softplus(lo - f)
+  up = (k.hi == __builtin_huge_val()) ? 0.0 : up;
+  dn = (k.lo == -__builtin_huge_val()) ? 0.0 : dn;
+  const double v = up + dn;
+  return (k.hi == k.hi) ? v : k.hi;
+}
+__device__ __forceinline__ double ordinal_deriv(const CostP &c, double y, double f) {  // one value for both modes
+#pragma clang fp contract(off)
+  const OrdinalCuts k = ordinal_cuts(c, y);
+  const double tu = f - k.hi, td = k.lo - f;
+  const NbExp u = nb_exp_reduce(tu), d = nb_exp_reduce(td);
+  const double bu = fast_div_normal(1.0, u.s), bd = fast_div_normal(1.0, d.s);  // sigma(|t|); 1 <= s <= 2
+  double a = u.pos ? bu : u.e * bu, b = d.pos ? bd : d.e * bd;  // sigma(f - hi), sigma(lo - f)
+  a = (k.hi == __builtin_huge_val()) ? -0.0 : a;  // (-0: an underflowed sigma(lo - f) then leaves -0, the sign of the derivative)
+  b = (k.lo == -__builtin_huge_val()) ? -0.0 : b;
+  const double g = a - b;
+  return (k.hi == k.hi) ? g : k.hi;
+}
+
 // cost(y, f) for one (n, j) entry; summed over n by the callers.
 __device__ inline double cost_value(const CostP &c, double y, double f) {
 #pragma clang fp contract(off)
@@ -310,7 +370,7 @@ __device__ inline double cost_deriv(const CostP &c, double y, double f) {
 }
 
 // The per-element calls of the kernels that are instantiated per pair: COST as for_cost_link passed it (a kernel with
-// COST >= 0 sets c.cost = COST, and c.link = LINK where LINK >= 0).  p0 = phi, y = logit of the observation.
+// COST >= 0 sets c.cost = COST, and c.link = LINK where LINK >= 0).  Beta: p0 = phi, y = logit of the observation.
 __device__ __forceinline__ double beta_cost_value(const CostP &c, double y, double f) {
 #pragma clang fp contract(off)
   if (c.link == PLS_LINK_SIGMOID) return beta_logit_value(c.p0, c.mm_l1, y, f);  // (in f: no clip)
@@ -328,11 +388,13 @@ __device__ __forceinline__ double beta_cost_deriv(const CostP &c, double y, doub
 template <int COST>
 __device__ __forceinline__ double cost_value_of(const CostP &c, double y, double f) {
   if constexpr (COST == PLS_COST_BETA) return beta_cost_value(c, y, f);
+  else if constexpr (COST == PLS_COST_ORDINAL) return ordinal_value(c, y, f);
   else return cost_value(c, y, f);
 }
 template <int COST>
 __device__ __forceinline__ double cost_deriv_of(const CostP &c, double y, double f) {
   if constexpr (COST == PLS_COST_BETA) return beta_cost_deriv(c, y, f);
+  else if constexpr (COST == PLS_COST_ORDINAL) return ordinal_deriv(c, y, f);
   else return cost_deriv(c, y, f);
 }
 

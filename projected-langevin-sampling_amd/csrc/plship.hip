@@ -710,7 +710,9 @@ __global__ __launch_bounds__(256) void cost_deriv_kernel(CostP cp, const double 
   if (col >= j) return;
   for (int64_t row = blockIdx.y; row < n; row += gridDim.y) {
     const double yv = y[row], f = F[row * ldf + col];
-    G[row * ldg + col] = (cp.cost == PLS_COST_BETA) ? beta_cost_deriv(cp, yv, f) : cost_deriv(cp, yv, f);
+    G[row * ldg + col] = (cp.cost == PLS_COST_BETA)      ? beta_cost_deriv(cp, yv, f)
+                         : (cp.cost == PLS_COST_ORDINAL) ? ordinal_deriv(cp, yv, f)
+                                                         : cost_deriv(cp, yv, f);
   }
 }
 
@@ -729,7 +731,9 @@ __global__ __launch_bounds__(256) void cost_value_partial_kernel(CostP cp, const
       const int64_t row = r0 + rr;
       if (row < n) {
         const double yv = y[row], f = F[row * ldf + col];
-        s += (cp.cost == PLS_COST_BETA) ? beta_cost_value(cp, yv, f) : cost_value(cp, yv, f);
+        s += (cp.cost == PLS_COST_BETA)      ? beta_cost_value(cp, yv, f)
+             : (cp.cost == PLS_COST_ORDINAL) ? ordinal_value(cp, yv, f)
+                                             : cost_value(cp, yv, f);
       }
     }
   }
@@ -1604,7 +1608,8 @@ static int launch_langevin_update(double *out, int64_t ldo, int add_u, const dou
 // ---------------------------------------------------------------------------------------------------------------
 static int validate_cost(const pls_cost_desc *c) {
   PLS_REQUIRE(c != nullptr, "cost descriptor is NULL");
-  PLS_REQUIRE((c->cost >= PLS_COST_GAUSSIAN && c->cost <= PLS_COST_NEGATIVE_BINOMIAL) || c->cost == PLS_COST_BETA,
+  PLS_REQUIRE((c->cost >= PLS_COST_GAUSSIAN && c->cost <= PLS_COST_NEGATIVE_BINOMIAL) || c->cost == PLS_COST_BETA ||
+                  c->cost == PLS_COST_ORDINAL,
               "unknown cost kind %d", c->cost);
   PLS_REQUIRE(c->link >= PLS_LINK_IDENTITY && c->link <= PLS_LINK_EXP, "unknown link kind %d", c->link);
   PLS_REQUIRE(c->deriv_mode == PLS_DERIV_REFERENCE || c->deriv_mode == PLS_DERIV_AUTOGRAD, "unknown deriv_mode %d",
@@ -1617,6 +1622,19 @@ static int validate_cost(const pls_cost_desc *c) {
   if (c->cost == PLS_COST_NEGATIVE_BINOMIAL)
     PLS_REQUIRE(c->p[0] > 0.0 && std::isfinite(c->p[0]), "negative-binomial cost needs a finite dispersion > 0");
   if (c->cost == PLS_COST_BETA) PLS_REQUIRE(c->p[0] > 0.0 && std::isfinite(c->p[0]), "beta cost needs a finite precision > 0");
+  if (c->cost == PLS_COST_ORDINAL) {  // p[0 .. 3]: ascending cutpoints, +inf for the unused trailing ones
+    PLS_REQUIRE(c->link == PLS_LINK_IDENTITY, "ordinal cost needs the identity link (cumulative logit), got link kind %d", c->link);
+    for (int i = 0; i < 4; ++i) PLS_REQUIRE(!std::isnan(c->p[i]), "ordinal cost: cutpoint p[%d] is NaN", i);
+    PLS_REQUIRE(std::isfinite(c->p[0]), "ordinal cost needs a finite first cutpoint p[0]");
+    for (int i = 1; i < 4; ++i) {
+      if (std::isfinite(c->p[i])) {
+        PLS_REQUIRE(std::isfinite(c->p[i - 1]), "ordinal cost: finite cutpoint p[%d] after an infinite one", i);
+        PLS_REQUIRE(c->p[i] > c->p[i - 1], "ordinal cost needs strictly increasing cutpoints, p[%d] <= p[%d]", i, i - 1);
+      } else {
+        PLS_REQUIRE(c->p[i] > 0.0, "ordinal cost: an unused cutpoint is +inf, p[%d] is -inf", i);
+      }
+    }
+  }
   return PLS_OK;
 }
 

@@ -20,6 +20,8 @@ def _point(prediction) -> torch.Tensor:
         return prediction.loc
     if isinstance(prediction, (torch.distributions.NegativeBinomial, torch.distributions.Beta)):  # (not in the reference)
         return prediction.mean
+    if isinstance(prediction, torch.distributions.Categorical):  # (not in the reference) the expected category index
+        return prediction.probs @ torch.arange(prediction.probs.shape[-1], dtype=prediction.probs.dtype, device=prediction.probs.device)
     if isinstance(prediction, ConformalPrediction):
         return prediction.mean
     raise ValueError(f"Prediction type {type(prediction)} not supported")
@@ -50,6 +52,8 @@ def calculate_nll(prediction, y: torch.Tensor) -> float:
         return prediction.log_prob(y.to(prediction.loc)).mean().item()  # metrics.py:98-99 (sign as in the reference)
     if isinstance(prediction, (torch.distributions.NegativeBinomial, torch.distributions.Beta)):  # (not in the reference)
         return -prediction.log_prob(y.to(prediction.mean)).mean().item()
+    if isinstance(prediction, torch.distributions.Categorical):  # (not in the reference)
+        return -prediction.log_prob(y.to(device=prediction.probs.device, dtype=torch.long)).mean().item()
     if isinstance(prediction, ConformalPrediction):
         # metrics.py:100-117: half the width of the 2/3 interval as the standard deviation of a normal around the median
         assert prediction.coverage == 2 / 3, f"NLL calculation needs 2/3 coverage, got {prediction.coverage=}"

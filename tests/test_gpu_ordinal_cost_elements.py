@@ -1,0 +1,125 @@
+"""GPU: the element-wise entries for the ordinal cost -- pls_cost_derivative (both derivative modes, which must be the same
+bits) and pls_cost_value -- against the per-element mpmath truth of tests/ordinal_cost_truth.py on its whole grid, dense and
+strided: bulk, both sides of every cutpoint, the root of an interior label where the derivative cancels, both tails, the far
+columns where the value is linear or underflows gradually, +-0 and subnormals.  And what the header states for a y that is
+not a category index (NaN) and for a label past the last category (+inf and -1).
+
+The bound is tests/test_gpu_cost_elements.py's, unchanged: per (parameter set, kind, regime) the larger of 4x the host
+restatement's recorded error (tests/golden/ordinal_cost_reference_errors.json) and 4 units; IEEE specials must match exactly.
+PLS_COST_TRUTH_DUMP=<file> appends the measured maxima as JSON lines (the rows of DESIGN.md section 3 are made from them)."""
+import json
+import math
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import ordinal_cost_truth as CT
+from test_gpu_parity import P, _f64_default  # noqa: F401  (fixtures)
+
+pytestmark = pytest.mark.gpu
+
+
+def _dump(record):
+    path = os.environ.get("PLS_COST_TRUTH_DUMP")
+    if path:
+        with open(path, "a") as fh:
+            fh.write(json.dumps(record) + "\n")
+
+
+def gpu_eval(P, pair, pset, kind, strided=False):
+    """the library on the grid, per element (N, J); ``strided``: the samples are the left columns of a wider matrix"""
+    y, f, _ = CT.grid(pair, pset)
+    yt, ft = torch.as_tensor(y), torch.as_tensor(f).cuda()
+    if strided:
+        wide = torch.full((f.shape[0], f.shape[1] + 3), float("nan"), device="cuda")
+        wide[:, :f.shape[1]] = ft
+        ft = wide[:, :f.shape[1]]
+    if kind == "value":  # the entry sums over rows: one row at a time
+        rows = [CT.gpu_cost(P, pair, pset, yt[a:a + 1]).calculate_cost(ft[a:a + 1]) for a in range(len(y))]
+        return torch.stack(rows).cpu().numpy()
+    return CT.gpu_cost(P, pair, pset, yt).calculate_cost_derivative(ft, force_autograd=kind == "deriv_autograd").cpu().numpy()
+
+
+@pytest.mark.parametrize("pair,pset", CT.cells())
+def test_elements_against_truth(P, pair, pset):
+    rec = CT.reference_errors()[pair][pset]
+    regimes = CT.grid(pair, pset)[2]
+    missed = []
+    for strided in (False, True):
+        got = {kind: gpu_eval(P, pair, pset, kind, strided) for kind in CT.KINDS}
+        assert np.array_equal(got["deriv_reference"], got["deriv_autograd"], equal_nan=True), "the two derivative modes differ"
+        assert (np.abs(got["deriv_reference"]) <= 1).all(), "the derivative leaves [-1, 1]"
+        for kind in CT.KINDS:
+            err = CT.by_regime(CT.errors(got[kind], CT.truth(pair, pset, kind)), regimes)
+            for regime, v in err.items():
+                bound = CT.bound(rec[kind][regime])
+                print(f"{pair} {pset} {kind:16s} {regime:10s} gpu {v:10.3g}  host {rec[kind][regime]!s:>10}  bound {bound:.3g}")
+                if not strided:
+                    _dump({"pair": pair, "pset": pset, "kind": kind, "regime": regime, "gpu": v if math.isfinite(v) else "inf",
+                           "oracle": rec[kind][regime]})
+                if not v <= bound:
+                    missed.append((kind, regime, "strided" if strided else "dense", v, bound))
+    assert not missed, f"{pair} {pset}: cells over their bound (kind, regime, layout, error, bound): {missed}"
+
+
+@pytest.mark.parametrize("pair,pset", CT.cells())
+def test_value_column_sums(P, pair, pset):
+    """calculate_cost on the whole matrix: the sum over rows against fsum of the truth, at the cells' bounds plus the N
+    roundings of the sum"""
+    y, f, regimes = CT.grid(pair, pset)
+    rec = CT.reference_errors()[pair][pset]["value"]
+    tr = CT.truth(pair, pset, "value")
+    got = CT.gpu_cost(P, pair, pset, torch.as_tensor(y)).calculate_cost(torch.as_tensor(f).cuda()).cpu().numpy()
+    n = len(y)
+    for b, regime in enumerate(regimes):
+        hi = tr["hi"][:, b]
+        assert np.isfinite(hi).all()
+        want = math.fsum(hi) + math.fsum(tr["lo"][:, b])
+        tol = CT.bound(rec[regime]) * float(tr["unit"][:, b].sum()) + n * 2.0 ** -53 * float(np.abs(hi).sum())
+        assert abs(got[b] - want) <= tol, (pair, pset, regime, b, got[b], want, abs(got[b] - want) / tol)
+
+
+def _raw(P, pset, labels):
+    """the cost on labels its constructor would refuse: they are handed to the library as they are"""
+    cost = CT.gpu_cost(P, "ordinal/identity", pset, torch.zeros(len(labels), dtype=torch.float64))
+    cost.y_train = torch.tensor(labels, dtype=torch.float64)
+    return cost
+
+
+@pytest.mark.parametrize("pset", list(CT.PARAMS))
+def test_a_y_that_is_no_category_index_gives_nan(P, pset):
+    """one row each of y = 2.5, -1, 5 and NaN (and a valid row between them, which keeps its values)"""
+    f = torch.tensor([[-40.0, -1.0, -0.0, 0.3, 2.0, 700.0, 1e300]], dtype=torch.float64).repeat(5, 1).cuda()
+    labels = [2.5, -1.0, 1.0, 5.0, math.nan]
+    g = _raw(P, pset, labels).calculate_cost_derivative(f).cpu()
+    g_auto = _raw(P, pset, labels).calculate_cost_derivative(f, force_autograd=True).cpu()
+    assert np.array_equal(g.numpy(), g_auto.numpy(), equal_nan=True), "the two derivative modes differ"
+    assert torch.isnan(g[[0, 1, 3, 4]]).all() and torch.isfinite(g[2]).all()
+    assert torch.equal(g[2], CT.gpu_cost(P, "ordinal/identity", pset, torch.ones(1)).calculate_cost_derivative(f[2:3]).cpu()[0])
+    for a, yy in enumerate(labels):
+        v = _raw(P, pset, [yy]).calculate_cost(f[a:a + 1]).cpu()
+        assert torch.isnan(v).all() if a != 2 else torch.isfinite(v).all(), (yy, v)
+    assert torch.isnan(_raw(P, pset, labels).calculate_cost(f).cpu()).all()  # (a NaN row poisons every column sum)
+
+
+def test_a_label_past_the_last_category_gives_inf_and_minus_one(P):
+    """set b has three categories: the lower cutpoint of labels 3 and 4 is +inf -- value +inf, derivative -1, whatever f"""
+    f = torch.tensor([[-1e300, -40.0, -0.0, 0.3, 700.0, 1e300]], dtype=torch.float64).repeat(2, 1).cuda()
+    cost = _raw(P, "b", [3.0, 4.0])
+    assert (cost.calculate_cost_derivative(f).cpu() == -1).all()
+    assert (cost.calculate_cost(f).cpu() == math.inf).all()
+
+
+def test_edge_terms_are_exactly_zero_and_the_ends_exact(P):
+    """the bottom category's lower and the top category's upper term are exactly 0: far on its own side an edge label costs
+    exactly 0 with derivative 0, and far on the other side exactly |f - b| with derivative +-1"""
+    f = torch.tensor([[-1e300, -1e10, 1e10, 1e300]], dtype=torch.float64).repeat(2, 1).cuda()
+    cost = CT.gpu_cost(P, "ordinal/identity", "a", torch.tensor([0.0, 4.0], dtype=torch.float64))
+    g = cost.calculate_cost_derivative(f).cpu()
+    assert torch.equal(g, torch.tensor([[0.0, 0.0, 1.0, 1.0], [-1.0, -1.0, 0.0, 0.0]], dtype=torch.float64))
+    lo = CT.gpu_cost(P, "ordinal/identity", "a", torch.zeros(1)).calculate_cost(f[:1]).cpu()
+    hi = CT.gpu_cost(P, "ordinal/identity", "a", torch.full((1,), 4.0)).calculate_cost(f[1:]).cpu()
+    assert torch.equal(lo, torch.tensor([0.0, 0.0, 1e10 + 1.5, 1e300], dtype=torch.float64))
+    assert torch.equal(hi, torch.tensor([1e300, 1e10 + 2.0, 0.0, 0.0], dtype=torch.float64))
