@@ -23,6 +23,10 @@ from .kernel import _dev
 from .projected_langevin_sampling import PLS
 
 
+# the cost parameters that travel with the particles: (key in the file = attribute of the cost, the form it is stored in)
+COST_PARAMETERS = (("dispersion", float), ("precision", float), ("cutpoints", lambda c: [float(x) for x in c]))
+
+
 def _basis_fingerprint(pls) -> Optional[dict]:
     fn = getattr(getattr(pls, "basis", None), "spectrum_fingerprint", None)
     return fn() if callable(fn) else None
@@ -43,15 +47,10 @@ def save_pls(pls: PLS, particles: torch.Tensor, model_path: str, best_lr: Option
         state["noise_step"] = int(noise_step)
     if number_of_particles is not None:
         state["number_of_particles"] = int(number_of_particles)
-    dispersion = getattr(getattr(pls, "cost", None), "dispersion", None)
-    if dispersion is not None:
-        state["dispersion"] = float(dispersion)
-    precision = getattr(getattr(pls, "cost", None), "precision", None)
-    if precision is not None:
-        state["precision"] = float(precision)
-    cutpoints = getattr(getattr(pls, "cost", None), "cutpoints", None)
-    if cutpoints is not None:
-        state["cutpoints"] = [float(c) for c in cutpoints]
+    for key, convert in COST_PARAMETERS:
+        value = getattr(getattr(pls, "cost", None), key, None)
+        if value is not None:
+            state[key] = convert(value)
     fingerprint = _basis_fingerprint(pls)
     if fingerprint is not None:
         state["spectrum_fingerprint"] = fingerprint
@@ -79,12 +78,9 @@ def load_pls(pls: PLS, model_path: str, on_gauge_mismatch: str = "raise") -> Tup
             warnings.warn(message)
     particles = _dev(model_config["particles"])
     pls.observation_noise = model_config["observation_noise"]
-    if "dispersion" in model_config and hasattr(getattr(pls, "cost", None), "dispersion"):
-        pls.cost.dispersion = float(model_config["dispersion"])
-    if "precision" in model_config and hasattr(getattr(pls, "cost", None), "precision"):
-        pls.cost.precision = float(model_config["precision"])
-    if "cutpoints" in model_config and hasattr(getattr(pls, "cost", None), "cutpoints"):
-        pls.cost.cutpoints = [float(c) for c in model_config["cutpoints"]]
+    for key, convert in COST_PARAMETERS:
+        if key in model_config and hasattr(getattr(pls, "cost", None), key):
+            setattr(pls.cost, key, convert(model_config[key]))
     print(f"Loaded particles and observation_noise from {model_path=}.")
     best_lr = model_config.get("best_lr")
     number_of_epochs = model_config.get("number_of_epochs")

@@ -46,6 +46,15 @@ PARAMS = {"a": 0.3, "b": 400.0, "c": 3.0}  # both shapes below 1; Stirling range
 JITTER = 1e-10
 U = T.U
 HUGE = 1e6  # |f| beyond which exp(-|f|) is stated (0), not computed
+# The selector problems of tests/step_fixtures.py (their ``y`` holds the logits z, the library's second argument): carrier
+# values F = c_n V_j with |c_n| <= 8 and a jiggle of up to 1 + 2^-4.  The probe rows must neither overflow nor land between
+# 2^-1000 and 0 after the scaling by eta 2^p >= 2^-23 (SelectorProblem.expected):
+#   beta/sigmoid: |G| <= 1 + phi |z| / 4, and G -> +-1 in the tails: any finite F will do; |f| <= 1e30 keeps F itself finite
+#   beta/probit: G = phi (psi(a) - psi(b) - z) slope with slope ~ e^(-F^2 / 2) inside the clip and exactly 0 outside it
+#     (|F| > 6.36): every F is fine
+SELECTOR_RANGE = {"beta/sigmoid": lambda a: a <= 1e30, "beta/probit": lambda a: a <= 1e30}
+OWN_CARRIER_STREAM = True  # the carrier values and logits come from a generator of their own (seed + 4242)
+MODES_AGREE = True  # both derivative modes are the same bits, through the same instantiation
 Y_ROWS = [0.5, 0.01, 0.999, 1.0 / 3.0, 1e-9, 1.0 - 2.0 ** -30, 0.2]
 PSI_ROOT = mp.findroot(mp.digamma, 1.46)
 SPECIALS = {"lgamma": 4, "digamma": 5, "xdigamma": 6}  # name: op of pls_debug_math
@@ -191,6 +200,10 @@ bound = T.bound  # the project's rule, unchanged: the larger of 4x the recorded 
 
 def cells():
     return [(pair, pset) for pair in PAIRS for pset in PARAMS]
+
+
+def applies(pair, kind):
+    return True
 
 
 # ---- the special functions ------------------------------------------------------------------------------------------------------

@@ -50,6 +50,12 @@ BERNOULLI_CANCEL = {"lo_tail", "hi_tail", "clip_lo", "clip_hi", "clipped", "over
 CLIP_MARGIN = 2.0 ** -44
 ORACLE_MISS = 1e6  # units beyond which a recorded oracle error is a miss of the oracle, not a rounding
 U = mp.mpf(2) ** -53
+# What the selector problems of tests/step_fixtures.py take from a family (every truth module states these three):
+# |f| of the grid values that may carry a selector problem (on top of finite and >= 1e-30): here any up to 1e30, whose
+# products with |c_n| <= 8 stay finite
+SELECTOR_RANGE = {pair: (lambda a: a <= 1e30) for pair in PAIRS}
+OWN_CARRIER_STREAM = False  # the carrier values and labels come from the problem's one generator, with everything else
+MODES_AGREE = False  # the two derivative modes are different formulas (Bernoulli/sigmoid: closed form against autograd)
 
 
 def unit_kind(pair, kind, regime):
@@ -348,7 +354,7 @@ def _make(costs, links, pair, pset, y):
     return costs[4](*prm["multimodal"], y, lk)
 
 
-def oracle_cost(pair, pset, y):
+def host_cost(pair, pset, y):
     return _make((O.GaussianCost, O.PoissonCost, O.BernoulliCost, O.StudentTCost, O.MultiModalCost),
                  (O.IdentityLink, O.SquareLink, O.SigmoidLink, O.ProbitLink), pair, pset, y)
 
@@ -367,11 +373,11 @@ def oracle_eval(pair, pset, kind):
     torch.set_default_dtype(torch.float64)
     try:
         if kind == "link":
-            return oracle_cost(pair, pset, yt).link_function(ft).numpy()
+            return host_cost(pair, pset, yt).link_function(ft).numpy()
         if kind == "value":  # the cost sums over rows: one row at a time
-            rows = [oracle_cost(pair, pset, yt[a:a + 1]).calculate_cost(ft[a:a + 1]).reshape(-1) for a in range(len(y))]
+            rows = [host_cost(pair, pset, yt[a:a + 1]).calculate_cost(ft[a:a + 1]).reshape(-1) for a in range(len(y))]
             return torch.stack(rows).numpy()
-        return oracle_cost(pair, pset, yt).calculate_cost_derivative(ft, force_autograd=kind == "deriv_autograd").numpy()
+        return host_cost(pair, pset, yt).calculate_cost_derivative(ft, force_autograd=kind == "deriv_autograd").numpy()
     finally:
         torch.set_default_dtype(prev)
 
@@ -396,7 +402,7 @@ def cells():
 
 
 # ---- the recorded oracle errors and the bound they set ------------------------------------------------------------------------
-def oracle_errors():
+def reference_errors():
     import json
     import os
 

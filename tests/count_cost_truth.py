@@ -42,6 +42,15 @@ KINDS = T.KINDS
 PARAMS = {"a": {"negative_binomial": (0.7,), "gaussian": (0.3,)}, "b": {"negative_binomial": (50.0,), "gaussian": (2.5,)}}
 U = T.U
 HUGE = 1e6  # |x| beyond which e^x is stated (inf / 0), not computed
+# The selector problems of tests/step_fixtures.py: carrier values F = c_n V_j with |c_n| <= 8 and a jiggle of up to 1 + 2^-4.
+# The probe rows must neither overflow nor land between 2^-1000 and 0 after the scaling by eta 2^p >= 2^-23
+# (SelectorProblem.expected):
+#   negative binomial/exp: G lies in [-y, r]; for y = 0 it is r sigma(t) ~ e^F, fine down to F = -640 (e^-640 = 2^-923) and
+#     exactly 0 from F = -1e9 on, so |f| <= 75 or |f| >= 1e9 (the grid's +-1e10: value and derivative in their linear ends)
+#   Gaussian/exp: G = (e^F - y) e^F / sigma2 ~ e^2F must stay finite and above 2^-970: |F| <= 255, |f| <= 30
+SELECTOR_RANGE = {"negative_binomial/exp": lambda a: (a <= 75) | ((a >= 1e9) & (a <= 1e30)), "gaussian/exp": lambda a: a <= 30}
+OWN_CARRIER_STREAM = True  # the carrier values and labels come from a generator of their own (seed + 4242)
+MODES_AGREE = True  # both derivative modes are the same bits, through the same instantiation
 
 
 def unit_kind(pair, kind, regime):

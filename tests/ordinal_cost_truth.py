@@ -44,6 +44,15 @@ PARAMS = {"a": (-1.5, -0.25, 0.5, 2.0), "b": (-0.001, 0.002, INF, INF)}
 U = T.U
 HUGE = 1e6  # |x| beyond which e^x is stated (0), not computed
 CANCEL_REGIMES = ("bulk", "cut", "root", "zero")
+# The selector problems of tests/step_fixtures.py: carrier values F = c_n V_j with |c_n| <= 8 and a jiggle of up to 1 + 2^-4.
+# The probe rows must neither overflow nor land between 2^-1000 and 0 after the scaling by eta 2^p >= 2^-23
+# (SelectorProblem.expected):
+#   ordinal/identity: G lies in (-1, 1); in an edge label's own tail it is +-sigma(-|F - b|) ~ e^-|F|, fine down to
+#     |F| = 640 (e^-640 = 2^-923) and exactly 0 from |F| = 1e9 on (e^-|F| underflows from 745), so |f| <= 75 or |f| >= 1e9
+#     (the grid's +-1e10: value and derivative in their linear ends), as for the negative binomial
+SELECTOR_RANGE = {"ordinal/identity": lambda a: (a <= 75) | ((a >= 1e9) & (a <= 1e30))}
+OWN_CARRIER_STREAM = True  # the carrier values and labels come from a generator of their own (seed + 4242)
+MODES_AGREE = True  # both derivative modes are the same bits, through the same instantiation
 
 
 def categories(pset):

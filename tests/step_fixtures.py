@@ -530,19 +530,34 @@ WINO_OUTSIDE = [(496, 16384, 2048), (512, 16380, 2048), (512, 16384, 1920), (512
 # ---- selector problems: G observable bit for bit through a step, for any cost ---------------------------------------------------
 # One carrier direction k0 has A[k0, n] = c_n (signed powers of two, 2^-3 .. 2^3) and U[k0, j] = V_j (any nonzero double); every
 # other row of U is zero.  So F[n, j] = c_n V_j exactly in any summation order (one product by a power of two plus zeros): F
-# is arbitrary, finite and nonzero, and runs through the regimes of tests/cost_truth.py.  Every other direction k carries one
+# is arbitrary, finite and nonzero, and runs through the regimes of the pair's truth module.  Every other direction k carries one
 # probe entry A[k, n_k] = 2^p_k and zeros, so D[k, j] = 2^p_k G[n_k, j] exactly, the prior term U[k, j] / lambda_k is zero,
 # and without noise (or with injected zeros) out[k, j] = -eta 2^p_k G[n_k, j] with eta a power of two: not one rounding after
 # cost_deriv.  A probe row of a step therefore shows G[n_k, :] bit for bit, on any route, in any tile position.
 SELECTOR_PLACEMENTS = ["head", "half", "tail", "spread"]
 
 
-def selector_values(pair, pset="a", lo=1e-30, hi=1e30):
-    """the finite nonzero f of the pair's cost_truth grid (|f| in [lo, hi]): the regimes the carrier values run through"""
+def truth_module(pair):
+    """The truth module that describes the pair's family (a pair name occurs in one of them only): its grid, mpmath truth,
+    recorded errors and bound, host and library cost, and what the selector problems take from it (SELECTOR_RANGE,
+    OWN_CARRIER_STREAM, MODES_AGREE)."""
+    import beta_cost_truth
     import cost_truth
+    import count_cost_truth
+    import ordinal_cost_truth
 
-    y, f, _ = cost_truth.grid(pair, pset)
-    keep = np.isfinite(f) & (np.abs(f) >= lo) & (np.abs(f) <= hi)
+    for module in (cost_truth, count_cost_truth, beta_cost_truth, ordinal_cost_truth):
+        if pair in module.PAIRS:
+            return module
+    raise KeyError(f"no truth module describes the pair {pair}")
+
+
+def selector_values(pair, pset="a"):
+    """the finite f of the pair's truth grid with |f| >= 1e-30 and inside the family's SELECTOR_RANGE: the regimes the
+    carrier values run through; and the grid's labels"""
+    y, f, _ = truth_module(pair).grid(pair, pset)
+    a = np.abs(f)
+    keep = np.isfinite(f) & (a >= 1e-30) & truth_module(pair).SELECTOR_RANGE[pair](a)
     return np.unique(f[keep]), y
 
 
@@ -556,16 +571,30 @@ class SelectorProblem:
         self.pair, self.pset, self.mk, self.n, self.j, self.placement = pair, pset, mk, n, j, placement
         self.k0 = k0 = (mk // 3 if k0 is None else k0)
         vals, ys = selector_values(pair, pset)
-        # V_j: the grid's values (every regime), each also scaled by a full-mantissa factor near one, and plain normals
-        pick = torch.as_tensor(vals)[torch.randint(0, len(vals), (j,), generator=g)]
-        jiggle = 1 + (torch.rand(j, generator=g, dtype=torch.float64) - 0.5) * 2.0 ** -3
-        third = torch.arange(j) % 3
-        self.v = torch.where(third == 0, pick, torch.where(third == 1, pick * jiggle, 1.5 * torch.randn(j, generator=g, dtype=torch.float64)))
-        self.v[self.v == 0] = 0.75
+
+        def carrier_values(g):
+            """V_j: the grid's values (every regime), each also scaled by a full-mantissa factor near one, and plain normals"""
+            pick = torch.as_tensor(vals)[torch.randint(0, len(vals), (j,), generator=g)]
+            jiggle = 1 + (torch.rand(j, generator=g, dtype=torch.float64) - 0.5) * 2.0 ** -3
+            third = torch.arange(j) % 3
+            v = torch.where(third == 0, pick, torch.where(third == 1, pick * jiggle, 1.5 * torch.randn(j, generator=g, dtype=torch.float64)))
+            v[v == 0] = 0.75
+            return v
+
+        def labels(g):
+            return torch.as_tensor(ys)[torch.randint(0, len(ys), (n,), generator=g)]
+
+        self.v = carrier_values(g)
         self.c = (2.0 ** torch.randint(-3, 4, (n,), generator=g).double()) * (1 - 2 * torch.randint(0, 2, (n,), generator=g).double())
         self.c[torch.arange(n) % 3 == 0] = 1.0  # a third of the rows see the carrier values themselves
-        self.y = torch.as_tensor(ys)[torch.randint(0, len(ys), (n,), generator=g)]
+        self.y = labels(g)
         self.lam = 2.0 ** torch.randint(-2, 4, (mk,), generator=g, dtype=torch.int64).double()
+        if truth_module(pair).OWN_CARRIER_STREAM:
+            # the family's carrier values and labels come from a generator of their own; the draws above still advance the
+            # problem's generator, so that everything else of the construction is what it is for any other family
+            own = torch.Generator().manual_seed(seed + 4242)
+            self.v = carrier_values(own)
+            self.y = labels(own)
         others = [k for k in range(mk) if k != k0]
         nprobe = min(len(others), n)
         if placement == "head":
@@ -624,9 +653,7 @@ class SelectorProblem:
         return self.c[:, None] * v[None, :]
 
     def cost(self, P, force_autograd=False):
-        import cost_truth
-
-        cost = cost_truth.gpu_cost(P, self.pair, self.pset, self.y)
+        cost = truth_module(self.pair).gpu_cost(P, self.pair, self.pset, self.y)
         if force_autograd:  # the step takes the derivative mode from the cost's descriptor
             plain = cost.desc
             cost.desc = lambda force_autograd=False: plain(force_autograd=True)
@@ -647,10 +674,8 @@ class SelectorProblem:
         the carrier row may differ by the two formulas' roundings, sum_n |c_n| 2^-52 (|F| + |y|) / sigma2 per unit eta."""
         from fractions import Fraction
 
-        import cost_truth
-
         assert self.pair == "gaussian/identity"
-        ip0 = 1.0 / cost_truth.PARAMS[self.pset]["gaussian"][0]
+        ip0 = 1.0 / truth_module(self.pair).PARAMS[self.pset]["gaussian"][0]
         f = self.f(cols)
         rows = self.probe_n if rows is None else rows
         g = g.clone()
@@ -665,13 +690,11 @@ class SelectorProblem:
         """cost(y_n, F[n, j]) per element through the element-wise entry pls_cost_value (which sums over rows: the rows of one
         label go in as a single row, every element a column of its own; tests/test_gpu_cost_elements.py holds the entry to
         the truth)"""
-        import cost_truth
-
         f = self.f(cols)
         out = torch.empty_like(f)
         for yy in torch.unique(self.y).tolist():
             rows = (self.y == yy).nonzero().flatten()
-            cost = cost_truth.gpu_cost(P, self.pair, self.pset, torch.tensor([yy], dtype=torch.float64))
+            cost = truth_module(self.pair).gpu_cost(P, self.pair, self.pset, torch.tensor([yy], dtype=torch.float64))
             out[rows] = cost.calculate_cost(f[rows].reshape(1, -1).cuda()).cpu().reshape(len(rows), -1)
         return out
 
@@ -680,8 +703,6 @@ class SelectorProblem:
         summation order (cost_value is evaluated without contraction, so every route forms the same element values).
         ``gauss_fma``: the Gaussian/identity GEMM epilogues form the value as G^2 sigma2 / 2 from G = fma(F, 1 / sigma2,
         -(1 / sigma2) y), which differs from (F - y)^2 / (2 sigma2) by 2^-52 |F - y| (|F| + |y|) / sigma2 per element."""
-        import cost_truth
-
         cols = torch.arange(self.j) if cols is None else torch.as_tensor(cols)
         v = self.values_direct(P, cols)
         assert torch.isfinite(v).all()
@@ -690,7 +711,7 @@ class SelectorProblem:
         tol = (self.n + 2) * 2.0 ** -53 * (v.abs().sum(0) + prior) + 2.0 ** -52 * want.abs()
         if gauss_fma:
             f = self.f(cols)
-            s2 = cost_truth.PARAMS[self.pset]["gaussian"][0]
+            s2 = truth_module(self.pair).PARAMS[self.pset]["gaussian"][0]
             tol = tol + 2.0 ** -51 * ((f - self.y[:, None]).abs() * (f.abs() + self.y.abs()[:, None])).sum(0) / s2
         return want, tol
 
@@ -725,16 +746,18 @@ class SelectorProblem:
 
     def energy_truth(self, cols):
         """per column: the sum of the mpmath cost values plus the exact prior V_j^2 / (2 lambda_k0), sum_n |cost_n|, and
-        the sum of the elements' error units (the larger of an ulp of the value and cost_truth's cancel unit)"""
-        import cost_truth
+        the sum of the elements' error units (the larger of an ulp of the value and the truth module's cancel unit; where
+        that is a tuple -- the count family's also carries a unit for a subnormal link value -- its first member)"""
         import mpmath as mp
 
+        point_truth = truth_module(self.pair).point_truth
         f = self.f(cols)
         want, mag, units = [], [], []
         for b, col in enumerate(torch.as_tensor(cols).tolist()):
             tot, ab, un = mp.mpf(0), mp.mpf(0), mp.mpf(0)
             for a in range(self.n):
-                t, cu = cost_truth.point_truth(self.pair, self.pset, "value", float(self.y[a]), float(f[a, b]))
+                t, cu = point_truth(self.pair, self.pset, "value", float(self.y[a]), float(f[a, b]))
+                cu = cu[0] if isinstance(cu, tuple) else cu
                 tot, ab, un = tot + t, ab + abs(t), un + max(cu, abs(t) * mp.mpf(2) ** -52)
             want.append(float(tot + mp.mpf(self.prior_energy(col))))
             mag.append(float(ab))

@@ -116,7 +116,7 @@ def test_oracle_against_truth_matches_the_recorded_errors():
     """A fresh run of the oracle on the grid against the file.  torch's vectorised exp / log / erf differ by an ulp between
     CPU generations, so a cell may move: fresh and recorded must agree within a factor of two plus one unit, and the same
     cells must be the ones the oracle misses outright."""
-    fresh, rec = T.measure_oracle(), T.oracle_errors()
+    fresh, rec = T.measure_oracle(), T.reference_errors()
     assert {(p, s) for p in rec for s in rec[p]} == set(T.cells())
     for pair, pset in T.cells():
         assert set(fresh[pair][pset]) == set(rec[pair][pset]) == {k for k in T.KINDS if T.applies(pair, k)}
@@ -136,31 +136,38 @@ def test_oracle_against_truth_matches_the_recorded_errors():
 
 def test_bound_rule():
     assert T.bound(0.3) == 4 and T.bound(35.0) == 140 and T.bound("inf") == 4 and T.bound(5.6e15) == 4
-    rec = T.oracle_errors()
+    rec = T.reference_errors()
     assert all(T.bound(v) <= 4e4 for p in rec for s in rec[p] for k in rec[p][s] for v in rec[p][s][k].values())
 
 
 # ---- the selector problems of tests/step_fixtures.py: their exactness, proved on the host ---------------------------------------
-@pytest.mark.parametrize("pair", T.PAIRS)
-@pytest.mark.parametrize("mk,n,j,placement", [(10, 100, 64, "head"), (17, 333, 37, "spread"), (120, 1530, 200, "tail"),
-                                              (129, 1200, 110, "half"), (12, 40, 5, "spread"), (200, 90, 33, "head")])
-def test_selector_problem_shows_g_bit_for_bit(pair, mk, n, j, placement):
-    """The fixture's own checks (F exact in either summation order, one power-of-two entry per probe direction), and the
-    construction's claim on the host: with G the oracle's derivative on F, the step written out in fp64 torch, in two
-    summation orders, shows -eta 2^p G[n_k, :] on every probe row without a rounding, and the carrier row within its
-    bound."""
+# the pairs of the other three truth modules (count, Beta, ordinal), each with its parameter sets "a" and "b"
+FAMILY_CELLS = [(pair, pset) for pair in ("negative_binomial/exp", "gaussian/exp", "beta/sigmoid", "beta/probit", "ordinal/identity")
+                for pset in "ab"]
+
+
+def _host_g(ex):
+    """G on the problem's F by the host cost of the pair's truth module (the oracle's, or the family's restatement)"""
+    import torch
+
+    from step_fixtures import truth_module
+
+    prev = torch.get_default_dtype()
+    torch.set_default_dtype(torch.float64)
+    try:
+        return truth_module(ex.pair).host_cost(ex.pair, ex.pset, ex.y).calculate_cost_derivative(ex.f())
+    finally:
+        torch.set_default_dtype(prev)
+
+
+def _selector_problem_shows_g(pair, pset, mk, n, j, placement):
     import torch
 
     from step_fixtures import BLOCK_ETAS, EXACT_ETA, SelectorProblem, assert_selector
 
-    ex = SelectorProblem(pair, mk, n, j, placement, seed=mk + n)
+    ex = SelectorProblem(pair, mk, n, j, placement, seed=mk + n, pset=pset)
     assert len(ex.probe_k) == min(mk - 1, n) or placement == "spread"
-    prev = torch.get_default_dtype()
-    torch.set_default_dtype(torch.float64)
-    try:
-        g = T.oracle_cost(pair, "a", ex.y).calculate_cost_derivative(ex.f())
-    finally:
-        torch.set_default_dtype(prev)
+    g = _host_g(ex)
     etas = torch.tensor(BLOCK_ETAS)[torch.arange(j) % 4]
     for eta in (EXACT_ETA, etas):
         e = torch.as_tensor(eta, dtype=torch.float64).expand(j)[None, :]
@@ -175,6 +182,24 @@ def test_selector_problem_shows_g_bit_for_bit(pair, mk, n, j, placement):
     bad[k, col] = np.nextafter(float(bad[k, col]), math.inf)
     with pytest.raises(AssertionError):
         assert_selector(ex, bad, g, what="mutant")
+
+
+@pytest.mark.parametrize("pair", T.PAIRS)
+@pytest.mark.parametrize("mk,n,j,placement", [(10, 100, 64, "head"), (17, 333, 37, "spread"), (120, 1530, 200, "tail"),
+                                              (129, 1200, 110, "half"), (12, 40, 5, "spread"), (200, 90, 33, "head")])
+def test_selector_problem_shows_g_bit_for_bit(pair, mk, n, j, placement):
+    """The fixture's own checks (F exact in either summation order, one power-of-two entry per probe direction), and the
+    construction's claim on the host: with G the oracle's derivative on F, the step written out in fp64 torch, in two
+    summation orders, shows -eta 2^p G[n_k, :] on every probe row without a rounding, and the carrier row within its
+    bound."""
+    _selector_problem_shows_g(pair, "a", mk, n, j, placement)
+
+
+@pytest.mark.parametrize("pair,pset", FAMILY_CELLS)
+@pytest.mark.parametrize("mk,n,j,placement", [(10, 100, 64, "head"), (17, 333, 37, "spread"), (120, 1530, 200, "tail"), (12, 40, 5, "spread")])
+def test_selector_problem_shows_g_bit_for_bit_in_every_family(pair, pset, mk, n, j, placement):
+    """the same proof for the pairs of the count, Beta and ordinal truth modules, with G each module's host cost's"""
+    _selector_problem_shows_g(pair, pset, mk, n, j, placement)
 
 
 def test_selector_values_run_through_the_regimes():
@@ -193,29 +218,33 @@ def test_selector_values_run_through_the_regimes():
             assert (np.abs(f) < 1e-9).any() and {0.0, 1.0, 1e6} <= set(ex.y.tolist())
 
 
-@pytest.mark.parametrize("pair", ["poisson/square", "bernoulli/probit", "multimodal/identity"])
-@pytest.mark.parametrize("m,n,j,placement", [(17, 333, 37, "tail"), (64, 1000, 100, "head"), (200, 300, 33, "half")])
-def test_selector_ipb_problem_shows_g_bit_for_bit(pair, m, n, j, placement):
-    """the inducing-point form: k(Z,Z) = diag(4^e) factorises, inverts and solves exactly, V holds the carrier values on one
-    row, and the step -- written out in fp64 torch, plain and in whitened coordinates -- shows G on its probe rows"""
+def _selector_ipb_problem_shows_g(pair, pset, m, n, j, placement):
     import torch
 
     from step_fixtures import EXACT_ETA, SelectorIpbProblem, assert_selector
 
-    ex = SelectorIpbProblem(pair, m, n, j, placement, seed=m + n)
+    ex = SelectorIpbProblem(pair, m, n, j, placement, seed=m + n, pset=pset)
     lc = torch.linalg.cholesky(ex.kzz)
     assert torch.equal(lc, torch.diag(ex.d)) and torch.equal(lc @ lc.T, ex.kzz)
     v = torch.cholesky_solve(ex.u, lc)
     assert torch.equal(ex.kzx.T @ v, ex.f()) and (v[torch.arange(m) != ex.k0] == 0).all() and torch.equal(v[ex.k0], ex.v)
-    prev = torch.get_default_dtype()
-    torch.set_default_dtype(torch.float64)
-    try:
-        g = T.oracle_cost(pair, "a", ex.y).calculate_cost_derivative(ex.f())
-    finally:
-        torch.set_default_dtype(prev)
+    g = _host_g(ex)
     step = -EXACT_ETA * (ex.kzx @ g + m * v)
     assert_selector(ex, step, g, what="host")
     assert_selector(ex, ex.u + step, g, new_state=True, what="host, new state")
     ex.whitened()
     assert_selector(ex, step / ex.d[:, None], g, what="host, whitened")
     assert_selector(ex, ex.s + step / ex.d[:, None], g, new_state=True, what="host, whitened, new state")
+
+
+@pytest.mark.parametrize("pair", ["poisson/square", "bernoulli/probit", "multimodal/identity"])
+@pytest.mark.parametrize("m,n,j,placement", [(17, 333, 37, "tail"), (64, 1000, 100, "head"), (200, 300, 33, "half")])
+def test_selector_ipb_problem_shows_g_bit_for_bit(pair, m, n, j, placement):
+    """the inducing-point form: k(Z,Z) = diag(4^e) factorises, inverts and solves exactly, V holds the carrier values on one
+    row, and the step -- written out in fp64 torch, plain and in whitened coordinates -- shows G on its probe rows"""
+    _selector_ipb_problem_shows_g(pair, "a", m, n, j, placement)
+
+
+@pytest.mark.parametrize("pair,pset", FAMILY_CELLS)
+def test_selector_ipb_problem_shows_g_bit_for_bit_in_every_family(pair, pset):
+    _selector_ipb_problem_shows_g(pair, pset, 17, 333, 37, "tail")

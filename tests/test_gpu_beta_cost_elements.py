@@ -7,60 +7,23 @@ functions themselves (pls_debug_math ops 4-6) per element against mpmath.
 The bound is tests/test_gpu_cost_elements.py's, unchanged: per cell the larger of 4x the host restatement's recorded error
 (tests/golden/beta_cost_reference_errors.json) and 4 units.  PLS_COST_TRUTH_DUMP=<file> appends the measured maxima as JSON
 lines (the rows of DESIGN.md section 3 are made from them)."""
-import json
 import math
-import os
 
 import numpy as np
 import pytest
 import torch
 
 import beta_cost_truth as BT
+import test_gpu_cost_elements as E
 from test_gpu_parity import P, _f64_default  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
 
 
-def _dump(record):
-    path = os.environ.get("PLS_COST_TRUTH_DUMP")
-    if path:
-        with open(path, "a") as fh:
-            fh.write(json.dumps(record) + "\n")
-
-
-def gpu_eval(P, pair, pset, kind, strided=False):
-    """the library on the grid, per element (N, J); ``strided``: the samples are the left columns of a wider matrix"""
-    z, f, _ = BT.grid(pair, pset)
-    zt, ft = torch.as_tensor(z), torch.as_tensor(f).cuda()
-    if strided:
-        wide = torch.full((f.shape[0], f.shape[1] + 3), float("nan"), device="cuda")
-        wide[:, :f.shape[1]] = ft
-        ft = wide[:, :f.shape[1]]
-    if kind == "value":  # the entry sums over rows: one row at a time
-        rows = [BT.gpu_cost(P, pair, pset, zt[a:a + 1]).calculate_cost(ft[a:a + 1]) for a in range(len(z))]
-        return torch.stack(rows).cpu().numpy()
-    return BT.gpu_cost(P, pair, pset, zt).calculate_cost_derivative(ft, force_autograd=kind == "deriv_autograd").cpu().numpy()
-
-
 @pytest.mark.parametrize("pair,pset", BT.cells())
 def test_elements_against_truth(P, pair, pset):
-    rec = BT.reference_errors()[pair][pset]
-    regimes = BT.grid(pair, pset)[2]
-    missed = []
-    for strided in (False, True):
-        got = {kind: gpu_eval(P, pair, pset, kind, strided) for kind in BT.KINDS}
-        assert np.array_equal(got["deriv_reference"], got["deriv_autograd"], equal_nan=True), "the two derivative modes differ"
-        for kind in BT.KINDS:
-            err = BT.by_regime(BT.errors(got[kind], BT.truth(pair, pset, kind)), regimes)
-            for regime, v in err.items():
-                bound = BT.bound(rec[kind][regime])
-                print(f"{pair} {pset} {kind:16s} {regime:10s} gpu {v:10.3g}  host {rec[kind][regime]!s:>10}  bound {bound:.3g}")
-                if not strided:
-                    _dump({"pair": pair, "pset": pset, "kind": kind, "regime": regime, "gpu": v if math.isfinite(v) else "inf",
-                           "oracle": rec[kind][regime]})
-                if not v <= bound:
-                    missed.append((kind, regime, "strided" if strided else "dense", v, bound))
-    assert not missed, f"{pair} {pset}: cells over their bound (kind, regime, layout, error, bound): {missed}"
+    got = E.elements_against_truth(P, BT, pair, pset)
+    E.modes_agree(got)
 
 
 def test_the_tails_stay_finite_and_the_drift_is_exactly_one(P):
@@ -79,18 +42,8 @@ def test_the_tails_stay_finite_and_the_drift_is_exactly_one(P):
 
 @pytest.mark.parametrize("pair,pset", BT.cells())
 def test_value_column_sums(P, pair, pset):
-    """calculate_cost on the whole matrix: the sum over rows against fsum of the truth, at the cells' bounds plus the N
-    roundings of the sum"""
-    z, f, regimes = BT.grid(pair, pset)
-    rec = BT.reference_errors()[pair][pset]["value"]
-    tr = BT.truth(pair, pset, "value")
-    got = BT.gpu_cost(P, pair, pset, torch.as_tensor(z)).calculate_cost(torch.as_tensor(f).cuda()).cpu().numpy()
-    n = len(z)
-    for b, regime in enumerate(regimes):
-        hi = tr["hi"][:, b]
-        want = math.fsum(hi) + math.fsum(tr["lo"][:, b])
-        tol = BT.bound(rec[regime]) * float(tr["unit"][:, b].sum()) + n * 2.0 ** -53 * float(np.abs(hi).sum())
-        assert abs(got[b] - want) <= tol, (pair, pset, regime, b, got[b], want, abs(got[b] - want) / tol)
+    assert np.isfinite(BT.truth(pair, pset, "value")["hi"]).all()
+    E.value_column_sums(P, BT, pair, pset)
 
 
 @pytest.mark.parametrize("name", list(BT.SPECIALS))
@@ -109,7 +62,7 @@ def test_special_functions_against_mpmath(P, name):
     for regime, v in err.items():
         bound = BT.bound(rec[regime])
         print(f"{name:9s} {regime:10s} gpu {v:10.3g}  host {rec[regime]!s:>10}  bound {bound:.3g}")
-        _dump({"pair": "special", "pset": name, "kind": "value", "regime": regime, "gpu": v if math.isfinite(v) else "inf", "oracle": rec[regime]})
+        E._dump({"pair": "special", "pset": name, "kind": "value", "regime": regime, "gpu": v if math.isfinite(v) else "inf", "oracle": rec[regime]})
         if not v <= bound:
             missed.append((regime, v, bound))
     assert not missed, f"{name}: regimes over their bound (regime, error, bound): {missed}"

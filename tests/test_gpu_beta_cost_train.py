@@ -1,9 +1,8 @@
-"""GPU: train_pls with BetaCost under the sigmoid link, on both bases: 20 iterations on the reference's host noise stream
-against oracle.pls_oracle.train_pls driven by the host restatement of tests/beta_cost_truth.py (the helper and tolerance rule
-of the small-step parity tests: test_gpu_parity.step_tolerance, TOL unless the problem itself is ill-conditioned), one launch
-per iteration, and a checkpoint saved half way and resumed bit for bit.  And one run on the in-kernel Philox stream from
-particles that put f beyond +-700, against the restatement fed the same normals (oracle/philox_ref.py), with what the bounded
-drift implies for the distance from the data-free recursion."""
+"""GPU: train_pls with BetaCost under the sigmoid link, on both bases: the loop of tests/train_loop_fixtures.py -- 20
+iterations against oracle.pls_oracle.train_pls driven by the host restatement of tests/beta_cost_truth.py, one launch per
+iteration, and a checkpoint saved half way, whose precision travels with the particles, resumed bit for bit.  And one run
+on the in-kernel Philox stream from particles that put f beyond +-700, against the restatement fed the same normals
+(oracle/philox_ref.py), with what the bounded drift implies for the distance from the data-free recursion."""
 import math
 
 import numpy as np
@@ -13,86 +12,33 @@ import torch
 import beta_cost_truth as BT
 from oracle import philox_ref
 from oracle import pls_oracle as O
-from test_gpu_parity import FUZZ_SEED, build_ipb, build_onb, cu, make_problem, relerr, step_tolerance
+from test_gpu_parity import cu, relerr, step_tolerance
 from test_gpu_parity import P, _f64_default  # noqa: F401  (fixtures)
 from test_gpu_small_step import route  # noqa: F401  (fixture)
+from train_loop_fixtures import SHAPES, problem, training_loop
 
 pytestmark = pytest.mark.gpu
 
-SHAPES = [(100, 10, 64), (1000, 32, 100)]  # (N, M, J): the count-cost shapes
 PHI = 8.0
-ITERATIONS = 20
 
 
-def _problem(P, n, m, j, base):
-    pr = make_problem(n, m, j, 2, seed=7 * n + m + FUZZ_SEED)
-    mu = torch.sigmoid(1.5 * pr["fstar"])  # proportions scattered around sigmoid(1.5 f*) with precision phi
+def _y(pr, n):
+    """proportions scattered around sigmoid(1.5 f*) with precision phi"""
+    mu = torch.sigmoid(1.5 * pr["fstar"])
     torch.manual_seed(11 + n)
-    y = torch.distributions.Beta(PHI * mu, PHI * (1 - mu)).sample().clamp(1e-6, 1 - 1e-6)
-    if base == "onb":
-        ob, gb = build_onb(P, pr)
-        mk = ob.approximation_dimension
-        u0 = 0.1 * pr["u"][:mk].contiguous()
-        eta = 0.25 * float(ob.eigenvalues.min())  # inside the stability bound of the stiffest prior mode
-    else:
-        pr["ls"] = pr["ls"] * 0.35
-        ob, gb = build_ipb(P, pr)
-        u0 = 0.1 * pr["u"]
-        eta = 0.25 * float(torch.linalg.eigvalsh(ob.base_gram_induce).min()) / m
-    gc = P.costs.BetaCost(y, P.links.SigmoidLinkFunction(), PHI)
-    oc = BT.BetaHostCost(gc.y_device().cpu(), BT.SigmoidLink(), PHI)  # (the very logits the library gets)
-    torch.manual_seed(5)
-    noises = [ob.sample_update_noise(u0) for _ in range(ITERATIONS)]  # the reference's host stream (torch's generator)
-    return ob, gb, oc, gc, u0, eta, noises
+    return torch.distributions.Beta(PHI * mu, PHI * (1 - mu)).sample().clamp(1e-6, 1 - 1e-6)
 
 
-def _per_iteration(summary):
-    """the kernels a loop launches every iteration; whatever else it launches (entering and leaving the loop's coordinates,
-    the whitened operand, the last energies) does not grow with the iterations: a handful per run"""
-    named = {k: v for k, v in summary.items() if k != "other"}
-    assert all(v["launches"] >= ITERATIONS or v["launches"] <= 4 for v in named.values()), summary
-    return {k for k, v in named.items() if v["launches"] >= ITERATIONS}
+def _costs(P, y, precision=PHI):
+    gc = P.costs.BetaCost(y, P.links.SigmoidLinkFunction(), precision)
+    return BT.BetaHostCost(gc.y_device().cpu(), BT.SigmoidLink(), precision), gc  # (the very logits the library gets)
 
 
 @pytest.mark.parametrize("base", ["onb", "ipb"])
 @pytest.mark.parametrize("n,m,j", SHAPES)
 def test_training_loop_against_the_host_restatement(P, route, tmp_path, n, m, j, base):  # noqa: F811
-    ob, gb, oc, gc, u0, eta, noises = _problem(P, n, m, j, base)
-    assert gc.is_native()
-    pls = P.pkg.PLS(gb, gc)
-    want, e_want = O.train_pls(O.PLS(ob, oc), u0.clone(), ITERATIONS, eta, 1e9, noises=[x.clone() for x in noises])
-    first = O.PLS(ob, oc).calculate_particle_update(u0.clone(), eta, noise=noises[0])
-    tol = step_tolerance(ob, oc, u0, eta, noises[0], first)
-    route(1)
-    dev_noises = [cu(x) for x in noises]
-    got, e_got = P.pkg.train_pls(pls, cu(u0).clone(), ITERATIONS, eta, 1e9, noises=dev_noises)
-    print(f"{base} {n}x{m}x{j}: particles rel err {relerr(got, want):.3e} (tol {tol:.1e}), energies "
-          f"{np.abs(np.array(e_got) / np.array(e_want) - 1).max():.3e}")
-    assert len(e_got) == len(e_want) == ITERATIONS
-    assert relerr(got, want) < tol
-    assert np.allclose(e_got, e_want, rtol=max(tol, 1e-9))
-    # one launch per iteration: the step, the energies of its input and their sums in one kernel (the inducing-point basis
-    # with injected noise solves in front of it; on its own stream of draws it runs in whitened coordinates, one launch)
-    with P.pkg._lib.Timeline(512) as tl:
-        P.pkg.train_pls(pls, cu(u0).clone(), ITERATIONS, eta, 1e9, noises=dev_noises)
-    assert _per_iteration(tl.summary()) == ({"small_rank_step"} if base == "onb" else {"small_rank_step", "ipb_prep"})
-    if base == "ipb":
-        with P.pkg._lib.Timeline(512) as tl:
-            torch.manual_seed(3)
-            P.pkg.train_pls(pls, cu(u0).clone(), ITERATIONS, eta, 1e9)
-        assert _per_iteration(tl.summary()) == {"small_rank_step"}
-    # a checkpoint half way: the precision travels with the particles, and the resumed run ends on the same bits
-    from projected_langevin_sampling_amd.checkpoint import load_pls, save_pls
-
-    half = ITERATIONS // 2
-    mid, e_mid = P.pkg.train_pls(pls, cu(u0).clone(), half, eta, 1e9, noises=dev_noises[:half])
-    path = str(tmp_path / "beta.pt")
-    save_pls(pls, mid, path, best_lr=eta, number_of_epochs=half)
-    other = P.pkg.PLS(gb, P.costs.BetaCost(gc.y_train, P.links.SigmoidLinkFunction(), 99.0))
-    other, loaded, lr, epochs = load_pls(other, path)
-    assert other.cost.precision == PHI and lr == eta and epochs == half and torch.equal(loaded, mid)
-    end, e_end = P.pkg.train_pls(other, loaded, ITERATIONS - half, eta, 1e9, noises=dev_noises[half:])
-    assert torch.equal(end, got) and np.allclose(e_mid + e_end, e_got, rtol=1e-12)
+    gc = training_loop(P, route, tmp_path, n, m, j, base, _y, _costs, "precision", 99.0)
+    assert gc.precision == PHI
 
 
 def test_philox_run_from_the_far_tails_keeps_a_bounded_drift(P, route):  # noqa: F811
@@ -105,7 +51,7 @@ def test_philox_run_from_the_far_tails_keeps_a_bounded_drift(P, route):  # noqa:
     d_(t+1) = (1 - eta / lambda) d_t - eta A G_t with 0 < eta / lambda <= 1/4, so per particle
     |d_T|_2 <= T eta |A|_2 sqrt(N) g_max -- whatever the start."""
     n, m, j, steps = 100, 10, 64, 10
-    ob, gb, oc, gc, u0, eta, _ = _problem(P, n, m, j, "onb")
+    ob, gb, oc, gc, u0, eta, _ = problem(P, n, m, j, "onb", _y, _costs)
     a = ob.scaled_eigenvectors.T @ ob.base_gram_induce_train  # (M_k, N): F = A^T U
     mk = a.shape[0]
     u0 = u0 * (2000.0 / float((a.T @ u0).abs().max()))

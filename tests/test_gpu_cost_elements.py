@@ -28,8 +28,9 @@ def _dump(record):
             fh.write(json.dumps(record) + "\n")
 
 
-def gpu_eval(P, pair, pset, kind, strided=False):
-    """the library on the grid, per element (N, J); ``strided``: the samples are the left columns of a wider matrix"""
+def gpu_eval(P, T, pair, pset, kind, strided=False):
+    """the library on the grid of the truth module ``T``, per element (N, J); ``strided``: the samples are the left columns of
+    a wider matrix"""
     y, f, _ = T.grid(pair, pset)
     yt, ft = torch.as_tensor(y), torch.as_tensor(f).cuda()
     if strided:
@@ -44,35 +45,43 @@ def gpu_eval(P, pair, pset, kind, strided=False):
     return T.gpu_cost(P, pair, pset, yt).calculate_cost_derivative(ft, force_autograd=kind == "deriv_autograd").cpu().numpy()
 
 
-@pytest.mark.parametrize("pair,pset", T.cells())
-def test_elements_against_truth(P, pair, pset):
-    rec = T.oracle_errors()[pair][pset]
+def elements_against_truth(P, T, pair, pset, reference="host"):
+    """Every kind the pair has, dense and strided, per regime within the bound its recorded reference error sets
+    (``reference``: what the printed line calls it).  Returns {(kind, strided): the library's (N, J) values}, for the asserts
+    a family adds of its own."""
+    rec = T.reference_errors()[pair][pset]
     regimes = T.grid(pair, pset)[2]
-    missed = []
+    got, missed = {}, []
     for kind in T.KINDS:
         if not T.applies(pair, kind):
             continue
         tr = T.truth(pair, pset, kind)
         for strided in (False, True):
-            got = gpu_eval(P, pair, pset, kind, strided)
-            err = T.by_regime(T.errors(got, tr), regimes)
+            got[kind, strided] = gpu_eval(P, T, pair, pset, kind, strided)
+            err = T.by_regime(T.errors(got[kind, strided], tr), regimes)
             for regime, v in err.items():
                 bound = T.bound(rec[kind][regime])
-                print(f"{pair} {pset} {kind:16s} {regime:10s} gpu {v:10.3g}  oracle {rec[kind][regime]!s:>10}  bound {bound:.3g}")
+                print(f"{pair} {pset} {kind:16s} {regime:10s} gpu {v:10.3g}  {reference} {rec[kind][regime]!s:>10}  bound {bound:.3g}")
                 if not strided:
                     _dump({"pair": pair, "pset": pset, "kind": kind, "regime": regime, "gpu": v if math.isfinite(v) else "inf",
                            "oracle": rec[kind][regime]})
                 if not v <= bound:
                     missed.append((kind, regime, "strided" if strided else "dense", v, bound))
     assert not missed, f"{pair} {pset}: cells over their bound (kind, regime, layout, error, bound): {missed}"
+    return got
 
 
-@pytest.mark.parametrize("pair,pset", T.cells())
-def test_value_column_sums(P, pair, pset):
+def modes_agree(got):
+    """for a family whose two derivative modes are one formula: the same bits, dense and strided"""
+    for strided in (False, True):
+        assert np.array_equal(got["deriv_reference", strided], got["deriv_autograd", strided], equal_nan=True), "the two derivative modes differ"
+
+
+def value_column_sums(P, T, pair, pset):
     """calculate_cost on the whole matrix (every row slot of the kernel, mixed labels within a register's rows): the sum
-    over rows against the truth's, at the cells' bounds of test_elements_against_truth plus the N roundings of the sum"""
+    over rows against the truth's, at the cells' bounds of elements_against_truth plus the N roundings of the sum"""
     y, f, regimes = T.grid(pair, pset)
-    rec = T.oracle_errors()[pair][pset]["value"]
+    rec = T.reference_errors()[pair][pset]["value"]
     tr = T.truth(pair, pset, "value")
     got = T.gpu_cost(P, pair, pset, torch.as_tensor(y)).calculate_cost(torch.as_tensor(f).cuda()).cpu().numpy()
     n = len(y)
@@ -86,3 +95,13 @@ def test_value_column_sums(P, pair, pset):
         want = math.fsum(hi) + math.fsum(tr["lo"][:, b])
         tol = T.bound(rec[regime]) * float(tr["unit"][:, b].sum()) + n * 2.0 ** -53 * float(np.abs(hi).sum())
         assert abs(got[b] - want) <= tol, (pair, pset, regime, b, got[b], want, abs(got[b] - want) / tol)
+
+
+@pytest.mark.parametrize("pair,pset", T.cells())
+def test_elements_against_truth(P, pair, pset):
+    elements_against_truth(P, T, pair, pset, reference="oracle")
+
+
+@pytest.mark.parametrize("pair,pset", T.cells())
+def test_value_column_sums(P, pair, pset):
+    value_column_sums(P, T, pair, pset)

@@ -13,8 +13,9 @@ import pytest
 import torch
 
 import cost_truth as T
-from step_fixtures import (EXACT_ETA, SELECTOR_PLACEMENTS, WINO_EDGES, WINO_THREE_CHUNKS, SelectorProblem, assert_selector, option,
-                           probe_winograd, run_selector_forms, spread_columns, winograd_option, wino_one_chunk_bytes)
+from step_fixtures import (EXACT_ETA, SELECTOR_PLACEMENTS, WINO_EDGES, WINO_THREE_CHUNKS, SelectorIpbProblem, SelectorProblem, option,
+                           probe_winograd, run_selector_forms, spread_columns, step_wg, truth_module, winograd_option,
+                           wino_one_chunk_bytes)
 from test_gpu_ksplit import ksplit
 from test_gpu_parity import P, _f64_default  # noqa: F401  (fixtures)
 from test_gpu_rows import row_blocks
@@ -41,7 +42,7 @@ def energy_check(P, ex, gb, cost, e, what, cols=None, gauss_fma=False, truth=Fal
     """The energy by-product ``e`` and fused_particle_energy, on every route: on the sampled columns against fsum of the
     element-wise entry's cost values on the host-built F plus the exact prior (SelectorProblem.energy_direct: N roundings
     of the sum, nothing per element); ``truth``: also on three columns against fsum of the mpmath cost values, N roundings
-    and per element the pair's bound of test_gpu_cost_elements in the element's unit."""
+    and per element the pair's bound of test_gpu_cost_elements (its truth module's) in the element's unit."""
     got = [("by-product", e)]
     if particle_energy:
         got.append(("fused_particle_energy", gb.fused_particle_energy(cost, ex.u.cuda(), force_generic=True)))
@@ -53,7 +54,8 @@ def energy_check(P, ex, gb, cost, e, what, cols=None, gauss_fma=False, truth=Fal
     if truth:
         idx = torch.unique(torch.linspace(0, ex.j - 1, 3).long())
         want, mag, units = ex.energy_truth(idx)
-        b = max(T.bound(v) for v in T.oracle_errors()[ex.pair][ex.pset]["value"].values())
+        tm = truth_module(ex.pair)
+        b = max(tm.bound(v) for v in tm.reference_errors()[ex.pair][ex.pset]["value"].values())
         tol = (ex.n + 2) * 2.0 ** -53 * (mag + want.abs()) + b * units
         for name, en in got:
             err = (en.cpu()[idx] - want).abs()
@@ -61,16 +63,25 @@ def energy_check(P, ex, gb, cost, e, what, cols=None, gauss_fma=False, truth=Fal
             assert (err <= tol).all(), f"{what}: energy {name} off by {(err / tol).max().item():.2f} x its bound"
 
 
-def run(P, pair, fa, mk, n, j, place, what, force_generic=True, truth=None, setup=None, gemm=True):
+def g_direct(P, ex, cost, cols, fa):
+    """the element-wise entry's G in the derivative mode ``fa``; in a family whose two modes are one formula (MODES_AGREE),
+    the same bits as the other mode's"""
+    g = ex.g_direct(P, cost, cols, force_autograd=fa)
+    if fa and truth_module(ex.pair).MODES_AGREE:
+        assert torch.equal(g, ex.g_direct(P, cost, cols, force_autograd=False)), "the two derivative modes differ"
+    return g
+
+
+def run(P, pair, fa, mk, n, j, place, what, force_generic=True, truth=None, setup=None, gemm=True, pset="a"):
     """``gemm``: the route's forward GEMM carries the cost in its epilogue.  For Gaussian/identity that epilogue is one fma
     per element (SelectorProblem.g_gauss_fma): the probe rows are held, bit for bit, to that operation order emulated on the
     host; every other pair runs cost_deriv itself there.  ``truth``: the energies also against mpmath (default: N <= 1600)."""
-    ex = SelectorProblem(pair, mk, n, j, place, seed=mk + n + j)
+    ex = SelectorProblem(pair, mk, n, j, place, seed=mk + n + j, pset=pset)
     gb, cost = ex.basis(P), ex.cost(P, force_autograd=fa)
     if setup:
         setup(gb)
     cols = sample(j)
-    g = ex.g_direct(P, cost, cols, force_autograd=fa)
+    g = g_direct(P, ex, cost, cols, fa)
     gauss = gemm and pair == "gaussian/identity"
     if gauss:
         g, ex.carrier_slack = ex.g_gauss_fma(g, cols)
@@ -166,15 +177,13 @@ def _winograd_orders(a, g, slabs=16):
     yield tot
 
 
-def winograd_case(P, pair, fa, mk, n, j, place, three_chunks=False):
+def winograd_case(P, pair, fa, mk, n, j, place, three_chunks=False, pset="a"):
     """The Winograd route: top-left quadrant as everywhere (probe rows torch.equal: out of place, strided, as new state, with
     per-block step sizes), the energies of EpiWinoCost / EpiWinoGauss against fsum, the other three per element within 4x
     the error the route's formulas make in fp64 on the host on the same G (tests/test_winograd_host.py _winograd; the
     largest over three summation orders of the products), in units of (|A11| + |A12| + |A21| + |A22|) (|G11| + |G12| + |G21|
     + |G22|) -- the sizes the seven products combine -- with a floor of 2^-52 for the roundings of the final combination."""
-    from step_fixtures import step_wg
-
-    ex = SelectorProblem(pair, mk, n, j, place, seed=mk + n + j)
+    ex = SelectorProblem(pair, mk, n, j, place, seed=mk + n + j, pset=pset)
     gb, cost = ex.basis(P), ex.cost(P, force_autograd=fa)
     lib = P.pkg._lib.load()
     u, xi = ex.u.cuda(), P.basis.NoiseSpec(injected=ex.injected.cuda())
@@ -280,16 +289,14 @@ def test_winograd_three_chunks(P, pair):
 
 # -------------------------------------------------------------------------------------------------------------------------
 # the inducing-point basis
-def run_ipb(P, pair, fa, m, n, j, place, what, chunk=None, whitened=False, truth=None, gemm=True, explicit_inverse=False):
-    from step_fixtures import SelectorIpbProblem
-
-    ex = SelectorIpbProblem(pair, m, n, j, place, seed=m + n + j)
+def run_ipb(P, pair, fa, m, n, j, place, what, chunk=None, whitened=False, truth=None, gemm=True, explicit_inverse=False, pset="a"):
+    ex = SelectorIpbProblem(pair, m, n, j, place, seed=m + n + j, pset=pset)
     gb, cost = ex.basis(P, explicit_inverse=explicit_inverse), ex.cost(P, force_autograd=fa)
     if chunk:
         gb.workspace_bytes = P.pkg._lib.load().pls_ipb_step_workspace_bytes(gb._desc(), j, chunk)
     assert torch.equal(gb.whiten(ex.u.cuda()).cpu(), ex.s), "whiten"
     cols = sample(j)
-    g = ex.g_direct(P, cost, cols, force_autograd=fa)
+    g = g_direct(P, ex, cost, cols, fa)
     gauss = gemm and pair == "gaussian/identity"
     if gauss:
         g, ex.carrier_slack = ex.g_gauss_fma(g, cols)

@@ -6,83 +6,27 @@ the fp64 range while the negative binomial stays finite, +-0 and subnormals.
 The bound is tests/test_gpu_cost_elements.py's, unchanged: per (pair, parameter set, kind, regime) the larger of 4x the host
 restatement's recorded error (tests/golden/count_cost_reference_errors.json) and 4 units; IEEE specials must match exactly.
 PLS_COST_TRUTH_DUMP=<file> appends the measured maxima as JSON lines (the rows of DESIGN.md section 3 are made from them)."""
-import json
 import math
-import os
 
-import numpy as np
 import pytest
 import torch
 
 import count_cost_truth as CT
+import test_gpu_cost_elements as E
 from test_gpu_parity import P, _f64_default  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
 
 
-def _dump(record):
-    path = os.environ.get("PLS_COST_TRUTH_DUMP")
-    if path:
-        with open(path, "a") as fh:
-            fh.write(json.dumps(record) + "\n")
-
-
-def gpu_eval(P, pair, pset, kind, strided=False):
-    """the library on the grid, per element (N, J); ``strided``: the samples are the left columns of a wider matrix"""
-    y, f, _ = CT.grid(pair, pset)
-    yt, ft = torch.as_tensor(y), torch.as_tensor(f).cuda()
-    if strided:
-        wide = torch.full((f.shape[0], f.shape[1] + 3), float("nan"), device="cuda")
-        wide[:, :f.shape[1]] = ft
-        ft = wide[:, :f.shape[1]]
-    if kind == "link":
-        return CT.gpu_cost(P, pair, pset, yt).link_function(ft).cpu().numpy()
-    if kind == "value":  # the entry sums over rows: one row at a time
-        rows = [CT.gpu_cost(P, pair, pset, yt[a:a + 1]).calculate_cost(ft[a:a + 1]) for a in range(len(y))]
-        return torch.stack(rows).cpu().numpy()
-    return CT.gpu_cost(P, pair, pset, yt).calculate_cost_derivative(ft, force_autograd=kind == "deriv_autograd").cpu().numpy()
-
-
 @pytest.mark.parametrize("pair,pset", CT.cells())
 def test_elements_against_truth(P, pair, pset):
-    rec = CT.reference_errors()[pair][pset]
-    regimes = CT.grid(pair, pset)[2]
-    missed = []
-    for strided in (False, True):
-        got = {kind: gpu_eval(P, pair, pset, kind, strided) for kind in CT.KINDS}
-        assert np.array_equal(got["deriv_reference"], got["deriv_autograd"], equal_nan=True), "the two derivative modes differ"
-        for kind in CT.KINDS:
-            err = CT.by_regime(CT.errors(got[kind], CT.truth(pair, pset, kind)), regimes)
-            for regime, v in err.items():
-                bound = CT.bound(rec[kind][regime])
-                print(f"{pair} {pset} {kind:16s} {regime:10s} gpu {v:10.3g}  host {rec[kind][regime]!s:>10}  bound {bound:.3g}")
-                if not strided:
-                    _dump({"pair": pair, "pset": pset, "kind": kind, "regime": regime, "gpu": v if math.isfinite(v) else "inf",
-                           "oracle": rec[kind][regime]})
-                if not v <= bound:
-                    missed.append((kind, regime, "strided" if strided else "dense", v, bound))
-    assert not missed, f"{pair} {pset}: cells over their bound (kind, regime, layout, error, bound): {missed}"
+    got = E.elements_against_truth(P, CT, pair, pset)
+    E.modes_agree(got)
 
 
 @pytest.mark.parametrize("pair,pset", CT.cells())
 def test_value_column_sums(P, pair, pset):
-    """calculate_cost on the whole matrix: the sum over rows against fsum of the truth, at the cells' bounds plus the N
-    roundings of the sum"""
-    y, f, regimes = CT.grid(pair, pset)
-    rec = CT.reference_errors()[pair][pset]["value"]
-    tr = CT.truth(pair, pset, "value")
-    got = CT.gpu_cost(P, pair, pset, torch.as_tensor(y)).calculate_cost(torch.as_tensor(f).cuda()).cpu().numpy()
-    n = len(y)
-    for b, regime in enumerate(regimes):
-        hi = tr["hi"][:, b]
-        if not np.isfinite(hi).all():
-            with np.errstate(invalid="ignore"):
-                want = hi.sum()
-            assert (np.isnan(want) and np.isnan(got[b])) or got[b] == want, (pair, pset, regime, b, got[b], want)
-            continue
-        want = math.fsum(hi) + math.fsum(tr["lo"][:, b])
-        tol = CT.bound(rec[regime]) * float(tr["unit"][:, b].sum()) + n * 2.0 ** -53 * float(np.abs(hi).sum())
-        assert abs(got[b] - want) <= tol, (pair, pset, regime, b, got[b], want, abs(got[b] - want) / tol)
+    E.value_column_sums(P, CT, pair, pset)
 
 
 def test_predict_samples_with_a_column_offset(P):

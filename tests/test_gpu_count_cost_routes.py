@@ -5,15 +5,11 @@ mpmath truth -- whatever the route, its tiling, its compile-time specialisation,
 carrier row is held to its summation bound against fsum, the energies to fsum of the element-wise values and, on the small
 shapes, of the mpmath values.  Gaussian/exp, the exponential link through the run-time-switch instantiation, runs the plain
 route and the small-rank route.  Shapes: the smallest at which each route can still go wrong."""
-import types
-
 import pytest
-import torch
 
 import count_cost_truth as CT
 import test_gpu_cost_routes as R
-from count_cost_fixtures import CountSelectorIpbProblem, CountSelectorProblem, energy_check
-from step_fixtures import option, run_selector_forms, winograd_option
+from step_fixtures import SelectorProblem, option, winograd_option
 from test_gpu_ksplit import ksplit
 from test_gpu_parity import P, _f64_default  # noqa: F401  (fixtures)
 from test_gpu_rows import row_blocks
@@ -25,30 +21,6 @@ NB = "negative_binomial/exp"
 VARIANTS = [(NB, False), (NB, True)]
 IDS = ["negative_binomial/exp", "negative_binomial/exp/autograd"]
 RUNTIME = "gaussian/exp"
-
-
-def run(P, pair, fa, mk, n, j, place, what, truth=None, setup=None, pset="a"):
-    ex = CountSelectorProblem(pair, mk, n, j, place, seed=mk + n + j, pset=pset)
-    gb, cost = ex.basis(P), ex.cost(P, force_autograd=fa)
-    if setup:
-        setup(gb)
-    cols = R.sample(j)
-    g = ex.g_direct(P, cost, cols, force_autograd=fa)
-    if fa:
-        assert torch.equal(g, ex.g_direct(P, cost, cols, force_autograd=False)), "the two derivative modes differ"
-    e = run_selector_forms(P, ex, gb, cost, g, cols, f"{what} {pair} {place}", True)
-    energy_check(P, ex, gb, cost, e, f"{what} {pair} {place}", cols, truth if truth is not None else n <= 1600)
-    return ex, gb, cost
-
-
-def run_ipb(P, pair, fa, m, n, j, place, what, whitened=False, truth=None):
-    ex = CountSelectorIpbProblem(pair, m, n, j, place, seed=m + n + j)
-    gb, cost = ex.basis(P), ex.cost(P, force_autograd=fa)
-    assert torch.equal(gb.whiten(ex.u.cuda()).cpu(), ex.s), "whiten"
-    cols = R.sample(j)
-    g = ex.g_direct(P, cost, cols, force_autograd=fa)
-    e = run_selector_forms(P, ex.whitened(whitened), gb, cost, g, cols, f"{what} {pair} {place}", whitened=whitened)
-    energy_check(P, ex, gb, cost, e, f"{what} {pair} {place}", cols, truth if truth is not None else n <= 1600)
 
 
 # -------------------------------------------------------------------------------------------------------------------------
@@ -64,12 +36,12 @@ def test_plain_general_route(P, pair, fa, chunks):
 
     with winograd_option(P, 0):
         for place in R.PLACES:
-            run(P, pair, fa, mk, n, j, place, f"plain, {chunks} chunk(s)", setup=setup, truth=False)
+            R.run(P, pair, fa, mk, n, j, place, f"plain, {chunks} chunk(s)", setup=setup, truth=False)
 
 
 def test_second_parameter_set_on_the_plain_route(P):
     with winograd_option(P, 0):
-        run(P, NB, False, 300, 2950, 333, "tail", "plain, r = 50", truth=False, pset="b")
+        R.run(P, NB, False, 300, 2950, 333, "tail", "plain, r = 50", truth=False, pset="b")
 
 
 @pytest.mark.parametrize("pair,fa", VARIANTS, ids=IDS)
@@ -77,7 +49,7 @@ def test_second_parameter_set_on_the_plain_route(P):
 def test_row_block_route(P, pair, fa, mk, mode):
     with row_blocks(P, mode):
         for place in R.PLACES:
-            run(P, pair, fa, mk, 3000, 520, place, f"row blocks {mode}, mk {mk}")
+            R.run(P, pair, fa, mk, 3000, 520, place, f"row blocks {mode}, mk {mk}")
 
 
 @pytest.mark.parametrize("pair,fa", VARIANTS, ids=IDS)
@@ -85,7 +57,7 @@ def test_row_block_route(P, pair, fa, mk, mode):
 def test_ksplit_routes(P, pair, fa, mode):
     with ksplit(P, mode):
         for place in R.PLACES:
-            run(P, pair, fa, 200, 1500, 333, place, f"k-split {mode}", truth=(place == "head"))
+            R.run(P, pair, fa, 200, 1500, 333, place, f"k-split {mode}", truth=(place == "head"))
 
 
 @pytest.mark.parametrize("pair,fa", VARIANTS + [(RUNTIME, False)], ids=IDS + [RUNTIME])
@@ -95,7 +67,7 @@ def test_small_rank_routes(P, pair, fa, mode):
     for i, (n, mk, j) in enumerate(R.SMALL):
         with option(P, P.pkg._lib.OPT_SMALL_RANK_STEP, mode):
             for place in (R.placement(len(pair), int(fa), i), R.placement(len(pair), int(fa), i + 2)):
-                run(P, pair, fa, mk, n, j, place, f"small rank {mode} {n}x{mk}x{j}", truth=(n <= 1530 and place == "head" and i < 2))
+                R.run(P, pair, fa, mk, n, j, place, f"small rank {mode} {n}x{mk}x{j}", truth=(n <= 1530 and place == "head" and i < 2))
 
 
 @pytest.mark.parametrize("pair,fa", VARIANTS, ids=IDS)
@@ -105,24 +77,11 @@ def test_small_shapes_through_the_gemm_route(P, pair, fa):
     for n, mk, j in (R.SMALL[1], R.SMALL[3]):
         with option(P, L.OPT_SMALL_RANK_MAX, 0):
             for place in R.PLACES:
-                run(P, pair, fa, mk, n, j, place, f"small rank off {n}x{mk}x{j}", truth=False)
-
-
-# the Winograd case of tests/test_gpu_cost_routes.py, word for word, with the two names through which it reaches cost_truth
-# (the problem class and the energy check) bound to the count fixtures: a copy of the function over its own globals, the
-# module it comes from is left as it is
-def _count_energy_check(P, ex, gb, cost, e, what, cols=None, gauss_fma=False, truth=False, particle_energy=True):
-    assert not gauss_fma
-    energy_check(P, ex, gb, cost, e, what, cols, truth, particle_energy)
-
-
-winograd_case = types.FunctionType(R.winograd_case.__code__,
-                                   {**vars(R), "SelectorProblem": CountSelectorProblem, "energy_check": _count_energy_check},
-                                   "count_winograd_case", R.winograd_case.__defaults__, R.winograd_case.__closure__)
+                R.run(P, pair, fa, mk, n, j, place, f"small rank off {n}x{mk}x{j}", truth=False)
 
 
 def test_winograd_route(P):
-    winograd_case(P, NB, False, 512, 16384, 2048, "half")
+    R.winograd_case(P, NB, False, 512, 16384, 2048, "half")
 
 
 # -------------------------------------------------------------------------------------------------------------------------
@@ -130,7 +89,7 @@ def test_winograd_route(P):
 @pytest.mark.parametrize("pair,fa", VARIANTS, ids=IDS)
 def test_ipb_general_route(P, pair, fa):
     for place in R.PLACES:
-        run_ipb(P, pair, fa, 200, 300, 333, place, "ipb general", truth=(place == "head"))
+        R.run_ipb(P, pair, fa, 200, 300, 333, place, "ipb general", truth=(place == "head"))
 
 
 @pytest.mark.parametrize("pair,fa", VARIANTS, ids=IDS)
@@ -138,20 +97,20 @@ def test_ipb_one_launch_route(P, pair, fa):
     for i, (n, m, j) in enumerate(R.IPB_SMALL):
         with option(P, P.pkg._lib.OPT_SMALL_RANK_STEP, 2):
             for place in (R.placement(len(pair), int(fa), i), "tail"):
-                run_ipb(P, pair, fa, m, n, j, place, f"ipb one launch {n}x{m}x{j}", truth=(place == "tail" and n <= 333))
+                R.run_ipb(P, pair, fa, m, n, j, place, f"ipb one launch {n}x{m}x{j}", truth=(place == "tail" and n <= 333))
 
 
 @pytest.mark.parametrize("pair,fa", VARIANTS, ids=IDS)
 def test_ipb_whitened_entries(P, pair, fa):
     for n, m, j in ((100, 4, 64), (333, 16, 37)):
         for place in ("tail", "head"):
-            run_ipb(P, pair, fa, m, n, j, place, f"ipb whitened generic {n}x{m}x{j}", whitened=True, truth=False)
+            R.run_ipb(P, pair, fa, m, n, j, place, f"ipb whitened generic {n}x{m}x{j}", whitened=True, truth=False)
 
 
 def test_the_selector_problems_run_through_the_regimes():
     for pair in CT.PAIRS:
-        ex = CountSelectorProblem(pair, 17, 333, 600, "head", seed=1)
+        ex = SelectorProblem(pair, 17, 333, 600, "head", seed=1)
         f = ex.f()
         assert (f.abs() < 3).any() and (f.abs() > 20).any() and (f > 0).any() and (f < 0).any()
         assert set(ex.y.tolist()) == {0.0, 1.0, 3.0, 25.0, 1e6, 0.5, 1.0 / 3.0}
-    assert (CountSelectorProblem(NB, 17, 333, 600, "head", seed=1).f().abs() > 1e9).any()
+    assert (SelectorProblem(NB, 17, 333, 600, "head", seed=1).f().abs() > 1e9).any()

@@ -6,12 +6,10 @@ request.  The carrier row is held to its summation bound against fsum, the energ
 on the small shapes, of the mpmath values.  Shapes: those of the count-cost route tests, the smallest at which each route can
 still go wrong."""
 import pytest
-import torch
 
 import ordinal_cost_truth as CT
 import test_gpu_cost_routes as R
-from ordinal_cost_fixtures import OrdinalSelectorIpbProblem, OrdinalSelectorProblem, bind_winograd_case, energy_check
-from step_fixtures import option, run_selector_forms, winograd_option
+from step_fixtures import SelectorProblem, option, winograd_option
 from test_gpu_ksplit import ksplit
 from test_gpu_parity import P, _f64_default  # noqa: F401  (fixtures)
 from test_gpu_rows import row_blocks
@@ -22,30 +20,6 @@ ORD = "ordinal/identity"
 # (pair, force_autograd): both derivative modes of the dedicated pair (the same bits, through the same instantiation)
 VARIANTS = [(ORD, False), (ORD, True)]
 IDS = ["ordinal/identity", "ordinal/identity/autograd"]
-
-
-def run(P, pair, fa, mk, n, j, place, what, truth=None, setup=None, pset="a"):
-    ex = OrdinalSelectorProblem(pair, mk, n, j, place, seed=mk + n + j, pset=pset)
-    gb, cost = ex.basis(P), ex.cost(P, force_autograd=fa)
-    if setup:
-        setup(gb)
-    cols = R.sample(j)
-    g = ex.g_direct(P, cost, cols, force_autograd=fa)
-    if fa:
-        assert torch.equal(g, ex.g_direct(P, cost, cols, force_autograd=False)), "the two derivative modes differ"
-    e = run_selector_forms(P, ex, gb, cost, g, cols, f"{what} {pair} {place}", True)
-    energy_check(P, ex, gb, cost, e, f"{what} {pair} {place}", cols, truth if truth is not None else n <= 1600)
-    return ex, gb, cost
-
-
-def run_ipb(P, pair, fa, m, n, j, place, what, whitened=False, truth=None):
-    ex = OrdinalSelectorIpbProblem(pair, m, n, j, place, seed=m + n + j)
-    gb, cost = ex.basis(P), ex.cost(P, force_autograd=fa)
-    assert torch.equal(gb.whiten(ex.u.cuda()).cpu(), ex.s), "whiten"
-    cols = R.sample(j)
-    g = ex.g_direct(P, cost, cols, force_autograd=fa)
-    e = run_selector_forms(P, ex.whitened(whitened), gb, cost, g, cols, f"{what} {pair} {place}", whitened=whitened)
-    energy_check(P, ex, gb, cost, e, f"{what} {pair} {place}", cols, truth if truth is not None else n <= 1600)
 
 
 # -------------------------------------------------------------------------------------------------------------------------
@@ -61,13 +35,13 @@ def test_plain_general_route(P, pair, fa, chunks):
 
     with winograd_option(P, 0):
         for place in R.PLACES:
-            run(P, pair, fa, mk, n, j, place, f"plain, {chunks} chunk(s)", setup=setup, truth=False)
+            R.run(P, pair, fa, mk, n, j, place, f"plain, {chunks} chunk(s)", setup=setup, truth=False)
 
 
 def test_second_parameter_set_on_the_plain_route(P):
     """three categories with the narrow middle one (two of the four cutpoint slots are +inf)"""
     with winograd_option(P, 0):
-        run(P, ORD, False, 300, 2950, 333, "tail", "plain, set b", truth=False, pset="b")
+        R.run(P, ORD, False, 300, 2950, 333, "tail", "plain, set b", truth=False, pset="b")
 
 
 @pytest.mark.parametrize("pair,fa", VARIANTS, ids=IDS)
@@ -75,7 +49,7 @@ def test_second_parameter_set_on_the_plain_route(P):
 def test_row_block_route(P, pair, fa, mk, mode):
     with row_blocks(P, mode):
         for place in R.PLACES:
-            run(P, pair, fa, mk, 3000, 520, place, f"row blocks {mode}, mk {mk}")
+            R.run(P, pair, fa, mk, 3000, 520, place, f"row blocks {mode}, mk {mk}")
 
 
 @pytest.mark.parametrize("pair,fa", VARIANTS, ids=IDS)
@@ -83,7 +57,7 @@ def test_row_block_route(P, pair, fa, mk, mode):
 def test_ksplit_routes(P, pair, fa, mode):
     with ksplit(P, mode):
         for place in R.PLACES:
-            run(P, pair, fa, 200, 1500, 333, place, f"k-split {mode}", truth=(place == "head"))
+            R.run(P, pair, fa, 200, 1500, 333, place, f"k-split {mode}", truth=(place == "head"))
 
 
 @pytest.mark.parametrize("pair,fa", VARIANTS, ids=IDS)
@@ -94,7 +68,7 @@ def test_small_rank_routes(P, pair, fa, mode):
     for i, (n, mk, j) in enumerate(R.SMALL):
         with option(P, P.pkg._lib.OPT_SMALL_RANK_STEP, mode):
             for place in (R.placement(len(pair), int(fa), i), R.placement(len(pair), int(fa), i + 2)):
-                run(P, pair, fa, mk, n, j, place, f"small rank {mode} {n}x{mk}x{j}", truth=(n <= 1530 and place == "head" and i < 2),
+                R.run(P, pair, fa, mk, n, j, place, f"small rank {mode} {n}x{mk}x{j}", truth=(n <= 1530 and place == "head" and i < 2),
                     pset="ab"[i % 2])
 
 
@@ -105,15 +79,12 @@ def test_small_shapes_through_the_gemm_route(P, pair, fa):
     for n, mk, j in (R.SMALL[1], R.SMALL[3]):
         with option(P, L.OPT_SMALL_RANK_MAX, 0):
             for place in R.PLACES:
-                run(P, pair, fa, mk, n, j, place, f"small rank off {n}x{mk}x{j}", truth=False)
-
-
-winograd_case = bind_winograd_case(OrdinalSelectorProblem, energy_check, "ordinal_winograd_case")
+                R.run(P, pair, fa, mk, n, j, place, f"small rank off {n}x{mk}x{j}", truth=False)
 
 
 def test_winograd_route(P):
     """at the route's eligibility floor"""
-    winograd_case(P, ORD, False, 512, 16384, 2048, "half")
+    R.winograd_case(P, ORD, False, 512, 16384, 2048, "half")
 
 
 # -------------------------------------------------------------------------------------------------------------------------
@@ -121,7 +92,7 @@ def test_winograd_route(P):
 @pytest.mark.parametrize("pair,fa", VARIANTS, ids=IDS)
 def test_ipb_general_route(P, pair, fa):
     for place in R.PLACES:
-        run_ipb(P, pair, fa, 200, 300, 333, place, "ipb general", truth=(place == "head"))
+        R.run_ipb(P, pair, fa, 200, 300, 333, place, "ipb general", truth=(place == "head"))
 
 
 @pytest.mark.parametrize("pair,fa", VARIANTS, ids=IDS)
@@ -129,21 +100,21 @@ def test_ipb_one_launch_route(P, pair, fa):
     for i, (n, m, j) in enumerate(R.IPB_SMALL):
         with option(P, P.pkg._lib.OPT_SMALL_RANK_STEP, 2):
             for place in (R.placement(len(pair), int(fa), i), "tail"):
-                run_ipb(P, pair, fa, m, n, j, place, f"ipb one launch {n}x{m}x{j}", truth=(place == "tail" and n <= 333))
+                R.run_ipb(P, pair, fa, m, n, j, place, f"ipb one launch {n}x{m}x{j}", truth=(place == "tail" and n <= 333))
 
 
 @pytest.mark.parametrize("pair,fa", VARIANTS, ids=IDS)
 def test_ipb_whitened_entries(P, pair, fa):
     for n, m, j in ((100, 4, 64), (333, 16, 37)):
         for place in ("tail", "head"):
-            run_ipb(P, pair, fa, m, n, j, place, f"ipb whitened generic {n}x{m}x{j}", whitened=True, truth=False)
+            R.run_ipb(P, pair, fa, m, n, j, place, f"ipb whitened generic {n}x{m}x{j}", whitened=True, truth=False)
 
 
 def test_the_selector_problems_run_through_the_regimes():
     """the values drawn still hold |f| < 3 and |f| > 20, both signs, every label of the parameter set and a value >= 1e9;
     none lies where an edge label's derivative would fall between 2^-1000 and 0"""
     for pset in CT.PARAMS:
-        ex = OrdinalSelectorProblem(ORD, 17, 333, 600, "head", seed=1, pset=pset)
+        ex = SelectorProblem(ORD, 17, 333, 600, "head", seed=1, pset=pset)
         f = ex.f()
         assert (f.abs() < 3).any() and (f.abs() > 20).any() and (f > 0).any() and (f < 0).any()
         assert (f >= 1e9).any() and (f <= -1e9).any()
