@@ -37,7 +37,9 @@ def mean_from_chunk_sums(sums, count: int) -> float:
     pls_block_means computes, bit for bit) or from the 16-column sums of the one-launch small-rank step
     (pls_block_desc.energy_sums16): the entries added in ascending order, divided by the particle count."""
     if isinstance(sums, np.ndarray) and sums.shape[0] > 16:
-        return float(np.cumsum(sums)[-1]) / count  # (a cumulative sum is strictly sequential: the loop below, vectorised)
+        # (a cumulative sum is strictly sequential: the loop below, vectorised; the loop starts at 0.0 and np.cumsum at
+        # sums[0], which differ when every sum is -0.0: the + 0.0 is the kernel's +0.0 there and changes nothing else)
+        return (float(np.cumsum(sums)[-1]) + 0.0) / count
     total = 0.0
     for v in sums:
         total += float(v)

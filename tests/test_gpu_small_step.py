@@ -415,7 +415,9 @@ def test_edges_of_the_one_launch_step(P, route, n, mk, j):
         b16 = torch.empty_like(res[2][3])
         P.pkg._lib.check(lib.pls_sums16(res[2][1].data_ptr(), j, b16.data_ptr(), P.pkg._lib.stream_ptr()), "pls_sums16")
         assert torch.equal(res[2][2], chunk) and torch.equal(res[2][3], b16)
-        assert torch.equal(res[0][2], torch.stack([res[0][1][256 * c:256 * c + 256].sum() for c in range(nchunk)])) or relerr(res[0][2], chunk) < 1e-12
+        chunk0 = torch.empty_like(res[0][2])  # (the slab-kernel route: pls_chunk_sums of ITS energies, bit for bit)
+        P.pkg._lib.check(lib.pls_chunk_sums(res[0][1].data_ptr(), j, chunk0.data_ptr(), P.pkg._lib.stream_ptr()), "pls_chunk_sums")
+        assert torch.equal(res[0][2].view(torch.int64), chunk0.view(torch.int64))
         if gauss:
             f = a.T @ u
             want = -eta * (a @ ((f - y[:, None]) / 0.3)) - eta * u / lam[:, None] + math.sqrt(2 * eta) * xi
