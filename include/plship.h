@@ -171,7 +171,26 @@ typedef enum {
  * side) are exactly 0.  Both derivative modes return the same bits; the jitter is ignored.  A y that is not one of 0, 1, 2,
  * 3, 4 (NaN included) gives NaN for value and derivative; a label >= K (its lower cutpoint is +inf) gives the value +inf and
  * the derivative -1: callers validate their labels.  Only PLS_LINK_IDENTITY is accepted (ordered probit is not provided);
- * the pair has kernel instantiations of its own on every step route. */
+ * the pair has kernel instantiations of its own on every step route.
+ * GAMMA is not in the reference either (an addition within ABI 7), for strictly positive, right-skewed continuous data.
+ * p[0] = k, the shape (concentration), 0 < k < inf; mean mu = exp(f), variance mu^2 / k.  The library's y argument holds
+ * z_n = log y_n, NOT y_n: any finite z is valid (an observation beyond the fp64 range of y keeps its bits).  With t = z - f
+ * the value is the negative log-likelihood WITHOUT its f-independent terms z + lgamma(k) - k log k (so energies are
+ * comparable between runs with the same k only):
+ *   cost(z, f)      = k (exp(t) - t)                      >= k, = k at f = log y
+ *   d cost / d f    = k (1 - exp(t)) = -k expm1(t)        in (-inf, k)
+ * exp(t) and expm1(t) come from one argument reduction; the derivative is relatively accurate at its root t = 0.  The rounding
+ * of the subtraction z - f is recovered (a two-sum) and applied to first order, so value and derivative are within a few ulps
+ * of the ones at the exact real z - f wherever they are finite.  The edges:
+ *   t above the exponential's range (e^t rounds to +inf), f = -inf or z = +inf:   value +inf (never NaN), derivative -inf
+ *   e^t underflows:                                                                value -k t, derivative exactly k
+ *   z = -inf (y = 0) or f = +inf:                                                  value +inf, derivative k
+ *   a NaN in z or f:                                                               that NaN, in value and derivative
+ * (z and f infinite with the same sign have no difference: NaN; finite z and f whose fp64 difference overflows count as
+ * t = +-inf).  Both derivative modes return the same bits, and the jitter is ignored.  Only PLS_LINK_EXP is accepted; the pair
+ * has kernel instantiations of its own on every step route.  The drift is bounded above by k but not below, and its slope in f
+ * is k e^t: the stable step size behaves like Poisson's (it shrinks with the largest y_n / mu_n a particle meets), not like
+ * that of the three bounded families NEGATIVE_BINOMIAL/EXP, BETA/SIGMOID and ORDINAL. */
 typedef enum {
   PLS_COST_GAUSSIAN = 0,
   PLS_COST_POISSON = 1,
@@ -180,12 +199,14 @@ typedef enum {
   PLS_COST_MULTIMODAL = 4,
   PLS_COST_NEGATIVE_BINOMIAL = 5,
   PLS_COST_BETA = 7, /* (6 is not a kind) */
-  PLS_COST_ORDINAL = 9 /* (8 is not a kind) */
+  PLS_COST_ORDINAL = 9, /* (8 is not a kind) */
+  PLS_COST_GAMMA = 11  /* (10 is not a kind) */
 } pls_cost_kind;
 
 /* src/projected_langevin_sampling/link_functions.py:30-80
  * EXP is not in the reference (an addition within ABI 7): p = exp(f), slope p, no clip -- the jitter is ignored; +inf above
- * the fp64 range, gradual underflow below it.  Under a cost other than NEGATIVE_BINOMIAL it runs by the generic chain rule. */
+ * the fp64 range, gradual underflow below it.  Under a cost other than NEGATIVE_BINOMIAL and GAMMA (which is stated in f
+ * itself) it runs by the generic chain rule. */
 typedef enum {
   PLS_LINK_IDENTITY = 0,
   PLS_LINK_SQUARE = 1,
@@ -213,6 +234,7 @@ typedef struct {
    *          negative_binomial {dispersion r};
    *          beta {precision phi};
    *          ordinal {up to four ascending cutpoints, +inf for the unused trailing ones};
+   *          gamma {shape k};
    *          poisson / bernoulli: unused */
   double p[4];
   double jitter; /* clip of sigmoid / probit links (link_functions.py:36, :64), default 1e-10 */

@@ -6,7 +6,7 @@ side: it owns device memory through torch tensors and calls the C ABI (include/p
 The one exception is the eigendecomposition of setup and prediction, torch.linalg.eigh by default as in the reference;
 eigh_device="plship" runs it in the library as well (pls_sym_eigh)."""
 from . import _lib
-from .costs import BetaCost, NegativeBinomialCost, OrdinalCost
+from .costs import BetaCost, GammaCost, NegativeBinomialCost, OrdinalCost
 from .conformalise import ConformaliseGP, ConformalisePLS, ConformalPrediction, gaussian_interval
 from .gaussian_process import (SVGP, DirichletExactGP, ExactGP, construct_average_ard_kernel, construct_average_gaussian_noise,
                                dirichlet_targets, estimate_student_parameters, exact_gp_runner, fit_student_t, nearest_subsample,
@@ -26,4 +26,4 @@ __all__ = ["PLS", "PLSKernel", "ARDKernel", "MaternKernel", "RQKernel", "Periodi
            "nearest_subsample", "SVGP", "train_svgp", "train_svgp_runner", "epoch_batches", "TemperGP", "GaussianLikelihood",
            "BernoulliLikelihood", "StudentTLikelihood", "fit_student_t", "estimate_student_parameters", "ConformaliseGP",
            "ConformalisePLS", "ConformalPrediction", "gaussian_interval", "NegativeBinomialCost", "ExponentialLinkFunction", "BetaCost",
-           "OrdinalCost", "_lib"]
+           "OrdinalCost", "GammaCost", "_lib"]

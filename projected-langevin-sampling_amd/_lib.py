@@ -33,6 +33,7 @@ def kernel_shape_params(kind: int, d: int) -> int:
 COST_GAUSSIAN, COST_POISSON, COST_BERNOULLI, COST_STUDENT_T, COST_MULTIMODAL, COST_NEGATIVE_BINOMIAL = range(6)
 COST_BETA = 7  # (6 is not a kind)
 COST_ORDINAL = 9  # (8 is not a kind)
+COST_GAMMA = 11  # (10 is not a kind)
 LINK_IDENTITY, LINK_SQUARE, LINK_SIGMOID, LINK_PROBIT, LINK_EXP = range(5)
 DERIV_REFERENCE, DERIV_AUTOGRAD = 0, 1
 NOISE_NONE, NOISE_INJECTED, NOISE_PHILOX = 0, 1, 2

@@ -5,8 +5,8 @@ The reference stores a trained sampler as ``torch.save({"particles", "observatio
 (experiments/loaders.py:10-28).  Files written by either implementation load in the other.  Two optional extra keys
 make a J-sharded run exactly resumable: ``noise_step`` (the step counter of the Philox stream) and
 ``number_of_particles`` (the global J a shard belongs to); the reference ignores unknown keys.  A cost with a
-``dispersion`` (NegativeBinomialCost), a ``precision`` (BetaCost) or ``cutpoints`` (OrdinalCost, a list of floats) has it
-stored under that key and restored from it, as ``observation_noise`` is.
+``dispersion`` (NegativeBinomialCost), a ``precision`` (BetaCost), ``cutpoints`` (OrdinalCost, a list of floats) or a
+``concentration`` (GammaCost) has it stored under that key and restored from it, as ``observation_noise`` is.
 
 Particles of the orthonormal basis are COORDINATES in the eigenvector gauge of the basis they were trained with
 (orthonormal.py:46-68), and an eigendecomposition is defined only up to signs and rotations inside clusters: the file
@@ -24,7 +24,8 @@ from .projected_langevin_sampling import PLS
 
 
 # the cost parameters that travel with the particles: (key in the file = attribute of the cost, the form it is stored in)
-COST_PARAMETERS = (("dispersion", float), ("precision", float), ("cutpoints", lambda c: [float(x) for x in c]))
+COST_PARAMETERS = (("dispersion", float), ("precision", float), ("cutpoints", lambda c: [float(x) for x in c]),
+                   ("concentration", float))
 
 
 def _basis_fingerprint(pls) -> Optional[dict]:

@@ -1,6 +1,7 @@
 from .base import PLSCost
 from .bernoulli import BernoulliCost
 from .beta import BetaCost
+from .gamma import GammaCost
 from .gaussian import GaussianCost
 from .multimodal import MultiModalCost
 from .negative_binomial import NegativeBinomialCost
@@ -9,4 +10,4 @@ from .poisson import PoissonCost
 from .student_t import StudentTCost
 
 __all__ = ["PLSCost", "BernoulliCost", "GaussianCost", "PoissonCost", "StudentTCost", "MultiModalCost",
-           "NegativeBinomialCost", "BetaCost", "OrdinalCost"]
+           "NegativeBinomialCost", "BetaCost", "OrdinalCost", "GammaCost"]

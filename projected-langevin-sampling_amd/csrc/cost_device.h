@@ -46,7 +46,8 @@ __host__ inline CostP make_costp(const pls_cost_desc *d) {
 }
 
 // THE list of the (cost, link) pairs with kernel instantiations of their own (the pairs the reference's experiments use, and
-// negative binomial/exp, beta/sigmoid and ordinal/identity -- the only link the ordinal cost is accepted with):
+// negative binomial/exp, beta/sigmoid, ordinal/identity and gamma/exp -- the only links the ordinal and the Gamma cost are
+// accepted with):
 // f(integral_constant<COST>, integral_constant<LINK>) for one of them, f(-1, -1) -- the instantiation that switches at run
 // time -- for every other pair; Beta under another link gets f(PLS_COST_BETA, -1), which switches the link only (the
 // run-time-switch instantiation does not carry the Beta code).  Every launcher that dispatches on the pair goes through here.
@@ -64,6 +65,7 @@ __host__ inline int for_cost_link(const CostP &cp, F &&f) {
   if (c == PLS_COST_BETA && l == PLS_LINK_SIGMOID) return f(integral_constant<int, PLS_COST_BETA>{}, integral_constant<int, PLS_LINK_SIGMOID>{});
   if (c == PLS_COST_BETA) return f(integral_constant<int, PLS_COST_BETA>{}, integral_constant<int, -1>{});  // (the link at run time)
   if (c == PLS_COST_ORDINAL && l == PLS_LINK_IDENTITY) return f(integral_constant<int, PLS_COST_ORDINAL>{}, integral_constant<int, PLS_LINK_IDENTITY>{});
+  if (c == PLS_COST_GAMMA && l == PLS_LINK_EXP) return f(integral_constant<int, PLS_COST_GAMMA>{}, integral_constant<int, PLS_LINK_EXP>{});
   return f(integral_constant<int, -1>{}, integral_constant<int, -1>{});
 }
 
@@ -284,6 +286,51 @@ __device__ __forceinline__ double ordinal_deriv(const CostP &c, double y, double
   return (k.hi == k.hi) ? g : k.hi;
 }
 
+// The Gamma cost (shape k = p0, mean e^f; plship.h) under the exponential link.  y holds z = log of the observation.  In
+// t = z - f:
+//   cost  = k (e^t - t)   >= k,      cost' = k (1 - e^t) = -k expm1(t)   in (-inf, k)
+// One exponential, no logarithm and no division: fast_exp_expm1 gives e^t and expm1(t) from one reduction, so the derivative is
+// relatively accurate at its root t = 0 (the posterior mode), where 1 - e^t would leave an absolute 2^-53.
+// t itself rounds where z and f differ in size (at |t| = 600 half an ulp of t is 2^-44: hundreds of ulps of e^t).  A two-sum
+// recovers the subtraction's error t_lo exactly, and it enters to first order (t_lo^2 < 2^-88):
+//   e^t = e^t_hi (1 + t_lo),   expm1(t) = expm1(t_hi) + e^t_hi t_lo,   e^t - t = (e^t - t_hi) - t_lo
+// so value and derivative are a few ulps from the ones at the exact real z - f wherever they are finite.  The ends: e^t_hi = +inf
+// (t above the exponential's range, f = -inf, z = +inf) gives the value +inf -- not inf - inf -- and the derivative -inf; where
+// e^t underflows the value is -k t and the derivative exactly k (also for z = -inf, an observation of 0, and f = +inf: value
+// +inf); a NaN in z or f comes back.  There is one formula for both derivative modes and no clip.
+// A kernel that asks for value and derivative calls both functions with the same arguments: the two-sum and the reduction are
+// the same expressions in both and are evaluated once.  Like the Beta and ordinal code this is NOT a case of cost_value /
+// cost_deriv.
+struct GammaT {
+  double hi, lo;
+};
+__device__ __forceinline__ GammaT gamma_t(double z, double f) {
+#pragma clang fp contract(off)
+  GammaT t;
+  t.hi = z - f;
+  const double fv = t.hi - z;  // the part of -f that arrived in hi
+  const double lo = (z - (t.hi - fv)) + (-f - fv);  // exact: z - f = hi + lo
+  t.lo = (fabs(t.hi) < 1024.0) ? lo : 0.0;  // (beyond: e^t is 0 or +inf, and an infinite or NaN hi would leave NaN here)
+  return t;
+}
+__device__ __forceinline__ double gamma_exp_value(const CostP &c, double z, double f) {
+#pragma clang fp contract(off)
+  const GammaT t = gamma_t(z, f);
+  const ExpPair q = fast_exp_expm1(t.hi);
+  const double e = fma(q.e, t.lo, q.e);
+  double v = (e - t.hi) - t.lo;
+  v = (q.e == __builtin_huge_val()) ? q.e : v;
+  return c.p0 * v;
+}
+__device__ __forceinline__ double gamma_exp_deriv(const CostP &c, double z, double f) {  // one value for both modes
+#pragma clang fp contract(off)
+  const GammaT t = gamma_t(z, f);
+  const ExpPair q = fast_exp_expm1(t.hi);
+  double em1 = fma(q.e, t.lo, q.em1);
+  em1 = (q.e == __builtin_huge_val()) ? q.e : em1;
+  return -c.p0 * em1;
+}
+
 // cost(y, f) for one (n, j) entry; summed over n by the callers.
 __device__ inline double cost_value(const CostP &c, double y, double f) {
 #pragma clang fp contract(off)
@@ -370,7 +417,8 @@ __device__ inline double cost_deriv(const CostP &c, double y, double f) {
 }
 
 // The per-element calls of the kernels that are instantiated per pair: COST as for_cost_link passed it (a kernel with
-// COST >= 0 sets c.cost = COST, and c.link = LINK where LINK >= 0).  Beta: p0 = phi, y = logit of the observation.
+// COST >= 0 sets c.cost = COST, and c.link = LINK where LINK >= 0).  Beta: p0 = phi, y = logit of the observation.  Gamma (only
+// ever under the exponential link): p0 = k, y = log of the observation.
 __device__ __forceinline__ double beta_cost_value(const CostP &c, double y, double f) {
 #pragma clang fp contract(off)
   if (c.link == PLS_LINK_SIGMOID) return beta_logit_value(c.p0, c.mm_l1, y, f);  // (in f: no clip)
@@ -389,12 +437,14 @@ template <int COST>
 __device__ __forceinline__ double cost_value_of(const CostP &c, double y, double f) {
   if constexpr (COST == PLS_COST_BETA) return beta_cost_value(c, y, f);
   else if constexpr (COST == PLS_COST_ORDINAL) return ordinal_value(c, y, f);
+  else if constexpr (COST == PLS_COST_GAMMA) return gamma_exp_value(c, y, f);
   else return cost_value(c, y, f);
 }
 template <int COST>
 __device__ __forceinline__ double cost_deriv_of(const CostP &c, double y, double f) {
   if constexpr (COST == PLS_COST_BETA) return beta_cost_deriv(c, y, f);
   else if constexpr (COST == PLS_COST_ORDINAL) return ordinal_deriv(c, y, f);
+  else if constexpr (COST == PLS_COST_GAMMA) return gamma_exp_deriv(c, y, f);
   else return cost_deriv(c, y, f);
 }
 

@@ -58,6 +58,52 @@ __device__ __forceinline__ double fast_exp(double x) {
   return v;
 }
 
+// exp(x) and expm1(x) from one reduction x = n ln 2 + r (the split and the polynomial of fast_exp; e has fast_exp's bits).
+// With w = expm1(r) - r = r^2 (1/2 + r/6 + ... + r^11 / 13!), |w| <= 0.07:
+//   expm1(x) = 2^n (1 + r + w) - 1 = [2^n r + (2^n - 1)] + 2^n w,
+// the bracket one fma, the correction a second: r is exact up to half an ulp of itself, 2^n - 1 is exact for |n| <= 53, and the
+// bracket is never below 0.29 of its larger term (n = +-1 at |x| just above ln 2 / 2), so nothing cancels -- <= 2 ulp on the
+// whole range.  For n = 0 r is x itself: expm1(x) = x + w, x to the last bit where w is below half an ulp of it (subnormals
+// included).  From n = -54 down 2^n - 1 rounds to -1 and the result is exactly -1 (e^x < 2^-54: half an ulp of 1 from below);
+// above n = 64 the 1 is below a 2^-11th of an ulp of e^x and expm1 is e itself (2^n overflows from n = 1024, where e^x need
+// not).  The limits are fast_exp's: (0, -1) below -745.2, (+inf, +inf) above 709.8, NaN for NaN.
+struct ExpPair {
+  double e, em1;
+};
+__device__ __forceinline__ ExpPair fast_exp_expm1(double x) {
+#pragma clang fp contract(off)
+  const double n = rint(x * 1.4426950408889634074);
+  double r = fma(n, -6.93147180369123816490e-01, x);
+  r = fma(n, -1.90821492927058770002e-10, r);
+  double p = 1.6059043836821613e-10;  // 1/13!
+  p = fma_k(p, r, 2.0876756987868098e-09);
+  p = fma_k(p, r, 2.5052108385441720e-08);
+  p = fma_k(p, r, 2.7557319223985893e-07);
+  p = fma_k(p, r, 2.7557319223985888e-06);
+  p = fma_k(p, r, 2.4801587301587302e-05);
+  p = fma_k(p, r, 1.9841269841269841e-04);
+  p = fma_k(p, r, 1.3888888888888889e-03);
+  p = fma_k(p, r, 8.3333333333333332e-03);
+  p = fma_k(p, r, 4.1666666666666664e-02);
+  p = fma_k(p, r, 1.6666666666666666e-01);
+  p = fma(p, r, 0.5);
+  const double w = (r * r) * p;
+  p = fma(p, r, 1.0);
+  p = fma(p, r, 1.0);
+  const int k = (int)n;
+  const double s = ldexp(1.0, k);
+  ExpPair q;
+  q.e = ldexp(p, k);
+  q.em1 = fma(s, w, fma(s, r, s - 1.0));
+  q.em1 = (n > 64.0) ? q.e : q.em1;
+  const bool under = x < -745.2, over = x > 709.8;  // (NaN fails both comparisons and has already propagated through r)
+  q.e = under ? 0.0 : q.e;
+  q.em1 = under ? -1.0 : q.em1;
+  q.e = over ? __builtin_huge_val() : q.e;
+  q.em1 = over ? __builtin_huge_val() : q.em1;
+  return q;
+}
+
 // Newton steps on the v_rcp_f64 seed before the quotient's residual correction.  The seed r0 has a relative error e0; one
 // step leaves e0^2 in r, the quotient q = a r inherits it, and the correction q + r (a - b q) squares it again: with the
 // ~2^-26 seed of gfx9 one step gives 2^-52 before and 2^-104 after the correction, i.e. the correctly rounded quotient up to

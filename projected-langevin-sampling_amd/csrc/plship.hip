@@ -712,6 +712,7 @@ __global__ __launch_bounds__(256) void cost_deriv_kernel(CostP cp, const double 
     const double yv = y[row], f = F[row * ldf + col];
     G[row * ldg + col] = (cp.cost == PLS_COST_BETA)      ? beta_cost_deriv(cp, yv, f)
                          : (cp.cost == PLS_COST_ORDINAL) ? ordinal_deriv(cp, yv, f)
+                         : (cp.cost == PLS_COST_GAMMA)   ? gamma_exp_deriv(cp, yv, f)
                                                          : cost_deriv(cp, yv, f);
   }
 }
@@ -733,6 +734,7 @@ __global__ __launch_bounds__(256) void cost_value_partial_kernel(CostP cp, const
         const double yv = y[row], f = F[row * ldf + col];
         s += (cp.cost == PLS_COST_BETA)      ? beta_cost_value(cp, yv, f)
              : (cp.cost == PLS_COST_ORDINAL) ? ordinal_value(cp, yv, f)
+             : (cp.cost == PLS_COST_GAMMA)   ? gamma_exp_value(cp, yv, f)
                                              : cost_value(cp, yv, f);
       }
     }
@@ -1609,7 +1611,7 @@ static int launch_langevin_update(double *out, int64_t ldo, int add_u, const dou
 static int validate_cost(const pls_cost_desc *c) {
   PLS_REQUIRE(c != nullptr, "cost descriptor is NULL");
   PLS_REQUIRE((c->cost >= PLS_COST_GAUSSIAN && c->cost <= PLS_COST_NEGATIVE_BINOMIAL) || c->cost == PLS_COST_BETA ||
-                  c->cost == PLS_COST_ORDINAL,
+                  c->cost == PLS_COST_ORDINAL || c->cost == PLS_COST_GAMMA,
               "unknown cost kind %d", c->cost);
   PLS_REQUIRE(c->link >= PLS_LINK_IDENTITY && c->link <= PLS_LINK_EXP, "unknown link kind %d", c->link);
   PLS_REQUIRE(c->deriv_mode == PLS_DERIV_REFERENCE || c->deriv_mode == PLS_DERIV_AUTOGRAD, "unknown deriv_mode %d",
@@ -1634,6 +1636,10 @@ static int validate_cost(const pls_cost_desc *c) {
         PLS_REQUIRE(c->p[i] > 0.0, "ordinal cost: an unused cutpoint is +inf, p[%d] is -inf", i);
       }
     }
+  }
+  if (c->cost == PLS_COST_GAMMA) {  // p[0]: the shape k
+    PLS_REQUIRE(c->link == PLS_LINK_EXP, "gamma cost needs the exponential link (log link), got link kind %d", c->link);
+    PLS_REQUIRE(c->p[0] > 0.0 && std::isfinite(c->p[0]), "gamma cost needs a finite shape (concentration) > 0");
   }
   return PLS_OK;
 }

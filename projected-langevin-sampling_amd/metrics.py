@@ -18,7 +18,7 @@ def _point(prediction) -> torch.Tensor:
         return prediction.rate
     if isinstance(prediction, torch.distributions.StudentT):
         return prediction.loc
-    if isinstance(prediction, (torch.distributions.NegativeBinomial, torch.distributions.Beta)):  # (not in the reference)
+    if isinstance(prediction, (torch.distributions.NegativeBinomial, torch.distributions.Beta, torch.distributions.Gamma)):  # (not in the reference)
         return prediction.mean
     if isinstance(prediction, torch.distributions.Categorical):  # (not in the reference) the expected category index
         return prediction.probs @ torch.arange(prediction.probs.shape[-1], dtype=prediction.probs.dtype, device=prediction.probs.device)
@@ -50,7 +50,7 @@ def calculate_nll(prediction, y: torch.Tensor) -> float:
         return torch.nn.functional.poisson_nll_loss(prediction.rate, y.to(prediction.rate), reduction="mean").item()
     if isinstance(prediction, torch.distributions.StudentT):
         return prediction.log_prob(y.to(prediction.loc)).mean().item()  # metrics.py:98-99 (sign as in the reference)
-    if isinstance(prediction, (torch.distributions.NegativeBinomial, torch.distributions.Beta)):  # (not in the reference)
+    if isinstance(prediction, (torch.distributions.NegativeBinomial, torch.distributions.Beta, torch.distributions.Gamma)):  # (not in the reference)
         return -prediction.log_prob(y.to(prediction.mean)).mean().item()
     if isinstance(prediction, torch.distributions.Categorical):  # (not in the reference)
         return -prediction.log_prob(y.to(device=prediction.probs.device, dtype=torch.long)).mean().item()
