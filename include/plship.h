@@ -532,19 +532,89 @@ int pls_kernel_gram(int32_t kernel_kind, const double *x1, int64_t n1, const dou
                     int64_t d, const double *lengthscale, double outputscale, double *out, int64_t ldout,
                     void *stream);
 
+/* Leading dimensions.  Every ld* argument and descriptor field counts doubles and is an int64_t; a strided view of a
+ * wider buffer is a valid operand.  The element-wise and reduction kernels index with 64 bits and take ANY leading
+ * dimension: pls_kernel_gram, pls_cost_derivative, pls_cost_value, pls_link_transform, pls_row_power_sums,
+ * pls_row_quantiles, pls_normal_fill, pls_softmax_normal_mean, pls_kernel_mean, pls_sym_eigh, pls_svgp_*, pls_gp_mll_*,
+ * pls_onb_build_gaussian, pls_ipb_build_gaussian, pls_chol_factor's K, and the output / particle / noise arguments
+ * (ldu, ldo, ldf, ldg, ldxi) of every step, forward, update and energy entry wherever they are not an operand of a
+ * contraction.  The MFMA kernels address operands with 32-bit byte offsets behind 2 GiB buffer descriptors.  For each
+ * such site the call is either ROUTED to a kernel that takes the stride (nothing to do for the caller) or REFUSED with
+ * PLS_ERR_INVALID_ARGUMENT and a message that names the leading dimension -- never answered with wrong numbers:
+ *   - contraction operands (ldl, ldr of pls_gemm_tn; lda, ldat, ldb of pls_onb_desc; ldkzx, ldkxz, ldw, ldlct, ldb,
+ *     ldlinv, ldlinvt, ldq, ldpt, ldawa of pls_ipb_desc; the particles U / S where a step contracts them; ldvs, ldkzx of
+ *     pls_onb_build_projection; ldlc, ldlct, ldsf, ldsb of pls_chol_factor and pls_chol_build_operators): a shape of
+ *     few tiles runs on the k-split kernels while both leading dimensions are below 2^22, and is ROUTED to the tile
+ *     kernels from 2^22 on.  The 128 x 128 tiles (256 or more of them), their row-block form and the Winograd route
+ *     copy 16-byte aligned operands with even leading dimensions by LDS-DMA and REFUSE ld >
+ *     pls_ld_limit(PLS_LD_GEMM_TILES, 1, cols) = (0x7FFFFFF0 - 8 cols) / 120 for an operand of `cols` columns, an odd
+ *     count rounded up to even (17895688 at cols = 128).  Operands that are not so
+ *     aligned, and every shape below 256 tiles of 128 x 128, load through 64-bit pointers: no limit.
+ *   - contraction outputs (ldc of pls_gemm_tn, ldf of pls_onb_forward / pls_ipb_forward, the outputs of the Gaussian
+ *     fast-path steps, the outputs of the solves' products): interior tiles are stored from registers below 2^21 and
+ *     through LDS with 64-bit addresses from 2^21 on (ROUTED inside the kernel): no limit.
+ *   - the substitution kernel (pls_chol_solve, pls_chol_build_inverse; pls_chol_forward_solve and pls_chol_solve_ws
+ *     when they substitute; the solves inside the pls_ipb_* entries): ldu, ldv REFUSED above
+ *     pls_ld_limit(PLS_LD_TRI_SOLVE, m, j) = (0x7FFFFF00 / 8 - j) / (min(m, 128) - 1), and ldsf, ldsb above the same
+ *     with j = m (2113664 at m >= 128, j = 96).
+ *   - the fused small-rank kernels and the one-launch step (mk or m <= 128): ROUTED to the contraction kernels when the
+ *     back-projection operand's leading dimension (ldat, ldkxz) exceeds pls_ld_limit(PLS_LD_SMALL_RANK, ..) = 2^23;
+ *     pls_ipb_whitened_generic_step, which has no other kernel, REFUSES ldawa beyond it (pls_ipb_whitened_generic_applies
+ *     returns 0 for such a descriptor).
+ *   - the solve-and-noise launch of the inducing-point step (m <= 128): ROUTED to the separate solve and noise launches
+ *     when ldlinv, ldlinvt or ldlct exceeds pls_ld_limit(PLS_LD_IPB_PREP, m, 1) = (0x7FFFFFF0 / 8 - m) / (m - 1).
+ * pls_ld_limit returns the largest leading dimension a site takes (the bound the library itself applies; pure host
+ * code; -1 for an unknown site or rows / cols < 1). */
+typedef enum {
+  PLS_LD_GEMM_TILES = 0,        /* LDS-DMA k-loop of the 128 x 128 tiles: operand of `cols` columns (refused beyond) */
+  PLS_LD_GEMM_KSPLIT = 1,       /* k-split kernels (routed to the tile kernels beyond) */
+  PLS_LD_GEMM_DIRECT_STORE = 2, /* register -> global tile store (routed through LDS beyond) */
+  PLS_LD_TRI_SOLVE = 3,         /* substitution kernel: factor of order `rows`, operand of `cols` columns (refused beyond) */
+  PLS_LD_SMALL_RANK = 4,        /* fused small-rank kernels (routed to the contraction kernels beyond) */
+  PLS_LD_IPB_PREP = 5           /* solve-and-noise launch: factor of order `rows` (routed to separate launches beyond) */
+} pls_ld_site;
+int64_t pls_ld_limit(int32_t site, int64_t rows, int64_t cols);
+
 /* C(I x J) = alpha * L^T R + beta * C with L (K x I, ldl), R (K x J, ldr): the fp64 MFMA contraction.
- * Replaces every `@` on the path: orthonormal.py:106-108, :152-155; inducing_point.py:89-93, :144. */
+ * Replaces every `@` on the path: orthonormal.py:106-108, :152-155; inducing_point.py:89-93, :144.
+ * Leading dimensions: ldl, ldr as contraction operands, ldc as a contraction output (above). */
 int pls_gemm_tn(const double *L, int64_t ldl, const double *R, int64_t ldr, double *C, int64_t ldc, int64_t I,
                 int64_t J, int64_t K, double alpha, double beta, void *stream);
 
+/* The kernel pls_gemm_tn would launch for these arguments under the calling thread's options, decided by the launchers'
+ * own predicates; nothing is launched and L, R are only inspected for alignment.  *direct_store (may be NULL): 1 when
+ * interior tiles are stored from registers, 0 when every tile leaves through LDS.  Returns a pls_gemm_route, or
+ * -PLS_ERR_INVALID_ARGUMENT when pls_gemm_tn would refuse the call (pls_last_error() says why).  I, J >= 1. */
+typedef enum {
+  PLS_GEMM_ROUTE_TILES_128 = 0,
+  PLS_GEMM_ROUTE_TILES_64 = 1,
+  PLS_GEMM_ROUTE_KSPLIT_1 = 2,
+  PLS_GEMM_ROUTE_KSPLIT_2 = 3,
+  PLS_GEMM_ROUTE_ROW_BLOCKS = 4
+} pls_gemm_route;
+int pls_gemm_tn_route(const double *L, int64_t ldl, const double *R, int64_t ldr, int64_t ldc, int64_t I, int64_t J,
+                      int64_t K, int32_t *direct_store);
+
+/* Which fused small-rank kernels the step and energy entries would hand the back-projection operand Lb (n x kdim, ldlb:
+ * At of pls_onb_desc, Kxz or Awa of pls_ipb_desc) for targets y and j particle columns, under the calling thread's
+ * options, by the entries' own predicates; nothing is launched and Lb, y are only inspected for alignment.  Returns an
+ * OR of pls_small_rank_route_bits (0: the contraction kernels take the operand), or -PLS_ERR_INVALID_ARGUMENT.
+ * Leading dimensions: ldlb as the small-rank kernels' operand (above): both bits clear beyond 2^23. */
+typedef enum {
+  PLS_SMALL_RANK_SLABS = 1,     /* the slab kernels of the general routes and energies (kdim <= PLS_OPT_SMALL_RANK_MAX) */
+  PLS_SMALL_RANK_ONE_LAUNCH = 2 /* the one-launch step (PLS_OPT_SMALL_RANK_STEP, 16-byte aligned y, launch-bound sizes) */
+} pls_small_rank_route_bits;
+int pls_small_rank_route(const double *Lb, int64_t ldlb, int64_t kdim, int64_t n, const double *y, int64_t j);
+
 /* G(N x J) = d cost / d f evaluated at F(N x J), y(N).  Replaces PLSCost.calculate_cost_derivative
- * (costs/gaussian.py:86-88, poisson.py:76-82, bernoulli.py:64-77, student_t.py:82-88, base.py:68-84). */
+ * (costs/gaussian.py:86-88, poisson.py:76-82, bernoulli.py:64-77, student_t.py:82-88, base.py:68-84).
+ * Leading dimensions: ldf, ldg any (64-bit indexing). */
 int pls_cost_derivative(const pls_cost_desc *cost, const double *F, int64_t ldf, const double *y, int64_t n,
                         int64_t j, double *G, int64_t ldg, void *stream);
 
 /* c(J) = sum_n cost(y_n, F_nj).  Replaces PLSCost.calculate_cost (gaussian.py:63-73, poisson.py:59-66,
  * bernoulli.py:57-62, student_t.py:57-72, multimodal.py:37-77).  Deterministic summation order.
- * workspace: pls_cost_value_workspace_bytes(n, j) bytes. */
+ * workspace: pls_cost_value_workspace_bytes(n, j) bytes.  Leading dimensions: ldf any (64-bit indexing). */
 size_t pls_cost_value_workspace_bytes(int64_t n, int64_t j);
 int pls_cost_value(const pls_cost_desc *cost, const double *F, int64_t ldf, const double *y, int64_t n, int64_t j,
                    double *c, void *workspace, size_t workspace_bytes, void *stream);
@@ -594,29 +664,41 @@ int pls_chunk_sums(const double *e, int64_t j, double *out, void *stream);
  * Outputs (caller-allocated, M x M each, 16-byte aligned, even leading dimensions): Lc, LcT and -- unless NULL -- the
  * substitution operators Sf, Sb (see pls_chol_desc).  info (DEVICE int32): 0, or the 1-based index of the first
  * pivot that was not positive (K + jitter I is not numerically positive definite; the outputs are then garbage and the
- * caller retries with a larger jitter, as gpytorch's psd_safe_cholesky does).  Nothing synchronises. */
+ * caller retries with a larger jitter, as gpytorch's psd_safe_cholesky does).  Nothing synchronises.
+ * Leading dimensions: ldk any (64-bit indexing); ldlc, ldlct, ldsf, ldsb as contraction operands and outputs (above). */
 int pls_chol_factor(const double *K, int64_t ldk, int64_t m, double jitter, double *Lc, int64_t ldlc, double *LcT,
                     int64_t ldlct, double *Sf, int64_t ldsf, double *Sb, int64_t ldsb, int32_t *info, void *stream);
 
 /* The substitution operators Sf, Sb (see pls_chol_desc) of a factor that is already on the device -- pls_chol_factor
  * ends with this call; parity runs upload the oracle's own LAPACK factor (Lc and its transpose, zeros in the other
  * triangle) and build the operators from it, so that both sides solve with the SAME factor.  Sf and Sb must be zero
- * outside the blocks this call writes (block upper / lower triangle). */
+ * outside the blocks this call writes (block upper / lower triangle).
+ * Leading dimensions: ldlc, ldlct, ldsf, ldsb as contraction operands and outputs (above; the solves that later read Sf,
+ * Sb have the substitution kernel's limit). */
 int pls_chol_build_operators(const double *Lc, int64_t ldlc, const double *LcT, int64_t ldlct, int64_t m, double *Sf,
                              int64_t ldsf, double *Sb, int64_t ldsb, void *stream);
 
 /* V (M x J) = K^-1 U = Lc^-T Lc^-1 U: block forward then backward substitution in ONE launch (a workgroup owns 32
- * columns for the whole solve).  Replaces gpytorch.solve(lhs = k(Z,Z), input = k(Z,Z), rhs = U).  V must not alias U. */
+ * columns for the whole solve).  Replaces gpytorch.solve(lhs = k(Z,Z), input = k(Z,Z), rhs = U).  V must not alias U.
+ * Leading dimensions: ldu, ldv, ldsf, ldsb as operands of the substitution kernel (refused beyond PLS_LD_TRI_SOLVE). */
 int pls_chol_solve(const pls_chol_desc *factor, const double *U, int64_t ldu, int64_t j, double *V, int64_t ldv,
                    void *stream);
 
+/* PLS_OK if the substitution kernel takes a right-hand side and a solution of j >= 1 columns with these leading dimensions
+ * and the descriptor's ldsf, ldsb; else the refusal pls_chol_solve (and every entry that substitutes) would answer with.
+ * The entries' own check; pure host code, nothing is launched and no pointer is dereferenced. */
+int pls_chol_solve_check(const pls_chol_desc *factor, int64_t ldu, int64_t j, int64_t ldv);
+
 /* Linv = Lc^-1 and LinvT = Lc^-T (M x M each, 16-byte aligned, even leading dimensions): the identity pushed through the
- * block forward substitution of pls_chol_solve, column by column the backward-stable solve Lc x = e_c.  Needs Sf / Sb. */
+ * block forward substitution of pls_chol_solve, column by column the backward-stable solve Lc x = e_c.  Needs Sf / Sb.
+ * Leading dimensions: ldlinv, ldlinvt, ldsf, ldsb as operands of the substitution kernel (refused beyond PLS_LD_TRI_SOLVE). */
 int pls_chol_build_inverse(const pls_chol_desc *factor, double *Linv, int64_t ldlinv, double *LinvT, int64_t ldlinvt,
                            void *stream);
 
 /* Y (M x J) = Lc^-1 U: the forward half of pls_chol_solve (one triangular product with LinvT when the descriptor has it
- * and PLS_OPT_SOLVE_MODE is 1, block forward substitution otherwise).  Y must not alias U. */
+ * and PLS_OPT_SOLVE_MODE is 1, block forward substitution otherwise).  Y must not alias U.
+ * Leading dimensions: as pls_gemm_tn's (ldlinvt, ldu operands; ldy output) on the product route, as pls_chol_solve's when it
+ * substitutes. */
 int pls_chol_forward_solve(const pls_chol_desc *factor, const double *U, int64_t ldu, int64_t j, double *Y, int64_t ldy,
                            void *stream);
 
@@ -626,14 +708,16 @@ size_t pls_tri_scratch_bytes(int64_t m, int64_t j);
 
 /* pls_chol_solve with a workspace of pls_chol_solve_workspace_bytes(M, J): with Linv / LinvT in the descriptor (and
  * PLS_OPT_SOLVE_MODE 1) the solve is two triangular products, Lc^-1 U into the workspace and Lc^-T of that into V; a
- * narrow J-shard then uses every CU (M = 1024, J = 1024: 32 workgroups of the substitution kernel on 256 CUs). */
+ * narrow J-shard then uses every CU (M = 1024, J = 1024: 32 workgroups of the substitution kernel on 256 CUs).
+ * Leading dimensions: as pls_gemm_tn's (ldlinv, ldlinvt, ldu operands; ldv output) on the product route, as pls_chol_solve's
+ * when it substitutes. */
 size_t pls_chol_solve_workspace_bytes(int64_t m, int64_t j);
 int pls_chol_solve_ws(const pls_chol_desc *factor, const double *U, int64_t ldu, int64_t j, double *V, int64_t ldv,
                       void *workspace, size_t workspace_bytes, void *stream);
 
 /* out (M x J) = Lc X with the TRANSPOSED factor LcT (upper) as the k-major operand; only k <= row is contracted.
  * Colours standard normals: e = Lc xi ~ N(0, k(Z,Z)) (replaces sample_multivariate_normal's Q sqrt(Lambda) xi,
- * samplers.py:37-44, same law). */
+ * samplers.py:37-44, same law).  Leading dimensions: ldlct, ldx as contraction operands, ldo as a contraction output. */
 int pls_tri_multiply(const double *LcT, int64_t ldlct, int64_t m, const double *X, int64_t ldx, int64_t j, double *out,
                      int64_t ldo, void *stream);
 
@@ -953,12 +1037,14 @@ int pls_onb_build_gaussian(const pls_onb_desc *basis, const double *y, double *B
                            void *stream);
 
 /* F(N x J) = A^T U.  Replaces OrthonormalBasis.calculate_untransformed_train_prediction_samples
- * (orthonormal.py:98-108). */
+ * (orthonormal.py:98-108).  Leading dimensions: lda, ldu as contraction operands, ldf as a contraction output (see
+ * "Leading dimensions" above). */
 int pls_onb_forward(const pls_onb_desc *basis, const double *U, int64_t ldu, int64_t j, double *F, int64_t ldf,
                     void *stream);
 
 /* dU(Mk x J) = -eta * A G - eta * diag(1/lam) U + sqrt(2 eta) * xi.
- * Replaces OrthonormalBasis._calculate_particle_update (orthonormal.py:128-159). */
+ * Replaces OrthonormalBasis._calculate_particle_update (orthonormal.py:128-159).
+ * Leading dimensions: ldat, ldg as contraction operands; ldu, lddu any. */
 int pls_onb_particle_update(const pls_onb_desc *basis, const double *U, int64_t ldu, const double *G, int64_t ldg,
                             int64_t j, double eta, const pls_noise_desc *noise, double *dU, int64_t lddu,
                             void *stream);
@@ -980,7 +1066,10 @@ int pls_onb_particle_update(const pls_onb_desc *basis, const double *U, int64_t 
  * route the call may take: for a basis of at most 128 functions it is the larger of the general route's layout for chunks of
  * n_chunk rows and the one-launch step's (its row slabs, and its counters where the caller brings none).  A smaller workspace
  * is not refused while it holds the layout of a route that applies -- the one-launch step first, else the general route in
- * chunks of at least min(n, 128) rows -- and PLS_ERR_WORKSPACE_TOO_SMALL means that it holds neither. */
+ * chunks of at least min(n, 128) rows -- and PLS_ERR_WORKSPACE_TOO_SMALL means that it holds neither.
+ * Leading dimensions (this and every other pls_onb_* / pls_ipb_* step, update and energy entry): the descriptor's matrices and
+ * the particles are contraction operands; ldo, ldxi any; the fused small-rank kernels and the solve-and-noise launch are routed
+ * around their limits; the solves follow pls_chol_solve (see "Leading dimensions" above). */
 size_t pls_onb_step_workspace_bytes(const pls_onb_desc *basis, int64_t j, int64_t n_chunk);
 int pls_onb_step(const pls_onb_desc *basis, const pls_cost_desc *cost, const double *y, double *U, int64_t ldu,
                  int64_t j, double eta, const pls_noise_desc *noise, double *out, int64_t ldo, int32_t out_mode,
@@ -1024,7 +1113,9 @@ int pls_onb_step_blocks(const pls_onb_desc *basis, const pls_cost_desc *cost, co
  * particles of all ranks).  Replaces PLS.calculate_energy_potential -> OrthonormalBasis.calculate_energy_potential
  * (projected_langevin_sampling.py:125-138, orthonormal.py:110-126).
  * Gaussian/identity with basis->B/c set (and force_generic == 0): cost_j = (u_j^T B u_j - 2 c^T u_j + y^T y) / (2 sigma2)
- * from ONE Mk x Mk x J contraction instead of the N x Mk x J one. */
+ * from ONE Mk x Mk x J contraction instead of the N x Mk x J one.
+ * Leading dimensions: ldu, lda, ldat, ldb as contraction operands; ldat beyond 2^23 is ROUTED from the fused small-rank
+ * kernel to the contractions (above). */
 size_t pls_onb_energy_workspace_bytes(const pls_onb_desc *basis, int64_t j, int64_t n_chunk);
 int pls_onb_energy(const pls_onb_desc *basis, const pls_cost_desc *cost, const double *y, const double *U,
                    int64_t ldu, int64_t j, double *e, int32_t force_generic, void *workspace, size_t workspace_bytes,
@@ -1040,7 +1131,9 @@ int pls_onb_prior_energy(const pls_onb_desc *basis, const double *U, int64_t ldu
  * Inducing-point basis: step (setup = pls_kernel_gram + pls_chol_factor)
  * ------------------------------------------------------------------------------------------- */
 
-/* F = Kxz k(Z,Z)^-1 U (inducing_point.py:81-93). workspace: m*j doubles. */
+/* F = Kxz k(Z,Z)^-1 U (inducing_point.py:81-93). workspace: m*j doubles.
+ * Leading dimensions: ldu as the solve's right-hand side (a contraction operand with the inverse factor, the substitution
+ * kernel's limit without it), ldkzx as a contraction operand, ldf as a contraction output (above). */
 int pls_ipb_forward(const pls_ipb_desc *basis, const double *U, int64_t ldu, int64_t j, double *F, int64_t ldf,
                     void *workspace, size_t workspace_bytes, void *stream);
 
@@ -1061,6 +1154,12 @@ size_t pls_ipb_step_workspace_bytes(const pls_ipb_desc *basis, int64_t j, int64_
 int pls_ipb_step(const pls_ipb_desc *basis, const pls_cost_desc *cost, const double *y, double *U, int64_t ldu,
                  int64_t j, double eta, const pls_noise_desc *noise, double *out, int64_t ldo, int32_t out_mode,
                  int32_t force_generic, double *energy_in, void *workspace, size_t workspace_bytes, void *stream);
+
+/* 1 if the two-launch route of pls_ipb_step would solve and colour the noise in the launch of csrc/ipb_prep.h for this
+ * descriptor under the calling thread's options (philox != 0: Philox noise, which LcT colours), 0 if it takes the separate
+ * solve and noise launches; the step's own predicate, nothing is launched.  Leading dimensions: 0 when ldlinv, ldlinvt
+ * (or, with philox, ldlct) exceeds pls_ld_limit(PLS_LD_IPB_PREP, m, 1). */
+int pls_ipb_prep_applies(const pls_ipb_desc *basis, int32_t philox);
 
 /* pls_ipb_step with one step size PER COLUMN BLOCK (pls_block_desc): the batched step-size search. */
 int pls_ipb_step_blocks(const pls_ipb_desc *basis, const pls_cost_desc *cost, const double *y, double *U, int64_t ldu,

@@ -172,6 +172,10 @@ SIGNATURES = {
     "pls_timeline_end": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_int32), _I32, C.POINTER(C.c_int32)]),
     "pls_kernel_gram": (C.c_int, [_I32, _P, _I64, _P, _I64, _I64, _P, _D, _P, _I64, _P]),
     "pls_gemm_tn": (C.c_int, [_P, _I64, _P, _I64, _P, _I64, _I64, _I64, _I64, _D, _D, _P]),
+    "pls_gemm_tn_route": (C.c_int, [_P, _I64, _P, _I64, _I64, _I64, _I64, _I64, C.POINTER(C.c_int32)]),
+    "pls_ld_limit": (C.c_int64, [_I32, _I64, _I64]),
+    "pls_small_rank_route": (C.c_int, [_P, _I64, _I64, _I64, _P, _I64]),
+    "pls_chol_solve_check": (C.c_int, [_CHD, _I64, _I64, _I64]),
     "pls_cost_derivative": (C.c_int, [_CD, _P, _I64, _P, _I64, _I64, _P, _I64, _P]),
     "pls_cost_value_workspace_bytes": (_SZ, [_I64, _I64]),
     "pls_cost_value": (C.c_int, [_CD, _P, _I64, _P, _I64, _I64, _P, _P, _SZ, _P]),
@@ -227,6 +231,7 @@ SIGNATURES = {
     "pls_ipb_whitened_energy": (C.c_int, [_ID, _CD, _P, _I64, _I64, _P, _P, _SZ, _P]),
     "pls_ipb_build_whitened_operand": (C.c_int, [_ID, _P, _I64, _P]),
     "pls_ipb_whitened_generic_applies": (C.c_int, [_ID, _P, _I64]),
+    "pls_ipb_prep_applies": (C.c_int, [_ID, _I32]),
     "pls_ipb_whitened_generic_workspace_bytes": (_SZ, [_ID, _I64]),
     "pls_ipb_whitened_generic_step": (C.c_int, [_ID, _CD, _P, _P, _I64, _I64, _D, _BD, _ND, _P, _I64, _I32, _P, _P, _SZ, _P]),
     "pls_onb_step_blocks": (C.c_int, [_OD, _CD, _P, _P, _I64, _I64, _BD, _ND, _P, _I64, _I32, _I32, _P, _P, _SZ, _P]),
@@ -294,6 +299,8 @@ OPT_KG_NOISE_PREGEN = 12
 OPT_SMALL_RANK_STEP = 13
 OPT_IPB_PREP = 14
 OPT_WINOGRAD = 15
+LD_GEMM_TILES, LD_GEMM_KSPLIT, LD_GEMM_DIRECT_STORE, LD_TRI_SOLVE, LD_SMALL_RANK, LD_IPB_PREP = range(6)  # pls_ld_site
+GEMM_ROUTE_NAMES = {0: "tiles_128", 1: "tiles_64", 2: "ksplit_1", 3: "ksplit_2", 4: "row_blocks"}  # pls_gemm_route
 TAG_NAMES = {1: "gemm_store", 2: "gemm_cost_deriv", 3: "gemm_cost_value", 4: "gemm_langevin_gaussian",
              5: "langevin_update", 6: "kernel_gram", 7: "other", 8: "small_rank_drift", 9: "small_rank_value",
              10: "tri_solve", 11: "small_rank_step", 12: "ipb_prep"}

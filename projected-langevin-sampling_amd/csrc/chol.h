@@ -17,4 +17,6 @@ int launch_transpose(const double *in, int64_t ldi, double *out, int64_t ldo, in
 int launch_scale_add_diag(const double *in, int64_t ldi, double alpha, double diag, double *out, int64_t ldo, int64_t m,
                           hipStream_t st);
 int64_t solve_mode();  // pls_set_option(PLS_OPT_SOLVE_MODE), defined in plship.hip
+// largest leading dimension chol_solve_launch accepts for an operand of `cols` columns of a factor of order m
+int64_t strip_max_ld(int64_t m, int64_t cols);
 }  // namespace plship

@@ -548,8 +548,31 @@ int launch_scale_add_diag(const double *in, int64_t ldi, double alpha, double di
 
 static size_t strip_lds_bytes() { return (size_t)4 * TS_TILE * sizeof(double); }
 
+// Largest leading dimension (doubles) the strip kernel addresses in an operand of `cols` columns (strip_max_ld of chol.h).  A
+// tile is TS_RK = 128 rows behind a descriptor of at most 0x7FFFFF00 bytes (clamp_range): the last element of its last row,
+// ((rows - 1) * ld + cols) * 8 bytes in, must lie inside, or the range check hands the MFMAs zeros for the tile's last rows.
+int64_t strip_max_ld(int64_t m, int64_t cols) {
+  const int64_t rows = m < TS_RK ? m : TS_RK;
+  return rows <= 1 ? INT64_MAX : (0x7FFFFF00 / 8 - cols) / (rows - 1);
+}
+
+// PLS_OK if the substitution kernel addresses a right-hand side and a solution of j columns with these leading dimensions
+// and the descriptor's operators, else the refusal that names the leading dimension (what chol_solve_launch starts with)
+static int chol_solve_check(const pls_chol_desc *f, int64_t ldu, int64_t j, int64_t ldv) {
+  const int64_t m = f->m;
+  PLS_REQUIRE(ldu <= strip_max_ld(m, j) && ldv <= strip_max_ld(m, j),
+              "tri_solve: leading dimension ldu=%lld or ldv=%lld is beyond %lld, the largest the substitution kernel addresses "
+              "for m=%lld, j=%lld", (long long)ldu, (long long)ldv, (long long)strip_max_ld(m, j), (long long)m, (long long)j);
+  PLS_REQUIRE(f->ldsf <= strip_max_ld(m, m) && f->ldsb <= strip_max_ld(m, m),
+              "tri_solve: leading dimension ldsf=%lld or ldsb=%lld of the substitution operators is beyond %lld, the largest "
+              "the substitution kernel addresses for m=%lld", (long long)f->ldsf, (long long)f->ldsb,
+              (long long)strip_max_ld(m, m), (long long)m);
+  return PLS_OK;
+}
+
 int chol_solve_launch(const pls_chol_desc *f, const double *U, int64_t ldu, int64_t j, double *V, int64_t ldv,
                       int fwd_only, hipStream_t st) {
+  if (int rc = chol_solve_check(f, ldu, j, ldv)) return rc;
   if (int rc = ensure_lds<tri_solve_strip_kernel>(strip_lds_bytes())) return rc;
   StripArgs a{f->Sf, f->Sb, f->ldsf, f->ldsb, U, ldu, V, ldv, f->m, j};
   {
@@ -661,11 +684,23 @@ int pls_chol_solve(const pls_chol_desc *f, const double *U, int64_t ldu, int64_t
   return chol_solve_launch(f, U, ldu, j, V, ldv, 0, S(stream));
 }
 
+int pls_chol_solve_check(const pls_chol_desc *f, int64_t ldu, int64_t j, int64_t ldv) {
+  PLS_REQUIRE(f && f->Sf && f->Sb && f->m > 0 && f->ldsf >= f->m && f->ldsb >= f->m, "chol_solve_check: bad factor descriptor");
+  PLS_REQUIRE(j >= 1 && ldu >= j && ldv >= j, "chol_solve_check: bad arguments");
+  return chol_solve_check(f, ldu, j, ldv);
+}
+
 int pls_chol_build_inverse(const pls_chol_desc *f, double *Linv, int64_t ldlinv, double *LinvT, int64_t ldlinvt, void *stream) {
   PLS_REQUIRE(f && f->Sf && f->Sb && f->m > 0 && f->ldsf >= f->m && f->ldsb >= f->m, "chol_build_inverse: bad factor descriptor");
   PLS_REQUIRE(Linv && LinvT && Linv != LinvT && ldlinv >= f->m && ldlinvt >= f->m, "chol_build_inverse: bad arguments");
   PLS_REQUIRE(((ldlinv | ldlinvt) & 1) == 0 && ((reinterpret_cast<uintptr_t>(Linv) | reinterpret_cast<uintptr_t>(LinvT)) & 15) == 0,
               "chol_build_inverse: outputs must be 16-byte aligned with even leading dimensions");
+  // (what chol_solve_launch below would refuse, refused before the identity is written)
+  PLS_REQUIRE(ldlinv <= strip_max_ld(f->m, f->m) && ldlinvt <= strip_max_ld(f->m, f->m) && f->ldsf <= strip_max_ld(f->m, f->m) &&
+                  f->ldsb <= strip_max_ld(f->m, f->m),
+              "chol_build_inverse: leading dimension ldlinv=%lld, ldlinvt=%lld, ldsf=%lld or ldsb=%lld is beyond %lld, the largest "
+              "the substitution kernel addresses for m=%lld", (long long)ldlinv, (long long)ldlinvt, (long long)f->ldsf,
+              (long long)f->ldsb, (long long)strip_max_ld(f->m, f->m), (long long)f->m);
   hipStream_t st = S(stream);
   // the identity (in LinvT) as the right-hand side of a forward substitution: column c of Lc^-1 solves Lc x = e_c
   int rc = launch_scale_add_diag(nullptr, 0, 0.0, 1.0, LinvT, ldlinvt, f->m, st);

@@ -12,12 +12,29 @@ extern unsigned long long *g_stamp_buffer;  // diagnostic build only (tools/stam
 // ---------------------------------------------------------------------------------------------------------------
 // GEMM launcher
 // ---------------------------------------------------------------------------------------------------------------
+// Every launcher of a configuration whose k-loop copies by LDS-DMA (the 128 x 128 tiles, their row-block, paired and
+// Winograd-product forms) calls this first, before anything touches the device: operands of lcols / rcols columns whose
+// leading dimension the DMA's 32-bit offsets cannot address (gemm_dma_max_ld) are refused, not contracted with zeros.
+// Operands that are not 16-byte aligned with even leading dimensions go through registers with 64-bit addresses: no limit.
+static inline int gemm_dma_check(const double *L, int64_t ldl, int64_t lcols, const double *R, int64_t ldr, int64_t rcols) {
+  if (!gemm_vec_operands(L, ldl, R, ldr)) return PLS_OK;
+  if (ldl > gemm_dma_max_ld(lcols))
+    return fail(PLS_ERR_INVALID_ARGUMENT, "gemm: leading dimension ldl=%lld of the %lld-column left operand is beyond %lld, the "
+                "largest the 128 x 128 tiles address", (long long)ldl, (long long)lcols, (long long)gemm_dma_max_ld(lcols));
+  if (ldr > gemm_dma_max_ld(rcols))
+    return fail(PLS_ERR_INVALID_ARGUMENT, "gemm: leading dimension ldr=%lld of the %lld-column right operand is beyond %lld, the "
+                "largest the 128 x 128 tiles address", (long long)ldr, (long long)rcols, (long long)gemm_dma_max_ld(rcols));
+  return PLS_OK;
+}
+
 template <int BI, int BJ, int WI, int WJ, class Epi, int MINW = ((BI >= 128) ? 2 : 4)>
 static int launch_gemm_cfg(GemmShape g, const Epi &epi, hipStream_t st) {
   constexpr int BK = 16;  // MINW: waves per SIMD the register allocation must leave room for
   constexpr int NT = (BI / WI) * (BJ / WJ) * 64;
   constexpr size_t lds_bytes = gemm_tile_lds_bytes(BI, BJ, BK);
   constexpr auto kern = gemm_tn_f64_kernel<BI, BJ, WI, WJ, BK, MINW, Epi>;
+  if constexpr (BI == 128 && BJ == 128)  // (gemm_tile's kDma)
+    if (int rc = gemm_dma_check(g.L, g.ldl, g.I, g.R, g.ldr, g.J)) return rc;
   if (int rc = ensure_lds<kern>(lds_bytes)) return rc;
 #ifdef PLS_STAMP
   g.stamps = g_stamp_buffer;

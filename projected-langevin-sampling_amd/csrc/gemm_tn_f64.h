@@ -151,8 +151,10 @@ __device__ __forceinline__ void gemm_tn_mainloop(const GemmShape &g, int64_t i0,
 
   typedef __attribute__((address_space(3))) void *lds_ptr_t;
   // DMA addressing (buffer_load_dwordx4 ... offen lds): a 128-bit buffer descriptor whose base is the wave-uniform
-  // address of the step's first k-row (rebuilt with two scalar adds per step, so any matrix size works), the row
+  // address of the step's first k-row (rebuilt with two scalar adds per step, so any number of k-rows works), the row
   // inside the step as an SGPR offset, and ONE loop-invariant 32-bit lane offset in a VGPR: no VALU in the k-loop.
+  // The last row of a step and the lane's global column must stay inside the descriptor's range: gemm_dma_max_ld below,
+  // which every launcher of a DMA configuration checks on the host (gemm_dma_check, gemm_launch.h).
   static_assert(!DMA || (BI == 128 && BJ == 128), "one wave-instruction must cover exactly one k-row");
   const int wrow = __builtin_amdgcn_readfirstlane(lrow);  // = wave index: uniform
   const int loff = (int)((l0 ? lcg : 0) * 8), roff = (int)((r0 ? rcg : 0) * 8);
@@ -422,6 +424,18 @@ struct epi_has_pregen<E, std::void_t<decltype(&E::pregen_on)>> : std::true_type 
 
 // largest leading dimension (doubles) the direct epilogue addresses with 32-bit byte offsets (67 rows * ld * 8 < 2^31)
 constexpr int64_t kDirectMaxLd = (int64_t)1 << 21;
+
+// largest leading dimension (doubles) of an operand of `cols` columns that the LDS-DMA k-loop addresses (gemm_tn_mainloop,
+// DMA): the 16 bytes of the last column pair in row 15 of a k-step, (15 * ld + cols) * 8 bytes from the step's first row,
+// must end inside the 0x7FFFFFF0-byte descriptor; beyond, the range check would hand the MFMAs zeros for real data.  (An odd
+// column count rounds up: the last lane's pair reaches one column further, and a pair that ends out of range reads as zero
+// in both halves.)
+constexpr int64_t kDmaRange = 0x7FFFFFF0;
+constexpr int64_t gemm_dma_max_ld(int64_t cols) { return (kDmaRange - 8 * (cols + (cols & 1))) / (15 * 8); }
+// the operands the k-loop reads with 16-byte loads (gemm_tile's `vec`): the only ones the 128 x 128 tiles copy by DMA
+inline bool gemm_vec_operands(const double *L, int64_t ldl, const double *R, int64_t ldr) {
+  return ((ldl | ldr) & 1) == 0 && ((reinterpret_cast<uintptr_t>(L) | reinterpret_cast<uintptr_t>(R)) & 15) == 0;
+}
 
 // One output tile (tile_i, tile_j) of the contraction: k-loop + epilogue.
 template <int BI, int BJ, int WI, int WJ, int BK, class Epilogue>

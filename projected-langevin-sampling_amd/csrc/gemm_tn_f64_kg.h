@@ -27,6 +27,11 @@
 
 namespace plship {
 
+// Leading dimensions (doubles) at and above which pick_gemm_cfg (plship.hip) hands a shape to the tile kernels of
+// gemm_tn_f64.h instead: kg_contract's 32-bit DMA offsets reach (248 * ld + 8 * cols) bytes (voffl + 15 * pairl), which
+// stays inside the 0x7FFFFFF0-byte descriptor up to about 8.6e6; 2^22 keeps a factor of two in hand.
+constexpr int64_t kKsplitMaxLd = (int64_t)1 << 22;
+
 template <int KG>
 struct KgGeom {
   static constexpr int NW = 4 * KG, NT = 64 * NW, SROWS = 16 * KG;

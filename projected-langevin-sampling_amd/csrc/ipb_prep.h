@@ -46,6 +46,12 @@ struct IpbPrepP {
   NoiseP nz;
 };
 
+// Largest leading dimension of a factor matrix (LinvT, Linv, LcT) of order m the kernel addresses: its descriptor spans the
+// matrix, ((m - 1) * ld + m) * 8 bytes, and a dead fragment is parked at offset 0x7FFFFFF0, which reads as zero only while
+// it lies beyond that span (and the live offsets stay below 2^31).  The step falls back to its separate solve and noise
+// launches beyond it (ipb_one_launch_route, plship.hip).
+inline int64_t ipb_prep_max_ld(int64_t m) { return m <= 1 ? INT64_MAX : (0x7FFFFFF0 / 8 - m) / (m - 1); }
+
 int launch_ipb_prep(const IpbPrepP &p, hipStream_t st);
 
 }  // namespace plship

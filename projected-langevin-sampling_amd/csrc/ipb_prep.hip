@@ -144,6 +144,11 @@ int launch_ipb_prep(const IpbPrepP &p, hipStream_t st) {
     return fail(PLS_ERR_INVALID_ARGUMENT, "ipb_prep: NULL operand");
   if (p.ldlinvt < p.m || p.ldlinv < p.m || (p.draw && p.ldlct < p.m) || p.ldu < p.j || p.ldv < p.j || (p.draw && p.lde < p.j))
     return fail(PLS_ERR_INVALID_ARGUMENT, "ipb_prep: leading dimension too small");
+  const int64_t max_ld = ipb_prep_max_ld(p.m);
+  if (p.ldlinvt > max_ld || p.ldlinv > max_ld || (p.draw && p.ldlct > max_ld))
+    return fail(PLS_ERR_INVALID_ARGUMENT, "ipb_prep: a factor's leading dimension (ldlinvt=%lld ldlinv=%lld ldlct=%lld) is beyond "
+                "%lld, the largest the kernel addresses for m=%d", (long long)p.ldlinvt, (long long)p.ldlinv,
+                (long long)p.ldlct, (long long)max_ld, p.m);
   if (p.j <= 0) return PLS_OK;
   LaunchScope scope(PLS_TAG_IPB_PREP, st);
   const dim3 grid((unsigned)cdiv(p.j, IPB_PREP_COLS), p.draw ? 2u : 1u);

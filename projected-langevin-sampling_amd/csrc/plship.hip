@@ -565,7 +565,7 @@ static GemmCfg pick_gemm_cfg(const double *L, int64_t ldl, const double *R, int6
   const int64_t mode = g_ksplit_mode.load();
   const int64_t tiles128 = cdiv(I, 128) * cdiv(J, 128) * nsplit;
   const bool aligned = ((ldl | ldr) & 1) == 0 && ((reinterpret_cast<uintptr_t>(L) | reinterpret_cast<uintptr_t>(R)) & 15) == 0 &&
-                       ldl < ((int64_t)1 << 22) && ldr < ((int64_t)1 << 22);
+                       ldl < kKsplitMaxLd && ldr < kKsplitMaxLd;
   if (mode != 0 && aligned && nsplit == 1 && K >= 1) {
     if (mode == 2) return CFG_KG2;
     if (mode == 3) return CFG_KG1;
@@ -666,6 +666,7 @@ static int launch_gemm_rows(const double *L, int64_t ldl, const double *R, int64
                             const EpiStore &e, hipStream_t st, int64_t kchunk) {
   GemmShape g{L, ldl, R, ldr, I, J, K, 0, 0, kchunk, 0};
   constexpr size_t lds_bytes = gemm_tile_lds_bytes(128, 128, 16);
+  if (int rc = gemm_dma_check(L, ldl, I, R, ldr, J)) return rc;
   if (int rc = ensure_lds<gemm_tn_f64_rows_kernel>(lds_bytes)) return rc;
   g.nti = (int)cdiv(I, 128);
   g.ntj = (int)cdiv(J, 128);
@@ -894,6 +895,8 @@ __global__ __launch_bounds__(256, 2) void wino_products_kernel(GemmShape g, EpiS
 static int launch_wino_products(const WinoProducts &t, int64_t mh, int64_t jh, int64_t K, int64_t kchunk, double *P, int64_t slab,
                                 double beta, hipStream_t st) {
   constexpr size_t lds_bytes = gemm_tile_lds_bytes(128, 128, 16);
+  for (int p = 0; p < 7; ++p)
+    if (int rc = gemm_dma_check(t.L[p], t.ldl[p], mh, t.R[p], jh, jh)) return rc;
   if (int rc = ensure_lds<wino_products_kernel>(lds_bytes)) return rc;
   GemmShape g{nullptr, 0, nullptr, jh, mh, jh, K, 0, 0, kchunk, 0};
   g.nti = (int)cdiv(mh, 128);
@@ -1668,7 +1671,8 @@ static thread_local RouteOption g_solve_mode{1};  // pls_set_option(PLS_OPT_SOLV
 int64_t solve_mode() { return g_solve_mode.load(); }
 
 static bool small_rank_ok(const double *Lb, int64_t ldlb, int64_t kdim) {
-  return kdim >= 1 && kdim <= g_small_rank_max.load() && (ldlb & 1) == 0 && (reinterpret_cast<uintptr_t>(Lb) & 15) == 0;
+  return kdim >= 1 && kdim <= g_small_rank_max.load() && (ldlb & 1) == 0 && (reinterpret_cast<uintptr_t>(Lb) & 15) == 0 &&
+         ldlb <= kSmallRankMaxLd;
 }
 
 // (the launchers of the fused small-rank kernels live in their own translation units: small_rank_launch.h)
@@ -2147,6 +2151,39 @@ int pls_gemm_tn(const double *L, int64_t ldl, const double *R, int64_t ldr, doub
   PLS_REQUIRE(ldl >= I && ldr >= J && ldc >= J, "gemm_tn: leading dimension too small (ldl=%lld I=%lld ldr=%lld J=%lld ldc=%lld)",
               (long long)ldl, (long long)I, (long long)ldr, (long long)J, (long long)ldc);
   return gemm_tn_ex(L, ldl, R, ldr, C, ldc, I, J, K, alpha, beta, 0, S(stream));
+}
+
+// The decisions of gemm_tn_ex (tri = 0) for this call, by the predicates its launchers use; nothing is launched.
+int pls_gemm_tn_route(const double *L, int64_t ldl, const double *R, int64_t ldr, int64_t ldc, int64_t I, int64_t J, int64_t K,
+                      int32_t *direct_store) {
+  if (!(I >= 1 && J >= 1 && K >= 0)) return -fail(PLS_ERR_INVALID_ARGUMENT, "gemm_tn_route: bad sizes");
+  if (!(ldl >= I && ldr >= J && ldc >= J)) return -fail(PLS_ERR_INVALID_ARGUMENT, "gemm_tn_route: leading dimension too small");
+  int route;
+  if (gemm_rows_ok(L, ldl, R, ldr, I, J, K, ldc, 1)) {
+    route = PLS_GEMM_ROUTE_ROW_BLOCKS;
+  } else {
+    const GemmCfg cfg = pick_gemm_cfg(L, ldl, R, ldr, I, J, K, 1);
+    route = cfg == CFG_BIG ? PLS_GEMM_ROUTE_TILES_128 : cfg == CFG_SMALL ? PLS_GEMM_ROUTE_TILES_64
+            : cfg == CFG_KG1 ? PLS_GEMM_ROUTE_KSPLIT_1 : PLS_GEMM_ROUTE_KSPLIT_2;
+  }
+  if (route == PLS_GEMM_ROUTE_ROW_BLOCKS || route == PLS_GEMM_ROUTE_TILES_128)
+    if (int rc = gemm_dma_check(L, ldl, I, R, ldr, J)) return -rc;
+  // (the 64 x 64 tiles and the k-split kernels store interior tiles from registers too: gemm_tile, gemm_tn_f64_kg.h)
+  if (direct_store) *direct_store = ldc < kDirectMaxLd ? 1 : 0;
+  return route;
+}
+
+int64_t pls_ld_limit(int32_t site, int64_t rows, int64_t cols) {
+  if (rows < 1 || cols < 1) return -1;
+  switch (site) {
+    case PLS_LD_GEMM_TILES: return gemm_dma_max_ld(cols);
+    case PLS_LD_GEMM_KSPLIT: return kKsplitMaxLd - 1;
+    case PLS_LD_GEMM_DIRECT_STORE: return kDirectMaxLd - 1;
+    case PLS_LD_TRI_SOLVE: return strip_max_ld(rows, cols);
+    case PLS_LD_SMALL_RANK: return kSmallRankMaxLd;
+    case PLS_LD_IPB_PREP: return ipb_prep_max_ld(rows);
+    default: return -1;
+  }
 }
 
 int pls_block_means(const double *e, int64_t j, int64_t block_cols, double *out, void *stream) {
@@ -2948,15 +2985,23 @@ static int ipb_fast_route(const pls_ipb_desc *basis, const StepCall &c, const Dr
 // launch-bound problems (the reference's curve experiments build this basis with 10-100 inducing points and 50-100
 // particles): the one-launch small-rank step after the solve and the coloured noise -- and those two in one launch of
 // their own when the descriptor carries the inverse factor (csrc/ipb_prep.h): 2 launches per step instead of 8
+// The solve-and-noise launch takes the call: the option, the inverse factor, and factor matrices no wider than the launch
+// addresses (ipb_prep_max_ld; wider ones go to the separate solve and noise launches).  `draw`: Philox noise, coloured by LcT.
+static bool ipb_prep_ok(const pls_ipb_desc *basis, int draw) {
+  const int64_t prep_ld = ipb_prep_max_ld(basis->m);
+  return g_ipb_prep.load() != 0 && basis->m <= IPB_PREP_MAX_M && basis->Linv && basis->LinvT && solve_mode() != 0 &&
+         !(g_ipb_explicit_inverse.load() != 0 && basis->W) && basis->ldlinv <= prep_ld && basis->ldlinvt <= prep_ld &&
+         !(draw && basis->LcT && basis->ldlct > prep_ld);
+}
+
 static int ipb_one_launch_route(const pls_ipb_desc *basis, const StepCall &c, const DriftLayout &L, const SrStepLayout &sl) {
   char *w = static_cast<char *>(c.workspace);
   double *V = reinterpret_cast<double *>(w), *xi = reinterpret_cast<double *>(w + L.mj);
   double *e = reinterpret_cast<double *>(w + 2 * L.mj);
   NoiseP nz = c.noisep();
   int rc;
-  if (g_ipb_prep.load() != 0 && basis->m <= IPB_PREP_MAX_M && basis->Linv && basis->LinvT && solve_mode() != 0 &&
-      !(g_ipb_explicit_inverse.load() != 0 && basis->W)) {
-    const int draw = nz.kind == PLS_NOISE_PHILOX ? 1 : 0;
+  const int draw = nz.kind == PLS_NOISE_PHILOX ? 1 : 0;
+  if (ipb_prep_ok(basis, draw)) {
     if (draw && !basis->LcT) return fail(PLS_ERR_INVALID_ARGUMENT, "ipb: Philox noise needs the Cholesky factor LcT");
     const IpbPrepP pp{basis->LinvT, basis->ldlinvt, basis->Linv, basis->ldlinv, basis->LcT, basis->ldlct, c.U, c.ldu, V, c.j, e,
                       c.j, (int)basis->m, c.j, draw, nz};
@@ -3244,6 +3289,18 @@ int pls_ipb_whitened_generic_applies(const pls_ipb_desc *basis, const double *y,
   return ipb_whitened_generic_ok(basis, y, j) ? 1 : 0;
 }
 
+// The step entries' own predicates for the fused small-rank kernels and the solve-and-noise launch; nothing is launched.
+int pls_small_rank_route(const double *Lb, int64_t ldlb, int64_t kdim, int64_t n, const double *y, int64_t j) {
+  if (!Lb || kdim < 1 || n < 1 || j < 1 || ldlb < kdim) return -fail(PLS_ERR_INVALID_ARGUMENT, "small_rank_route: bad arguments");
+  return (small_rank_ok(Lb, ldlb, kdim) ? PLS_SMALL_RANK_SLABS : 0) |
+         (sr_step_route_for(Lb, ldlb, kdim, n, y, j) ? PLS_SMALL_RANK_ONE_LAUNCH : 0);
+}
+
+int pls_ipb_prep_applies(const pls_ipb_desc *basis, int32_t philox) {
+  if (!basis || validate_ipb(basis) != PLS_OK) return 0;
+  return ipb_prep_ok(basis, philox ? 1 : 0) ? 1 : 0;
+}
+
 size_t pls_ipb_whitened_generic_workspace_bytes(const pls_ipb_desc *basis, int64_t j) {
   if (!basis || j <= 0) return 0;
   return sr_step_query_bytes(0, basis->m, basis->n + basis->m, j);
@@ -3259,6 +3316,10 @@ int pls_ipb_whitened_generic_step(const pls_ipb_desc *basis, const pls_cost_desc
   if (!rc) rc = validate_step_call("ipb_whitened_generic_step", c, true);
   if (rc) return rc;
   if (j == 0) return PLS_OK;
+  // (this entry has no other kernel to hand a wide operand to: pls_ipb_whitened_generic_applies says 0, the caller stays in
+  // the original coordinates)
+  PLS_REQUIRE(!basis->Awa || basis->ldawa <= kSmallRankMaxLd, "ipb_whitened_generic_step: leading dimension ldawa=%lld is beyond "
+              "%lld, the largest the one-launch step addresses", (long long)basis->ldawa, (long long)kSmallRankMaxLd);
   if (!ipb_whitened_generic_ok(basis, y, j))
     return fail(PLS_ERR_INVALID_ARGUMENT, "ipb_whitened_generic_step: needs pls_ipb_desc.Awa (pls_ipb_build_whitened_operand), at most 128 "
                 "inducing points, 16-byte aligned targets and a launch-bound problem (pls_ipb_whitened_generic_applies)");

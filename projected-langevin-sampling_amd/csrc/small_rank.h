@@ -50,6 +50,12 @@ struct SmallRankP {
 // reports the energy of its input particles)
 constexpr int SR_MODE_DRIFT = 0, SR_MODE_VALUE = 1, SR_MODE_DRIFT_VALUE = 2;
 constexpr int SR_ROWS = 32;  // rows of Lb per LDS tile (two 16-row MFMA blocks)
+// Largest leading dimension of Lb the fused small-rank kernels address.  A tile of this kernel is SR_ROWS rows behind a
+// descriptor of at most 0x7FFFFF00 bytes, lane offsets up to (31 * ldlb + 128) * 8; the one-launch step (small_rank_step.h)
+// reaches (15 * ldlb + 128) * 8 behind 0x7FFFFFF0.  2^23 satisfies both: (31 * 2^23 + 128) * 8 = 0x7C000400.  Beyond it the
+// routes fall back to the GEMM kernels (small_rank_ok, plship.hip).
+constexpr int64_t kSmallRankMaxLd = (int64_t)1 << 23;
+static_assert((31 * kSmallRankMaxLd + 128) * 8 <= 0x7FFFFF00, "small-rank tile beyond its descriptor");
 
 template <int KB>
 constexpr int sr_stride() { return 16 * KB + 2; }  // doubles per LDS row: +2 keeps both read patterns conflict-free

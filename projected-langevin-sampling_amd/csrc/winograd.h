@@ -192,6 +192,8 @@ static int launch_gemm_paired(const double *Lf, int64_t ldlf, int64_t pair_i, co
                               int64_t rows, int64_t K, const Epi &epi, hipStream_t st) {
   constexpr size_t lds_bytes = gemm_tile_lds_bytes(128, 128, 16);
   constexpr auto kern = gemm_paired_kernel<Epi>;
+  // (the second halves sit pair_i / pair_j columns into the rows: the DMA's lane offsets carry them)
+  if (int rc = gemm_dma_check(Lf, ldlf, pair_i + rows, V, ldv, 2 * pair_j)) return rc;
   if (int rc = ensure_lds<kern>(lds_bytes)) return rc;
   GemmShape g{Lf, ldlf, V, ldv, rows, pair_j, K, 0, 0, 0, 0};
   g.pair_i = pair_i;
