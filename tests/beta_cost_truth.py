@@ -366,3 +366,26 @@ def measure_reference():
 def reference_errors():
     with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "beta_cost_reference_errors.json")) as fh:
         return json.load(fh)
+
+
+# ---- what the family batteries take (tests/test_gpu_family_cost_{train,elements}.py) ----------------------------------------------
+CHECKPOINT = ("precision", 99.0)  # the attribute a checkpoint carries, and the value the model it is loaded into was built with
+VALUE_TRUTH_FINITE = True  # the column-sum test asserts it before it sums
+check_elements = None  # nothing beyond both derivative modes being the same bits
+TRAIN_PRECISION = 8.0
+
+
+def train_y(pr, n):
+    """proportions scattered around sigmoid(1.5 f*) with precision phi"""
+    mu = torch.sigmoid(1.5 * pr["fstar"])
+    torch.manual_seed(11 + n)
+    return torch.distributions.Beta(TRAIN_PRECISION * mu, TRAIN_PRECISION * (1 - mu)).sample().clamp(1e-6, 1 - 1e-6)
+
+
+def train_costs(P, y, precision=TRAIN_PRECISION):
+    gc = P.costs.BetaCost(y, P.links.SigmoidLinkFunction(), precision)
+    return BetaHostCost(gc.y_device().cpu(), SigmoidLink(), precision), gc  # (the very logits the library gets)
+
+
+def check_trained_cost(gc):
+    assert gc.precision == TRAIN_PRECISION

@@ -249,3 +249,27 @@ def measure_reference():
 def reference_errors():
     with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "count_cost_reference_errors.json")) as fh:
         return json.load(fh)
+
+
+# ---- what the family batteries take (tests/test_gpu_family_cost_{train,elements}.py) ----------------------------------------------
+CHECKPOINT = ("dispersion", 99.0)  # the attribute a checkpoint carries, and the value the model it is loaded into was built with
+VALUE_TRUTH_FINITE = False  # (the column-sum test asserts nothing about the truth's values first)
+check_elements = None  # nothing beyond both derivative modes being the same bits
+TRAIN_DISPERSION = 3.0
+
+
+def train_y(pr, n):
+    """over-dispersed counts around exp(1 + f*): a gamma-mixed Poisson with shape r"""
+    rate = torch.exp(1.0 + pr["fstar"])
+    mix = torch.distributions.Gamma(torch.tensor(TRAIN_DISPERSION, dtype=torch.float64), torch.tensor(TRAIN_DISPERSION, dtype=torch.float64))
+    torch.manual_seed(11 + n)
+    return torch.poisson(rate * mix.sample((n,)))
+
+
+def train_costs(P, y, dispersion=TRAIN_DISPERSION):
+    return (NegativeBinomialHostCost(y, ExpLink(), dispersion),
+            P.costs.NegativeBinomialCost(y, P.links.ExponentialLinkFunction(), dispersion))
+
+
+def check_trained_cost(gc):
+    assert gc.dispersion == TRAIN_DISPERSION

@@ -217,3 +217,31 @@ def measure_reference():
 def reference_errors():
     with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "gamma_cost_reference_errors.json")) as fh:
         return json.load(fh)
+
+
+# ---- what the family batteries take (tests/test_gpu_family_cost_{train,elements}.py) ----------------------------------------------
+CHECKPOINT = ("concentration", 0.75)  # the attribute a checkpoint carries, and the value the model it is loaded into was built with
+VALUE_TRUTH_FINITE = False  # (above the exponential's range the value is +inf)
+TRAIN_CONCENTRATION = 4.0
+
+
+def train_y(pr, n):
+    """Gamma variates of shape TRAIN_CONCENTRATION around the mean exp(fstar)"""
+    g = torch.Generator().manual_seed(11 + n)
+    unit = torch._standard_gamma(torch.full((n,), TRAIN_CONCENTRATION, dtype=torch.float64), generator=g) / TRAIN_CONCENTRATION
+    return torch.exp(pr["fstar"].reshape(-1).double()) * unit.clamp_min(1e-300)
+
+
+def train_costs(P, y, concentration=TRAIN_CONCENTRATION):
+    y = y.double()
+    return (GammaHostCost(torch.log(y), ExpLink(), concentration),
+            P.costs.GammaCost(y, P.links.ExponentialLinkFunction(), concentration=concentration))
+
+
+def check_trained_cost(gc):
+    assert bool((gc.y_train > 0).all()) and torch.equal(gc.y_device().cpu(), torch.log(gc.y_train.double()))
+
+
+def check_elements(got, pset):
+    with np.errstate(invalid="ignore"):
+        assert all(not (got["deriv_reference", strided] > PARAMS[pset]).any() for strided in (False, True)), "the derivative exceeds k"

@@ -261,3 +261,30 @@ def measure_reference():
 def reference_errors():
     with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ordinal_cost_reference_errors.json")) as fh:
         return json.load(fh)
+
+
+# ---- what the family batteries take (tests/test_gpu_family_cost_{train,elements}.py) ----------------------------------------------
+CHECKPOINT = ("cutpoints", [-3.0, 0.125, 7.0])  # the attribute a checkpoint carries, and the value the model it is loaded into was built with
+VALUE_TRUTH_FINITE = True  # the column-sum test asserts it before it sums
+TRAIN_THRESHOLDS = [-1.5, -0.25, 1.0]  # four grades cut from the noisy latent
+
+
+def train_y(pr, n):
+    g = torch.Generator().manual_seed(11 + n)
+    uniform = torch.rand(n, generator=g, dtype=torch.float64).clamp(1e-12, 1 - 1e-12)
+    latent = 1.5 * pr["fstar"].reshape(-1).double() + torch.log(uniform) - torch.log1p(-uniform)  # logistic noise
+    return torch.bucketize(latent, torch.tensor(TRAIN_THRESHOLDS, dtype=torch.float64)).double()
+
+
+def train_costs(P, y, cutpoints=None):
+    if cutpoints is None:
+        cutpoints = P.costs.OrdinalCost.cutpoints_from_labels(y, num_categories=len(TRAIN_THRESHOLDS) + 1)
+    return OrdinalHostCost(y, O.IdentityLink(), cutpoints), P.costs.OrdinalCost(y, P.links.IdentityLinkFunction(), cutpoints=cutpoints)
+
+
+def check_trained_cost(gc):
+    assert len(set(gc.y_train.tolist())) == len(TRAIN_THRESHOLDS) + 1
+
+
+def check_elements(got, pset):
+    assert all((np.abs(got["deriv_reference", strided]) <= 1).all() for strided in (False, True)), "the derivative leaves [-1, 1]"

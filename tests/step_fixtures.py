@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+from cost_families import truth_module
 from oracle import pls_oracle as O
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -535,21 +536,6 @@ WINO_OUTSIDE = [(496, 16384, 2048), (512, 16380, 2048), (512, 16384, 1920), (512
 # and without noise (or with injected zeros) out[k, j] = -eta 2^p_k G[n_k, j] with eta a power of two: not one rounding after
 # cost_deriv.  A probe row of a step therefore shows G[n_k, :] bit for bit, on any route, in any tile position.
 SELECTOR_PLACEMENTS = ["head", "half", "tail", "spread"]
-
-
-def truth_module(pair):
-    """The truth module that describes the pair's family (a pair name occurs in one of them only): its grid, mpmath truth,
-    recorded errors and bound, host and library cost, and what the selector problems take from it (SELECTOR_RANGE,
-    OWN_CARRIER_STREAM, MODES_AGREE)."""
-    import beta_cost_truth
-    import cost_truth
-    import count_cost_truth
-    import ordinal_cost_truth
-
-    for module in (cost_truth, count_cost_truth, beta_cost_truth, ordinal_cost_truth):
-        if pair in module.PAIRS:
-            return module
-    raise KeyError(f"no truth module describes the pair {pair}")
 
 
 def selector_values(pair, pset="a"):

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import cost_truth as T
+from cost_families import family_cells, truth_module
 
 
 @pytest.mark.parametrize("pair,pset", T.cells())
@@ -141,16 +142,9 @@ def test_bound_rule():
 
 
 # ---- the selector problems of tests/step_fixtures.py: their exactness, proved on the host ---------------------------------------
-# the pairs of the other three truth modules (count, Beta, ordinal), each with its parameter sets "a" and "b"
-FAMILY_CELLS = [(pair, pset) for pair in ("negative_binomial/exp", "gaussian/exp", "beta/sigmoid", "beta/probit", "ordinal/identity")
-                for pset in "ab"]
-
-
 def _host_g(ex):
     """G on the problem's F by the host cost of the pair's truth module (the oracle's, or the family's restatement)"""
     import torch
-
-    from step_fixtures import truth_module
 
     prev = torch.get_default_dtype()
     torch.set_default_dtype(torch.float64)
@@ -195,10 +189,10 @@ def test_selector_problem_shows_g_bit_for_bit(pair, mk, n, j, placement):
     _selector_problem_shows_g(pair, "a", mk, n, j, placement)
 
 
-@pytest.mark.parametrize("pair,pset", FAMILY_CELLS)
+@pytest.mark.parametrize("pair,pset", family_cells())
 @pytest.mark.parametrize("mk,n,j,placement", [(10, 100, 64, "head"), (17, 333, 37, "spread"), (120, 1530, 200, "tail"), (12, 40, 5, "spread")])
 def test_selector_problem_shows_g_bit_for_bit_in_every_family(pair, pset, mk, n, j, placement):
-    """the same proof for the pairs of the count, Beta and ordinal truth modules, with G each module's host cost's"""
+    """the same proof for the pairs of every family's truth module (tests/cost_families.py), with G each module's host cost's"""
     _selector_problem_shows_g(pair, pset, mk, n, j, placement)
 
 
@@ -245,6 +239,6 @@ def test_selector_ipb_problem_shows_g_bit_for_bit(pair, m, n, j, placement):
     _selector_ipb_problem_shows_g(pair, "a", m, n, j, placement)
 
 
-@pytest.mark.parametrize("pair,pset", FAMILY_CELLS)
+@pytest.mark.parametrize("pair,pset", family_cells())
 def test_selector_ipb_problem_shows_g_bit_for_bit_in_every_family(pair, pset):
     _selector_ipb_problem_shows_g(pair, pset, 17, 333, 37, "tail")

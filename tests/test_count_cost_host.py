@@ -107,7 +107,7 @@ def test_checkpoint_round_trips_the_dispersion(tmp_path):
     state = torch.load(path)
     assert state["dispersion"] == 1.0 / 3.0 and state["observation_noise"] is None
     if not torch.cuda.is_available():
-        return  # (load_pls puts the particles on the device: tests/test_gpu_count_cost_train.py loads)
+        return  # (load_pls puts the particles on the device: tests/test_gpu_family_cost_train.py loads)
     other = Stub(_cost(r=9.0))
     _, got, lr, ep = load_pls(other, path)
     assert other.cost.dispersion == 1.0 / 3.0 and torch.equal(got.cpu(), u) and (lr, ep) == (1e-3, 4)

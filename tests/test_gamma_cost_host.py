@@ -13,11 +13,11 @@ import numpy as np
 import pytest
 import torch
 
-import gamma_cost_fixtures  # noqa: F401  (registers the pair with step_fixtures.truth_module)
+from cost_families import truth_module
 import gamma_cost_truth as CT
 import projected_langevin_sampling_amd as pkg
 from projected_langevin_sampling_amd import costs, link_functions, metrics
-from step_fixtures import SelectorProblem, truth_module
+from step_fixtures import SelectorProblem
 
 L = pkg._lib
 INF = math.inf
@@ -256,7 +256,7 @@ def test_checkpoint_round_trips_the_concentration(tmp_path):
     save_pls(Plain(), torch.zeros(2, 2), str(tmp_path / "p.pt"))
     assert "concentration" not in torch.load(str(tmp_path / "p.pt"))
     if not torch.cuda.is_available():
-        return  # (load_pls puts the particles on the device: tests/test_gpu_gamma_cost_train.py loads)
+        return  # (load_pls puts the particles on the device: tests/test_gpu_family_cost_train.py loads)
     other = Stub(_cost(9.0))
     _, got, lr, ep = load_pls(other, path)
     assert other.cost.concentration == 1.0 / 3.0 and torch.equal(got.cpu(), u) and (lr, ep) == (1e-3, 4)

@@ -1,8 +1,7 @@
-"""GPU: train_pls with BetaCost under the sigmoid link, on both bases: the loop of tests/train_loop_fixtures.py -- 20
-iterations against oracle.pls_oracle.train_pls driven by the host restatement of tests/beta_cost_truth.py, one launch per
-iteration, and a checkpoint saved half way, whose precision travels with the particles, resumed bit for bit.  And one run
-on the in-kernel Philox stream from particles that put f beyond +-700, against the restatement fed the same normals
-(oracle/philox_ref.py), with what the bounded drift implies for the distance from the data-free recursion."""
+"""GPU: train_pls with BetaCost under the sigmoid link, next to the loop every family runs
+(tests/test_gpu_family_cost_train.py), on the problem of tests/train_loop_fixtures.py: one run on the in-kernel Philox stream
+from particles that put f beyond +-700, against the restatement fed the same normals (oracle/philox_ref.py), with what the
+bounded drift implies for the distance from the data-free recursion."""
 import math
 
 import numpy as np
@@ -15,30 +14,11 @@ from oracle import pls_oracle as O
 from test_gpu_parity import cu, relerr, step_tolerance
 from test_gpu_parity import P, _f64_default  # noqa: F401  (fixtures)
 from test_gpu_small_step import route  # noqa: F401  (fixture)
-from train_loop_fixtures import SHAPES, problem, training_loop
+from train_loop_fixtures import problem
 
 pytestmark = pytest.mark.gpu
 
-PHI = 8.0
-
-
-def _y(pr, n):
-    """proportions scattered around sigmoid(1.5 f*) with precision phi"""
-    mu = torch.sigmoid(1.5 * pr["fstar"])
-    torch.manual_seed(11 + n)
-    return torch.distributions.Beta(PHI * mu, PHI * (1 - mu)).sample().clamp(1e-6, 1 - 1e-6)
-
-
-def _costs(P, y, precision=PHI):
-    gc = P.costs.BetaCost(y, P.links.SigmoidLinkFunction(), precision)
-    return BT.BetaHostCost(gc.y_device().cpu(), BT.SigmoidLink(), precision), gc  # (the very logits the library gets)
-
-
-@pytest.mark.parametrize("base", ["onb", "ipb"])
-@pytest.mark.parametrize("n,m,j", SHAPES)
-def test_training_loop_against_the_host_restatement(P, route, tmp_path, n, m, j, base):  # noqa: F811
-    gc = training_loop(P, route, tmp_path, n, m, j, base, _y, _costs, "precision", 99.0)
-    assert gc.precision == PHI
+PHI = BT.TRAIN_PRECISION
 
 
 def test_philox_run_from_the_far_tails_keeps_a_bounded_drift(P, route):  # noqa: F811
@@ -51,7 +31,7 @@ def test_philox_run_from_the_far_tails_keeps_a_bounded_drift(P, route):  # noqa:
     d_(t+1) = (1 - eta / lambda) d_t - eta A G_t with 0 < eta / lambda <= 1/4, so per particle
     |d_T|_2 <= T eta |A|_2 sqrt(N) g_max -- whatever the start."""
     n, m, j, steps = 100, 10, 64, 10
-    ob, gb, oc, gc, u0, eta, _ = problem(P, n, m, j, "onb", _y, _costs)
+    ob, gb, oc, gc, u0, eta, _ = problem(P, n, m, j, "onb", BT.train_y, BT.train_costs)
     a = ob.scaled_eigenvectors.T @ ob.base_gram_induce_train  # (M_k, N): F = A^T U
     mk = a.shape[0]
     u0 = u0 * (2000.0 / float((a.T @ u0).abs().max()))

@@ -13,9 +13,9 @@ import pytest
 import torch
 
 import cost_truth as T
+from cost_families import truth_module
 from step_fixtures import (EXACT_ETA, SELECTOR_PLACEMENTS, WINO_EDGES, WINO_THREE_CHUNKS, SelectorIpbProblem, SelectorProblem, option,
-                           probe_winograd, run_selector_forms, spread_columns, step_wg, truth_module, winograd_option,
-                           wino_one_chunk_bytes)
+                           probe_winograd, run_selector_forms, spread_columns, step_wg, winograd_option, wino_one_chunk_bytes)
 from test_gpu_ksplit import ksplit
 from test_gpu_parity import P, _f64_default  # noqa: F401  (fixtures)
 from test_gpu_rows import row_blocks

@@ -1,32 +1,16 @@
-"""GPU: the element-wise entries for the count-model pairs -- pls_cost_derivative (both derivative modes, which must be the
-same bits), pls_cost_value and pls_link_transform -- against the per-element mpmath truth of tests/count_cost_truth.py on
-its whole grid, dense and strided: bulk, the root where the derivative cancels, both tails, the far columns where e^f leaves
-the fp64 range while the negative binomial stays finite, +-0 and subnormals.
-
-The bound is tests/test_gpu_cost_elements.py's, unchanged: per (pair, parameter set, kind, regime) the larger of 4x the host
-restatement's recorded error (tests/golden/count_cost_reference_errors.json) and 4 units; IEEE specials must match exactly.
-PLS_COST_TRUTH_DUMP=<file> appends the measured maxima as JSON lines (the rows of DESIGN.md section 3 are made from them)."""
+"""GPU: what the count-model pairs test of their own next to tests/test_gpu_family_cost_elements.py, which holds the element-wise
+entries to the per-element mpmath truth of tests/count_cost_truth.py on its whole grid (bulk, the root where the derivative
+cancels, both tails, the far columns where e^f leaves the fp64 range while the negative binomial stays finite, +-0 and
+subnormals): predict_samples through the link entry pls_link_transform, and the negative binomial under the square link."""
 import math
 
 import pytest
 import torch
 
 import count_cost_truth as CT
-import test_gpu_cost_elements as E
 from test_gpu_parity import P, _f64_default  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.mark.parametrize("pair,pset", CT.cells())
-def test_elements_against_truth(P, pair, pset):
-    got = E.elements_against_truth(P, CT, pair, pset)
-    E.modes_agree(got)
-
-
-@pytest.mark.parametrize("pair,pset", CT.cells())
-def test_value_column_sums(P, pair, pset):
-    E.value_column_sums(P, CT, pair, pset)
 
 
 def test_predict_samples_with_a_column_offset(P):

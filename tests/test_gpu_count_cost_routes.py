@@ -1,6 +1,6 @@
 """GPU: the negative-binomial/exp epilogue per element on every route of the step, as tests/test_gpu_cost_routes.py holds the
 other pairs: a probe row of a selector problem is -eta 2^p G[n_k, :] without one rounding after cost_deriv, so it must equal
-(torch.equal) the element-wise entry's G on the host-built F -- which tests/test_gpu_count_cost_elements.py holds to the
+(torch.equal) the element-wise entry's G on the host-built F -- which tests/test_gpu_family_cost_elements.py holds to the
 mpmath truth -- whatever the route, its tiling, its compile-time specialisation, the output form or the energy request.  The
 carrier row is held to its summation bound against fsum, the energies to fsum of the element-wise values and, on the small
 shapes, of the mpmath values.  Gaussian/exp, the exponential link through the run-time-switch instantiation, runs the plain

@@ -1,11 +1,8 @@
-"""GPU: the element-wise entries for the Gamma cost -- pls_cost_derivative (both derivative modes, which must be the same
-bits) and pls_cost_value -- against the per-element mpmath truth of tests/gamma_cost_truth.py on its whole grid, dense and
-strided: bulk, the root down to a subnormal difference, the rounded subtraction at |t| in the hundreds, the overflow edge, the
-underflow side and a non-finite f.  And the edges include/plship.h tables, also for the non-finite z the grid cannot hold.
-
-The bound is tests/test_gpu_cost_elements.py's, unchanged: per (parameter set, kind, regime) the larger of 4x the host
-restatement's recorded error (tests/golden/gamma_cost_reference_errors.json) and 4 units; IEEE specials must match exactly.
-PLS_COST_TRUTH_DUMP=<file> appends the measured maxima as JSON lines (the rows of DESIGN.md section 3 are made from them)."""
+"""GPU: what the Gamma cost tests of its own next to tests/test_gpu_family_cost_elements.py, which holds the element-wise
+entries to the per-element mpmath truth of tests/gamma_cost_truth.py on its whole grid (bulk, the root down to a subnormal
+difference, the rounded subtraction at |t| in the hundreds, the overflow edge, the underflow side and a non-finite f): the
+edges include/plship.h tables, also for the non-finite z the grid cannot hold, and the derivative's relative accuracy at its
+root."""
 import math
 
 import mpmath as mp
@@ -14,26 +11,12 @@ import pytest
 import torch
 
 import gamma_cost_truth as CT
-import test_gpu_cost_elements as E
 from test_gpu_parity import P, _f64_default  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
 
 PAIR = "gamma/exp"
 INF = math.inf
-
-
-@pytest.mark.parametrize("pair,pset", CT.cells())
-def test_elements_against_truth(P, pair, pset):
-    got = E.elements_against_truth(P, CT, pair, pset)
-    E.modes_agree(got)
-    with np.errstate(invalid="ignore"):
-        assert all(not (got["deriv_reference", strided] > CT.PARAMS[pset]).any() for strided in (False, True)), "the derivative exceeds k"
-
-
-@pytest.mark.parametrize("pair,pset", CT.cells())
-def test_value_column_sums(P, pair, pset):
-    E.value_column_sums(P, CT, pair, pset)
 
 
 def _raw(P, pset, z):

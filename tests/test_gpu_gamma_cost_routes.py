@@ -1,13 +1,12 @@
 """GPU: the gamma/exp epilogue per element on every route of the step, as tests/test_gpu_ordinal_cost_routes.py holds the
 ordinal cost, case for case and shape for shape: a probe row of a selector problem is -eta 2^p G[n_k, :] without one rounding
 after cost_deriv, so it must equal (torch.equal) the element-wise entry's G on the host-built F -- which
-tests/test_gpu_gamma_cost_elements.py holds to the mpmath truth -- whatever the route, its tiling, its compile-time
+tests/test_gpu_family_cost_elements.py holds to the mpmath truth -- whatever the route, its tiling, its compile-time
 specialisation, the output form or the energy request.  The carrier row is held to its summation bound against fsum, the
 energies to fsum of the element-wise values and, on the small shapes, of the mpmath values.  Shapes: the smallest at which each
 route can still go wrong.  (tests/test_gamma_cost_host.py holds the selector problems themselves to their regimes.)"""
 import pytest
 
-import gamma_cost_fixtures  # noqa: F401  (registers the pair with the truth-module lookup of both fixture modules)
 import test_gpu_cost_routes as R
 from step_fixtures import option, winograd_option
 from test_gpu_ksplit import ksplit

@@ -1,12 +1,8 @@
-"""GPU: the element-wise entries for the ordinal cost -- pls_cost_derivative (both derivative modes, which must be the same
-bits) and pls_cost_value -- against the per-element mpmath truth of tests/ordinal_cost_truth.py on its whole grid, dense and
-strided: bulk, both sides of every cutpoint, the root of an interior label where the derivative cancels, both tails, the far
-columns where the value is linear or underflows gradually, +-0 and subnormals.  And what the header states for a y that is
-not a category index (NaN) and for a label past the last category (+inf and -1).
-
-The bound is tests/test_gpu_cost_elements.py's, unchanged: per (parameter set, kind, regime) the larger of 4x the host
-restatement's recorded error (tests/golden/ordinal_cost_reference_errors.json) and 4 units; IEEE specials must match exactly.
-PLS_COST_TRUTH_DUMP=<file> appends the measured maxima as JSON lines (the rows of DESIGN.md section 3 are made from them)."""
+"""GPU: what the ordinal cost tests of its own next to tests/test_gpu_family_cost_elements.py, which holds the element-wise
+entries to the per-element mpmath truth of tests/ordinal_cost_truth.py on its whole grid (bulk, both sides of every cutpoint,
+the root of an interior label where the derivative cancels, both tails, the far columns where the value is linear or
+underflows gradually, +-0 and subnormals): what the header states for a y that is not a category index (NaN) and for a label
+past the last category (+inf and -1), and the exact zeros and ends of the edge labels."""
 import math
 
 import numpy as np
@@ -14,23 +10,9 @@ import pytest
 import torch
 
 import ordinal_cost_truth as CT
-import test_gpu_cost_elements as E
 from test_gpu_parity import P, _f64_default  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.mark.parametrize("pair,pset", CT.cells())
-def test_elements_against_truth(P, pair, pset):
-    got = E.elements_against_truth(P, CT, pair, pset)
-    E.modes_agree(got)
-    assert all((np.abs(got["deriv_reference", strided]) <= 1).all() for strided in (False, True)), "the derivative leaves [-1, 1]"
-
-
-@pytest.mark.parametrize("pair,pset", CT.cells())
-def test_value_column_sums(P, pair, pset):
-    assert np.isfinite(CT.truth(pair, pset, "value")["hi"]).all()
-    E.value_column_sums(P, CT, pair, pset)
 
 
 def _raw(P, pset, labels):

@@ -211,7 +211,7 @@ def test_checkpoint_round_trips_the_cutpoints(tmp_path):
     save_pls(Plain(), torch.zeros(2, 2), str(tmp_path / "p.pt"))
     assert "cutpoints" not in torch.load(str(tmp_path / "p.pt"))
     if not torch.cuda.is_available():
-        return  # (load_pls puts the particles on the device: tests/test_gpu_ordinal_cost_train.py loads)
+        return  # (load_pls puts the particles on the device: tests/test_gpu_family_cost_train.py loads)
     other = Stub(_cost((0.0, 9.0)))
     _, got, lr, ep = load_pls(other, path)
     assert other.cost.cutpoints == (-1.0 / 3.0, 0.5, 2.0) and torch.equal(got.cpu(), u) and (lr, ep) == (1e-3, 4)

@@ -1,9 +1,9 @@
-"""GPU: what the train_pls tests of the newer cost families share (tests/test_gpu_{count,beta,ordinal}_cost_train.py): the
+"""GPU: what the train_pls tests of the cost families share (tests/test_gpu_family_cost_train.py, tests/test_gpu_beta_cost_train.py): the
 problem on both bases, and one body -- 20 iterations on the reference's host noise stream against
 oracle.pls_oracle.train_pls driven by the family's host restatement (the helper and tolerance rule of the small-step parity
 tests: test_gpu_parity.step_tolerance, TOL unless the problem itself is ill-conditioned), one launch per iteration, and a
-checkpoint saved half way and resumed bit for bit.  A family passes in how it draws y, how it builds its host cost and its
-library cost from y, and which attribute of the cost the checkpoint carries."""
+checkpoint saved half way and resumed bit for bit.  A family's truth module states how it draws y, how it builds its host cost and
+its library cost from y, and which attribute of the cost the checkpoint carries (train_y, train_costs, CHECKPOINT)."""
 import numpy as np
 import torch
 
