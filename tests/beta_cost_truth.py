@@ -368,10 +368,13 @@ def reference_errors():
         return json.load(fh)
 
 
-# ---- what the family batteries take (tests/test_gpu_family_cost_{train,elements}.py) ----------------------------------------------
+# ---- what the family batteries take (tests/test_gpu_family_cost_{train,elements}.py) and the route tests ---------------------------
 CHECKPOINT = ("precision", 99.0)  # the attribute a checkpoint carries, and the value the model it is loaded into was built with
 VALUE_TRUTH_FINITE = True  # the column-sum test asserts it before it sums
 check_elements = None  # nothing beyond both derivative modes being the same bits
+ROUTE_PAIR = "beta/sigmoid"  # its own compile-time instantiation: every route, both derivative modes
+ROUTE_RUNTIME_PAIR = "beta/probit"  # the run-time-switch instantiation: the plain route and the small-rank routes
+ROUTE_SMALL_RANK_SETS = "a"  # the parameter sets the small-rank shapes cycle through
 TRAIN_PRECISION = 8.0
 
 

@@ -1,9 +1,10 @@
 """The cost families of the test suite, listed once: every truth module, in the order the families were added.  A truth module
 describes its pairs (PAIRS, PARAMS, grid, truth, host_cost, gpu_cost, ...) and, next to them, what the shared batteries need of
-the family as data (train_y, train_costs, CHECKPOINT, check_trained_cost, check_elements, VALUE_TRUTH_FINITE).
-tests/step_fixtures.py, tests/test_gpu_cost_routes.py and the tests/test_gpu_family_cost_{train,elements}.py batteries reach a
-family through this module alone: a new family appends its truth module to TRUTH_MODULES.  (The route tests are still one file
-per family, tests/test_gpu_<family>_cost_routes.py: they find their truth module through truth_module like everything else.)
+the family as data (train_y, train_costs, CHECKPOINT, check_trained_cost, check_elements, VALUE_TRUTH_FINITE, and for the route
+battery ROUTE_PAIR, ROUTE_RUNTIME_PAIR and ROUTE_SMALL_RANK_SETS).  tests/step_fixtures.py, tests/test_gpu_cost_routes.py and
+the tests/test_gpu_family_cost_{train,elements,routes}.py batteries reach a family through this module alone: a new family
+appends its truth module to TRUTH_MODULES.  (tests/test_gpu_{beta,gamma}_cost_routes.py hold the route tests of those two
+families and take the three ROUTE_ names from the truth module as well; the route battery runs every other family.)
 
 Importing this module imports every truth module (the pair table below is built and checked once, here), and
 tests/step_fixtures.py imports this module: a truth module that needs step_fixtures imports it inside the function that uses it."""
@@ -23,6 +24,9 @@ for _module in TRUTH_MODULES:
         _owner[_pair] = _module
 for _module in FAMILIES:  # family_cells() builds a selector problem for the sets "a" and "b" of every family
     assert {"a", "b"} <= set(_module.PARAMS), f"{_module.__name__} must state the parameter sets a and b"
+    assert _module.ROUTE_PAIR in _module.PAIRS, f"{_module.__name__} does not describe its route pair {_module.ROUTE_PAIR}"
+    assert _module.ROUTE_RUNTIME_PAIR is None or _module.ROUTE_RUNTIME_PAIR in _module.PAIRS, (
+        f"{_module.__name__} does not describe its run-time route pair {_module.ROUTE_RUNTIME_PAIR}")
 
 
 def truth_module(pair):

@@ -39,6 +39,7 @@ from oracle import pls_oracle as O
 mp.mp.dps = 50
 PAIRS = ["negative_binomial/exp", "gaussian/exp"]
 KINDS = T.KINDS
+# the dispersion r, the noise variance: set b is r = 50, close to the Poisson limit
 PARAMS = {"a": {"negative_binomial": (0.7,), "gaussian": (0.3,)}, "b": {"negative_binomial": (50.0,), "gaussian": (2.5,)}}
 U = T.U
 HUGE = 1e6  # |x| beyond which e^x is stated (inf / 0), not computed
@@ -251,10 +252,13 @@ def reference_errors():
         return json.load(fh)
 
 
-# ---- what the family batteries take (tests/test_gpu_family_cost_{train,elements}.py) ----------------------------------------------
+# ---- what the family batteries take (tests/test_gpu_family_cost_{train,elements,routes}.py) ---------------------------------------
 CHECKPOINT = ("dispersion", 99.0)  # the attribute a checkpoint carries, and the value the model it is loaded into was built with
 VALUE_TRUTH_FINITE = False  # (the column-sum test asserts nothing about the truth's values first)
 check_elements = None  # nothing beyond both derivative modes being the same bits
+ROUTE_PAIR = "negative_binomial/exp"  # its own compile-time instantiation: every route, both derivative modes
+ROUTE_RUNTIME_PAIR = "gaussian/exp"  # the run-time-switch instantiation: the plain route and the small-rank routes
+ROUTE_SMALL_RANK_SETS = "a"  # the parameter sets the small-rank shapes cycle through
 TRAIN_DISPERSION = 3.0
 
 

@@ -219,9 +219,12 @@ def reference_errors():
         return json.load(fh)
 
 
-# ---- what the family batteries take (tests/test_gpu_family_cost_{train,elements}.py) ----------------------------------------------
+# ---- what the family batteries take (tests/test_gpu_family_cost_{train,elements}.py) and the route tests ---------------------------
 CHECKPOINT = ("concentration", 0.75)  # the attribute a checkpoint carries, and the value the model it is loaded into was built with
 VALUE_TRUTH_FINITE = False  # (above the exponential's range the value is +inf)
+ROUTE_PAIR = "gamma/exp"  # its own compile-time instantiation: every route, both derivative modes
+ROUTE_RUNTIME_PAIR = None  # no pair of this family goes through the run-time-switch instantiation
+ROUTE_SMALL_RANK_SETS = "ab"  # the parameter sets the small-rank shapes cycle through: the logarithms differ from lane to lane here
 TRAIN_CONCENTRATION = 4.0
 
 

@@ -40,6 +40,7 @@ mp.mp.dps = 50
 PAIRS = ["ordinal/identity"]
 KINDS = ["value", "deriv_reference", "deriv_autograd"]
 INF = math.inf
+# the cutpoints: set b is three categories with the narrow middle one (two of the four cutpoint slots are +inf)
 PARAMS = {"a": (-1.5, -0.25, 0.5, 2.0), "b": (-0.001, 0.002, INF, INF)}
 U = T.U
 HUGE = 1e6  # |x| beyond which e^x is stated (0), not computed
@@ -263,9 +264,12 @@ def reference_errors():
         return json.load(fh)
 
 
-# ---- what the family batteries take (tests/test_gpu_family_cost_{train,elements}.py) ----------------------------------------------
+# ---- what the family batteries take (tests/test_gpu_family_cost_{train,elements,routes}.py) ---------------------------------------
 CHECKPOINT = ("cutpoints", [-3.0, 0.125, 7.0])  # the attribute a checkpoint carries, and the value the model it is loaded into was built with
 VALUE_TRUTH_FINITE = True  # the column-sum test asserts it before it sums
+ROUTE_PAIR = "ordinal/identity"  # its own compile-time instantiation: every route, both derivative modes
+ROUTE_RUNTIME_PAIR = None  # no pair of this family goes through the run-time-switch instantiation
+ROUTE_SMALL_RANK_SETS = "ab"  # the parameter sets the small-rank shapes cycle through: the labels differ from lane to lane here
 TRAIN_THRESHOLDS = [-1.5, -0.25, 1.0]  # four grades cut from the noisy latent
 
 

@@ -1,7 +1,8 @@
 """CPU: the Beta cost without a GPU -- ids, descriptors, argument validation in the C ABI, the logit conversion, nativeness,
 the predictive distribution, the checkpoint key, the metrics branches; and the truth of tests/beta_cost_truth.py: its grid,
-the header's formula in (a, b) against the dedicated pair's form in mpmath, the derivative as the value's slope, and the
-recorded errors of the host restatement (tests/golden/beta_cost_reference_errors.json) against a fresh measurement."""
+the header's formula in (a, b) against the dedicated pair's form in mpmath, the derivative as the value's slope, the
+recorded errors of the host restatement (tests/golden/beta_cost_reference_errors.json) against a fresh measurement, and the
+regimes the selector problems of the route tests run through."""
 import math
 
 import mpmath as mp
@@ -12,6 +13,7 @@ import torch
 import beta_cost_truth as BT
 import projected_langevin_sampling_amd as pkg
 from projected_langevin_sampling_amd import costs, link_functions, metrics
+from step_fixtures import SelectorProblem
 
 L = pkg._lib
 Y = torch.tensor(BT.Y_ROWS, dtype=torch.float64)
@@ -313,3 +315,13 @@ def test_host_cost_drives_the_oracle_unchanged():
         assert len(energies) == 5 and energies[-1] < energies[0] and torch.isfinite(out).all()
     finally:
         torch.set_default_dtype(prev)
+
+
+def test_the_selector_problems_run_through_the_regimes():
+    for pair in BT.PAIRS:
+        ex = SelectorProblem(pair, 17, 333, 600, "head", seed=1)
+        f = ex.f()
+        assert (f.abs() < 3).any() and (f.abs() > 6.4).any() and (f > 0).any() and (f < 0).any()
+        assert set(ex.y.tolist()) == set(BT.Z_ROWS)
+    f = SelectorProblem("beta/sigmoid", 17, 333, 600, "head", seed=1).f()
+    assert (f.abs() > 1e9).any() and (f.abs() < 2.0 ** -20).any() and ((f.abs() > 700) & (f.abs() < 1e4)).any()

@@ -1,7 +1,8 @@
 """CPU: the negative-binomial cost and the exponential link without a GPU -- descriptors, argument validation in the C ABI,
 nativeness, the predictive distribution, the checkpoint key, the ABI version; and the truth of tests/count_cost_truth.py: its
-grid, the header's formula in mu against the softplus form in mpmath, the derivative as the value's slope, and the recorded
-errors of the host restatement (tests/golden/count_cost_reference_errors.json) against a fresh measurement."""
+grid, the header's formula in mu against the softplus form in mpmath, the derivative as the value's slope, the recorded
+errors of the host restatement (tests/golden/count_cost_reference_errors.json) against a fresh measurement, and the regimes the
+selector problems of the route tests run through."""
 import math
 
 import mpmath as mp
@@ -12,6 +13,7 @@ import torch
 import count_cost_truth as CT
 import projected_langevin_sampling_amd as pkg
 from projected_langevin_sampling_amd import costs, link_functions
+from step_fixtures import SelectorProblem
 
 L = pkg._lib
 
@@ -226,3 +228,12 @@ def test_host_cost_drives_the_oracle_unchanged():
         assert len(energies) == 5 and energies[-1] < energies[0] and torch.isfinite(out).all()
     finally:
         torch.set_default_dtype(prev)
+
+
+def test_the_selector_problems_run_through_the_regimes():
+    for pair in CT.PAIRS:
+        ex = SelectorProblem(pair, 17, 333, 600, "head", seed=1)
+        f = ex.f()
+        assert (f.abs() < 3).any() and (f.abs() > 20).any() and (f > 0).any() and (f < 0).any()
+        assert set(ex.y.tolist()) == {0.0, 1.0, 3.0, 25.0, 1e6, 0.5, 1.0 / 3.0}
+    assert (SelectorProblem("negative_binomial/exp", 17, 333, 600, "head", seed=1).f().abs() > 1e9).any()

@@ -1,4 +1,4 @@
-"""GPU: the Beta/sigmoid epilogue per element on every route of the step, as tests/test_gpu_count_cost_routes.py holds the
+"""GPU: the Beta/sigmoid epilogue per element on every route of the step, as tests/test_gpu_family_cost_routes.py holds the
 negative binomial: a probe row of a selector problem is -eta 2^p G[n_k, :] without one rounding after cost_deriv, so it must
 equal (torch.equal) the element-wise entry's G on the host-built F -- which tests/test_gpu_family_cost_elements.py holds to the
 mpmath truth -- whatever the route, its tiling, its compile-time specialisation, the output form or the energy request.  The
@@ -9,18 +9,18 @@ import pytest
 
 import beta_cost_truth as CT
 import test_gpu_cost_routes as R
-from step_fixtures import SelectorProblem, option, winograd_option
+from step_fixtures import option, winograd_option
 from test_gpu_ksplit import ksplit
 from test_gpu_parity import P, _f64_default  # noqa: F401  (fixtures)
 from test_gpu_rows import row_blocks
 
 pytestmark = pytest.mark.gpu
 
-BETA = "beta/sigmoid"
+BETA = CT.ROUTE_PAIR
 # (pair, force_autograd): both derivative modes of the dedicated pair (the same bits, through the same instantiation)
 VARIANTS = [(BETA, False), (BETA, True)]
-IDS = ["beta/sigmoid", "beta/sigmoid/autograd"]
-RUNTIME = "beta/probit"
+IDS = [BETA, BETA + "/autograd"]
+RUNTIME = CT.ROUTE_RUNTIME_PAIR
 
 
 # -------------------------------------------------------------------------------------------------------------------------
@@ -105,13 +105,3 @@ def test_ipb_whitened_entries(P, pair, fa):
     for n, m, j in ((100, 4, 64), (333, 16, 37)):
         for place in ("tail", "head"):
             R.run_ipb(P, pair, fa, m, n, j, place, f"ipb whitened generic {n}x{m}x{j}", whitened=True, truth=False)
-
-
-def test_the_selector_problems_run_through_the_regimes():
-    for pair in CT.PAIRS:
-        ex = SelectorProblem(pair, 17, 333, 600, "head", seed=1)
-        f = ex.f()
-        assert (f.abs() < 3).any() and (f.abs() > 6.4).any() and (f > 0).any() and (f < 0).any()
-        assert set(ex.y.tolist()) == set(CT.Z_ROWS)
-    f = SelectorProblem(BETA, 17, 333, 600, "head", seed=1).f()
-    assert (f.abs() > 1e9).any() and (f.abs() < 2.0 ** -20).any() and ((f.abs() > 700) & (f.abs() < 1e4)).any()

@@ -2,8 +2,9 @@
 with its own message, before any HIP call), the Python-side refusals, nativeness, cutpoints_from_labels, the predictive
 distribution against mpmath, the two metrics, the checkpoint key, the ABI version; and the truth of
 tests/ordinal_cost_truth.py: its grid, the library's cost against the full negative log-likelihood and against
-Bernoulli/sigmoid in mpmath, the derivative as the value's slope, and the recorded errors of the host restatement
-(tests/golden/ordinal_cost_reference_errors.json) against a fresh measurement."""
+Bernoulli/sigmoid in mpmath, the derivative as the value's slope, the recorded errors of the host restatement
+(tests/golden/ordinal_cost_reference_errors.json) against a fresh measurement, and the regimes the selector problems of the
+route tests run through."""
 import math
 
 import mpmath as mp
@@ -14,6 +15,7 @@ import torch
 import ordinal_cost_truth as CT
 import projected_langevin_sampling_amd as pkg
 from projected_langevin_sampling_amd import costs, link_functions, metrics
+from step_fixtures import SelectorProblem
 
 L = pkg._lib
 INF = math.inf
@@ -359,3 +361,16 @@ def test_host_cost_drives_the_oracle_unchanged():
         assert len(energies) == 5 and energies[-1] < energies[0] and torch.isfinite(out).all()
     finally:
         torch.set_default_dtype(prev)
+
+
+def test_the_selector_problems_run_through_the_regimes():
+    """the values drawn still hold |f| < 3 and |f| > 20, both signs, every label of the parameter set and a value >= 1e9;
+    none lies where an edge label's derivative would fall between 2^-1000 and 0"""
+    for pset in CT.PARAMS:
+        ex = SelectorProblem(PAIR, 17, 333, 600, "head", seed=1, pset=pset)
+        f = ex.f()
+        assert (f.abs() < 3).any() and (f.abs() > 20).any() and (f > 0).any() and (f < 0).any()
+        assert (f >= 1e9).any() and (f <= -1e9).any()
+        assert set(ex.y.tolist()) == set(float(k) for k in range(CT.categories(pset)))
+        a = f.abs()
+        assert ((a <= 8 * 75 * (1 + 2.0 ** -4)) | (a >= 1e9 / 8)).all()  # (|c_n| in [1/8, 8], the jiggle up to 1 + 2^-4)
